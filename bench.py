@@ -5,6 +5,10 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds every secondary reading (cold figure,
+rooflines, config-3 / config-5 / GeneralGNN extras, CPU baselines, the config-4 step of N > 1 lines); --dump-outputs DIR
+writes what the last timed step computed as DIR/<name>.npy.
+
 A "step" is one train_step (src/scripts/gcn.py:330-340: forward, CCE loss, every gradient, SGD
 apply) of the BN-free 2-layer GCNConv model of BASELINE.md section 3 over one synthetic
 DisjointLoader batch that is already resident in HBM.  torch is never imported: either launcher
@@ -263,6 +267,21 @@ def env_knobs():
     return {k: v for k, v in os.environ.items() if k.startswith("GCNX_") and k not in allowed}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float64 arrays as float64 and everything else as float32.  Every
+    array is written whole (the models' gradients and weights are a few MB at most); a set over the limit is an error."""
+    arrays = {k: np.asarray(v, np.float64 if np.asarray(v).dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes, more than {DUMP_LIMIT_BYTES}")
+    os.makedirs(directory, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(directory, k + ".npy"), a)
+
+
 def bench_generalgnn(ctx, args):
     """Secondary line: the reference's live model (GeneralGNN defaults, NetSurfP-width inputs F_in = 16,
     gcn_utills.py:293-300) on the E. coli-shaped batch; forward + CCE + all gradients + SGD."""
@@ -274,6 +293,8 @@ def bench_generalgnn(ctx, args):
     a = DeviceCSR.from_host_csr(ctx, hb.rowptr, hb.colidx, None, hb.graph_ptr)
     batch = DeviceBatch(ctx, ctx.to_device(hb.x), a, Segments(ctx, hb.graph_ptr), ctx.to_device(hb.y))
     model = GeneralGNN(ctx, 2, activation="softmax", prec=args.prec)
+    model.build(hb.f)
+    weights0 = model.get_weights()                        # (Keras order: BatchNorm's moving statistics included)
     for _ in range(max(args.warmup, 3)):
         model.train_step(batch, None, lr=0.0002, fetch=False)
     ctx.sync()
@@ -282,12 +303,20 @@ def bench_generalgnn(ctx, args):
         model.train_step(batch, None, lr=0.0002, fetch=False)
         ctx.sync()
         burn_steps += 1
+    model.set_weights(weights0)                           # as in main(): the timed steps start from the seeded weights
     t0 = time.perf_counter()
     for k in range(args.steps):
         model.train_step(batch, None, lr=0.0002, fetch=False)
         drain(ctx, k, 1)
     ctx.sync()
     el = time.perf_counter() - t0
+    if args.dump_outputs:
+        la = model.loss_acc.numpy()
+        outs = {"loss": np.float64(la[0]), "accuracy": np.float64(la[1]) / hb.n_graphs}
+        for i, (L, g) in enumerate(zip(model.layers, model.gradients())):
+            outs.update({f"weights_l{i}_{k}": L[k].numpy() for k in model._weight_keys(L, "keras")})
+            outs.update({f"grad_l{i}_{k}": v for k, v in g.items()})
+        dump_outputs(args.dump_outputs, outs)
     print(json.dumps({"metric": "graphs/sec (fwd+bwd) GeneralGNN (gcn.py:320 defaults)", "value": hb.n_graphs * args.steps / el,
                       "unit": "graphs/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
                       "burn_in": {"steps": burn_steps, "ms": args.burn_in_ms},
@@ -506,9 +535,19 @@ def main():
     ap.add_argument("--selftest-launcher", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--selftest-config4", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--no-config4", action="store_true", help="N > 1: skip the extra config-4 (strong-scaled 1M-node batch) reading")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the cold figure, the SpMM / fused-launch rooflines, the config-3 "
+                         "and config-5 readings, the GeneralGNN extra, the CPU baselines (N = 1) and the config-4 step (N > 1); "
+                         "without it a run times the K steps and nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, accuracy, gradients, updated weights) "
+                         "as DIR/<name>.npy; the timed steps start from the model's seeded initial weights, so the files depend "
+                         "on the arguments only")
     args = ap.parse_args()
     if args.prec is None:
         args.prec = CONFIG_PREC[args.workload]
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     # ---- N > 1 started plainly: become the launcher (nothing below has touched the GPU yet) ----------------
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -525,10 +564,12 @@ def main():
         # CPU-only check (tests/test_host.py) that an N > 1 line carries the config4_step key and what it is cut into: the ranks
         # meet through the launcher's rendezvous like the real run, rank 0 prints the line's skeleton with the shard plan
         if rank == 0:
-            plan, b = config4_plan(world)
-            print(json.dumps({"selftest": "config4", "n_gpus": world, "scaling_of_main_line": args.scaling or "weak",
-                              "config4_step": {"scaling": "strong", "n_gpus": world, "global_graphs": b, "shards": plan,
-                                               "ms_per_step": None, "graphs_per_s": None}}), flush=True)
+            rec = {"selftest": "config4", "n_gpus": world, "scaling_of_main_line": args.scaling or "weak"}
+            if args.full:                     # (as in the real line: the config-4 step is a --full reading)
+                plan, b = config4_plan(world)
+                rec["config4_step"] = {"scaling": "strong", "n_gpus": world, "global_graphs": b, "shards": plan,
+                                       "ms_per_step": None, "graphs_per_s": None}
+            print(json.dumps(rec), flush=True)
         sys.exit(launcher_selftest(rank, world))
     knobs = env_knobs()
     if knobs and not args.allow_knobs:
@@ -556,7 +597,8 @@ def main():
     batch = DeviceBatch(ctx, ctx.to_device(hb.x), a, Segments(ctx, hb.graph_ptr), ctx.to_device(hb.y))
     model = GCN2(ctx, 2, hidden=hidden, prec=args.prec, seed=0, comm=comm, use_graph=False if args.no_graph else (True if args.graph else "auto"))
     model.build(hb.f)
-    params0 = np.concatenate([w.ravel() for w in model.get_weights()])
+    model_weights0 = model.get_weights()
+    params0 = np.concatenate([w.ravel() for w in model_weights0])
     lr = 0.0002   # the reference's steady-state rate (gcn.py:323: values[-1]); constant so one graph serves
 
     for _ in range(max(args.warmup, 3)):        # >= 3: eager run, capture, first replay
@@ -567,15 +609,17 @@ def main():
     # a 2000-step run: 0.1017).  A training run is minutes long: the steady state is the quantity of interest, so the same
     # step is repeated until `--burn-in-ms` of wall time have passed, then the K timed steps follow as the contract says.
     # (The count is agreed between the ranks -- every step holds a collective: 5 probe steps, max over ranks.)
-    # The contract-cold figure next to the steady-state one: K steps timed right behind the W warm-up
-    # steps, before any burn-in -- what `value` would be with --burn-in-ms 0.
-    comm.barrier(); ctx.sync()
-    t_cold = time.perf_counter()
-    for k in range(args.steps):
-        model.train_step(batch, None, lr=lr, global_batch=global_graphs, fetch=False)
-        drain(ctx, k)
-    ctx.sync(); comm.barrier()
-    cold_ms = 1e3 * float(comm.allreduce_host([time.perf_counter() - t_cold], "max")[0]) / args.steps
+    # The contract-cold figure next to the steady-state one (--full): K steps timed right behind the W
+    # warm-up steps, before any burn-in -- what `value` would be with --burn-in-ms 0.
+    cold_ms = None
+    if args.full:
+        comm.barrier(); ctx.sync()
+        t_cold = time.perf_counter()
+        for k in range(args.steps):
+            model.train_step(batch, None, lr=lr, global_batch=global_graphs, fetch=False)
+            drain(ctx, k)
+        ctx.sync(); comm.barrier()
+        cold_ms = 1e3 * float(comm.allreduce_host([time.perf_counter() - t_cold], "max")[0]) / args.steps
     burn_steps = 0
     if args.burn_in_ms > 0:
         ctx.sync(); t_burn = time.perf_counter()
@@ -587,6 +631,9 @@ def main():
         for k in range(burn_steps - 5):
             model.train_step(batch, None, lr=lr, global_batch=global_graphs, fetch=False)
             drain(ctx, k)
+    # the burn-in's step count follows the clock: the timed steps start again from the seeded initial weights, so that what
+    # the last of them computes (--dump-outputs) depends on the arguments only
+    model.set_weights(model_weights0)
     comm.barrier()
     ctx.sync()
     evs = [ctx.event() for _ in range(args.steps + 1)]     # created outside the timed region
@@ -605,20 +652,27 @@ def main():
     elapsed = float(comm.allreduce_host([elapsed], "max")[0])
     med_ms = float(comm.allreduce_host([med_ms], "max")[0])
     loss, acc = model.fetch_metrics(global_graphs)
+    if args.dump_outputs and rank == 0:
+        grads = model.gradients()
+        outs = {"loss": np.float64(loss), "accuracy": np.float64(acc)}
+        for k, w in zip(model.PARAM_ORDER, model.get_weights()):
+            outs["grad_" + k], outs["weights_" + k] = grads[k], w
+        dump_outputs(args.dump_outputs, outs)
 
     # ---- roofline of the dominant hot-path kernel: the GCNConv SpMM (forward shape of layer 1/2)
-    iters = args.spmm_iters or 4 * args.steps
-    h = ctx.to_device(np.random.default_rng(1).standard_normal((hb.n, hidden), dtype=np.float32))
-    out = ctx.empty((hb.n, hidden))
-    spmm_ms = time_spmm(ctx, D, a, h, model.p["b1"], out, iters)
-    alg = synth.spmm_algorithmic_bytes(hb.n, hb.nnz, hidden, weighted=True)
-    achieved = alg / (spmm_ms * 1e-3) / 1e9
+    if args.full:
+        iters = args.spmm_iters or 4 * args.steps
+        h = ctx.to_device(np.random.default_rng(1).standard_normal((hb.n, hidden), dtype=np.float32))
+        out = ctx.empty((hb.n, hidden))
+        spmm_ms = time_spmm(ctx, D, a, h, model.p["b1"], out, iters)
+        alg = synth.spmm_algorithmic_bytes(hb.n, hb.nnz, hidden, weighted=True)
+        achieved = alg / (spmm_ms * 1e-3) / 1e9
 
     # ---- small-feature regime (config 2): the step does not launch gcnx_spmm_csr at all -- every GCNConv is ONE launch,
     # aggregation + dense product (csrc/fused.hip).  Its launch time and bytes, measured the same way, next to the
     # stand-alone aggregation above (which stays the `roofline` entry: it is the kernel the metric names).
     fused = None
-    if getattr(model, "_fused", None) and model._fused(batch):
+    if args.full and getattr(model, "_fused", None) and model._fused(batch):
         s_buf = ctx.empty((hb.n, hb.f)); y_buf = ctx.empty((hb.n, hidden))
         for _ in range(5):
             D.gcn_conv_fwd(ctx, a, batch.x, model.p["w1"], model.p["b1"], y_buf, act="relu", s=s_buf, prec=args.prec)
@@ -640,7 +694,7 @@ def main():
     # ---- the same kernel at BASELINE config 3 size (1M nodes / 10M entries / F=256), where the launch is long
     # enough for a bandwidth reading; reported next to the primary roofline, never as `value`
     big = step3 = big5 = None
-    if world == 1 and args.workload == "ecoli" and not args.no_config3:
+    if args.full and world == 1 and args.workload == "ecoli" and not args.no_config3:
         sizes3, pairs3 = synth.block_diag_plan()
         hb3 = synth.block_diag_shard(0, len(sizes3), sizes3, pairs3, 256, seed=2, with_x=True)
         v3 = synth.gcn_norm_host(hb3.rowptr, hb3.colidx)
@@ -714,14 +768,12 @@ def main():
                 "kernels": "row gather + hub-row segments (rows of more than 256 entries on their own workgroups) of one gcnx_spmm_csr call"}
 
     gnn_extra = None
-    if world == 1 and args.workload == "ecoli" and args.emulate_rank is None and not args.no_generalgnn:
+    if args.full and world == 1 and args.workload == "ecoli" and args.emulate_rank is None and not args.no_generalgnn:
         gnn_extra = generalgnn_extra(ctx, cpu_seconds=min(args.cpu_seconds, 6.0))
     cfg4 = None
-    if world > 1 and args.workload == "ecoli" and not args.no_config4 and not args.no_config3:
+    if args.full and world > 1 and args.workload == "ecoli" and not args.no_config4 and not args.no_config3:
         cfg4 = config4_extra(ctx, comm, rank, world, lr, not args.no_graph)
     if rank == 0:
-        small = hb.n < 128 * 1024
-        tr, src = pmc_traffic(args.workload)
         rec = {
             "metric": "graphs/sec (fwd+bwd) on E.coli-sized batches; GCNConv SpMM achieved HBM GB/s",
             "value": global_graphs * args.steps / elapsed, "unit": "graphs/s", "n_gpus": world,
@@ -742,18 +794,22 @@ def main():
             "burn_in": {"steps": burn_steps, "ms": args.burn_in_ms,
                         "what": "untimed repetitions of the same step after the W warm-up steps and before the timed region (clock / "
                                 "cache steady state; the timed region is exactly `steps` full steps)"},
-            "cold": {"ms_per_step": cold_ms, "graphs_per_s": global_graphs / (cold_ms * 1e-3),
-                     "what": "the same K steps timed directly behind the W warm-up steps, before the burn-in (the figure --burn-in-ms 0 gives)"},
             "device_ms_per_step": dev_ms / args.steps,
             "m1_median": {"ms_per_step": med_ms, "graphs_per_s": global_graphs / (med_ms * 1e-3),
                           "what": "median of per-step HIP-event times on the ctx stream, max over ranks (SURVEY 8(d) M1); "
                                   "`value` is the wall-clock figure the bench contract defines"},
-            "final_loss": loss, "final_acc": acc, "profiled": PROFILED,
-            "roofline": {"kernel": ("spmm_rows_kernel" if small else "spmm tile kernel(s) + row chunks") +
-                                   " (GCNConv aggregation, weighted, bias+relu fused)", "bound": "hbm",
-                         "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                         "traffic": tr, "traffic_source": src, "algorithmic_bytes": alg, "avg_launch_us": 1e3 * spmm_ms, "launches": iters},
+            "final_loss": loss, "final_acc": acc, "profiled": PROFILED, "full": args.full,
         }
+        if args.full:
+            tr, src = pmc_traffic(args.workload)
+            rec["cold"] = {"ms_per_step": cold_ms, "graphs_per_s": global_graphs / (cold_ms * 1e-3),
+                           "what": "the same K steps timed directly behind the W warm-up steps, before the burn-in (the figure "
+                                   "--burn-in-ms 0 gives)"}
+            rec["roofline"] = {"kernel": ("spmm_rows_kernel" if hb.n < 128 * 1024 else "spmm tile kernel(s) + row chunks") +
+                                         " (GCNConv aggregation, weighted, bias+relu fused)", "bound": "hbm",
+                               "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                               "traffic": tr, "traffic_source": src, "algorithmic_bytes": alg, "avg_launch_us": 1e3 * spmm_ms,
+                               "launches": iters}
         if args.emulate_rank is not None:
             # `value` stays this process's own rate (its shard's graphs per second); the proxy's reading is ms_per_step
             shard_graphs = hb.n_graphs
@@ -775,7 +831,7 @@ def main():
             rec["roofline_config3_bf16"] = big_bf16
             rec["config3_step"] = step3
             rec["roofline_config5"] = big5
-        if world == 1 and args.cpu_seconds > 0 and args.emulate_rank is None:
+        if args.full and world == 1 and args.cpu_seconds > 0 and args.emulate_rank is None:
             rec["cpu_baseline"] = cpu_baseline(hb, hidden, params0, args.cpu_seconds)
             if args.scipy_seconds > 0:
                 rec["cpu_baseline_scipy"] = cpu_baseline_scipy(hb, hidden, params0, args.scipy_seconds)

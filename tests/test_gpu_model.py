@@ -291,6 +291,41 @@ def test_ecoli_config2_full_size_vs_cpu_restatement(ctx):
     assert np.array_equal(got, again)
 
 
+def test_bench_dump_outputs_are_the_last_timed_step_from_the_seeded_weights(ctx, tmp_path):
+    """`bench.py --dump-outputs DIR` (a plain run: none of the --full readings in its line) writes the loss, accuracy,
+    gradients and updated weights of its last timed step.  The timed steps start from the model's seeded initial weights
+    whatever the warm-up and burn-in did, so the files equal K steps of the same model on the same batch run here."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from gcnx import synth
+    from gcnx.device import DeviceCSR, Segments
+    from gcnx.models import DeviceBatch
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    k = 4
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(k), "--warmup", "2",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-4000:]
+    rec = json.loads(r.stdout.strip().splitlines()[-1])
+    assert rec["steps"] == k and rec["ms_per_step"] > 0 and rec["unit"] == "graphs/s" and rec["dtype"] == "f32"
+    assert rec["full"] is False and not {"cold", "roofline", "generalgnn", "config3_step", "cpu_baseline"} & set(rec)
+    got = {p.name[:-4]: np.load(p) for p in tmp_path.glob("*.npy")}
+    assert set(got) == {"loss", "accuracy"} | {f"{p}_{q}" for p in ("grad", "weights") for q in ORDER}
+    hb = synth.ecoli_shard(0, 32, 128, seed=1)            # bench.py's config-2 batch at N = 1
+    hb.vals = synth.gcn_norm_host(hb.rowptr, hb.colidx)
+    a = DeviceCSR.from_host_csr(ctx, hb.rowptr, hb.colidx, hb.vals, hb.graph_ptr)
+    batch = DeviceBatch(ctx, ctx.to_device(hb.x), a, Segments(ctx, hb.graph_ptr), ctx.to_device(hb.y))
+    m = GCN2(ctx, 2, hidden=128, seed=0)
+    for _ in range(k):
+        loss, acc = m.train_step(batch, None, lr=0.0002)
+    assert abs(float(got["loss"]) - loss) < 1e-6 * max(1.0, loss) and float(got["loss"]) == pytest.approx(rec["final_loss"])
+    assert float(got["accuracy"]) == pytest.approx(acc)
+    for q, w in zip(ORDER, m.get_weights()):
+        assert got["weights_" + q].dtype == np.float32 and rel_err(got["weights_" + q], w) < 1e-6, q
+        assert rel_err(got["grad_" + q], m.gradients()[q]) < 1e-6, q
+
+
 def test_rccl_path_single_rank(ctx):
     """The RCCL leg of the C ABI (dlopen librccl, unique id, ncclCommInitRank, in-place fp32 all-reduce on the
     ctx stream) with one rank: sum and max of one rank are the identity.  Multi-rank runs need one GPU per rank

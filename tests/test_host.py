@@ -286,14 +286,20 @@ def test_bench_launcher_starts_ranks_itself_and_rendezvous_is_keyed_by_the_launc
 
 
 def test_bench_n_gpu_line_carries_the_config4_strong_scaling_key():
-    """`bench.py --gpus N` (N > 1) reports BASELINE config 4 -- the 1M-node batch strong-scaled over the
-    ranks -- as `config4_step` next to the weak-scaled headline.  CPU-side check through the real launcher: the key is emitted
-    and the cut it describes covers the batch in cost-balanced contiguous ranges (timings need GPUs: None here)."""
+    """`bench.py --gpus N --full` (N > 1) reports BASELINE config 4 -- the 1M-node batch strong-scaled over
+    the ranks -- as `config4_step` next to the weak-scaled headline; a plain line times the headline only.  CPU-side check
+    through the real launcher: the key is emitted and the cut it describes covers the batch in cost-balanced contiguous ranges
+    (timings need GPUs: None here)."""
     import json
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "GCNX_RUN_ID")}
+    plain = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--selftest-config4"],
+                           capture_output=True, text=True, env=env, timeout=300)
+    assert plain.returncode == 0, plain.stderr
+    recs = [json.loads(l) for l in plain.stdout.strip().splitlines()]
+    assert [x for x in recs if x.get("selftest") == "config4"] and not any("config4_step" in x for x in recs)
     for world in (2, 8):
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--selftest-config4"],
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--selftest-config4", "--full"],
                            capture_output=True, text=True, env=env, timeout=300)
         assert r.returncode == 0, r.stderr
         recs = [json.loads(l) for l in r.stdout.strip().splitlines()]
