@@ -11,6 +11,10 @@
 //             dz = gamma*inv*(dzb - s1/n - xhat*s2/n)     2 reads + 1 write
 // xhat and zb are recomputed from z and the saved (mu, inv): nothing but z itself is kept for
 // the backward pass.
+// PRELU_SHARED (torch.nn.PReLU(): one slope alpha[0] for every feature) takes the PRELU code path with the slope
+// broadcast; its dalpha is the sum of the per-column sums (prelu_shared_dalpha_kernel, fixed order).
+// gcnx_bn_act_pool(_bwd) at the end: BatchNorm1d + activation + global_max_pool of the reference's torch GCN
+// (gcn_utills.py:832-842) without the [N, F] activation in memory.
 #include <type_traits>
 
 #include "common.h"
@@ -248,6 +252,18 @@ __device__ __forceinline__ float prelu(float x, float a) { return x > 0.f ? x : 
 // there) a pre-activation within an ulp of zero could take one branch forward and the other backward.  It also makes the
 // branch reproducible on the host from (z, mu, inv, gamma, beta): sign(zb) = sign of the exact (z - mu) * sc + beta.
 __device__ __forceinline__ float bn_zb(float z, float mu, float sc, float be) { return __builtin_fmaf(z - mu, sc, be); }
+// One output element of gcnx_bn_act: bn_act_kernel and bn_act_pool_max_kernel both evaluate it through this helper, so
+// that the fused pool sees the very numbers gcnx_bn_act writes (bit-identical pooled rows and argmax).
+__device__ __forceinline__ float bn_act1(float z, float mu, float sc, float be, int act, float al) {
+  const float o = bn_zb(z, mu, sc, be);
+  if (act == GCNX_ACT_RELU) return fmaxf(o, 0.f);
+  if (act >= GCNX_ACT_PRELU) return prelu(o, al);
+  return o;
+}
+// The slope of column c: per-feature alpha[c] (PRELU), the one shared alpha[0] (PRELU_SHARED), unused otherwise.
+__device__ __forceinline__ float bn_alpha(const float* alpha, int act, int c) {
+  return act == GCNX_ACT_PRELU ? alpha[c] : (act == GCNX_ACT_PRELU_SHARED ? alpha[0] : 0.f);
+}
 
 __global__ __launch_bounds__(256) void bn_act_kernel(const float* __restrict__ z, int64_t ldz, int64_t n, int32_t f,
                                                      const float* __restrict__ mean, const float* __restrict__ inv,
@@ -263,13 +279,11 @@ __global__ __launch_bounds__(256) void bn_act_kernel(const float* __restrict__ z
   const float4 ga = ld4g(gamma + c, false, valid), be = ld4g(beta + c, false, valid);
   float4 al = f4(0.f);
   if (act == GCNX_ACT_PRELU) al = ld4g(alpha + c, false, valid);
+  else if (act == GCNX_ACT_PRELU_SHARED) al = f4(alpha[0]);
   const float4 sc = make_float4(ga.x * iv.x, ga.y * iv.y, ga.z * iv.z, ga.w * iv.w);
   auto apply = [&](float4 v) {
-    float4 o = make_float4(bn_zb(v.x, mu.x, sc.x, be.x), bn_zb(v.y, mu.y, sc.y, be.y), bn_zb(v.z, mu.z, sc.z, be.z),
-                           bn_zb(v.w, mu.w, sc.w, be.w));
-    if (act == GCNX_ACT_RELU) o = make_float4(fmaxf(o.x, 0.f), fmaxf(o.y, 0.f), fmaxf(o.z, 0.f), fmaxf(o.w, 0.f));
-    else if (act == GCNX_ACT_PRELU) o = make_float4(prelu(o.x, al.x), prelu(o.y, al.y), prelu(o.z, al.z), prelu(o.w, al.w));
-    return o;
+    return make_float4(bn_act1(v.x, mu.x, sc.x, be.x, act, al.x), bn_act1(v.y, mu.y, sc.y, be.y, act, al.y),
+                       bn_act1(v.z, mu.z, sc.z, be.z, act, al.z), bn_act1(v.w, mu.w, sc.w, be.w, act, al.w));
   };
   const int64_t step = (int64_t)gridDim.y * 4;
   int64_t r = (int64_t)blockIdx.y * 4 + (threadIdx.x >> 6);
@@ -291,7 +305,7 @@ __device__ __forceinline__ BnCols bn_cols(const float* mean, const float* inv, c
   BnCols q;
   q.mu = ld4g(mean + c, false, valid); q.iv = ld4g(inv + c, false, valid);
   q.ga = ld4g(gamma + c, false, valid); q.be = ld4g(beta + c, false, valid);
-  q.al = act == GCNX_ACT_PRELU ? ld4g(alpha + c, false, valid) : f4(0.f);
+  q.al = act == GCNX_ACT_PRELU ? ld4g(alpha + c, false, valid) : (act == GCNX_ACT_PRELU_SHARED ? f4(alpha[0]) : f4(0.f));
   return q;
 }
 
@@ -302,7 +316,7 @@ __device__ __forceinline__ void bn_bwd_terms(float dy, float z, float mu, float 
   const float zb = bn_zb(z, mu, ga * iv, be);          // the forward pass's number (bn_act_kernel), not ga * xhat + be
   dalpha = 0.f;
   if (act == GCNX_ACT_RELU) dzb = zb > 0.f ? dy : 0.f;
-  else if (act == GCNX_ACT_PRELU) { dzb = zb > 0.f ? dy : al * dy; dalpha = dy * fminf(zb, 0.f); }
+  else if (act >= GCNX_ACT_PRELU) { dzb = zb > 0.f ? dy : al * dy; dalpha = dy * fminf(zb, 0.f); }
   else dzb = dy;
 }
 
@@ -446,6 +460,163 @@ __global__ __launch_bounds__(256) void bn_act_bwd_small_kernel(const float* __re
 
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// dalpha[0] = sum over the f columns of sums[2f + c] (the shared slope's gradient): one workgroup, fixed order.
+__device__ __forceinline__ float block_sum256(float v, float* red) {
+  red[threadIdx.x] = v;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  const float r = red[0];
+  __syncthreads();
+  return r;
+}
+
+__global__ __launch_bounds__(256) void prelu_shared_dalpha_kernel(const float* __restrict__ cols, int32_t f, float* __restrict__ dalpha) {
+  __shared__ float red[256];
+  float a = 0.f;
+  for (int c = threadIdx.x; c < f; c += 256) a += cols[c];
+  const float t = block_sum256(a, red);
+  if (threadIdx.x == 0) dalpha[0] = t;
+}
+
+int shared_dalpha(gcnx_ctx* ctx, const float* sums3, int32_t f, float* dalpha) {
+  hipLaunchKernelGGL(prelu_shared_dalpha_kernel, dim3(1), dim3(256), 0, ctx->stream, sums3 + 2 * (int64_t)f, f, dalpha);
+  GCNX_LAUNCH_OK(ctx);
+  return GCNX_OK;
+}
+
+// The pool pair runs on 1024-thread workgroups: 64 columns x kPoolRG row (or graph) groups.  At the reference's sizes a
+// graph is a few hundred rows and there are few graphs, so the time is the chain of dependent loads each thread walks:
+// 16 groups with four loads in flight per step keep it short.
+constexpr int kPoolRG = 16;
+constexpr int kPoolThreads = 64 * kPoolRG;
+
+// gcnx_bn_act_pool, MAX: one workgroup per (graph, 64 columns).  Every element goes through bn_act1 -- the numbers
+// gcnx_bn_act writes -- and the reduction keeps the first maximal row, as gcnx_segment_pool does (strict > along a row
+// group, ties between groups to the smaller row; an empty graph pools to 0 with argmax = its start row).
+__global__ __launch_bounds__(kPoolThreads) void bn_act_pool_max_kernel(const int32_t* __restrict__ gp, const float* __restrict__ z,
+                                                              int64_t ldz, int32_t f, const float* __restrict__ mean,
+                                                              const float* __restrict__ inv, const float* __restrict__ gamma,
+                                                              const float* __restrict__ beta, int act, const float* __restrict__ alpha,
+                                                              float* __restrict__ pooled, int64_t ldp, int32_t* __restrict__ argmax) {
+  __shared__ float sv[kPoolRG][64];
+  __shared__ int si[kPoolRG][64];
+  const int g = blockIdx.x, cl = threadIdx.x & 63, rg = threadIdx.x >> 6;
+  const int c = blockIdx.y * 64 + cl;
+  const int lo = gp[g], hi = gp[g + 1];
+  float best = -INFINITY;
+  int arg = lo;
+  if (c < f) {
+    const float mu = mean[c], sc = gamma[c] * inv[c], be = beta[c], al = bn_alpha(alpha, act, c);
+#pragma unroll 4
+    for (int r = lo + rg; r < hi; r += kPoolRG) {
+      const float v = bn_act1(z[(int64_t)r * ldz + c], mu, sc, be, act, al);
+      if (v > best) { best = v; arg = r; }
+    }
+  }
+  sv[rg][cl] = best;
+  si[rg][cl] = arg;
+  __syncthreads();
+  if (rg == 0 && c < f) {
+    for (int q = 1; q < kPoolRG; ++q)
+      if (sv[q][cl] > best || (sv[q][cl] == best && si[q][cl] < arg)) { best = sv[q][cl]; arg = si[q][cl]; }
+    if (hi == lo) { best = 0.f; arg = lo; }
+    pooled[(int64_t)g * ldp + c] = best;
+    argmax[(int64_t)g * f + c] = arg;
+  }
+}
+
+// Backward, launch 1 of 2 (one workgroup): dY is nonzero only at the B x F argmax entries, so the three column sums of
+// gcnx_bn_act_bwd -- sum dzb, sum dzb * xhat, sum dy * min(zb, 0) -- are sums over the graphs alone (graph group q takes
+// the graphs q, q + 16, ...; the 16 partial sums are added in group order).  sums[3f] (scratch) feeds launch 2; dbeta /
+// dgamma / dalpha (may be NULL) receive the parameter gradients (dalpha[0] for the shared slope).
+__global__ __launch_bounds__(kPoolThreads) void bn_act_pool_bwd_stats_kernel(const int32_t* __restrict__ gp, int32_t b,
+                                                                    const float* __restrict__ dp, int64_t lddp,
+                                                                    const int32_t* __restrict__ argmax, const float* __restrict__ z,
+                                                                    int64_t ldz, int32_t f, const float* __restrict__ mean,
+                                                                    const float* __restrict__ inv, const float* __restrict__ gamma,
+                                                                    const float* __restrict__ beta, int act,
+                                                                    const float* __restrict__ alpha, float* __restrict__ sums,
+                                                                    float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                                                    float* __restrict__ dalpha) {
+  __shared__ float part[3][kPoolRG][64];
+  __shared__ float red[64];
+  const int cl = threadIdx.x & 63, gg = threadIdx.x >> 6;
+  float da_all = 0.f;                                  // (threads of group 0: their columns' dalpha sums)
+  for (int c0 = 0; c0 < f; c0 += 64) {
+    const int c = c0 + cl;
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+    if (c < f) {
+      const float mu = mean[c], iv = inv[c], ga = gamma[c], be = beta[c], al = bn_alpha(alpha, act, c);
+#pragma unroll 2
+      for (int g = gg; g < b; g += kPoolRG) {
+        if (gp[g + 1] <= gp[g]) continue;            // an empty graph routes no gradient
+        const int r = argmax[(int64_t)g * f + c];
+        float dzb, xh, da;
+        bn_bwd_terms(dp[(int64_t)g * lddp + c], z[(int64_t)r * ldz + c], mu, iv, ga, be, al, act, dzb, xh, da);
+        s0 += dzb;
+        s1 += dzb * xh;
+        s2 += da;
+      }
+    }
+    part[0][gg][cl] = s0;
+    part[1][gg][cl] = s1;
+    part[2][gg][cl] = s2;
+    __syncthreads();
+    if (gg == 0 && c < f) {
+      float t0 = part[0][0][cl], t1 = part[1][0][cl], t2 = part[2][0][cl];
+      for (int q = 1; q < kPoolRG; ++q) { t0 += part[0][q][cl]; t1 += part[1][q][cl]; t2 += part[2][q][cl]; }
+      sums[c] = t0;
+      sums[f + c] = t1;
+      sums[2 * f + c] = t2;
+      if (dbeta) dbeta[c] = t0;
+      if (dgamma) dgamma[c] = t1;
+      if (dalpha && act == GCNX_ACT_PRELU) dalpha[c] = t2;
+      da_all += t2;
+    }
+    __syncthreads();
+  }
+  if (act == GCNX_ACT_PRELU_SHARED) {                  // the 64 column-lane totals of group 0, tree order
+    if (gg == 0) red[cl] = da_all;
+    __syncthreads();
+    for (int s = 32; s > 0; s >>= 1) {
+      if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+      __syncthreads();
+    }
+    if (dalpha && threadIdx.x == 0) dalpha[0] = red[0];
+  }
+}
+
+// Launch 2: dz = gamma * inv * (dzb - s1 / n - xhat * s2 / n) over every row (bn_bwd_apply_kernel's arithmetic), dzb = 0 off
+// the argmax rows.  One workgroup per (graph, 64 columns).
+__global__ __launch_bounds__(kPoolThreads) void bn_act_pool_bwd_apply_kernel(const int32_t* __restrict__ gp, const float* __restrict__ dp,
+                                                                    int64_t lddp, const int32_t* __restrict__ argmax,
+                                                                    const float* __restrict__ z, int64_t ldz, int32_t f,
+                                                                    const float* __restrict__ mean, const float* __restrict__ inv,
+                                                                    const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                    int act, const float* __restrict__ alpha,
+                                                                    const float* __restrict__ sums, float count,
+                                                                    float* __restrict__ dz, int64_t lddz) {
+  const int g = blockIdx.x, cl = threadIdx.x & 63, rg = threadIdx.x >> 6;
+  const int c = blockIdx.y * 64 + cl;
+  if (c >= f) return;
+  const int lo = gp[g], hi = gp[g + 1];
+  if (hi <= lo) return;
+  const float mu = mean[c], iv = inv[c], ga = gamma[c], be = beta[c], al = bn_alpha(alpha, act, c);
+  const float ic = 1.0f / count;
+  const float s1 = sums[c] * ic, s2 = sums[f + c] * ic;
+  const int ar = argmax[(int64_t)g * f + c];
+  const float d = dp[(int64_t)g * lddp + c];
+#pragma unroll 4
+  for (int r = lo + rg; r < hi; r += kPoolRG) {
+    float dzb, xh, unused;
+    bn_bwd_terms(r == ar ? d : 0.f, z[(int64_t)r * ldz + c], mu, iv, ga, be, al, act, dzb, xh, unused);
+    dz[(int64_t)r * lddz + c] = ga * iv * (dzb - s1 - xh * s2);
+  }
+}
+
 int reduce_parts(gcnx_ctx* ctx, int nchunks, int ns, int32_t f, float* out, float* o0 = nullptr, float* o1 = nullptr,
                  float* o2 = nullptr) {
   hipLaunchKernelGGL(part_reduce_kernel, dim3(gcnx_cdiv((long long)ns * f, 64)), dim3(256), 0, ctx->stream,
@@ -527,10 +698,10 @@ int gcnx_bn_act(gcnx_ctx* ctx, const float* z, int64_t ldz, int64_t n, int32_t f
   GCNX_CHECK_CTX(ctx);
   GCNX_RANGE(ctx, "batch norm (apply)");
   GCNX_REQUIRE(ctx, n >= 0 && f >= 0, "gcnx_bn_act: negative size");
-  GCNX_REQUIRE(ctx, act >= GCNX_ACT_NONE && act <= GCNX_ACT_PRELU, "gcnx_bn_act: unknown activation %d", act);
+  GCNX_REQUIRE(ctx, act >= GCNX_ACT_NONE && act <= GCNX_ACT_PRELU_SHARED, "gcnx_bn_act: unknown activation %d", act);
   if (n == 0 || f == 0) return GCNX_OK;
   GCNX_REQUIRE(ctx, z && y && mean && inv && gamma && beta, "gcnx_bn_act: NULL pointer");
-  GCNX_REQUIRE(ctx, act != GCNX_ACT_PRELU || alpha, "gcnx_bn_act: PReLU needs alpha");
+  GCNX_REQUIRE(ctx, act < GCNX_ACT_PRELU || alpha, "gcnx_bn_act: PReLU needs alpha");
   GCNX_REQUIRE(ctx, ldz >= f && ldy >= f, "gcnx_bn_act: leading dimension too small");
   int gy = gcnx_cdiv(n, 4);
   if (gy > 8 * ctx->num_cus) gy = 8 * ctx->num_cus;
@@ -548,18 +719,18 @@ int gcnx_bn_act_bwd_stats(gcnx_ctx* ctx, const float* dy, int64_t lddy, const fl
                           const float* alpha, float* sums_scratch, float* dgamma, float* dbeta, float* dalpha) {
   GCNX_CHECK_CTX(ctx);
   GCNX_REQUIRE(ctx, n >= 0 && f >= 0, "gcnx_bn_act_bwd: negative size");
-  GCNX_REQUIRE(ctx, act >= GCNX_ACT_NONE && act <= GCNX_ACT_PRELU, "gcnx_bn_act_bwd: unknown activation %d", act);
+  GCNX_REQUIRE(ctx, act >= GCNX_ACT_NONE && act <= GCNX_ACT_PRELU_SHARED, "gcnx_bn_act_bwd: unknown activation %d", act);
   if (f == 0) return GCNX_OK;
   GCNX_REQUIRE(ctx, sums_scratch != nullptr, "gcnx_bn_act_bwd: sums_scratch (device float[3f]) is NULL");
   if (n == 0) {   // no rows: sums and gradients are zero
     GCNX_HIP(ctx, hipMemsetAsync(sums_scratch, 0, (size_t)3 * f * 4, ctx->stream));
     if (dbeta) GCNX_HIP(ctx, hipMemsetAsync(dbeta, 0, (size_t)f * 4, ctx->stream));
     if (dgamma) GCNX_HIP(ctx, hipMemsetAsync(dgamma, 0, (size_t)f * 4, ctx->stream));
-    if (dalpha) GCNX_HIP(ctx, hipMemsetAsync(dalpha, 0, (size_t)f * 4, ctx->stream));
+    if (dalpha) GCNX_HIP(ctx, hipMemsetAsync(dalpha, 0, (size_t)(act == GCNX_ACT_PRELU_SHARED ? 1 : f) * 4, ctx->stream));
     return GCNX_OK;
   }
   GCNX_REQUIRE(ctx, dy && z && mean && inv && gamma && beta, "gcnx_bn_act_bwd: NULL pointer");
-  GCNX_REQUIRE(ctx, act != GCNX_ACT_PRELU || alpha, "gcnx_bn_act_bwd: PReLU needs alpha");
+  GCNX_REQUIRE(ctx, act < GCNX_ACT_PRELU || alpha, "gcnx_bn_act_bwd: PReLU needs alpha");
   GCNX_REQUIRE(ctx, lddy >= f && ldz >= f, "gcnx_bn_act_bwd: leading dimension too small");
   const int nchunks = gcnx_cdiv(n, kRows);
   int rc = gcnx_ws_reserve(ctx, (size_t)nchunks * 3 * f * sizeof(float));
@@ -569,7 +740,10 @@ int gcnx_bn_act_bwd_stats(gcnx_ctx* ctx, const float* dy, int64_t lddy, const fl
                      f, mean, inv, gamma, beta, act, alpha, (float*)ctx->ws, vec);
   GCNX_LAUNCH_OK(ctx);
   // parameter gradients ride along: dbeta = sum dzb, dgamma = sum dzb*xhat, dalpha = sum dy*min(zb,0)
-  return reduce_parts(ctx, nchunks, 3, f, sums_scratch, dbeta, dgamma, dalpha);
+  const bool shared = act == GCNX_ACT_PRELU_SHARED;
+  rc = reduce_parts(ctx, nchunks, 3, f, sums_scratch, dbeta, dgamma, shared ? nullptr : dalpha);
+  if (rc || !shared || !dalpha) return rc;
+  return shared_dalpha(ctx, sums_scratch, f, dalpha);
 }
 
 int gcnx_bn_act_bwd_apply(gcnx_ctx* ctx, const float* dy, int64_t lddy, const float* z, int64_t ldz, int64_t n, int32_t f,
@@ -577,10 +751,10 @@ int gcnx_bn_act_bwd_apply(gcnx_ctx* ctx, const float* dy, int64_t lddy, const fl
                           const float* alpha, const float* sums, float count, int training, float* dz, int64_t lddz) {
   GCNX_CHECK_CTX(ctx);
   GCNX_REQUIRE(ctx, n >= 0 && f >= 0, "gcnx_bn_act_bwd: negative size");
-  GCNX_REQUIRE(ctx, act >= GCNX_ACT_NONE && act <= GCNX_ACT_PRELU, "gcnx_bn_act_bwd: unknown activation %d", act);
+  GCNX_REQUIRE(ctx, act >= GCNX_ACT_NONE && act <= GCNX_ACT_PRELU_SHARED, "gcnx_bn_act_bwd: unknown activation %d", act);
   if (f == 0 || n == 0) return GCNX_OK;
   GCNX_REQUIRE(ctx, dy && z && dz && mean && inv && gamma && beta && sums, "gcnx_bn_act_bwd: NULL pointer");
-  GCNX_REQUIRE(ctx, act != GCNX_ACT_PRELU || alpha, "gcnx_bn_act_bwd: PReLU needs alpha");
+  GCNX_REQUIRE(ctx, act < GCNX_ACT_PRELU || alpha, "gcnx_bn_act_bwd: PReLU needs alpha");
   GCNX_REQUIRE(ctx, lddy >= f && ldz >= f && lddz >= f, "gcnx_bn_act_bwd: leading dimension too small");
   GCNX_REQUIRE(ctx, count > 0.f, "gcnx_bn_act_bwd: count must be positive");
   const int vec = al16(dy) && al16(z) && al16(dz) && lddy % 4 == 0 && ldz % 4 == 0 && lddz % 4 == 0;
@@ -597,23 +771,67 @@ int gcnx_bn_act_bwd(gcnx_ctx* ctx, const float* dy, int64_t lddy, const float* z
                     const float* alpha, int training, float* dz, int64_t lddz, float* dgamma, float* dbeta,
                     float* dalpha, float* sums_scratch) {
   if (ctx && n > 0 && n <= kRows && f > 0 && dy && z && dz && mean && inv && gamma && beta && sums_scratch && lddy >= f && ldz >= f &&
-      lddz >= f && act >= GCNX_ACT_NONE && act <= GCNX_ACT_PRELU && (act != GCNX_ACT_PRELU || alpha)) {
+      lddz >= f && act >= GCNX_ACT_NONE && act <= GCNX_ACT_PRELU_SHARED && (act < GCNX_ACT_PRELU || alpha)) {
     // a batch of one chunk (the post-MLP's rows): statistics, their reduction and dz in one launch, the same bits
     GCNX_CHECK_CTX(ctx);
     GCNX_RANGE(ctx, "batch norm + activation backward (small batch)");
     int rc1 = gcnx_ws_reserve(ctx, (size_t)3 * f * sizeof(float));
     if (rc1) return rc1;
     const int vec = al16(dy) && al16(z) && al16(dz) && lddy % 4 == 0 && ldz % 4 == 0 && lddz % 4 == 0;
+    const bool shared = act == GCNX_ACT_PRELU_SHARED;
     hipLaunchKernelGGL(bn_act_bwd_small_kernel, dim3(gcnx_cdiv(f, 64)), dim3(256), 0, ctx->stream, dy, lddy, z, ldz, n, f, mean, inv, gamma,
-                       beta, act, alpha, (float*)ctx->ws, sums_scratch, dbeta, dgamma, dalpha, training, dz, lddz, vec);
+                       beta, act, alpha, (float*)ctx->ws, sums_scratch, dbeta, dgamma, shared ? nullptr : dalpha, training, dz, lddz, vec);
     GCNX_LAUNCH_OK(ctx);
-    return GCNX_OK;
+    return shared && dalpha ? shared_dalpha(ctx, sums_scratch, f, dalpha) : GCNX_OK;
   }
   int rc = gcnx_bn_act_bwd_stats(ctx, dy, lddy, z, ldz, n, f, mean, inv, gamma, beta, act, alpha, sums_scratch, dgamma,
                                  dbeta, dalpha);
   if (rc || n == 0 || f == 0) return rc;
   return gcnx_bn_act_bwd_apply(ctx, dy, lddy, z, ldz, n, f, mean, inv, gamma, beta, act, alpha, sums_scratch, (float)n,
                                training, dz, lddz);
+}
+
+int gcnx_bn_act_pool(gcnx_ctx* ctx, const int32_t* graph_ptr, int32_t b, const float* z, int64_t ldz, int32_t f,
+                     const float* mean, const float* inv, const float* gamma, const float* beta, int act, const float* alpha,
+                     int pool_mode, float* pooled, int64_t ldp, int32_t* argmax) {
+  GCNX_CHECK_CTX(ctx);
+  GCNX_RANGE(ctx, "batch norm + activation + pool");
+  GCNX_REQUIRE(ctx, b >= 0 && f >= 0, "gcnx_bn_act_pool: negative size");
+  GCNX_REQUIRE(ctx, act >= GCNX_ACT_NONE && act <= GCNX_ACT_PRELU_SHARED, "gcnx_bn_act_pool: unknown activation %d", act);
+  if (pool_mode != GCNX_POOL_MAX) return gcnx_fail(ctx, GCNX_ERR_UNSUPPORTED, "gcnx_bn_act_pool: only GCNX_POOL_MAX is served");
+  if (b == 0 || f == 0) return GCNX_OK;
+  GCNX_REQUIRE(ctx, graph_ptr && z && mean && inv && gamma && beta && pooled && argmax, "gcnx_bn_act_pool: NULL pointer");
+  GCNX_REQUIRE(ctx, act < GCNX_ACT_PRELU || alpha, "gcnx_bn_act_pool: PReLU needs alpha");
+  GCNX_REQUIRE(ctx, ldz >= f && ldp >= f, "gcnx_bn_act_pool: leading dimension too small");
+  hipLaunchKernelGGL(bn_act_pool_max_kernel, dim3(b, gcnx_cdiv(f, 64)), dim3(kPoolThreads), 0, ctx->stream, graph_ptr, z, ldz, f, mean, inv,
+                     gamma, beta, act, alpha, pooled, ldp, argmax);
+  GCNX_LAUNCH_OK(ctx);
+  return GCNX_OK;
+}
+
+int gcnx_bn_act_pool_bwd(gcnx_ctx* ctx, const int32_t* graph_ptr, int32_t b, const float* dpooled, int64_t lddp,
+                         const int32_t* argmax, const float* z, int64_t ldz, int64_t n, int32_t f, const float* mean,
+                         const float* inv, const float* gamma, const float* beta, int act, const float* alpha, int pool_mode,
+                         float* dz, int64_t lddz, float* dgamma, float* dbeta, float* dalpha) {
+  GCNX_CHECK_CTX(ctx);
+  GCNX_RANGE(ctx, "batch norm + activation + pool backward");
+  GCNX_REQUIRE(ctx, b >= 0 && n >= 0 && f >= 0, "gcnx_bn_act_pool_bwd: negative size");
+  GCNX_REQUIRE(ctx, act >= GCNX_ACT_NONE && act <= GCNX_ACT_PRELU_SHARED, "gcnx_bn_act_pool_bwd: unknown activation %d", act);
+  if (pool_mode != GCNX_POOL_MAX) return gcnx_fail(ctx, GCNX_ERR_UNSUPPORTED, "gcnx_bn_act_pool_bwd: only GCNX_POOL_MAX is served");
+  if (f == 0 || n == 0) return GCNX_OK;
+  GCNX_REQUIRE(ctx, b > 0 && graph_ptr && dpooled && argmax && z && mean && inv && gamma && beta && dz, "gcnx_bn_act_pool_bwd: NULL pointer");
+  GCNX_REQUIRE(ctx, act < GCNX_ACT_PRELU || alpha, "gcnx_bn_act_pool_bwd: PReLU needs alpha");
+  GCNX_REQUIRE(ctx, ldz >= f && lddz >= f && lddp >= f, "gcnx_bn_act_pool_bwd: leading dimension too small");
+  int rc = gcnx_ws_reserve(ctx, (size_t)3 * f * sizeof(float));
+  if (rc) return rc;
+  float* sums = (float*)ctx->ws;
+  hipLaunchKernelGGL(bn_act_pool_bwd_stats_kernel, dim3(1), dim3(kPoolThreads), 0, ctx->stream, graph_ptr, b, dpooled, lddp, argmax, z, ldz, f,
+                     mean, inv, gamma, beta, act, alpha, sums, dgamma, dbeta, dalpha);
+  GCNX_LAUNCH_OK(ctx);
+  hipLaunchKernelGGL(bn_act_pool_bwd_apply_kernel, dim3(b, gcnx_cdiv(f, 64)), dim3(kPoolThreads), 0, ctx->stream, graph_ptr, dpooled, lddp,
+                     argmax, z, ldz, f, mean, inv, gamma, beta, act, alpha, (const float*)sums, (float)n, dz, lddz);
+  GCNX_LAUNCH_OK(ctx);
+  return GCNX_OK;
 }
 
 }  // extern "C"

@@ -8,25 +8,25 @@ No PyTorch, no TensorFlow, no CPU fallback.
 from . import _lib
 from .io import best_epoch, load_weights_npz, save_to_npz
 from .loader import Dataset, DisjointLoader, Graph, ListDataset, NetworkxDataset, SparseTensor, format_graph, from_networkx
-from .train import PiecewiseConstantDecay, auc, fit, roc_curve
+from .train import PiecewiseConstantDecay, auc, binary_acc, fit, roc_curve
 
 __all__ = ["Dataset", "DisjointLoader", "Graph", "ListDataset", "NetworkxDataset", "from_networkx", "format_graph", "SparseTensor", "Context", "default_context", "GCNConv", "GeneralConv",
-           "GlobalSumPool", "GlobalAvgPool", "GlobalMaxPool", "Dense", "GCN2", "GeneralGNN", "DeviceBatch",
+           "GlobalSumPool", "GlobalAvgPool", "GlobalMaxPool", "Dense", "BatchNorm1d", "PReLU", "GCN2", "GCN", "GeneralGNN", "DeviceBatch",
            "save_to_npz", "load_weights_npz", "best_epoch", "DeviceDataset", "DeviceDisjointLoader",
-           "PiecewiseConstantDecay", "fit", "roc_curve", "auc"]
+           "PiecewiseConstantDecay", "fit", "roc_curve", "auc", "binary_acc"]
 
 
 def __getattr__(name):  # device-side names load libgcnx lazily, host-only use needs no .so
     if name in ("Context", "default_context", "DeviceArray", "DeviceCSR", "Segments"):
         from . import device
         return getattr(device, name)
-    if name in ("GCNConv", "GeneralConv", "GlobalSumPool", "GlobalAvgPool", "GlobalMaxPool", "Dense"):
+    if name in ("GCNConv", "GeneralConv", "GlobalSumPool", "GlobalAvgPool", "GlobalMaxPool", "Dense", "BatchNorm1d", "PReLU"):
         from . import layers
         return getattr(layers, name)
     if name in ("DeviceDataset", "DeviceDisjointLoader", "collate_on_device"):
         from . import device_loader
         return getattr(device_loader, name)
-    if name in ("GCN2", "GeneralGNN", "DeviceBatch", "evaluate"):
+    if name in ("GCN2", "GCN", "GeneralGNN", "DeviceBatch", "evaluate"):
         from . import models
         return getattr(models, name)
     raise AttributeError(name)

@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("GCNX_LIB") or os.path.join(_HERE, "libgcnx.so")   # G
 # enums of include/gcnx.h
 OK = 0
 ERR_UNSUPPORTED = 5   # GCNX_ERR_UNSUPPORTED: a valid request this build has no kernel for (callers fall back)
-ACT_NONE, ACT_RELU, ACT_PRELU = 0, 1, 2
+ACT_NONE, ACT_RELU, ACT_PRELU, ACT_PRELU_SHARED = 0, 1, 2, 3
 POOL_SUM, POOL_AVG, POOL_MAX = 0, 1, 2
 PREC_F32, PREC_BF16, PREC_BF16X3 = 0, 1, 2
 NORM_SPEKTRAL, NORM_PYG = 0, 1
@@ -24,7 +24,8 @@ CCE_PROBS, CCE_LOGITS = 0, 1
 CSR_SYMMETRIC, CSR_BLOCK_DIAGONAL, CSR_GRAPH_PTR_OK = 1, 2, 4
 UNIQUE_ID_BYTES = 128
 
-ACTS = {None: ACT_NONE, "linear": ACT_NONE, "none": ACT_NONE, "relu": ACT_RELU, "prelu": ACT_PRELU}
+ACTS = {None: ACT_NONE, "linear": ACT_NONE, "none": ACT_NONE, "relu": ACT_RELU, "prelu": ACT_PRELU,
+        "prelu_shared": ACT_PRELU_SHARED}
 POOLS = {"sum": POOL_SUM, "avg": POOL_AVG, "mean": POOL_AVG, "max": POOL_MAX}
 CCES = {"probs": CCE_PROBS, "eager": CCE_PROBS, "logits": CCE_LOGITS, "graph": CCE_LOGITS}
 PRECS = {"f32": PREC_F32, "fp32": PREC_F32, "bf16": PREC_BF16, "bf16x3": PREC_BF16X3}
@@ -107,6 +108,11 @@ SIGNATURES = {
                         _vp],
     "gcnx_bn_act_bwd_stats": [_vp, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp],
     "gcnx_bn_act_bwd_apply": [_vp, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _int, _vp, _vp, _f32, _int, _vp, _i64],
+    "gcnx_bn_act_pool": [_vp, _vp, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _int, _vp, _int, _vp, _i64, _vp],
+    "gcnx_bn_act_pool_bwd": [_vp, _vp, _i32, _vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _int, _vp, _int, _vp, _i64,
+                             _vp, _vp, _vp],
+    "gcnx_bce_head_scratch_floats": [_i32, _i32],
+    "gcnx_bn_prelu_bce_head": [_vp, _vp],
     "gcnx_sgd": [_vp, _vp, _vp, _i64, _f32],
     "gcnx_dropout": [_vp, _vp, _i64, _i64, _i32, _f32, C.c_uint32, C.c_uint32, _vp, _vp, _i64],
     "gcnx_counter_add": [_vp, _vp, C.c_uint32],
@@ -136,7 +142,7 @@ SIGNATURES = {
     "gcnx_comm_destroy": [_vp],
     "gcnx_allreduce_f32": [_vp, _vp, _vp, _i64, _int],
 }
-_RESTYPE = {"gcnx_last_error": C.c_char_p, "gcnx_dense_bwd_scratch_floats": C.c_int64,
+_RESTYPE = {"gcnx_last_error": C.c_char_p, "gcnx_dense_bwd_scratch_floats": C.c_int64, "gcnx_bce_head_scratch_floats": C.c_int64,
             "gcnx_gcn_conv_bwd_scratch_floats": C.c_int64, "gcnx_wimage_elems": C.c_int64, "gcnx_gemm_wimage_parts": C.c_int64}
 
 
@@ -167,6 +173,21 @@ class HeadArgs(C.Structure):
                 ("w", C.c_void_p), ("bias", C.c_void_p), ("y", C.c_void_p), ("c", C.c_int32), ("denom", C.c_float), ("cce_mode", C.c_int),
                 ("probs", C.c_void_p), ("loss_acc", C.c_void_p), ("dw", C.c_void_p), ("db", C.c_void_p), ("db_relu", C.c_void_p),
                 ("pooled", C.c_void_p), ("dpooled", C.c_void_p)]
+
+
+class BceHeadArgs(C.Structure):
+    """gcnx_bce_head_args (include/gcnx.h): the post-pool half of the torch GCN, its BCE loss and gradients in one launch."""
+    _fields_ = [("pooled", C.c_void_p), ("ldp", C.c_int64), ("b", C.c_int32), ("h", C.c_int32),
+                ("w3", C.c_void_p), ("b3", C.c_void_p), ("gamma3", C.c_void_p), ("beta3", C.c_void_p), ("alpha3", C.c_void_p),
+                ("w4", C.c_void_p), ("b4", C.c_void_p), ("gamma4", C.c_void_p), ("beta4", C.c_void_p), ("alpha4", C.c_void_p),
+                ("eps", C.c_float), ("denom", C.c_float),
+                ("y", C.c_void_p), ("y_stride", C.c_int32), ("y_col", C.c_int32), ("grads", C.c_int32),
+                ("out", C.c_void_p), ("probs", C.c_void_p), ("loss_acc", C.c_void_p),
+                ("dpooled", C.c_void_p), ("lddp", C.c_int64),
+                ("dw3", C.c_void_p), ("db3", C.c_void_p), ("dgamma3", C.c_void_p), ("dbeta3", C.c_void_p), ("dalpha3", C.c_void_p),
+                ("dw4", C.c_void_p), ("db4", C.c_void_p), ("dgamma4", C.c_void_p), ("dbeta4", C.c_void_p), ("dalpha4", C.c_void_p),
+                ("scratch", C.c_void_p), ("scratch_floats", C.c_int64)]
+
 
 _lib = None
 

@@ -1038,3 +1038,56 @@ def spmm_minmax_bwd(ctx, at, h, out, cnt, dy, dh, mode="max"):
     ctx._ck(ctx.lib.gcnx_spmm_csr_minmax_bwd(ctx.h, at.rowptr.ptr, at.colidx.ptr, _p(h), h.ld, _p(out), out.ld, _p(cnt), cnt.ld,
                                              _p(dy), dy.ld, _p(dh), dh.ld, n, f))
     return dh
+
+
+# ---- the reference's torch GCN (gcn_utills.py:795-853): BatchNorm1d + PReLU() + global_max_pool, BCE head ----------------
+TORCH_BN_EPS = 1e-5                  # torch.nn.BatchNorm1d default
+
+
+def bn_act_pool(ctx, seg, z, mean, inv, gamma, beta, pooled, argmax, act="prelu_shared", alpha=None, mode="max"):
+    """pooled[g] = max over graph g's rows of act(BN(z)) and its argmax rows, in one pass (gcnx_bn_act_pool)."""
+    n, f = z.shape
+    ctx._ck(ctx.lib.gcnx_bn_act_pool(ctx.h, seg.dev.ptr, seg.n_graphs, _p(z), z.ld, f, _p(mean), _p(inv), _p(gamma), _p(beta),
+                                     L.ACTS[act], _p(alpha), L.POOLS[mode], _p(pooled), pooled.ld, argmax.ptr))
+    return pooled
+
+
+def bn_act_pool_bwd(ctx, seg, dpooled, argmax, z, mean, inv, gamma, beta, dz, act="prelu_shared", alpha=None, dgamma=None,
+                    dbeta=None, dalpha=None, mode="max"):
+    """dZ and the BN / PReLU parameter gradients from dPooled (gcnx_bn_act_pool_bwd)."""
+    n, f = z.shape
+    ctx._ck(ctx.lib.gcnx_bn_act_pool_bwd(ctx.h, seg.dev.ptr, seg.n_graphs, _p(dpooled), dpooled.ld, argmax.ptr, _p(z), z.ld, n, f,
+                                         _p(mean), _p(inv), _p(gamma), _p(beta), L.ACTS[act], _p(alpha), L.POOLS[mode], _p(dz),
+                                         dz.ld, _p(dgamma), _p(dbeta), _p(dalpha)))
+    return dz
+
+
+def bce_head_scratch_floats(ctx, b, h):
+    return int(ctx.lib.gcnx_bce_head_scratch_floats(int(b), int(h)))
+
+
+def bce_head_args(pooled, p, scratch, out, probs, y=None, loss_acc=None, denom=None, g=None, dpooled=None, eps=TORCH_BN_EPS):
+    """gcnx_bce_head_args.  p / g: dicts of the head's parameters / gradients ("w3", "b3", "g3", "be3", "a3", "w4", ...;
+    w3 [h, h] and w4 [1, h] in torch's [out, in] layout).  y: labels [b, 2] one-hot (t = y[:, 1]), [b, 1] or [b]
+    (t = y[:, 0] / y); None for the forward alone.  g (needs y): the gradients are written."""
+    b, h = pooled.shape
+    if y is not None:
+        stride = y.shape[1] if len(y.shape) == 2 else 1
+        col = 1 if stride == 2 else 0
+        if stride > 2:
+            raise ValueError(f"binary labels are [B], [B, 1] or one-hot [B, 2], got {tuple(y.shape)}")
+    else:
+        stride, col = 1, 0
+    gp = (lambda k: _p(g[k])) if g is not None else (lambda k: None)
+    return L.BceHeadArgs(
+        _p(pooled), pooled.ld, b, h, _p(p["w3"]), _p(p["b3"]), _p(p["g3"]), _p(p["be3"]), _p(p["a3"]),
+        _p(p["w4"]), _p(p["b4"]), _p(p["g4"]), _p(p["be4"]), _p(p["a4"]), float(eps), float(denom if denom else b),
+        _p(y), stride, col, 1 if g is not None else 0, _p(out), _p(probs), _p(loss_acc),
+        _p(dpooled), dpooled.ld if dpooled is not None else 0,
+        gp("w3"), gp("b3"), gp("g3"), gp("be3"), gp("a3"), gp("w4"), gp("b4"), gp("g4"), gp("be4"), gp("a4"),
+        _p(scratch), scratch.size)
+
+
+def bn_prelu_bce_head(ctx, args):
+    """The post-pool half of the torch GCN in one launch (gcnx_bn_prelu_bce_head); args from bce_head_args."""
+    ctx._ck(ctx.lib.gcnx_bn_prelu_bce_head(ctx.h, C.byref(args)))

@@ -368,3 +368,73 @@ class GlobalAvgPool(_GlobalPool):
 class GlobalMaxPool(_GlobalPool):
     """global_max_pool of the reference's torch topology (gcn_utills.py:842)."""
     mode = "max"
+
+
+class BatchNorm1d(Layer):
+    """torch.nn.BatchNorm1d(F, track_running_stats=False, momentum=None) -- the reference's torch GCN
+    (gcn_utills.py:816-826): batch mean and biased variance, eps 1e-5, in training AND evaluation (no running
+    statistics); weight (gamma) 1, bias (beta) 0.  One row raises ValueError, as torch does.  ``backward(dy)`` is the
+    training-mode backward; the parameter gradients land in ``grads["weight"]`` / ``grads["bias"]``."""
+
+    def __init__(self, eps=D.TORCH_BN_EPS, **kw):
+        super().__init__(**kw)
+        self.eps = float(eps)
+
+    def _param_spec(self, in_dim):
+        return [("weight", (in_dim,), np.ones(in_dim, np.float32)), ("bias", (in_dim,), np.zeros(in_dim, np.float32))]
+
+    def call(self, x, training=False, out=None):
+        n, f = x.shape
+        if n < 2:
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size [{n}, {f}]")
+        if not self.built:
+            self.build(x.ctx, f)
+        mean, inv = self._buf("mean", (f,)), self._buf("inv", (f,))
+        D.bn_moments(self.ctx, x, None, mean, inv, eps=self.eps)
+        y = out if out is not None else self._buf("y", (n, f))
+        D.bn_act(self.ctx, x, mean, inv, self.params["weight"], self.params["bias"], y)
+        self._saved = (x, mean, inv)
+        return y
+
+    def backward(self, dy, need_dx=True):
+        x, mean, inv = self._saved
+        dx = self._buf("dx", x.shape)
+        D.bn_act_bwd(self.ctx, dy, x, mean, inv, self.params["weight"], self.params["bias"], dx, self._buf("sums", (3 * x.shape[1],)),
+                     dgamma=self.grads["weight"], dbeta=self.grads["bias"])
+        return dx
+
+
+class PReLU(Layer):
+    """torch.nn.PReLU(): y = max(0, x) + a * min(0, x) with ONE slope a for every feature (init 0.25);
+    ``grads["weight"]`` = sum over all elements of dY * min(x, 0).  Runs on gcnx_bn_act(_bwd) with an identity
+    normalisation (mean 0, inv 1, gamma 1, beta 0: fma(x - 0, 1, 0) == x exactly) and GCNX_ACT_PRELU_SHARED."""
+
+    def __init__(self, init=0.25, **kw):
+        super().__init__(**kw)
+        self.init = float(init)
+
+    def _param_spec(self, in_dim):
+        return [("weight", (1,), np.full(1, self.init, np.float32))]
+
+    def _identity(self, f):
+        key = ("id", f)
+        if key not in self._scratch:
+            self._scratch[key] = (self.ctx.zeros(f), self.ctx.to_device(np.ones(f, np.float32)))
+        return self._scratch[key]
+
+    def call(self, x, out=None):
+        if not self.built:
+            self.build(x.ctx, x.shape[1])
+        zero, one = self._identity(x.shape[1])
+        y = out if out is not None else self._buf("y", x.shape)
+        D.bn_act(self.ctx, x, zero, one, one, zero, y, act="prelu_shared", alpha=self.params["weight"])
+        self._saved = x
+        return y
+
+    def backward(self, dy, need_dx=True):
+        x = self._saved
+        zero, one = self._identity(x.shape[1])
+        dx = self._buf("dx", x.shape)
+        D.bn_act_bwd(self.ctx, dy, x, zero, one, one, zero, dx, self._buf("sums", (3 * x.shape[1],)), act="prelu_shared",
+                     alpha=self.params["weight"], training=False, dalpha=self.grads["weight"])
+        return dx

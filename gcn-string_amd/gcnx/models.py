@@ -9,6 +9,9 @@ mean categorical accuracy.  BN-free, so an N-GPU step equals the 1-GPU step (SUR
 
 The step is a fixed sequence of libgcnx calls on preallocated buffers; after one eager run it
 is captured into a HIP graph (the role tf.function plays at gcn.py:328) and replayed.
+
+``GCN``: the reference's torch class (gcn_utills.py:795-853): GCNConv·BatchNorm1d·PReLU twice, global_max_pool,
+Linear·BatchNorm1d·PReLU twice, one logit with BCEWithLogitsLoss (eager launches).
 """
 from __future__ import annotations
 
@@ -1201,3 +1204,326 @@ class GeneralGNN(_GraphRunner):
 
     def gradients(self):
         return [{k[2:]: L[k].numpy() for k in L if k.startswith("g_")} for L in self.layers]
+
+
+def _with_remaining_self_loops(a, n):
+    """PyG's add_remaining_self_loops on the batch adjacency (host, COO or scipy): a weight-1 loop where a row stores no
+    diagonal entry, existing loops kept.  The device normalisation (gcnx_gcn_norm, PYG mode) needs every diagonal
+    stored; values are ignored afterwards (the torch GCN passes no edge_weight)."""
+    from .loader import sp_matrix_to_sp_tensor
+    if not isinstance(a, SparseTensor):
+        a = sp_matrix_to_sp_tensor(a)
+    idx = np.asarray(a.indices, np.int64).reshape(-1, 2)
+    has = np.zeros(n, bool)
+    d = idx[:, 0] == idx[:, 1]
+    has[idx[d, 0]] = True
+    if has.all():
+        return a
+    miss = np.nonzero(~has)[0].astype(np.int64)
+    idx = np.concatenate([idx, np.stack([miss, miss], 1)])
+    vals = np.concatenate([np.asarray(a.values, np.float64).ravel(), np.ones(miss.size)])
+    order = np.lexsort((idx[:, 1], idx[:, 0]))
+    return SparseTensor(idx[order], vals[order], (n, n))
+
+
+class GCN(_GraphRunner):
+    """The reference's torch class ``GCN`` (src/utilities/gcn_utills.py:795-853), BASELINE config 1's topology:
+
+        GCNConv(F->H)·BN·PReLU -> GCNConv(H->H)·BN·PReLU -> global_max_pool -> Linear(H->H)·BN·PReLU -> Linear(H->1)·BN·PReLU
+
+    with BCEWithLogitsLoss on the single logit and plain SGD.  Semantics ("torch GCN"): PyG GCNConv on the
+    UNWEIGHTED adjacency with add_remaining_self_loops and symmetric normalisation; BatchNorm1d(track_running_stats=False):
+    batch statistics (biased variance, eps 1e-5) in training AND evaluation, so a batch of one graph raises ValueError as
+    torch does; PReLU(): one slope per layer.  fp32, eager launches.
+
+    Hot path: gcnx_gemm / gcnx_gcn_conv_fwd + gcnx_spmm_csr for the convolutions, gcnx_bn_moments and gcnx_bn_act
+    (GCNX_ACT_PRELU_SHARED) for BN1·PReLU1, gcnx_bn_act_pool (BN2·PReLU2·max-pool in one pass, and its two-launch backward)
+    and gcnx_bn_prelu_bce_head (Linear·BN·PReLU twice, the loss and all their gradients in one launch).  GCNX_BN_POOL=0
+    (read at construction) replaces the fused pool pair by gcnx_bn_act + gcnx_segment_pool and their backward.
+
+    Weights: ``state_dict()`` / ``load_state_dict()`` use torch's key names and layouts; ``get_weights()`` lists the same
+    tensors in ``named_parameters()`` order (modules in the reference's __init__ order; inside PyG 2.x GCNConv the bias
+    is registered before ``lin.weight``).  That order follows PyG 2.x's source; neither torch_geometric nor the
+    reference's checkpoint was available to confirm it against a live module, so prefer the named dicts."""
+
+    PARAM_ORDER = ("w1", "b1", "g1", "be1", "a1", "w2", "b2", "g2", "be2", "a2",
+                   "w3", "b3", "g3", "be3", "a3", "w4", "b4", "g4", "be4", "a4")
+    # (torch key, internal key, transposed): named_parameters() order; the conv kernels are stored [in, out] (gcnx_gemm)
+    TORCH_KEYS = (("conv1.bias", "b1", False), ("conv1.lin.weight", "w1", True),
+                  ("conv2.bias", "b2", False), ("conv2.lin.weight", "w2", True),
+                  ("linear_1.weight", "w3", False), ("linear_1.bias", "b3", False),
+                  ("linear_2.weight", "w4", False), ("linear_2.bias", "b4", False),
+                  ("prelu_1.weight", "a1", False), ("prelu_2.weight", "a2", False),
+                  ("prelu_3.weight", "a3", False), ("prelu_4.weight", "a4", False),
+                  ("batch_norm_1.weight", "g1", False), ("batch_norm_1.bias", "be1", False),
+                  ("batch_norm_2.weight", "g2", False), ("batch_norm_2.bias", "be2", False),
+                  ("batch_norm_3.weight", "g3", False), ("batch_norm_3.bias", "be3", False),
+                  ("batch_norm_4.weight", "g4", False), ("batch_norm_4.bias", "be4", False))
+    EPS = D.TORCH_BN_EPS
+
+    def __init__(self, *args, **kw):
+        """GCN([ctx,] hidden_channels=64, num_classes=1, seed=0): the reference's constructor behind an optional ctx."""
+        if args and isinstance(args[0], D.Context):
+            ctx, args = args[0], args[1:]
+        else:
+            ctx = kw.pop("ctx", None)
+        self._init(ctx, *args, **kw)
+
+    def _init(self, ctx, hidden_channels=64, num_classes=1, seed=0, comm=None):
+        if int(num_classes) != 1:
+            raise NotImplementedError("gcnx.GCN: num_classes must be 1 (one logit + BCEWithLogitsLoss, as the reference)")
+        if comm is not None:
+            raise NotImplementedError("gcnx.GCN: multi-GPU needs sync-BN, which this model does not implement")
+        self.ctx = ctx if ctx is not None else D.default_context()
+        self.hidden, self.num_classes = int(hidden_channels), 1
+        self.use_graph = False               # eager launches (~20 per step)
+        self._bn_pool = os.environ.get("GCNX_BN_POOL", "1") != "0"    # knob, read once
+        self._rng = np.random.default_rng(seed)
+        self.built = False
+        self._bufs = None
+        self._graphs = {}
+        self._op_cache = None
+
+    # ---- parameters: one flat buffer (one SGD launch) ------------------------------------------------------------------
+    def _shapes(self, f_in):
+        h = self.hidden
+        s = {"w1": (f_in, h), "w2": (h, h), "w3": (h, h), "w4": (1, h), "b4": (1,), "g4": (1,), "be4": (1,), "a4": (1,)}
+        for k in ("b1", "g1", "be1", "b2", "g2", "be2", "b3", "g3", "be3"):
+            s[k] = (h,)
+        for k in ("a1", "a2", "a3"):
+            s[k] = (1,)
+        return s
+
+    def build(self, f_in):
+        h = self.hidden
+        if h > 256:
+            raise NotImplementedError("gcnx.GCN: hidden_channels <= 256 (the one-workgroup head)")
+        shapes = self._shapes(f_in)
+        self.f_in = int(f_in)
+        # every parameter starts on a 16-byte boundary (the one-launch GCNConv reads W and b as float4); the padding
+        # floats have zero gradients, so the single SGD launch over the whole buffer leaves them at zero
+        offs, off = {}, 0
+        for k in self.PARAM_ORDER:
+            offs[k] = off
+            off += -(-int(np.prod(shapes[k])) // 4) * 4
+        self.n_params = off
+        self.flat_p = self.ctx.zeros(self.n_params)
+        self.flat_g = self.ctx.zeros(self.n_params + 2)
+        self.p, self.g = {}, {}
+        for k in self.PARAM_ORDER:
+            n = int(np.prod(shapes[k]))
+            self.p[k] = self.flat_p.flat(offs[k], n, shapes[k])
+            self.g[k] = self.flat_g.flat(offs[k], n, shapes[k])
+        self.loss_acc = self.flat_g.flat(self.n_params, 2)
+        rng, lim = self._rng, 1.0 / np.sqrt(h)
+        init = {"w1": glorot_uniform(rng, f_in, h), "w2": glorot_uniform(rng, h, h),
+                "w3": rng.uniform(-lim, lim, (h, h)), "b3": rng.uniform(-lim, lim, h),
+                "w4": rng.uniform(-lim, lim, (1, h)), "b4": rng.uniform(-lim, lim, 1)}
+        for k in ("g1", "g2", "g3", "g4"):
+            init[k] = np.ones(shapes[k])
+        for k in ("a1", "a2", "a3", "a4"):
+            init[k] = np.full(1, 0.25)
+        for k, v in init.items():
+            self.p[k].copy_from_host(np.asarray(v, np.float32))
+        self.built = True
+
+    def state_dict(self):
+        """{torch key: array in torch's layout}: conv*.lin.weight [out, in], linear_*.weight [out, in], prelu_*.weight [1]."""
+        return {tk: (self.p[k].numpy().T.copy() if tr else self.p[k].numpy()) for tk, k, tr in self.TORCH_KEYS}
+
+    def load_state_dict(self, d):
+        """Inverse of state_dict (a converted torch checkpoint: tensors as NumPy arrays).  Builds the model if needed."""
+        if not self.built:
+            self.build(int(np.asarray(d["conv1.lin.weight"]).shape[1]))
+        missing = [tk for tk, _, _ in self.TORCH_KEYS if tk not in d]
+        if missing:
+            raise KeyError(f"gcnx.GCN.load_state_dict: missing {missing}")
+        for tk, k, tr in self.TORCH_KEYS:
+            v = np.asarray(d[tk], np.float32)
+            v = v.T if tr else v
+            if v.shape != self.p[k].shape:
+                raise ValueError(f"{tk}: shape {np.asarray(d[tk]).shape} does not fit this model")
+            self.p[k].copy_from_host(np.ascontiguousarray(v))
+
+    def get_weights(self):
+        """The state_dict tensors in named_parameters() order (see the class docstring)."""
+        sd = self.state_dict()
+        return [sd[tk] for tk, _, _ in self.TORCH_KEYS]
+
+    def set_weights(self, weights):
+        self.load_state_dict({tk: w for (tk, _, _), w in zip(self.TORCH_KEYS, weights)})
+
+    def gradients(self):
+        """{torch key: gradient of the last loss_and_grads / train_step} in torch's layouts."""
+        return {tk: (self.g[k].numpy().T.copy() if tr else self.g[k].numpy()) for tk, k, tr in self.TORCH_KEYS}
+
+    @property
+    def trainable_variables(self):
+        return [self.p[k] for _, k, _ in self.TORCH_KEYS]
+
+    @property
+    def losses(self):
+        return []
+
+    # ---- batches ------------------------------------------------------------------------------------------------------
+    def _as_batch(self, inputs, target=None):
+        if isinstance(inputs, DeviceBatch):
+            if target is not None and inputs.y is None:
+                inputs.y = self.ctx.to_device(target, np.float32)
+            return inputs
+        x, a, i = inputs
+        if not isinstance(a, D.DeviceCSR):
+            a = _with_remaining_self_loops(a, np.asarray(x).shape[0])
+        return DeviceBatch.from_host(self.ctx, (x, a, i), target, weighted=False)
+
+    def _op(self, batch):
+        """A^ = D^-1/2 (A + I_missing) D^-1/2 of the batch, values ignored (built once per batch object)."""
+        if self._op_cache is None or self._op_cache[0] != batch.uid:
+            a_hat = batch.a.unweighted().gcn_norm("pyg")
+            self._op_cache = (batch.uid, a_hat, a_hat.transpose())
+        return self._op_cache[1], self._op_cache[2]
+
+    def _ensure(self, batch):
+        if batch.n_graphs < 2 or batch.n < 2:
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size [{batch.n_graphs}, "
+                             f"{self.hidden}]: BatchNorm1d(track_running_stats=False) needs at least 2 graphs per batch")
+        if not self.built:
+            self.build(batch.f)
+        if batch.f != self.f_in:
+            raise ValueError(f"gcnx.GCN was built for {self.f_in} node features, got {batch.f}")
+        key = (batch.n, batch.n_graphs)
+        if self._bufs is not None and self._bufs["key"] == key:
+            return self._bufs
+        if getattr(self, "_cap", None) is None:
+            self._cap = _Capacity(self.ctx)
+        v, n, b, h = self._cap.view, batch.n, batch.n_graphs, self.hidden
+        bufs = {"key": key}
+        for k in ("h1", "z1", "y1", "z2", "y2", "dz2", "t", "dy1", "dz1", "s2"):
+            bufs[k] = v(k, n, h)
+        for k in ("m1", "i1", "m2", "i2"):
+            bufs[k] = v(k, 1, h).flat(0, h)
+        bufs["sums"] = v("sums", 1, 3 * h).flat(0, 3 * h)
+        bufs["pooled"], bufs["dpooled"] = v("pooled", b, h), v("dpooled", b, h)
+        bufs["arg"] = v("arg", b, h, np.int32)
+        bufs["out"], bufs["probs"] = v("out", b, 1), v("probs", b, 1)
+        nh = D.bce_head_scratch_floats(self.ctx, b, h)
+        bufs["head"] = v("head", 1, nh).flat(0, nh)
+        self._bufs = bufs
+        return bufs
+
+    # ---- the call sequences --------------------------------------------------------------------------------------------
+    def _conv(self, a_hat, x, w, bias, out, h_tmp, s=None):
+        """A^ (x W) + b.  Returns True if it ran as the one-launch (A^ x) W (then ``s`` receives S = A^ x, the operand of
+        dW = S^T dZ, as GCNConv.backward uses it)."""
+        ctx = self.ctx
+        if a_hat.plan is None and x.contiguous and D.gcn_conv_fused_ok(ctx, x.shape[0], x.shape[1], w.shape[1], x.ld):
+            D.gcn_conv_fwd(ctx, a_hat, x, w, bias, out, act=None, s=s)     # (A^ x) W + b in one launch
+            return True
+        D.gemm(ctx, x, w, None, h_tmp)
+        D.spmm(ctx, a_hat, h_tmp, bias, out)
+        return False
+
+    def _forward(self, batch, bufs, mode, denom=None):
+        """mode: "fwd" (logits only), "loss" (+ loss and hits), "grads" (+ dPooled and the head's gradients)."""
+        ctx, p, e = self.ctx, self.p, self.EPS
+        a_hat, _ = self._op(batch)
+        self._conv(a_hat, batch.x, p["w1"], p["b1"], bufs["z1"], bufs["h1"])
+        D.bn_moments(ctx, bufs["z1"], None, bufs["m1"], bufs["i1"], eps=e)
+        D.bn_act(ctx, bufs["z1"], bufs["m1"], bufs["i1"], p["g1"], p["be1"], bufs["y1"], act="prelu_shared", alpha=p["a1"])
+        bufs["s2_ok"] = self._conv(a_hat, bufs["y1"], p["w2"], p["b2"], bufs["z2"], bufs["h1"],
+                                   s=bufs["s2"] if mode == "grads" else None)
+        D.bn_moments(ctx, bufs["z2"], None, bufs["m2"], bufs["i2"], eps=e)
+        if self._bn_pool:
+            D.bn_act_pool(ctx, batch.seg, bufs["z2"], bufs["m2"], bufs["i2"], p["g2"], p["be2"], bufs["pooled"], bufs["arg"],
+                          alpha=p["a2"])
+        else:
+            D.bn_act(ctx, bufs["z2"], bufs["m2"], bufs["i2"], p["g2"], p["be2"], bufs["y2"], act="prelu_shared", alpha=p["a2"])
+            D.segment_pool(ctx, batch.seg, bufs["y2"], bufs["pooled"], "max", bufs["arg"])
+        y = batch.y if mode != "fwd" else None
+        if y is None and mode != "fwd":
+            raise ValueError("gcnx.GCN: labels are needed for the loss")
+        grads = mode == "grads"
+        args = D.bce_head_args(bufs["pooled"], p, bufs["head"], bufs["out"], bufs["probs"], y=y,
+                               loss_acc=self.loss_acc if y is not None else None, denom=denom or batch.n_graphs,
+                               g=self.g if grads else None, dpooled=bufs["dpooled"] if grads else None, eps=e)
+        D.bn_prelu_bce_head(ctx, args)
+
+    def _backward(self, batch, bufs):
+        ctx, p, g = self.ctx, self.p, self.g
+        _, a_t = self._op(batch)
+        if self._bn_pool:
+            D.bn_act_pool_bwd(ctx, batch.seg, bufs["dpooled"], bufs["arg"], bufs["z2"], bufs["m2"], bufs["i2"], p["g2"], p["be2"],
+                              bufs["dz2"], alpha=p["a2"], dgamma=g["g2"], dbeta=g["be2"], dalpha=g["a2"])
+        else:
+            D.segment_pool_bwd(ctx, batch.seg, bufs["dpooled"], bufs["y2"], "max", bufs["arg"])
+            D.bn_act_bwd(ctx, bufs["y2"], bufs["z2"], bufs["m2"], bufs["i2"], p["g2"], p["be2"], bufs["dz2"], bufs["sums"],
+                         act="prelu_shared", alpha=p["a2"], dgamma=g["g2"], dbeta=g["be2"], dalpha=g["a2"])
+        D.act_bias_grad(ctx, bufs["dz2"], None, bufs["dz2"], None, db=g["b2"])       # conv2.bias: column sums of dZ2
+        if bufs["s2_ok"]:                                   # forward was (A^ Y1) W2: the association of GCNConv.backward
+            D.gemm_dw(ctx, bufs["s2"], bufs["dz2"], g["w2"])                        # dW2 = S2^T dZ2
+            D.gemm_dx(ctx, bufs["dz2"], p["w2"], bufs["t"])                         # dZ2 W2^T
+            D.spmm(ctx, a_t, bufs["t"], None, bufs["dy1"])                          # dY1 = A^T (dZ2 W2^T)
+        else:
+            D.spmm(ctx, a_t, bufs["dz2"], None, bufs["t"])                          # A^T dZ2
+            D.gemm_dw(ctx, bufs["y1"], bufs["t"], g["w2"])                          # dW2 = Y1^T (A^T dZ2)
+            D.gemm_dx(ctx, bufs["t"], p["w2"], bufs["dy1"])                         # dY1 = (A^T dZ2) W2^T
+        D.bn_act_bwd(ctx, bufs["dy1"], bufs["z1"], bufs["m1"], bufs["i1"], p["g1"], p["be1"], bufs["dz1"], bufs["sums"],
+                     act="prelu_shared", alpha=p["a1"], dgamma=g["g1"], dbeta=g["be1"], dalpha=g["a1"])
+        D.act_bias_grad(ctx, bufs["dz1"], None, bufs["dz1"], None, db=g["b1"])
+        D.spmm(ctx, a_t, bufs["dz1"], None, bufs["t"])
+        D.gemm_dw(ctx, batch.x, bufs["t"], g["w1"])
+
+    # ---- public surface ---------------------------------------------------------------------------------------------
+    def __call__(self, inputs, training=False):
+        """model((x, a, i), training=False) -> the logits [B, 1] (torch's forward output; BatchNorm uses batch statistics
+        either way)."""
+        batch = self._as_batch(inputs)
+        bufs = self._ensure(batch)
+        self._forward(batch, bufs, "fwd")
+        return bufs["out"].numpy()
+
+    def forward(self, x, edge_index, batch):
+        """The torch-style call: x [N, F], edge_index [2, E] (PyG's source -> target flow: row = edge_index[1], column =
+        edge_index[0]; duplicate edges count once), batch [N] graph ids.  Returns the logits [B, 1]."""
+        import scipy.sparse as sp
+        x = np.asarray(x, np.float32)
+        ei = np.asarray(edge_index, np.int64).reshape(2, -1)
+        n = x.shape[0]
+        a = sp.coo_matrix((np.ones(ei.shape[1]), (ei[1], ei[0])), shape=(n, n)).tocsr()
+        a.data[:] = 1.0
+        return self((x, a, np.asarray(batch, np.int64)))
+
+    def loss_and_grads(self, inputs, target=None, global_batch=None, _lr=None):
+        """Forward + BCE + every gradient (+ the SGD update with ``_lr``).  Returns the device batch."""
+        batch = self._as_batch(inputs, target)
+        bufs = self._ensure(batch)
+        denom = float(global_batch or batch.n_graphs)
+        self._forward(batch, bufs, "grads", denom)
+        self._backward(batch, bufs)
+        if _lr is not None:
+            D.sgd(self.ctx, self.flat_p, self.flat_g.flat(0, self.n_params), _lr)
+        self._last_batch = batch
+        return batch
+
+    def train_step(self, inputs, target=None, lr=0.02, fetch=True, global_batch=None):
+        """One optimisation step: loss, gradients, p -= lr * g.  fetch: True -> (loss, acc); False -> None; "stash" ->
+        None, metrics kept on the device for collect_metrics()."""
+        batch = self.loss_and_grads(inputs, target, global_batch, _lr=float(lr))
+        if fetch == "stash":
+            self.stash_metrics(global_batch or batch.n_graphs)
+            return None
+        if not fetch:
+            return None
+        return self.fetch_metrics(global_batch or batch.n_graphs)
+
+    def fetch_metrics(self, n_graphs):
+        la = self.loss_acc.numpy()
+        return float(la[0]), float(la[1]) / float(n_graphs)
+
+    def evaluate_batch(self, inputs, target):
+        """(loss, accuracy, probabilities [B, 1]) without gradients (BatchNorm on batch statistics, as torch's eval here)."""
+        batch = self._as_batch(inputs, target)
+        bufs = self._ensure(batch)
+        self._forward(batch, bufs, "loss", float(batch.n_graphs))
+        la = self.loss_acc.numpy()
+        return float(la[0]), float(la[1]) / batch.n_graphs, bufs["probs"].numpy()

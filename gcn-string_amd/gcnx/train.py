@@ -6,6 +6,7 @@
 * ``fit`` -- the loop of gcn.py:364-385: train over ``loader_tr``, after every epoch evaluate on ``loader_te`` (batch-size
   weighted means, gcn.py:362), print the reference's progress line, collect ``model.get_weights()`` and the test
   accuracy per epoch.
+* ``binary_acc`` -- the accuracy helper of gcn.py:42-57 for the torch GCN's single logit, restated in NumPy.
 * ``roc_curve`` / ``auc`` -- what gcn.py:402-403 takes from scikit-learn, restated in NumPy (same thresholds, same
   trapezoid rule), so the script needs no scikit-learn.
 Loaders may be ``DisjointLoader`` (host batches, uploaded per step) or ``DeviceDisjointLoader`` (batches assembled on
@@ -118,3 +119,16 @@ def auc(x, y):
             return -float(np.trapezoid(y, x)) if hasattr(np, "trapezoid") else -float(np.trapz(y, x))
         raise ValueError("x is neither increasing nor decreasing")
     return float(np.trapezoid(y, x)) if hasattr(np, "trapezoid") else float(np.trapz(y, x))
+
+
+def binary_acc(y_pred, y_test):
+    """gcn.py:42-57 in NumPy: probas = sigmoid(logits), tags = round(probas) (half to even, as torch.round: a logit of 0
+    gives tag 0), acc = round(100 * #(tags == y_test) / len(y_test)).  Returns (acc, tags, probas)."""
+    z = np.asarray(y_pred, np.float64)
+    probas = 1.0 / (1.0 + np.exp(-z))
+    tags = np.round(probas)
+    y = np.asarray(y_test, np.float64)
+    if y.size == tags.size:
+        y = y.reshape(tags.shape)
+    acc = float(np.sum(tags == y)) / y.shape[0]
+    return float(np.round(acc * 100)), tags, probas

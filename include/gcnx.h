@@ -54,7 +54,11 @@ typedef enum {
   GCNX_ERR_DATA = 6         /* device-side validation of input data failed */
 } gcnx_status;
 
-typedef enum { GCNX_ACT_NONE = 0, GCNX_ACT_RELU = 1, GCNX_ACT_PRELU = 2 } gcnx_act;
+/* PRELU: one slope per feature, alpha[f] (Keras PReLU).  PRELU_SHARED: ONE slope alpha[0] for every feature
+ * (torch.nn.PReLU(), num_parameters = 1); its gradient dalpha[0] is the sum over all features.  PRELU_SHARED is served
+ * by gcnx_bn_act, gcnx_bn_act_bwd (+ _stats / _apply), gcnx_bn_act_pool(_bwd) and gcnx_bn_prelu_bce_head; every other
+ * entry point that takes an activation refuses it (GCNX_ERR_INVALID). */
+typedef enum { GCNX_ACT_NONE = 0, GCNX_ACT_RELU = 1, GCNX_ACT_PRELU = 2, GCNX_ACT_PRELU_SHARED = 3 } gcnx_act;
 typedef enum { GCNX_POOL_SUM = 0, GCNX_POOL_AVG = 1, GCNX_POOL_MAX = 2 } gcnx_pool;
 /* GEMM arithmetic: F32 = exact fp32 MFMA (v_mfma_f32_*_f32); BF16 = inputs rounded to bf16,
  * fp32 accumulate; BF16X3 = hi/lo bf16 split (16 significand bits per operand, 2^-18 relative), three MFMA passes. */
@@ -431,6 +435,49 @@ GCNX_API int gcnx_bn_act_bwd_stats(gcnx_ctx* ctx, const float* dy, int64_t lddy,
 GCNX_API int gcnx_bn_act_bwd_apply(gcnx_ctx* ctx, const float* dy, int64_t lddy, const float* z, int64_t ldz, int64_t n,
                           int32_t f, const float* mean, const float* inv, const float* gamma, const float* beta, int act,
                           const float* alpha, const float* sums, float count, int training, float* dz, int64_t lddz);
+
+/* ---- the reference's torch GCN (gcn_utills.py:795-853): BatchNorm1d(track_running_stats=False) + PReLU() -------------
+ * gcnx_bn_act + gcnx_segment_pool(MAX) in one pass over z: pooled[g, c] = max over graph g's rows of
+ * act(gamma * (z - mean) * inv + beta) and argmax[g, c] its row (int32[b * f]), the [n, f] activation never written.
+ * Every element is evaluated as gcnx_bn_act evaluates it and ties go to the first maximal row, so pooled and argmax are
+ * BIT-IDENTICAL to the two calls; an empty graph pools to 0.  pool_mode: GCNX_POOL_MAX only (GCNX_ERR_UNSUPPORTED
+ * otherwise). */
+GCNX_API int gcnx_bn_act_pool(gcnx_ctx* ctx, const int32_t* graph_ptr, int32_t b, const float* z, int64_t ldz, int32_t f,
+                     const float* mean, const float* inv, const float* gamma, const float* beta, int act, const float* alpha,
+                     int pool_mode, float* pooled, int64_t ldp, int32_t* argmax);
+/* Its backward (training-mode BatchNorm, batch statistics over the n rows): from dpooled [b, f], argmax and the saved z,
+ * mean, inv: dZ [n, f] = gamma * inv * (dzb - sum(dzb) / n - xhat * sum(dzb * xhat) / n) with dzb nonzero only at the
+ * argmax rows, and dgamma / dbeta [f], dalpha ([f] for PRELU, [1] for PRELU_SHARED) -- each may be NULL.  Two launches (the
+ * three column sums come from the b * f argmax entries alone, then one dense write of dZ).  graph_ptr must cover the rows:
+ * graph_ptr[0] = 0, graph_ptr[b] = n (rows outside every graph are not written).  pool_mode: GCNX_POOL_MAX only. */
+GCNX_API int gcnx_bn_act_pool_bwd(gcnx_ctx* ctx, const int32_t* graph_ptr, int32_t b, const float* dpooled, int64_t lddp,
+                         const int32_t* argmax, const float* z, int64_t ldz, int64_t n, int32_t f, const float* mean,
+                         const float* inv, const float* gamma, const float* beta, int act, const float* alpha, int pool_mode,
+                         float* dz, int64_t lddz, float* dgamma, float* dbeta, float* dalpha);
+/* The post-pool half of the torch GCN -- Linear(h->h) . BatchNorm1d . PReLU() -> Linear(h->1) . BatchNorm1d . PReLU() --
+ * with BCEWithLogitsLoss and its backward in ONE launch (one workgroup: every BatchNorm needs all b rows).  Torch layouts:
+ * w3 [h, h] and w4 [1, h] are [out, in]; y = x W^T + b.  BatchNorm: batch mean, biased variance, eps; gamma / beta [h] and
+ * [1]; PReLU: one slope each (alpha3[0], alpha4[0]).  Forward: out[b] (the logits: torch's forward output), probs = sigmoid(out),
+ * and, with y != NULL, loss_acc[0] = sum_g bce(out_g, t_g) / denom, loss_acc[1] = #(out_g > 0 == t_g > 0.5) (OVERWRITTEN,
+ * the layout of gcnx_dense_softmax_cce) where t_g = y[g * y_stride + y_col]; bce(z, t) = max(z, 0) - z t + log1p(exp(-|z|)).
+ * grads != 0 (needs y): dout = (sigmoid(out) - t) / denom through the whole head: dpooled [b, h] and the gradients of
+ * every parameter (dw3 [h, h], db3, dgamma3, dbeta3 [h], dalpha3 [1], dw4 [1, h], db4, dgamma4, dbeta4, dalpha4 [1]).
+ * Limits: b >= 2 (a BatchNorm over one row is undefined; GCNX_ERR_INVALID), 1 <= h <= 256 (GCNX_ERR_UNSUPPORTED above);
+ * scratch: >= gcnx_bce_head_scratch_floats(b, h) floats of device memory, not kept between calls.  Deterministic. */
+typedef struct gcnx_bce_head_args {
+  const float* pooled; int64_t ldp; int32_t b; int32_t h;
+  const float* w3; const float* b3; const float* gamma3; const float* beta3; const float* alpha3;
+  const float* w4; const float* b4; const float* gamma4; const float* beta4; const float* alpha4;
+  float eps; float denom;
+  const float* y; int32_t y_stride; int32_t y_col; int32_t grads;
+  float* out; float* probs; float* loss_acc;
+  float* dpooled; int64_t lddp;
+  float* dw3; float* db3; float* dgamma3; float* dbeta3; float* dalpha3;
+  float* dw4; float* db4; float* dgamma4; float* dbeta4; float* dalpha4;
+  float* scratch; int64_t scratch_floats;
+} gcnx_bce_head_args;
+GCNX_API int64_t gcnx_bce_head_scratch_floats(int32_t b, int32_t h);
+GCNX_API int gcnx_bn_prelu_bce_head(gcnx_ctx* ctx, const gcnx_bce_head_args* args);
 
 /* ---- GeneralGNN options beside gcn.py:320's defaults (csrc/elementwise.hip) ------------------ */
 /* Keras Dropout(rate) in training mode (the Dropout layer of Spektral's MLP and GeneralConv):
