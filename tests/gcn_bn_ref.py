@@ -149,8 +149,9 @@ def bn_act_pool_bwd(dP, argmax, z, gamma, beta, alpha, n_graph_ptr, pos=None, ep
 
 def model(x, a, graph_ptr, p, y=None, denom=None, masks=None, argmax=None):
     """Forward (+ loss, accuracy and every gradient with labels) of the whole model.  a: scipy adjacency (row = target);
-    graph_ptr [B + 1].  Returns a dict: out [B, 1], probs, loss, hits, grads {torch key: array}, and the kink sides it used
-    (m1..m4, argmax)."""
+    graph_ptr [B + 1].  Returns a dict: out [B, 1], probs, loss, hits, grads {torch key: array}, the kink sides it used
+    (m1..m4, argmax), the pooled rows and the second layer's activation y2 [N, H].  The adjacency may be directed: A^ is
+    then not symmetric and the backward pass aggregates with A^T."""
     m = dict(masks or {})
     q = {k: np.asarray(v, np.float64) for k, v in p.items()}
     x = np.asarray(x, np.float64)
@@ -167,7 +168,7 @@ def model(x, a, graph_ptr, p, y=None, denom=None, masks=None, argmax=None):
     P = np.stack([y2[arg[g], cols] if graph_ptr[g + 1] > graph_ptr[g] else np.zeros(y2.shape[1])
                   for g in range(len(graph_ptr) - 1)])
     r = head(P, p, y, denom, m)
-    r.update(m1=p1, m2=p2, argmax=arg, pooled=P)
+    r.update(m1=p1, m2=p2, argmax=arg, pooled=P, y2=y2)
     if y is None:
         return r
     g = r["grads"]

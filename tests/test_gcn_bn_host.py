@@ -11,8 +11,9 @@ from conftest import ROOT
 import gcn_bn_ref as R
 
 
-def _graphs(n_graphs=16, f=16, seed=0, self_loops=True):
-    """Random undirected graphs of 8-64 nodes, as one disjoint batch: x, scipy adjacency (row = target), graph_ptr, y."""
+def _graphs(n_graphs=16, f=16, seed=0, self_loops=True, directed=False):
+    """Random undirected (or directed) graphs of 8-64 nodes, as one disjoint batch: x, scipy adjacency (row = target),
+    graph_ptr, y."""
     import scipy.sparse as sp
     rng = np.random.default_rng(seed)
     sizes = rng.integers(8, 65, n_graphs)
@@ -20,7 +21,7 @@ def _graphs(n_graphs=16, f=16, seed=0, self_loops=True):
     blocks = []
     for s in sizes:
         m = np.triu(rng.random((s, s)) < 0.15, 1)
-        m = m | m.T
+        m = m | (np.tril(rng.random((s, s)) < 0.15, -1) if directed else m.T)
         if self_loops:
             m[np.diag_indices(s)] = rng.random(s) < 0.7        # some rows with a stored loop, some without
         blocks.append(sp.csr_matrix(m.astype(np.float64) * rng.uniform(0.5, 2.0, (s, s))))   # values are ignored
@@ -88,7 +89,20 @@ def _torch_model64(torch, x, a, gp, y, p):
 
 @pytest.mark.parametrize("self_loops", [True, False])
 def test_oracle_matches_torch_autograd(self_loops):
-    x, a, gp, y = _graphs(self_loops=self_loops)
+    _check_oracle_against_torch(*_graphs(self_loops=self_loops))
+
+
+@pytest.mark.parametrize("self_loops", [True, False])
+def test_oracle_matches_torch_autograd_directed(self_loops):
+    """A directed adjacency (as gcnx.GCN.forward's edge_index allows): A^ != A^T, so the oracle's backward must aggregate
+    with the transpose, and PyG's degrees are in-degrees of the targets (the rows)."""
+    x, a, gp, y = _graphs(self_loops=self_loops, directed=True, seed=1)
+    pat = a != 0
+    assert (pat != pat.T).nnz > 0
+    _check_oracle_against_torch(x, a, gp, y)
+
+
+def _check_oracle_against_torch(x, a, gp, y):
     p = R.init_params(16, 64, seed=3)
     out_t, loss_t, g_t = _torch_model(x, a, gp, y, p)
     r = R.model(x, a, gp, p, y)
