@@ -834,4 +834,48 @@ int gcnx_bn_act_pool_bwd(gcnx_ctx* ctx, const int32_t* graph_ptr, int32_t b, con
   return GCNX_OK;
 }
 
+// The two launches of gcnx_bn_act_pool_bwd with caller-held sums, so that a sharded caller can all-reduce them in between
+// (sync-BN), as gcnx_bn_act_bwd_stats / _apply split gcnx_bn_act_bwd.
+int gcnx_bn_act_pool_bwd_stats(gcnx_ctx* ctx, const int32_t* graph_ptr, int32_t b, const float* dpooled, int64_t lddp,
+                               const int32_t* argmax, const float* z, int64_t ldz, int32_t f, const float* mean, const float* inv,
+                               const float* gamma, const float* beta, int act, const float* alpha, int pool_mode, float* sums,
+                               float* dgamma, float* dbeta, float* dalpha) {
+  GCNX_CHECK_CTX(ctx);
+  GCNX_RANGE(ctx, "batch norm + activation + pool backward (sums)");
+  GCNX_REQUIRE(ctx, b >= 0 && f >= 0, "gcnx_bn_act_pool_bwd_stats: negative size");
+  GCNX_REQUIRE(ctx, act >= GCNX_ACT_NONE && act <= GCNX_ACT_PRELU_SHARED, "gcnx_bn_act_pool_bwd_stats: unknown activation %d", act);
+  if (pool_mode != GCNX_POOL_MAX) return gcnx_fail(ctx, GCNX_ERR_UNSUPPORTED, "gcnx_bn_act_pool_bwd_stats: only GCNX_POOL_MAX is served");
+  if (f == 0) return GCNX_OK;
+  GCNX_REQUIRE(ctx, sums != nullptr, "gcnx_bn_act_pool_bwd_stats: sums (device float[3f]) is NULL");
+  GCNX_REQUIRE(ctx, b == 0 || (graph_ptr && dpooled && argmax && z && mean && inv && gamma && beta),
+               "gcnx_bn_act_pool_bwd_stats: NULL pointer");
+  GCNX_REQUIRE(ctx, act < GCNX_ACT_PRELU || alpha, "gcnx_bn_act_pool_bwd_stats: PReLU needs alpha");
+  GCNX_REQUIRE(ctx, b == 0 || (ldz >= f && lddp >= f), "gcnx_bn_act_pool_bwd_stats: leading dimension too small");
+  hipLaunchKernelGGL(bn_act_pool_bwd_stats_kernel, dim3(1), dim3(kPoolThreads), 0, ctx->stream, graph_ptr, b, dpooled, lddp, argmax, z, ldz, f,
+                     mean, inv, gamma, beta, act, alpha, sums, dgamma, dbeta, dalpha);
+  GCNX_LAUNCH_OK(ctx);
+  return GCNX_OK;
+}
+
+int gcnx_bn_act_pool_bwd_apply(gcnx_ctx* ctx, const int32_t* graph_ptr, int32_t b, const float* dpooled, int64_t lddp,
+                               const int32_t* argmax, const float* z, int64_t ldz, int32_t f, const float* mean, const float* inv,
+                               const float* gamma, const float* beta, int act, const float* alpha, int pool_mode, const float* sums,
+                               float count, float* dz, int64_t lddz) {
+  GCNX_CHECK_CTX(ctx);
+  GCNX_RANGE(ctx, "batch norm + activation + pool backward (apply)");
+  GCNX_REQUIRE(ctx, b >= 0 && f >= 0, "gcnx_bn_act_pool_bwd_apply: negative size");
+  GCNX_REQUIRE(ctx, act >= GCNX_ACT_NONE && act <= GCNX_ACT_PRELU_SHARED, "gcnx_bn_act_pool_bwd_apply: unknown activation %d", act);
+  if (pool_mode != GCNX_POOL_MAX) return gcnx_fail(ctx, GCNX_ERR_UNSUPPORTED, "gcnx_bn_act_pool_bwd_apply: only GCNX_POOL_MAX is served");
+  if (b == 0 || f == 0) return GCNX_OK;
+  GCNX_REQUIRE(ctx, graph_ptr && dpooled && argmax && z && mean && inv && gamma && beta && sums && dz,
+               "gcnx_bn_act_pool_bwd_apply: NULL pointer");
+  GCNX_REQUIRE(ctx, act < GCNX_ACT_PRELU || alpha, "gcnx_bn_act_pool_bwd_apply: PReLU needs alpha");
+  GCNX_REQUIRE(ctx, ldz >= f && lddz >= f && lddp >= f, "gcnx_bn_act_pool_bwd_apply: leading dimension too small");
+  GCNX_REQUIRE(ctx, count > 0.f, "gcnx_bn_act_pool_bwd_apply: count must be positive");
+  hipLaunchKernelGGL(bn_act_pool_bwd_apply_kernel, dim3(b, gcnx_cdiv(f, 64)), dim3(kPoolThreads), 0, ctx->stream, graph_ptr, dpooled, lddp,
+                     argmax, z, ldz, f, mean, inv, gamma, beta, act, alpha, sums, count, dz, lddz);
+  GCNX_LAUNCH_OK(ctx);
+  return GCNX_OK;
+}
+
 }  // extern "C"

@@ -113,6 +113,13 @@ SIGNATURES = {
                              _vp, _vp, _vp],
     "gcnx_bce_head_scratch_floats": [_i32, _i32],
     "gcnx_bn_prelu_bce_head": [_vp, _vp],
+    "gcnx_bn_act_pool_bwd_stats": [_vp, _vp, _i32, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _int, _vp, _int, _vp,
+                                   _vp, _vp, _vp],
+    "gcnx_bn_act_pool_bwd_apply": [_vp, _vp, _i32, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _int, _vp, _int, _vp,
+                                   _f32, _vp, _i64],
+    "gcnx_bce_head_phase_scratch_floats": [_i32, _i32],
+    "gcnx_bce_head_phase_red_floats": [_i32],
+    "gcnx_bce_head_phase": [_vp, _vp, _i32, _f32, _vp],
     "gcnx_sgd": [_vp, _vp, _vp, _i64, _f32],
     "gcnx_dropout": [_vp, _vp, _i64, _i64, _i32, _f32, C.c_uint32, C.c_uint32, _vp, _vp, _i64],
     "gcnx_counter_add": [_vp, _vp, C.c_uint32],
@@ -143,6 +150,7 @@ SIGNATURES = {
     "gcnx_allreduce_f32": [_vp, _vp, _vp, _i64, _int],
 }
 _RESTYPE = {"gcnx_last_error": C.c_char_p, "gcnx_dense_bwd_scratch_floats": C.c_int64, "gcnx_bce_head_scratch_floats": C.c_int64,
+            "gcnx_bce_head_phase_scratch_floats": C.c_int64, "gcnx_bce_head_phase_red_floats": C.c_int64,
             "gcnx_gcn_conv_bwd_scratch_floats": C.c_int64, "gcnx_wimage_elems": C.c_int64, "gcnx_gemm_wimage_parts": C.c_int64}
 
 

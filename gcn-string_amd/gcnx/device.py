@@ -1062,6 +1062,27 @@ def bn_act_pool_bwd(ctx, seg, dpooled, argmax, z, mean, inv, gamma, beta, dz, ac
     return dz
 
 
+def bn_act_pool_bwd_stats(ctx, seg, dpooled, argmax, z, mean, inv, gamma, beta, sums, act="prelu_shared", alpha=None, dgamma=None,
+                          dbeta=None, dalpha=None, mode="max"):
+    """First launch of bn_act_pool_bwd (sync-BN): the three LOCAL column sums -> sums[3f] and the local parameter gradients
+    (gcnx_bn_act_pool_bwd_stats)."""
+    f = z.shape[1]
+    ctx._ck(ctx.lib.gcnx_bn_act_pool_bwd_stats(ctx.h, seg.dev.ptr, seg.n_graphs, _p(dpooled), dpooled.ld, argmax.ptr, _p(z), z.ld, f,
+                                               _p(mean), _p(inv), _p(gamma), _p(beta), L.ACTS[act], _p(alpha), L.POOLS[mode],
+                                               _p(sums), _p(dgamma), _p(dbeta), _p(dalpha)))
+
+
+def bn_act_pool_bwd_apply(ctx, seg, dpooled, argmax, z, mean, inv, gamma, beta, sums, count, dz, act="prelu_shared", alpha=None,
+                          mode="max"):
+    """Second launch: dZ over the local rows from the (all-reduced) sums and the global row count
+    (gcnx_bn_act_pool_bwd_apply)."""
+    f = z.shape[1]
+    ctx._ck(ctx.lib.gcnx_bn_act_pool_bwd_apply(ctx.h, seg.dev.ptr, seg.n_graphs, _p(dpooled), dpooled.ld, argmax.ptr, _p(z), z.ld, f,
+                                               _p(mean), _p(inv), _p(gamma), _p(beta), L.ACTS[act], _p(alpha), L.POOLS[mode],
+                                               _p(sums), float(count), _p(dz), dz.ld))
+    return dz
+
+
 def bce_head_scratch_floats(ctx, b, h):
     return int(ctx.lib.gcnx_bce_head_scratch_floats(int(b), int(h)))
 
@@ -1091,3 +1112,24 @@ def bce_head_args(pooled, p, scratch, out, probs, y=None, loss_acc=None, denom=N
 def bn_prelu_bce_head(ctx, args):
     """The post-pool half of the torch GCN in one launch (gcnx_bn_prelu_bce_head); args from bce_head_args."""
     ctx._ck(ctx.lib.gcnx_bn_prelu_bce_head(ctx.h, C.byref(args)))
+
+
+def bce_head_phase_scratch_floats(ctx, b, h):
+    return int(ctx.lib.gcnx_bce_head_phase_scratch_floats(int(b), int(h)))
+
+
+def bce_head_phase_red_floats(ctx, h):
+    return int(ctx.lib.gcnx_bce_head_phase_red_floats(int(h)))
+
+
+def bce_head_phase_slice(phase, h):
+    """(offset, length) of the slice of `red` that phase `phase` of gcnx_bce_head_phase leaves for the all-reduce (include/gcnx.h),
+    None after phase 6."""
+    return ((0, h), (h, h), (2 * h, 1), (2 * h + 1, 1), (2 * h + 2, 2), (2 * h + 4, 2 * h), None)[phase]
+
+
+def bce_head_phase(ctx, args, phase, count, red):
+    """One phase of the head over a graph shard (gcnx_bce_head_phase): args from bce_head_args with the LOCAL rows, count = the
+    global row count, red: device float[bce_head_phase_red_floats(h)] whose phase slice the caller all-reduces before the next
+    phase."""
+    ctx._ck(ctx.lib.gcnx_bce_head_phase(ctx.h, C.byref(args), int(phase), float(count), _p(red)))

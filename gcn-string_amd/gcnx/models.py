@@ -1272,9 +1272,11 @@ class GCN(_GraphRunner):
     def _init(self, ctx, hidden_channels=64, num_classes=1, seed=0, comm=None):
         if int(num_classes) != 1:
             raise NotImplementedError("gcnx.GCN: num_classes must be 1 (one logit + BCEWithLogitsLoss, as the reference)")
-        if comm is not None:
-            raise NotImplementedError("gcnx.GCN: multi-GPU needs sync-BN, which this model does not implement")
+        if comm is not None and not all(hasattr(comm, k) for k in ("rank", "world_size", "allreduce_sum", "allreduce_host")):
+            raise NotImplementedError("gcnx.GCN: comm must have the gcnx.comm.Communicator interface (rank, world_size, "
+                                      "allreduce_sum, allreduce_host)")
         self.ctx = ctx if ctx is not None else D.default_context()
+        self.comm = comm                     # gcnx.comm.Communicator (sync-BN training over graph shards) or None
         self.hidden, self.num_classes = int(hidden_channels), 1
         self.use_graph = False               # eager launches (~20 per step)
         self._bn_pool = os.environ.get("GCNX_BN_POOL", "1") != "0"    # knob, read once
@@ -1383,15 +1385,35 @@ class GCN(_GraphRunner):
             self._op_cache = (batch.uid, a_hat, a_hat.transpose())
         return self._op_cache[1], self._op_cache[2]
 
-    def _ensure(self, batch):
-        if batch.n_graphs < 2 or batch.n < 2:
+    def _multi(self):
+        return self.comm is not None and self.comm.world_size > 1
+
+    def _global_counts(self, batch):
+        """(N, B) of the whole sharded batch: one host all-reduce per batch (cached by its uid).  Every rank raises the same
+        ValueError when a rank holds no graph or the whole batch holds fewer than 2 graphs (or rows)."""
+        if getattr(self, "_counts_uid", None) != batch.uid:
+            tot = self.comm.allreduce_host([batch.n, batch.n_graphs, 1.0 if batch.n_graphs == 0 else 0.0], "sum")
+            self._counts = (float(tot[0]), float(tot[1]), int(tot[2]))
+            self._counts_uid = batch.uid
+        n, b, empty_ranks = self._counts
+        if b < 2 or n < 2:
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size [{int(b)}, {self.hidden}]: "
+                             "BatchNorm1d(track_running_stats=False) needs at least 2 graphs per batch")
+        if empty_ranks:
+            raise ValueError(f"gcnx.GCN: {empty_ranks} rank(s) hold no graph; every rank needs at least one graph of the batch")
+        return n, b
+
+    def _ensure(self, batch, sharded=False):
+        """sharded: a sync-BN training step, where the batch is one rank's shard (the global sizes are checked by
+        _global_counts; the shard may hold a single graph)."""
+        if not sharded and (batch.n_graphs < 2 or batch.n < 2):
             raise ValueError(f"Expected more than 1 value per channel when training, got input size [{batch.n_graphs}, "
                              f"{self.hidden}]: BatchNorm1d(track_running_stats=False) needs at least 2 graphs per batch")
         if not self.built:
             self.build(batch.f)
         if batch.f != self.f_in:
             raise ValueError(f"gcnx.GCN was built for {self.f_in} node features, got {batch.f}")
-        key = (batch.n, batch.n_graphs)
+        key = (batch.n, batch.n_graphs) + (("sync-BN",) if sharded else ())
         if self._bufs is not None and self._bufs["key"] == key:
             return self._bufs
         if getattr(self, "_cap", None) is None:
@@ -1408,6 +1430,9 @@ class GCN(_GraphRunner):
         bufs["out"], bufs["probs"] = v("out", b, 1), v("probs", b, 1)
         nh = D.bce_head_scratch_floats(self.ctx, b, h)
         bufs["head"] = v("head", 1, nh).flat(0, nh)
+        if sharded:
+            nh, nr = D.bce_head_phase_scratch_floats(self.ctx, b, h), D.bce_head_phase_red_floats(self.ctx, h)
+            bufs["phase"], bufs["red"] = v("phase", 1, nh).flat(0, nh), v("red", 1, nr).flat(0, nr)
         self._bufs = bufs
         return bufs
 
@@ -1423,16 +1448,32 @@ class GCN(_GraphRunner):
         D.spmm(ctx, a_hat, h_tmp, bias, out)
         return False
 
-    def _forward(self, batch, bufs, mode, denom=None):
-        """mode: "fwd" (logits only), "loss" (+ loss and hits), "grads" (+ dPooled and the head's gradients)."""
+    def _moments(self, z, mean, inv, bufs, counts):
+        """Training-mode BatchNorm statistics over the rows of z; with counts (sync-BN) over every rank's rows: the two moment
+        passes with their column sums all-reduced and the global row count."""
+        ctx, e = self.ctx, self.EPS
+        if counts is None:
+            D.bn_moments(ctx, z, None, mean, inv, eps=e)
+            return
+        sums, f = bufs["sums"], z.shape[1]
+        D.bn_stats(ctx, z, sums)
+        self.comm.allreduce_sum(sums, 2 * f)
+        D.bn_finalize(ctx, sums, counts[0], mean, inv, eps=e)
+        D.bn_stats(ctx, z, sums, shift=mean)
+        self.comm.allreduce_sum(sums, 2 * f)
+        D.bn_finalize(ctx, sums, counts[0], mean, inv, shift=mean, eps=e)
+
+    def _forward(self, batch, bufs, mode, denom=None, counts=None):
+        """mode: "fwd" (logits only), "loss" (+ loss and hits), "grads" (+ dPooled and the head's gradients).  counts: the
+        global (N, B) of a sync-BN training step over graph shards (None: this batch's own statistics)."""
         ctx, p, e = self.ctx, self.p, self.EPS
         a_hat, _ = self._op(batch)
         self._conv(a_hat, batch.x, p["w1"], p["b1"], bufs["z1"], bufs["h1"])
-        D.bn_moments(ctx, bufs["z1"], None, bufs["m1"], bufs["i1"], eps=e)
+        self._moments(bufs["z1"], bufs["m1"], bufs["i1"], bufs, counts)
         D.bn_act(ctx, bufs["z1"], bufs["m1"], bufs["i1"], p["g1"], p["be1"], bufs["y1"], act="prelu_shared", alpha=p["a1"])
         bufs["s2_ok"] = self._conv(a_hat, bufs["y1"], p["w2"], p["b2"], bufs["z2"], bufs["h1"],
                                    s=bufs["s2"] if mode == "grads" else None)
-        D.bn_moments(ctx, bufs["z2"], None, bufs["m2"], bufs["i2"], eps=e)
+        self._moments(bufs["z2"], bufs["m2"], bufs["i2"], bufs, counts)
         if self._bn_pool:
             D.bn_act_pool(ctx, batch.seg, bufs["z2"], bufs["m2"], bufs["i2"], p["g2"], p["be2"], bufs["pooled"], bufs["arg"],
                           alpha=p["a2"])
@@ -1443,21 +1484,47 @@ class GCN(_GraphRunner):
         if y is None and mode != "fwd":
             raise ValueError("gcnx.GCN: labels are needed for the loss")
         grads = mode == "grads"
-        args = D.bce_head_args(bufs["pooled"], p, bufs["head"], bufs["out"], bufs["probs"], y=y,
+        args = D.bce_head_args(bufs["pooled"], p, bufs["head" if counts is None else "phase"], bufs["out"], bufs["probs"], y=y,
                                loss_acc=self.loss_acc if y is not None else None, denom=denom or batch.n_graphs,
                                g=self.g if grads else None, dpooled=bufs["dpooled"] if grads else None, eps=e)
-        D.bn_prelu_bce_head(ctx, args)
+        if counts is None:
+            D.bn_prelu_bce_head(ctx, args)
+            return
+        # sync-BN (a training step): the head in seven phases, each phase's partial sums all-reduced before the next reads
+        # them; the loss, the hits and the gradients stay local parts until the step's gradient all-reduce
+        for k in range(7):
+            D.bce_head_phase(ctx, args, k, counts[1], bufs["red"])
+            if k < 6:
+                self.comm.allreduce_sum(bufs["red"].flat(*D.bce_head_phase_slice(k, self.hidden)))
 
-    def _backward(self, batch, bufs):
+    def _bn_bwd(self, dy, z, mean, inv, gamma, beta, alpha, dz, g_gamma, g_beta, g_alpha, bufs, counts):
+        """BN·PReLU backward over the rows of z; with counts (sync-BN) the column sums all-reduced between the two halves."""
+        ctx = self.ctx
+        if counts is None:
+            D.bn_act_bwd(ctx, dy, z, mean, inv, gamma, beta, dz, bufs["sums"], act="prelu_shared", alpha=alpha, dgamma=g_gamma,
+                         dbeta=g_beta, dalpha=g_alpha)
+            return
+        D.bn_act_bwd_stats(ctx, dy, z, mean, inv, gamma, beta, bufs["sums"], act="prelu_shared", alpha=alpha, dgamma=g_gamma,
+                           dbeta=g_beta, dalpha=g_alpha)
+        self.comm.allreduce_sum(bufs["sums"], 3 * z.shape[1])
+        D.bn_act_bwd_apply(ctx, dy, z, mean, inv, gamma, beta, bufs["sums"], counts[0], dz, act="prelu_shared", alpha=alpha)
+
+    def _backward(self, batch, bufs, counts=None):
         ctx, p, g = self.ctx, self.p, self.g
         _, a_t = self._op(batch)
-        if self._bn_pool:
+        if self._bn_pool and counts is not None:
+            D.bn_act_pool_bwd_stats(ctx, batch.seg, bufs["dpooled"], bufs["arg"], bufs["z2"], bufs["m2"], bufs["i2"], p["g2"],
+                                    p["be2"], bufs["sums"], alpha=p["a2"], dgamma=g["g2"], dbeta=g["be2"], dalpha=g["a2"])
+            self.comm.allreduce_sum(bufs["sums"], 3 * self.hidden)
+            D.bn_act_pool_bwd_apply(ctx, batch.seg, bufs["dpooled"], bufs["arg"], bufs["z2"], bufs["m2"], bufs["i2"], p["g2"],
+                                    p["be2"], bufs["sums"], counts[0], bufs["dz2"], alpha=p["a2"])
+        elif self._bn_pool:
             D.bn_act_pool_bwd(ctx, batch.seg, bufs["dpooled"], bufs["arg"], bufs["z2"], bufs["m2"], bufs["i2"], p["g2"], p["be2"],
                               bufs["dz2"], alpha=p["a2"], dgamma=g["g2"], dbeta=g["be2"], dalpha=g["a2"])
         else:
             D.segment_pool_bwd(ctx, batch.seg, bufs["dpooled"], bufs["y2"], "max", bufs["arg"])
-            D.bn_act_bwd(ctx, bufs["y2"], bufs["z2"], bufs["m2"], bufs["i2"], p["g2"], p["be2"], bufs["dz2"], bufs["sums"],
-                         act="prelu_shared", alpha=p["a2"], dgamma=g["g2"], dbeta=g["be2"], dalpha=g["a2"])
+            self._bn_bwd(bufs["y2"], bufs["z2"], bufs["m2"], bufs["i2"], p["g2"], p["be2"], p["a2"], bufs["dz2"], g["g2"], g["be2"],
+                         g["a2"], bufs, counts)
         D.act_bias_grad(ctx, bufs["dz2"], None, bufs["dz2"], None, db=g["b2"])       # conv2.bias: column sums of dZ2
         if bufs["s2_ok"]:                                   # forward was (A^ Y1) W2: the association of GCNConv.backward
             D.gemm_dw(ctx, bufs["s2"], bufs["dz2"], g["w2"])                        # dW2 = S2^T dZ2
@@ -1467,8 +1534,8 @@ class GCN(_GraphRunner):
             D.spmm(ctx, a_t, bufs["dz2"], None, bufs["t"])                          # A^T dZ2
             D.gemm_dw(ctx, bufs["y1"], bufs["t"], g["w2"])                          # dW2 = Y1^T (A^T dZ2)
             D.gemm_dx(ctx, bufs["t"], p["w2"], bufs["dy1"])                         # dY1 = (A^T dZ2) W2^T
-        D.bn_act_bwd(ctx, bufs["dy1"], bufs["z1"], bufs["m1"], bufs["i1"], p["g1"], p["be1"], bufs["dz1"], bufs["sums"],
-                     act="prelu_shared", alpha=p["a1"], dgamma=g["g1"], dbeta=g["be1"], dalpha=g["a1"])
+        self._bn_bwd(bufs["dy1"], bufs["z1"], bufs["m1"], bufs["i1"], p["g1"], p["be1"], p["a1"], bufs["dz1"], g["g1"], g["be1"],
+                     g["a1"], bufs, counts)
         D.act_bias_grad(ctx, bufs["dz1"], None, bufs["dz1"], None, db=g["b1"])
         D.spmm(ctx, a_t, bufs["dz1"], None, bufs["t"])
         D.gemm_dw(ctx, batch.x, bufs["t"], g["w1"])
@@ -1494,12 +1561,20 @@ class GCN(_GraphRunner):
         return self((x, a, np.asarray(batch, np.int64)))
 
     def loss_and_grads(self, inputs, target=None, global_batch=None, _lr=None):
-        """Forward + BCE + every gradient (+ the SGD update with ``_lr``).  Returns the device batch."""
+        """Forward + BCE + every gradient (+ the SGD update with ``_lr``).  Returns the device batch.
+
+        With a communicator of world_size > 1 the batch is this rank's shard of whole graphs (gcnx.shard) and the step is
+        torch's SyncBatchNorm step on the whole batch: every BatchNorm uses the statistics of all ranks' rows (BN1 / BN2:
+        the global node count N; BN3 / BN4: the global graph count B), the loss is normalised by ``global_batch`` (default:
+        B), and one all-reduce sums the flat gradient buffer (+ loss / hits) over the ranks before SGD."""
         batch = self._as_batch(inputs, target)
-        bufs = self._ensure(batch)
-        denom = float(global_batch or batch.n_graphs)
-        self._forward(batch, bufs, "grads", denom)
-        self._backward(batch, bufs)
+        counts = self._global_counts(batch) if self._multi() else None
+        bufs = self._ensure(batch, sharded=counts is not None)
+        denom = float(global_batch or (counts[1] if counts else batch.n_graphs))
+        self._forward(batch, bufs, "grads", denom, counts)
+        self._backward(batch, bufs, counts)
+        if counts is not None:
+            self.comm.allreduce_sum(self.flat_g)
         if _lr is not None:
             D.sgd(self.ctx, self.flat_p, self.flat_g.flat(0, self.n_params), _lr)
         self._last_batch = batch
@@ -1509,12 +1584,13 @@ class GCN(_GraphRunner):
         """One optimisation step: loss, gradients, p -= lr * g.  fetch: True -> (loss, acc); False -> None; "stash" ->
         None, metrics kept on the device for collect_metrics()."""
         batch = self.loss_and_grads(inputs, target, global_batch, _lr=float(lr))
+        n_graphs = global_batch or (self._counts[1] if self._multi() else batch.n_graphs)
         if fetch == "stash":
-            self.stash_metrics(global_batch or batch.n_graphs)
+            self.stash_metrics(n_graphs)
             return None
         if not fetch:
             return None
-        return self.fetch_metrics(global_batch or batch.n_graphs)
+        return self.fetch_metrics(n_graphs)
 
     def fetch_metrics(self, n_graphs):
         la = self.loss_acc.numpy()

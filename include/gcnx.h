@@ -56,8 +56,8 @@ typedef enum {
 
 /* PRELU: one slope per feature, alpha[f] (Keras PReLU).  PRELU_SHARED: ONE slope alpha[0] for every feature
  * (torch.nn.PReLU(), num_parameters = 1); its gradient dalpha[0] is the sum over all features.  PRELU_SHARED is served
- * by gcnx_bn_act, gcnx_bn_act_bwd (+ _stats / _apply), gcnx_bn_act_pool(_bwd) and gcnx_bn_prelu_bce_head; every other
- * entry point that takes an activation refuses it (GCNX_ERR_INVALID). */
+ * by gcnx_bn_act, gcnx_bn_act_bwd (+ _stats / _apply), gcnx_bn_act_pool(_bwd, + _stats / _apply) and gcnx_bn_prelu_bce_head
+ * (+ gcnx_bce_head_phase); every other entry point that takes an activation refuses it (GCNX_ERR_INVALID). */
 typedef enum { GCNX_ACT_NONE = 0, GCNX_ACT_RELU = 1, GCNX_ACT_PRELU = 2, GCNX_ACT_PRELU_SHARED = 3 } gcnx_act;
 typedef enum { GCNX_POOL_SUM = 0, GCNX_POOL_AVG = 1, GCNX_POOL_MAX = 2 } gcnx_pool;
 /* GEMM arithmetic: F32 = exact fp32 MFMA (v_mfma_f32_*_f32); BF16 = inputs rounded to bf16,
@@ -454,6 +454,19 @@ GCNX_API int gcnx_bn_act_pool_bwd(gcnx_ctx* ctx, const int32_t* graph_ptr, int32
                          const int32_t* argmax, const float* z, int64_t ldz, int64_t n, int32_t f, const float* mean,
                          const float* inv, const float* gamma, const float* beta, int act, const float* alpha, int pool_mode,
                          float* dz, int64_t lddz, float* dgamma, float* dbeta, float* dalpha);
+/* The two launches of gcnx_bn_act_pool_bwd with caller-held sums, for sync-BN over graph shards: _stats writes the three
+ * LOCAL column sums (sum dzb, sum dzb * xhat, sum dy * min(zb, 0)), formed from the b * f argmax entries alone, to
+ * sums[3f] (device memory) and the local parts of dgamma / dbeta / dalpha ([1] for PRELU_SHARED; each may be NULL);
+ * the caller all-reduces sums; _apply writes dZ over every local row with the reduced sums and the GLOBAL row count
+ * `count`.  _stats + _apply with count = n make the same launches as gcnx_bn_act_pool_bwd, with the same bits. */
+GCNX_API int gcnx_bn_act_pool_bwd_stats(gcnx_ctx* ctx, const int32_t* graph_ptr, int32_t b, const float* dpooled, int64_t lddp,
+                         const int32_t* argmax, const float* z, int64_t ldz, int32_t f, const float* mean, const float* inv,
+                         const float* gamma, const float* beta, int act, const float* alpha, int pool_mode, float* sums,
+                         float* dgamma, float* dbeta, float* dalpha);
+GCNX_API int gcnx_bn_act_pool_bwd_apply(gcnx_ctx* ctx, const int32_t* graph_ptr, int32_t b, const float* dpooled, int64_t lddp,
+                         const int32_t* argmax, const float* z, int64_t ldz, int32_t f, const float* mean, const float* inv,
+                         const float* gamma, const float* beta, int act, const float* alpha, int pool_mode, const float* sums,
+                         float count, float* dz, int64_t lddz);
 /* The post-pool half of the torch GCN -- Linear(h->h) . BatchNorm1d . PReLU() -> Linear(h->1) . BatchNorm1d . PReLU() --
  * with BCEWithLogitsLoss and its backward in ONE launch (one workgroup: every BatchNorm needs all b rows).  Torch layouts:
  * w3 [h, h] and w4 [1, h] are [out, in]; y = x W^T + b.  BatchNorm: batch mean, biased variance, eps; gamma / beta [h] and
@@ -478,6 +491,25 @@ typedef struct gcnx_bce_head_args {
 } gcnx_bce_head_args;
 GCNX_API int64_t gcnx_bce_head_scratch_floats(int32_t b, int32_t h);
 GCNX_API int gcnx_bn_prelu_bce_head(gcnx_ctx* ctx, const gcnx_bce_head_args* args);
+/* The same head in seven phases, for a batch sharded by graph over ranks (sync-BN: every BatchNorm uses the statistics
+ * of the whole batch).  args is as above with args->b the LOCAL row count (>= 1); count is the GLOBAL row count (>= 2,
+ * else GCNX_ERR_INVALID).  Phase k writes local partial sums to its slice of red (device float[gcnx_bce_head_phase_red_floats(h)]);
+ * the caller all-reduces that slice and phase k + 1 reads it.  red's slices (offsets in floats):
+ *   phase 0  z3 = P W3^T + b3; sum z3                                   -> red[0, h)
+ *   phase 1  mean3; sum (z3 - mean3)^2                                   -> red[h, 2h)
+ *   phase 2  inv3, y3 = PReLU3(BN3(z3)), z4 = y3 W4^T + b4; sum z4       -> red[2h]
+ *   phase 3  mean4; sum (z4 - mean4)^2                                   -> red[2h + 1]
+ *   phase 4  inv4, out, probs; with y: loss_acc (local part); with grads:
+ *            sum dzb4, sum dzb4 xhat4 and the local dbeta4 / dgamma4 / dalpha4   -> red[2h + 2, 2h + 4)
+ *   phase 5  dz4, db4, dw4; sum dzb3, sum dzb3 xhat3 and the local dbeta3 / dgamma3 / dalpha3 -> red[2h + 4, 4h + 4)
+ *   phase 6  dZ3, db3, dpooled = dZ3 W3, dw3                              (nothing to reduce)
+ * Phases 0-3 are the forward, 4 the loss; 5 and 6 need grads.  Every gradient and both loss_acc floats are the LOCAL
+ * parts, OVERWRITTEN: summed over the ranks they give the whole batch's (loss_acc[0] is sum bce / denom).  scratch: >=
+ * gcnx_bce_head_phase_scratch_floats(b, h) floats, kept between the phases; red too.  Each reduction has a fixed order.
+ * One workgroup per phase.  With one shard and count = b the phases give the one-launch head's numbers. */
+GCNX_API int64_t gcnx_bce_head_phase_scratch_floats(int32_t b, int32_t h);
+GCNX_API int64_t gcnx_bce_head_phase_red_floats(int32_t h);
+GCNX_API int gcnx_bce_head_phase(gcnx_ctx* ctx, const gcnx_bce_head_args* args, int32_t phase, float count, float* red);
 
 /* ---- GeneralGNN options beside gcn.py:320's defaults (csrc/elementwise.hip) ------------------ */
 /* Keras Dropout(rate) in training mode (the Dropout layer of Spektral's MLP and GeneralConv):
