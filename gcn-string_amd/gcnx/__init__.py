@@ -7,11 +7,11 @@ No PyTorch, no TensorFlow, no CPU fallback.
 """
 from . import _lib
 from .io import best_epoch, load_weights_npz, save_to_npz
-from .loader import Dataset, DisjointLoader, Graph, ListDataset, NetworkxDataset, SparseTensor, format_graph, from_networkx
+from .loader import Dataset, DisjointLoader, Graph, ListDataset, NetworkxDataset, SparseTensor, entry_edge_features, format_graph, from_networkx
 from .train import PiecewiseConstantDecay, auc, binary_acc, fit, roc_curve
 
-__all__ = ["Dataset", "DisjointLoader", "Graph", "ListDataset", "NetworkxDataset", "from_networkx", "format_graph", "SparseTensor", "Context", "default_context", "GCNConv", "GeneralConv",
-           "GlobalSumPool", "GlobalAvgPool", "GlobalMaxPool", "Dense", "BatchNorm1d", "PReLU", "GCN2", "GCN", "GeneralGNN", "DeviceBatch",
+__all__ = ["Dataset", "DisjointLoader", "Graph", "ListDataset", "NetworkxDataset", "from_networkx", "entry_edge_features", "format_graph", "SparseTensor", "Context", "default_context", "GCNConv", "GeneralConv",
+           "ECCConv", "GlobalSumPool", "GlobalAvgPool", "GlobalMaxPool", "Dense", "BatchNorm1d", "PReLU", "GCN2", "GCN", "GeneralGNN", "ECCNet", "DeviceBatch",
            "save_to_npz", "load_weights_npz", "best_epoch", "DeviceDataset", "DeviceDisjointLoader",
            "PiecewiseConstantDecay", "fit", "roc_curve", "auc", "binary_acc"]
 
@@ -20,13 +20,13 @@ def __getattr__(name):  # device-side names load libgcnx lazily, host-only use n
     if name in ("Context", "default_context", "DeviceArray", "DeviceCSR", "Segments"):
         from . import device
         return getattr(device, name)
-    if name in ("GCNConv", "GeneralConv", "GlobalSumPool", "GlobalAvgPool", "GlobalMaxPool", "Dense", "BatchNorm1d", "PReLU"):
+    if name in ("GCNConv", "GeneralConv", "ECCConv", "GlobalSumPool", "GlobalAvgPool", "GlobalMaxPool", "Dense", "BatchNorm1d", "PReLU"):
         from . import layers
         return getattr(layers, name)
     if name in ("DeviceDataset", "DeviceDisjointLoader", "collate_on_device"):
         from . import device_loader
         return getattr(device_loader, name)
-    if name in ("GCN2", "GCN", "GeneralGNN", "DeviceBatch", "evaluate"):
+    if name in ("GCN2", "GCN", "GeneralGNN", "ECCNet", "DeviceBatch", "evaluate"):
         from . import models
         return getattr(models, name)
     raise AttributeError(name)

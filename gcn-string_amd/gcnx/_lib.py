@@ -67,6 +67,9 @@ SIGNATURES = {
     "gcnx_set_tuning": [_vp, C.c_char_p, _int],
     "gcnx_csr_inspect": [_vp, _vp, _vp, _vp, _i32, _vp, _i32, C.POINTER(C.c_int)],
     "gcnx_csr_transpose": [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp],
+    "gcnx_csr_transpose_perm": [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp],
+    "gcnx_ecc_expand": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i64, _i32, _vp, _i64, _i32, _i32, _int],
+    "gcnx_ecc_bwd": [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _i32, _i32],
     "gcnx_gemm": [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _int, _int, _vp],
     "gcnx_spmm_plan_create": [_vp, _vp, _i32, C.POINTER(_vp)],
     "gcnx_spmm_plan_destroy": [_vp, _vp],

@@ -391,6 +391,18 @@ class DeviceCSR:
             self._t = DeviceCSR(ctx, self.n, self.nnz, rp, ci, v, self.block_ptr, self.n_blocks, False, self.max_block_rows)
         return self._t
 
+    def transpose_perm(self):
+        """(rowptr_t, colidx_t, perm_t) of the transposed pattern, perm_t[p] = entry of THIS CSR that became entry p of the
+        transpose (gcnx_csr_transpose_perm): the destination-side view ECCConv's forward gathers by, with the row of the
+        per-entry features that belongs to every entry.  Built once per operator, also for a symmetric one (the two
+        directions of an edge are different entries with rows of their own)."""
+        if getattr(self, "_tperm", None) is None:
+            ctx = self.ctx
+            rp, ci, pm = ctx.empty(self.n + 1, np.int32), ctx.empty(max(self.nnz, 1), np.int32), ctx.empty(max(self.nnz, 1), np.int32)
+            ctx._ck(ctx.lib.gcnx_csr_transpose_perm(ctx.h, self.rowptr.ptr, self.colidx.ptr, self.n, self.nnz, rp.ptr, ci.ptr, pm.ptr))
+            self._tperm = (rp, ci, pm)
+        return self._tperm
+
     def row_mean(self):
         """Same structure with 1 / (entries of the row) on every entry: GeneralConv(aggregate="mean") -- the mean over a row's
         messages (tf.math.unsorted_segment_mean); a row without entries aggregates to 0.  Built once per operator."""
@@ -602,6 +614,31 @@ def spmm(ctx, a, h, bias, out, act=None):
     ctx._ck(ctx.lib.gcnx_spmm_csr(ctx.h, a.rowptr.ptr, a.colidx.ptr, _p(a.vals), _p(h), h.ld, _p(bias), _p(out),
                                   out.ld, n, f, L.ACTS[act], a.plan))
     return out
+
+
+def ecc_expand(ctx, a, u, x, scat, root=False, identity_perm=False):
+    """scat[:, :C*F] = the edge-conditioned aggregation of x over the stored entries of ``a`` (messages from an entry's row to
+    its column; u [nnz, S'] = the entry's channels, None = no channel but the constant one), C = S' + 1; root: x copied
+    into the next F columns (gcnx_ecc_expand).  identity_perm: ``a`` IS the destination-side CSR and u is in its order."""
+    n, f = x.shape
+    sp = u.shape[1] if u is not None else 0
+    assert a.n == n and scat.shape[0] == n and scat.shape[1] >= (sp + 1 + bool(root)) * f and (u is None or u.shape[0] == a.nnz)
+    rp, ci, pm = (a.rowptr, a.colidx, None) if identity_perm else a.transpose_perm()
+    ctx._ck(ctx.lib.gcnx_ecc_expand(ctx.h, rp.ptr, ci.ptr, pm.ptr if pm is not None else None, _p(u), u.ld if u is not None else 0, sp,
+                                    _p(x), x.ld, f, _p(scat), scat.ld, n, a.nnz, 1 if root else 0))
+    return scat
+
+
+def ecc_bwd(ctx, a, u, x, dscat, dx_root=None, dx=None, du=None):
+    """dx = dx_root + the gradient of ecc_expand wrt x, du = its gradient wrt u, in one launch (gcnx_ecc_bwd); either may be
+    None.  dscat: [N, C*F] (a column view of the GEMM's dX is fine)."""
+    n, f = a.n, (x.shape[1] if x is not None else dx.shape[1])
+    sp = u.shape[1] if u is not None else 0
+    assert dscat.shape == (n, (sp + 1) * f) and (du is None or du.shape == (a.nnz, sp))
+    ctx._ck(ctx.lib.gcnx_ecc_bwd(ctx.h, a.rowptr.ptr, a.colidx.ptr, _p(u), u.ld if u is not None else 0, sp, _p(x),
+                                 x.ld if x is not None else 0, _p(dscat), dscat.ld, _p(dx_root), dx_root.ld if dx_root is not None else 0,
+                                 f, _p(dx), dx.ld if dx is not None else 0, _p(du), du.ld if du is not None else 0, n, a.nnz))
+    return dx, du
 
 
 def segment_pool(ctx, seg, x, pooled, mode="sum", argmax=None):

@@ -20,12 +20,15 @@ from .models import DeviceBatch
 
 
 class DeviceDataset:
-    """All graphs of a ``Dataset`` resident in HBM."""
+    """All graphs of a ``Dataset`` resident in HBM.  Edge features are not carried: graphs built with ``Graph(e=...)`` are
+    accepted and their ``e`` is ignored (gcnx_collate gathers x, the adjacency and the labels only), so the batches of a
+    DeviceDisjointLoader serve GCN2 / GeneralGNN / GCN; gcnx.ECCNet takes host DisjointLoader batches."""
 
     def __init__(self, ctx, dataset, normalize=None, weighted=True, symmetric=None):
         self.ctx = ctx
         graphs = [dataset[i] for i in range(len(dataset))]
-        (x, a, i), y = collate_disjoint(graphs)
+        inputs, y = collate_disjoint(graphs)
+        x, a, i = inputs[0], inputs[1], inputs[-1]          # ((x, a, e, i), y) when the graphs carry e: ignored here
         sizes = np.array([g.n_nodes for g in graphs], np.int64)
         self.n_graphs = len(graphs)
         self.node_ptr_host = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)

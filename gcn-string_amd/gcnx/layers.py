@@ -438,3 +438,210 @@ class PReLU(Layer):
         D.bn_act_bwd(self.ctx, dy, x, zero, one, one, zero, dx, self._buf("sums", (3 * x.shape[1],)), act="prelu_shared",
                      alpha=self.params["weight"], training=False, dalpha=self.grads["weight"])
         return dx
+
+
+# ---- ECCConv: Keras shapes <-> the stacked weight of the factorised form (host arrays only) ------------------------------------
+def ecc_weight_names(kernel_network=None, root=True, use_bias=True):
+    """The Keras variable names of an ECCConv in the order get_weights() lists them: the kernel network's hidden Dense layers
+    "FGN_<m>_kernel" / "FGN_<m>_bias", its output Dense "FGN_out_kernel" / "FGN_out_bias", then "root_kernel" and "bias"."""
+    names = []
+    for m in range(len(kernel_network or ())):
+        names += [f"FGN_{m}_kernel", f"FGN_{m}_bias"]
+    names += ["FGN_out_kernel", "FGN_out_bias"]
+    if root:
+        names.append("root_kernel")
+    if use_bias:
+        names.append("bias")
+    return names
+
+
+def ecc_pack_weights(weights, f_in, channels, root=True):
+    """{Keras name: array} -> the arrays libgcnx holds: "wstack" [(S' + 1 (+ 1 with root)) * F, F_out] =
+    [W_0; ..; W_{S'-1}; B; W_root] with W_c = reshape(FGN_out_kernel[c], (F, F_out)), B = reshape(FGN_out_bias, (F, F_out));
+    every other entry ("bias", "FGN_<m>_kernel", "FGN_<m>_bias") unchanged."""
+    w = {k: np.asarray(v, np.float32) for k, v in weights.items()}
+    wk, bk = w.pop("FGN_out_kernel"), w.pop("FGN_out_bias")
+    f, fo = int(f_in), int(channels)
+    if wk.ndim != 2 or wk.shape[1] != f * fo or bk.shape != (f * fo,):
+        raise ValueError(f"FGN_out kernel {wk.shape} / bias {bk.shape}: expected [S', {f * fo}] and [{f * fo}]")
+    parts = [wk.reshape(wk.shape[0] * f, fo), bk.reshape(f, fo)]
+    rk = w.pop("root_kernel", None)
+    if root:
+        if rk is None or rk.shape != (f, fo):
+            raise ValueError(f"root_kernel: expected [{f}, {fo}]")
+        parts.append(rk)
+    elif rk is not None:
+        raise ValueError("root_kernel given for a layer built with root=False")
+    w["wstack"] = np.ascontiguousarray(np.concatenate(parts, 0))
+    return w
+
+
+def ecc_unpack_weights(params, f_in, channels, root=True):
+    """Inverse of ecc_pack_weights: the arrays libgcnx holds -> {Keras name: array in its Keras shape}."""
+    w = {k: np.asarray(v) for k, v in params.items()}
+    ws = w.pop("wstack")
+    f, fo = int(f_in), int(channels)
+    sp = ws.shape[0] // f - 1 - (1 if root else 0)
+    if ws.shape != ((sp + 1 + (1 if root else 0)) * f, fo) or sp < 0:
+        raise ValueError(f"wstack {ws.shape} does not fit F = {f}, F_out = {fo}, root = {root}")
+    w["FGN_out_kernel"] = ws[:sp * f].reshape(sp, f * fo).copy()
+    w["FGN_out_bias"] = ws[sp * f:(sp + 1) * f].reshape(f * fo).copy()
+    if root:
+        w["root_kernel"] = ws[(sp + 1) * f:].copy()
+    return w
+
+
+class ECCConv(Layer):
+    """spektral.layers.ECCConv (edge-conditioned convolution) in single / disjoint mode, called as ``layer([x, a, e])``:
+
+        u_0 = e,  u_m = relu(u_{m-1} V_m + v_m)  per hidden width of kernel_network;  K_k = reshape(u_M[k] Wk + bk, (F, F_out))
+        out[c_k] += x[r_k] K_k  over the stored entries k = (r_k, c_k) of a;   out = activation(out + x W_root + bias)
+
+    ``a``: DeviceCSR of the batch (values ignored); ``e``: DeviceArray [nnz, S], row k belonging to stored entry k (row-major).
+    Evaluated in the factorised form of DESIGN.md ("ECCConv"): gcnx_ecc_expand writes [Scat | x], one gcnx_gemm with the
+    stacked weight gives the output; the per-entry kernels are never formed.  ``backward(dy, need_dx=True)`` returns dx and
+    leaves the gradients in ``grads`` ("wstack" holds those of FGN_out's kernel, its bias and root_kernel in the stacked
+    layout; ``gradients()`` converts to the Keras shapes).  Activation None / "relu"; Keras default initialisers (glorot
+    uniform on every kernel in its Keras shape, zero biases).  S' + 1 <= 17 (S' = the last hidden width, or S).
+
+    ``get_weights(as_dict=True)`` / ``set_weights(dict)``: keyed by the Keras names (ecc_weight_names) -- the primary form.
+    The list form follows ecc_weight_names' order; Keras' own order was not confirmed against a live layer (PARITY UNPINNED)."""
+
+    MAX_C = 17
+
+    def __init__(self, channels, kernel_network=None, root=True, activation=None, use_bias=True, **kw):
+        super().__init__(**kw)
+        if activation not in (None, "linear", "relu"):
+            raise NotImplementedError(f"ECCConv activation {activation!r}: only None / 'relu'")
+        if int(channels) < 1:
+            raise ValueError(f"ECCConv(channels={channels!r}): a positive width")
+        kn = list(kernel_network) if kernel_network is not None else []
+        if any((not isinstance(w, (int, np.integer))) or int(w) < 1 for w in kn):
+            raise ValueError(f"ECCConv(kernel_network={kernel_network!r}): a list of positive hidden widths (or None)")
+        if kn and int(kn[-1]) + 1 > self.MAX_C:
+            raise NotImplementedError(f"ECCConv: last kernel_network width {kn[-1]} + 1 exceeds C = {self.MAX_C}")
+        self.channels, self.kernel_network, self.root = int(channels), [int(w) for w in kn], bool(root)
+        self.activation = None if activation == "linear" else activation
+        self.use_bias = bool(use_bias)
+        self.edge_dim = None
+
+    @property
+    def sp(self):
+        """S': channels per entry that reach the aggregation."""
+        return self.kernel_network[-1] if self.kernel_network else self.edge_dim
+
+    def _param_spec(self, in_dim):
+        if self.edge_dim is None:
+            raise ValueError("ECCConv: the edge feature width is not known yet (set edge_dim, or call the layer)")
+        if self.sp + 1 > self.MAX_C:
+            raise NotImplementedError(f"ECCConv: {self.sp} edge channels + 1 exceed C = {self.MAX_C}; reduce them with a kernel_network")
+        f, fo, spec, w_in = int(in_dim), self.channels, [], self.edge_dim
+        for m, w in enumerate(self.kernel_network):
+            spec += [(f"FGN_{m}_kernel", (w_in, w), glorot_uniform(self._rng, w_in, w)), (f"FGN_{m}_bias", (w,), np.zeros(w, np.float32))]
+            w_in = w
+        keras = {"FGN_out_kernel": glorot_uniform(self._rng, w_in, f * fo), "FGN_out_bias": np.zeros(f * fo, np.float32)}
+        if self.root:
+            keras["root_kernel"] = glorot_uniform(self._rng, f, fo)
+        ws = ecc_pack_weights(keras, f, fo, self.root)["wstack"]
+        spec.append(("wstack", ws.shape, ws))
+        if self.use_bias:
+            spec.append(("bias", (fo,), np.zeros(fo, np.float32)))
+        return spec
+
+    def build(self, ctx, in_dim, p_store=None, g_store=None, offset=0):
+        """Layer.build with every parameter on a 16-byte boundary (the padding floats have zero gradients, so a single SGD
+        launch over a model's flat buffer leaves them at zero)."""
+        self.ctx = ctx
+        spec = self._param_spec(in_dim)
+        pad = lambda k: -(-int(k) // 4) * 4
+        total = sum(pad(np.prod(s)) for _, s, _ in spec)
+        if p_store is None:
+            p_store, g_store, offset = ctx.zeros(max(total, 1)), ctx.zeros(max(total, 1)), 0
+        off = offset
+        for name, shape, init in spec:
+            k = int(np.prod(shape))
+            self.params[name] = p_store.flat(off, k, shape)
+            self.grads[name] = g_store.flat(off, k, shape)
+            self.params[name].copy_from_host(init)
+            off += pad(k)
+        self.in_dim, self.built = int(in_dim), True
+        return off
+
+    def n_params(self, in_dim):
+        return sum(-(-int(np.prod(s)) // 4) * 4 for _, s, _ in self._param_spec(in_dim))
+
+    # ---- weights in the Keras shapes ----------------------------------------------------------------------------------
+    def get_weights(self, as_dict=False):
+        d = ecc_unpack_weights({k: v.numpy() for k, v in self.params.items()}, self.in_dim, self.channels, self.root)
+        return d if as_dict else [d[k] for k in ecc_weight_names(self.kernel_network, self.root, self.use_bias)]
+
+    def set_weights(self, weights):
+        names = ecc_weight_names(self.kernel_network, self.root, self.use_bias)
+        if not isinstance(weights, dict):
+            weights = dict(zip(names, weights))
+        missing = [k for k in names if k not in weights]
+        if missing:
+            raise KeyError(f"ECCConv.set_weights: missing {missing}")
+        packed = ecc_pack_weights({k: weights[k] for k in names}, self.in_dim, self.channels, self.root)
+        for k, v in packed.items():
+            if v.shape != self.params[k].shape:
+                raise ValueError(f"ECCConv.set_weights: {k} has shape {v.shape}, the layer holds {self.params[k].shape}")
+            self.params[k].copy_from_host(v)
+
+    def gradients(self):
+        """{Keras name: gradient of the last backward()} in the Keras shapes."""
+        return ecc_unpack_weights({k: v.numpy() for k, v in self.grads.items()}, self.in_dim, self.channels, self.root)
+
+    # ---- forward / backward -------------------------------------------------------------------------------------------
+    def call(self, inputs, out=None):
+        x, a, e = inputs
+        if e is None:
+            raise ValueError("ECCConv needs edge features: layer([x, a, e])")
+        if not self.built:
+            self.edge_dim = int(e.shape[1])
+            self.build(x.ctx, x.shape[1])
+        ctx, n, f = self.ctx, x.shape[0], x.shape[1]
+        if e.shape != (a.nnz, self.edge_dim):
+            raise ValueError(f"ECCConv: e has shape {e.shape}, expected ({a.nnz}, {self.edge_dim}): one row per stored entry of a")
+        us = [e]
+        for m, w in enumerate(self.kernel_network):
+            u = self._buf(f"u{m}", (a.nnz, w))
+            D.gemm(ctx, us[-1], self.params[f"FGN_{m}_kernel"], self.params[f"FGN_{m}_bias"], u, act="relu")
+            us.append(u)
+        cols = (self.sp + 1 + (1 if self.root else 0)) * f
+        sx = self._buf("sx", (n, cols))
+        D.ecc_expand(ctx, a, us[-1], x, sx, root=self.root)
+        y = out if out is not None else self._buf("y", (n, self.channels))
+        D.gemm(ctx, sx, self.params["wstack"], self.params.get("bias"), y, act=self.activation)
+        self._saved = (x, a, us, sx, y)
+        return y
+
+    def backward(self, dy, need_dx=True):
+        x, a, us, sx, y = self._saved
+        ctx, n, f, fo, sp = self.ctx, x.shape[0], x.shape[1], self.channels, self.sp
+        dz = dy
+        if self.activation is not None:
+            dz = self._buf("dz", (n, fo))
+            D.act_bias_grad(ctx, dy, y, dz, self.activation, db=self.grads.get("bias"))
+        elif self.use_bias:
+            D.act_bias_grad(ctx, dy, None, dy, None, db=self.grads["bias"])         # a pure column sum
+        D.gemm_dw(ctx, sx, dz, self.grads["wstack"])
+        need_du = bool(self.kernel_network)
+        if not need_dx and not need_du:
+            return None
+        cf = (sp + 1) * f
+        take_root = self.root and need_dx
+        rows = cf + (f if take_root else 0)
+        g = self._buf("g", (n, rows))                                               # [dScat | dx_root] = dZ Wstack^T
+        D.gemm_dx(ctx, dz, self.params["wstack"].flat(0, rows * fo, (rows, fo)), g)
+        dx = self._buf("dx", (n, f)) if need_dx else None
+        du = self._buf("du", (a.nnz, sp)) if need_du else None
+        D.ecc_bwd(ctx, a, us[-1], x, g.cols(0, cf), g.cols(cf, cf + f) if take_root else None, dx, du)
+        for m in reversed(range(len(self.kernel_network))):
+            dzu = self._buf(f"dzu{m}", us[m + 1].shape)
+            D.act_bias_grad(ctx, du, us[m + 1], dzu, "relu", db=self.grads[f"FGN_{m}_bias"])
+            D.gemm_dw(ctx, us[m], dzu, self.grads[f"FGN_{m}_kernel"])
+            if m > 0:
+                du = self._buf(f"du{m - 1}", us[m].shape)
+                D.gemm_dx(ctx, dzu, self.params[f"FGN_{m}_kernel"], du)
+        return dx

@@ -120,7 +120,9 @@ def from_networkx(graph, label, use_edge_data=False, feature_name="x"):
       x  np.vstack of every node's ``feature_name`` attribute in node order (float64 as stored);
       y  np.array(label) (the one-hot pair of gcn.py:259,262);
       e  the edge attributes as an [n_edges, n_attrs] array, attached only with use_edge_data (gcn.py:173-180 computes
-         them either way and drops them by default)."""
+         them either way and drops them by default).  use_edge_data=True: one row per UNDIRECTED edge in graph.edges
+         order, as the reference builds it; use_edge_data="entries": entry_edge_features -- one row per stored entry of
+         ``a``, what Spektral's edge-feature layers (and gcnx.layers.ECCConv) expect."""
     import networkx as nx
     import scipy.sparse as sp
     g = format_graph(graph)
@@ -130,10 +132,43 @@ def from_networkx(graph, label, use_edge_data=False, feature_name="x"):
     y = np.array(label)
     if not use_edge_data:
         return Graph(x=x, a=a, y=y)
-    attrs = [d for _, _, d in g.edges(data=True)]
+    if isinstance(use_edge_data, str):
+        if use_edge_data != "entries":
+            raise ValueError(f"use_edge_data={use_edge_data!r}: False, True (one row per edge) or 'entries' (one per stored entry)")
+        return Graph(x=x, a=a, y=y, e=entry_edge_features(g, a))
+    attrs =[d for _, _, d in g.edges(data=True)]
     names = list(attrs[0].keys()) if attrs else []
     e = np.array([[d[k] for d in attrs] for k in names]).T if names else np.zeros((len(attrs), 0))
     return Graph(x=x, a=a, y=y, e=e)
+
+
+def entry_edge_features(graph, a, names=None):
+    """Edge attributes of ``graph`` (integer node labels 0..n-1 in the order of ``a``'s rows: format_graph) as one row per
+    STORED ENTRY of ``a`` in row-major order: [nnz(a), S], row k = the attributes ``names`` of the edge {r_k, c_k}.  Both
+    directions of an undirected edge get the same row; an attribute an edge does not carry counts as 0 (the builder puts
+    ``dca`` on the bridges and ``proximity`` on the contacts, gcn_utills.py:379-443, and zero-fills the other).  names:
+    default the first edge's keys -- for the reference's pickles ``dca``, ``proximity``.  Explicitly stored zeros of ``a``
+    are not entries (sp.find drops them, as the loader does)."""
+    import scipy.sparse as sp
+    c = sp.csr_matrix(a)
+    if not c.has_sorted_indices:
+        c = c.sorted_indices()
+    rows = np.repeat(np.arange(c.shape[0], dtype=np.int64), np.diff(c.indptr))
+    cols = c.indices.astype(np.int64)
+    keep = c.data != 0
+    rows, cols = rows[keep], cols[keep]
+    if names is None:
+        first = next(iter(graph.edges(data=True)), None)
+        names = list(first[2].keys()) if first is not None else []
+    names = list(names)
+    e = np.zeros((rows.size, len(names)), np.float64)
+    for k, (r, q) in enumerate(zip(rows.tolist(), cols.tolist())):
+        d = graph.get_edge_data(r, q)
+        if d is None:
+            raise ValueError(f"entry ({r}, {q}) of the adjacency is not an edge of the graph")
+        for j, name in enumerate(names):
+            e[k, j] = d.get(name, 0.0)
+    return e
 
 
 class NetworkxDataset(Dataset):
@@ -205,8 +240,9 @@ def collate_disjoint(graphs, node_level=False):
     """DisjointLoader.collate: the same ((x, a, i), y) as to_disjoint + sp_matrix_to_sp_tensor, built directly.
     Graphs that carry edge features (Graph(e=...): the reference computes them either way and attaches them only with
     use_edge_data, gcn.py:173-180) yield ((x, a, e, i), y) as Spektral does -- e = vstack of the graphs' [n_edges, S]
-    arrays, a dense [n, n, S] array reduced to the adjacency's stored entries first (to_disjoint).  The models of this
-    package take (x, a, i), like spektral.models.GeneralGNN: a batch with e is for the caller's own layers."""
+    arrays, a dense [n, n, S] array reduced to the adjacency's stored entries first (to_disjoint).  gcnx.ECCNet /
+    gcnx.layers.ECCConv read e (one row per stored entry of a: from_networkx(use_edge_data="entries")); the other models of
+    this package take (x, a, i), like spektral.models.GeneralGNN, and ignore e when it is there."""
     x_list = [g.x for g in graphs]
     x = np.vstack(x_list)
     n_nodes = np.array([x_.shape[0] for x_ in x_list], dtype=np.int64)

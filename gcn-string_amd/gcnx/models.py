@@ -26,12 +26,12 @@ from .loader import SparseTensor
 
 class DeviceBatch:
     """A DisjointLoader batch resident in HBM: x [N,F] fp32, adjacency CSR, graph segments,
-    one-hot labels y [B,C] fp32."""
+    one-hot labels y [B,C] fp32; optionally edge features e [nnz, S] fp32, row k belonging to stored entry k of the CSR."""
 
     _next_uid = 0
 
-    def __init__(self, ctx, x, a, seg, y=None):
-        self.ctx, self.x, self.a, self.seg, self.y = ctx, x, a, seg, y
+    def __init__(self, ctx, x, a, seg, y=None, e=None):
+        self.ctx, self.x, self.a, self.seg, self.y, self.e = ctx, x, a, seg, y, e
         DeviceBatch._next_uid += 1
         self.uid = DeviceBatch._next_uid  # never reused (unlike id()): keys captured graphs
         self.n, self.f = x.shape
@@ -39,10 +39,17 @@ class DeviceBatch:
 
     @classmethod
     def from_host(cls, ctx, inputs, y=None, normalize=None, weighted=True, symmetric=None):
-        """inputs = (x, a, i) as yielded by DisjointLoader.  ``a`` is a SparseTensor (COO) or a
+        """inputs = (x, a, i) or (x, a, e, i) as yielded by DisjointLoader.  ``a`` is a SparseTensor (COO) or a
         scipy sparse matrix.  normalize='spektral'|'pyg' applies gcn_filter on the device (the
-        CSR must then hold every diagonal entry, as the reference's self-looped graphs do)."""
-        x, a, i = inputs
+        CSR must then hold every diagonal entry, as the reference's self-looped graphs do).
+        e [nnz, S]: one row per stored entry of ``a`` in row-major order (gcnx_coo_to_csr keeps that order, so CSR entry k
+        is COO entry k); kept as ``batch.e``.  Any other row count -- one row per undirected edge, or rows for explicitly
+        stored zeros, which the COO build drops -- raises ValueError."""
+        e = None
+        if len(inputs) == 4:
+            x, a, e, i = inputs
+        else:
+            x, a, i = inputs
         n = x.shape[0]
         seg = i if isinstance(i, D.Segments) else D.Segments.from_ids(ctx, i)
         dx = ctx.to_device(x, np.float32)
@@ -57,7 +64,20 @@ class DeviceBatch:
         if normalize:
             csr = csr.gcn_norm(normalize)
         dy = ctx.to_device(y, np.float32) if y is not None else None
-        return cls(ctx, dx, csr, seg, dy)
+        de = None
+        if e is not None:
+            e = np.asarray(e)
+            if e.ndim != 2 or e.shape[0] != csr.nnz:
+                raise ValueError(f"edge features e have shape {e.shape}: expected one row per stored entry of the adjacency "
+                                 f"({csr.nnz} entries, row-major; from_networkx(use_edge_data='entries') builds them so)")
+            de = ctx.to_device(e, np.float32) if e.shape[0] else ctx.empty((0, e.shape[1]))
+        return cls(ctx, dx, csr, seg, dy, de)
+
+
+def _without_e(inputs):
+    """(x, a, e, i) -> (x, a, i): the models that do not read edge features take the loader's output as it is, as
+    spektral.models.GeneralGNN does, whatever rows e has (the reference's use_edge_data=True gives one per undirected edge)."""
+    return (inputs[0], inputs[1], inputs[-1]) if len(inputs) == 4 else inputs
 
 
 class _Capacity:
@@ -583,7 +603,7 @@ class GCN2(_GraphRunner):
             if target is not None and inputs.y is None:
                 inputs.y = self.ctx.to_device(target, np.float32)
             return inputs
-        return DeviceBatch.from_host(self.ctx, inputs, target)
+        return DeviceBatch.from_host(self.ctx, _without_e(inputs), target)
 
     def __call__(self, inputs, training=False):
         """model([x, a, i], training=False) -> probabilities [B, C] (gcn.py:351)."""
@@ -1111,7 +1131,7 @@ class GeneralGNN(_GraphRunner):
             if target is not None and inputs.y is None:
                 inputs.y = self.ctx.to_device(target, np.float32)
             return inputs
-        return DeviceBatch.from_host(self.ctx, inputs, target, weighted=False)
+        return DeviceBatch.from_host(self.ctx, _without_e(inputs), target, weighted=False)
 
     def __call__(self, inputs, training=False):
         batch = self._as_batch(inputs)
@@ -1373,7 +1393,7 @@ class GCN(_GraphRunner):
             if target is not None and inputs.y is None:
                 inputs.y = self.ctx.to_device(target, np.float32)
             return inputs
-        x, a, i = inputs
+        x, a, i = _without_e(inputs)
         if not isinstance(a, D.DeviceCSR):
             a = _with_remaining_self_loops(a, np.asarray(x).shape[0])
         return DeviceBatch.from_host(self.ctx, (x, a, i), target, weighted=False)
@@ -1598,6 +1618,205 @@ class GCN(_GraphRunner):
 
     def evaluate_batch(self, inputs, target):
         """(loss, accuracy, probabilities [B, 1]) without gradients (BatchNorm on batch statistics, as torch's eval here)."""
+        batch = self._as_batch(inputs, target)
+        bufs = self._ensure(batch)
+        self._forward(batch, bufs, "loss", float(batch.n_graphs))
+        la = self.loss_acc.numpy()
+        return float(la[0]), float(la[1]) / batch.n_graphs, bufs["probs"].numpy()
+
+
+class ECCNet(_GraphRunner):
+    """Graph classification on the edge features the reference's pipeline computes and its training script drops
+    (``dca`` on the bridges, ``proximity`` on the contacts: gcn_utills.py:379-443; gcn.py:71):
+
+        ECCConv(channels, relu) -> ECCConv(channels, relu) -> GlobalSumPool -> Dense(n_labels, softmax)
+
+    -- the shape of Spektral's ECC graph-classification example and of GCN2 -- with the categorical cross-entropy and one-hot
+    labels of gcn.py:259-262,326 and plain SGD.  ``ECCNet([ctx,] n_labels=2, channels=32, kernel_network=None, pool="sum",
+    seed=0)``; inputs are ``(x, a, e, i)`` as DisjointLoader yields them for ``Graph(e=...)`` (e: one row per stored entry of a,
+    from_networkx(use_edge_data="entries")) or a DeviceBatch that carries ``e``.  The values of ``a`` are ignored.
+
+    Follows the GCN2 protocol (model(inputs, training=), loss_and_grads, train_step(fetch=True | False | "stash"),
+    evaluate_batch, collect_metrics; one flat parameter buffer, one SGD launch), so gcnx.fit / gcnx.evaluate drive it.
+    fp32, eager launches, one device.  Hot path: gcnx_ecc_expand + gcnx_gemm per layer, gcnx_segment_pool,
+    gcnx_dense_softmax_cce, gcnx_act_bias_grad / gcnx_gemm_dw / gcnx_gemm_dx / gcnx_ecc_bwd backwards, gcnx_sgd (DESIGN.md,
+    "ECCConv", lists one step's launches).
+
+    Weights: ``get_weights(as_dict=True)`` / ``set_weights(dict)`` use {"conv1": {Keras names}, "conv2": {...},
+    "dense_kernel", "dense_bias"}; the list form is conv1's, conv2's (layers.ecc_weight_names order), then the Dense pair --
+    Keras' own order was not confirmed against a live model (PARITY UNPINNED): prefer the dict."""
+
+    uses_edge_features = True            # gcnx.fit / gcnx.evaluate keep e in the batches they upload for this model
+
+    @D.with_default_context
+    def __init__(self, ctx, n_labels=2, channels=32, kernel_network=None, pool="sum", seed=0, comm=None, prec="f32",
+                 cce_train="logits", cce_eval="probs"):
+        from .layers import ECCConv
+        if comm is not None:
+            raise NotImplementedError("gcnx.ECCNet runs on one device (comm is not supported)")
+        if prec not in ("f32", "fp32"):
+            raise NotImplementedError(f"gcnx.ECCNet: prec={prec!r}; fp32 only")
+        if pool not in ("sum", "avg", "mean"):
+            raise NotImplementedError(f"gcnx.ECCNet: pool={pool!r}; 'sum' (the default) or 'avg'")
+        if int(n_labels) < 1:
+            raise ValueError(f"gcnx.ECCNet(n_labels={n_labels!r})")
+        self.ctx, self.n_labels, self.channels, self.pool = ctx, int(n_labels), int(channels), pool
+        self.cce_train, self.cce_eval = cce_train, cce_eval
+        self.comm, self.prec = None, "f32"
+        self.use_graph = False                                  # eager: 14 library calls per step without a kernel network
+        rng = np.random.default_rng(seed)
+        s1, s2, self._head_seed = (int(v) for v in rng.integers(0, 2 ** 31, 3))
+        self.conv1 = ECCConv(channels, kernel_network, activation="relu", seed=s1)     # (validates channels / kernel_network)
+        self.conv2 = ECCConv(channels, kernel_network, activation="relu", seed=s2)
+        self.kernel_network = self.conv1.kernel_network
+        self.built = False
+        self._bufs = None
+        self._graphs = {}
+
+    # ---- parameters: one flat buffer (one SGD launch) ------------------------------------------------------------------
+    def build(self, f_in, edge_dim):
+        h, c = self.channels, self.n_labels
+        self.f_in, self.edge_dim = int(f_in), int(edge_dim)
+        self.conv1.edge_dim = self.conv2.edge_dim = self.edge_dim
+        n1, n2 = self.conv1.n_params(self.f_in), self.conv2.n_params(h)
+        self.n_params = n1 + n2 + -(-h * c // 4) * 4 + -(-c // 4) * 4
+        self.flat_p = self.ctx.zeros(self.n_params)
+        self.flat_g = self.ctx.zeros(self.n_params + 2)          # + (loss sum, correct count)
+        off = self.conv1.build(self.ctx, self.f_in, self.flat_p, self.flat_g, 0)
+        off = self.conv2.build(self.ctx, h, self.flat_p, self.flat_g, off)
+        self.p, self.g = {}, {}
+        for k, shape in (("dense_kernel", (h, c)), ("dense_bias", (c,))):
+            n = int(np.prod(shape))
+            self.p[k], self.g[k] = self.flat_p.flat(off, n, shape), self.flat_g.flat(off, n, shape)
+            off += -(-n // 4) * 4
+        assert off == self.n_params
+        self.loss_acc = self.flat_g.flat(self.n_params, 2)
+        self.p["dense_kernel"].copy_from_host(glorot_uniform(np.random.default_rng(self._head_seed), h, c))
+        self.built = True
+
+    def get_weights(self, as_dict=False):
+        d = {"conv1": self.conv1.get_weights(as_dict=True), "conv2": self.conv2.get_weights(as_dict=True),
+             "dense_kernel": self.p["dense_kernel"].numpy(), "dense_bias": self.p["dense_bias"].numpy()}
+        if as_dict:
+            return d
+        return self.conv1.get_weights() + self.conv2.get_weights() + [d["dense_kernel"], d["dense_bias"]]
+
+    def set_weights(self, weights):
+        if not self.built:
+            raise ValueError("gcnx.ECCNet.set_weights: build(f_in, edge_dim) first (or run a batch)")
+        if not isinstance(weights, dict):
+            weights = list(weights)
+            k = len(weights) - 2
+            weights = {"conv1": weights[:k // 2], "conv2": weights[k // 2:k], "dense_kernel": weights[-2], "dense_bias": weights[-1]}
+        self.conv1.set_weights(weights["conv1"])
+        self.conv2.set_weights(weights["conv2"])
+        for k in ("dense_kernel", "dense_bias"):
+            self.p[k].copy_from_host(np.asarray(weights[k], np.float32).reshape(self.p[k].shape))
+
+    def gradients(self):
+        """Gradients of the last loss_and_grads / train_step, nested and shaped as get_weights(as_dict=True)."""
+        return {"conv1": self.conv1.gradients(), "conv2": self.conv2.gradients(),
+                "dense_kernel": self.g["dense_kernel"].numpy(), "dense_bias": self.g["dense_bias"].numpy()}
+
+    @property
+    def trainable_variables(self):
+        return self.conv1.trainable_variables + self.conv2.trainable_variables + [self.p["dense_kernel"], self.p["dense_bias"]]
+
+    @property
+    def losses(self):
+        return []
+
+    # ---- batches -------------------------------------------------------------------------------------------------------
+    def _as_batch(self, inputs, target=None):
+        if isinstance(inputs, DeviceBatch):
+            if target is not None and inputs.y is None:
+                inputs.y = self.ctx.to_device(target, np.float32)
+            batch = inputs
+        else:
+            if len(inputs) != 4:
+                raise ValueError("gcnx.ECCNet takes (x, a, e, i): build the graphs with edge features (Graph(e=...), "
+                                 "from_networkx(use_edge_data='entries'))")
+            batch = DeviceBatch.from_host(self.ctx, inputs, target, weighted=False)
+        if batch.e is None:
+            raise ValueError("gcnx.ECCNet: the batch carries no edge features (DeviceBatch.e)")
+        return batch
+
+    def _ensure(self, batch):
+        if not self.built:
+            self.build(batch.f, batch.e.shape[1])
+        if batch.f != self.f_in or batch.e.shape[1] != self.edge_dim:
+            raise ValueError(f"gcnx.ECCNet was built for {self.f_in} node / {self.edge_dim} edge features, got {batch.f} / {batch.e.shape[1]}")
+        key = (batch.n, batch.n_graphs)
+        if self._bufs is not None and self._bufs["key"] == key:
+            return self._bufs
+        if getattr(self, "_cap", None) is None:
+            self._cap = _Capacity(self.ctx)
+        v, n, b, h, c = self._cap.view, batch.n, batch.n_graphs, self.channels, self.n_labels
+        self._bufs = {"key": key, "y1": v("y1", n, h), "y2": v("y2", n, h), "dy2": v("dy2", n, h),
+                      "pooled": v("pooled", b, h), "dpooled": v("dpooled", b, h), "probs": v("probs", b, c)}
+        return self._bufs
+
+    # ---- the call sequences ------------------------------------------------------------------------------------------------
+    def _forward(self, batch, bufs, mode, denom=None):
+        """mode: "fwd" (probabilities), "loss" (+ loss and hits, cce_eval), "grads" (+ dPooled and the head's gradients, cce_train)."""
+        ctx, p, g = self.ctx, self.p, self.g
+        a = batch.a.unweighted()
+        self.conv1([batch.x, a, batch.e], out=bufs["y1"])
+        self.conv2([bufs["y1"], a, batch.e], out=bufs["y2"])
+        D.segment_pool(ctx, batch.seg, bufs["y2"], bufs["pooled"], self.pool)
+        if mode != "fwd" and batch.y is None:
+            raise ValueError("gcnx.ECCNet: labels are needed for the loss")
+        if mode == "grads":
+            D.dense_softmax_cce(ctx, bufs["pooled"], p["dense_kernel"], p["dense_bias"], batch.y, bufs["probs"], self.loss_acc, denom,
+                                dw=g["dense_kernel"], db=g["dense_bias"], dpooled=bufs["dpooled"], cce=self.cce_train)
+        elif mode == "loss":
+            D.dense_softmax_cce(ctx, bufs["pooled"], p["dense_kernel"], p["dense_bias"], batch.y, bufs["probs"], self.loss_acc, denom,
+                                cce=self.cce_eval)
+        else:
+            D.dense_softmax_cce(ctx, bufs["pooled"], p["dense_kernel"], p["dense_bias"], None, bufs["probs"])
+
+    def _backward(self, batch, bufs):
+        D.segment_pool_bwd(self.ctx, batch.seg, bufs["dpooled"], bufs["dy2"], self.pool)
+        dy1 = self.conv2.backward(bufs["dy2"])
+        self.conv1.backward(dy1, need_dx=False)
+
+    # ---- public surface ----------------------------------------------------------------------------------------------------
+    def __call__(self, inputs, training=False):
+        """model((x, a, e, i), training=False) -> probabilities [B, n_labels]."""
+        batch = self._as_batch(inputs)
+        bufs = self._ensure(batch)
+        self._forward(batch, bufs, "fwd")
+        return bufs["probs"].numpy()
+
+    def loss_and_grads(self, inputs, target=None, global_batch=None, _lr=None):
+        """Forward + loss + every gradient (+ the SGD update with ``_lr``).  Returns the device batch."""
+        batch = self._as_batch(inputs, target)
+        bufs = self._ensure(batch)
+        self._forward(batch, bufs, "grads", float(global_batch or batch.n_graphs))
+        self._backward(batch, bufs)
+        if _lr is not None:
+            D.sgd(self.ctx, self.flat_p, self.flat_g.flat(0, self.n_params), _lr)
+        self._last_batch = batch
+        return batch
+
+    def train_step(self, inputs, target=None, lr=0.02, fetch=True, global_batch=None):
+        """One optimisation step (gcn.py:330-340): loss, gradients, p -= lr * g.  fetch: True -> (loss, acc); False -> None;
+        "stash" -> None, metrics kept on the device for collect_metrics()."""
+        batch = self.loss_and_grads(inputs, target, global_batch, _lr=float(lr))
+        n_graphs = global_batch or batch.n_graphs
+        if fetch == "stash":
+            self.stash_metrics(n_graphs)
+            return None
+        if not fetch:
+            return None
+        return self.fetch_metrics(n_graphs)
+
+    def fetch_metrics(self, n_graphs):
+        la = self.loss_acc.numpy()
+        return float(la[0]), float(la[1]) / float(n_graphs)
+
+    def evaluate_batch(self, inputs, target):
+        """(loss, accuracy, probabilities) without gradients (the body of evaluate(), gcn.py:350-357; loss by cce_eval)."""
         batch = self._as_batch(inputs, target)
         bufs = self._ensure(batch)
         self._forward(batch, bufs, "loss", float(batch.n_graphs))

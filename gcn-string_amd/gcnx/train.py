@@ -42,6 +42,8 @@ def _as_batch(model, inputs, target, normalize):
     from .models import DeviceBatch
     if isinstance(inputs, DeviceBatch):
         return inputs
+    if len(inputs) == 4 and not getattr(model, "uses_edge_features", False):
+        inputs = (inputs[0], inputs[1], inputs[-1])       # (x, a, e, i) for a model that does not read e
     return DeviceBatch.from_host(model.ctx, inputs, target, normalize=normalize)
 
 

@@ -171,6 +171,42 @@ GCNX_API int gcnx_csr_inspect(gcnx_ctx* ctx, const int32_t* rowptr, const int32_
 GCNX_API int gcnx_csr_transpose(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx,
                        const float* vals, int32_t n, int32_t nnz, int32_t* rowptr_t,
                        int32_t* colidx_t, float* vals_t);
+/* gcnx_csr_transpose of the pattern that also returns where every transposed entry came from: perm_t[p] = index of the
+ * entry of the original CSR that became entry p of the transpose -- the row of per-entry data (edge features) that
+ * belongs to it.  Integers throughout (entry numbers carried as float values stop being exact at 2^24).  Stable
+ * counting sort; synchronises. */
+GCNX_API int gcnx_csr_transpose_perm(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, int32_t n, int32_t nnz,
+                            int32_t* rowptr_t, int32_t* colidx_t, int32_t* perm_t);
+
+/* ---- edge-conditioned convolution (csrc/ecc.hip) ------------------------------------------- */
+/* Replaces spektral.layers.ECCConv in single / disjoint mode (the layer Spektral offers for DisjointLoader batches with
+ * edge features e -- the DCA / proximity pair the reference computes at gcn_utills.py:379-443 and its training script
+ * drops, gcn.py:71): the gather of x by a.indices[:, 0], the per-entry [F, F_out] kernels of the "FGN_out" Dense, the
+ * einsum and the scatter-add by a.indices[:, 1], in the factorised form of DESIGN.md ("ECCConv") that never forms the
+ * per-entry kernels.  u [nnz, ldu] holds sp = S' channels per stored entry (the constant channel u^ = [u, 1] is
+ * implicit; C = sp + 1 <= 17, more is refused with GCNX_ERR_UNSUPPORTED before anything is launched).  fp32, no
+ * atomics: every row sums its entries in stored order, so results are bit-reproducible.  Any f >= 1 (float4 lanes when
+ * f % 4 == 0 and leading dimensions / pointers are 16-byte aligned), any row length; leading dimensions honoured.
+ *
+ * gcnx_ecc_expand (forward): rowptr_t / colidx_t = CSR of the DESTINATIONS (row t lists the sources of the messages
+ * into t: the transpose of the batch adjacency), eperm[nnz] = row of u of every entry of that CSR (perm_t of
+ * gcnx_csr_transpose_perm; NULL = identity).  Writes
+ *     scat[t, c*f + i] = sum over entries k of row t of  u^_k[c] * x[colidx_t[k], i]        (c < C; every row written)
+ * and, with root != 0, the row's own x[t] into columns [C*f, (C+1)*f): [Scat | x], the operand of the layer's one
+ * weight GEMM (gcnx_gemm with Wstack = [W_0; ..; W_{S'-1}; B; W_root]). */
+GCNX_API int gcnx_ecc_expand(gcnx_ctx* ctx, const int32_t* rowptr_t, const int32_t* colidx_t, const int32_t* eperm, const float* u,
+                    int64_t ldu, int32_t sp, const float* x, int64_t ldx, int32_t f, float* scat, int64_t ld, int32_t n,
+                    int32_t nnz, int root);
+/* gcnx_ecc_bwd: the gradient of that aggregation wrt x and u in ONE launch (what tape.gradient derives from the gather /
+ * einsum / scatter): rowptr / colidx = the batch adjacency itself (row s lists the destinations of s's messages, entry k
+ * owns u[k]); dscat [n, ldd] = gradient wrt scat (C*f columns), dx_root [n, lddr] = gradient reaching x directly (the
+ * root term; NULL = none).
+ *     dx[s, i] = dx_root[s, i] + sum over entries k of row s, over c, of  u^_k[c] * dscat[colidx[k], c*f + i]
+ *     du[k, c] = sum_i x[s, i] * dscat[colidx[k], c*f + i]                                        (c < sp)
+ * dx (may alias dx_root) and du may each be NULL (the first layer needs no dx; u that is an input needs no du). */
+GCNX_API int gcnx_ecc_bwd(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, const float* u, int64_t ldu, int32_t sp,
+                 const float* x, int64_t ldx, const float* dscat, int64_t ldd, const float* dx_root, int64_t lddr, int32_t f,
+                 float* dx, int64_t lddx, float* du, int64_t lddu, int32_t n, int32_t nnz);
 
 /* ---- forward ----------------------------------------------------------------------------- */
 /* K1 MatMul+BiasAdd (+activation): out[N,Fo] = act(X[N,Fi] * W[Fi,Fo] + bias).
