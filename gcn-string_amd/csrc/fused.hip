@@ -13,7 +13,9 @@
 // Shape of a workgroup: 512 threads, 32 rows.
 //   gather   K / 4 lanes per row (float4 each), 64 / (K / 4) rows per wave instruction, every row group walks its two
 //            rows together, four entries each per trip: eight 16-byte loads in flight per lane.  Range-checked buffer
-//            loads: slots past a row's end fetch nothing.  The tile's CSR entries are staged in LDS first.
+//            loads: slots past a row's end fetch nothing.  The tile's CSR entries are staged in LDS first.  The backward
+//            needs only [Y2 > 0]: given its byte image (written by the forward of the pooled layer) it gathers that instead,
+//            K / 16 lanes per row, 16 columns per 16-byte load -- a quarter of the bytes and of the load instructions.
 //   product  v_mfma_f32_16x16x4_f32 (exact fp32 products, fp32 accumulate): wave w owns output columns [16w, 16w + 16)
 //            of both 16-row halves.  Its slice of W sits in REGISTERS (K / 4 per lane, loaded straight from L2 in the
 //            B-operand layout: lane l holds k = 4 kk + (l >> 4), column l & 15) -- no LDS image of W, so a workgroup
@@ -65,6 +67,10 @@ struct FusedArgs {
   const float* hd_part; const float* hd_cnt; int hd_rows; int hd_b;   // tile partials [(tiles + b)][K]; rows of the arrays
   float* hd_psum; float* hd_csum;                                      // [b][K] each
   const float* hd_w; const float* hd_bias; const float* hd_y; int hd_c; float hd_denom; int hd_fl;
+  // the byte image of a ReLU output, [n, nc] / [n, K] uint8, 1 where the activation is positive.  Forward: written beside
+  // (or, with out == NULL, instead of) the fp32 activation.  Backward (M8 instances): gathered in place of x = Y2, whose
+  // values the launch only ever tests for > 0 -- a quarter of the bytes and of the gather instructions
+  unsigned char* m8_out; const unsigned char* m8; int64_t ldm8;
   int dbg;                               // tuning builds: phase-ablation bits (1 no gather, 2 no MFMA, 4 no weight load)
 };
 
@@ -87,6 +93,21 @@ __device__ __forceinline__ float4 f4step(float4 a) {
   asm("v_pk_mul_f32 %0, %1, %2 clamp" : "=v"(lo) : "v"(t0), "v"(big));
   asm("v_pk_mul_f32 %0, %1, %2 clamp" : "=v"(hi) : "v"(t1), "v"(big));
   return make_float4(lo[0], lo[1], hi[0], hi[1]);
+}
+
+// Gather of the byte image: one 16-byte load carries 16 mask bytes (16 columns of the gathered row); v_cvt_f32_ubyte0..3
+// turns a byte into 0.0f / 1.0f, which is what the four v_pk_mul_f32 of f4step cost per float4 of an fp32 row.
+constexpr int kM8B = 16;          // mask bytes (= columns) per lane and load
+constexpr int kM8U = 4;           // entries per trip
+typedef unsigned m8x16 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ m8x16 m8load(__amdgpu_buffer_rsrc_t rs, unsigned off) {
+  return __builtin_bit_cast(m8x16, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0));
+}
+__device__ __forceinline__ void m8fma(float v, m8x16 m, float (&a)[kM8B]) {
+#pragma unroll
+  for (int d = 0; d < kM8B / 4; ++d)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) a[4 * d + k] = fmaf(v, (float)((m[d] >> (8 * k)) & 0xffu), a[4 * d + k]);
 }
 
 // The classifier head inside the backward launch: pooled sums of a graph (this lane's 4 of the K columns; LPR lanes hold
@@ -119,27 +140,36 @@ __device__ __forceinline__ float2 fused_head_dlogits(const FusedArgs& p, float4 
 // X3: the product phase on the bf16 MFMA with split operands (hi = bf16(x), lo = bf16(x - hi); hi*lo + lo*hi + hi*hi, fp32
 // accumulate: GCNX_PREC_BF16X3, ~2^-17 per operand) instead of exact fp32 products -- three 16x16x32 MFMAs per 32 k where
 // the fp32 path issues eight 16x16x4.
-template <int K, bool WEIGHTED, bool BWD, bool X3 = false>
+// M8 (backward only): the gathered operand is the byte image of [Y2 > 0] (FusedArgs::m8), kM8B bytes per lane and load and
+// kM8U entries per trip; every row is still accumulated by ONE lane group in CSR order, acc = fma(w, m, acc) with m in {0, 1}:
+// the operations and the order of the fp32-row form, so the two forms agree bit for bit.
+template <int K, bool WEIGHTED, bool BWD, bool X3 = false, bool M8 = false>
 __global__ __launch_bounds__(512, 6) void gcn_conv_fused_kernel(FusedArgs p) {
-  constexpr int LPR = K / 4;                 // lanes per gathered row
+  constexpr int MLB = kM8B, UM = kM8U;
+  constexpr int HL = K / 4;                  // lanes per row of the head's partial sums (float4 each)
+  constexpr int LPR = M8 ? K / MLB : K / 4;  // lanes per gathered row
+  constexpr int CPL = K / LPR;               // columns per lane
   constexpr int GW = 64 / LPR;               // row groups per wave
   constexpr int NG = 8 * GW;                 // row groups per workgroup
   constexpr int RPG = NG >= kFRows ? 1 : kFRows / NG;   // rows per group (2 at K = 128)
   constexpr int U = 4;                       // entries per row per trip
+  constexpr int SL = 2 * U;                  // slack entries behind the staged ones
+  static_assert(UM <= SL, "the mask gather reads up to UM - 1 entries past a row's end");
   static_assert(K == 32 || K == 64 || K == 128, "gather width");
+  static_assert(!M8 || (BWD && RPG == 1), "the byte-image gather is a backward form, one row per lane group");
   __shared__ __attribute__((aligned(16))) float tile[kFRows][K + 4];   // row stride K + 4: see the A-operand read
   // staged CSR entries: {byte offset of the gathered row = column * ldx * 4, weight}.  One multiply per entry here
   // instead of one per lane and entry in the gather loop, and one ds_read_b64 for both: the gather loop is bound by VALU
   // issue, not by memory (bit-image experiment: 2-byte loads in place of the 16-byte ones ran no faster), so every
   // instruction per (lane, entry) shows.  2 U slack entries: the loop reads up to U - 1 past a row's end unclamped.
-  __shared__ __attribute__((aligned(8))) int2 s_ent[kFCap + 2 * U];
+  __shared__ __attribute__((aligned(8))) int2 s_ent[kFCap + SL];
   __shared__ int32_t s_rp[kFRows + 1];
   __shared__ unsigned char s_mb[BWD ? kFRows * 32 : 1];   // backward: [Y1 > 0] of the tile, 4 columns per byte
   __shared__ float2 s_dl[BWD ? kFRows : 1];               // backward, head folded in: dlogits x pool scale of the tile's graphs
   __shared__ __attribute__((aligned(16))) float s_w3[BWD ? 2 : 1][K];   // ... and the two columns of W3
   __shared__ float s_b3[2];
   __shared__ int32_t s_g[BWD ? 1 : kFRows];               // forward with the pool's partial sums: graph of each row
-  static_assert(!BWD || sizeof(float) * kFRows * (K + 4) >= sizeof(float4) * 2 * 8 * 2 * LPR, "the head's wave partials alias the tile");
+  static_assert(!BWD || sizeof(float) * kFRows * (K + 4) >= sizeof(float4) * 2 * 8 * 2 * HL, "the head's wave partials alias the tile");
 #ifdef GCNX_TUNING
   const int dbg = p.dbg;
 #else
@@ -155,8 +185,8 @@ __global__ __launch_bounds__(512, 6) void gcn_conv_fused_kernel(FusedArgs p) {
     s_g[tid] = tid < nr ? min(max(p.node_graph[r0 + tid], 0), p.hd_b - 1) : -1;
   const int e0 = p.rowptr[r0], e1 = p.rowptr[r0 + nr];
   const int staged = min(e1 - e0, kFCap);
-  const unsigned ld4 = (unsigned)p.ldx * 4u;
-  for (int i = tid; i < staged + 2 * U; i += 512) {       // the slack entries carry weight 0: never NaN * 0
+  const unsigned ld4 = M8 ? (unsigned)p.ldm8 : (unsigned)p.ldx * 4u;     // bytes per gathered row
+  for (int i = tid; i < staged + SL; i += 512) {       // the slack entries carry weight 0: never NaN * 0
     int2 en = make_int2(0, 0);
     if (i < staged) {
       en.x = (int)((unsigned)p.colidx[e0 + i] * ld4);
@@ -167,7 +197,7 @@ __global__ __launch_bounds__(512, 6) void gcn_conv_fused_kernel(FusedArgs p) {
   // ---- gather ------------------------------------------------------------------------------------------------
   const int gid = wave * GW + lane / LPR, sub = lane % LPR;
   const __amdgpu_buffer_rsrc_t xr =
-      __builtin_amdgcn_make_buffer_rsrc((void*)p.x, (short)0, (int)((unsigned)p.n * (unsigned)p.ldx * 4u), 0x00020000);
+      __builtin_amdgcn_make_buffer_rsrc(M8 ? (void*)p.m8 : (void*)p.x, (short)0, (int)((unsigned)p.n * ld4), 0x00020000);
   // backward: the graph of each row (its dPooled vector is fetched after the gather: fewer live registers in the loop)
   int grow[RPG];
   if (BWD) {
@@ -196,8 +226,8 @@ __global__ __launch_bounds__(512, 6) void gcn_conv_fused_kernel(FusedArgs p) {
   // them), under the staging latency; the round's barrier is the staging barrier; wave 0 then combines the eight in order
   // -- the same order wherever a graph is evaluated -- and leaves the graphs' dlogits in LDS while the others gather.
   // The workgroup that holds a graph's first row also writes its totals (the head's leaves read them in gcnx_gemm_dw2).
-  float4 (*s_pv)[2][2][LPR] = reinterpret_cast<float4 (*)[2][2][LPR]>(&tile[0][0]);   // [wave][sum | count][graph][lane]
-  const int hsel = lane / LPR, hsub = lane % LPR;
+  float4 (*s_pv)[2][2][HL] = reinterpret_cast<float4 (*)[2][2][HL]>(&tile[0][0]);   // [wave][sum | count][graph][lane]
+  const int hsel = lane / HL, hsub = lane % HL;
   int g_first = 0;
   if (BWD && p.hd_part) {
     g_first = min(max(__builtin_amdgcn_readfirstlane(p.node_graph[r0]), 0), p.hd_b - 1);       // (clamped, as in the forward)
@@ -250,7 +280,7 @@ __global__ __launch_bounds__(512, 6) void gcn_conv_fused_kernel(FusedArgs p) {
           *reinterpret_cast<float4*>(p.hd_psum + (int64_t)hd_g * K + hsub * 4) = pv;
           *reinterpret_cast<float4*>(p.hd_csum + (int64_t)hd_g * K + hsub * 4) = pc;
         }
-        const float2 dl = fused_head_dlogits<LPR>(p, pv, hd_n, *reinterpret_cast<const float4*>(&s_w3[0][hsub * 4]),
+        const float2 dl = fused_head_dlogits<HL>(p, pv, hd_n, *reinterpret_cast<const float4*>(&s_w3[0][hsub * 4]),
                                                   *reinterpret_cast<const float4*>(&s_w3[1][hsub * 4]),
                                                   s_b3[0], s_b3[1], y0, y1);
         if (hsub == 0) s_dl[hd_g - g_first] = dl;
@@ -287,6 +317,37 @@ __global__ __launch_bounds__(512, 6) void gcn_conv_fused_kernel(FusedArgs p) {
   // Branch-free on purpose -- a load inside a branch makes hipcc close the trip with s_waitcnt vmcnt(0), i.e. the eight
   // row loads would complete one after the other.  Slots past the row's end get an out-of-range offset (the buffer load
   // returns zeros without a fetch); their weight is whatever the next row's entry holds -- finite -- times zero.
+  float am[M8 ? CPL : 1] = {};                 // M8: the row's accumulators, columns [CPL sub, CPL sub + CPL)
+  if constexpr (M8) {
+    // the same loop on the byte image: UM loads of MLB bytes in flight per lane, one row per lane group
+    const unsigned subb = (unsigned)sub * (unsigned)MLB;
+    for (int tt = 0; __builtin_amdgcn_ballot_w64(tt < len) != 0; tt += UM) {
+      m8x16 hv[UM];
+      float wv[UM];
+      const int eb_ = min(ea[0] + tt, ebf[0]);
+#pragma unroll
+      for (int u = 0; u < UM; ++u) {
+        const int e = eb_ + u;
+        const int2 en = s_ent[e];
+        wv[u] = __int_as_float(en.y);
+        hv[u] = m8load(xr, e < ebf[0] ? (unsigned)en.x + subb : 0xFFFFFFF0u);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int u = 0; u < UM; ++u) {
+        m8fma(wv[u], hv[u], am);
+        // the next entry's bytes become visible to the compiler only here, behind this entry's first fma: hipcc otherwise
+        // converts the whole trip first (UM * MLB floats alive: spills) and waits for all loads at once (vmcnt(0))
+        if (u + 1 < UM) asm volatile("" : "+v"(hv[u + 1]), "+v"(am[0]));
+      }
+    }
+    if (e1 - e0 > kFCap) {
+      for (int e = max(eb[0] > 0 ? s_rp[gid] - e0 : 0, kFCap); e < eb[0]; ++e) {
+        const float v = WEIGHTED ? p.vals[e0 + e] : 1.0f;
+        m8fma(v, m8load(xr, (unsigned)p.colidx[e0 + e] * ld4 + subb), am);
+      }
+    }
+  } else {
   for (int tt = 0; __builtin_amdgcn_ballot_w64(tt < len) != 0; tt += U) {
     float4 hv[RPG][U];
     float wv[RPG][U];
@@ -319,7 +380,13 @@ __global__ __launch_bounds__(512, 6) void gcn_conv_fused_kernel(FusedArgs p) {
         acc[j] = f4fma(v, BWD ? f4step(h) : h, acc[j]);
       }
   }
+  }
   float4 own[RPG], dscale[RPG];   // backward: pool'(dPooled) of the row's graph, and the row's own [Y2 > 0] row (dZ2 out)
+  m8x16 ownm = {};
+  if constexpr (M8) {
+    if (grow[0] >= 0 && p.dz2) ownm = *reinterpret_cast<const m8x16*>(p.m8 + (int64_t)(r0 + gid) * p.ldm8 + sub * MLB);
+    if (p.hd_part && !(dbg & 32)) __syncthreads();     // (as below; the scale is formed four columns at a time at the tile write)
+  } else
   if (BWD) {
 #pragma unroll
     for (int j = 0; j < RPG; ++j) {
@@ -380,6 +447,36 @@ __global__ __launch_bounds__(512, 6) void gcn_conv_fused_kernel(FusedArgs p) {
         wl[st][j] = (__bf16)(v - (float)h);
       }
   }
+  if constexpr (M8) {
+    if (gid < kFRows) {
+      const int r = gid, g = grow[0];
+      float2 dl = make_float2(0.f, 0.f);
+      float sc = 1.0f;
+      if (g >= 0 && p.hd_part) dl = s_dl[(g - g_first) & (kFRows - 1)];
+      else if (g >= 0 && p.avg) sc = 1.0f / (float)(p.gp[g + 1] - p.gp[g]);
+#pragma unroll
+      for (int q = 0; q < CPL / 4; ++q) {
+        const int c = sub * CPL + 4 * q;
+        float4 d = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (g >= 0 && (dbg & 32)) d = make_float4(1.f, 1.f, 1.f, 1.f);
+        else if (g >= 0 && p.hd_part) {
+          const float4 w0 = *reinterpret_cast<const float4*>(&s_w3[0][c]), w1 = *reinterpret_cast<const float4*>(&s_w3[1][c]);
+          d = make_float4(fmaf(dl.y, w1.x, dl.x * w0.x), fmaf(dl.y, w1.y, dl.x * w0.y), fmaf(dl.y, w1.z, dl.x * w0.z),
+                          fmaf(dl.y, w1.w, dl.x * w0.w));
+        } else if (g >= 0) {
+          d = *reinterpret_cast<const float4*>(p.dp + (int64_t)g * p.lddp + c);
+          if (p.avg) { d.x *= sc; d.y *= sc; d.z *= sc; d.w *= sc; }
+        }
+        if (p.dz2 && r < nr && !(dbg & 8)) {
+          const unsigned ow = ownm[q];                   // the row's own bytes of these four columns, as 0.0f / 1.0f
+          *reinterpret_cast<float4*>(p.dz2 + (int64_t)(r0 + r) * p.lddz2 + c) =
+              make_float4((float)(ow & 0xffu) * d.x, (float)((ow >> 8) & 0xffu) * d.y, (float)((ow >> 16) & 0xffu) * d.z,
+                          (float)(ow >> 24) * d.w);
+        }
+        *reinterpret_cast<float4*>(&tile[r][c]) = make_float4(am[4 * q] * d.x, am[4 * q + 1] * d.y, am[4 * q + 2] * d.z, am[4 * q + 3] * d.w);
+      }
+    }
+  } else
   if (gid < kFRows) {
 #pragma unroll
     for (int j = 0; j < RPG; ++j) {
@@ -454,7 +551,8 @@ __global__ __launch_bounds__(512, 6) void gcn_conv_fused_kernel(FusedArgs p) {
     float v = r < 4 ? c0[r & 3] : c1[r & 3];
     if (BWD) v = mk[r] > 0.f ? v : 0.f;               // rows past the end: mask 0 (and an all-zero gathered row)
     else { v += bcol; if (p.act == GCNX_ACT_RELU) v = fmaxf(v, 0.f); }
-    if (row < nr) p.out[(int64_t)(r0 + row) * p.ldo + col] = v;
+    if (row < nr && (BWD || p.out)) p.out[(int64_t)(r0 + row) * p.ldo + col] = v;
+    if (!BWD && p.m8_out && row < nr) p.m8_out[(int64_t)(r0 + row) * p.ldm8 + col] = v > 0.f ? (unsigned char)1 : (unsigned char)0;
     cs += v;                                          // rows in ascending order within the lane
     vout[r] = v;
   }
@@ -499,6 +597,14 @@ int launch_fused(gcnx_ctx* ctx, const FusedArgs& a_in, int k, bool x3) {
 #ifdef GCNX_TUNING
   if (const char* e = getenv("GCNX_FUSED_LDS")) dyn = atoi(e);
 #endif
+#define GCNX_FUSED_LAUNCH_M8(K_)                                                                                      \
+  do {                                                                                                                \
+    if (x3) {                                                                                                         \
+      if (a.vals) hipLaunchKernelGGL((gcn_conv_fused_kernel<K_, true, BWD, true, BWD>), dim3(tiles), dim3(512), dyn, ctx->stream, a); \
+      else hipLaunchKernelGGL((gcn_conv_fused_kernel<K_, false, BWD, true, BWD>), dim3(tiles), dim3(512), dyn, ctx->stream, a);      \
+    } else if (a.vals) hipLaunchKernelGGL((gcn_conv_fused_kernel<K_, true, BWD, false, BWD>), dim3(tiles), dim3(512), dyn, ctx->stream, a); \
+    else hipLaunchKernelGGL((gcn_conv_fused_kernel<K_, false, BWD, false, BWD>), dim3(tiles), dim3(512), dyn, ctx->stream, a);      \
+  } while (0)
 #define GCNX_FUSED_LAUNCH(K_)                                                                                         \
   do {                                                                                                                \
     if (x3) {                                                                                                         \
@@ -507,10 +613,15 @@ int launch_fused(gcnx_ctx* ctx, const FusedArgs& a_in, int k, bool x3) {
     } else if (a.vals) hipLaunchKernelGGL((gcn_conv_fused_kernel<K_, true, BWD>), dim3(tiles), dim3(512), dyn, ctx->stream, a); \
     else hipLaunchKernelGGL((gcn_conv_fused_kernel<K_, false, BWD>), dim3(tiles), dim3(512), dyn, ctx->stream, a);      \
   } while (0)
-  if (k == 128) GCNX_FUSED_LAUNCH(128);
+  if (BWD && a.m8) {                    // (the M8 instances exist for the backward only: <.., BWD, .., BWD>)
+    if (k == 128) GCNX_FUSED_LAUNCH_M8(128);
+    else if (k == 64) GCNX_FUSED_LAUNCH_M8(64);
+    else GCNX_FUSED_LAUNCH_M8(32);
+  } else if (k == 128) GCNX_FUSED_LAUNCH(128);
   else if (k == 64) GCNX_FUSED_LAUNCH(64);
   else GCNX_FUSED_LAUNCH(32);
 #undef GCNX_FUSED_LAUNCH
+#undef GCNX_FUSED_LAUNCH_M8
   GCNX_LAUNCH_OK(ctx);
   return GCNX_OK;
 }
@@ -529,11 +640,14 @@ extern "C" {
 
 int gcnx_gcn_conv_fused_ok(int64_t n, int32_t fi, int32_t fo, int64_t ldx) { return fused_shape_ok(n, fi, fo, ldx) ? 1 : 0; }
 
-int gcnx_gcn_conv_fwd_pool(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, const float* vals, const float* x,
-                           int64_t ldx, int32_t n, int32_t fi, const float* w, int32_t fo, const float* bias, int act, float* s,
-                           int64_t lds, float* out, int64_t ldo, float* wt_out, int prec, const int32_t* node_graph, int32_t b,
-                           float* tile_part, float* tile_cnt) {
+int gcnx_gcn_conv_fwd_mask8(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, const float* vals, const float* x,
+                            int64_t ldx, int32_t n, int32_t fi, const float* w, int32_t fo, const float* bias, int act, float* s,
+                            int64_t lds, float* out, int64_t ldo, float* wt_out, int prec, const int32_t* node_graph, int32_t b,
+                            float* tile_part, float* tile_cnt, uint8_t* mask8, int64_t ldmask8) {
   GCNX_CHECK_CTX(ctx);
+  GCNX_REQUIRE(ctx, !mask8 || act == GCNX_ACT_RELU, "gcnx_gcn_conv_fwd_mask8: the byte mask is that of a ReLU output");
+  GCNX_REQUIRE(ctx, !mask8 || (ldmask8 >= fo && ldmask8 % 16 == 0 && fal16(mask8)),
+               "gcnx_gcn_conv_fwd_mask8: mask8 must be 16-byte aligned with a leading dimension in multiples of 16 bytes");
   GCNX_RANGE(ctx, "GCNConv forward (one launch)");
   GCNX_REQUIRE(ctx, (!tile_part && !tile_cnt) || (tile_part && tile_cnt && node_graph && b > 0 && fal16(tile_part) && fal16(tile_cnt)),
                "gcnx_gcn_conv_fwd_pool: the pool's partial sums need node_graph, b > 0 and two 16-byte aligned outputs");
@@ -545,16 +659,24 @@ int gcnx_gcn_conv_fwd_pool(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* 
   if (!fused_shape_ok(n, fi, fo, ldx))
     return gcnx_fail(ctx, GCNX_ERR_UNSUPPORTED, "gcnx_gcn_conv_fwd: needs fi in {32, 64, 128}, fo a multiple of 16 up to 128 and "
                      "n * ldx * 4 < 2^32 (got n=%d fi=%d fo=%d): use gcnx_gemm + gcnx_spmm_csr", n, fi, fo);
-  GCNX_REQUIRE(ctx, rowptr && colidx && x && w && out, "gcnx_gcn_conv_fwd: NULL pointer");
-  GCNX_REQUIRE(ctx, ldo >= fo && ldo % 4 == 0 && fal16(x) && fal16(out) && (!bias || fal16(bias)) &&
+  GCNX_REQUIRE(ctx, rowptr && colidx && x && w && (out || mask8), "gcnx_gcn_conv_fwd: NULL pointer");
+  GCNX_REQUIRE(ctx, (!out || (ldo >= fo && ldo % 4 == 0 && fal16(out))) && fal16(x) && (!bias || fal16(bias)) &&
                         (!s || (lds >= fi && lds % 4 == 0 && fal16(s))),
                "gcnx_gcn_conv_fwd: operands must be 16-byte aligned with leading dimensions in multiples of 4 floats");
   GCNX_REQUIRE(ctx, x != out && x != s, "gcnx_gcn_conv_fwd: in-place aggregation is not possible");
   FusedArgs a{};
   a.rowptr = rowptr; a.colidx = colidx; a.vals = vals; a.x = x; a.ldx = ldx; a.n = n; a.w = w; a.ldw = fo; a.nc = fo;
   a.bias = bias; a.act = act; a.s = s; a.lds = lds; a.out = out; a.ldo = ldo; a.wt_out = wt_out;
-  a.node_graph = node_graph; a.tp_part = tile_part; a.tp_cnt = tile_cnt; a.hd_b = b;
+  a.node_graph = node_graph; a.tp_part = tile_part; a.tp_cnt = tile_cnt; a.hd_b = b; a.m8_out = mask8; a.ldm8 = ldmask8;
   return launch_fused<false>(ctx, a, fi, prec == GCNX_PREC_BF16X3);
+}
+
+int gcnx_gcn_conv_fwd_pool(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, const float* vals, const float* x,
+                           int64_t ldx, int32_t n, int32_t fi, const float* w, int32_t fo, const float* bias, int act, float* s,
+                           int64_t lds, float* out, int64_t ldo, float* wt_out, int prec, const int32_t* node_graph, int32_t b,
+                           float* tile_part, float* tile_cnt) {
+  return gcnx_gcn_conv_fwd_mask8(ctx, rowptr, colidx, vals, x, ldx, n, fi, w, fo, bias, act, s, lds, out, ldo, wt_out, prec,
+                                 node_graph, b, tile_part, tile_cnt, nullptr, 0);
 }
 
 int gcnx_gcn_conv_fwd(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, const float* vals, const float* x,
@@ -566,8 +688,13 @@ int gcnx_gcn_conv_fwd(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colid
 
 int64_t gcnx_gcn_conv_bwd_scratch_floats(int64_t n, int32_t f1) { return n <= 0 || f1 <= 0 ? 0 : (int64_t)gcnx_cdiv(n, kFRows) * f1; }
 
-int gcnx_gcn_conv_bwd_pool(gcnx_ctx* ctx, const int32_t* rowptr_t, const int32_t* colidx_t, const float* vals_t,
-                           const float* y2, int64_t ldy2, const int32_t* node_graph, const int32_t* graph_ptr, int32_t b,
+}  // extern "C"
+
+namespace {
+
+// y2 (fp32 rows) or y2m (their byte image, gcnx_gcn_conv_bwd_pool_mask8): exactly one of the two
+int conv_bwd_pool(gcnx_ctx* ctx, const int32_t* rowptr_t, const int32_t* colidx_t, const float* vals_t,
+                           const float* y2, const uint8_t* y2m, int64_t ldy2, const int32_t* node_graph, const int32_t* graph_ptr, int32_t b,
                            const float* dpooled, int64_t lddp, int mode, int32_t n, int32_t f2, const float* w2, int32_t f1,
                            int w2_transposed, const float* y1, int64_t ldy1, float* dz2, int64_t lddz2, float* dz1, int64_t lddz1, float* db1,
                            float* scratch, int64_t scratch_floats, gcnx_pending_reduce* pending, int prec,
@@ -584,13 +711,15 @@ int gcnx_gcn_conv_bwd_pool(gcnx_ctx* ctx, const int32_t* rowptr_t, const int32_t
     if (db1 && f1 > 0) GCNX_HIP(ctx, hipMemsetAsync(db1, 0, (size_t)f1 * 4, ctx->stream));
     return GCNX_OK;
   }
-  if (!fused_shape_ok(n, f2, f1, ldy2))
-    return gcnx_fail(ctx, GCNX_ERR_UNSUPPORTED, "gcnx_gcn_conv_bwd_pool: needs f2 in {32, 64, 128}, f1 a multiple of 16 up to 128 "
-                     "and n * ldy2 * 4 < 2^32 (got n=%d f1=%d f2=%d)", n, f1, f2);
-  GCNX_REQUIRE(ctx, b > 0 && rowptr_t && colidx_t && y2 && node_graph && graph_ptr && (dpooled || head) && w2 && y1 && dz1,
+  if (!fused_shape_ok(n, f2, f1, y2m ? f2 : ldy2) || (y2m && (ldy2 < f2 || (uint64_t)n * (uint64_t)ldy2 >= 0xFFFFFFF0ull)))
+    return gcnx_fail(ctx, GCNX_ERR_UNSUPPORTED, "%s: needs f2 in {32, 64, 128}, f1 a multiple of 16 up to 128 and %s (got n=%d f1=%d f2=%d)",
+                     y2m ? "gcnx_gcn_conv_bwd_pool_mask8" : "gcnx_gcn_conv_bwd_pool",
+                     y2m ? "ldmask8 >= f2, n * ldmask8 < 2^32 - 16" : "n * ldy2 * 4 < 2^32", n, f1, f2);
+  GCNX_REQUIRE(ctx, !y2m || ldy2 % 16 == 0, "gcnx_gcn_conv_bwd_pool_mask8: the mask's leading dimension must be a multiple of 16 bytes");
+  GCNX_REQUIRE(ctx, b > 0 && rowptr_t && colidx_t && (y2 || y2m) && node_graph && graph_ptr && (dpooled || head) && w2 && y1 && dz1,
                "gcnx_gcn_conv_bwd_pool: NULL pointer");
   GCNX_REQUIRE(ctx, (head || (lddp >= f2 && lddp % 4 == 0 && fal16(dpooled))) && ldy1 >= f1 && ldy1 % 4 == 0 && lddz1 >= f1 &&
-                        lddz1 % 4 == 0 && fal16(y2) && fal16(y1) && fal16(dz1) &&
+                        lddz1 % 4 == 0 && fal16(y2) && fal16(y2m) && fal16(y1) && fal16(dz1) &&
                         (!dz2 || (fal16(dz2) && lddz2 >= f2 && lddz2 % 4 == 0)),
                "gcnx_gcn_conv_bwd_pool: operands must be 16-byte aligned with leading dimensions in multiples of 4 floats");
   if (head) {
@@ -603,7 +732,8 @@ int gcnx_gcn_conv_bwd_pool(gcnx_ctx* ctx, const int32_t* rowptr_t, const int32_t
     if (head->c > 2)
       return gcnx_fail(ctx, GCNX_ERR_UNSUPPORTED, "gcnx_gcn_conv_bwd_pool: the in-kernel head serves one or two classes (got %d)", head->c);
   }
-  GCNX_REQUIRE(ctx, y2 != dz1 && y2 != dz2 && y1 != dz1, "gcnx_gcn_conv_bwd_pool: outputs must not alias the saved activations");
+  GCNX_REQUIRE(ctx, (y2m ? ((const void*)y2m != (const void*)dz1 && (const void*)y2m != (const void*)dz2) : (y2 != dz1 && y2 != dz2)) && y1 != dz1,
+               "gcnx_gcn_conv_bwd_pool: outputs must not alias the saved activations");
   const int64_t tiles = gcnx_cdiv(n, kFRows);
   float* colpart = nullptr;
   bool defer = false;
@@ -618,7 +748,7 @@ int gcnx_gcn_conv_bwd_pool(gcnx_ctx* ctx, const int32_t* rowptr_t, const int32_t
     }
   }
   FusedArgs a{};
-  a.rowptr = rowptr_t; a.colidx = colidx_t; a.vals = vals_t; a.x = y2; a.ldx = ldy2; a.n = n; a.w = w2; a.ldw = w2_transposed ? f1 : f2; a.w_t = w2_transposed ? 1 : 0; a.nc = f1;
+  a.rowptr = rowptr_t; a.colidx = colidx_t; a.vals = vals_t; a.x = y2; a.ldx = y2m ? f2 : ldy2; a.m8 = y2m; a.ldm8 = y2m ? ldy2 : 0; a.n = n; a.w = w2; a.ldw = w2_transposed ? f1 : f2; a.w_t = w2_transposed ? 1 : 0; a.nc = f1;
   a.out = dz1; a.ldo = lddz1; a.node_graph = node_graph; a.gp = graph_ptr; a.dp = dpooled; a.lddp = lddp;
   a.avg = mode == GCNX_POOL_AVG ? 1 : 0; a.mask = y1; a.ldmask = ldy1; a.dz2 = dz2; a.lddz2 = lddz2; a.colpart = colpart;
   if (head) {
@@ -633,6 +763,31 @@ int gcnx_gcn_conv_bwd_pool(gcnx_ctx* ctx, const int32_t* rowptr_t, const int32_t
     else return gcnx_colsum_partials(ctx, tiles, f1, db1);
   }
   return GCNX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gcnx_gcn_conv_bwd_pool(gcnx_ctx* ctx, const int32_t* rowptr_t, const int32_t* colidx_t, const float* vals_t,
+                           const float* y2, int64_t ldy2, const int32_t* node_graph, const int32_t* graph_ptr, int32_t b,
+                           const float* dpooled, int64_t lddp, int mode, int32_t n, int32_t f2, const float* w2, int32_t f1,
+                           int w2_transposed, const float* y1, int64_t ldy1, float* dz2, int64_t lddz2, float* dz1, int64_t lddz1, float* db1,
+                           float* scratch, int64_t scratch_floats, gcnx_pending_reduce* pending, int prec,
+                           const gcnx_head_args* head) {
+  return conv_bwd_pool(ctx, rowptr_t, colidx_t, vals_t, y2, nullptr, ldy2, node_graph, graph_ptr, b, dpooled, lddp, mode, n, f2, w2, f1,
+                       w2_transposed, y1, ldy1, dz2, lddz2, dz1, lddz1, db1, scratch, scratch_floats, pending, prec, head);
+}
+
+int gcnx_gcn_conv_bwd_pool_mask8(gcnx_ctx* ctx, const int32_t* rowptr_t, const int32_t* colidx_t, const float* vals_t,
+                                 const uint8_t* y2_mask8, int64_t ldmask8, const int32_t* node_graph, const int32_t* graph_ptr, int32_t b,
+                                 const float* dpooled, int64_t lddp, int mode, int32_t n, int32_t f2, const float* w2, int32_t f1,
+                                 int w2_transposed, const float* y1, int64_t ldy1, float* dz2, int64_t lddz2, float* dz1, int64_t lddz1,
+                                 float* db1, float* scratch, int64_t scratch_floats, gcnx_pending_reduce* pending, int prec,
+                                 const gcnx_head_args* head) {
+  if (ctx && !y2_mask8 && n > 0 && f1 > 0) return gcnx_fail(ctx, GCNX_ERR_INVALID, "gcnx_gcn_conv_bwd_pool_mask8: NULL pointer");
+  return conv_bwd_pool(ctx, rowptr_t, colidx_t, vals_t, nullptr, y2_mask8, ldmask8, node_graph, graph_ptr, b, dpooled, lddp, mode, n, f2, w2,
+                       f1, w2_transposed, y1, ldy1, dz2, lddz2, dz1, lddz1, db1, scratch, scratch_floats, pending, prec, head);
 }
 
 }  // extern "C"

@@ -145,6 +145,10 @@ SIGNATURES = {
     "gcnx_bf16_to_f32": [_vp, _vp, _vp, _i64],
     "gcnx_gcn_conv_fwd_pool": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _i32, _vp, _int, _vp, _i64, _vp, _i64, _vp, _int,
                                _vp, _i32, _vp, _vp],
+    "gcnx_gcn_conv_fwd_mask8": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _i32, _vp, _int, _vp, _i64, _vp, _i64, _vp, _int,
+                                _vp, _i32, _vp, _vp, _vp, _i64],
+    "gcnx_gcn_conv_bwd_pool_mask8": [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _i64, _int, _i32, _i32, _vp, _i32, _int, _vp, _i64,
+                                     _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _int, _vp],
     "gcnx_gemm_dw2": [_vp, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _i64, _int, _vp, _vp,
                       _i64, _f32, _vp, _vp],
     "gcnx_comm_unique_id": [C.c_char_p],

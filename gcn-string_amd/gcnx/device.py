@@ -727,13 +727,26 @@ def gcn_conv_fused_ok(ctx, n, fi, fo, ldx=None):
     return bool(ctx.lib.gcnx_gcn_conv_fused_ok(int(n), int(fi), int(fo), int(ldx if ldx is not None else fi)))
 
 
-def gcn_conv_fwd(ctx, a, x, w, bias, out, act="relu", s=None, wt=None, prec="f32", pool=None):
+def gcn_conv_fwd(ctx, a, x, w, bias, out, act="relu", s=None, wt=None, prec="f32", pool=None, mask8=None):
     """out = act((A x) w + bias) in one launch; s (optional) receives A x, wt (optional, [fo, fi]) w^T
     (gcnx_gcn_conv_fwd).  pool = (seg, tile_part, tile_cnt): the launch also leaves the global pool's per-tile partial
-    sums / positive counts of ``out`` in the two [pool_tile_rows(n, b), fo] arrays (gcnx_gcn_conv_fwd_pool)."""
+    sums / positive counts of ``out`` in the two [pool_tile_rows(n, b), fo] arrays (gcnx_gcn_conv_fwd_pool).
+    mask8 ([n, fo] uint8, act "relu"): also receives [out > 0] as bytes; ``out`` may then be None -- the fp32 activation is
+    not stored (gcnx_gcn_conv_fwd_mask8)."""
     n, fi = x.shape
     fo = w.shape[1]
-    assert a.n == n and w.shape[0] == fi and w.contiguous and out.shape == (n, fo) and (s is None or s.shape == (n, fi))
+    assert a.n == n and w.shape[0] == fi and w.contiguous and (s is None or s.shape == (n, fi))
+    assert (out is None and mask8 is not None) or out.shape == (n, fo)
+    if mask8 is not None:
+        assert mask8.dtype == np.uint8 and mask8.shape == (n, fo)
+        seg, tp, tc = pool if pool is not None else (None, None, None)
+        assert pool is None or (tp.shape == tc.shape == (pool_tile_rows(n, seg.n_graphs), fo) and tp.contiguous and tc.contiguous)
+        ctx._ck(ctx.lib.gcnx_gcn_conv_fwd_mask8(ctx.h, a.rowptr.ptr, a.colidx.ptr, _p(a.vals), _p(x), x.ld, n, fi, _p(w), fo, _p(bias),
+                                                L.ACTS[act], _p(s), s.ld if s is not None else 0, _p(out),
+                                                out.ld if out is not None else 0, _p(wt), L.PRECS[prec],
+                                                seg.ids.ptr if seg is not None else None, seg.n_graphs if seg is not None else 0,
+                                                _p(tp), _p(tc), mask8.ptr, mask8.ld))
+        return out
     if pool is None:
         ctx._ck(ctx.lib.gcnx_gcn_conv_fwd(ctx.h, a.rowptr.ptr, a.colidx.ptr, _p(a.vals), _p(x), x.ld, n, fi, _p(w), fo, _p(bias),
                                           L.ACTS[act], _p(s), s.ld if s is not None else 0, _p(out), out.ld, _p(wt), L.PRECS[prec]))
@@ -796,16 +809,22 @@ def head_args(seg, tile_part, tile_cnt, pool_sum, pool_cnt, w, bias, y, denom, p
 
 
 def gcn_conv_bwd_pool(ctx, at, y2, seg, dpooled, w2, y1, dz2, dz1, db1=None, mode="sum", scratch=None, w2t=None, prec="f32",
-                      head=None):
+                      head=None, mask8=None):
     """dz2 = pool'(dpooled) * [y2 > 0], dz1 = ((A^T dz2) w2^T) * [y1 > 0], db1 = column sums of dz1 -- one launch
     (gcnx_gcn_conv_bwd_pool).  With ``scratch`` the db1 reduction is left pending: returns the PendingReduce for
-    gemm_dw2 (all zeros when nothing is pending).  w2t: w2^T as written by gcn_conv_fwd(wt=...), read instead of w2."""
+    gemm_dw2 (all zeros when nothing is pending).  w2t: w2^T as written by gcn_conv_fwd(wt=...), read instead of w2.
+    mask8: [y2 > 0] as bytes (gcn_conv_fwd(mask8=...)), gathered instead of y2, which may then be None
+    (gcnx_gcn_conv_bwd_pool_mask8: the same results bit for bit)."""
+    if mask8 is not None:
+        assert mask8.dtype == np.uint8 and (y2 is None or y2.shape == mask8.shape)
+        y2 = mask8
     n, f2 = y2.shape
     f1 = w2.shape[0]
     assert at.n == n and w2.shape == (f1, f2) and w2.contiguous and y1.shape == (n, f1) and dz1.shape == (n, f1)
     assert (head is not None or dpooled.shape == (seg.n_graphs, f2)) and (dz2 is None or dz2.shape == (n, f2))
     pend = L.PendingReduce()
-    ctx._ck(ctx.lib.gcnx_gcn_conv_bwd_pool(ctx.h, at.rowptr.ptr, at.colidx.ptr, _p(at.vals), _p(y2), y2.ld, seg.ids.ptr,
+    fn = ctx.lib.gcnx_gcn_conv_bwd_pool_mask8 if mask8 is not None else ctx.lib.gcnx_gcn_conv_bwd_pool
+    ctx._ck(fn(ctx.h, at.rowptr.ptr, at.colidx.ptr, _p(at.vals), y2.ptr if mask8 is not None else _p(y2), y2.ld, seg.ids.ptr,
                                            seg.dev.ptr, seg.n_graphs, _p(dpooled), dpooled.ld if dpooled is not None else 0,
                                            L.POOLS[mode], n, f2,
                                            _p(w2t if w2t is not None else w2), f1, 1 if w2t is not None else 0, _p(y1), y1.ld, _p(dz2), dz2.ld if dz2 is not None else 0, _p(dz1), dz1.ld, _p(db1),

@@ -214,7 +214,8 @@ class GCN2(_GraphRunner):
                       "s_order": os.environ.get("GCNX_S_ORDER", "1") != "0",
                       "buckets": os.environ.get("GCNX_COMM_BUCKETS", "1") != "0",
                       "act16": os.environ.get("GCNX_ACT16", "1") != "0",
-                      "pool_in_spmm": os.environ.get("GCNX_POOL_IN_SPMM", "1") != "0"}
+                      "pool_in_spmm": os.environ.get("GCNX_POOL_IN_SPMM", "1") != "0",
+                      "mask8": os.environ.get("GCNX_MASK8", "1") != "0"}
         self._rng = np.random.default_rng(seed)
         self.built = False
         self._bufs = None
@@ -281,6 +282,10 @@ class GCN2(_GraphRunner):
         if self._fused(batch):                                  # one-launch layers: S1 = A X, S2 = A Y1 (operands of dW)
             self._bufs["s1"], self._bufs["s2"] = v("s1", n, self.f_in), v("s2", n, h)
             self._bufs["w2t"] = v("w2t", h, h)                  # W2^T, a by-product of layer 2's forward launch
+            # [Y2 > 0] as bytes: what the backward launch gathers.  NOTE: a train_step on the head-late route then does not
+            # store the fp32 "y2" at all -- the buffer keeps whatever an earlier loss_and_grads / forward call left in it
+            if self._knob["mask8"]:
+                self._bufs["y2m8"] = v("y2m8", n, h, np.uint8)
             # head inside the backward: the pool's per-tile partial sums / positive counts (layer 2's launch writes them)
             # and the per-graph totals (the backward launch does)
             tr = D.pool_tile_rows(n, b)
@@ -294,8 +299,9 @@ class GCN2(_GraphRunner):
         return self._bufs
 
     # ---- the call sequences --------------------------------------------------------------------
-    def _forward(self, batch, bufs, with_loss, denom):
+    def _forward(self, batch, bufs, with_loss, denom, train=False):
         ctx, p, prec = self.ctx, self.p, self.prec
+        bufs["_mask8"] = None
         if self._fused(batch):
             # small-feature regime: each GCNConv is one launch, evaluated as (A X) W (gcnx_gcn_conv_fwd); A X is kept
             # for the weight gradient when a backward pass follows
@@ -303,9 +309,15 @@ class GCN2(_GraphRunner):
             late = keep and self._head_late(batch)
             D.gcn_conv_fwd(ctx, batch.a, batch.x, p["w1"], p["b1"], bufs["y1"], act="relu", s=bufs["s1"] if keep else None,
                            prec=prec)
-            D.gcn_conv_fwd(ctx, batch.a, bufs["y1"], p["w2"], p["b2"], bufs["y2"], act="relu", s=bufs["s2"] if keep else None,
-                           wt=bufs["w2t"] if keep else None, prec=prec,
-                           pool=(batch.seg, bufs["tp_part"], bufs["tp_cnt"]) if late else None)
+            # with a backward pass to follow, layer 2's launch also writes [Y2 > 0] as bytes: the backward launch only tests
+            # Y2 for > 0 and gathers the byte image instead (a quarter of the bytes and of the loads; GCNX_MASK8=0: fp32 rows).
+            # In a training step with the head folded in nothing else reads Y2: its fp32 store is dropped (loss_and_grads
+            # keeps it, and so does every route whose pool or head is a launch of its own).
+            m8 = bufs["y2m8"] if keep and self._knob["mask8"] else None
+            bufs["_mask8"] = m8
+            D.gcn_conv_fwd(ctx, batch.a, bufs["y1"], p["w2"], p["b2"], None if (m8 is not None and train and late) else bufs["y2"],
+                           act="relu", s=bufs["s2"] if keep else None, wt=bufs["w2t"] if keep else None, prec=prec,
+                           pool=(batch.seg, bufs["tp_part"], bufs["tp_cnt"]) if late else None, mask8=m8)
         else:
             bufs["act16"] = False
             if self._s_order() and self._act16_try(batch, with_loss):
@@ -415,7 +427,7 @@ class GCN2(_GraphRunner):
             ha = bufs.get("_head_late")
             pend = D.gcn_conv_bwd_pool(ctx, at, bufs["y2"], batch.seg, None if ha is not None else bufs["dpooled"], p["w2"], bufs["y1"],
                                        bufs["dz"], bufs["dz2"], db1=g["b1"], mode=self.pool, scratch=self._defer_scratch(batch),
-                                       w2t=bufs["w2t"], prec=prec, head=ha)
+                                       w2t=bufs["w2t"], prec=prec, head=ha, mask8=bufs.get("_mask8"))
             if lr is None:
                 D.gemm_dw2(ctx, bufs["s1"], bufs["dz2"], g["w1"], bufs["s2"], bufs["dz"], g["w2"], prec="f32",
                            grads=self.flat_g.flat(0, self.n_params), pending=pend, leaf=ha)
@@ -637,7 +649,7 @@ class GCN2(_GraphRunner):
         buckets = multi and self._knob["buckets"] and (fused_comm or not self.use_graph)
 
         def seq():
-            self._forward(batch, bufs, "grads", denom)
+            self._forward(batch, bufs, "grads", denom, train=_lr is not None)
             if self._backward(batch, bufs, None if multi else _lr, buckets=buckets):
                 return
             if fused_comm and not self._reduced_in_backward:

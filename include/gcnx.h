@@ -651,6 +651,15 @@ GCNX_API int gcnx_gcn_conv_fwd_pool(gcnx_ctx* ctx, const int32_t* rowptr, const 
                       const float* x, int64_t ldx, int32_t n, int32_t fi, const float* w, int32_t fo,
                       const float* bias, int act, float* s, int64_t lds, float* out, int64_t ldo, float* wt_out,
                       int prec, const int32_t* node_graph, int32_t b, float* tile_part, float* tile_cnt);
+/* gcnx_gcn_conv_fwd_pool that also writes the byte image of the ReLU output: mask8 [n, fo] uint8 (16-byte aligned,
+ * ldmask8 >= fo a multiple of 16 bytes), mask8[r, c] = out[r, c] > 0 ? 1 : 0 -- what gcnx_gcn_conv_bwd_pool_mask8 gathers
+ * in place of the fp32 rows.  act must be GCNX_ACT_RELU when mask8 is given; `out` may then be NULL: the fp32 activation
+ * is not stored (s, wt_out and the pool's partial sums as usual).  mask8 == NULL: gcnx_gcn_conv_fwd_pool exactly. */
+GCNX_API int gcnx_gcn_conv_fwd_mask8(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, const float* vals,
+                      const float* x, int64_t ldx, int32_t n, int32_t fi, const float* w, int32_t fo,
+                      const float* bias, int act, float* s, int64_t lds, float* out, int64_t ldo, float* wt_out,
+                      int prec, const int32_t* node_graph, int32_t b, float* tile_part, float* tile_cnt,
+                      uint8_t* mask8, int64_t ldmask8);
 /* The classifier head of a small-batch step whose pool is still in per-tile partial sums (plain data, no ownership).  In
  * a latency-bound step the pool and the head -- Dense(softmax) + CCE + their gradients on a [B, H] operand: 7 + 10 us of
  * little parallel work -- sit between the forward and the backward aggregation only because that needs dPooled.  With
@@ -687,6 +696,16 @@ typedef struct gcnx_head_args {
 GCNX_API int64_t gcnx_gcn_conv_bwd_scratch_floats(int64_t n, int32_t f1);
 GCNX_API int gcnx_gcn_conv_bwd_pool(gcnx_ctx* ctx, const int32_t* rowptr_t, const int32_t* colidx_t, const float* vals_t,
                       const float* y2, int64_t ldy2, const int32_t* node_graph, const int32_t* graph_ptr, int32_t b,
+                      const float* dpooled, int64_t lddp, int mode, int32_t n, int32_t f2, const float* w2, int32_t f1,
+                      int w2_transposed, const float* y1, int64_t ldy1, float* dz2, int64_t lddz2, float* dz1, int64_t lddz1, float* db1,
+                      float* scratch, int64_t scratch_floats, gcnx_pending_reduce* pending, int prec,
+                      const gcnx_head_args* head);
+/* gcnx_gcn_conv_bwd_pool with y2 given as its byte image (gcnx_gcn_conv_fwd_mask8: 1 where y2 > 0; ldmask8 >= f2 a
+ * multiple of 16 bytes, n * ldmask8 < 2^32): the launch only ever tests y2 for > 0, so it gathers a quarter of the bytes with
+ * a quarter of the load instructions.  Every row is accumulated in the same order with the same operations: all outputs
+ * equal those of the fp32-row form bit for bit. */
+GCNX_API int gcnx_gcn_conv_bwd_pool_mask8(gcnx_ctx* ctx, const int32_t* rowptr_t, const int32_t* colidx_t, const float* vals_t,
+                      const uint8_t* y2_mask8, int64_t ldmask8, const int32_t* node_graph, const int32_t* graph_ptr, int32_t b,
                       const float* dpooled, int64_t lddp, int mode, int32_t n, int32_t f2, const float* w2, int32_t f1,
                       int w2_transposed, const float* y1, int64_t ldy1, float* dz2, int64_t lddz2, float* dz1, int64_t lddz1, float* db1,
                       float* scratch, int64_t scratch_floats, gcnx_pending_reduce* pending, int prec,

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Fused GCNConv launch times at config-2 shapes (tuning aid): forward, backward, the two-gradient GEMM; HIP events.
-GCNX_FUSED_DBG (tuning build only) ablates phases: 1 no gather, 2 no MFMA, 4 no weight load."""
+GCNX_FUSED_DBG (tuning build only) ablates phases: 1 no gather, 2 no MFMA, 4 no weight load.  The backward is timed in its
+fp32-row form and in its byte-mask form (gcn_conv_bwd_pool(mask8=...))."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "gcn-string_amd"))
@@ -37,6 +38,11 @@ print("fwd  (S, W^T, pool partials): %.1f us" % timeit(lambda: D.gcn_conv_fwd(ct
 ha = D.head_args(seg, tp, tc, ctx.empty((32, f)), ctx.empty((32, f)), w3, b3, yl, 32.0, ctx.empty((32, 2)), ctx.zeros(2), ctx.empty((f, 2)),
                  ctx.empty(2), ctx.empty(f), ctx.empty((32, f)), ctx.empty((32, f)))
 print("bwd  (head inside): %.1f us" % timeit(lambda: D.gcn_conv_bwd_pool(ctx, at, out, seg, None, w, s, dz2, dz1, db1=g.flat(2 * f * f, f), scratch=scratch, w2t=wt, head=ha)))
+m8 = ctx.zeros((hb.n, f), np.uint8)
+print("fwd  (S, W^T, pool partials, byte mask, no Y): %.1f us" % timeit(lambda: D.gcn_conv_fwd(ctx, a, x, w, b, None, act="relu", s=s, wt=wt, pool=(seg, tp, tc), mask8=m8)))
+D.gcn_conv_fwd(ctx, a, x, w, b, out, act="relu", s=s, wt=wt, pool=(seg, tp, tc), mask8=m8)
+print("bwd  (byte mask)  : %.1f us" % timeit(lambda: D.gcn_conv_bwd_pool(ctx, at, None, seg, dp, w, s, dz2, dz1, db1=g.flat(2 * f * f, f), scratch=scratch, w2t=wt, mask8=m8)))
+print("bwd  (byte mask, head inside): %.1f us" % timeit(lambda: D.gcn_conv_bwd_pool(ctx, at, None, seg, None, w, s, dz2, dz1, db1=g.flat(2 * f * f, f), scratch=scratch, w2t=wt, head=ha, mask8=m8)))
 print("dw2              : %.1f us" % timeit(lambda: D.gemm_dw2(ctx, s, dz1, g.flat(0, f * f, (f, f)), s, dz2, g.flat(f * f, f * f, (f, f)), grads=g)))
 h = ctx.empty((hb.n, f))
 print("gemm + spmm      : %.1f us" % timeit(lambda: (D.gemm(ctx, x, w, None, h), D.spmm(ctx, a, h, b, out, act="relu"))))
