@@ -586,6 +586,146 @@ __global__ __launch_bounds__(512, 6) void gcn_conv_fused_kernel(FusedArgs p) {
   }
 }
 
+// The forward of a layer whose aggregated input S = A X is already in memory (gcnx_gcn_conv_fwd_pre): the first layer's
+// input carries no trainable parameter, so S is a constant of the batch -- what gcn_conv_fused_kernel's forward wrote as
+// `s` one step earlier, or what the loader gathered -- and the launch is the product phase and the epilogue of that kernel
+// alone: no CSR staging, no gather, no S store.  The tile's rows come straight from `s` as coalesced 16-byte loads; the W
+// slice sits in registers in the same B layout; the MFMAs run in the same order on the same operands (k ascending on the
+// fp32 MFMA, lo-hi / hi-lo / hi-hi per 32 k on the bf16 one), the epilogue is the same bias / ReLU: `out` carries the bits
+// of the gathering launch.  Every output row depends on its own S row only, so the row tiling is free: a workgroup walks
+// the 32-row tiles blockIdx.x, + gridDim.x, ... with its W slice loaded once, and the next tile's rows are in flight
+// (registers) while the MFMAs of the current one run.
+struct PreArgs {
+  const float* s; int64_t lds; int32_t n;
+  const float* w; int32_t nc;              // W [K, nc], contiguous
+  const float* bias; int act;
+  float* out; int64_t ldo;
+};
+
+template <int K, bool X3>
+__global__ __launch_bounds__(512, 6) void gcn_conv_pre_kernel(PreArgs p) {
+  constexpr int RL = K / 4;                              // 16-byte pieces per row
+  constexpr int NQ = (kFRows * RL + 511) / 512;          // ... per thread and tile (2 at K = 128)
+  __shared__ __attribute__((aligned(16))) float tile[kFRows][K + 4];   // row stride K + 4: as in gcn_conv_fused_kernel
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int ntiles = (p.n + kFRows - 1) / kFRows, stride = gridDim.x;
+  const int c16 = lane & 15, kq = lane >> 4;
+  const bool wave_on = 16 * wave < p.nc;
+  const int col = 16 * wave + c16;
+  auto k_of = [&](int e) { return X3 ? 32 * (e / 8) + 8 * kq + (e % 8) : 4 * e + kq; };
+  float wreg[K / 4];
+  fbf16x8 wh[X3 ? K / 32 : 1], wl[X3 ? K / 32 : 1];
+  float bcol = 0.f;
+  if (wave_on) {
+#pragma unroll
+    for (int e = 0; e < K / 4; ++e) wreg[e] = p.w[(int64_t)k_of(e) * p.nc + col];
+    if (p.bias) bcol = p.bias[col];
+  }
+  float4 nx[NQ];
+  auto fetch = [&](int t) {                              // rows past the end hold zeros (their outputs are not stored)
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      const int i = tid + 512 * q, row = i / RL, c4 = i - row * RL;
+      nx[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (row < kFRows && t * kFRows + row < p.n)
+        nx[q] = *reinterpret_cast<const float4*>(p.s + (int64_t)(t * kFRows + row) * p.lds + 4 * c4);
+    }
+  };
+  int t = blockIdx.x;
+  if (t >= ntiles) return;
+  fetch(t);
+  if (X3 && wave_on) {
+#pragma unroll
+    for (int st = 0; st < K / 32; ++st)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float v = wreg[st * 8 + j];
+        const __bf16 h = (__bf16)v;
+        wh[st][j] = h;
+        wl[st][j] = (__bf16)(v - (float)h);
+      }
+  }
+  for (;;) {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      const int i = tid + 512 * q, row = i / RL, c4 = i - row * RL;
+      if (row < kFRows) *reinterpret_cast<float4*>(&tile[row][4 * c4]) = nx[q];
+    }
+    __syncthreads();
+    const int r0 = t * kFRows, nr = min(p.n - r0, kFRows);
+    const bool more = t + stride < ntiles;               // uniform
+    if (more) fetch(t + stride);
+    if (wave_on) {
+      f32x4v c0 = {0.f, 0.f, 0.f, 0.f}, c1 = c0;
+      if (X3) {
+#pragma unroll
+        for (int st = 0; st < K / 32; ++st) {
+#pragma unroll
+          for (int hf = 0; hf < 2; ++hf) {
+            const float* ap = &tile[16 * hf + c16][32 * st + 8 * kq];
+            const float4 x0 = *reinterpret_cast<const float4*>(ap), x1 = *reinterpret_cast<const float4*>(ap + 4);
+            const float xv[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
+            fbf16x8 ah, al;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+              const __bf16 h = (__bf16)xv[j];
+              ah[j] = h;
+              al[j] = (__bf16)(xv[j] - (float)h);
+            }
+            f32x4v& cc = hf ? c1 : c0;
+            cc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, wl[st], cc, 0, 0, 0);     // small terms first
+            cc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, wh[st], cc, 0, 0, 0);
+            cc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, wh[st], cc, 0, 0, 0);
+          }
+        }
+      } else {
+#pragma unroll
+        for (int kk = 0; kk < K / 4; ++kk) {
+          const float a0 = tile[c16][4 * kk + kq];
+          const float a1 = tile[16 + c16][4 * kk + kq];
+          c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, wreg[kk], c0, 0, 0, 0);
+          c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, wreg[kk], c1, 0, 0, 0);
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < 8; ++r) {
+        const int row = 16 * (r >> 2) + 4 * kq + (r & 3);
+        float v = r < 4 ? c0[r & 3] : c1[r & 3];
+        v += bcol;
+        if (p.act == GCNX_ACT_RELU) v = fmaxf(v, 0.f);
+        if (row < nr) p.out[(int64_t)(r0 + row) * p.ldo + col] = v;
+      }
+    }
+    if (!more) break;
+    t += stride;
+    __syncthreads();                                     // every wave is done reading the tile
+  }
+}
+
+int launch_pre(gcnx_ctx* ctx, const PreArgs& a, int k, bool x3) {
+  const int tiles = gcnx_cdiv(a.n, kFRows);
+  // two workgroups per CU walk the tiles (each loads its W slice once): 12.0 us at config 2's 706 tiles against 13.1 with one
+  // workgroup per tile; 353 workgroups (CUs unevenly loaded) 14.4, 177 (too few) 14.7 (profiles/r06/pre_ab.txt)
+  int grid = tiles <= 2 * ctx->num_cus ? tiles : 2 * ctx->num_cus;
+#ifdef GCNX_TUNING
+  if (const char* e = getenv("GCNX_PRE_GRID")) {
+    const int g = atoi(e);
+    if (g > 0 && g <= tiles) grid = g;
+  }
+#endif
+#define GCNX_PRE_LAUNCH(K_)                                                                                           \
+  do {                                                                                                                \
+    if (x3) hipLaunchKernelGGL((gcn_conv_pre_kernel<K_, true>), dim3(grid), dim3(512), 0, ctx->stream, a);             \
+    else hipLaunchKernelGGL((gcn_conv_pre_kernel<K_, false>), dim3(grid), dim3(512), 0, ctx->stream, a);               \
+  } while (0)
+  if (k == 128) GCNX_PRE_LAUNCH(128);
+  else if (k == 64) GCNX_PRE_LAUNCH(64);
+  else GCNX_PRE_LAUNCH(32);
+#undef GCNX_PRE_LAUNCH
+  GCNX_LAUNCH_OK(ctx);
+  return GCNX_OK;
+}
+
 template <bool BWD>
 int launch_fused(gcnx_ctx* ctx, const FusedArgs& a_in, int k, bool x3) {
   FusedArgs a = a_in;
@@ -684,6 +824,27 @@ int gcnx_gcn_conv_fwd(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colid
                       int64_t lds, float* out, int64_t ldo, float* wt_out, int prec) {
   return gcnx_gcn_conv_fwd_pool(ctx, rowptr, colidx, vals, x, ldx, n, fi, w, fo, bias, act, s, lds, out, ldo, wt_out, prec,
                                 nullptr, 0, nullptr, nullptr);
+}
+
+int gcnx_gcn_conv_fwd_pre(gcnx_ctx* ctx, const float* s, int64_t lds, int32_t n, int32_t fi, const float* w, int32_t fo,
+                          const float* bias, int act, float* out, int64_t ldo, int prec) {
+  GCNX_CHECK_CTX(ctx);
+  GCNX_RANGE(ctx, "GCNConv forward on a stored A X (one launch)");
+  GCNX_REQUIRE(ctx, n >= 0 && fi >= 0 && fo >= 0, "gcnx_gcn_conv_fwd_pre: negative size");
+  if (prec != GCNX_PREC_F32 && prec != GCNX_PREC_BF16X3)
+    return gcnx_fail(ctx, GCNX_ERR_UNSUPPORTED, "gcnx_gcn_conv_fwd_pre: precision %d (GCNX_PREC_F32 or GCNX_PREC_BF16X3 here)", prec);
+  GCNX_REQUIRE(ctx, act == GCNX_ACT_NONE || act == GCNX_ACT_RELU, "gcnx_gcn_conv_fwd_pre: activation %d not supported here", act);
+  if (n == 0 || fo == 0) return GCNX_OK;
+  if (!fused_shape_ok(n, fi, fo, lds))
+    return gcnx_fail(ctx, GCNX_ERR_UNSUPPORTED, "gcnx_gcn_conv_fwd_pre: needs fi in {32, 64, 128}, fo a multiple of 16 up to 128, lds >= fi "
+                     "in multiples of 4 floats and n * lds * 4 < 2^32 (got n=%d fi=%d fo=%d lds=%lld)", n, fi, fo, (long long)lds);
+  GCNX_REQUIRE(ctx, s && w && out, "gcnx_gcn_conv_fwd_pre: NULL pointer");
+  GCNX_REQUIRE(ctx, ldo >= fo && ldo % 4 == 0 && fal16(out) && fal16(s) && (!bias || fal16(bias)),
+               "gcnx_gcn_conv_fwd_pre: operands must be 16-byte aligned with leading dimensions in multiples of 4 floats");
+  GCNX_REQUIRE(ctx, s != out, "gcnx_gcn_conv_fwd_pre: out must not alias s");
+  PreArgs a{};
+  a.s = s; a.lds = lds; a.n = n; a.w = w; a.nc = fo; a.bias = bias; a.act = act; a.out = out; a.ldo = ldo;
+  return launch_pre(ctx, a, fi, prec == GCNX_PREC_BF16X3);
 }
 
 int64_t gcnx_gcn_conv_bwd_scratch_floats(int64_t n, int32_t f1) { return n <= 0 || f1 <= 0 ? 0 : (int64_t)gcnx_cdiv(n, kFRows) * f1; }

@@ -127,7 +127,8 @@ __global__ __launch_bounds__(256) void collate_kernel(const int32_t* __restrict_
                                                       int32_t* __restrict__ o_rowptr, int32_t* __restrict__ o_colidx,
                                                       float* __restrict__ o_vals, float* __restrict__ o_x, int64_t ldo,
                                                       float* __restrict__ o_y, int32_t* __restrict__ o_gp,
-                                                      int32_t* __restrict__ o_ids) {
+                                                      int32_t* __restrict__ o_ids, const float* __restrict__ s,
+                                                      int64_t lds, float* __restrict__ o_s, int64_t ldos) {
   const int g = blockIdx.y;                       // position in the batch
   const int src = desc[g];
   const int bn = desc[(b + 1) + g], be = desc[2 * (b + 1) + g];
@@ -149,6 +150,7 @@ __global__ __launch_bounds__(256) void collate_kernel(const int32_t* __restrict_
   for (int64_t k = tid; k < total; k += nth) {
     const int64_t i = k / f, j = k - i * f;
     o_x[(int64_t)(bn + i) * ldo + j] = x[(int64_t)(n0 + i) * ldx + j];
+    if (s) o_s[(int64_t)(bn + i) * ldos + j] = s[(int64_t)(n0 + i) * lds + j];   // the same rows of A x (gcnx_collate2)
   }
   if (blockIdx.x == 0) {
     if (y) for (int k = threadIdx.x; k < c; k += blockDim.x) o_y[(int64_t)g * c + k] = y[(int64_t)src * c + k];
@@ -285,10 +287,10 @@ int gcnx_csr_transpose(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* coli
 }
 
 
-int gcnx_collate(gcnx_ctx* ctx, const int32_t* desc, int32_t b, const int32_t* node_ptr, const int32_t* rowptr,
+int gcnx_collate2(gcnx_ctx* ctx, const int32_t* desc, int32_t b, const int32_t* node_ptr, const int32_t* rowptr,
                  const int32_t* colidx, const float* vals, const float* x, int64_t ldx, int32_t f, const float* y, int32_t c,
                  int32_t* o_rowptr, int32_t* o_colidx, float* o_vals, float* o_x, int64_t ldo, float* o_y,
-                 int32_t* o_graph_ptr, int32_t* o_node_graph) {
+                 int32_t* o_graph_ptr, int32_t* o_node_graph, const float* s, int64_t lds, float* o_s, int64_t ldos) {
   GCNX_CHECK_CTX(ctx);
   GCNX_RANGE(ctx, "device-side collate");
   GCNX_REQUIRE(ctx, b >= 0 && f >= 0 && c >= 0, "gcnx_collate: negative size");
@@ -297,10 +299,20 @@ int gcnx_collate(gcnx_ctx* ctx, const int32_t* desc, int32_t b, const int32_t* n
   GCNX_REQUIRE(ctx, f == 0 || (x && o_x && ldx >= f && ldo >= f), "gcnx_collate: bad feature buffers");
   GCNX_REQUIRE(ctx, (vals == nullptr) == (o_vals == nullptr), "gcnx_collate: values in and out go together");
   GCNX_REQUIRE(ctx, !y || o_y, "gcnx_collate: labels need an output");
+  GCNX_REQUIRE(ctx, !s || f == 0 || (o_s && lds >= f && ldos >= f && o_s != o_x), "gcnx_collate2: bad aggregate buffers");
   hipLaunchKernelGGL(collate_kernel, dim3(16, b), dim3(256), 0, ctx->stream, desc, b, node_ptr, rowptr, colidx, vals, x, ldx,
-                     f, y, c, o_rowptr, o_colidx, o_vals, o_x, ldo, o_y, o_graph_ptr, o_node_graph);
+                     f, y, c, o_rowptr, o_colidx, o_vals, o_x, ldo, o_y, o_graph_ptr, o_node_graph, s, lds, o_s, ldos);
   GCNX_LAUNCH_OK(ctx);
   return GCNX_OK;
+}
+
+
+int gcnx_collate(gcnx_ctx* ctx, const int32_t* desc, int32_t b, const int32_t* node_ptr, const int32_t* rowptr,
+                 const int32_t* colidx, const float* vals, const float* x, int64_t ldx, int32_t f, const float* y, int32_t c,
+                 int32_t* o_rowptr, int32_t* o_colidx, float* o_vals, float* o_x, int64_t ldo, float* o_y,
+                 int32_t* o_graph_ptr, int32_t* o_node_graph) {
+  return gcnx_collate2(ctx, desc, b, node_ptr, rowptr, colidx, vals, x, ldx, f, y, c, o_rowptr, o_colidx, o_vals, o_x, ldo, o_y,
+                       o_graph_ptr, o_node_graph, nullptr, 0, nullptr, 0);
 }
 
 }  // extern "C"

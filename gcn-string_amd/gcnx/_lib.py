@@ -63,6 +63,8 @@ SIGNATURES = {
     "gcnx_graph_destroy": [_vp, _vp],
     "gcnx_coo_to_csr": [_vp, _vp, _vp, _i64, _i64, _vp, _vp],
     "gcnx_collate": [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp],
+    "gcnx_collate2": [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
+                      _vp, _i64, _vp, _i64],
     "gcnx_gcn_norm": [_vp, _vp, _vp, _vp, _i32, _int, _vp],
     "gcnx_set_tuning": [_vp, C.c_char_p, _int],
     "gcnx_csr_inspect": [_vp, _vp, _vp, _vp, _i32, _vp, _i32, C.POINTER(C.c_int)],
@@ -137,6 +139,7 @@ SIGNATURES = {
                                 _i64, _vp],
     "gcnx_gcn_conv_fused_ok": [_i64, _i32, _i32, _i64],
     "gcnx_gcn_conv_fwd": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _i32, _vp, _int, _vp, _i64, _vp, _i64, _vp, _int],
+    "gcnx_gcn_conv_fwd_pre": [_vp, _vp, _i64, _i32, _i32, _vp, _i32, _vp, _int, _vp, _i64, _int],
     "gcnx_gcn_conv_bwd_scratch_floats": [_i64, _i32],
     "gcnx_gcn_conv_bwd_pool": [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _i64, _int, _i32, _i32, _vp, _i32, _int, _vp, _i64,
                                _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _int, _vp],

@@ -759,6 +759,17 @@ def gcn_conv_fwd(ctx, a, x, w, bias, out, act="relu", s=None, wt=None, prec="f32
     return out
 
 
+def gcn_conv_fwd_pre(ctx, s, w, bias, out, act="relu", prec="f32"):
+    """out = act(s w + bias) in one launch, s = A x as gcn_conv_fwd(..., s=s) wrote it (gcnx_gcn_conv_fwd_pre): the product and
+    epilogue of that launch without its gather, bit for bit the same ``out``."""
+    n, fi = s.shape
+    fo = w.shape[1]
+    assert w.shape[0] == fi and w.contiguous and out.shape == (n, fo)
+    ctx._ck(ctx.lib.gcnx_gcn_conv_fwd_pre(ctx.h, _p(s), s.ld, n, fi, _p(w), fo, _p(bias), L.ACTS[act], _p(out), out.ld,
+                                          L.PRECS[prec]))
+    return out
+
+
 def to_bf16(ctx, x):
     """bf16 copy (uint16 bit patterns, round to nearest even) of a contiguous fp32 array (gcnx_f32_to_bf16)."""
     assert x.contiguous and x.dtype == np.float32

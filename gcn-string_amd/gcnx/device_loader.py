@@ -7,6 +7,10 @@ gcn_filter already applied per graph -- the filter of a block-diagonal matrix is
 labels, node offsets); a batch is then one ``gcnx_collate`` launch that gathers the selected graphs' rows and
 re-bases their indices, into buffers sized for the largest possible batch and reused for every batch.  Per batch
 only 3(B+1) ints cross PCIe.  Iteration order, shuffling and batch boundaries are those of ``DisjointLoader``.
+
+``DeviceDataset(aggregate_x=True)`` also keeps S = A X of the union: the filter being block-diagonal, A X of a batch is the
+selected graphs' rows of it, gathered by the same launch (gcnx_collate2) into ``batch.ax`` -- GCN2's first layer then
+needs no neighbour gather at all, in any step of any epoch.  It costs a second copy of the features (N_all x F x 4 bytes).
 """
 from __future__ import annotations
 
@@ -24,7 +28,9 @@ class DeviceDataset:
     accepted and their ``e`` is ignored (gcnx_collate gathers x, the adjacency and the labels only), so the batches of a
     DeviceDisjointLoader serve GCN2 / GeneralGNN / GCN; gcnx.ECCNet takes host DisjointLoader batches."""
 
-    def __init__(self, ctx, dataset, normalize=None, weighted=True, symmetric=None):
+    def __init__(self, ctx, dataset, normalize=None, weighted=True, symmetric=None, aggregate_x=False):
+        """aggregate_x: also compute S_all = A X once, here, and hand every batch its rows as ``batch.ax`` (see the module
+        docstring).  Doubles the feature storage: N_all x F x 4 bytes more.  False (default): batches carry no ``ax``."""
         self.ctx = ctx
         graphs = [dataset[i] for i in range(len(dataset))]
         inputs, y = collate_disjoint(graphs)
@@ -49,6 +55,34 @@ class DeviceDataset:
         self.n_features, self.n_labels = self.x.shape[1], self.y.shape[1]
         self.sizes = sizes
         self.nnz_sizes = np.diff(self.ent_ptr_host)
+        self.ax = self._aggregate() if aggregate_x else None
+
+    def _aggregate(self, max_rows=1 << 20):
+        """S_all = A X with, in every row, the bits the one-launch GCNConv forward writes as its S output for a batch that
+        holds the row's graph: that launch itself, run for its S output alone (a [F, 16] zero weight; the product is
+        discarded) over runs of consecutive graphs collated like any batch.  A row is accumulated by one lane group in CSR
+        order from zero wherever it lies in a tile, and a graph's rows and entries keep their order in every batch, so the
+        bits do not depend on the batch.  (The row-gather SpMM splits a row's entries over lane groups: other bits.)"""
+        ctx, f = self.ctx, self.n_features
+        n = int(self.node_ptr_host[-1])
+        if f not in (32, 64, 128):
+            raise ValueError(f"DeviceDataset(aggregate_x=True) needs 32, 64 or 128 features (the one-launch GCNConv's widths), got {f}")
+        out = ctx.empty((max(n, 1), f))
+        w0 = ctx.zeros((f, 16))
+        g = 0
+        while g < self.n_graphs:
+            h = g + 1
+            while h < self.n_graphs and self.node_ptr_host[h + 1] - self.node_ptr_host[g] <= max_rows:
+                h += 1
+            batch = collate_on_device(self, np.arange(g, h))
+            if batch.n:
+                if not D.gcn_conv_fused_ok(ctx, batch.n, f, 16):
+                    raise ValueError(f"DeviceDataset(aggregate_x=True): a graph of {batch.n} rows is beyond the one-launch GCNConv")
+                s = D.DeviceArray._view(out, int(self.node_ptr_host[g]) * f, (batch.n, f))
+                D.gcn_conv_fwd(ctx, batch.a, batch.x, w0, None, ctx.empty((batch.n, 16)), act=None, s=s)
+            ctx.sync()                                       # the chunk's buffers go with it
+            g = h
+        return out
 
     def __len__(self):
         return self.n_graphs
@@ -63,6 +97,7 @@ class _BatchBuffers:
     def __init__(self, ctx, ds, batch_size):
         ncap, ecap = ds.capacity(batch_size)
         self.x = ctx.empty((ncap, ds.n_features))
+        self.ax = ctx.empty((ncap, ds.n_features)) if getattr(ds, "ax", None) is not None else None
         self.rowptr = ctx.empty(ncap + 1, np.int32)
         self.colidx = ctx.empty(max(ecap, 1), np.int32)
         self.vals = ctx.empty(max(ecap, 1), np.float32) if ds.csr.vals is not None else None
@@ -73,7 +108,8 @@ class _BatchBuffers:
 
 
 def collate_on_device(ds, indices, bufs=None):
-    """The DeviceBatch of the graphs `indices` (dataset order positions), assembled by gcnx_collate."""
+    """The DeviceBatch of the graphs `indices` (dataset order positions), assembled by one gcnx_collate2 launch (with the
+    dataset's A X rows as ``batch.ax`` when it keeps them)."""
     ctx = ds.ctx
     sel = np.asarray(indices, np.int64)
     b = len(sel)
@@ -87,16 +123,19 @@ def collate_on_device(ds, indices, bufs=None):
     dview.copy_from_host(desc, wait=False)               # queued: the host runs ahead of the GPU across batches
     f, c = ds.n_features, ds.n_labels
     csr = ds.csr
-    ctx._ck(ctx.lib.gcnx_collate(ctx.h, dview.ptr, b, ds.node_ptr.ptr, csr.rowptr.ptr, csr.colidx.ptr,
-                                 csr.vals.ptr if csr.vals is not None else None, ds.x.ptr, ds.x.ld, f, ds.y.ptr, c,
-                                 bufs.rowptr.ptr, bufs.colidx.ptr, bufs.vals.ptr if bufs.vals is not None else None,
-                                 bufs.x.ptr, bufs.x.ld, bufs.y.ptr, bufs.gp.ptr, bufs.ids.ptr))
+    ax = getattr(ds, "ax", None)                         # (None while the dataset is still computing it)
+    ctx._ck(ctx.lib.gcnx_collate2(ctx.h, dview.ptr, b, ds.node_ptr.ptr, csr.rowptr.ptr, csr.colidx.ptr,
+                                  csr.vals.ptr if csr.vals is not None else None, ds.x.ptr, ds.x.ld, f, ds.y.ptr, c,
+                                  bufs.rowptr.ptr, bufs.colidx.ptr, bufs.vals.ptr if bufs.vals is not None else None,
+                                  bufs.x.ptr, bufs.x.ld, bufs.y.ptr, bufs.gp.ptr, bufs.ids.ptr,
+                                  ax.ptr if ax is not None else None, ax.ld if ax is not None else 0,
+                                  bufs.ax.ptr if ax is not None else None, bufs.ax.ld if ax is not None else 0))
     seg = D.Segments.from_device(ctx, V(bufs.gp, 0, (b + 1,)), bn)
     seg._ids = V(bufs.ids, 0, (max(n, 1),))              # (otherwise built on the host on first use and uploaded)
     a = D.DeviceCSR(ctx, n, nnz, V(bufs.rowptr, 0, (n + 1,)), V(bufs.colidx, 0, (max(nnz, 1),)),
                     V(bufs.vals, 0, (max(nnz, 1),)) if bufs.vals is not None else None, seg.dev, b, ds.symmetric,
                     int(ds.sizes[sel].max()) if b else 0)
-    batch = DeviceBatch(ctx, V(bufs.x, 0, (n, f)), a, seg, V(bufs.y, 0, (b, c)))
+    batch = DeviceBatch(ctx, V(bufs.x, 0, (n, f)), a, seg, V(bufs.y, 0, (b, c)), ax=V(bufs.ax, 0, (n, f)) if ax is not None else None)
     batch._bufs = bufs                                   # keeps the capacity buffers alive with the batch
     return batch
 

@@ -26,16 +26,31 @@ from .loader import SparseTensor
 
 class DeviceBatch:
     """A DisjointLoader batch resident in HBM: x [N,F] fp32, adjacency CSR, graph segments,
-    one-hot labels y [B,C] fp32; optionally edge features e [nnz, S] fp32, row k belonging to stored entry k of the CSR."""
+    one-hot labels y [B,C] fp32; optionally edge features e [nnz, S] fp32, row k belonging to stored entry k of the CSR.
+    ax (optional, [N,F] fp32): the aggregated features A x of this batch, bit for bit what the one-launch GCNConv forward
+    writes as its S output (DeviceDataset(aggregate_x=True) gathers it per batch); GCN2's first layer then runs without a
+    gather.
+
+    Contract: ``x`` and ``a`` are not modified in place once a model has seen the batch -- the cached transpose of ``a``
+    assumes it, and so does GCN2, which keeps S1 = A x of the batch it is stepping on from one step to the next.  A caller
+    that does overwrite ``x`` calls ``invalidate()`` afterwards."""
 
     _next_uid = 0
 
-    def __init__(self, ctx, x, a, seg, y=None, e=None):
-        self.ctx, self.x, self.a, self.seg, self.y, self.e = ctx, x, a, seg, y, e
+    def __init__(self, ctx, x, a, seg, y=None, e=None, ax=None):
+        self.ctx, self.x, self.a, self.seg, self.y, self.e, self.ax = ctx, x, a, seg, y, e, ax
+        assert ax is None or ax.shape == x.shape
         DeviceBatch._next_uid += 1
         self.uid = DeviceBatch._next_uid  # never reused (unlike id()): keys captured graphs
         self.n, self.f = x.shape
         self.n_graphs = seg.n_graphs
+
+    def invalidate(self):
+        """After ``x`` was overwritten in place: the batch takes a fresh uid, so that every model drops the graphs it
+        captured for it and whatever it derived from the old ``x`` (GCN2's kept S1); ``ax`` no longer matches and is dropped."""
+        DeviceBatch._next_uid += 1
+        self.uid = DeviceBatch._next_uid
+        self.ax = None
 
     @classmethod
     def from_host(cls, ctx, inputs, y=None, normalize=None, weighted=True, symmetric=None):
@@ -215,7 +230,9 @@ class GCN2(_GraphRunner):
                       "buckets": os.environ.get("GCNX_COMM_BUCKETS", "1") != "0",
                       "act16": os.environ.get("GCNX_ACT16", "1") != "0",
                       "pool_in_spmm": os.environ.get("GCNX_POOL_IN_SPMM", "1") != "0",
-                      "mask8": os.environ.get("GCNX_MASK8", "1") != "0"}
+                      "mask8": os.environ.get("GCNX_MASK8", "1") != "0",
+                      "ax_reuse": os.environ.get("GCNX_AX_REUSE", "1") != "0"}
+        self._s1_uid = None                  # uid of the batch whose S1 = A X bufs["s1"] holds (one-launch route), or None
         self._rng = np.random.default_rng(seed)
         self.built = False
         self._bufs = None
@@ -273,6 +290,7 @@ class GCN2(_GraphRunner):
             return self._bufs
         n, b, h, c = batch.n, batch.n_graphs, self.hidden, self.n_labels
         self._drop_graphs()
+        self._s1_uid = None                                     # new views, possibly new storage: no S1 is kept across this
         if getattr(self, "_cap", None) is None:
             self._cap = _Capacity(self.ctx)
         v = self._cap.view
@@ -307,8 +325,23 @@ class GCN2(_GraphRunner):
             # for the weight gradient when a backward pass follows
             keep = with_loss == "grads"
             late = keep and self._head_late(batch)
-            D.gcn_conv_fwd(ctx, batch.a, batch.x, p["w1"], p["b1"], bufs["y1"], act="relu", s=bufs["s1"] if keep else None,
-                           prec=prec)
+            # S1 = A X holds no trainable parameter: a constant of the batch.  Given with the batch (batch.ax, gathered by the
+            # loader) or still in bufs["s1"] from the last gradient step on this very batch, layer 1 is the product and the
+            # epilogue alone (gcnx_gcn_conv_fwd_pre: same bits, no gather); otherwise the gathering launch, which writes S1 --
+            # and only a pass that writes it marks it valid (GCNX_AX_REUSE=0: the gather every step)
+            if self._s1_uid != batch.uid:
+                self._s1_uid = None                             # another batch runs through the model
+            s1 = None
+            if self._knob["ax_reuse"]:
+                s1 = batch.ax if batch.ax is not None else (bufs["s1"] if self._s1_uid is not None else None)
+            if s1 is not None:
+                D.gcn_conv_fwd_pre(ctx, s1, p["w1"], p["b1"], bufs["y1"], act="relu", prec=prec)
+            else:
+                D.gcn_conv_fwd(ctx, batch.a, batch.x, p["w1"], p["b1"], bufs["y1"], act="relu", s=bufs["s1"] if keep else None,
+                               prec=prec)
+                if keep and self._knob["ax_reuse"]:
+                    self._s1_uid = batch.uid
+            bufs["_s1"] = s1 if s1 is not None else bufs["s1"]  # the S operand of dW1
             # with a backward pass to follow, layer 2's launch also writes [Y2 > 0] as bytes: the backward launch only tests
             # Y2 for > 0 and gathers the byte image instead (a quarter of the bytes and of the loads; GCNX_MASK8=0: fp32 rows).
             # In a training step with the head folded in nothing else reads Y2: its fp32 store is dropped (loss_and_grads
@@ -429,10 +462,10 @@ class GCN2(_GraphRunner):
                                        bufs["dz"], bufs["dz2"], db1=g["b1"], mode=self.pool, scratch=self._defer_scratch(batch),
                                        w2t=bufs["w2t"], prec=prec, head=ha, mask8=bufs.get("_mask8"))
             if lr is None:
-                D.gemm_dw2(ctx, bufs["s1"], bufs["dz2"], g["w1"], bufs["s2"], bufs["dz"], g["w2"], prec="f32",
+                D.gemm_dw2(ctx, bufs["_s1"], bufs["dz2"], g["w1"], bufs["s2"], bufs["dz"], g["w2"], prec="f32",
                            grads=self.flat_g.flat(0, self.n_params), pending=pend, leaf=ha)
                 return False
-            D.gemm_dw2(ctx, bufs["s1"], bufs["dz2"], g["w1"], bufs["s2"], bufs["dz"], g["w2"], prec="f32", params=self.flat_p,
+            D.gemm_dw2(ctx, bufs["_s1"], bufs["dz2"], g["w1"], bufs["s2"], bufs["dz"], g["w2"], prec="f32", params=self.flat_p,
                        grads=self.flat_g.flat(0, self.n_params), lr=lr, pending=pend, leaf=ha)
             return True
         act16 = bool(bufs.get("act16"))

@@ -146,6 +146,13 @@ GCNX_API int gcnx_collate(gcnx_ctx* ctx, const int32_t* desc, int32_t b, const i
                  const int32_t* colidx, const float* vals, const float* x, int64_t ldx, int32_t f, const float* y,
                  int32_t c, int32_t* o_rowptr, int32_t* o_colidx, float* o_vals, float* o_x, int64_t ldo, float* o_y,
                  int32_t* o_graph_ptr, int32_t* o_node_graph);
+/* gcnx_collate that also gathers the selected graphs' rows of a second per-node matrix s [Ntot, f] (lds) into o_s [N, f]
+ * (ldos) in the same launch: the aggregated features A x of the resident union, a per-graph constant because the filter of
+ * a disjoint union is block-diagonal.  s == NULL (then o_s is ignored): exactly gcnx_collate. */
+GCNX_API int gcnx_collate2(gcnx_ctx* ctx, const int32_t* desc, int32_t b, const int32_t* node_ptr, const int32_t* rowptr,
+                 const int32_t* colidx, const float* vals, const float* x, int64_t ldx, int32_t f, const float* y,
+                 int32_t c, int32_t* o_rowptr, int32_t* o_colidx, float* o_vals, float* o_x, int64_t ldo, float* o_y,
+                 int32_t* o_graph_ptr, int32_t* o_node_graph, const float* s, int64_t lds, float* o_s, int64_t ldos);
 /* Spektral GCNConv.preprocess = gcn_filter on a CSR whose every row stores its
  * diagonal entry (true for the reference's data: gcn_utills.py:224-227 keeps the 0-Angstrom
  * diagonal).  vals_in NULL = ones.  SPEKTRAL: diag += 1; PYG: existing loops kept.
@@ -641,6 +648,13 @@ GCNX_API int gcnx_gcn_conv_fwd(gcnx_ctx* ctx, const int32_t* rowptr, const int32
                       const float* x, int64_t ldx, int32_t n, int32_t fi, const float* w, int32_t fo,
                       const float* bias, int act, float* s, int64_t lds, float* out, int64_t ldo, float* wt_out,
                       int prec);
+/* The same layer on a stored aggregate: out[n, fo] = act(s w + bias) with s = A x [n, fi] as gcnx_gcn_conv_fwd wrote it
+ * (or as the loader gathered it: A x of a layer's INPUT is a constant of the batch).  No CSR, no gather, no S store; the
+ * product and the epilogue are those of gcnx_gcn_conv_fwd operation for operation, so `out` is bit-identical to that
+ * call's on the (A, x) that produced s.  Same shape and alignment rules (lds in the place of ldx): GCNX_ERR_UNSUPPORTED
+ * otherwise. */
+GCNX_API int gcnx_gcn_conv_fwd_pre(gcnx_ctx* ctx, const float* s, int64_t lds, int32_t n, int32_t fi, const float* w,
+                      int32_t fo, const float* bias, int act, float* out, int64_t ldo, int prec);
 /* gcnx_gcn_conv_fwd with the global pool's partial sums out of the same launch (GlobalSumPool / GlobalAvgPool over the
  * layer's output, gcn.py:334): node_graph [n] is the DisjointLoader id vector `i` (non-decreasing, values in [0, b)), b the
  * number of graphs.  Row t + g of tile_part / tile_cnt ((ceil(n / 32) + b) rows of fo floats each, 16-byte aligned) receives the

@@ -29,6 +29,9 @@ def timeit(fn, iters=50):
     return e1.elapsed_ms_since(e0) / iters * 1e3
 
 print("fwd  (S, W^T out): %.1f us" % timeit(lambda: D.gcn_conv_fwd(ctx, a, x, w, b, out, act="relu", s=s, wt=wt)))
+y_pre = ctx.empty((hb.n, f))
+print("fwd  (stored A X): %.1f us" % timeit(lambda: D.gcn_conv_fwd_pre(ctx, s, w, b, y_pre, act="relu")))   # GCNX_PRE_GRID (tuning build): workgroups
+assert np.array_equal(y_pre.numpy().view(np.uint32), out.numpy().view(np.uint32))
 print("fwd  (inference) : %.1f us" % timeit(lambda: D.gcn_conv_fwd(ctx, a, x, w, b, out, act="relu")))
 print("bwd              : %.1f us" % timeit(lambda: D.gcn_conv_bwd_pool(ctx, at, out, seg, dp, w, s, dz2, dz1, db1=g.flat(2 * f * f, f), scratch=scratch, w2t=wt)))
 tp, tc = ctx.zeros((D.pool_tile_rows(hb.n, 32), f)), ctx.zeros((D.pool_tile_rows(hb.n, 32), f))
