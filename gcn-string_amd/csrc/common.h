@@ -107,33 +107,73 @@ int gcnx_gemm_dw_panels(gcnx_ctx* ctx, const float* x, int64_t ldx, const float*
                         int32_t fi, int32_t fo, int prec);
 #ifdef __HIPCC__
 // Column sums of a few hundred partial rows [rows][f] (f % 4 == 0): workgroup bx owns 8 columns (two float4 lanes)
-// x 128 row groups and folds the 128 partial sums in a fixed tree through LDS.  (colsum_kernel's 64 columns x 16 row
+// x 128 row groups and folds the 128 partial sums in a fixed tree.  (colsum_kernel's 64 columns x 16 row
 // groups would leave config 2's 642 rows to 2 workgroups walking 40 dependent trips each: 22 us against 6.)
 // A device function so that it can share a launch with the split-K reduction (gemm.hip, gcnx_dense_bwd).
-__device__ __forceinline__ void gcnx_colpart_reduce_body(const float* __restrict__ part, int64_t rows, int32_t f,
-                                                         float* __restrict__ out, int bx, float4 (*s)[2]) {
+//
+// Row group rg adds rows rg, rg + 128, ... in ascending order from +0.f, sixteen rows per trip, every load of a trip
+// issued before its first add and no branch inside: the loads go through a buffer descriptor that ends with the last
+// row, so a slot past it returns +0.f from the range check (no bit of the sum changes).  The tree is
+// s[rg] += s[rg + off] for off = 64, 32, ..., 1: its first two rounds cross waves and go through LDS; from off = 16
+// on both operands sit in wave 0 (lane = 2 rg + cl), so the last five rounds are lane shifts without a barrier --
+// the same additions in the same order.
+// gcnx_colpart_reduce_sum returns the sums of columns c .. c + 3 to the two threads with rg == 0.
+typedef float gcnx_f32x4 __attribute__((ext_vector_type(4)));
+constexpr int kColpartTrip = 16;                 // rows per thread and trip
+constexpr int32_t kColpartFMax = 1 << 18;        // a trip's 32-bit offsets: 2048 rows of f floats stay below 4 GiB
+
+__device__ __forceinline__ float4 gcnx_colpart_reduce_sum(const float* __restrict__ part, int64_t rows, int32_t f, int bx,
+                                                          float4 (*s)[2]) {
+  constexpr int kU = kColpartTrip;
   const int cl = threadIdx.x & 1, rg = threadIdx.x >> 1;
   const int c = bx * 8 + cl * 4;
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (c < f) {
-#pragma unroll 4
+  if (c < f && f > kColpartFMax) {                          // (rows of over a MiB: plain loads)
     for (int64_t r = rg; r < rows; r += 128) {
       const float4 v = *reinterpret_cast<const float4*>(part + r * f + c);
       acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
     }
-  }
-  s[rg][cl] = acc;
-  __syncthreads();
-  for (int off = 64; off > 0; off >>= 1) {
-    if (rg < off) {
-      const float4 o = s[rg + off][cl];
-      float4 m = s[rg][cl];
-      m.x += o.x; m.y += o.y; m.z += o.z; m.w += o.w;
-      s[rg][cl] = m;
+  } else if (c < f) {
+    const uint32_t off0 = ((uint32_t)rg * (uint32_t)f + (uint32_t)c) * 4u, step = 512u * (uint32_t)f;
+    for (int64_t r0 = 0; r0 < rows; r0 += kU * 128) {       // (uniform trip count)
+      const uint32_t nrow = (uint32_t)(rows - r0 < kU * 128 ? rows - r0 : kU * 128);
+      const __amdgpu_buffer_rsrc_t rs =
+          __builtin_amdgcn_make_buffer_rsrc((void*)(part + r0 * f), (short)0, (int)(nrow * (uint32_t)f * 4u), 0x00020000);
+      gcnx_f32x4 v[kU];
+#pragma unroll
+      for (int u = 0; u < kU; ++u)
+        v[u] = __builtin_bit_cast(gcnx_f32x4, __builtin_amdgcn_raw_buffer_load_b128(   // (past the last row: an offset no descriptor holds)
+            rs, (uint32_t)(rg + u * 128) < nrow ? off0 + (uint32_t)u * step : 0xFFFFFFF0u, 0, 0));
+      __builtin_amdgcn_sched_barrier(0);                    // no add moves up between the loads
+#pragma unroll
+      for (int u = 0; u < kU; ++u) { acc.x += v[u].x; acc.y += v[u].y; acc.z += v[u].z; acc.w += v[u].w; }
     }
-    __syncthreads();
   }
-  if (rg == 0 && c < f) *reinterpret_cast<float4*>(out + c) = s[0][cl];
+  if (rg >= 32) s[rg][cl] = acc;
+  __syncthreads();
+  if (rg < 64) {
+    const float4 o = s[rg + 64][cl];
+    acc.x += o.x; acc.y += o.y; acc.z += o.z; acc.w += o.w;
+    if (rg >= 32) s[rg][cl] = acc;
+  }
+  __syncthreads();
+  if (rg < 32) {                                           // wave 0
+    const float4 o = s[rg + 32][cl];
+    acc.x += o.x; acc.y += o.y; acc.z += o.z; acc.w += o.w;
+#pragma unroll
+    for (int off = 16; off > 0; off >>= 1) {
+      acc.x += __shfl_down(acc.x, 2 * off); acc.y += __shfl_down(acc.y, 2 * off);
+      acc.z += __shfl_down(acc.z, 2 * off); acc.w += __shfl_down(acc.w, 2 * off);
+    }
+  }
+  return acc;
+}
+
+__device__ __forceinline__ void gcnx_colpart_reduce_body(const float* __restrict__ part, int64_t rows, int32_t f,
+                                                         float* __restrict__ out, int bx, float4 (*s)[2]) {
+  const float4 t = gcnx_colpart_reduce_sum(part, rows, f, bx, s);
+  const int c = bx * 8 + (threadIdx.x & 1) * 4;
+  if ((threadIdx.x >> 1) == 0 && c < f) *reinterpret_cast<float4*>(out + c) = t;
 }
 #endif
 

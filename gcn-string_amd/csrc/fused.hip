@@ -95,19 +95,35 @@ __device__ __forceinline__ float4 f4step(float4 a) {
   return make_float4(lo[0], lo[1], hi[0], hi[1]);
 }
 
-// Gather of the byte image: one 16-byte load carries 16 mask bytes (16 columns of the gathered row); v_cvt_f32_ubyte0..3
-// turns a byte into 0.0f / 1.0f, which is what the four v_pk_mul_f32 of f4step cost per float4 of an fp32 row.
-constexpr int kM8B = 16;          // mask bytes (= columns) per lane and load
-constexpr int kM8U = 4;           // entries per trip
-typedef unsigned m8x16 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ m8x16 m8load(__amdgpu_buffer_rsrc_t rs, unsigned off) {
-  return __builtin_bit_cast(m8x16, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0));
+// Gather of the byte image: a lane loads K / 16 mask bytes (as many columns of the gathered row) per entry -- 8 at K = 128,
+// one 8-byte load -- so a row takes 16 lanes whatever K is, a wave holds four rows and all eight waves gather the tile's 32
+// rows (with 16 bytes per lane a row took 8 lanes and only four waves had rows).  v_cvt_f32_ubyte0..3 turns a byte into
+// 0.0f / 1.0f, which is what the four v_pk_mul_f32 of f4step cost per float4 of an fp32 row.
+constexpr int kM8B = 8;           // most mask bytes (= columns) per lane and load
+constexpr int kM8U = 8;           // entries per trip
+typedef unsigned m8x2 __attribute__((ext_vector_type(2)));
+template <int MLB> struct M8Bytes { typedef unsigned type; };          // 2 or 4 bytes: one register
+template <> struct M8Bytes<8> { typedef m8x2 type; };
+template <int MLB>
+__device__ __forceinline__ typename M8Bytes<MLB>::type m8load(__amdgpu_buffer_rsrc_t rs, unsigned off) {
+  if constexpr (MLB == 8) return __builtin_bit_cast(m8x2, __builtin_amdgcn_raw_buffer_load_b64(rs, off, 0, 0));
+  else if constexpr (MLB == 4) return (unsigned)__builtin_amdgcn_raw_buffer_load_b32(rs, off, 0, 0);
+  else return (unsigned)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(rs, off, 0, 0);
 }
-__device__ __forceinline__ void m8fma(float v, m8x16 m, float (&a)[kM8B]) {
+template <int MLB>
+__device__ __forceinline__ typename M8Bytes<MLB>::type m8own(const unsigned char* q) {   // the same bytes by a plain load
+  if constexpr (MLB == 8) return *reinterpret_cast<const m8x2*>(q);
+  else if constexpr (MLB == 4) return *reinterpret_cast<const unsigned*>(q);
+  else return (unsigned)*reinterpret_cast<const unsigned short*>(q);
+}
+template <int MLB>
+__device__ __forceinline__ unsigned m8word(typename M8Bytes<MLB>::type m, int d) {       // bytes 4 d .. 4 d + 3
+  if constexpr (MLB == 8) return m[d]; else return m;
+}
+template <int MLB>
+__device__ __forceinline__ void m8fma(float v, typename M8Bytes<MLB>::type m, float (&a)[MLB]) {
 #pragma unroll
-  for (int d = 0; d < kM8B / 4; ++d)
-#pragma unroll
-    for (int k = 0; k < 4; ++k) a[4 * d + k] = fmaf(v, (float)((m[d] >> (8 * k)) & 0xffu), a[4 * d + k]);
+  for (int c = 0; c < MLB; ++c) a[c] = fmaf(v, (float)((m8word<MLB>(m, c / 4) >> (8 * (c % 4))) & 0xffu), a[c]);
 }
 
 // The classifier head inside the backward launch: pooled sums of a graph (this lane's 4 of the K columns; LPR lanes hold
@@ -140,12 +156,13 @@ __device__ __forceinline__ float2 fused_head_dlogits(const FusedArgs& p, float4 
 // X3: the product phase on the bf16 MFMA with split operands (hi = bf16(x), lo = bf16(x - hi); hi*lo + lo*hi + hi*hi, fp32
 // accumulate: GCNX_PREC_BF16X3, ~2^-17 per operand) instead of exact fp32 products -- three 16x16x32 MFMAs per 32 k where
 // the fp32 path issues eight 16x16x4.
-// M8 (backward only): the gathered operand is the byte image of [Y2 > 0] (FusedArgs::m8), kM8B bytes per lane and load and
+// M8 (backward only): the gathered operand is the byte image of [Y2 > 0] (FusedArgs::m8), K / 16 bytes per lane and load and
 // kM8U entries per trip; every row is still accumulated by ONE lane group in CSR order, acc = fma(w, m, acc) with m in {0, 1}:
 // the operations and the order of the fp32-row form, so the two forms agree bit for bit.
 template <int K, bool WEIGHTED, bool BWD, bool X3 = false, bool M8 = false>
 __global__ __launch_bounds__(512, 6) void gcn_conv_fused_kernel(FusedArgs p) {
-  constexpr int MLB = kM8B, UM = kM8U;
+  constexpr int MLB = K / 16 < kM8B ? K / 16 : kM8B, UM = kM8U;   // 16 lanes per mask row
+  typedef typename M8Bytes<MLB>::type m8v;
   constexpr int HL = K / 4;                  // lanes per row of the head's partial sums (float4 each)
   constexpr int LPR = M8 ? K / MLB : K / 4;  // lanes per gathered row
   constexpr int CPL = K / LPR;               // columns per lane
@@ -322,7 +339,7 @@ __global__ __launch_bounds__(512, 6) void gcn_conv_fused_kernel(FusedArgs p) {
     // the same loop on the byte image: UM loads of MLB bytes in flight per lane, one row per lane group
     const unsigned subb = (unsigned)sub * (unsigned)MLB;
     for (int tt = 0; __builtin_amdgcn_ballot_w64(tt < len) != 0; tt += UM) {
-      m8x16 hv[UM];
+      m8v hv[UM];
       float wv[UM];
       const int eb_ = min(ea[0] + tt, ebf[0]);
 #pragma unroll
@@ -330,12 +347,12 @@ __global__ __launch_bounds__(512, 6) void gcn_conv_fused_kernel(FusedArgs p) {
         const int e = eb_ + u;
         const int2 en = s_ent[e];
         wv[u] = __int_as_float(en.y);
-        hv[u] = m8load(xr, e < ebf[0] ? (unsigned)en.x + subb : 0xFFFFFFF0u);
+        hv[u] = m8load<MLB>(xr, e < ebf[0] ? (unsigned)en.x + subb : 0xFFFFFFF0u);
       }
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int u = 0; u < UM; ++u) {
-        m8fma(wv[u], hv[u], am);
+        m8fma<MLB>(wv[u], hv[u], am);
         // the next entry's bytes become visible to the compiler only here, behind this entry's first fma: hipcc otherwise
         // converts the whole trip first (UM * MLB floats alive: spills) and waits for all loads at once (vmcnt(0))
         if (u + 1 < UM) asm volatile("" : "+v"(hv[u + 1]), "+v"(am[0]));
@@ -344,7 +361,7 @@ __global__ __launch_bounds__(512, 6) void gcn_conv_fused_kernel(FusedArgs p) {
     if (e1 - e0 > kFCap) {
       for (int e = max(eb[0] > 0 ? s_rp[gid] - e0 : 0, kFCap); e < eb[0]; ++e) {
         const float v = WEIGHTED ? p.vals[e0 + e] : 1.0f;
-        m8fma(v, m8load(xr, (unsigned)p.colidx[e0 + e] * ld4 + subb), am);
+        m8fma<MLB>(v, m8load<MLB>(xr, (unsigned)p.colidx[e0 + e] * ld4 + subb), am);
       }
     }
   } else {
@@ -382,9 +399,9 @@ __global__ __launch_bounds__(512, 6) void gcn_conv_fused_kernel(FusedArgs p) {
   }
   }
   float4 own[RPG], dscale[RPG];   // backward: pool'(dPooled) of the row's graph, and the row's own [Y2 > 0] row (dZ2 out)
-  m8x16 ownm = {};
+  m8v ownm = {};
   if constexpr (M8) {
-    if (grow[0] >= 0 && p.dz2) ownm = *reinterpret_cast<const m8x16*>(p.m8 + (int64_t)(r0 + gid) * p.ldm8 + sub * MLB);
+    if (grow[0] >= 0 && p.dz2) ownm = m8own<MLB>(p.m8 + (int64_t)(r0 + gid) * p.ldm8 + sub * MLB);
     if (p.hd_part && !(dbg & 32)) __syncthreads();     // (as below; the scale is formed four columns at a time at the tile write)
   } else
   if (BWD) {
@@ -454,26 +471,55 @@ __global__ __launch_bounds__(512, 6) void gcn_conv_fused_kernel(FusedArgs p) {
       float sc = 1.0f;
       if (g >= 0 && p.hd_part) dl = s_dl[(g - g_first) & (kFRows - 1)];
       else if (g >= 0 && p.avg) sc = 1.0f / (float)(p.gp[g + 1] - p.gp[g]);
+      // The lane's CPL columns go out W at a time.  At CPL = 8 the eight lanes that one pass of a ds_write_b128 serves hold
+      // sub = 0 .. 7 or 8 .. 15 of one row: written in column order they would start at 8 sub + 4 q, four distinct bank
+      // groups for eight lanes.  The lanes with bit 2 of sub set write their upper four columns first: 8 sub + 4 (q ^ qs)
+      // covers all 32 banks in either pass.  (CPL = 4: 4 sub, CPL = 2 and ds_write_b64: 2 sub -- distinct as they are.)
+      constexpr int W = CPL < 4 ? CPL : 4, NQ = CPL / W;
+      const bool qs = NQ == 2 && ((sub >> 2) & 1);
+      auto ldw = [](const float* q_, float (&o)[W]) {
+        if constexpr (W == 4) { const float4 v = *reinterpret_cast<const float4*>(q_); o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w; }
+        else { const float2 v = *reinterpret_cast<const float2*>(q_); o[0] = v.x; o[1] = v.y; }
+      };
+      auto stw = [](float* q_, const float (&o)[W]) {
+        if constexpr (W == 4) *reinterpret_cast<float4*>(q_) = make_float4(o[0], o[1], o[2], o[3]);
+        else *reinterpret_cast<float2*>(q_) = make_float2(o[0], o[1]);
+      };
+      // pool'(dPooled) of both column slots first: their loads are out before the first store needs them
+      float d[NQ][W];
 #pragma unroll
-      for (int q = 0; q < CPL / 4; ++q) {
-        const int c = sub * CPL + 4 * q;
-        float4 d = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (g >= 0 && (dbg & 32)) d = make_float4(1.f, 1.f, 1.f, 1.f);
-        else if (g >= 0 && p.hd_part) {
-          const float4 w0 = *reinterpret_cast<const float4*>(&s_w3[0][c]), w1 = *reinterpret_cast<const float4*>(&s_w3[1][c]);
-          d = make_float4(fmaf(dl.y, w1.x, dl.x * w0.x), fmaf(dl.y, w1.y, dl.x * w0.y), fmaf(dl.y, w1.z, dl.x * w0.z),
-                          fmaf(dl.y, w1.w, dl.x * w0.w));
+      for (int q = 0; q < NQ; ++q) {
+        const int c = sub * CPL + W * (q ^ (int)qs);
+#pragma unroll
+        for (int k = 0; k < W; ++k) d[q][k] = (g >= 0 && (dbg & 32)) ? 1.f : 0.f;
+        if (g >= 0 && (dbg & 32)) {
+        } else if (g >= 0 && p.hd_part) {
+          float w0[W], w1[W];
+          ldw(&s_w3[0][c], w0); ldw(&s_w3[1][c], w1);
+#pragma unroll
+          for (int k = 0; k < W; ++k) d[q][k] = fmaf(dl.y, w1[k], dl.x * w0[k]);
         } else if (g >= 0) {
-          d = *reinterpret_cast<const float4*>(p.dp + (int64_t)g * p.lddp + c);
-          if (p.avg) { d.x *= sc; d.y *= sc; d.z *= sc; d.w *= sc; }
+          ldw(p.dp + (int64_t)g * p.lddp + c, d[q]);
+          if (p.avg) {
+#pragma unroll
+            for (int k = 0; k < W; ++k) d[q][k] *= sc;
+          }
         }
+      }
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) {
+        const int c = sub * CPL + W * (q ^ (int)qs);
+        const bool hi = NQ == 2 && ((q != 0) != qs);       // the slot holds the lane's upper W columns
+        float o[W];
         if (p.dz2 && r < nr && !(dbg & 8)) {
-          const unsigned ow = ownm[q];                   // the row's own bytes of these four columns, as 0.0f / 1.0f
-          *reinterpret_cast<float4*>(p.dz2 + (int64_t)(r0 + r) * p.lddz2 + c) =
-              make_float4((float)(ow & 0xffu) * d.x, (float)((ow >> 8) & 0xffu) * d.y, (float)((ow >> 16) & 0xffu) * d.z,
-                          (float)(ow >> 24) * d.w);
+          const unsigned ow = hi ? m8word<MLB>(ownm, NQ - 1) : m8word<MLB>(ownm, 0);   // the row's own bytes of these columns, as 0.0f / 1.0f
+#pragma unroll
+          for (int k = 0; k < W; ++k) o[k] = (float)((ow >> (8 * k)) & 0xffu) * d[q][k];
+          stw(p.dz2 + (int64_t)(r0 + r) * p.lddz2 + c, o);
         }
-        *reinterpret_cast<float4*>(&tile[r][c]) = make_float4(am[4 * q] * d.x, am[4 * q + 1] * d.y, am[4 * q + 2] * d.z, am[4 * q + 3] * d.w);
+#pragma unroll
+        for (int k = 0; k < W; ++k) o[k] = (hi ? am[(NQ - 1) * W + k] : am[k]) * d[q][k];
+        stw(&tile[r][c], o);
       }
     }
   } else

@@ -367,18 +367,57 @@ __global__ __launch_bounds__(256) void gemm_f32_dw2_head_kernel(GemmJob ja, Gemm
 // Second stage of the deterministic split-K: out[i] = sum_s part[s][i].  Block = 64 outputs x 4
 // split groups; each group sums its splits in ascending order, the 4 group sums are combined in
 // a fixed order -- the result does not depend on scheduling.
+//
+// One group's share of that sum: workgroup wave `grp` (64 outputs, one per lane) adds its `per` consecutive slabs in
+// ascending order from +0.f.  Every load of a chunk is issued before the first add (16 slabs in flight, 32 when a
+// group has more than 16) and the chunk is branch-free: the loads go through a buffer descriptor that ends with the
+// group's last slab, so a slot past it returns +0.f from the range check without touching memory, and adding +0.f
+// leaves every bit of the sum as it was.  (With one conditional load per trip the 17 slabs of a config-2 group were
+// five dependent round trips, the first a single 4-byte load.)  The descriptor is wave-uniform: slab z, the
+// workgroup's first output; a lane's offset is 4 el + u slab bytes.
+template <int N>
+__device__ __forceinline__ float splitk_chunk(const float* __restrict__ base, int cnt, uint32_t slab_bytes,
+                                              uint32_t lane_bytes, float acc) {
+  // (the descriptor ends inside the chunk's last slab even when a slab is under 64 floats)
+  const uint32_t bytes = (uint32_t)(min(cnt, N) - 1) * slab_bytes + min(256u, slab_bytes);
+  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)base, (short)0, (int)bytes, 0x00020000);
+  float v[N];
+#pragma unroll
+  for (int u = 0; u < N; ++u)
+    v[u] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(   // (past the group: an offset no descriptor holds)
+        rs, lane_bytes + (u < cnt ? (uint32_t)u * slab_bytes : 0xFFFFFE00u), 0, 0));
+  __builtin_amdgcn_sched_barrier(0);                                   // no add moves up between the loads
+#pragma unroll
+  for (int u = 0; u < N; ++u) acc += v[u];
+  return acc;
+}
+
+// A chunk's offsets are 32-bit: 31 slabs + 256 bytes must stay below 4 GiB
+constexpr int64_t kSplitkSlabMax = (int64_t)1 << 25;
+
+// (bx: the workgroup's block of 64 outputs, el: the lane's output in it)
+__device__ __forceinline__ float splitk_group_sum(const float* __restrict__ part, int64_t slab, int nsplit, int bx, int el) {
+  const int grp = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // = the wave
+  const int per = (nsplit + 3) / 4;
+  const int z0 = grp * per, z1 = min(nsplit, z0 + per);
+  const float* base = part + (int64_t)z0 * slab + (int64_t)bx * 64;
+  float acc = 0.f;
+  if (slab > kSplitkSlabMax) {                                         // (a 128 MiB slab: plain loads)
+    for (int z = z0; z < z1; ++z) acc += base[(int64_t)(z - z0) * slab + el];
+  } else if (per <= 16) {
+    if (z0 < z1) acc = splitk_chunk<16>(base, z1 - z0, (uint32_t)slab * 4u, 4u * (uint32_t)el, acc);
+  } else {
+    for (int z = z0; z < z1; z += 32)
+      acc = splitk_chunk<32>(base + (int64_t)(z - z0) * slab, z1 - z, (uint32_t)slab * 4u, 4u * (uint32_t)el, acc);
+  }
+  return acc;
+}
+
 __device__ __forceinline__ void splitk_reduce_body(const float* __restrict__ part, int64_t slab, int nsplit,
                                                    float* __restrict__ out, int64_t total, int bx, float (*s)[64]) {
   const int el = threadIdx.x & 63, grp = threadIdx.x >> 6;
   const int64_t i = (int64_t)bx * 64 + el;
-  float acc = 0.f;
-  if (i < total) {
-    const int per = (nsplit + 3) / 4;
-    const int z0 = grp * per, z1 = min(nsplit, z0 + per);
-#pragma unroll 4
-    for (int z = z0; z < z1; ++z) acc += part[(int64_t)z * slab + i];
-  }
-  s[grp][el] = acc;
+  s[grp][el] = i < total ? splitk_group_sum(part, slab, nsplit, bx, el) : 0.f;
   __syncthreads();
   if (grp == 0 && i < total) out[i] = (s[0][el] + s[1][el]) + (s[2][el] + s[3][el]);
 }
@@ -437,17 +476,10 @@ struct SgdPending {
   int n_pc, n_ps;
 };
 
-__device__ __forceinline__ float splitk_sum(const float* __restrict__ part, int64_t slab, int nsplit, int64_t i,
+__device__ __forceinline__ float splitk_sum(const float* __restrict__ part, int64_t slab, int nsplit, int bx,
                                             int64_t total, float (*s)[64]) {
   const int el = threadIdx.x & 63, grp = threadIdx.x >> 6;
-  float acc = 0.f;
-  if (i < total) {
-    const int per = (nsplit + 3) / 4;
-    const int z0 = grp * per, z1 = min(nsplit, z0 + per);
-#pragma unroll 4
-    for (int z = z0; z < z1; ++z) acc += part[(int64_t)z * slab + i];
-  }
-  s[grp][el] = acc;
+  s[grp][el] = (int64_t)bx * 64 + el < total ? splitk_group_sum(part, slab, nsplit, bx, el) : 0.f;
   __syncthreads();
   return (s[0][el] + s[1][el]) + (s[2][el] + s[3][el]);              // the order of splitk_reduce_kernel
 }
@@ -459,29 +491,38 @@ __global__ __launch_bounds__(256) void reduce_sgd_kernel(const float* __restrict
   const float lr = lr_dev ? *lr_dev : lr_arg;            // (gcnx_set_lr_source)
   __shared__ float4 s4[128][2];
   float (*s)[64] = reinterpret_cast<float(*)[64]>(&s4[0][0]);
+  // Every branch loads its parameters BEFORE the partial sums, so that the load travels with them: only p - lr * g
+  // and the stores stay behind the sum.
   int bid = blockIdx.x;
   if (bid < n_s) {
     const int64_t i = (int64_t)bid * 64 + (threadIdx.x & 63);
-    const float g = splitk_sum(part, slab, nsplit, i, total, s);
-    if ((threadIdx.x >> 6) == 0 && i < total) { grads[off + i] = g; if (params) params[off + i] = params[off + i] - lr * g; }
+    const bool own = (threadIdx.x >> 6) == 0 && i < total;
+    const float p = own && params ? params[off + i] : 0.f;
+    const float g = splitk_sum(part, slab, nsplit, bid, total, s);
+    if (own) { grads[off + i] = g; if (params) params[off + i] = p - lr * g; }
     return;
   }
   bid -= n_s;
   if (bid < pd.n_pc) {
-    gcnx_colpart_reduce_body(pd.cpart, pd.crows, pd.cf, grads + pd.coff, bid, s4);       // writes grads (all threads sync inside)
     const int cl = threadIdx.x & 1, c = bid * 8 + cl * 4;
-    if ((threadIdx.x >> 1) == 0 && c < pd.cf && params) {
-      const float4 g = s4[0][cl];
-      float* p = params + pd.coff + c;
-      p[0] -= lr * g.x; p[1] -= lr * g.y; p[2] -= lr * g.z; p[3] -= lr * g.w;
+    const bool own = (threadIdx.x >> 1) == 0 && c < pd.cf;
+    float* pp = params + pd.coff + c;
+    float p0 = 0.f, p1 = 0.f, p2 = 0.f, p3 = 0.f;
+    if (own && params) { p0 = pp[0]; p1 = pp[1]; p2 = pp[2]; p3 = pp[3]; }
+    const float4 g = gcnx_colpart_reduce_sum(pd.cpart, pd.crows, pd.cf, bid, s4);
+    if (own) {
+      *reinterpret_cast<float4*>(grads + pd.coff + c) = g;
+      if (params) { pp[0] = p0 - lr * g.x; pp[1] = p1 - lr * g.y; pp[2] = p2 - lr * g.z; pp[3] = p3 - lr * g.w; }
     }
     return;
   }
   bid -= pd.n_pc;
   if (bid < pd.n_ps) {
     const int64_t i = (int64_t)bid * 64 + (threadIdx.x & 63);
-    const float g = splitk_sum(pd.slabs, pd.total, pd.nsplit, i, pd.total, s);
-    if ((threadIdx.x >> 6) == 0 && i < pd.total) { grads[pd.soff + i] = g; if (params) params[pd.soff + i] = params[pd.soff + i] - lr * g; }
+    const bool own = (threadIdx.x >> 6) == 0 && i < pd.total;
+    const float p = own && params ? params[pd.soff + i] : 0.f;
+    const float g = splitk_sum(pd.slabs, pd.total, pd.nsplit, bid, pd.total, s);
+    if (own) { grads[pd.soff + i] = g; if (params) params[pd.soff + i] = p - lr * g; }
     return;
   }
   bid -= pd.n_ps;
@@ -1490,7 +1531,14 @@ int gcnx_gemm_dw2(gcnx_ctx* ctx, const float* xa, int64_t ldxa, const float* dha
   const bool merged = leaf && leaf->c == 2 && gcnx_head::head_lds_floats(leaf->h, leaf->c, want_db) <= (size_t)kDw2HeadLds &&
                       leaf->b <= gcnx_head::kHeadRows;
   if (leaf && !merged) { rc = gcnx_head_from_parts(ctx, leaf); if (rc) return rc; }   // (many graphs / wide operands: its own launch)
-  if (merged) {
+#ifdef GCNX_TUNING
+  const char* dbg_env = getenv("GCNX_DW2_DBG");          // 1: no tile launch -- the reduction launch alone, on whatever the
+  const bool tiles_off = dbg_env && atoi(dbg_env) == 1;  // workspace holds (results wrong by design; scripts/fused_bench.py)
+#else
+  constexpr bool tiles_off = false;
+#endif
+  if (tiles_off) {
+  } else if (merged) {
     HeadLeaf hl{leaf->w, leaf->bias, leaf->y, leaf->b, leaf->h, leaf->c, leaf->denom, leaf->probs, leaf->loss_acc, leaf->dw, leaf->db,
                 leaf->dpooled, (int64_t)leaf->h, (int64_t)leaf->h, nullptr, ctx->flag + 3,
                 gcnx_head::PoolParts{leaf->pool_sum, leaf->graph_ptr, leaf->pooled, 1, leaf->pool_mode == GCNX_POOL_AVG ? 1 : 0,

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Fused GCNConv launch times at config-2 shapes (tuning aid): forward, backward, the two-gradient GEMM; HIP events.
 GCNX_FUSED_DBG (tuning build only) ablates phases: 1 no gather, 2 no MFMA, 4 no weight load.  The backward is timed in its
-fp32-row form and in its byte-mask form (gcn_conv_bwd_pool(mask8=...))."""
+fp32-row form and in its byte-mask form (gcn_conv_bwd_pool(mask8=...)).  GCNX_DW2_DBG=1 (tuning build, set here) leaves the
+two-gradient GEMM's reduction launch on its own; that line needs GCNX_LIB=.../libgcnx_tuning.so (scripts/build_tuning.sh)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "gcn-string_amd"))
@@ -47,6 +48,16 @@ D.gcn_conv_fwd(ctx, a, x, w, b, out, act="relu", s=s, wt=wt, pool=(seg, tp, tc),
 print("bwd  (byte mask)  : %.1f us" % timeit(lambda: D.gcn_conv_bwd_pool(ctx, at, None, seg, dp, w, s, dz2, dz1, db1=g.flat(2 * f * f, f), scratch=scratch, w2t=wt, mask8=m8)))
 print("bwd  (byte mask, head inside): %.1f us" % timeit(lambda: D.gcn_conv_bwd_pool(ctx, at, None, seg, None, w, s, dz2, dz1, db1=g.flat(2 * f * f, f), scratch=scratch, w2t=wt, head=ha, mask8=m8)))
 print("dw2              : %.1f us" % timeit(lambda: D.gemm_dw2(ctx, s, dz1, g.flat(0, f * f, (f, f)), s, dz2, g.flat(f * f, f * f, (f, f)), grads=g)))
+# the reduction launch alone (tuning build: GCNX_DW2_DBG=1 drops the tile launch): dW1's and dW2's split-K slabs, the pending db1
+# partial rows of the backward launch and the SGD step, at the slab shape the calls above leave behind
+if os.environ.get("GCNX_LIB", "").endswith("tuning.so"):
+    par = ctx.to_device(rng.standard_normal(2 * f * f + f, dtype=np.float32))
+    pend = D.gcn_conv_bwd_pool(ctx, at, None, seg, dp, w, s, dz2, dz1, db1=g.flat(2 * f * f, f), scratch=scratch, w2t=wt, mask8=m8)
+    dw2_sgd = lambda: D.gemm_dw2(ctx, s, dz1, g.flat(0, f * f, (f, f)), s, dz2, g.flat(f * f, f * f, (f, f)), params=par, grads=g, lr=1e-3, pending=pend)
+    print("dw2 + reduce + sgd: %.1f us" % timeit(dw2_sgd))
+    os.environ["GCNX_DW2_DBG"] = "1"
+    print("reduce + sgd alone (%d partial rows): %.1f us" % (pend.crows, timeit(dw2_sgd)))
+    del os.environ["GCNX_DW2_DBG"]
 h = ctx.empty((hb.n, f))
 print("gemm + spmm      : %.1f us" % timeit(lambda: (D.gemm(ctx, x, w, None, h), D.spmm(ctx, a, h, b, out, act="relu"))))
 ctx.close()
