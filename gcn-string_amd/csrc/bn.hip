@@ -458,7 +458,6 @@ __global__ __launch_bounds__(256) void bn_act_bwd_small_kernel(const float* __re
   }
 }
 
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // dalpha[0] = sum over the f columns of sums[2f + c] (the shared slope's gradient): one workgroup, fixed order.
 __device__ __forceinline__ float block_sum256(float v, float* red) {
@@ -640,7 +639,7 @@ int gcnx_bn_stats(gcnx_ctx* ctx, const float* z, int64_t ldz, int64_t n, int32_t
   int rc = gcnx_ws_reserve(ctx, (size_t)nchunks * 2 * f * sizeof(float));
   if (rc) return rc;
   hipLaunchKernelGGL(bn_stats_kernel, dim3(gcnx_cdiv(f, 64), nchunks), dim3(256), 0, ctx->stream, z, ldz, n, f,
-                     shift, (float*)ctx->ws, (int)(al16(z) && ldz % 4 == 0));
+                     shift, (float*)ctx->ws, (int)(gcnx_aligned16(z) && ldz % 4 == 0));
   GCNX_LAUNCH_OK(ctx);
   return reduce_parts(ctx, nchunks, 2, f, sums);
 }
@@ -671,7 +670,7 @@ int gcnx_bn_moments(gcnx_ctx* ctx, const float* z, int64_t ldz, int64_t n, int32
   const int nchunks = gcnx_cdiv(n, kRows);
   int rc = gcnx_ws_reserve(ctx, (size_t)nchunks * 2 * f * sizeof(float));
   if (rc) return rc;
-  const int vec = (int)(al16(z) && ldz % 4 == 0);
+  const int vec = (int)(gcnx_aligned16(z) && ldz % 4 == 0);
   dim3 gs(gcnx_cdiv(f, 64), nchunks), gr(gcnx_cdiv(f, 64));
   if (nchunks == 1) {                                  // a batch of at most kRows rows: both passes in one launch, same bits
     hipLaunchKernelGGL(bn_moments_small_kernel, gr, dim3(256), 0, ctx->stream, z, ldz, n, f, momentum, eps, (float*)ctx->ws, mean, inv,
@@ -705,7 +704,7 @@ int gcnx_bn_act(gcnx_ctx* ctx, const float* z, int64_t ldz, int64_t n, int32_t f
   GCNX_REQUIRE(ctx, ldz >= f && ldy >= f, "gcnx_bn_act: leading dimension too small");
   int gy = gcnx_cdiv(n, 4);
   if (gy > 8 * ctx->num_cus) gy = 8 * ctx->num_cus;
-  const int vec = al16(z) && al16(y) && ldz % 4 == 0 && ldy % 4 == 0;
+  const int vec = gcnx_aligned16(z) && gcnx_aligned16(y) && ldz % 4 == 0 && ldy % 4 == 0;
   hipLaunchKernelGGL(bn_act_kernel, dim3(gcnx_cdiv(f, 256), gy), dim3(256), 0, ctx->stream, z, ldz, n, f, mean, inv, gamma,
                      beta, act, alpha, y, ldy, vec);
   GCNX_LAUNCH_OK(ctx);
@@ -735,7 +734,7 @@ int gcnx_bn_act_bwd_stats(gcnx_ctx* ctx, const float* dy, int64_t lddy, const fl
   const int nchunks = gcnx_cdiv(n, kRows);
   int rc = gcnx_ws_reserve(ctx, (size_t)nchunks * 3 * f * sizeof(float));
   if (rc) return rc;
-  const int vec = al16(dy) && al16(z) && lddy % 4 == 0 && ldz % 4 == 0;
+  const int vec = gcnx_aligned16(dy) && gcnx_aligned16(z) && lddy % 4 == 0 && ldz % 4 == 0;
   hipLaunchKernelGGL(bn_bwd_stats_kernel, dim3(gcnx_cdiv(f, 64), nchunks), dim3(256), 0, ctx->stream, dy, lddy, z, ldz, n,
                      f, mean, inv, gamma, beta, act, alpha, (float*)ctx->ws, vec);
   GCNX_LAUNCH_OK(ctx);
@@ -757,7 +756,7 @@ int gcnx_bn_act_bwd_apply(gcnx_ctx* ctx, const float* dy, int64_t lddy, const fl
   GCNX_REQUIRE(ctx, act < GCNX_ACT_PRELU || alpha, "gcnx_bn_act_bwd: PReLU needs alpha");
   GCNX_REQUIRE(ctx, lddy >= f && ldz >= f && lddz >= f, "gcnx_bn_act_bwd: leading dimension too small");
   GCNX_REQUIRE(ctx, count > 0.f, "gcnx_bn_act_bwd: count must be positive");
-  const int vec = al16(dy) && al16(z) && al16(dz) && lddy % 4 == 0 && ldz % 4 == 0 && lddz % 4 == 0;
+  const int vec = gcnx_aligned16(dy) && gcnx_aligned16(z) && gcnx_aligned16(dz) && lddy % 4 == 0 && ldz % 4 == 0 && lddz % 4 == 0;
   int gy = gcnx_cdiv(n, 4);
   if (gy > 8 * ctx->num_cus) gy = 8 * ctx->num_cus;
   hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(gcnx_cdiv(f, 256), gy), dim3(256), 0, ctx->stream, dy, lddy, z, ldz, n, f,
@@ -777,7 +776,7 @@ int gcnx_bn_act_bwd(gcnx_ctx* ctx, const float* dy, int64_t lddy, const float* z
     GCNX_RANGE(ctx, "batch norm + activation backward (small batch)");
     int rc1 = gcnx_ws_reserve(ctx, (size_t)3 * f * sizeof(float));
     if (rc1) return rc1;
-    const int vec = al16(dy) && al16(z) && al16(dz) && lddy % 4 == 0 && ldz % 4 == 0 && lddz % 4 == 0;
+    const int vec = gcnx_aligned16(dy) && gcnx_aligned16(z) && gcnx_aligned16(dz) && lddy % 4 == 0 && ldz % 4 == 0 && lddz % 4 == 0;
     const bool shared = act == GCNX_ACT_PRELU_SHARED;
     hipLaunchKernelGGL(bn_act_bwd_small_kernel, dim3(gcnx_cdiv(f, 64)), dim3(256), 0, ctx->stream, dy, lddy, z, ldz, n, f, mean, inv, gamma,
                        beta, act, alpha, (float*)ctx->ws, sums_scratch, dbeta, dgamma, shared ? nullptr : dalpha, training, dz, lddz, vec);

@@ -225,6 +225,9 @@ struct GcnxRange {
 
 static inline int gcnx_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
+// What a float4 / b128 access of p needs (host side: the launchers pick their vector forms by it).
+static inline bool gcnx_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
 // Blocks b and b+8 share an XCD (observed round-robin dealing; speed only, never correctness).
 // Bijective remap that gives every XCD one contiguous range of logical work items, so that
 // neighbouring row chunks -- which gather the same feature rows -- share one L2.

@@ -185,7 +185,6 @@ __global__ __launch_bounds__(256) void ecc_bwd_kernel(const int32_t* __restrict_
   }
 }
 
-inline bool ecc_al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // lanes per row: the smallest power of two that covers ceil(f / vec) columns, at most one wave
 inline int ecc_lpr_log2(int32_t f, int vec) {
@@ -216,7 +215,7 @@ int gcnx_ecc_expand(gcnx_ctx* ctx, const int32_t* rowptr_t, const int32_t* colid
   GCNX_REQUIRE(ctx, nnz == 0 || (colidx_t && (sp == 0 || u)), "gcnx_ecc_expand: entries without colidx / u");
   GCNX_REQUIRE(ctx, ldx >= f && ld >= (int64_t)(c + (root ? 1 : 0)) * f && (sp == 0 || ldu >= sp),
                "gcnx_ecc_expand: leading dimension too small");
-  const int vec = (f % 4 == 0 && ldx % 4 == 0 && ld % 4 == 0 && ecc_al16(x) && ecc_al16(scat)) ? 4 : 1;
+  const int vec = (f % 4 == 0 && ldx % 4 == 0 && ld % 4 == 0 && gcnx_aligned16(x) && gcnx_aligned16(scat)) ? 4 : 1;
   const int l2 = ecc_lpr_log2(f, vec);
   const dim3 grid(gcnx_cdiv(n, 256 >> l2), gcnx_cdiv(f, (1 << l2) * vec));
 #define GCNX_ECC_FWD(C_)                                                                                                   \
@@ -255,8 +254,8 @@ int gcnx_ecc_bwd(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, co
   GCNX_REQUIRE(ctx, ldd >= (int64_t)c * f && (!du || (ldx >= f && lddu >= sp)) && (sp == 0 || ldu >= sp) &&
                         (!dx || (lddx >= f && (!dx_root || lddr >= f))),
                "gcnx_ecc_bwd: leading dimension too small");
-  const bool al = f % 4 == 0 && ldd % 4 == 0 && ecc_al16(dscat) && (!du || (ldx % 4 == 0 && ecc_al16(x))) &&
-                  (!dx || (lddx % 4 == 0 && ecc_al16(dx) && (!dx_root || (lddr % 4 == 0 && ecc_al16(dx_root)))));
+  const bool al = f % 4 == 0 && ldd % 4 == 0 && gcnx_aligned16(dscat) && (!du || (ldx % 4 == 0 && gcnx_aligned16(x))) &&
+                  (!dx || (lddx % 4 == 0 && gcnx_aligned16(dx) && (!dx_root || (lddr % 4 == 0 && gcnx_aligned16(dx_root)))));
   const int vec = al ? 4 : 1;
   const int l2 = ecc_lpr_log2(f, vec);
   const dim3 grid(gcnx_cdiv(n, 256 >> l2));

@@ -812,7 +812,6 @@ int launch_fused(gcnx_ctx* ctx, const FusedArgs& a_in, int k, bool x3) {
   return GCNX_OK;
 }
 
-inline bool fal16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline int64_t tiles_of(int64_t n) { return (n + kFRows - 1) / kFRows; }
 
 bool fused_shape_ok(int64_t n, int32_t k, int32_t nc, int64_t ldx) {
@@ -832,10 +831,10 @@ int gcnx_gcn_conv_fwd_mask8(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t*
                             float* tile_part, float* tile_cnt, uint8_t* mask8, int64_t ldmask8) {
   GCNX_CHECK_CTX(ctx);
   GCNX_REQUIRE(ctx, !mask8 || act == GCNX_ACT_RELU, "gcnx_gcn_conv_fwd_mask8: the byte mask is that of a ReLU output");
-  GCNX_REQUIRE(ctx, !mask8 || (ldmask8 >= fo && ldmask8 % 16 == 0 && fal16(mask8)),
+  GCNX_REQUIRE(ctx, !mask8 || (ldmask8 >= fo && ldmask8 % 16 == 0 && gcnx_aligned16(mask8)),
                "gcnx_gcn_conv_fwd_mask8: mask8 must be 16-byte aligned with a leading dimension in multiples of 16 bytes");
   GCNX_RANGE(ctx, "GCNConv forward (one launch)");
-  GCNX_REQUIRE(ctx, (!tile_part && !tile_cnt) || (tile_part && tile_cnt && node_graph && b > 0 && fal16(tile_part) && fal16(tile_cnt)),
+  GCNX_REQUIRE(ctx, (!tile_part && !tile_cnt) || (tile_part && tile_cnt && node_graph && b > 0 && gcnx_aligned16(tile_part) && gcnx_aligned16(tile_cnt)),
                "gcnx_gcn_conv_fwd_pool: the pool's partial sums need node_graph, b > 0 and two 16-byte aligned outputs");
   GCNX_REQUIRE(ctx, n >= 0 && fi >= 0 && fo >= 0, "gcnx_gcn_conv_fwd: negative size");
   if (prec != GCNX_PREC_F32 && prec != GCNX_PREC_BF16X3)
@@ -846,8 +845,8 @@ int gcnx_gcn_conv_fwd_mask8(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t*
     return gcnx_fail(ctx, GCNX_ERR_UNSUPPORTED, "gcnx_gcn_conv_fwd: needs fi in {32, 64, 128}, fo a multiple of 16 up to 128 and "
                      "n * ldx * 4 < 2^32 (got n=%d fi=%d fo=%d): use gcnx_gemm + gcnx_spmm_csr", n, fi, fo);
   GCNX_REQUIRE(ctx, rowptr && colidx && x && w && (out || mask8), "gcnx_gcn_conv_fwd: NULL pointer");
-  GCNX_REQUIRE(ctx, (!out || (ldo >= fo && ldo % 4 == 0 && fal16(out))) && fal16(x) && (!bias || fal16(bias)) &&
-                        (!s || (lds >= fi && lds % 4 == 0 && fal16(s))),
+  GCNX_REQUIRE(ctx, (!out || (ldo >= fo && ldo % 4 == 0 && gcnx_aligned16(out))) && gcnx_aligned16(x) && (!bias || gcnx_aligned16(bias)) &&
+                        (!s || (lds >= fi && lds % 4 == 0 && gcnx_aligned16(s))),
                "gcnx_gcn_conv_fwd: operands must be 16-byte aligned with leading dimensions in multiples of 4 floats");
   GCNX_REQUIRE(ctx, x != out && x != s, "gcnx_gcn_conv_fwd: in-place aggregation is not possible");
   FusedArgs a{};
@@ -885,7 +884,7 @@ int gcnx_gcn_conv_fwd_pre(gcnx_ctx* ctx, const float* s, int64_t lds, int32_t n,
     return gcnx_fail(ctx, GCNX_ERR_UNSUPPORTED, "gcnx_gcn_conv_fwd_pre: needs fi in {32, 64, 128}, fo a multiple of 16 up to 128, lds >= fi "
                      "in multiples of 4 floats and n * lds * 4 < 2^32 (got n=%d fi=%d fo=%d lds=%lld)", n, fi, fo, (long long)lds);
   GCNX_REQUIRE(ctx, s && w && out, "gcnx_gcn_conv_fwd_pre: NULL pointer");
-  GCNX_REQUIRE(ctx, ldo >= fo && ldo % 4 == 0 && fal16(out) && fal16(s) && (!bias || fal16(bias)),
+  GCNX_REQUIRE(ctx, ldo >= fo && ldo % 4 == 0 && gcnx_aligned16(out) && gcnx_aligned16(s) && (!bias || gcnx_aligned16(bias)),
                "gcnx_gcn_conv_fwd_pre: operands must be 16-byte aligned with leading dimensions in multiples of 4 floats");
   GCNX_REQUIRE(ctx, s != out, "gcnx_gcn_conv_fwd_pre: out must not alias s");
   PreArgs a{};
@@ -925,15 +924,15 @@ int conv_bwd_pool(gcnx_ctx* ctx, const int32_t* rowptr_t, const int32_t* colidx_
   GCNX_REQUIRE(ctx, !y2m || ldy2 % 16 == 0, "gcnx_gcn_conv_bwd_pool_mask8: the mask's leading dimension must be a multiple of 16 bytes");
   GCNX_REQUIRE(ctx, b > 0 && rowptr_t && colidx_t && (y2 || y2m) && node_graph && graph_ptr && (dpooled || head) && w2 && y1 && dz1,
                "gcnx_gcn_conv_bwd_pool: NULL pointer");
-  GCNX_REQUIRE(ctx, (head || (lddp >= f2 && lddp % 4 == 0 && fal16(dpooled))) && ldy1 >= f1 && ldy1 % 4 == 0 && lddz1 >= f1 &&
-                        lddz1 % 4 == 0 && fal16(y2) && fal16(y2m) && fal16(y1) && fal16(dz1) &&
-                        (!dz2 || (fal16(dz2) && lddz2 >= f2 && lddz2 % 4 == 0)),
+  GCNX_REQUIRE(ctx, (head || (lddp >= f2 && lddp % 4 == 0 && gcnx_aligned16(dpooled))) && ldy1 >= f1 && ldy1 % 4 == 0 && lddz1 >= f1 &&
+                        lddz1 % 4 == 0 && gcnx_aligned16(y2) && gcnx_aligned16(y2m) && gcnx_aligned16(y1) && gcnx_aligned16(dz1) &&
+                        (!dz2 || (gcnx_aligned16(dz2) && lddz2 >= f2 && lddz2 % 4 == 0)),
                "gcnx_gcn_conv_bwd_pool: operands must be 16-byte aligned with leading dimensions in multiples of 4 floats");
   if (head) {
     GCNX_REQUIRE(ctx, head->tile_part && head->tile_cnt && head->pool_sum && head->pool_cnt && head->w && head->y &&
                           head->tile_rows >= tiles_of(n) + b && head->tile_rows * f2 * 4 < 0xFFFFFFF0ll && head->b == b &&
-                          head->h == f2 && head->c >= 1 && head->denom > 0.f && fal16(head->tile_part) && fal16(head->tile_cnt) &&
-                          fal16(head->pool_sum) && fal16(head->pool_cnt) && head->pool_mode == mode &&
+                          head->h == f2 && head->c >= 1 && head->denom > 0.f && gcnx_aligned16(head->tile_part) && gcnx_aligned16(head->tile_cnt) &&
+                          gcnx_aligned16(head->pool_sum) && gcnx_aligned16(head->pool_cnt) && head->pool_mode == mode &&
                           (head->cce_mode == GCNX_CCE_PROBS || head->cce_mode == GCNX_CCE_LOGITS),
                  "gcnx_gcn_conv_bwd_pool: inconsistent head arguments");
     if (head->c > 2)
@@ -945,8 +944,8 @@ int conv_bwd_pool(gcnx_ctx* ctx, const int32_t* rowptr_t, const int32_t* colidx_
   float* colpart = nullptr;
   bool defer = false;
   if (db1) {
-    GCNX_REQUIRE(ctx, fal16(db1) && f1 % 4 == 0, "gcnx_gcn_conv_bwd_pool: db1 must be 16-byte aligned");
-    defer = pending && scratch && fal16(scratch) && scratch_floats >= tiles * f1 && tiles <= 4096;
+    GCNX_REQUIRE(ctx, gcnx_aligned16(db1) && f1 % 4 == 0, "gcnx_gcn_conv_bwd_pool: db1 must be 16-byte aligned");
+    defer = pending && scratch && gcnx_aligned16(scratch) && scratch_floats >= tiles * f1 && tiles <= 4096;
     if (defer) colpart = scratch;
     else {
       int rc = gcnx_ws_reserve(ctx, gcnx_colsum_partials_ws(tiles, f1));

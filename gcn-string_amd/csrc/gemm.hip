@@ -786,7 +786,6 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(const float* __restrict_
   }
 }
 
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 
@@ -821,7 +820,7 @@ int launch_bf16_nn(gcnx_ctx* ctx, const float* a, int64_t lda, const float* w, i
                      kpad, hi, lo);
   GCNX_LAUNCH_OK(ctx);
   dim3 grid(gcnx_cdiv(ncol, HN), gcnx_cdiv(m, HM), 1);
-  const int va = al16(a) && lda % 4 == 0;
+  const int va = gcnx_aligned16(a) && lda % 4 == 0;
   if (prec == GCNX_PREC_BF16X3)
     hipLaunchKernelGGL((gemm_bf16_kernel<0, true>), grid, dim3(256), 0, ctx->stream, a, lda, (const float*)nullptr,
                        (int64_t)0, hi, lo, kpad, c, ldc, m, ncol, (int64_t)K, (int64_t)kpad + HK, ep, va, 0);
@@ -951,7 +950,7 @@ __global__ __launch_bounds__(1024, 4) void gemm_f32_rowtile_kernel(const float* 
 static bool rowtile_ok(const gcnx_ctx* ctx, int64_t m, int k, int nc, const float* a, int64_t lda) {
   // (>= 192 columns: at least 12 of the 16 waves have a column tile; narrower products measured no faster than the tiles)
   return ctx->knob_gemm_stream && m >= 2048 && (k == 16 || k == 32 || k == 64 || k == 128 || k == 256) && nc >= 192 && nc <= 256 &&
-         nc % 16 == 0 && lda % 4 == 0 && al16(a);
+         nc % 16 == 0 && lda % 4 == 0 && gcnx_aligned16(a);
 }
 
 // out[o][i] = w[i][o]: the [K, nc] operand of the row-tile kernel for dH W^T (a strided read of W in the kernel costs
@@ -1006,12 +1005,12 @@ int gcnx_gemm(gcnx_ctx* ctx, const float* x, int64_t ldx, const float* w, const 
   if (n == 0 || fo == 0) return GCNX_OK;
   GCNX_REQUIRE(ctx, x && w && out, "gcnx_gemm: NULL pointer");
   GCNX_REQUIRE(ctx, ldx >= fi && ldo >= fo, "gcnx_gemm: leading dimension too small");
-  Epilogue ep{bias, act == GCNX_ACT_PRELU ? alpha : nullptr, nullptr, 0, act, 0, al16(out) && ldo % 4 == 0};
+  Epilogue ep{bias, act == GCNX_ACT_PRELU ? alpha : nullptr, nullptr, 0, act, 0, gcnx_aligned16(out) && ldo % 4 == 0};
   if (prec != GCNX_PREC_F32) return launch_bf16_nn(ctx, x, ldx, w, fi, fo, 1, out, ldo, n, prec, ep);
   if (rowtile_ok(ctx, n, fi, fo, x, ldx))
     return launch_rowtile(ctx, x, ldx, w, (int64_t)fo, out, ldo, n, fi, fo, ep, std::min(gcnx_cdiv(n, kRtRows), ctx->num_cus));
   dim3 grid(gcnx_cdiv(fo, BN), gcnx_cdiv(n, BM), 1);
-  const int va = al16(x) && ldx % 4 == 0, vb = al16(w) && fo % 4 == 0;
+  const int va = gcnx_aligned16(x) && ldx % 4 == 0, vb = gcnx_aligned16(w) && fo % 4 == 0;
   hipLaunchKernelGGL((gemm_f32_kernel<true, false>), grid, dim3(256), 0, ctx->stream, x, ldx, w, (int64_t)fo, out,
                      ldo, n, fo, (int64_t)fi, (int64_t)fi + BK, ep, va, vb);
   GCNX_LAUNCH_OK(ctx);
@@ -1031,7 +1030,7 @@ int gcnx_gemm_relu_bits(gcnx_ctx* ctx, const float* x, int64_t ldx, const float*
   GCNX_REQUIRE(ctx, x && w && out && bits, "gcnx_gemm_relu_bits: NULL pointer");
   GCNX_REQUIRE(ctx, ldx >= fi && ldo >= fo, "gcnx_gemm_relu_bits: leading dimension too small");
   int rc = GCNX_ERR_UNSUPPORTED;
-  if (prec != GCNX_PREC_F32 && fo == 256 && al16(out) && ldo % 4 == 0)
+  if (prec != GCNX_PREC_F32 && fo == 256 && gcnx_aligned16(out) && ldo % 4 == 0)
     rc = gcnx_gemm_stream_nn(ctx, x, ldx, w, fi, fo, 1, out, ldo, n, prec, bias, nullptr, GCNX_ACT_RELU, nullptr, 0, 0, nullptr, nullptr, bits);
   // (UNSUPPORTED is an answer, not a failure: returned without a message, ctx's last error stays what it was -- a caller
   // that probes every step must not pay for formatting one, nor find a stale "unsupported" text after its fallback worked)
@@ -1046,7 +1045,7 @@ int gcnx_gemm_dx_bits(gcnx_ctx* ctx, const float* dh, int64_t lddh, const float*
   GCNX_REQUIRE(ctx, dh && w && dx && mask_bits, "gcnx_gemm_dx_bits: NULL pointer");
   GCNX_REQUIRE(ctx, lddh >= fo && lddx >= fi, "gcnx_gemm_dx_bits: leading dimension too small");
   int rc = GCNX_ERR_UNSUPPORTED;
-  if (prec != GCNX_PREC_F32 && fi == 256 && al16(dx) && lddx % 4 == 0 && (!db || al16(db)))
+  if (prec != GCNX_PREC_F32 && fi == 256 && gcnx_aligned16(dx) && lddx % 4 == 0 && (!db || gcnx_aligned16(db)))
     rc = gcnx_gemm_stream_nn(ctx, dh, lddh, w, fi, fo, 0, dx, lddx, n, prec, nullptr, nullptr, GCNX_ACT_NONE, nullptr, 0, 0, db, mask_bits,
                              nullptr);
   return rc;                                   // (UNSUPPORTED without a message, as above)
@@ -1064,7 +1063,7 @@ int gcnx_gemm_stream_images(gcnx_ctx* ctx, int32_t njobs, const gcnx_stream_imag
   if (njobs == 0) return GCNX_OK;
   const float* w[4]; int tr[4]; void* img[4];
   for (int j = 0; j < njobs; ++j) {
-    GCNX_REQUIRE(ctx, jobs[j].w && jobs[j].img && (reinterpret_cast<uintptr_t>(jobs[j].img) & 15) == 0,
+    GCNX_REQUIRE(ctx, jobs[j].w && jobs[j].img && gcnx_aligned16(jobs[j].img),
                  "gcnx_gemm_stream_images: job %d: NULL weight / image, or an image that is not 16-byte aligned", j);
     GCNX_REQUIRE(ctx, jobs[j].fi == 256 && jobs[j].fo == 256, "gcnx_gemm_stream_images: job %d: the streaming bf16 kernels take 256 x 256 "
                  "operands (got %d x %d)", j, jobs[j].fi, jobs[j].fo);
@@ -1082,7 +1081,7 @@ int gcnx_gemm_fwd_bf16(gcnx_ctx* ctx, const void* x16, int64_t ldx, const float*
   GCNX_REQUIRE(ctx, ldx >= fi && ldo >= fo, "gcnx_gemm_fwd_bf16: leading dimension too small");
   GCNX_REQUIRE(ctx, act == GCNX_ACT_NONE || act == GCNX_ACT_RELU, "gcnx_gemm_fwd_bf16: activation %d not supported here", act);
   GCNX_REQUIRE(ctx, !relu_bits || act == GCNX_ACT_RELU, "gcnx_gemm_fwd_bf16: the bit image is that of a ReLU output");
-  if (fi != 256 || fo != 256 || (bias && !al16(bias))) return GCNX_ERR_UNSUPPORTED;
+  if (fi != 256 || fo != 256 || (bias && !gcnx_aligned16(bias))) return GCNX_ERR_UNSUPPORTED;
   return gcnx_gemm_stream_bf16(ctx, x16, ldx, w, fi, fo, 1, out, ldo, out_bf16, n, bias, act, nullptr, nullptr, relu_bits, wimg);
 }
 
@@ -1104,7 +1103,7 @@ int gcnx_gemm_dw_bf16(gcnx_ctx* ctx, const void* x16, int64_t ldx, const void* d
   GCNX_REQUIRE(ctx, n >= 0 && fi >= 0 && fo >= 0, "gcnx_gemm_dw_bf16: negative size");
   GCNX_REQUIRE(ctx, x16 && dh16 && dw, "gcnx_gemm_dw_bf16: NULL pointer");
   GCNX_REQUIRE(ctx, ldx >= fi && lddh >= fo, "gcnx_gemm_dw_bf16: leading dimension too small");
-  if (fi != 256 || fo != 256 || n < 32 * 1024 || !ctx->knob_gemm_stream || !al16(dw)) return GCNX_ERR_UNSUPPORTED;
+  if (fi != 256 || fo != 256 || n < 32 * 1024 || !ctx->knob_gemm_stream || !gcnx_aligned16(dw)) return GCNX_ERR_UNSUPPORTED;
   const int max_slices = ctx->num_cus;
   int rc = gcnx_ws_reserve(ctx, (size_t)max_slices * 65536 * sizeof(float));
   if (rc) return rc;
@@ -1132,7 +1131,7 @@ int gcnx_gemm_dx(gcnx_ctx* ctx, const float* dh, int64_t lddh, const float* w, f
   GCNX_REQUIRE(ctx, lddh >= fo && lddx >= fi && (!y_mask || ldy >= fi), "gcnx_gemm_dx: leading dimension too small");
   // dX[n, i] = sum_o dH[n, o] * W[i, o]:  A = dH (k contiguous), B[k=o][j=i] = W[i*fo + o] (k contiguous).
   Epilogue ep{nullptr, nullptr, y_mask, ldy, GCNX_ACT_NONE, accumulate,
-              al16(dx) && lddx % 4 == 0 && (!y_mask || (al16(y_mask) && ldy % 4 == 0))};
+              gcnx_aligned16(dx) && lddx % 4 == 0 && (!y_mask || (gcnx_aligned16(y_mask) && ldy % 4 == 0))};
   if (prec != GCNX_PREC_F32) {
     int db_done = 0;
     int rc = launch_bf16_nn(ctx, dh, lddh, w, fi, fo, 0, dx, lddx, n, prec, ep, db, &db_done);
@@ -1140,7 +1139,7 @@ int gcnx_gemm_dx(gcnx_ctx* ctx, const float* dh, int64_t lddh, const float* w, f
     if (db && !db_done) return gcnx_colsum(ctx, dx, lddx, n, fi, db);
     return GCNX_OK;
   }
-  if (rowtile_ok(ctx, n, fo, fi, dh, lddh) && (!db || al16(db))) {   // dX[n, i] = sum_o dH[n, o] W[i, o]: K = fo, columns = fi
+  if (rowtile_ok(ctx, n, fo, fi, dh, lddh) && (!db || gcnx_aligned16(db))) {   // dX[n, i] = sum_o dH[n, o] W[i, o]: K = fo, columns = fi
     const int wgs = std::min(gcnx_cdiv(n, kRtRows), ctx->num_cus);
     // workspace: [db partial rows + their reduction's scratch | W^T]
     const size_t part_bytes = db ? (((size_t)gcnx_colsum_partials_ws(wgs, fi) + 255) & ~(size_t)255) : 0;
@@ -1155,7 +1154,7 @@ int gcnx_gemm_dx(gcnx_ctx* ctx, const float* dh, int64_t lddh, const float* w, f
     return gcnx_colsum_partials(ctx, wgs, fi, db);
   }
   dim3 grid(gcnx_cdiv(fi, BN), gcnx_cdiv(n, BM), 1);
-  const int va = al16(dh) && lddh % 4 == 0, vb = al16(w) && fo % 4 == 0;
+  const int va = gcnx_aligned16(dh) && lddh % 4 == 0, vb = gcnx_aligned16(w) && fo % 4 == 0;
   // db: every wave adds up the columns of the 32 rows it writes (float4 epilogue, all column tiles full) and a
   // second launch sums those n/32 partial rows -- instead of a column-sum pass that reads dX back (2 launches over
   // the whole matrix; at config 2 they were 17 us of the critical path, the partial reduce is 5).
@@ -1233,9 +1232,9 @@ static int dense_bwd_impl(gcnx_ctx* ctx, const float* x, int64_t ldx, const floa
   GCNX_REQUIRE(ctx, prec >= GCNX_PREC_F32 && prec <= GCNX_PREC_BF16X3, "gcnx_dense_bwd: unknown precision %d", prec);
   GCNX_REQUIRE(ctx, dx && dw, "gcnx_dense_bwd: dx and dw are both required (use gcnx_gemm_dx / gcnx_gemm_dw for one of them)");
   const int64_t gy = gcnx_cdiv(n, BM);
-  const bool fused = prec == GCNX_PREC_F32 && n > 0 && fi > 0 && fo > 0 && x && dh && w && fi % BN == 0 && al16(dx) &&
-                     lddx % 4 == 0 && (!y_mask || (al16(y_mask) && ldy % 4 == 0)) && fo % 4 == 0 &&
-                     (!db_prev || (al16(db_prev) && 2 * gy <= 4096)) && gy * (fi / BN) < (1 << 30);
+  const bool fused = prec == GCNX_PREC_F32 && n > 0 && fi > 0 && fo > 0 && x && dh && w && fi % BN == 0 && gcnx_aligned16(dx) &&
+                     lddx % 4 == 0 && (!y_mask || (gcnx_aligned16(y_mask) && ldy % 4 == 0)) && fo % 4 == 0 &&
+                     (!db_prev || (gcnx_aligned16(db_prev) && 2 * gy <= 4096)) && gy * (fi / BN) < (1 << 30);
   if (!fused) {   // bf16 paths, ragged widths, empty inputs: the two products as separate calls
     int rc = gcnx_gemm_dx(ctx, dh, lddh, w, dx, lddx, n, fi, fo, prec, 0, y_mask, ldy, db_prev);
     if (rc) return rc;
@@ -1251,7 +1250,7 @@ static int dense_bwd_impl(gcnx_ctx* ctx, const float* x, int64_t ldx, const floa
   const int64_t prow = db_prev ? 2 * gy : 0;
   const size_t part_floats = ((size_t)prow * fi + 63) & ~(size_t)63;
   const size_t slab_floats = nsplit > 1 ? (size_t)nsplit * fi * fo : 0;
-  const bool defer = pending && scratch && al16(scratch) && (size_t)scratch_floats >= part_floats + slab_floats &&
+  const bool defer = pending && scratch && gcnx_aligned16(scratch) && (size_t)scratch_floats >= part_floats + slab_floats &&
                      (prow > 0 || nsplit > 1);
   float* base = scratch;
   if (!defer) {
@@ -1265,10 +1264,10 @@ static int dense_bwd_impl(gcnx_ctx* ctx, const float* x, int64_t ldx, const floa
   float* slabs = base + part_floats;
   GemmJob jx{dh, lddh, w, (int64_t)fo, dx, lddx, n, fi, (int64_t)fo, (int64_t)fo + BK,
              Epilogue{nullptr, nullptr, y_mask, ldy, GCNX_ACT_NONE, 0, 1, colpart},
-             al16(dh) && lddh % 4 == 0, al16(w) && fo % 4 == 0, fi / BN, (int)gy, 1};
+             gcnx_aligned16(dh) && lddh % 4 == 0, gcnx_aligned16(w) && fo % 4 == 0, fi / BN, (int)gy, 1};
   GemmJob jw{x, ldx, dh, lddh, nsplit > 1 ? slabs : dw, (int64_t)fo, (int64_t)fi, fo, n, kchunk,
-             Epilogue{nullptr, nullptr, nullptr, 0, GCNX_ACT_NONE, 0, nsplit > 1 || al16(dw), nullptr},
-             al16(x) && ldx % 4 == 0, al16(dh) && lddh % 4 == 0, gcnx_cdiv(fo, BN), gcnx_cdiv(fi, BM), nsplit};
+             Epilogue{nullptr, nullptr, nullptr, 0, GCNX_ACT_NONE, 0, nsplit > 1 || gcnx_aligned16(dw), nullptr},
+             gcnx_aligned16(x) && ldx % 4 == 0, gcnx_aligned16(dh) && lddh % 4 == 0, gcnx_cdiv(fo, BN), gcnx_cdiv(fi, BM), nsplit};
   hipLaunchKernelGGL(gemm_f32_duo_kernel, dim3(n_dx + jw.gx * jw.gy * jw.gz), dim3(256), 0, ctx->stream, jx, jw, n_dx);
   GCNX_LAUNCH_OK(ctx);
   const int n_c = db_prev ? gcnx_cdiv(fi, 8) : 0;
@@ -1312,7 +1311,7 @@ int gcnx_gemm_dw(gcnx_ctx* ctx, const float* x, int64_t ldx, const float* dh, in
       const int ns = gcnx_gemm_dw_stream(ctx, x, ldx, dh, lddh, (float*)ctx->ws, n, fi, fo, prec, max_slices);
       if (ns < 0) return gcnx_fail(ctx, GCNX_ERR_HIP, "gcnx_gemm_dw: streaming kernel launch failed");
       if (ns > 0) {
-        if (al16(dw))
+        if (gcnx_aligned16(dw))
           hipLaunchKernelGGL(splitk_reduce_wide_kernel, dim3(gcnx_cdiv(65536, 256)), dim3(256), 0, ctx->stream, (const float*)ctx->ws,
                              (int64_t)65536, ns, dw, (int64_t)65536);
         else
@@ -1334,7 +1333,7 @@ int gcnx_gemm_dw(gcnx_ctx* ctx, const float* x, int64_t ldx, const float* dh, in
     if (ns < 1) ns = 1;
     const int64_t kchunk_h = ((ksteps_h + ns - 1) / ns) * HK;
     ns = (int)((n + kchunk_h - 1) / kchunk_h);
-    Epilogue eph{nullptr, nullptr, nullptr, 0, GCNX_ACT_NONE, 0, fo % 4 == 0 && (ns > 1 || al16(dw))};
+    Epilogue eph{nullptr, nullptr, nullptr, 0, GCNX_ACT_NONE, 0, fo % 4 == 0 && (ns > 1 || gcnx_aligned16(dw))};
     float* tgt = dw;
     if (ns > 1) {
       int rc = gcnx_ws_reserve(ctx, (size_t)ns * fi * fo * sizeof(float));
@@ -1342,7 +1341,7 @@ int gcnx_gemm_dw(gcnx_ctx* ctx, const float* x, int64_t ldx, const float* dh, in
       tgt = (float*)ctx->ws;
     }
     dim3 gridh(gcnx_cdiv(fo, HN), gcnx_cdiv(fi, HM), ns);
-    const int vah = al16(x) && ldx % 4 == 0, vbh = al16(dh) && lddh % 4 == 0;
+    const int vah = gcnx_aligned16(x) && ldx % 4 == 0, vbh = gcnx_aligned16(dh) && lddh % 4 == 0;
     if (prec == GCNX_PREC_BF16X3)
       hipLaunchKernelGGL((gemm_bf16_kernel<1, true>), gridh, dim3(256), 0, ctx->stream, x, ldx, dh, lddh,
                          (const __bf16*)nullptr, (const __bf16*)nullptr, 0, tgt, (int64_t)fo, (int64_t)fi, fo, n, kchunk_h,
@@ -1368,9 +1367,9 @@ int gcnx_gemm_dw(gcnx_ctx* ctx, const float* x, int64_t ldx, const float* dh, in
   const int64_t kchunk = ((ksteps + nsplit - 1) / nsplit) * BK;
   nsplit = (int)((n + kchunk - 1) / kchunk);
   Epilogue ep{nullptr, nullptr, nullptr, 0, GCNX_ACT_NONE, 0, 0};
-  const int va = al16(x) && ldx % 4 == 0, vb = al16(dh) && lddh % 4 == 0;
+  const int va = gcnx_aligned16(x) && ldx % 4 == 0, vb = gcnx_aligned16(dh) && lddh % 4 == 0;
   float* target = dw;
-  ep.vec_c = fo % 4 == 0 && (nsplit > 1 || al16(dw));   // partial slabs live in the 256-byte aligned workspace
+  ep.vec_c = fo % 4 == 0 && (nsplit > 1 || gcnx_aligned16(dw));   // partial slabs live in the 256-byte aligned workspace
   if (nsplit > 1) {
     int rc = gcnx_ws_reserve(ctx, (size_t)nsplit * fi * fo * sizeof(float));
     if (rc) return rc;
@@ -1408,7 +1407,7 @@ int gcnx_gemm_dw_sgd(gcnx_ctx* ctx, const float* x, int64_t ldx, const float* dh
   if (pending && !pending->colpart && !pending->slabs) pending = nullptr;
   if (pending) {
     GCNX_REQUIRE(ctx, !pending->colpart || (pending->cout >= grads && pending->cout + pending->cf <= grads + n_params &&
-                                            pending->cf % 4 == 0 && al16(pending->cout)),
+                                            pending->cf % 4 == 0 && gcnx_aligned16(pending->cout)),
                  "gcnx_gemm_dw_sgd: the pending column sums must land (16-byte aligned) inside the flat gradient buffer");
     GCNX_REQUIRE(ctx, !pending->slabs || (pending->out >= grads && pending->out + pending->total <= grads + n_params),
                  "gcnx_gemm_dw_sgd: the pending split-K result must land inside the flat gradient buffer");
@@ -1443,7 +1442,7 @@ int gcnx_gemm_dw_sgd(gcnx_ctx* ctx, const float* x, int64_t ldx, const float* dh
   int rc = gcnx_ws_reserve(ctx, (size_t)nsplit * total * sizeof(float));
   if (rc) return rc;
   Epilogue ep{nullptr, nullptr, nullptr, 0, GCNX_ACT_NONE, 0, 1};
-  const int va = al16(x) && ldx % 4 == 0, vb = al16(dh) && lddh % 4 == 0;
+  const int va = gcnx_aligned16(x) && ldx % 4 == 0, vb = gcnx_aligned16(dh) && lddh % 4 == 0;
   dim3 grid(gcnx_cdiv(fo, BN), gcnx_cdiv(fi, BM), nsplit);
   hipLaunchKernelGGL((gemm_f32_kernel<false, false>), grid, dim3(256), 0, ctx->stream, x, ldx, dh, lddh, (float*)ctx->ws,
                      (int64_t)fo, (int64_t)fi, fo, n, kchunk, ep, va, vb);
@@ -1488,7 +1487,7 @@ int gcnx_gemm_dw2(gcnx_ctx* ctx, const float* xa, int64_t ldxa, const float* dha
                           (tb == 0 || (dwb >= grads && dwb + tb <= grads + n_params)),
                  "gcnx_gemm_dw2: both gradients must lie inside the flat gradient buffer");
     GCNX_REQUIRE(ctx, !pending || !pending->colpart || (pending->cout >= grads && pending->cout + pending->cf <= grads + n_params &&
-                                                        pending->cf % 4 == 0 && al16(pending->cout)),
+                                                        pending->cf % 4 == 0 && gcnx_aligned16(pending->cout)),
                  "gcnx_gemm_dw2: the pending column sums must land (16-byte aligned) inside the flat gradient buffer");
   }
   int nsplit = 1;
@@ -1523,9 +1522,9 @@ int gcnx_gemm_dw2(gcnx_ctx* ctx, const float* xa, int64_t ldxa, const float* dha
   float* sb = sa + slab_a;
   const Epilogue ep{nullptr, nullptr, nullptr, 0, GCNX_ACT_NONE, 0, 1, nullptr};
   GemmJob ja{xa, ldxa, dha, lddha, sa, (int64_t)foa, (int64_t)fia, foa, n, kchunk, ep,
-             al16(xa) && ldxa % 4 == 0, al16(dha) && lddha % 4 == 0, gcnx_cdiv(foa, BN), gcnx_cdiv(fia, BM), nsplit};
+             gcnx_aligned16(xa) && ldxa % 4 == 0, gcnx_aligned16(dha) && lddha % 4 == 0, gcnx_cdiv(foa, BN), gcnx_cdiv(fia, BM), nsplit};
   GemmJob jb{xb, ldxb, dhb, lddhb, sb, (int64_t)fob, (int64_t)fib, fob, n, kchunk, ep,
-             al16(xb) && ldxb % 4 == 0, al16(dhb) && lddhb % 4 == 0, gcnx_cdiv(fob, BN), gcnx_cdiv(fib, BM), nsplit};
+             gcnx_aligned16(xb) && ldxb % 4 == 0, gcnx_aligned16(dhb) && lddhb % 4 == 0, gcnx_cdiv(fob, BN), gcnx_cdiv(fib, BM), nsplit};
   const int n_a = ja.gx * ja.gy * ja.gz, n_b = jb.gx * jb.gy * jb.gz;
   const bool want_db = leaf && leaf->db_relu;
   const bool merged = leaf && leaf->c == 2 && gcnx_head::head_lds_floats(leaf->h, leaf->c, want_db) <= (size_t)kDw2HeadLds &&

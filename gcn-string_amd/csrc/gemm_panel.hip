@@ -455,7 +455,6 @@ __global__ __launch_bounds__(256) void bn_finalize_parts_kernel(const float* __r
   inv[c] = 1.0f / sqrtf(v + eps);
 }
 
-inline bool pal16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 
@@ -480,7 +479,7 @@ int gcnx_wimage_prepare(gcnx_ctx* ctx, int32_t njobs, const gcnx_wimage_job* job
       const gcnx_wimage_job& j = jobs[base + i];
       GCNX_REQUIRE(ctx, j.w && j.img && j.fi > 0 && j.fo > 0, "gcnx_wimage_prepare: job %d: NULL pointer / empty matrix", base + i);
       GCNX_REQUIRE(ctx, j.prec == GCNX_PREC_BF16 || j.prec == GCNX_PREC_BF16X3, "gcnx_wimage_prepare: job %d: precision %d has no image", base + i, j.prec);
-      GCNX_REQUIRE(ctx, pal16(j.img), "gcnx_wimage_prepare: job %d: the image must be 16-byte aligned", base + i);
+      GCNX_REQUIRE(ctx, gcnx_aligned16(j.img), "gcnx_wimage_prepare: job %d: the image must be 16-byte aligned", base + i);
       const long long e = gcnx_wimage_elems(j.fi, j.fo, j.transpose, j.prec);
       js.j[i] = WimageJob{j.w, (__bf16*)j.img, j.fi, j.fo, j.transpose ? 1 : 0, j.prec == GCNX_PREC_BF16X3 ? 2 : 1, e};
       most = e > most ? e : most;
@@ -505,7 +504,7 @@ int gcnx_gemm_wimage(gcnx_ctx* ctx, const float* x, int64_t ldx, const void* img
   GCNX_REQUIRE(ctx, x && img && out, "gcnx_gemm_wimage: NULL pointer");
   GCNX_REQUIRE(ctx, ldx >= K && ldo >= nc, "gcnx_gemm_wimage: leading dimension too small");
   // what the kernel is built for (the caller falls back to gcnx_gemm / gcnx_gemm_dx otherwise; no message: an answer)
-  if (nc % 16 != 0 || K % 4 != 0 || ldx % 4 != 0 || !pal16(x) || !pal16(img) || (uint64_t)n * (uint64_t)ldx * 4u >= 0xFFFFFF00ull)
+  if (nc % 16 != 0 || K % 4 != 0 || ldx % 4 != 0 || !gcnx_aligned16(x) || !gcnx_aligned16(img) || (uint64_t)n * (uint64_t)ldx * 4u >= 0xFFFFFF00ull)
     return GCNX_ERR_UNSUPPORTED;
   GCNX_REQUIRE(ctx, !bn_parts || n_parts, "gcnx_gemm_wimage: bn_parts needs n_parts");
   const int ntiles = gcnx_cdiv(n, kTileRows);

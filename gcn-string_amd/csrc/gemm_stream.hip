@@ -447,7 +447,6 @@ __global__ __launch_bounds__(512, 2) void gemm_stream_kernel(const float* __rest
 #undef GS_WREAD
 }
 
-inline bool sal16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 template <int NP, int CW, int RT, int KSTEPS>
 int launch_stream(gcnx_ctx* ctx, const float* a, int64_t lda, const __bf16* img, float* c, int64_t ldc, int64_t m, int ncol,
@@ -499,9 +498,9 @@ int gcnx_gemm_stream_nn(gcnx_ctx* ctx, const float* a, int64_t lda, const float*
   if (accumulate) return GCNX_ERR_UNSUPPORTED;   // (a read-modify-write epilogue would drain the prefetch ring: tiled kernel)
   if (ctx->knob_gemm_stream == 0) return GCNX_ERR_UNSUPPORTED;
   const bool shape_ok = K == 256 && ncol % 4 == 0 && ncol <= 256 && ncol >= 64 && m >= 32 * 1024 &&
-                        lda % 4 == 0 && ldc % 4 == 0 && sal16(a) && sal16(c) && (uint64_t)m * (uint64_t)lda * 4u < 0xFFFFFF00ull &&
+                        lda % 4 == 0 && ldc % 4 == 0 && gcnx_aligned16(a) && gcnx_aligned16(c) && (uint64_t)m * (uint64_t)lda * 4u < 0xFFFFFF00ull &&
                         (uint64_t)m * (uint64_t)ldc * 4u < 0xFFFFFF00ull &&
-                        (!mask || (ldmask % 4 == 0 && sal16(mask) && (uint64_t)m * (uint64_t)ldmask * 4u < 0xFFFFFF00ull));
+                        (!mask || (ldmask % 4 == 0 && gcnx_aligned16(mask) && (uint64_t)m * (uint64_t)ldmask * 4u < 0xFFFFFF00ull));
   if (!shape_ok) return GCNX_ERR_UNSUPPORTED;
   // bf16x3: hi + lo planes of 256 k x 128 columns = 128 KiB of LDS, wider outputs as two column halves on
   // XCD-neighbouring workgroups, 32 rows per wave.  bf16: one plane of 256 k x 256 columns = 128 KiB, every
@@ -518,7 +517,7 @@ int gcnx_gemm_stream_nn(gcnx_ctx* ctx, const float* a, int64_t lda, const float*
   // workgroup of it writes its row -- no rows to clear)
   const int64_t n_rb_ = gcnx_cdiv(m, (np == 2 ? 32 : 16) * kSWaves);
   const int64_t prow = colsum_out ? std::min<int64_t>(grid_wgs / halves, n_rb_) : 0;
-  if (colsum_out && (ncol % 4 != 0 || !sal16(colsum_out))) return GCNX_ERR_UNSUPPORTED;
+  if (colsum_out && (ncol % 4 != 0 || !gcnx_aligned16(colsum_out))) return GCNX_ERR_UNSUPPORTED;
   const size_t part_bytes = colsum_out ? ((gcnx_colsum_partials_ws(prow, ncol) + 255) & ~(size_t)255) : 0;
   int rc = gcnx_ws_reserve(ctx, part_bytes + img_elems * sizeof(__bf16) + 256);
   if (rc) return rc;
@@ -570,11 +569,11 @@ int gcnx_gemm_stream_bf16(gcnx_ctx* ctx, const void* a16, int64_t lda, const flo
                           void* bits_out, const void* wimg) {
   const int ncol = transpose ? fo : fi, K = transpose ? fi : fo;
   if (ctx->knob_gemm_stream == 0 || K != 256 || ncol != 256 || m < 32 * 1024) return GCNX_ERR_UNSUPPORTED;
-  if (lda % 8 || ldc % 4 || !sal16(a16) || !sal16(c) || (uint64_t)m * (uint64_t)lda * 2u >= 0xFFFFFF00ull ||
+  if (lda % 8 || ldc % 4 || !gcnx_aligned16(a16) || !gcnx_aligned16(c) || (uint64_t)m * (uint64_t)lda * 2u >= 0xFFFFFF00ull ||
       (uint64_t)m * (uint64_t)ldc * (c_bf16 ? 2u : 4u) >= 0xFFFFFF00ull || (uint64_t)m * 64u >= 0xFFFFFF00ull ||
       (reinterpret_cast<uintptr_t>(mask_bits) & 7) || (reinterpret_cast<uintptr_t>(bits_out) & 7))
     return GCNX_ERR_UNSUPPORTED;
-  if (colsum_out && !sal16(colsum_out)) return GCNX_ERR_UNSUPPORTED;
+  if (colsum_out && !gcnx_aligned16(colsum_out)) return GCNX_ERR_UNSUPPORTED;
   const size_t img_elems = (size_t)8 * 256 * 32;
   const int64_t prow = colsum_out ? std::min<int64_t>(ctx->num_cus, gcnx_cdiv(m, 16 * kSWaves)) : 0;   // (= the grid: every workgroup writes its row)
   const size_t part_bytes = colsum_out ? ((gcnx_colsum_partials_ws(prow, ncol) + 255) & ~(size_t)255) : 0;
@@ -813,7 +812,7 @@ __global__ __launch_bounds__(256) void dw_panel_reduce_kernel(const float* __res
 int gcnx_gemm_dw_panels(gcnx_ctx* ctx, const float* x, int64_t ldx, const float* dh, int64_t lddh, float* dw, int64_t n,
                         int32_t fi, int32_t fo, int prec) {
   if (ctx->knob_gemm_stream == 0 || fo != 256 || fi % 256 != 0 || fi < 256 || fi > 2048 || n < 2048 || prec == GCNX_PREC_F32) return 0;
-  if (ldx % 4 || lddh % 4 || !sal16(x) || !sal16(dh) || !sal16(dw) || (uint64_t)n * (uint64_t)ldx * 4u >= 0xFFFFFF00ull ||
+  if (ldx % 4 || lddh % 4 || !gcnx_aligned16(x) || !gcnx_aligned16(dh) || !gcnx_aligned16(dw) || (uint64_t)n * (uint64_t)ldx * 4u >= 0xFFFFFF00ull ||
       (uint64_t)n * (uint64_t)lddh * 4u >= 0xFFFFFF00ull)
     return 0;
   const int panels = fi / 256;
@@ -844,7 +843,7 @@ int gcnx_gemm_dw_panels(gcnx_ctx* ctx, const float* x, int64_t ldx, const float*
 int gcnx_gemm_dw_stream16(gcnx_ctx* ctx, const void* x16, int64_t ldx, const void* dh16, int64_t lddh, float* slabs, int64_t n,
                           int32_t fi, int32_t fo, int max_slices) {
   if (ctx->knob_gemm_stream == 0 || fi != 256 || fo != 256 || n < 32 * 1024) return 0;
-  if (ldx % 8 || lddh % 8 || !sal16(x16) || !sal16(dh16) || (uint64_t)n * (uint64_t)ldx * 2u >= 0xFFFFFF00ull ||
+  if (ldx % 8 || lddh % 8 || !gcnx_aligned16(x16) || !gcnx_aligned16(dh16) || (uint64_t)n * (uint64_t)ldx * 2u >= 0xFFFFFF00ull ||
       (uint64_t)n * (uint64_t)lddh * 2u >= 0xFFFFFF00ull)
     return 0;
   int slices = ctx->num_cus < max_slices ? ctx->num_cus : max_slices;
@@ -862,7 +861,7 @@ int gcnx_gemm_dw_stream16(gcnx_ctx* ctx, const void* x16, int64_t ldx, const voi
 int gcnx_gemm_dw_stream(gcnx_ctx* ctx, const float* x, int64_t ldx, const float* dh, int64_t lddh, float* slabs, int64_t n,
                         int32_t fi, int32_t fo, int prec, int max_slices) {
   if (ctx->knob_gemm_stream == 0 || fi != 256 || fo != 256 || n < 32 * 1024 || prec == GCNX_PREC_F32) return 0;
-  if (ldx % 4 || lddh % 4 || !sal16(x) || !sal16(dh) || (uint64_t)n * (uint64_t)ldx * 4u >= 0xFFFFFF00ull ||
+  if (ldx % 4 || lddh % 4 || !gcnx_aligned16(x) || !gcnx_aligned16(dh) || (uint64_t)n * (uint64_t)ldx * 4u >= 0xFFFFFF00ull ||
       (uint64_t)n * (uint64_t)lddh * 4u >= 0xFFFFFF00ull)
     return 0;
   int slices = ctx->num_cus < max_slices ? ctx->num_cus : max_slices;

@@ -62,7 +62,7 @@ int gcnx_pooled_dense_softmax_cce(gcnx_ctx* ctx, const int32_t* graph_ptr, int p
   }
   int rc = gcnx_dense_softmax_cce(ctx, pooled, ldp, w, bias, y, b, h, c, denom, probs, loss_acc, dw, db, dpooled, lddp, cce_mode);
   if (rc || !db_relu || b == 0 || h == 0) return rc;
-  GCNX_REQUIRE(ctx, h % 4 == 0 && (reinterpret_cast<uintptr_t>(db_relu) & 15) == 0, "gcnx_pooled_dense_softmax_cce: db_relu needs h %% 4 == 0 and a 16-byte aligned buffer");
+  GCNX_REQUIRE(ctx, h % 4 == 0 && gcnx_aligned16(db_relu), "gcnx_pooled_dense_softmax_cce: db_relu needs h %% 4 == 0 and a 16-byte aligned buffer");
   hipLaunchKernelGGL(dp_cnt_kernel, dim3(gcnx_cdiv((int64_t)b * h, 256)), dim3(256), 0, ctx->stream, dpooled, lddp, cnt, graph_ptr, b, h,
                      pool_mode == GCNX_POOL_AVG ? 1 : 0, (float*)ctx->ws);
   GCNX_LAUNCH_OK(ctx);
@@ -85,8 +85,8 @@ int gcnx_pool_dense_softmax_cce(gcnx_ctx* ctx, const int32_t* graph_ptr, const f
                "gcnx_pool_dense_softmax_cce: db_relu needs the gradient outputs and SUM / AVG pooling");
   const bool fused = b > 0 && h > 0 && h % 4 == 0 && c <= kHeadMaxC &&
                      head_lds_floats(h, c, db_relu != nullptr) <= (size_t)kHeadLdsFloats &&
-                     (reinterpret_cast<uintptr_t>(x) & 15) == 0 && gcnx_pool_split(ctx, b, h, pool_mode, 1) > 1;
-  if (!fused && db_relu && b > 0 && b <= 4096 && h > 0 && h % 4 == 0 && ldp == h && (reinterpret_cast<uintptr_t>(db_relu) & 15) == 0 &&
+                     gcnx_aligned16(x) && gcnx_pool_split(ctx, b, h, pool_mode, 1) > 1;
+  if (!fused && db_relu && b > 0 && b <= 4096 && h > 0 && h % 4 == 0 && ldp == h && gcnx_aligned16(db_relu) &&
       gcnx_pool_split(ctx, b, h, pool_mode, 4) == 1) {   // (the row order gcnx_segment_pool sums in: same pooled bits)
     // Many graphs (a large batch): the pool's pass over x also counts the positive entries per (graph, column) -- all
     // that db_relu = sum_g pool'(dPooled)[g] * #[x_g > 0] needs -- instead of a second pass over x

@@ -437,8 +437,7 @@ int colsum_impl(gcnx_ctx* ctx, const float* x, int64_t ldx, int64_t n, int32_t f
                 int64_t ldy, float* dz, int64_t lddz, int act, const float* alpha, float* out_alpha,
                 size_t ws_off = 0) {   // ws_off: floats at the start of the workspace that belong to the caller
   const bool fuse = (dz != nullptr);
-  auto al = [](const void* p_) { return (reinterpret_cast<uintptr_t>(p_) & 15) == 0; };
-  const int vec = al(x) && ldx % 4 == 0 && (!fuse || (al(y) && ldy % 4 == 0 && al(dz) && lddz % 4 == 0));
+  const int vec = gcnx_aligned16(x) && ldx % 4 == 0 && (!fuse || (gcnx_aligned16(y) && ldy % 4 == 0 && gcnx_aligned16(dz) && lddz % 4 == 0));
   // tall plain sums of rows of at most 1 KiB: whole-row workgroups, 1024-row chunks (fewer partial rows to fold)
   const bool wide = !fuse && vec && out && n >= 65536 && f >= 16 && f <= 256 && (f & (f - 1)) == 0;
   const int64_t chunk_rows = wide ? 1024 : kColsumRows;
@@ -471,7 +470,7 @@ int colsum_impl(gcnx_ctx* ctx, const float* x, int64_t ldx, int64_t n, int32_t f
   if (nchunks > 1) {
     const int vec2 = f % 4 == 0;   // the partials live in the 256-B aligned workspace with row stride f
     dim3 g2(gcnx_cdiv(f, 64), 1);
-    if (out && wide && nchunks <= 4096 && al(out)) {
+    if (out && wide && nchunks <= 4096 && gcnx_aligned16(out)) {
       hipLaunchKernelGGL(colpart_reduce_kernel, dim3(gcnx_cdiv(f, 8)), dim3(256), 0, ctx->stream, (const float*)part,
                          (int64_t)nchunks, f, out);
       GCNX_LAUNCH_OK(ctx);
@@ -510,7 +509,7 @@ int gcnx_pool_split(const gcnx_ctx* ctx, int32_t b, int32_t f, int mode, int hal
 
 int gcnx_pool_partials(gcnx_ctx* ctx, const int32_t* graph_ptr, const float* x, int64_t ldx, int32_t b, int32_t f,
                        int mode, int nsplit, float* part, float* cnt_part, int wide) {
-  const int vec = (reinterpret_cast<uintptr_t>(x) & 15) == 0 && ldx % 4 == 0;
+  const int vec = gcnx_aligned16(x) && ldx % 4 == 0;
   dim3 grid(gcnx_cdiv(f, 64), b, nsplit);
   if (wide)
     hipLaunchKernelGGL(pool_fwd_kernel<64>, grid, dim3(1024), 0, ctx->stream, graph_ptr, x, ldx, part, f, mode,
@@ -526,7 +525,7 @@ int gcnx_pool_partials(gcnx_ctx* ctx, const int32_t* graph_ptr, const float* x, 
 int gcnx_pool_graph_list(gcnx_ctx* ctx, const int32_t* graph_ptr, const int32_t* glist, int32_t nlist, const float* x, int64_t ldx,
                          int32_t f, int mode, float* pooled, int64_t ldp, float* cnt) {
   if (nlist <= 0) return GCNX_OK;
-  const int vec = (reinterpret_cast<uintptr_t>(x) & 15) == 0 && ldx % 4 == 0;
+  const int vec = gcnx_aligned16(x) && ldx % 4 == 0;
   // 1024-thread workgroups (SUM / AVG only; the callers' case): the listed graphs are the tall ones -- 1 300 to 3 000 rows each, a
   // few per shard of an 8-rank run -- and a thread of the 256-thread shape walks 80-190 rows four at a time: a chain of
   // dependent round trips (17 us for nine graphs; r4 shard trace), a quarter of it with 64 row groups
@@ -551,7 +550,7 @@ size_t gcnx_colsum_partials_ws(int64_t rows, int32_t f) {
 int gcnx_colsum_partials(gcnx_ctx* ctx, int64_t rows, int32_t f, float* out) {
   const float* part = (const float*)ctx->ws;
   if (rows > kPartialsOneLaunch) return colsum_impl(ctx, part, f, rows, f, out, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, (size_t)rows * f);
-  if (f % 4 != 0 || (reinterpret_cast<uintptr_t>(out) & 15) != 0)
+  if (f % 4 != 0 || !gcnx_aligned16(out))
     return colsum_impl(ctx, part, f, rows, f, out, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, (size_t)rows * f);
   hipLaunchKernelGGL(colpart_reduce_kernel, dim3(gcnx_cdiv(f, 8)), dim3(256), 0, ctx->stream, part, rows, f, out);
   GCNX_LAUNCH_OK(ctx);
@@ -593,7 +592,7 @@ int gcnx_segment_pool(gcnx_ctx* ctx, const int32_t* graph_ptr, const float* x, i
   GCNX_REQUIRE(ctx, graph_ptr && x && pooled, "gcnx_segment_pool: NULL pointer");
   GCNX_REQUIRE(ctx, ldx >= f, "gcnx_segment_pool: leading dimension too small");
   GCNX_REQUIRE(ctx, mode != GCNX_POOL_MAX || argmax, "gcnx_segment_pool: MAX needs an argmax buffer");
-  const int vec = (reinterpret_cast<uintptr_t>(x) & 15) == 0 && ldx % 4 == 0;
+  const int vec = gcnx_aligned16(x) && ldx % 4 == 0;
   const int nsplit = gcnx_pool_split(ctx, b, f, mode, 4);
   if (nsplit > 1) {
     int rc = gcnx_ws_reserve(ctx, (size_t)nsplit * b * f * sizeof(float));
@@ -627,8 +626,7 @@ int gcnx_segment_pool_bwd(gcnx_ctx* ctx, const int32_t* graph_ptr, const float* 
   GCNX_REQUIRE(ctx, graph_ptr && dpooled && dx, "gcnx_segment_pool_bwd: NULL pointer");
   GCNX_REQUIRE(ctx, lddx >= f && (!y || ldy >= f), "gcnx_segment_pool_bwd: leading dimension too small");
   GCNX_REQUIRE(ctx, mode != GCNX_POOL_MAX || argmax, "gcnx_segment_pool_bwd: MAX needs the argmax buffer");
-  auto al = [](const void* p_) { return (reinterpret_cast<uintptr_t>(p_) & 15) == 0; };
-  const int vec = al(dx) && lddx % 4 == 0 && al(dpooled) && (!y || (al(y) && ldy % 4 == 0));
+  const int vec = gcnx_aligned16(dx) && lddx % 4 == 0 && gcnx_aligned16(dpooled) && (!y || (gcnx_aligned16(y) && ldy % 4 == 0));
   int rpw = (int)(n / (64LL * ctx->num_cus));   // rows per wave: ~16 waves per SIMD before runs get longer
   rpw = rpw < 1 ? 1 : (rpw > kPoolBwdRows ? kPoolBwdRows : rpw);
   hipLaunchKernelGGL(pool_bwd_kernel, dim3(gcnx_cdiv(n, 4 * rpw)), dim3(256), 0, ctx->stream, graph_ptr, b, dpooled, dx,
@@ -652,7 +650,7 @@ int gcnx_pool_bwd_colsum(gcnx_ctx* ctx, const int32_t* graph_ptr, int32_t b, con
   }
   GCNX_REQUIRE(ctx, graph_ptr && dpooled && y, "gcnx_pool_bwd_colsum: NULL pointer");
   GCNX_REQUIRE(ctx, lddp >= f && ldy >= f, "gcnx_pool_bwd_colsum: leading dimension too small");
-  const int vec = (reinterpret_cast<uintptr_t>(y) & 15) == 0 && ldy % 4 == 0;
+  const int vec = gcnx_aligned16(y) && ldy % 4 == 0;
   const int base_wgs = gcnx_cdiv(f, 64) * b;            // as gcnx_segment_pool: few graphs -> slice their rows
   int nsplit = 1;
   if (base_wgs < 2 * ctx->num_cus) {

@@ -6,7 +6,17 @@
 //
 // HBM-bound: algorithmic bytes per launch = 4(N+1) + 4 nnz (+4 nnz weighted) + 2*4*N*F.
 //
-// Two kernels.
+// Host routes (spmm_csr_impl forward, spmm_csr_pool_bwd_impl folded backward; every launcher takes one SpmmCall):
+//   scalar      operands that are not float4-able (forward only)                    spmm_scalar_kernel
+//   gather      no plan, or too few tile units: launch_gather -- all rows on dispatch_rows + launch_hubs (rows of more
+//               than kHubDeg entries, bound plan), or with column-block graphs launch_cb + the other graphs' rest chunks
+//   tiers fwd   launch_duo<1024> then <512>, taller graphs' chunks on dispatch_rows + launch_hubs, launch_cb; optionally
+//               as concurrent branches (spmm_conc); writes relu_bits / bf16 rows on request
+//   tiers bwd   launch_duo<512> then <1024> in their folded modes, ALL taller graphs' chunks on dispatch_rows + launch_hubs
+//   pipe        opt-in (spmm_kernel = pipe, forward): launch_pipe per slab width, taller graphs' chunks on dispatch_rows
+//   bits + pool gcnx_spmm_csr_relu_bits_pool: launch_duo<1024> in kDuoBitsPool, pool_parts_reduce_kernel, tall graphs apart
+//
+// The kernels:
 //
 // Tile kernel (used when the caller passes the diagonal blocks of the disjoint batch, i.e. a plan over graph_ptr,
 // and the batch has enough (graph, slab) units to fill the chip): the gather never leaves the CU.  A workgroup
@@ -1569,63 +1579,73 @@ __global__ __launch_bounds__(256) void spmm_scalar_kernel(const int32_t* __restr
   }
 }
 
+// What every host launcher of one aggregation call needs.  An entry point fills it once from its arguments and the _impl
+// function checks it before any launcher sees it; a launcher takes it plus only what is its own (a chunk list, a graph
+// list, a row order).  Launches go to ctx->stream as it stands at the launch (the concurrent tile route switches it).
+struct SpmmCall {
+  gcnx_ctx* ctx;
+  const int32_t *rowptr, *colidx;
+  const float* vals;       // NULL: unweighted
+  const float* h;          // the gathered matrix (forward: the features; folded backward: the saved layer output y)
+  int64_t ldh;
+  const float* bias;
+  float* out;
+  int64_t ldo;
+  int32_t n, f;
+  int act;
+  const FoldArgs* fold;    // NULL: forward
+  int out16;               // bf16 result rows (`out` then points at uint16 rows)
+};
+
+// The rows kernel over chunk_list[0, list_len) of list_rpc rows each (NULL: all n rows in order).  hub_deg > 0: rows of
+// more entries are left to launch_hubs.
 template <int LPR>
-void launch_rows(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, const float* vals, const float* h,
-                 int64_t ldh, const float* bias, float* out, int64_t ldo, int32_t n, int32_t f, int act,
-                 const int2* chunk_list = nullptr, int list_len = 0, const FoldArgs* fold = nullptr, int list_rpc = kRowsPerChunk,
-                 int hub_deg = 0, int out16 = 0) {
-  const FoldArgs fo = fold ? *fold : FoldArgs{nullptr, nullptr, 0, 0, 0};
-  if (out16) {   // (bf16 result rows: the one shape the bf16-storage path of large batches needs -- the caller has checked it)
+void launch_rows(const SpmmCall& c, const int2* chunk_list, int list_len, int list_rpc, int hub_deg) {
+  const FoldArgs fo = c.fold ? *c.fold : FoldArgs{nullptr, nullptr, 0, 0, 0};
+#define GCNX_ROWS_K(NCH, HD, ...)                                                                                            \
+  hipLaunchKernelGGL((spmm_rows_kernel<__VA_ARGS__>), dim3(NCH), dim3(256), 0, c.ctx->stream, c.rowptr, c.colidx, c.vals, c.h, c.ldh, \
+                     c.bias, c.out, c.ldo, c.n, c.f, col0, c.act, NCH, chunk_list, fo, HD)
+  if (c.out16) {   // (bf16 result rows: the one shape the bf16-storage path of large batches needs -- the caller has checked it)
     if constexpr (LPR == 64) {
-      for (int col0 = 0; col0 < f; col0 += LPR * 4) {
-        if (fold)
-          hipLaunchKernelGGL((spmm_rows_kernel<64, true, kRowsPerChunkSmall, true, false, true>), dim3(list_len), dim3(256), 0, ctx->stream, rowptr,
-                             colidx, vals, h, ldh, bias, out, ldo, n, f, col0, act, list_len, chunk_list, fo, 0);
-        else
-          hipLaunchKernelGGL((spmm_rows_kernel<64, true, kRowsPerChunkSmall, false, false, true>), dim3(list_len), dim3(256), 0, ctx->stream, rowptr,
-                             colidx, vals, h, ldh, bias, out, ldo, n, f, col0, act, list_len, chunk_list, fo, 0);
+      for (int col0 = 0; col0 < c.f; col0 += LPR * 4) {
+        if (c.fold) GCNX_ROWS_K(list_len, 0, 64, true, kRowsPerChunkSmall, true, false, true);
+        else GCNX_ROWS_K(list_len, 0, 64, true, kRowsPerChunkSmall, false, false, true);
       }
     }
     return;
   }
-  const bool small = chunk_list ? list_rpc <= kRowsPerChunkSmall : n < 16 * 1024 * kRowsPerChunk / 4;   // < 128k rows
-  const int nchunks = chunk_list ? list_len : gcnx_cdiv(n, small ? kRowsPerChunkSmall : kRowsPerChunk);
+  const bool small = chunk_list ? list_rpc <= kRowsPerChunkSmall : c.n < 16 * 1024 * kRowsPerChunk / 4;   // < 128k rows
+  const int nchunks = chunk_list ? list_len : gcnx_cdiv(c.n, small ? kRowsPerChunkSmall : kRowsPerChunk);
   const int span = LPR * 4;
-  for (int col0 = 0; col0 < f; col0 += span) {
-#define GCNX_ROWS_F(W, R, F, H)                                                                                      \
-    hipLaunchKernelGGL((spmm_rows_kernel<LPR, W, R, F, H>), dim3(nchunks), dim3(256), 0, ctx->stream, rowptr, colidx, vals, \
-                       h, ldh, bias, out, ldo, n, f, col0, act, nchunks, chunk_list, fo, hub_deg)
-#define GCNX_ROWS(W, R) do { if (hub_deg > 0) { if (fold) GCNX_ROWS_F(W, R, true, true); else GCNX_ROWS_F(W, R, false, true); }     \
-                             else { if (fold) GCNX_ROWS_F(W, R, true, false); else GCNX_ROWS_F(W, R, false, false); } } while (0)
-    if (small) { if (vals) GCNX_ROWS(true, kRowsPerChunkSmall); else GCNX_ROWS(false, kRowsPerChunkSmall); }
-    else { if (vals) GCNX_ROWS(true, kRowsPerChunk); else GCNX_ROWS(false, kRowsPerChunk); }
+  for (int col0 = 0; col0 < c.f; col0 += span) {
+#define GCNX_ROWS_F(W, R, F, H) GCNX_ROWS_K(nchunks, hub_deg, LPR, W, R, F, H)
+#define GCNX_ROWS(W, R) do { if (hub_deg > 0) { if (c.fold) GCNX_ROWS_F(W, R, true, true); else GCNX_ROWS_F(W, R, false, true); }     \
+                             else { if (c.fold) GCNX_ROWS_F(W, R, true, false); else GCNX_ROWS_F(W, R, false, false); } } while (0)
+    if (small) { if (c.vals) GCNX_ROWS(true, kRowsPerChunkSmall); else GCNX_ROWS(false, kRowsPerChunkSmall); }
+    else { if (c.vals) GCNX_ROWS(true, kRowsPerChunk); else GCNX_ROWS(false, kRowsPerChunk); }
 #undef GCNX_ROWS_F
 #undef GCNX_ROWS
   }
+#undef GCNX_ROWS_K
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-void dispatch_rows(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, const float* vals, const float* h,
-                   int64_t ldh, const float* bias, float* out, int64_t ldo, int32_t n, int32_t f, int act,
-                   const int2* chunk_list, int list_len, const FoldArgs* fold = nullptr, int list_rpc = kRowsPerChunk, int hub_deg = 0,
-                   int out16 = 0) {
-  if (out16) { launch_rows<64>(ctx, rowptr, colidx, vals, h, ldh, bias, out, ldo, n, f, act, chunk_list, list_len, fold, list_rpc, 0, 1); return; }
-  int lanes = f / 4;
+// The rows kernel at the lanes-per-row split that fits f (bf16 result rows: the 64-lane form, no hub rows).
+void dispatch_rows(const SpmmCall& c, const int2* chunk_list, int list_len, int list_rpc, int hub_deg) {
+  if (c.out16) { launch_rows<64>(c, chunk_list, list_len, list_rpc, 0); return; }
+  int lanes = c.f / 4;
   // Tuning knob (not part of the ABI contract): GCNX_SPMM_SLAB = column-slab width in floats
   // forces the lanes-per-row split of the rows kernel; results are identical.
-  if (ctx->knob_spmm_slab >= 16 && ctx->knob_spmm_slab / 4 < lanes) lanes = ctx->knob_spmm_slab / 4;
-  if (lanes > 32) launch_rows<64>(ctx, rowptr, colidx, vals, h, ldh, bias, out, ldo, n, f, act, chunk_list, list_len, fold, list_rpc, hub_deg);
-  else if (lanes > 16) launch_rows<32>(ctx, rowptr, colidx, vals, h, ldh, bias, out, ldo, n, f, act, chunk_list, list_len, fold, list_rpc, hub_deg);
-  else if (lanes > 8) launch_rows<16>(ctx, rowptr, colidx, vals, h, ldh, bias, out, ldo, n, f, act, chunk_list, list_len, fold, list_rpc, hub_deg);
-  else if (lanes > 4) launch_rows<8>(ctx, rowptr, colidx, vals, h, ldh, bias, out, ldo, n, f, act, chunk_list, list_len, fold, list_rpc, hub_deg);
-  else launch_rows<4>(ctx, rowptr, colidx, vals, h, ldh, bias, out, ldo, n, f, act, chunk_list, list_len, fold, list_rpc, hub_deg);
+  if (c.ctx->knob_spmm_slab >= 16 && c.ctx->knob_spmm_slab / 4 < lanes) lanes = c.ctx->knob_spmm_slab / 4;
+  if (lanes > 32) launch_rows<64>(c, chunk_list, list_len, list_rpc, hub_deg);
+  else if (lanes > 16) launch_rows<32>(c, chunk_list, list_len, list_rpc, hub_deg);
+  else if (lanes > 8) launch_rows<16>(c, chunk_list, list_len, list_rpc, hub_deg);
+  else if (lanes > 4) launch_rows<8>(c, chunk_list, list_len, list_rpc, hub_deg);
+  else launch_rows<4>(c, chunk_list, list_len, list_rpc, hub_deg);
 }
 
 template <int THREADS, int FT, int LPR>
-int launch_duo(gcnx_ctx* ctx, const int32_t* rowptr, const RowRec* rowrec, const int32_t* colidx, const float* vals, const float* h,
-               int64_t ldh, const float* bias, float* out, int64_t ldo, int32_t n, int32_t f, int act,
-               const int2* graphs, int ngraphs, const DuoFold* fold = nullptr, int mode = kDuoPlain, int out16 = 0) {
+int launch_duo(const SpmmCall& c, const RowRec* rowrec, const int2* graphs, int ngraphs, const DuoFold* fold, int mode) {
+  gcnx_ctx* const ctx = c.ctx;
   constexpr int lds_bytes = DuoShape<THREADS, FT>::LDSF * 4;
   static bool attr_set = false;
   if (!attr_set) {
@@ -1658,14 +1678,14 @@ int launch_duo(gcnx_ctx* ctx, const int32_t* rowptr, const RowRec* rowrec, const
   // column slabs per unit share one index burst; keep >= 3 units per workgroup so the static deal stays balanced
   // (config 3, measured per shape: 4 slabs per unit = 3.9 units per workgroup beats 2 slabs by 5 % and, on the
   // 1024-thread shape, 8 slabs = 1.9 units by 10 %)
-  const int slabs = f / FT;
+  const int slabs = c.f / FT;
   int sg = 1;
   // (r3, one workgroup per CU: >= 1.5 units per workgroup is enough -- the snake deal pairs the tall graphs of the first
   // round with the short ones of the second -- and at the shard sizes of an 8-GPU run the larger slab groups win:
   // 200 graphs: 4 slabs per unit 80 us against 85 (2) and 107 (8: fewer units than CUs); 400 graphs: 8 slabs 153 against 156)
   const long long need = THREADS == 512 ? 6LL * full : 3LL * full;            // in half units
-  for (int c = 8; c > 1; c >>= 1)
-    if (slabs % c == 0 && 2LL * ngraphs * (slabs / c) >= need) { sg = c; break; }
+  for (int k = 8; k > 1; k >>= 1)
+    if (slabs % k == 0 && 2LL * ngraphs * (slabs / k) >= need) { sg = k; break; }
   if (ctx->knob_spmm_sg >= 1 && slabs % ctx->knob_spmm_sg == 0) sg = ctx->knob_spmm_sg;
   const int upg = slabs / sg;
   const long long nunits = (long long)ngraphs * upg;
@@ -1673,37 +1693,25 @@ int launch_duo(gcnx_ctx* ctx, const int32_t* rowptr, const RowRec* rowrec, const
   const int grid = (int)(nunits < full ? nunits : full);
   const DuoFold nofold{nullptr, nullptr, 0, 0, nullptr};
   const DuoFold fo = fold ? *fold : nofold;
-#define GCNX_DUO_LAUNCH(W, M)                                                                                                \
-  hipLaunchKernelGGL((spmm_duo_kernel<THREADS, FT, LPR, W, M>), dim3(grid), dim3(THREADS), lds_bytes, ctx->stream, rowptr, rowrec, \
-                     colidx, vals, h, ldh, bias, out, ldo, graphs, upg, sg, act, (int)nunits, n, dbg, fo)
+#define GCNX_DUO_LAUNCH(W, ...)                                                                                              \
+  hipLaunchKernelGGL((spmm_duo_kernel<THREADS, FT, LPR, W, __VA_ARGS__>), dim3(grid), dim3(THREADS), lds_bytes, ctx->stream, c.rowptr, rowrec, \
+                     c.colidx, c.vals, c.h, c.ldh, c.bias, c.out, c.ldo, graphs, upg, sg, c.act, (int)nunits, c.n, dbg, fo)
+#define GCNX_DUO_MODE(M) do { if (c.vals) GCNX_DUO_LAUNCH(true, M); else GCNX_DUO_LAUNCH(false, M); } while (0)
   if (mode == kDuoBitsPool) {
+    if constexpr (THREADS == 1024) GCNX_DUO_MODE(kDuoBitsPool);
+  } else if (c.out16) {
     if constexpr (THREADS == 1024) {
-      if (vals) GCNX_DUO_LAUNCH(true, kDuoBitsPool); else GCNX_DUO_LAUNCH(false, kDuoBitsPool);
-    }
-  } else if (out16) {
-    if constexpr (THREADS == 1024) {
-      if (mode == kDuoFoldBits)
-        hipLaunchKernelGGL((spmm_duo_kernel<THREADS, FT, LPR, true, kDuoFoldBits, true>), dim3(grid), dim3(THREADS), lds_bytes, ctx->stream, rowptr,
-                           rowrec, colidx, vals, h, ldh, bias, out, ldo, graphs, upg, sg, act, (int)nunits, n, dbg, fo);
-      else
-        hipLaunchKernelGGL((spmm_duo_kernel<THREADS, FT, LPR, true, kDuoPlain, true>), dim3(grid), dim3(THREADS), lds_bytes, ctx->stream, rowptr,
-                           rowrec, colidx, vals, h, ldh, bias, out, ldo, graphs, upg, sg, act, (int)nunits, n, dbg, fo);
-    }
-  } else if (vals) {
-    switch (mode) {
-      case kDuoFold: GCNX_DUO_LAUNCH(true, kDuoFold); break;
-      case kDuoBitsOut: GCNX_DUO_LAUNCH(true, kDuoBitsOut); break;
-      case kDuoFoldBits: GCNX_DUO_LAUNCH(true, kDuoFoldBits); break;
-      default: GCNX_DUO_LAUNCH(true, kDuoPlain); break;
+      if (mode == kDuoFoldBits) GCNX_DUO_LAUNCH(true, kDuoFoldBits, true); else GCNX_DUO_LAUNCH(true, kDuoPlain, true);
     }
   } else {
     switch (mode) {
-      case kDuoFold: GCNX_DUO_LAUNCH(false, kDuoFold); break;
-      case kDuoBitsOut: GCNX_DUO_LAUNCH(false, kDuoBitsOut); break;
-      case kDuoFoldBits: GCNX_DUO_LAUNCH(false, kDuoFoldBits); break;
-      default: GCNX_DUO_LAUNCH(false, kDuoPlain); break;
+      case kDuoFold: GCNX_DUO_MODE(kDuoFold); break;
+      case kDuoBitsOut: GCNX_DUO_MODE(kDuoBitsOut); break;
+      case kDuoFoldBits: GCNX_DUO_MODE(kDuoFoldBits); break;
+      default: GCNX_DUO_MODE(kDuoPlain); break;
     }
   }
+#undef GCNX_DUO_MODE
 #undef GCNX_DUO_LAUNCH
   GCNX_LAUNCH_OK(ctx);
   return GCNX_OK;
@@ -1933,23 +1941,24 @@ static int plan_order(gcnx_ctx* ctx, const gcnx_spmm_plan* cplan, const int32_t*
 
 // The hub rows of a bound plan (all of them, or only those of graphs too tall for a tile): segments -> partial rows in the
 // ctx workspace -> combine + epilogue.
-static int launch_hubs(gcnx_ctx* ctx, const RowOrder* od, bool tall_only, const int32_t* colidx, const float* vals, const float* h,
-                       int64_t ldh, const float* bias, float* out, int64_t ldo, int32_t n, int32_t f, int act, const FoldArgs* fold,
-                       bool skip_cb = false /* the column-block graphs' hub rows are computed elsewhere */) {
+// skip_cb: the column-block graphs' hub rows are computed elsewhere (launch_cb).
+static int launch_hubs(const SpmmCall& c, const RowOrder* od, bool tall_only, bool skip_cb) {
+  gcnx_ctx* const ctx = c.ctx;
   const int seg0 = skip_cb ? od->nsegs_cb : 0, hub0 = skip_cb ? od->nhubs_cb : 0;
   const int nsegs = (tall_only ? od->nsegs_tall : od->nsegs) - seg0, nhubs = (tall_only ? od->nhubs_tall : od->nhubs) - hub0;
   if (nsegs <= 0) return GCNX_OK;
-  int rc = gcnx_ws_reserve(ctx, (size_t)(seg0 + nsegs) * f * sizeof(float));       // (slots are absolute list positions)
+  int rc = gcnx_ws_reserve(ctx, (size_t)(seg0 + nsegs) * c.f * sizeof(float));     // (slots are absolute list positions)
   if (rc) return rc;
   float* part = (float*)ctx->ws;
-  const FoldArgs fo = fold ? *fold : FoldArgs{nullptr, nullptr, 0, 0, 0};
-#define GCNX_HUB_SEG(W, F) hipLaunchKernelGGL((spmm_hub_seg_kernel<W, F>), dim3(nsegs), dim3(256), 0, ctx->stream, od->hub_segs + seg0, colidx, vals, h, ldh, part, n, f, od->nnz)
-  if (vals) { if (fold) GCNX_HUB_SEG(true, true); else GCNX_HUB_SEG(true, false); }
-  else { if (fold) GCNX_HUB_SEG(false, true); else GCNX_HUB_SEG(false, false); }
+  const FoldArgs fo = c.fold ? *c.fold : FoldArgs{nullptr, nullptr, 0, 0, 0};
+#define GCNX_HUB_SEG(W, F) hipLaunchKernelGGL((spmm_hub_seg_kernel<W, F>), dim3(nsegs), dim3(256), 0, ctx->stream, od->hub_segs + seg0, c.colidx, c.vals, c.h, c.ldh, part, c.n, c.f, od->nnz)
+  if (c.vals) { if (c.fold) GCNX_HUB_SEG(true, true); else GCNX_HUB_SEG(true, false); }
+  else { if (c.fold) GCNX_HUB_SEG(false, true); else GCNX_HUB_SEG(false, false); }
 #undef GCNX_HUB_SEG
   GCNX_LAUNCH_OK(ctx);
-  if (fold) hipLaunchKernelGGL((spmm_hub_combine_kernel<true>), dim3(nhubs), dim3(64), 0, ctx->stream, od->hub_rows + hub0, (const float*)part, bias, out, ldo, f, act, fo);
-  else hipLaunchKernelGGL((spmm_hub_combine_kernel<false>), dim3(nhubs), dim3(64), 0, ctx->stream, od->hub_rows + hub0, (const float*)part, bias, out, ldo, f, act, fo);
+#define GCNX_HUB_COMBINE(F) hipLaunchKernelGGL((spmm_hub_combine_kernel<F>), dim3(nhubs), dim3(64), 0, ctx->stream, od->hub_rows + hub0, (const float*)part, c.bias, c.out, c.ldo, c.f, c.act, fo)
+  if (c.fold) GCNX_HUB_COMBINE(true); else GCNX_HUB_COMBINE(false);
+#undef GCNX_HUB_COMBINE
   GCNX_LAUNCH_OK(ctx);
   return GCNX_OK;
 }
@@ -2021,16 +2030,18 @@ static int plan_cb_items(gcnx_ctx* ctx, const gcnx_spmm_plan* p, const RowOrder*
 }
 
 // Whether the column-block graphs of `plan` go through spmm_cb_kernel for this call (else: the row gather + hub segments).
-static bool cb_path_ok(const gcnx_ctx* ctx, const gcnx_spmm_plan* plan, int32_t n, int32_t f, int64_t ldh, int out16) {
-  return plan && plan->ncb_graphs > 0 && plan->ncb_graphs < 32768 && ctx->knob_spmm_cb != 0 && !out16 && f >= kCbMinF && f % kCbCols == 0 &&
-         f <= 32768 && (uint64_t)n * (uint64_t)ldh * 4u < 0xFFFFFF00ull;      // (an item packs column and graph index into 16 bits each)
+// (`order`: the row order bound to the call's rowptr, NULL when the plan is not bound to it)
+static bool cb_path_ok(const SpmmCall& c, const gcnx_spmm_plan* plan, const RowOrder* order) {
+  return plan && plan->ncb_graphs > 0 && plan->ncb_graphs < 32768 && c.ctx->knob_spmm_cb != 0 && !c.out16 && c.f >= kCbMinF &&
+         c.f % kCbCols == 0 && c.f <= 32768 &&                                 // (an item packs column and graph index into 16 bits each)
+         (uint64_t)c.n * (uint64_t)c.ldh * 4u < 0xFFFFFF00ull && order != nullptr;
 }
 
-static int launch_cb(gcnx_ctx* ctx, const gcnx_spmm_plan* plan, const RowOrder* order, const int32_t* colidx, const float* vals, const float* h,
-                     int64_t ldh, const float* bias, float* out, int64_t ldo, int32_t n, int32_t f, int act, const FoldArgs* fold = nullptr) {
+static int launch_cb(const SpmmCall& c, const gcnx_spmm_plan* plan, const RowOrder* order) {
+  gcnx_ctx* const ctx = c.ctx;
   const int4* items = nullptr;
   int nitems = 0;
-  const int rc = plan_cb_items(ctx, plan, order, f / kCbCols, &items, &nitems);
+  const int rc = plan_cb_items(ctx, plan, order, c.f / kCbCols, &items, &nitems);
   if (rc) return rc;
   if (nitems == 0) return GCNX_OK;
   int dbg = 0, pad_lds = 0;
@@ -2038,15 +2049,115 @@ static int launch_cb(gcnx_ctx* ctx, const gcnx_spmm_plan* plan, const RowOrder* 
   if (const char* e = getenv("GCNX_CB_DBG")) dbg = atoi(e);        // dynamic LDS per workgroup (caps the workgroups per CU)
   if (const char* e = getenv("GCNX_CB_LDS")) pad_lds = atoi(e);
 #endif
-  const FoldArgs fo = fold ? *fold : FoldArgs{nullptr, nullptr, 0, 0, 0};
+  const FoldArgs fo = c.fold ? *c.fold : FoldArgs{nullptr, nullptr, 0, 0, 0};
 #define GCNX_CB_LAUNCH(W, F)                                                                                                       \
-  hipLaunchKernelGGL((spmm_cb_kernel<W, F>), dim3(nitems), dim3(256), pad_lds, ctx->stream, (const RowRec*)order->dev, colidx, vals, h, ldh, \
-                     bias, out, ldo, n, order->nnz, act, nitems, items, dbg, fo, (const int32_t*)plan->cb_gids)
-  if (vals) { if (fold) GCNX_CB_LAUNCH(true, true); else GCNX_CB_LAUNCH(true, false); }
-  else { if (fold) GCNX_CB_LAUNCH(false, true); else GCNX_CB_LAUNCH(false, false); }
+  hipLaunchKernelGGL((spmm_cb_kernel<W, F>), dim3(nitems), dim3(256), pad_lds, ctx->stream, (const RowRec*)order->dev, c.colidx, c.vals, c.h, \
+                     c.ldh, c.bias, c.out, c.ldo, c.n, order->nnz, c.act, nitems, items, dbg, fo, (const int32_t*)plan->cb_gids)
+  if (c.vals) { if (c.fold) GCNX_CB_LAUNCH(true, true); else GCNX_CB_LAUNCH(true, false); }
+  else { if (c.fold) GCNX_CB_LAUNCH(false, true); else GCNX_CB_LAUNCH(false, false); }
 #undef GCNX_CB_LAUNCH
   GCNX_LAUNCH_OK(ctx);
   return GCNX_OK;
+}
+
+// The pipelined kernel: any graph size, one 1024-thread workgroup per CU with two source buffers.  Opt-in
+// (GCNX_SPMM_KERNEL=pipe / gcnx_set_tuning): correct on every case the tier kernels are tested on, but at config 3 it
+// measures 690-750 us against 646 for the tiers (LOG.md 4.1), so the tier kernels stay the default.
+static int launch_pipe(const SpmmCall& c, const PipeItem* list, int count, int ft) {
+  gcnx_ctx* const ctx = c.ctx;
+  static bool attr_set = false;
+  if (!attr_set) {
+    GCNX_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&spmm_pipe_kernel<true, 32>), hipFuncAttributeMaxDynamicSharedMemorySize, kPipeLds));
+    GCNX_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&spmm_pipe_kernel<false, 32>), hipFuncAttributeMaxDynamicSharedMemorySize, kPipeLds));
+    GCNX_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&spmm_pipe_kernel<true, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, kPipeLds));
+    GCNX_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&spmm_pipe_kernel<false, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, kPipeLds));
+    attr_set = true;
+  }
+  const int slabs = c.f / kSlab, full = ctx->num_cus;
+  int sg = 1;
+  for (int k = 8; k > 1; k >>= 1)
+    if (slabs % k == 0 && (long long)count * (slabs / k) >= 3LL * full) { sg = k; break; }
+  if (ctx->knob_spmm_sg >= 1 && slabs % ctx->knob_spmm_sg == 0) sg = ctx->knob_spmm_sg;
+  const int upg = slabs / sg;
+  const long long nunits = (long long)count * upg;
+  if (nunits >= 2000000000LL) return gcnx_fail(ctx, GCNX_ERR_INVALID, "gcnx_spmm_csr: too many work units");
+  const int grid = (int)(nunits < full ? nunits : full);
+  int pdbg = 0;
+  unsigned long long* stamps = nullptr;
+#ifdef GCNX_TUNING
+  if (const char* e = getenv("GCNX_SPMM_DBG")) pdbg = atoi(e);
+  static unsigned long long* stamp_buf = nullptr;
+  if (getenv("GCNX_SPMM_STAMPS")) {
+    if (!stamp_buf) (void)hipMalloc((void**)&stamp_buf, (size_t)full * 16 * 8 * sizeof(unsigned long long));
+    (void)hipMemsetAsync(stamp_buf, 0, (size_t)full * 16 * 8 * sizeof(unsigned long long), ctx->stream);
+    stamps = stamp_buf;
+  }
+#endif
+#define GCNX_PIPE_LAUNCH(W, FT_)                                                                                            \
+  hipLaunchKernelGGL((spmm_pipe_kernel<W, FT_>), dim3(grid), dim3(1024), kPipeLds, ctx->stream, c.rowptr, c.colidx, c.vals, c.h, \
+                     c.ldh, c.bias, c.out, c.ldo, list, upg, sg, c.act, (int)nunits, c.n, c.f, pdbg, stamps)
+  if (c.vals) { if (ft == 32) GCNX_PIPE_LAUNCH(true, 32); else GCNX_PIPE_LAUNCH(true, 16); }
+  else { if (ft == 32) GCNX_PIPE_LAUNCH(false, 32); else GCNX_PIPE_LAUNCH(false, 16); }
+#undef GCNX_PIPE_LAUNCH
+  GCNX_LAUNCH_OK(ctx);
+#ifdef GCNX_TUNING
+  if (stamps) {      // segment times (100 MHz ticks) of wave 0 and wave 15, averaged over the workgroups, to stderr
+    std::vector<unsigned long long> hst((size_t)full * 16 * 8);
+    (void)hipMemcpyAsync(hst.data(), stamps, hst.size() * 8, hipMemcpyDeviceToHost, ctx->stream);
+    (void)hipStreamSynchronize(ctx->stream);
+    const char* names[8] = {"prologue", "index burst", "-", "reduce+epilogue+dma issue", "dma wait", "barrier", "-", "-"};
+    for (int wv : {0, 15}) {
+      double sum[8] = {0};
+      for (int b = 0; b < grid; ++b) for (int k = 0; k < 8; ++k) sum[k] += (double)hst[((size_t)b * 16 + wv) * 8 + k];
+      fprintf(stderr, "[pipe stamps ft %d] wave %2d:", ft, wv);
+      for (int k = 0; k < 6; ++k) if (names[k][0] != '-') fprintf(stderr, "  %s %.1f us", names[k], sum[k] / grid * 0.01);
+      fprintf(stderr, "\n");
+    }
+  }
+#endif
+  return GCNX_OK;
+}
+
+// The tile kernels are a throughput design (one item per CU at a time): they need a few (graph, slab) units per CU to
+// fill the chip, otherwise the rows kernel's finer decomposition wins.  A 1024-thread tile counts as two units.
+static bool tile_units_fill(const gcnx_ctx* ctx, int n1, int n2, int32_t f) {
+  return (long long)(n1 + 2 * n2) * (f / kSlab) >= 4LL * ctx->num_cus;
+}
+// "Tiles are worth it": enough units, or the kernel knob asks for them (2 tiers, 3 pipe); knob 1 forces the rows kernel.
+// (The folded backward asks in addition that the plan is the one of its graph_ptr.)
+static bool tiles_worth_it(const gcnx_ctx* ctx, const gcnx_spmm_plan* plan, int32_t f) {
+  const int force = ctx->knob_spmm_kernel;
+  return plan && f % kSlab == 0 && force != 1 && (tile_units_fill(ctx, plan->n1, plan->n2, f) || force >= 2);
+}
+// "Tier 2 alone fills the chip" (f % kSlab == 0): what the forms that exist on the 1024-thread shape only ask for.
+static bool tier2_fills_chip(const gcnx_ctx* ctx, const gcnx_spmm_plan* plan, int32_t f) {
+  return ctx->knob_spmm_kernel != 1 && ctx->knob_spmm_kernel != 3 && tile_units_fill(ctx, 0, plan->n2, f);
+}
+// float4 rows throughout: every kernel but spmm_scalar_kernel needs it
+static bool spmm_vec_ok(const SpmmCall& c) {
+  return (c.f % 4 == 0) && (c.ldh % 4 == 0) && (c.ldo % 4 == 0) && gcnx_aligned16(c.h) && gcnx_aligned16(c.out) &&
+         (!c.bias || gcnx_aligned16(c.bias));
+}
+
+// The route without a tile kernel, forward and folded backward alike.  With column blocks (graphs too large for an XCD's
+// L2: spmm_cb_kernel, hub rows included): every other graph's rows as plan-listed chunks on the row gather, their hub rows
+// as segments.  Without: all rows on the row gather; with a bound plan the rows of more than kHubDeg entries go to the hub
+// kernels.
+static int launch_gather(const SpmmCall& c, const gcnx_spmm_plan* plan, const RowOrder* order) {
+  gcnx_ctx* const ctx = c.ctx;
+  if (cb_path_ok(c, plan, order)) {
+    if (plan->nrest > 0) {
+      const bool hubs = order->nsegs > order->nsegs_cb;
+      dispatch_rows(c, plan->rest, plan->nrest, plan->rest_rpc, hubs ? kHubDeg : 0);
+      GCNX_LAUNCH_OK(ctx);
+      if (hubs) { const int rh = launch_hubs(c, order, false, true); if (rh) return rh; }
+    }
+    return launch_cb(c, plan, order);
+  }
+  const bool hubs = order && order->nsegs > 0;
+  dispatch_rows(c, nullptr, 0, kRowsPerChunk, hubs ? kHubDeg : 0);
+  GCNX_LAUNCH_OK(ctx);
+  return hubs ? launch_hubs(c, order, false, false) : GCNX_OK;
 }
 
 extern "C" {
@@ -2239,16 +2350,86 @@ int gcnx_spmm_plan_bind(gcnx_ctx* ctx, gcnx_spmm_plan* plan, const int32_t* rowp
   return plan_order(ctx, plan, rowptr, n, !ctx->capturing, &unused);
 }
 
-static int spmm_csr_impl(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, const float* vals, const float* h,
-                         int64_t ldh, const float* bias, float* out, int64_t ldo, int32_t n, int32_t f, int act,
-                         const gcnx_spmm_plan* plan, uint32_t* relu_bits, int out16 = 0);
+// gcnx_spmm_csr and its variants: the checks, then one of the routes (see the list at the top of the file).
+static int spmm_csr_impl(const SpmmCall& c, const gcnx_spmm_plan* plan, uint32_t* relu_bits) {
+  gcnx_ctx* const ctx = c.ctx;
+  GCNX_CHECK_CTX(ctx);
+  GCNX_RANGE(ctx, "aggregation (GCNConv / GeneralConv SpMM)");
+  GCNX_REQUIRE(ctx, c.n >= 0 && c.f >= 0, "gcnx_spmm_csr: negative size");
+  GCNX_REQUIRE(ctx, c.act == GCNX_ACT_NONE || c.act == GCNX_ACT_RELU, "gcnx_spmm_csr: activation %d not supported here", c.act);
+  if (c.n == 0 || c.f == 0) return GCNX_OK;
+  GCNX_REQUIRE(ctx, c.rowptr && c.colidx && c.h && c.out, "gcnx_spmm_csr: NULL pointer");
+  GCNX_REQUIRE(ctx, c.ldh >= c.f && c.ldo >= c.f, "gcnx_spmm_csr: leading dimension smaller than f=%d", c.f);
+  GCNX_REQUIRE(ctx, c.h != c.out, "gcnx_spmm_csr: in-place aggregation is not possible");
+  const bool vec = spmm_vec_ok(c);
+  if (c.out16 && !vec) return GCNX_ERR_UNSUPPORTED;
+  if (!vec) {
+    hipLaunchKernelGGL(spmm_scalar_kernel, dim3(gcnx_cdiv(c.n, 4)), dim3(256), 0, ctx->stream, c.rowptr, c.colidx, c.vals,
+                       c.h, c.ldh, c.bias, c.out, c.ldo, c.n, c.f, c.act);
+    GCNX_LAUNCH_OK(ctx);
+    return GCNX_OK;
+  }
+  const int force = ctx->knob_spmm_kernel;   // tuning knob GCNX_SPMM_KERNEL / gcnx_set_tuning: 1 rows, 2 tile (tiers), 3 pipe
+  const bool tiles = tiles_worth_it(ctx, plan, c.f);
+  if (relu_bits && (!tiles || force == 3))
+    return gcnx_fail(ctx, GCNX_ERR_UNSUPPORTED, "gcnx_spmm_csr_relu_bits: the bit image is written by the tile kernels only "
+                     "(needs a plan with enough tile units and f %% 32 == 0): use gcnx_spmm_csr");
+  const RowRec* rowrec = nullptr;
+  const RowOrder* order = nullptr;
+  if (plan && force != 3) { const int rb = plan_order(ctx, plan, c.rowptr, c.n, false, &rowrec, &order); if (rb) return rb; }
+  if (c.out16 && (!tiles || (order && order->nsegs_tall > 0))) return GCNX_ERR_UNSUPPORTED;     // (checked by the caller; hub rows: fp32 only)
+  if (!tiles) return launch_gather(c, plan, order);
+  const bool pipe_ok = c.f <= kPipeMaxF && (uint64_t)c.n * (uint64_t)c.ldo * 4u < 0xFFFFFFF0ull;
+  if (force == 3 && pipe_ok) {
+    if (plan->n16 > 0) { int rc = launch_pipe(c, plan->items, plan->n16, 16); if (rc) return rc; }
+    if (plan->nitems > plan->n16) { int rc = launch_pipe(c, plan->items + plan->n16, plan->nitems - plan->n16, 32); if (rc) return rc; }
+    if (plan->npipe_chunks > 0) {   // graphs of more than 1248 rows: 32-row chunks on the rows kernel
+      dispatch_rows(c, plan->pipe_chunks, plan->npipe_chunks, kRowsPerChunk, 0);
+      GCNX_LAUNCH_OK(ctx);
+    }
+    return GCNX_OK;
+  }
+  // tier 1: two 512-thread workgroups per CU; tier 2: one 1024-thread workgroup with the whole LDS
+  const DuoFold bo{nullptr, nullptr, 0, 0, relu_bits};     // (graphs taller than a tile get no bits: their rows are folded from out)
+  const int dmode = relu_bits ? kDuoBitsOut : kDuoPlain;
+  // The three launches write disjoint rows.  GCNX_SPMM_CONC: as concurrent branches (two auxiliary streams), so that
+  // one launch's tail is filled by the next one's workgroups instead of draining the chip between them.
+  hipStream_t aux[2] = {nullptr, nullptr};
+  hipStream_t const home = ctx->stream;
+  const bool conc = ctx->knob_spmm_conc && (plan->n1 > 0) + (plan->n2 > 0) + (plan->nchunks > 0) >= 2;
+  if (conc) { int rc = gcnx_aux_fork(ctx, aux); if (rc) return rc; }
+  int rc = GCNX_OK;
+  if (plan->n2 > 0)          // (the 1024-thread tier first: its workgroups are the hardest to place)
+    rc = launch_duo<1024, 32, 4>(c, rowrec, plan->dev + plan->n1, plan->n2, &bo, dmode);
+  if (!rc && plan->n1 > 0) {
+    if (conc) ctx->stream = aux[0];
+    rc = launch_duo<512, 32, 4>(c, rowrec, plan->dev, plan->n1, &bo, dmode);
+    ctx->stream = home;
+  }
+  const bool cb = cb_path_ok(c, plan, order);
+  const int ch0 = cb ? plan->nchunks_cb : 0;         // (column-block graphs' chunks come first in the list)
+  if (!rc && plan->nchunks > ch0) {   // graphs taller than any tile: plan-listed 32-row chunks on the rows kernel
+    if (conc) ctx->stream = aux[1];
+    const bool hubs = order && order->nsegs_tall > (cb ? order->nsegs_cb : 0);
+    dispatch_rows(c, plan->dev + plan->n1 + plan->n2 + ch0, plan->nchunks - ch0, plan->chunk_rpc, hubs ? kHubDeg : 0);
+    if (hipGetLastError() != hipSuccess) rc = gcnx_fail(ctx, GCNX_ERR_HIP, "gcnx_spmm_csr: row-chunk launch failed");
+    if (!rc && hubs) rc = launch_hubs(c, order, true, cb);
+    ctx->stream = home;
+  }
+  if (!rc && cb) {
+    if (conc) ctx->stream = aux[1];
+    rc = launch_cb(c, plan, order);
+    ctx->stream = home;
+  }
+  if (conc) { const int rj = gcnx_aux_join(ctx); if (!rc) rc = rj; }
+  return rc;
+}
 
 // The conditions of the bf16-result forms (gcnx_spmm_csr_bf16out / _pool_bwd_bf16out): weighted operator, every tile
 // graph on the 1024-thread shape, taller graphs as 8-row chunks, no hub rows.
 static bool out16_shape_ok(gcnx_ctx* ctx, const gcnx_spmm_plan* plan, const float* vals, int32_t f, int64_t ldo, const void* out) {
-  return plan && vals && f % kSlab == 0 && f > 128 && ldo % 4 == 0 && aligned16(out) && plan->n1 == 0 && plan->n2 > 0 && plan->ncb_graphs == 0 &&
-         (plan->nchunks == 0 || plan->chunk_rpc == kRowsPerChunkSmall) && ctx->knob_spmm_kernel != 1 && ctx->knob_spmm_kernel != 3 &&
-         (long long)(2 * plan->n2) * (f / kSlab) >= 4LL * ctx->num_cus;
+  return plan && vals && f % kSlab == 0 && f > 128 && ldo % 4 == 0 && gcnx_aligned16(out) && plan->n1 == 0 && plan->n2 > 0 && plan->ncb_graphs == 0 &&
+         (plan->nchunks == 0 || plan->chunk_rpc == kRowsPerChunkSmall) && tier2_fills_chip(ctx, plan, f);
 }
 
 int gcnx_spmm_csr_bf16out(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, const float* vals, const float* h,
@@ -2257,13 +2438,13 @@ int gcnx_spmm_csr_bf16out(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* c
   GCNX_CHECK_CTX(ctx);
   GCNX_REQUIRE(ctx, out16 != nullptr || n == 0 || f == 0, "gcnx_spmm_csr_bf16out: NULL output");
   if (!out16_shape_ok(ctx, plan, vals, f, ldo, out16)) return GCNX_ERR_UNSUPPORTED;       // (an answer, not a failure: no message)
-  return spmm_csr_impl(ctx, rowptr, colidx, vals, h, ldh, bias, (float*)out16, ldo, n, f, act, plan, nullptr, 1);
+  return spmm_csr_impl(SpmmCall{ctx, rowptr, colidx, vals, h, ldh, bias, (float*)out16, ldo, n, f, act, nullptr, 1}, plan, nullptr);
 }
 
 int gcnx_spmm_csr(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, const float* vals, const float* h,
                   int64_t ldh, const float* bias, float* out, int64_t ldo, int32_t n, int32_t f, int act,
                   const gcnx_spmm_plan* plan) {
-  return spmm_csr_impl(ctx, rowptr, colidx, vals, h, ldh, bias, out, ldo, n, f, act, plan, nullptr);
+  return spmm_csr_impl(SpmmCall{ctx, rowptr, colidx, vals, h, ldh, bias, out, ldo, n, f, act, nullptr, 0}, plan, nullptr);
 }
 
 // pooled[g][c] (/ n_g for AVG) and cnt[g][c] of tile graph t = gids[t]: its 16 waves' partial rows, in wave order
@@ -2307,10 +2488,10 @@ int gcnx_spmm_csr_relu_bits_pool(gcnx_ctx* ctx, const int32_t* rowptr, const int
   if (n == 0 || f == 0 || b == 0) return GCNX_OK;
   GCNX_REQUIRE(ctx, rowptr && colidx && h && out && relu_bits && graph_ptr && pooled && cnt, "gcnx_spmm_csr_relu_bits_pool: NULL pointer");
   GCNX_REQUIRE(ctx, ldh >= f && ldo >= f && ldp >= f, "gcnx_spmm_csr_relu_bits_pool: leading dimension smaller than f=%d", f);
-  const bool ok = plan && plan->nblocks == b && plan->n1 == 0 && plan->n2 > 0 && f % kSlab == 0 && f % 4 == 0 && ldh % 4 == 0 && ldo % 4 == 0 &&
-                  ldp % 4 == 0 && aligned16(h) && aligned16(out) && aligned16(pooled) && aligned16(cnt) && (!bias || aligned16(bias)) &&
-                  (reinterpret_cast<uintptr_t>(relu_bits) & 3) == 0 && ctx->knob_spmm_kernel != 1 && ctx->knob_spmm_kernel != 3 &&
-                  (long long)(2 * plan->n2) * (f / kSlab) >= 4LL * ctx->num_cus;
+  const SpmmCall c{ctx, rowptr, colidx, vals, h, ldh, bias, out, ldo, n, f, GCNX_ACT_RELU, nullptr, 0};
+  const bool ok = plan && plan->nblocks == b && plan->n1 == 0 && plan->n2 > 0 && f % kSlab == 0 && spmm_vec_ok(c) && ldp % 4 == 0 &&
+                  gcnx_aligned16(pooled) && gcnx_aligned16(cnt) && (reinterpret_cast<uintptr_t>(relu_bits) & 3) == 0 &&
+                  tier2_fills_chip(ctx, plan, f);
   if (!ok) return GCNX_ERR_UNSUPPORTED;                   // (an answer: gcnx_spmm_csr_relu_bits + the pool then)
   const RowRec* rowrec = nullptr;
   const RowOrder* order = nullptr;
@@ -2322,16 +2503,14 @@ int gcnx_spmm_csr_relu_bits_pool(gcnx_ctx* ctx, const int32_t* rowptr, const int
   float* ppart = (float*)ctx->ws;
   float* cpart = ppart + part_floats;
   const DuoFold bo{nullptr, nullptr, 0, 0, (uint32_t*)relu_bits, ppart, cpart};
-  rc = launch_duo<1024, 32, 4>(ctx, rowptr, rowrec, colidx, vals, h, ldh, bias, out, ldo, n, f, GCNX_ACT_RELU, plan->dev + plan->n1, plan->n2, &bo,
-                               kDuoBitsPool);
+  rc = launch_duo<1024, 32, 4>(c, rowrec, plan->dev + plan->n1, plan->n2, &bo, kDuoBitsPool);
   if (rc) return rc;
   hipLaunchKernelGGL(pool_parts_reduce_kernel, dim3(gcnx_cdiv((long long)plan->n2 * f / 4, 256)), dim3(256), 0, ctx->stream, (const float*)ppart,
                      (const float*)cpart, (const int32_t*)(plan->gids + plan->n1), graph_ptr, plan->n2, f, pool_mode == GCNX_POOL_AVG ? 1 : 0,
                      pooled, ldp, cnt);
   GCNX_LAUNCH_OK(ctx);
   if (plan->nchunks > 0) {      // graphs taller than a tile: rows of `out` from the row chunks, then the pool over those graphs
-    dispatch_rows(ctx, rowptr, colidx, vals, h, ldh, bias, out, ldo, n, f, GCNX_ACT_RELU, plan->dev + plan->n1 + plan->n2, plan->nchunks, nullptr,
-                  plan->chunk_rpc, 0);
+    dispatch_rows(c, plan->dev + plan->n1 + plan->n2, plan->nchunks, plan->chunk_rpc, 0);
     GCNX_LAUNCH_OK(ctx);
     rc = gcnx_pool_graph_list(ctx, graph_ptr, plan->tall_gids, plan->ntall, out, ldo, f, pool_mode, pooled, ldp, cnt);
     if (rc) return rc;
@@ -2344,175 +2523,61 @@ int gcnx_spmm_csr_relu_bits(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t*
                             const gcnx_spmm_plan* plan, void* relu_bits) {
   GCNX_CHECK_CTX(ctx);
   GCNX_REQUIRE(ctx, relu_bits && (reinterpret_cast<uintptr_t>(relu_bits) & 3) == 0, "gcnx_spmm_csr_relu_bits: relu_bits must be a 4-byte aligned buffer");
-  return spmm_csr_impl(ctx, rowptr, colidx, vals, h, ldh, bias, out, ldo, n, f, GCNX_ACT_RELU, plan, (uint32_t*)relu_bits);
+  return spmm_csr_impl(SpmmCall{ctx, rowptr, colidx, vals, h, ldh, bias, out, ldo, n, f, GCNX_ACT_RELU, nullptr, 0}, plan, (uint32_t*)relu_bits);
 }
 
-static int spmm_csr_impl(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, const float* vals, const float* h,
-                         int64_t ldh, const float* bias, float* out, int64_t ldo, int32_t n, int32_t f, int act,
-                         const gcnx_spmm_plan* plan, uint32_t* relu_bits, int out16) {
+// gcnx_spmm_csr_pool_bwd and its bf16-result form (c.fold: the pool's operands; c.h: the saved layer output y).
+static int spmm_csr_pool_bwd_impl(const SpmmCall& c, int mode, const gcnx_spmm_plan* plan, const void* y_bits) {
+  gcnx_ctx* const ctx = c.ctx;
   GCNX_CHECK_CTX(ctx);
-  GCNX_RANGE(ctx, "aggregation (GCNConv / GeneralConv SpMM)");
-  GCNX_REQUIRE(ctx, n >= 0 && f >= 0, "gcnx_spmm_csr: negative size");
-  GCNX_REQUIRE(ctx, act == GCNX_ACT_NONE || act == GCNX_ACT_RELU, "gcnx_spmm_csr: activation %d not supported here", act);
-  if (n == 0 || f == 0) return GCNX_OK;
-  GCNX_REQUIRE(ctx, rowptr && colidx && h && out, "gcnx_spmm_csr: NULL pointer");
-  GCNX_REQUIRE(ctx, ldh >= f && ldo >= f, "gcnx_spmm_csr: leading dimension smaller than f=%d", f);
-  GCNX_REQUIRE(ctx, h != out, "gcnx_spmm_csr: in-place aggregation is not possible");
-  const bool vec = (f % 4 == 0) && (ldh % 4 == 0) && (ldo % 4 == 0) && aligned16(h) && aligned16(out) &&
-                   (!bias || aligned16(bias));
-  if (out16 && !vec) return GCNX_ERR_UNSUPPORTED;
-  if (!vec) {
-    hipLaunchKernelGGL(spmm_scalar_kernel, dim3(gcnx_cdiv(n, 4)), dim3(256), 0, ctx->stream, rowptr, colidx, vals,
-                       h, ldh, bias, out, ldo, n, f, act);
-    GCNX_LAUNCH_OK(ctx);
-    return GCNX_OK;
-  }
-  const int force = ctx->knob_spmm_kernel;   // tuning knob GCNX_SPMM_KERNEL / gcnx_set_tuning: 1 rows, 2 tile (tiers), 3 pipe
-  // The tile kernel is a throughput design (one item per CU at a time): it needs a few items
-  // per CU to fill the chip, otherwise the rows kernel's finer decomposition wins.
-  bool tiles = plan && f % kSlab == 0 && (long long)(plan->n1 + 2 * plan->n2) * (f / kSlab) >= 4LL * ctx->num_cus;
-  if (force == 1) tiles = false;
-  if (force >= 2 && plan && f % kSlab == 0) tiles = true;
-  if (relu_bits && (!tiles || force == 3))
-    return gcnx_fail(ctx, GCNX_ERR_UNSUPPORTED, "gcnx_spmm_csr_relu_bits: the bit image is written by the tile kernels only "
-                     "(needs a plan with enough tile units and f %% 32 == 0): use gcnx_spmm_csr");
+  GCNX_RANGE(ctx, "aggregation bwd (pool' folded)");
+  const FoldArgs& fo = *c.fold;
+  GCNX_REQUIRE(ctx, c.n >= 0 && c.f >= 0 && fo.b >= 0, "gcnx_spmm_csr_pool_bwd: negative size");
+  GCNX_REQUIRE(ctx, mode == GCNX_POOL_SUM || mode == GCNX_POOL_AVG,
+               "gcnx_spmm_csr_pool_bwd: pool mode %d has no folded form (use gcnx_segment_pool_bwd + gcnx_spmm_csr)", mode);
+  if (c.n == 0 || c.f == 0) return GCNX_OK;
+  GCNX_REQUIRE(ctx, fo.b > 0, "gcnx_spmm_csr_pool_bwd: rows without graphs");
+  GCNX_REQUIRE(ctx, c.rowptr && c.colidx && c.h && fo.gp && fo.dp && c.out, "gcnx_spmm_csr_pool_bwd: NULL pointer");
+  GCNX_REQUIRE(ctx, c.ldh >= c.f && c.ldo >= c.f && fo.lddp >= c.f, "gcnx_spmm_csr_pool_bwd: leading dimension smaller than f=%d", c.f);
+  GCNX_REQUIRE(ctx, c.h != c.out, "gcnx_spmm_csr_pool_bwd: in-place aggregation is not possible");
+  GCNX_REQUIRE(ctx, spmm_vec_ok(c) && (fo.lddp % 4 == 0) && gcnx_aligned16(fo.dp),
+               "gcnx_spmm_csr_pool_bwd: needs f and the leading dimensions in multiples of 4 floats and 16-byte aligned "
+               "operands (use gcnx_segment_pool_bwd + gcnx_spmm_csr otherwise)");
+  // with a plan (throughput regime): the tile kernels in their folded form, taller graphs' row chunks on the rows kernel
+  const bool bound = plan && plan->nblocks == fo.b;
+  const bool tiles = bound && tiles_worth_it(ctx, plan, c.f);
   const RowRec* rowrec = nullptr;
   const RowOrder* order = nullptr;
-  if (plan && force != 3) { const int rb = plan_order(ctx, plan, rowptr, n, false, &rowrec, &order); if (rb) return rb; }
-  if (out16 && (!tiles || (order && order->nsegs_tall > 0))) return GCNX_ERR_UNSUPPORTED;     // (checked by the caller; hub rows: fp32 only)
-  const bool cb = cb_path_ok(ctx, plan, n, f, ldh, out16) && order != nullptr;
-  if (!tiles) {
-    if (cb) {
-      // graphs too large for an XCD's L2: column blocks (spmm_cb_kernel, hub rows included); every other graph's rows
-      // as plan-listed chunks on the row gather, their hub rows as segments
-      if (plan->nrest > 0) {
-        const bool hubs = order->nsegs > order->nsegs_cb;
-        dispatch_rows(ctx, rowptr, colidx, vals, h, ldh, bias, out, ldo, n, f, act, plan->rest, plan->nrest, nullptr, plan->rest_rpc, hubs ? kHubDeg : 0);
-        GCNX_LAUNCH_OK(ctx);
-        if (hubs) { const int rh = launch_hubs(ctx, order, false, colidx, vals, h, ldh, bias, out, ldo, n, f, act, nullptr, true); if (rh) return rh; }
-      }
-      return launch_cb(ctx, plan, order, colidx, vals, h, ldh, bias, out, ldo, n, f, act);
-    }
-    // (with a bound plan: the rows of more than kHubDeg entries go to the hub kernels)
-    const bool hubs = order && order->nsegs > 0;
-    dispatch_rows(ctx, rowptr, colidx, vals, h, ldh, bias, out, ldo, n, f, act, nullptr, 0, nullptr, kRowsPerChunk, hubs ? kHubDeg : 0);
+  if (bound) { const int rb = plan_order(ctx, plan, c.rowptr, c.n, false, &rowrec, &order); if (rb) return rb; }
+  if (c.out16 && (!tiles || (order && order->nsegs_tall > 0))) return GCNX_ERR_UNSUPPORTED;
+  if (!tiles) return launch_gather(c, plan, order);     // (column blocks folded as in the forward aggregation: r4)
+  // y_bits (the forward's gcnx_spmm_csr_relu_bits image of y): the tiers expand it instead of reading y
+  const int dmode = y_bits ? kDuoFoldBits : kDuoFold;
+  if (plan->n1 > 0) {
+    const DuoFold df{plan->gids, fo.dp, fo.lddp, fo.avg, (uint32_t*)y_bits};
+    int rc = launch_duo<512, 32, 4>(c, rowrec, plan->dev, plan->n1, &df, dmode);
+    if (rc) return rc;
+  }
+  if (plan->n2 > 0) {
+    const DuoFold df{plan->gids + plan->n1, fo.dp, fo.lddp, fo.avg, (uint32_t*)y_bits};
+    int rc = launch_duo<1024, 32, 4>(c, rowrec, plan->dev + plan->n1, plan->n2, &df, dmode);
+    if (rc) return rc;
+  }
+  if (plan->nchunks > 0) {   // every graph taller than a tile, the column-block graphs included: no launch_cb on this route
+    const bool hubs = order && order->nsegs_tall > 0;
+    dispatch_rows(c, plan->dev + plan->n1 + plan->n2, plan->nchunks, plan->chunk_rpc, hubs ? kHubDeg : 0);
     GCNX_LAUNCH_OK(ctx);
-    return hubs ? launch_hubs(ctx, order, false, colidx, vals, h, ldh, bias, out, ldo, n, f, act, nullptr) : GCNX_OK;
+    if (hubs) return launch_hubs(c, order, true, false);
   }
-  // The pipelined kernel: any graph size, one 1024-thread workgroup per CU with two source buffers.  Opt-in
-  // (GCNX_SPMM_KERNEL=pipe / gcnx_set_tuning): correct on every case the tier kernels are tested on, but at config 3 it
-  // measures 690-750 us against 646 for the tiers (LOG.md 4.1), so the tier kernels stay the default.
-  auto launch_pipe = [&](const PipeItem* list, int count, int ft) -> int {
-    static bool attr_set = false;
-    if (!attr_set) {
-      GCNX_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&spmm_pipe_kernel<true, 32>), hipFuncAttributeMaxDynamicSharedMemorySize, kPipeLds));
-      GCNX_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&spmm_pipe_kernel<false, 32>), hipFuncAttributeMaxDynamicSharedMemorySize, kPipeLds));
-      GCNX_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&spmm_pipe_kernel<true, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, kPipeLds));
-      GCNX_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&spmm_pipe_kernel<false, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, kPipeLds));
-      attr_set = true;
-    }
-    const int slabs = f / kSlab, full = ctx->num_cus;
-    int sg = 1;
-    for (int c = 8; c > 1; c >>= 1)
-      if (slabs % c == 0 && (long long)count * (slabs / c) >= 3LL * full) { sg = c; break; }
-    if (ctx->knob_spmm_sg >= 1 && slabs % ctx->knob_spmm_sg == 0) sg = ctx->knob_spmm_sg;
-    const int upg = slabs / sg;
-    const long long nunits = (long long)count * upg;
-    if (nunits >= 2000000000LL) return gcnx_fail(ctx, GCNX_ERR_INVALID, "gcnx_spmm_csr: too many work units");
-    const int grid = (int)(nunits < full ? nunits : full);
-    int pdbg = 0;
-    unsigned long long* stamps = nullptr;
-#ifdef GCNX_TUNING
-    if (const char* e = getenv("GCNX_SPMM_DBG")) pdbg = atoi(e);
-    static unsigned long long* stamp_buf = nullptr;
-    if (getenv("GCNX_SPMM_STAMPS")) {
-      if (!stamp_buf) (void)hipMalloc((void**)&stamp_buf, (size_t)full * 16 * 8 * sizeof(unsigned long long));
-      (void)hipMemsetAsync(stamp_buf, 0, (size_t)full * 16 * 8 * sizeof(unsigned long long), ctx->stream);
-      stamps = stamp_buf;
-    }
-#endif
-#define GCNX_PIPE_LAUNCH(W, FT_)                                                                                            \
-    hipLaunchKernelGGL((spmm_pipe_kernel<W, FT_>), dim3(grid), dim3(1024), kPipeLds, ctx->stream, rowptr, colidx, vals, h, ldh, \
-                       bias, out, ldo, list, upg, sg, act, (int)nunits, n, f, pdbg, stamps)
-    if (vals) { if (ft == 32) GCNX_PIPE_LAUNCH(true, 32); else GCNX_PIPE_LAUNCH(true, 16); }
-    else { if (ft == 32) GCNX_PIPE_LAUNCH(false, 32); else GCNX_PIPE_LAUNCH(false, 16); }
-#undef GCNX_PIPE_LAUNCH
-    GCNX_LAUNCH_OK(ctx);
-#ifdef GCNX_TUNING
-    if (stamps) {      // segment times (100 MHz ticks) of wave 0 and wave 15, averaged over the workgroups, to stderr
-      std::vector<unsigned long long> hst((size_t)full * 16 * 8);
-      (void)hipMemcpyAsync(hst.data(), stamps, hst.size() * 8, hipMemcpyDeviceToHost, ctx->stream);
-      (void)hipStreamSynchronize(ctx->stream);
-      const char* names[8] = {"prologue", "index burst", "-", "reduce+epilogue+dma issue", "dma wait", "barrier", "-", "-"};
-      for (int wv : {0, 15}) {
-        double sum[8] = {0};
-        for (int b = 0; b < grid; ++b) for (int k = 0; k < 8; ++k) sum[k] += (double)hst[((size_t)b * 16 + wv) * 8 + k];
-        fprintf(stderr, "[pipe stamps ft %d] wave %2d:", ft, wv);
-        for (int k = 0; k < 6; ++k) if (names[k][0] != '-') fprintf(stderr, "  %s %.1f us", names[k], sum[k] / grid * 0.01);
-        fprintf(stderr, "\n");
-      }
-    }
-#endif
-    return GCNX_OK;
-  };
-  const bool pipe_ok = f <= kPipeMaxF && (uint64_t)n * (uint64_t)ldo * 4u < 0xFFFFFFF0ull;
-  if (force == 3 && pipe_ok) {
-    if (plan->n16 > 0) { int rc = launch_pipe(plan->items, plan->n16, 16); if (rc) return rc; }
-    if (plan->nitems > plan->n16) { int rc = launch_pipe(plan->items + plan->n16, plan->nitems - plan->n16, 32); if (rc) return rc; }
-    if (plan->npipe_chunks > 0) {   // graphs of more than 1248 rows: 32-row chunks on the rows kernel
-      dispatch_rows(ctx, rowptr, colidx, vals, h, ldh, bias, out, ldo, n, f, act, plan->pipe_chunks, plan->npipe_chunks);
-      GCNX_LAUNCH_OK(ctx);
-    }
-    return GCNX_OK;
-  }
-  // tier 1: two 512-thread workgroups per CU; tier 2: one 1024-thread workgroup with the whole LDS
-  const DuoFold bo{nullptr, nullptr, 0, 0, relu_bits};     // (graphs taller than a tile get no bits: their rows are folded from out)
-  const int dmode = relu_bits ? kDuoBitsOut : kDuoPlain;
-  // The three launches write disjoint rows.  GCNX_SPMM_CONC: as concurrent branches (two auxiliary streams), so that
-  // one launch's tail is filled by the next one's workgroups instead of draining the chip between them.
-  hipStream_t aux[2] = {nullptr, nullptr};
-  hipStream_t const home = ctx->stream;
-  const bool conc = ctx->knob_spmm_conc && (plan->n1 > 0) + (plan->n2 > 0) + (plan->nchunks > 0) >= 2;
-  if (conc) { int rc = gcnx_aux_fork(ctx, aux); if (rc) return rc; }
-  int rc = GCNX_OK;
-  if (plan->n2 > 0) {        // (the 1024-thread tier first: its workgroups are the hardest to place)
-    rc = launch_duo<1024, 32, 4>(ctx, rowptr, rowrec, colidx, vals, h, ldh, bias, out, ldo, n, f, act, plan->dev + plan->n1,
-                                 plan->n2, &bo, dmode, out16);
-  }
-  if (!rc && plan->n1 > 0) {
-    if (conc) ctx->stream = aux[0];
-    rc = launch_duo<512, 32, 4>(ctx, rowptr, rowrec, colidx, vals, h, ldh, bias, out, ldo, n, f, act, plan->dev, plan->n1, &bo, dmode);
-    ctx->stream = home;
-  }
-  const int ch0 = cb ? plan->nchunks_cb : 0;         // (column-block graphs' chunks come first in the list)
-  if (!rc && plan->nchunks > ch0) {   // graphs taller than any tile: plan-listed 32-row chunks on the rows kernel
-    if (conc) ctx->stream = aux[1];
-    const bool hubs = order && order->nsegs_tall > (cb ? order->nsegs_cb : 0);
-    dispatch_rows(ctx, rowptr, colidx, vals, h, ldh, bias, out, ldo, n, f, act, plan->dev + plan->n1 + plan->n2 + ch0,
-                  plan->nchunks - ch0, nullptr, plan->chunk_rpc, hubs ? kHubDeg : 0, out16);
-    if (hipGetLastError() != hipSuccess) rc = gcnx_fail(ctx, GCNX_ERR_HIP, "gcnx_spmm_csr: row-chunk launch failed");
-    if (!rc && hubs) rc = launch_hubs(ctx, order, true, colidx, vals, h, ldh, bias, out, ldo, n, f, act, nullptr, cb);
-    ctx->stream = home;
-  }
-  if (!rc && cb) {
-    if (conc) ctx->stream = aux[1];
-    rc = launch_cb(ctx, plan, order, colidx, vals, h, ldh, bias, out, ldo, n, f, act);
-    ctx->stream = home;
-  }
-  if (conc) { const int rj = gcnx_aux_join(ctx); if (!rc) rc = rj; }
-  return rc;
+  return GCNX_OK;
 }
-
-static int spmm_csr_pool_bwd_impl(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, const float* vals,
-                                  const float* y, int64_t ldy, const int32_t* graph_ptr, int32_t b, const float* dpooled,
-                                  int64_t lddp, float* out, int64_t ldo, int32_t n, int32_t f, int mode,
-                                  const gcnx_spmm_plan* plan, const void* y_bits, int out16);
 
 int gcnx_spmm_csr_pool_bwd(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, const float* vals,
                            const float* y, int64_t ldy, const int32_t* graph_ptr, int32_t b, const float* dpooled,
                            int64_t lddp, float* out, int64_t ldo, int32_t n, int32_t f, int mode,
                            const gcnx_spmm_plan* plan, const void* y_bits) {
-  return spmm_csr_pool_bwd_impl(ctx, rowptr, colidx, vals, y, ldy, graph_ptr, b, dpooled, lddp, out, ldo, n, f, mode, plan, y_bits, 0);
+  const FoldArgs fo{graph_ptr, dpooled, lddp, b, mode == GCNX_POOL_AVG ? 1 : 0};
+  return spmm_csr_pool_bwd_impl(SpmmCall{ctx, rowptr, colidx, vals, y, ldy, nullptr, out, ldo, n, f, GCNX_ACT_NONE, &fo, 0}, mode, plan, y_bits);
 }
 
 int gcnx_spmm_csr_pool_bwd_bf16out(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, const float* vals,
@@ -2522,74 +2587,8 @@ int gcnx_spmm_csr_pool_bwd_bf16out(gcnx_ctx* ctx, const int32_t* rowptr, const i
   GCNX_CHECK_CTX(ctx);
   GCNX_REQUIRE(ctx, out16 != nullptr || n == 0 || f == 0, "gcnx_spmm_csr_pool_bwd_bf16out: NULL output");
   if (!y_bits || !plan || plan->nblocks != b || !out16_shape_ok(ctx, plan, vals, f, ldo, out16)) return GCNX_ERR_UNSUPPORTED;
-  return spmm_csr_pool_bwd_impl(ctx, rowptr, colidx, vals, y, ldy, graph_ptr, b, dpooled, lddp, (float*)out16, ldo, n, f, mode, plan, y_bits, 1);
-}
-
-static int spmm_csr_pool_bwd_impl(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, const float* vals,
-                                  const float* y, int64_t ldy, const int32_t* graph_ptr, int32_t b, const float* dpooled,
-                                  int64_t lddp, float* out, int64_t ldo, int32_t n, int32_t f, int mode,
-                                  const gcnx_spmm_plan* plan, const void* y_bits, int out16) {
-  GCNX_CHECK_CTX(ctx);
-  GCNX_RANGE(ctx, "aggregation bwd (pool' folded)");
-  GCNX_REQUIRE(ctx, n >= 0 && f >= 0 && b >= 0, "gcnx_spmm_csr_pool_bwd: negative size");
-  GCNX_REQUIRE(ctx, mode == GCNX_POOL_SUM || mode == GCNX_POOL_AVG,
-               "gcnx_spmm_csr_pool_bwd: pool mode %d has no folded form (use gcnx_segment_pool_bwd + gcnx_spmm_csr)", mode);
-  if (n == 0 || f == 0) return GCNX_OK;
-  GCNX_REQUIRE(ctx, b > 0, "gcnx_spmm_csr_pool_bwd: rows without graphs");
-  GCNX_REQUIRE(ctx, rowptr && colidx && y && graph_ptr && dpooled && out, "gcnx_spmm_csr_pool_bwd: NULL pointer");
-  GCNX_REQUIRE(ctx, ldy >= f && ldo >= f && lddp >= f, "gcnx_spmm_csr_pool_bwd: leading dimension smaller than f=%d", f);
-  GCNX_REQUIRE(ctx, y != out, "gcnx_spmm_csr_pool_bwd: in-place aggregation is not possible");
-  GCNX_REQUIRE(ctx, (f % 4 == 0) && (ldy % 4 == 0) && (ldo % 4 == 0) && (lddp % 4 == 0) && aligned16(y) && aligned16(out) &&
-                        aligned16(dpooled),
-               "gcnx_spmm_csr_pool_bwd: needs f and the leading dimensions in multiples of 4 floats and 16-byte aligned "
-               "operands (use gcnx_segment_pool_bwd + gcnx_spmm_csr otherwise)");
   const FoldArgs fo{graph_ptr, dpooled, lddp, b, mode == GCNX_POOL_AVG ? 1 : 0};
-  // with a plan (throughput regime): the tile kernels in their folded form, taller graphs' row chunks on the rows kernel
-  const bool tiles = plan && plan->nblocks == b && f % kSlab == 0 && ctx->knob_spmm_kernel != 1 &&
-                     ((long long)(plan->n1 + 2 * plan->n2) * (f / kSlab) >= 4LL * ctx->num_cus || ctx->knob_spmm_kernel >= 2);
-  const RowRec* rowrec = nullptr;
-  const RowOrder* order = nullptr;
-  if (plan && plan->nblocks == b) { const int rb = plan_order(ctx, plan, rowptr, n, false, &rowrec, &order); if (rb) return rb; }
-  if (out16 && (!tiles || (order && order->nsegs_tall > 0))) return GCNX_ERR_UNSUPPORTED;
-  if (!tiles) {
-    if (cb_path_ok(ctx, plan, n, f, ldy, out16) && plan->nblocks == b && order != nullptr) {
-      // graphs too large for an XCD's L2 in column blocks, folded (r4: as the forward aggregation); the other graphs' rows as
-      // plan-listed chunks on the row gather, their hub rows as segments
-      if (plan->nrest > 0) {
-        const bool hubs = order->nsegs > order->nsegs_cb;
-        dispatch_rows(ctx, rowptr, colidx, vals, y, ldy, nullptr, out, ldo, n, f, GCNX_ACT_NONE, plan->rest, plan->nrest, &fo, plan->rest_rpc, hubs ? kHubDeg : 0);
-        GCNX_LAUNCH_OK(ctx);
-        if (hubs) { const int rh = launch_hubs(ctx, order, false, colidx, vals, y, ldy, nullptr, out, ldo, n, f, GCNX_ACT_NONE, &fo, true); if (rh) return rh; }
-      }
-      return launch_cb(ctx, plan, order, colidx, vals, y, ldy, nullptr, out, ldo, n, f, GCNX_ACT_NONE, &fo);
-    }
-    const bool hubs = order && order->nsegs > 0;
-    dispatch_rows(ctx, rowptr, colidx, vals, y, ldy, nullptr, out, ldo, n, f, GCNX_ACT_NONE, nullptr, 0, &fo, kRowsPerChunk, hubs ? kHubDeg : 0);
-    GCNX_LAUNCH_OK(ctx);
-    return hubs ? launch_hubs(ctx, order, false, colidx, vals, y, ldy, nullptr, out, ldo, n, f, GCNX_ACT_NONE, &fo) : GCNX_OK;
-  }
-  // y_bits (the forward's gcnx_spmm_csr_relu_bits image of y): the tiers expand it instead of reading y
-  const int dmode = y_bits ? kDuoFoldBits : kDuoFold;
-  if (plan->n1 > 0) {
-    const DuoFold df{plan->gids, dpooled, lddp, fo.avg, (uint32_t*)y_bits};
-    int rc = launch_duo<512, 32, 4>(ctx, rowptr, rowrec, colidx, vals, y, ldy, nullptr, out, ldo, n, f, GCNX_ACT_NONE, plan->dev, plan->n1, &df,
-                                    dmode);
-    if (rc) return rc;
-  }
-  if (plan->n2 > 0) {
-    const DuoFold df{plan->gids + plan->n1, dpooled, lddp, fo.avg, (uint32_t*)y_bits};
-    int rc = launch_duo<1024, 32, 4>(ctx, rowptr, rowrec, colidx, vals, y, ldy, nullptr, out, ldo, n, f, GCNX_ACT_NONE, plan->dev + plan->n1,
-                                     plan->n2, &df, dmode, out16);
-    if (rc) return rc;
-  }
-  if (plan->nchunks > 0) {
-    const bool hubs = order && order->nsegs_tall > 0;
-    dispatch_rows(ctx, rowptr, colidx, vals, y, ldy, nullptr, out, ldo, n, f, GCNX_ACT_NONE, plan->dev + plan->n1 + plan->n2,
-                  plan->nchunks, &fo, plan->chunk_rpc, hubs ? kHubDeg : 0, out16);
-    GCNX_LAUNCH_OK(ctx);
-    if (hubs) return launch_hubs(ctx, order, true, colidx, vals, y, ldy, nullptr, out, ldo, n, f, GCNX_ACT_NONE, &fo);
-  }
-  return GCNX_OK;
+  return spmm_csr_pool_bwd_impl(SpmmCall{ctx, rowptr, colidx, vals, y, ldy, nullptr, (float*)out16, ldo, n, f, GCNX_ACT_NONE, &fo, 1}, mode, plan, y_bits);
 }
 
 }  // extern "C"

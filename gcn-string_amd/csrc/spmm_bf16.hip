@@ -161,8 +161,8 @@ int gcnx_spmm_csr_bf16(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* coli
   if (!(f == 64 || f == 128 || f == 256) || (uint64_t)n * (uint64_t)ldh * 2u >= 0xFFFFFFF0ull)
     return gcnx_fail(ctx, GCNX_ERR_UNSUPPORTED, "gcnx_spmm_csr_bf16: needs f in {64, 128, 256} and n * ldh * 2 < 2^32 (got n=%d f=%d)", n, f);
   GCNX_REQUIRE(ctx, rowptr && colidx && h && out, "gcnx_spmm_csr_bf16: NULL pointer");
-  GCNX_REQUIRE(ctx, ldh >= f && ldo >= f && ldh % 8 == 0 && ldo % 8 == 0 && (reinterpret_cast<uintptr_t>(h) & 15) == 0 &&
-                        (reinterpret_cast<uintptr_t>(out) & 15) == 0,
+  GCNX_REQUIRE(ctx, ldh >= f && ldo >= f && ldh % 8 == 0 && ldo % 8 == 0 && gcnx_aligned16(h) &&
+                        gcnx_aligned16(out),
                "gcnx_spmm_csr_bf16: operands must be 16-byte aligned with leading dimensions in multiples of 8 elements");
   GCNX_REQUIRE(ctx, (const void*)h != (const void*)out, "gcnx_spmm_csr_bf16: in-place aggregation is not possible");
   const int tiles = gcnx_cdiv(n, kBRows);

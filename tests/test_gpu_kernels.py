@@ -109,6 +109,58 @@ def test_spmm_tile_kernel_all_tiers_forced(ctx, weighted, monkeypatch):
         ctx.set_tuning("spmm_sg", 0)
 
 
+@pytest.mark.parametrize("weighted", [False, True])
+def test_spmm_conc_branches_equal_serial_launches(ctx, weighted):
+    """spmm_conc = 1 (the tile route's launches as concurrent branches on two auxiliary streams) against spmm_conc = 0
+    (one after the other), bit for bit: once eagerly, once as a captured graph replayed twice.  The batch is the one of
+    test_spmm_tile_kernel_all_tiers_forced (17 312 rows, f = 64): under the forced tile kernels it has 512-thread tiles
+    (<= 632 rows), 1024-thread tiles (<= 1276) and two taller graphs on the row chunks, so all three branches launch."""
+    from gcnx import device as D, synth
+    import scipy.sparse as sp
+    rng = np.random.default_rng(11)
+    sizes = [1, 40, 100, 604, 605, 624, 625, 632, 633, 768, 769, 1024, 1025, 1236, 1237, 1264, 1265, 1276, 1277, 300, 2000, 7]
+    assert any(632 < m <= 1276 for m in sizes) and any(m > 1276 for m in sizes)
+    blocks = []
+    for i, m in enumerate(sizes):
+        dens = 0.5 if m in (40, 100) else min(1.0, 9.0 / m)
+        a = sp.random(m, m, density=dens, random_state=i, format="csr")
+        a = ((a + a.T) > 0).astype(np.float32) + sp.identity(m, dtype=np.float32, format="csr")
+        blocks.append((a > 0).astype(np.float32))
+    a = sp.block_diag(blocks).tocsr(); a.sort_indices()
+    n = a.shape[0]
+    gp = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+    hb = synth.HostBatch(rng.standard_normal((n, 64), dtype=np.float32), a.indptr.astype(np.int32), a.indices.astype(np.int32),
+                         None, gp, np.zeros((len(sizes), 2), np.float32))
+    csr, vals = _csr(ctx, hb, weighted)
+    bias = rng.standard_normal(64).astype(np.float32)
+    dx, db, out = ctx.to_device(hb.x), ctx.to_device(bias), ctx.zeros((n, 64))
+
+    def run():
+        D.spmm(ctx, csr, dx, db, out, act="relu")
+
+    try:
+        ctx.set_tuning("spmm_kernel", "tile")
+        ctx.set_tuning("spmm_conc", 0)
+        run()
+        serial = out.numpy().copy()
+        assert rel_err(serial, _ref_spmm(hb, vals, hb.x, bias, True)) < TIGHT
+        ctx.set_tuning("spmm_conc", 1)
+        out.fill_zero()
+        run()
+        assert np.array_equal(out.numpy(), serial), "eager"
+        g = ctx.capture(run)
+        try:
+            for replay in range(2):
+                out.fill_zero()
+                g.launch()
+                assert np.array_equal(out.numpy(), serial), ("captured", replay)
+        finally:
+            g.destroy()
+    finally:
+        ctx.set_tuning("spmm_kernel", "auto")
+        ctx.set_tuning("spmm_conc", 0)
+
+
 def test_side_sections_order_and_capture(ctx):
     """gcnx_side_begin / _end / _join: a side section sees everything submitted before it, the main stream sees the
     side results after the join, d2h joins implicitly, and a captured sequence with a side section replays
