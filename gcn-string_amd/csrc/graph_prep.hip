@@ -161,6 +161,46 @@ __global__ __launch_bounds__(256) void collate_kernel(const int32_t* __restrict_
   }
 }
 
+// The per-entry side of a batch, a second launch after collate_kernel (same desc, same grid): the selected graphs' blocks of
+// the union's TRANSPOSED pattern (gcnx_csr_transpose_perm of the union) and their rows of the edge features.  The union is
+// block-diagonal, so graph src's block of the transpose occupies the entry range [e0, e0 + ne) of its own CSR block, with
+// rowptr_t[n0] == rowptr[n0] (the caller checked that once, on the host) and perm_t values inside the same range: re-based, they
+// are the integers gcnx_csr_transpose_perm gives on the batch's own CSR -- no sort per batch.
+__global__ __launch_bounds__(256) void collate_edges_kernel(const int32_t* __restrict__ desc /* sel | bnode | bent, each b+1 */,
+                                                            int32_t b, const int32_t* __restrict__ node_ptr,
+                                                            const int32_t* __restrict__ rowptr, const int32_t* __restrict__ rowptr_t,
+                                                            const int32_t* __restrict__ colidx_t, const int32_t* __restrict__ perm_t,
+                                                            const float* __restrict__ e, int64_t lde, int32_t s,
+                                                            int32_t* __restrict__ o_rowptr_t, int32_t* __restrict__ o_colidx_t,
+                                                            int32_t* __restrict__ o_perm_t, float* __restrict__ o_e, int64_t ldoe) {
+  const int g = blockIdx.y;                       // position in the batch
+  const int src = desc[g];
+  const int bn = desc[(b + 1) + g], be = desc[2 * (b + 1) + g];
+  const int n0 = node_ptr[src], ng = node_ptr[src + 1] - n0;
+  const int e0 = rowptr[n0], ne = rowptr[n0 + ng] - e0;
+  const int tid = blockIdx.x * blockDim.x + threadIdx.x, nth = gridDim.x * blockDim.x;
+  // rows of the transpose: row pointers re-based to the batch's entry offset
+  for (int i = tid; i < ng; i += nth) o_rowptr_t[bn + i] = rowptr_t[n0 + i] - e0 + be;
+  // its entries: sources re-based to the batch's node offset, entry numbers to its entry offset
+  for (int p = tid; p < ne; p += nth) {
+    o_colidx_t[be + p] = colidx_t[e0 + p] - n0 + bn;
+    o_perm_t[be + p] = perm_t[e0 + p] - e0 + be;
+  }
+  // edge feature rows, in the order of the batch CSR's entries
+  const int64_t total = (int64_t)ne * s;
+  if (lde == s && ldoe == s) {                    // dense on both sides: the graph's rows are one run of ne * s floats
+    const float* __restrict__ from = e + (int64_t)e0 * s;
+    float* __restrict__ to = o_e + (int64_t)be * s;
+    for (int64_t k = tid; k < total; k += nth) to[k] = from[k];
+  } else {
+    for (int64_t k = tid; k < total; k += nth) {
+      const int64_t i = k / s, j = k - i * s;
+      o_e[(int64_t)(be + i) * ldoe + j] = e[(int64_t)(e0 + i) * lde + j];
+    }
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0 && g == b - 1) o_rowptr_t[desc[(b + 1) + b]] = desc[2 * (b + 1) + b];
+}
+
 }  // namespace
 
 extern "C" {
@@ -313,6 +353,24 @@ int gcnx_collate(gcnx_ctx* ctx, const int32_t* desc, int32_t b, const int32_t* n
                  int32_t* o_graph_ptr, int32_t* o_node_graph) {
   return gcnx_collate2(ctx, desc, b, node_ptr, rowptr, colidx, vals, x, ldx, f, y, c, o_rowptr, o_colidx, o_vals, o_x, ldo, o_y,
                        o_graph_ptr, o_node_graph, nullptr, 0, nullptr, 0);
+}
+
+
+int gcnx_collate_edges(gcnx_ctx* ctx, const int32_t* desc, int32_t b, const int32_t* node_ptr, const int32_t* rowptr,
+                       const int32_t* rowptr_t, const int32_t* colidx_t, const int32_t* perm_t, const float* e, int64_t lde,
+                       int32_t s, int32_t* o_rowptr_t, int32_t* o_colidx_t, int32_t* o_perm_t, float* o_e, int64_t ldoe) {
+  GCNX_CHECK_CTX(ctx);
+  GCNX_RANGE(ctx, "device-side collate: edges");
+  GCNX_REQUIRE(ctx, b >= 0, "gcnx_collate_edges: negative size");
+  if (b == 0) return GCNX_OK;
+  GCNX_REQUIRE(ctx, desc && node_ptr && rowptr && rowptr_t && colidx_t && perm_t && e, "gcnx_collate_edges: NULL pointer");
+  GCNX_REQUIRE(ctx, o_rowptr_t && o_colidx_t && o_perm_t && o_e, "gcnx_collate_edges: NULL output pointer");
+  GCNX_REQUIRE(ctx, s >= 1 && lde >= s && ldoe >= s, "gcnx_collate_edges: bad edge feature buffers (s=%d, lde=%lld, ldoe=%lld)",
+               (int)s, (long long)lde, (long long)ldoe);
+  hipLaunchKernelGGL(collate_edges_kernel, dim3(16, b), dim3(256), 0, ctx->stream, desc, b, node_ptr, rowptr, rowptr_t, colidx_t,
+                     perm_t, e, lde, s, o_rowptr_t, o_colidx_t, o_perm_t, o_e, ldoe);
+  GCNX_LAUNCH_OK(ctx);
+  return GCNX_OK;
 }
 
 }  // extern "C"

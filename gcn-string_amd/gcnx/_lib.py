@@ -65,6 +65,7 @@ SIGNATURES = {
     "gcnx_collate": [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp],
     "gcnx_collate2": [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
                       _vp, _i64, _vp, _i64],
+    "gcnx_collate_edges": [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i64],
     "gcnx_gcn_norm": [_vp, _vp, _vp, _vp, _i32, _int, _vp],
     "gcnx_set_tuning": [_vp, C.c_char_p, _int],
     "gcnx_csr_inspect": [_vp, _vp, _vp, _vp, _i32, _vp, _i32, C.POINTER(C.c_int)],

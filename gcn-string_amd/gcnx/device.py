@@ -421,6 +421,10 @@ class DeviceCSR:
         if getattr(self, "_unweighted", None) is None:
             self._unweighted = DeviceCSR(self.ctx, self.n, self.nnz, self.rowptr, self.colidx, None, self.block_ptr, self.n_blocks,
                                          self.symmetric, self.max_block_rows)
+        if getattr(self._unweighted, "_tperm", None) is None:
+            # the same pattern: the view takes the transposed pattern this operator already has (a device loader's batch
+            # arrives with it: gcnx_collate_edges), instead of sorting for one of its own
+            self._unweighted._tperm = getattr(self, "_tperm", None)
         return self._unweighted
 
 

@@ -593,6 +593,18 @@ class ECCConv(Layer):
         return ecc_unpack_weights({k: v.numpy() for k, v in self.grads.items()}, self.in_dim, self.channels, self.root)
 
     # ---- forward / backward -------------------------------------------------------------------------------------------
+    def _buf(self, key, shape, dtype=np.float32):
+        """Grow-only scratch: a view of exactly ``shape`` on storage that is replaced only when it is too small.  A streamed
+        epoch brings a new (N, nnz) with every batch, and Layer._buf would allocate [Scat | x] (15 MB at the config-2 batch
+        shape) and the rest again on every step."""
+        shape = tuple(int(d) for d in shape)
+        need = int(np.prod(shape, dtype=np.int64))
+        cur = self._scratch.get(key)
+        if cur is None or cur.size < need or cur.dtype != np.dtype(dtype):
+            cur = self.ctx.empty(max(need, int(1.25 * cur.size) if cur is not None else 0, 1), dtype)
+            self._scratch[key] = cur
+        return D.DeviceArray._view(cur, 0, shape)
+
     def call(self, inputs, out=None):
         x, a, e = inputs
         if e is None:

@@ -1679,7 +1679,9 @@ class ECCNet(_GraphRunner):
     -- the shape of Spektral's ECC graph-classification example and of GCN2 -- with the categorical cross-entropy and one-hot
     labels of gcn.py:259-262,326 and plain SGD.  ``ECCNet([ctx,] n_labels=2, channels=32, kernel_network=None, pool="sum",
     seed=0)``; inputs are ``(x, a, e, i)`` as DisjointLoader yields them for ``Graph(e=...)`` (e: one row per stored entry of a,
-    from_networkx(use_edge_data="entries")) or a DeviceBatch that carries ``e``.  The values of ``a`` are ignored.
+    from_networkx(use_edge_data="entries")) or a DeviceBatch that carries ``e`` -- from_host's, or the batches of a
+    DeviceDisjointLoader over ``DeviceDataset(edge_features=True)``, which arrive with e and the transposed pattern gathered on
+    the device (no host sort per batch).  The values of ``a`` are ignored.
 
     Follows the GCN2 protocol (model(inputs, training=), loss_and_grads, train_step(fetch=True | False | "stash"),
     evaluate_batch, collect_metrics; one flat parameter buffer, one SGD launch), so gcnx.fit / gcnx.evaluate drive it.

@@ -153,6 +153,18 @@ GCNX_API int gcnx_collate2(gcnx_ctx* ctx, const int32_t* desc, int32_t b, const 
                  const int32_t* colidx, const float* vals, const float* x, int64_t ldx, int32_t f, const float* y,
                  int32_t c, int32_t* o_rowptr, int32_t* o_colidx, float* o_vals, float* o_x, int64_t ldo, float* o_y,
                  int32_t* o_graph_ptr, int32_t* o_node_graph, const float* s, int64_t lds, float* o_s, int64_t ldos);
+/* The per-entry side of the same batch, a second launch on the same stream (Spektral's collate vstacks the graphs' edge
+ * features e, gcn.py:173-180; spektral.layers.ECCConv reads them): desc, b, node_ptr and rowptr (the union's CSR row pointer,
+ * read for every graph's entry offset and count) as in gcnx_collate; rowptr_t / colidx_t / perm_t = gcnx_csr_transpose_perm of
+ * the UNION, e [nnz_all, s] (lde) its edge features, row k belonging to stored entry k.  The union being block-diagonal, a
+ * graph's block of the transpose lies in the entry range of its own CSR block (rowptr_t[node_ptr[g]] == rowptr[node_ptr[g]]
+ * for every g: the caller's guarantee), so the batch's transpose is gathered, not sorted.  Writes o_rowptr_t[N+1],
+ * o_colidx_t[nnz], o_perm_t[nnz] -- exactly what gcnx_csr_transpose_perm returns on the batch's own CSR -- and o_e[nnz, s]
+ * (ldoe), the rows of e in the batch CSR's entry order; nothing else (columns >= s of o_e and whatever lies past N + 1 / nnz
+ * stay as they were).  Integer outputs are exact; floats are copies.  s >= 1; b == 0 writes nothing.  Does not synchronise. */
+GCNX_API int gcnx_collate_edges(gcnx_ctx* ctx, const int32_t* desc, int32_t b, const int32_t* node_ptr, const int32_t* rowptr,
+                       const int32_t* rowptr_t, const int32_t* colidx_t, const int32_t* perm_t, const float* e, int64_t lde,
+                       int32_t s, int32_t* o_rowptr_t, int32_t* o_colidx_t, int32_t* o_perm_t, float* o_e, int64_t ldoe);
 /* Spektral GCNConv.preprocess = gcn_filter on a CSR whose every row stores its
  * diagonal entry (true for the reference's data: gcn_utills.py:224-227 keeps the 0-Angstrom
  * diagonal).  vals_in NULL = ones.  SPEKTRAL: diag += 1; PYG: existing loops kept.

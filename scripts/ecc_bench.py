@@ -15,7 +15,17 @@ median of the rounds with their spread (min .. max); C = S' + 1 channels (S' = 2
   bwd (dx)  gcnx_ecc_bwd, dx (+ du with a   vs   C x gcnx_spmm_csr on the batch CSR into a scratch + (C - 1) x gcnx_add
             kernel network)                      (no existing kernel composes du: that side is dx only)
 
-for the two layer widths of the model (F = 16 and F = channels).  Prints one JSON line."""
+for the two layer widths of the model (F = 16 and F = channels).  Prints one JSON line.
+
+  python scripts/ecc_bench.py --stream --shape ref               # a NEW batch every step: 400 tiny graphs, batches of 50
+  python scripts/ecc_bench.py --stream --shape ecoli             # 256 E. coli-shaped graphs, batches of 32
+
+--stream: ms per batch of ECCNet.train_step INCLUDING the batch's assembly, fed (a) by DisjointLoader + DeviceBatch.from_host
+(host vstack / block_diag, upload, and gcnx_csr_transpose_perm's download + host sort + upload per batch) and (b) by
+DeviceDisjointLoader over DeviceDataset(edge_features=True) (gcnx_collate2 + gcnx_collate_edges per batch).  Both in this
+process, one epoch of each per round, alternating; wall time between two synchronisations, median with min .. max of the rounds
+(and the GPU's own time between two stream events).  The two models see the same batches and must end with the same weights.
+Also the two collate launches alone, HIP events around --reps back-to-back calls, alternated the same way.  One JSON line."""
 import argparse
 import json
 import os
@@ -107,6 +117,102 @@ def kernel_ab(ctx, a, f, u, with_du, rounds, reps, seed=0):
     return out
 
 
+def stream_dataset(shape, n_graphs, f=16):
+    """(ListDataset of Graph(x, a, e, y), batch size): the graphs of host_batch's shapes one by one, every graph with the
+    edge_features of its own entries."""
+    import scipy.sparse as sp
+    from types import SimpleNamespace
+    rng = np.random.default_rng(0)
+    if shape == "ecoli":
+        raw = []
+        for _ in range(n_graphs):
+            n, u, v = synth.ecoli_graph_pairs(rng)
+            a = sp.coo_matrix((np.ones(u.size), (u, v)), shape=(n, n)).tocsr()
+            y = np.zeros(2, np.float32)
+            y[int(rng.integers(0, 2))] = 1
+            raw.append((rng.standard_normal((n, f), dtype=np.float32), ((a + a.T + sp.identity(n)) > 0).astype(np.float32).tocsr(), y))
+    else:
+        raw = synth.tiny_graphs(n_graphs, f, seed=0)
+    graphs = []
+    for k, (x, a, y) in enumerate(raw):
+        a = sp.csr_matrix(a)
+        a.sort_indices()
+        e = edge_features(SimpleNamespace(n=a.shape[0], rowptr=a.indptr, colidx=a.indices), seed=k)
+        graphs.append(gcnx.Graph(x=np.asarray(x, np.float32), a=a, e=e, y=np.asarray(y, np.float32)))
+    return gcnx.ListDataset(graphs), (32 if shape == "ecoli" else 50)
+
+
+def spread(v, digits=4):
+    return {"median": round(float(np.median(v)), digits), "min": round(float(min(v)), digits), "max": round(float(max(v)), digits)}
+
+
+def stream(args, kn):
+    import time
+    from gcnx.device_loader import DeviceDataset, DeviceDisjointLoader, collate_on_device
+    ds, bs = stream_dataset(args.shape, args.graphs or (256 if args.shape == "ecoli" else 400))
+    ctx = gcnx.Context(0)
+    dsd = DeviceDataset(ctx, ds, edge_features=True)
+    epochs = args.rounds + 1                                            # the first epoch of either route is warm-up
+    routes = {"host_loader": gcnx.DisjointLoader(ds, batch_size=bs, epochs=epochs, shuffle=True, seed=1),
+              "device_loader": DeviceDisjointLoader(dsd, batch_size=bs, epochs=epochs, shuffle=True, seed=1)}
+    models = {k: gcnx.ECCNet(ctx, 2, channels=args.channels, kernel_network=kn, seed=0) for k in routes}
+    spe = routes["host_loader"].steps_per_epoch
+    wall, gpu = {k: [] for k in routes}, {k: [] for k in routes}
+    n_nodes = nnz = 0
+    for r in range(epochs):
+        for k, loader in routes.items():
+            ctx.sync()
+            t0, e0 = time.perf_counter(), ctx.event().record()
+            for _ in range(spe):
+                inputs, target = next(loader)
+                batch = inputs if k == "device_loader" else DeviceBatch.from_host(ctx, inputs, target, weighted=False)
+                models[k].train_step(batch, None, lr=1e-3, fetch=False)
+                n_nodes, nnz = max(n_nodes, batch.n), max(nnz, batch.a.nnz)
+            e1 = ctx.event().record()
+            ctx.sync()
+            if r:
+                wall[k].append((time.perf_counter() - t0) / spe * 1e3)
+                gpu[k].append(e1.elapsed_ms_since(e0) / spe)
+    w = {k: m.get_weights() for k, m in models.items()}
+    same = all(np.array_equal(p, q) for p, q in zip(w["host_loader"], w["device_loader"]))
+    # the collate launches alone, on one full batch of the device route (its descriptor stays in the buffers)
+    sel = np.arange(min(bs, len(ds)))
+    batch = collate_on_device(dsd, sel)
+    bufs, csr, b = batch._bufs, dsd.csr, len(sel)
+    rp_t, ci_t, pm_t = dsd.tperm
+    lib, vals = ctx.lib, (dsd.csr.vals.ptr if dsd.csr.vals is not None else None)
+
+    def collate2():
+        ctx._ck(lib.gcnx_collate2(ctx.h, bufs.desc.ptr, b, dsd.node_ptr.ptr, csr.rowptr.ptr, csr.colidx.ptr, vals, dsd.x.ptr, dsd.x.ld,
+                                  dsd.n_features, dsd.y.ptr, dsd.n_labels, bufs.rowptr.ptr, bufs.colidx.ptr,
+                                  bufs.vals.ptr if vals else None, bufs.x.ptr, bufs.x.ld, bufs.y.ptr, bufs.gp.ptr, bufs.ids.ptr,
+                                  None, 0, None, 0))
+
+    def both():
+        collate2()
+        ctx._ck(lib.gcnx_collate_edges(ctx.h, bufs.desc.ptr, b, dsd.node_ptr.ptr, csr.rowptr.ptr, rp_t.ptr, ci_t.ptr, pm_t.ptr,
+                                       dsd.e.ptr, dsd.e.ld, dsd.n_edge_features, bufs.rowptr_t.ptr, bufs.colidx_t.ptr,
+                                       bufs.perm_t.ptr, bufs.e.ptr, bufs.e.ld))
+    for fn in (collate2, both):
+        for _ in range(10):
+            fn()
+    ctx.sync()
+    us = {"collate2": [], "collate2+collate_edges": []}
+    for _ in range(args.rounds):
+        us["collate2"].append(timed(ctx, collate2, args.reps))
+        us["collate2+collate_edges"].append(timed(ctx, both, args.reps))
+    med = {k: float(np.median(v)) for k, v in wall.items()}
+    print(json.dumps({"model": "gcnx.ECCNet", "mode": "stream", "shape": args.shape, "graphs": len(ds), "batch_size": bs,
+                      "batches_per_epoch": spe, "rounds": args.rounds, "largest_batch": {"n_nodes": int(n_nodes), "nnz": int(nnz)},
+                      "f_in": 16, "edge_dim": dsd.n_edge_features, "channels": args.channels, "kernel_network": kn,
+                      "ms_per_batch_wall": {k: spread(v) for k, v in wall.items()},
+                      "ms_per_batch_between_stream_events": {k: spread(v) for k, v in gpu.items()},
+                      "host_over_device": round(med["host_loader"] / med["device_loader"], 2),
+                      "collate_us": {k: spread(v, 2) for k, v in us.items()},
+                      "collate_batch": {"n_nodes": batch.n, "nnz": batch.a.nnz}, "final_weights_equal": bool(same)}))
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shape", choices=("ref", "ecoli"), default="ref")
@@ -116,8 +222,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--stream", action="store_true", help="a new batch every step, host loader against device loader")
+    ap.add_argument("--graphs", type=int, default=0, help="--stream: graphs in the dataset (default 400 ref / 256 ecoli)")
     args = ap.parse_args()
     kn = None if args.kernel_network == "none" else [int(args.kernel_network)]
+    if args.stream:
+        return stream(args, kn)
     hb = host_batch(args.shape)
     e = edge_features(hb)
     ctx = gcnx.Context(0)
