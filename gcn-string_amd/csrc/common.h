@@ -85,18 +85,38 @@ int gcnx_ws_reserve(gcnx_ctx* ctx, size_t bytes);  // ensures ctx->ws has >= byt
 // ctx->stream ordered after everything submitted to them (join).  Both work inside stream capture.
 extern "C" int gcnx_aux_fork(gcnx_ctx* ctx, hipStream_t out[2]);
 extern "C" int gcnx_aux_join(gcnx_ctx* ctx);
-// gemm_stream.hip: X W (transpose = 1) / dH W^T (transpose = 0) on the streaming bf16 kernel; GCNX_ERR_UNSUPPORTED
-// (no message) when the shape is not one it is built for.
-int gcnx_gemm_stream_nn(gcnx_ctx* ctx, const float* a, int64_t lda, const float* w, int fi, int fo, int transpose, float* c,
-                        int64_t ldc, int64_t m, int prec, const float* bias, const float* alpha, int act, const float* mask,
-                        int64_t ldmask, int accumulate, float* colsum_out /* column sums of c, or NULL */,
-                        const void* mask_bits = nullptr /* bit image read instead of mask */, void* bits_out = nullptr /* written */);
+// gemm_stream.hip: the operands of one X W (transpose = 1) / dH W^T (transpose = 0) on the streaming bf16 kernels, filled by
+// field name at the call site and passed by reference (nothing is allocated).  gcnx_gemm_stream_nn streams fp32 rows
+// at `prec`; gcnx_gemm_stream_bf16 streams rows STORED as bf16 (plain bf16 products, fi = fo = 256) and stores the result
+// as bf16 (c_bf16) or fp32.  Both return GCNX_ERR_UNSUPPORTED, without a message and with nothing launched, when the
+// shape is not one the kernel is built for.
+struct GemmStreamCall {
+  gcnx_ctx* ctx = nullptr;
+  const void* a = nullptr;          // streamed operand [m][lda]: fp32 (stream_nn) / bf16 (stream_bf16), lda in elements
+  int64_t lda = 0;
+  const float* w = nullptr;         // [fi][fo]
+  int fi = 0, fo = 0, transpose = 0;
+  void* c = nullptr;                // result [m][ldc]: fp32, or bf16 with c_bf16 (stream_bf16 only)
+  int64_t ldc = 0;
+  int c_bf16 = 0;
+  int64_t m = 0;
+  int prec = GCNX_PREC_BF16;        // stream_nn only: GCNX_PREC_BF16 / GCNX_PREC_BF16X3
+  const float* bias = nullptr;
+  const float* alpha = nullptr;     // stream_nn only
+  int act = GCNX_ACT_NONE;
+  const float* mask = nullptr;      // stream_nn only: ReLU mask source (fp32, same shape as c) ...
+  int64_t ldmask = 0;
+  int accumulate = 0;               // ... and c += result (answered with UNSUPPORTED)
+  float* colsum_out = nullptr;      // column sums of c, or NULL
+  const void* mask_bits = nullptr;  // bit image read instead of mask
+  void* bits_out = nullptr;         // bit image of [c > 0], written
+  const void* wimg = nullptr;       // stream_bf16 only: the caller's image of w (gcnx_gemm_stream_images), or NULL
+};
+int gcnx_gemm_stream_nn(const GemmStreamCall& c);
+int gcnx_gemm_stream_bf16(const GemmStreamCall& c);
+int gcnx_gemm_stream_images_impl(gcnx_ctx* ctx, int njobs, const float* const* w, const int* transpose, void* const* img);
 // gemm_stream.hip: X^T dH for fi = fo = 256 on the streaming bf16 kernel: writes [slices][256 * 256] partial products to
 // `slabs` (room for max_slices of them) and returns the number of slices; 0 = shape not handled, < 0 = launch error.
-int gcnx_gemm_stream_bf16(gcnx_ctx* ctx, const void* a16, int64_t lda, const float* w, int fi, int fo, int transpose, void* c,
-                          int64_t ldc, int c_bf16, int64_t m, const float* bias, int act, float* colsum_out, const void* mask_bits,
-                          void* bits_out, const void* wimg);
-int gcnx_gemm_stream_images_impl(gcnx_ctx* ctx, int njobs, const float* const* w, const int* transpose, void* const* img);
 int gcnx_gemm_dw_stream16(gcnx_ctx* ctx, const void* x16, int64_t ldx, const void* dh16, int64_t lddh, float* slabs, int64_t n,
                           int32_t fi, int32_t fo, int max_slices);
 int gcnx_gemm_dw_stream(gcnx_ctx* ctx, const float* x, int64_t ldx, const float* dh, int64_t lddh, float* slabs, int64_t n,
@@ -227,6 +247,46 @@ static inline int gcnx_cdiv(long long a, long long b) { return (int)((a + b - 1)
 
 // What a float4 / b128 access of p needs (host side: the launchers pick their vector forms by it).
 static inline bool gcnx_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// What a bit image (one 64-bit word per lane group) needs; a NULL image passes.
+static inline bool gcnx_aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
+// rows x leading dimension x element bytes fit ONE buffer descriptor: 32-bit byte offsets, with the top 256 bytes left
+// to the offsets that must fall outside every descriptor.
+static inline bool gcnx_fits_buffer(int64_t rows, int64_t ld, unsigned elem_bytes) {
+  return (uint64_t)rows * (uint64_t)ld * elem_bytes < 0xFFFFFF00ull;
+}
+
+// Row slices of a product summed over n rows (split-K): `want` slices of whole K steps (kstep rows each), none shorter
+// than min_steps, then as many as the rounded slice length leaves (n > 0).
+struct GcnxSplit { int nsplit; int64_t kchunk; };
+static inline GcnxSplit gcnx_split_rows(int64_t want, int64_t n, int kstep, int64_t min_steps) {
+  const int64_t ksteps = (n + kstep - 1) / kstep;
+  int nsplit = (int)want;
+  if (nsplit > ksteps / min_steps) nsplit = (int)(ksteps / min_steps);
+  if (nsplit < 1) nsplit = 1;
+  const int64_t kchunk = ((ksteps + nsplit - 1) / nsplit) * kstep;
+  return GcnxSplit{(int)((n + kchunk - 1) / kchunk), kchunk};
+}
+
+// One reading of a launch for the bf16 / bf16x3 pair of a kernel family: LAUNCH(arg) is the site's launch text with the
+// template argument that differs left open, so the kernel arguments appear once per site.
+#define GCNX_BF16_PAIR(prec, LAUNCH, arg_bf16, arg_bf16x3) \
+  do { if ((prec) == GCNX_PREC_BF16X3) { LAUNCH(arg_bf16x3); } else { LAUNCH(arg_bf16); } } while (0)
+
+#ifdef __HIPCC__
+// Launch of a kernel with dynamic LDS: raises the kernel's dynamic-LDS limit once per instantiation (the flag is this
+// template's own static), then launches.  Returns the attribute call's error; launch errors are read by the caller.
+template <auto Kernel, typename... Args>
+static inline hipError_t gcnx_launch_dyn_lds(dim3 grid, dim3 block, int lds_bytes, hipStream_t stream, Args... args) {
+  static bool attr_set = false;
+  if (!attr_set) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+    if (e != hipSuccess) return e;
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(Kernel, grid, block, lds_bytes, stream, args...);
+  return hipSuccess;
+}
+#endif
 
 // Blocks b and b+8 share an XCD (observed round-robin dealing; speed only, never correctness).
 // Bijective remap that gives every XCD one contiguous range of logical work items, so that

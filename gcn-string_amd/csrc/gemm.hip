@@ -10,6 +10,27 @@
 // 32x32 MFMA accumulator tile each) owns a 64x64 output tile and walks K in steps of 32 through
 // LDS.  LDS images are k-major ([k][m] and [k][n]) so that the MFMA operand read -- lane l takes
 // element [k = 2*kk + (l>>5)][l & 31] -- is 32 consecutive dwords per half-wave: conflict-free.
+//
+// Host routes per entry point, and the launcher that serves each (first that applies):
+//   gcnx_gemm             bf16 precisions: launch_bf16_nn (gcnx_gemm_stream_nn for tall aligned activations, else wprep +
+//                         gemm_bf16_kernel<0>) | f32, >= 2048 rows of K <= 256: launch_rowtile | gemm_f32_kernel<true, false>
+//   gcnx_gemm_dx          bf16 precisions: launch_bf16_nn (+ gcnx_colsum unless the streaming kernel summed db) | f32 row
+//                         tile: transpose_small + launch_rowtile (+ gcnx_colsum_partials) | gemm_f32_kernel<true, true>
+//                         (+ gcnx_colsum_partials, or gcnx_colsum for ragged / unaligned shapes)
+//   gcnx_gemm_relu_bits, gcnx_gemm_dx_bits             gcnx_gemm_stream_nn with a bit image, or UNSUPPORTED
+//   gcnx_gemm_fwd_bf16, gcnx_gemm_dx_bf16              gcnx_gemm_stream_bf16, or UNSUPPORTED
+//   gcnx_gemm_dw_bf16     dw_streamed_tall (bf16-stored operands), or UNSUPPORTED
+//   gcnx_gemm_dw          bf16 precisions: dw_streamed_tall (256 x 256, >= 32 768 rows) | gcnx_gemm_dw_panels (mid-size /
+//                         wide) | gemm_bf16_kernel<1> + launch_splitk_reduce.  f32: splitk_plan_f32 -> dw_job ->
+//                         launch_dw_job (+ launch_splitk_reduce)
+//   gcnx_gemm_dw_sgd      f32 with something to reduce: the plan and job of gcnx_gemm_dw -> launch_dw_job ->
+//                         reduce_sgd_kernel (slabs + sgd_pending + update) | else flush_pending, gcnx_gemm_dw, gcnx_sgd
+//   gcnx_gemm_dw2         f32, both products split: two dw_job on one plan -> gemm_f32_dw2_kernel / _dw2_head_kernel (head
+//                         leaves inside, else gcnx_head_from_parts first) -> reduce_sgd_kernel | else flush_pending,
+//                         gcnx_head_from_parts, gcnx_gemm_dw twice, gcnx_sgd
+//   gcnx_dense_bwd, gcnx_dense_bwd_deferred            f32, aligned, fi % 64 == 0: dense_bwd_split -> dX job + dw_job ->
+//                         gemm_f32_duo_kernel, then flush_pending (reduce_duo_kernel) or the record handed to the
+//                         caller | else gcnx_gemm_dx + gcnx_gemm_dw
 #include "common.h"
 #include "head_body.h"
 
@@ -30,6 +51,16 @@ struct Epilogue {
   float* colpart = nullptr;   // f32 kernel, float4 epilogue only: column sums of each wave's 32 rows of what it
                               // wrote -> colpart[(blockIdx.y * 2 + wm) * Nc + col] (BiasAddGrad partials)
 };
+// The common forms (host side).  Plain: the raw product (dW and its split-K slabs).
+inline Epilogue epi_plain(int vec_c) { return Epilogue{nullptr, nullptr, nullptr, 0, GCNX_ACT_NONE, 0, vec_c, nullptr}; }
+// Forward: bias + activation (alpha only with PReLU).
+inline Epilogue epi_act(const float* bias, const float* alpha, int act, int vec_c) {
+  return Epilogue{bias, act == GCNX_ACT_PRELU ? alpha : nullptr, nullptr, 0, act, 0, vec_c, nullptr};
+}
+// dX: ReLU mask (or none) + column partials (or none), or C += result.
+inline Epilogue epi_mask(const float* mask, int64_t ldmask, int accumulate, int vec_c, float* colpart) {
+  return Epilogue{nullptr, nullptr, mask, ldmask, GCNX_ACT_NONE, accumulate, vec_c, colpart};
+}
 
 // One 64x32 (or 32x64) operand tile, global -> registers (2 float4 per thread), then registers
 // -> the k-major LDS image s[k][LD].  Splitting the two lets the loads of tile t+1 fly during
@@ -797,17 +828,21 @@ namespace {
 // colsum_out / colsum_done (may be NULL): column sums of c wanted / set to 1 if this call produced them (the streaming
 // kernel sums what it writes; otherwise the caller runs a column-sum pass).
 int launch_bf16_nn(gcnx_ctx* ctx, const float* a, int64_t lda, const float* w, int fi, int fo, int transpose,
-                   float* c, int64_t ldc, int64_t m, int prec, const Epilogue& ep, float* colsum_out = nullptr,
-                   int* colsum_done = nullptr) {
+                   float* c, int64_t ldc, int64_t m, int prec, const Epilogue& ep, float* colsum_out, int* colsum_done) {
   const int ncol = transpose ? fo : fi, K = transpose ? fi : fo;
   if (colsum_done) *colsum_done = 0;
   if (ep.vec_c && !ep.colpart) {            // tall activations: the streaming kernel (weights resident in LDS)
-    int rs = gcnx_gemm_stream_nn(ctx, a, lda, w, fi, fo, transpose, c, ldc, m, prec, ep.bias, ep.alpha, ep.act, ep.mask, ep.ldmask,
-                                 ep.accumulate, colsum_done ? colsum_out : nullptr);
+    GemmStreamCall sc;
+    sc.ctx = ctx; sc.a = a; sc.lda = lda; sc.w = w; sc.fi = fi; sc.fo = fo; sc.transpose = transpose;
+    sc.c = c; sc.ldc = ldc; sc.m = m; sc.prec = prec;
+    sc.bias = ep.bias; sc.alpha = ep.alpha; sc.act = ep.act; sc.mask = ep.mask; sc.ldmask = ep.ldmask; sc.accumulate = ep.accumulate;
+    sc.colsum_out = colsum_done ? colsum_out : nullptr;
+    int rs = gcnx_gemm_stream_nn(sc);
     if (rs == GCNX_OK && colsum_done && colsum_out) *colsum_done = 1;
-    if (rs == GCNX_ERR_UNSUPPORTED && colsum_done && colsum_out)   // (e.g. an unaligned db): without the sums
-      rs = gcnx_gemm_stream_nn(ctx, a, lda, w, fi, fo, transpose, c, ldc, m, prec, ep.bias, ep.alpha, ep.act, ep.mask, ep.ldmask,
-                               ep.accumulate, nullptr);
+    if (rs == GCNX_ERR_UNSUPPORTED && colsum_done && colsum_out) {   // (e.g. an unaligned db): without the sums
+      sc.colsum_out = nullptr;
+      rs = gcnx_gemm_stream_nn(sc);
+    }
     if (rs != GCNX_ERR_UNSUPPORTED) return rs;
   }
   const int kpad = ((K + HK - 1) / HK) * HK;
@@ -821,12 +856,11 @@ int launch_bf16_nn(gcnx_ctx* ctx, const float* a, int64_t lda, const float* w, i
   GCNX_LAUNCH_OK(ctx);
   dim3 grid(gcnx_cdiv(ncol, HN), gcnx_cdiv(m, HM), 1);
   const int va = gcnx_aligned16(a) && lda % 4 == 0;
-  if (prec == GCNX_PREC_BF16X3)
-    hipLaunchKernelGGL((gemm_bf16_kernel<0, true>), grid, dim3(256), 0, ctx->stream, a, lda, (const float*)nullptr,
-                       (int64_t)0, hi, lo, kpad, c, ldc, m, ncol, (int64_t)K, (int64_t)kpad + HK, ep, va, 0);
-  else
-    hipLaunchKernelGGL((gemm_bf16_kernel<0, false>), grid, dim3(256), 0, ctx->stream, a, lda, (const float*)nullptr,
-                       (int64_t)0, hi, lo, kpad, c, ldc, m, ncol, (int64_t)K, (int64_t)kpad + HK, ep, va, 0);
+#define GCNX_NN_K(X3)                                                                                                \
+  hipLaunchKernelGGL((gemm_bf16_kernel<0, X3>), grid, dim3(256), 0, ctx->stream, a, lda, (const float*)nullptr, (int64_t)0, \
+                     hi, lo, kpad, c, ldc, m, ncol, (int64_t)K, (int64_t)kpad + HK, ep, va, 0)
+  GCNX_BF16_PAIR(prec, GCNX_NN_K, false, true);
+#undef GCNX_NN_K
   GCNX_LAUNCH_OK(ctx);
   return GCNX_OK;
 }
@@ -992,6 +1026,100 @@ static int launch_rowtile(gcnx_ctx* ctx, const float* a, int64_t lda, const floa
 // 64 of 10: step 0.1496 -> 0.143 ms); long inputs still get ~4 workgroups per CU.
 constexpr int64_t kMinSliceSteps = 10;
 
+// ---- host side of the dW products: one split-K plan, one job, one launcher per kernel ----
+
+// The split-K plan of an f32 X^T dH over n > 0 rows: `want` slices, capped by the minimum slice depth.  Every caller
+// passes the slice count that fills ITS workgroup slots: gcnx_gemm_dw and gcnx_gemm_dw_sgd splitk_fill(tiles) (the same
+// call, so the same slices and the same dW bits), gcnx_gemm_dw2 splitk_fill(tiles of both products), dense_bwd_split
+// the spare slots next to its dX tiles.
+static GcnxSplit splitk_plan_f32(int64_t want, int64_t n) { return gcnx_split_rows(want, n, BK, kMinSliceSteps); }
+// ~4 workgroups per CU over `tiles` output tiles per slice
+static int64_t splitk_fill(const gcnx_ctx* ctx, int tiles) { return (4LL * ctx->num_cus + tiles - 1) / tiles; }
+static int dw_tiles(int32_t fi, int32_t fo) { return gcnx_cdiv(fi, BM) * gcnx_cdiv(fo, BN); }
+
+// dW[i, o] = sum_n X[n, i] * dH[n, o] as a job of the 64 x 64 tile kernels: A[i][k=n] = X[n*ldx + i], B[k=n][o] =
+// dH[n*lddh + o], over plan.nsplit slices of plan.kchunk rows.  target: dw, or (nsplit > 1) [nsplit][fi * fo] slabs.
+// vec_c: float4 stores of the target (the callers' conditions differ: they pass theirs).
+static GemmJob dw_job(const float* x, int64_t ldx, const float* dh, int64_t lddh, float* target, int32_t fi, int32_t fo, int64_t n,
+                      const GcnxSplit& plan, int vec_c) {
+  return GemmJob{x, ldx, dh, lddh, target, (int64_t)fo, (int64_t)fi, fo, n, plan.kchunk, epi_plain(vec_c),
+                 gcnx_aligned16(x) && ldx % 4 == 0, gcnx_aligned16(dh) && lddh % 4 == 0, gcnx_cdiv(fo, BN), gcnx_cdiv(fi, BM), plan.nsplit};
+}
+
+static int launch_dw_job(gcnx_ctx* ctx, const GemmJob& j) {
+  hipLaunchKernelGGL((gemm_f32_kernel<false, false>), dim3(j.gx, j.gy, j.gz), dim3(256), 0, ctx->stream, j.a, j.lda, j.b, j.ldb, j.c,
+                     j.ldc, j.M, j.Nc, j.K, j.kchunk, j.ep, j.vec_a, j.vec_b);
+  GCNX_LAUNCH_OK(ctx);
+  return GCNX_OK;
+}
+
+// out[total] = the nsplit slabs [nsplit][total] summed in the documented order.  wide: the float4 kernel for many slabs
+// (total % 4 == 0, 16-byte aligned out) -- only the tall streamed route asks for it.
+static int launch_splitk_reduce(gcnx_ctx* ctx, const float* slabs, int64_t total, int nsplit, float* out, bool wide) {
+  if (wide)
+    hipLaunchKernelGGL(splitk_reduce_wide_kernel, dim3(gcnx_cdiv(total, 256)), dim3(256), 0, ctx->stream, slabs, total, nsplit, out, total);
+  else
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(gcnx_cdiv(total, 64)), dim3(256), 0, ctx->stream, slabs, total, nsplit, out, total);
+  GCNX_LAUNCH_OK(ctx);
+  return GCNX_OK;
+}
+
+// The tall streamed dW (fi = fo = 256, n >= 32 768, bf16 precisions): one slice per CU with the whole product in
+// registers -> num_cus slabs of 65 536 floats in the workspace -> one reduction (the wide kernel when dw takes float4
+// stores).  x / dh are fp32 rows at `prec`, or rows stored as bf16 (stored_bf16).  GCNX_OK, GCNX_ERR_UNSUPPORTED when the
+// streaming launcher does not take the shape (nothing launched), or a launch error under the entry point's name.
+static int dw_streamed_tall(gcnx_ctx* ctx, const char* who, const void* x, int64_t ldx, const void* dh, int64_t lddh, bool stored_bf16,
+                            int prec, float* dw, int64_t n, int32_t fi, int32_t fo) {
+  const int max_slices = ctx->num_cus;
+  int rc = gcnx_ws_reserve(ctx, (size_t)max_slices * 65536 * sizeof(float));
+  if (rc) return rc;
+  float* slabs = (float*)ctx->ws;
+  const int ns = stored_bf16 ? gcnx_gemm_dw_stream16(ctx, x, ldx, dh, lddh, slabs, n, fi, fo, max_slices)
+                             : gcnx_gemm_dw_stream(ctx, (const float*)x, ldx, (const float*)dh, lddh, slabs, n, fi, fo, prec, max_slices);
+  if (ns < 0) return gcnx_fail(ctx, GCNX_ERR_HIP, "%s: streaming kernel launch failed", who);
+  if (ns == 0) return GCNX_ERR_UNSUPPORTED;
+  return launch_splitk_reduce(ctx, slabs, 65536, ns, dw, gcnx_aligned16(dw));
+}
+
+// ---- pending reductions (gcnx_dense_bwd_deferred / gcnx_gcn_conv_bwd_pool -> gcnx_gemm_dw_sgd / gcnx_gemm_dw2) ----
+
+// The pending column sums must land inside [grads, grads + n_params); `who` is the entry point.  (The matching check of
+// pending split-K slabs is gcnx_gemm_dw_sgd's alone: gcnx_gemm_dw2 hands such a record to flush_pending unchecked.)
+static int pending_colsums_land(gcnx_ctx* ctx, const char* who, const gcnx_pending_reduce* pd, const float* grads, int64_t n_params) {
+  GCNX_REQUIRE(ctx, !pd || !pd->colpart || (pd->cout >= grads && pd->cout + pd->cf <= grads + n_params && pd->cf % 4 == 0 &&
+                                            gcnx_aligned16(pd->cout)),
+               "%s: the pending column sums must land (16-byte aligned) inside the flat gradient buffer", who);
+  return GCNX_OK;
+}
+
+// A pending reduction as reduce_sgd_kernel takes it: targets as offsets from `base` (NULL or all-empty: nothing pending).
+static SgdPending sgd_pending(const gcnx_pending_reduce* p, const float* base) {
+  SgdPending pd{nullptr, 0, 0, 0, nullptr, 0, 0, 0, 0, 0};
+  if (p && p->colpart) { pd.cpart = p->colpart; pd.crows = p->crows; pd.cf = p->cf; pd.coff = p->cout - base; pd.n_pc = gcnx_cdiv(p->cf, 8); }
+  if (p && p->slabs) { pd.slabs = p->slabs; pd.total = p->total; pd.nsplit = p->nsplit; pd.soff = p->out - base; pd.n_ps = gcnx_cdiv(p->total, 64); }
+  return pd;
+}
+
+// Runs a pending reduction on its own: gcnx_dense_bwd's second launch, and the fallback paths of gcnx_gemm_dw_sgd /
+// gcnx_gemm_dw2.  Workgroups [0, n_c) fold the column partials, the rest the split-K slabs.
+static int flush_pending(gcnx_ctx* ctx, const gcnx_pending_reduce* pd) {
+  if (!pd || (!pd->colpart && !pd->slabs)) return GCNX_OK;
+  const int n_c = pd->colpart ? gcnx_cdiv(pd->cf, 8) : 0;
+  const int n_s = pd->slabs ? gcnx_cdiv(pd->total, 64) : 0;
+  hipLaunchKernelGGL(reduce_duo_kernel, dim3(n_c + n_s), dim3(256), 0, ctx->stream, pd->colpart, pd->crows, pd->cf, pd->cout,
+                     n_c, pd->slabs, pd->total, pd->nsplit, pd->out, pd->total);
+  GCNX_LAUNCH_OK(ctx);
+  return GCNX_OK;
+}
+
+// A streaming-kernel call with the operands every product has; the caller adds its epilogue pieces by name.
+static GemmStreamCall stream_call(gcnx_ctx* ctx, const void* a, int64_t lda, const float* w, int32_t fi, int32_t fo, int transpose, void* c,
+                                  int64_t ldc, int64_t m) {
+  GemmStreamCall sc;
+  sc.ctx = ctx; sc.a = a; sc.lda = lda; sc.w = w; sc.fi = fi; sc.fo = fo; sc.transpose = transpose; sc.c = c; sc.ldc = ldc; sc.m = m;
+  return sc;
+}
+
 extern "C" {
 
 int gcnx_gemm(gcnx_ctx* ctx, const float* x, int64_t ldx, const float* w, const float* bias, float* out,
@@ -1005,8 +1133,8 @@ int gcnx_gemm(gcnx_ctx* ctx, const float* x, int64_t ldx, const float* w, const 
   if (n == 0 || fo == 0) return GCNX_OK;
   GCNX_REQUIRE(ctx, x && w && out, "gcnx_gemm: NULL pointer");
   GCNX_REQUIRE(ctx, ldx >= fi && ldo >= fo, "gcnx_gemm: leading dimension too small");
-  Epilogue ep{bias, act == GCNX_ACT_PRELU ? alpha : nullptr, nullptr, 0, act, 0, gcnx_aligned16(out) && ldo % 4 == 0};
-  if (prec != GCNX_PREC_F32) return launch_bf16_nn(ctx, x, ldx, w, fi, fo, 1, out, ldo, n, prec, ep);
+  const Epilogue ep = epi_act(bias, alpha, act, gcnx_aligned16(out) && ldo % 4 == 0);
+  if (prec != GCNX_PREC_F32) return launch_bf16_nn(ctx, x, ldx, w, fi, fo, 1, out, ldo, n, prec, ep, nullptr, nullptr);
   if (rowtile_ok(ctx, n, fi, fo, x, ldx))
     return launch_rowtile(ctx, x, ldx, w, (int64_t)fo, out, ldo, n, fi, fo, ep, std::min(gcnx_cdiv(n, kRtRows), ctx->num_cus));
   dim3 grid(gcnx_cdiv(fo, BN), gcnx_cdiv(n, BM), 1);
@@ -1029,12 +1157,12 @@ int gcnx_gemm_relu_bits(gcnx_ctx* ctx, const float* x, int64_t ldx, const float*
   GCNX_REQUIRE(ctx, n >= 0 && fi >= 0 && fo >= 0, "gcnx_gemm_relu_bits: negative size");
   GCNX_REQUIRE(ctx, x && w && out && bits, "gcnx_gemm_relu_bits: NULL pointer");
   GCNX_REQUIRE(ctx, ldx >= fi && ldo >= fo, "gcnx_gemm_relu_bits: leading dimension too small");
-  int rc = GCNX_ERR_UNSUPPORTED;
-  if (prec != GCNX_PREC_F32 && fo == 256 && gcnx_aligned16(out) && ldo % 4 == 0)
-    rc = gcnx_gemm_stream_nn(ctx, x, ldx, w, fi, fo, 1, out, ldo, n, prec, bias, nullptr, GCNX_ACT_RELU, nullptr, 0, 0, nullptr, nullptr, bits);
   // (UNSUPPORTED is an answer, not a failure: returned without a message, ctx's last error stays what it was -- a caller
   // that probes every step must not pay for formatting one, nor find a stale "unsupported" text after its fallback worked)
-  return rc;
+  if (prec == GCNX_PREC_F32 || fo != 256 || !gcnx_aligned16(out) || ldo % 4 != 0) return GCNX_ERR_UNSUPPORTED;
+  GemmStreamCall sc = stream_call(ctx, x, ldx, w, fi, fo, 1, out, ldo, n);
+  sc.prec = prec; sc.bias = bias; sc.act = GCNX_ACT_RELU; sc.bits_out = bits;
+  return gcnx_gemm_stream_nn(sc);
 }
 
 int gcnx_gemm_dx_bits(gcnx_ctx* ctx, const float* dh, int64_t lddh, const float* w, float* dx, int64_t lddx, int64_t n,
@@ -1044,11 +1172,11 @@ int gcnx_gemm_dx_bits(gcnx_ctx* ctx, const float* dh, int64_t lddh, const float*
   GCNX_REQUIRE(ctx, n >= 0 && fi >= 0 && fo >= 0, "gcnx_gemm_dx_bits: negative size");
   GCNX_REQUIRE(ctx, dh && w && dx && mask_bits, "gcnx_gemm_dx_bits: NULL pointer");
   GCNX_REQUIRE(ctx, lddh >= fo && lddx >= fi, "gcnx_gemm_dx_bits: leading dimension too small");
-  int rc = GCNX_ERR_UNSUPPORTED;
-  if (prec != GCNX_PREC_F32 && fi == 256 && gcnx_aligned16(dx) && lddx % 4 == 0 && (!db || gcnx_aligned16(db)))
-    rc = gcnx_gemm_stream_nn(ctx, dh, lddh, w, fi, fo, 0, dx, lddx, n, prec, nullptr, nullptr, GCNX_ACT_NONE, nullptr, 0, 0, db, mask_bits,
-                             nullptr);
-  return rc;                                   // (UNSUPPORTED without a message, as above)
+  if (prec == GCNX_PREC_F32 || fi != 256 || !gcnx_aligned16(dx) || lddx % 4 != 0 || (db && !gcnx_aligned16(db)))
+    return GCNX_ERR_UNSUPPORTED;               // (without a message, as above)
+  GemmStreamCall sc = stream_call(ctx, dh, lddh, w, fi, fo, 0, dx, lddx, n);
+  sc.prec = prec; sc.colsum_out = db; sc.mask_bits = mask_bits;
+  return gcnx_gemm_stream_nn(sc);
 }
 
 // bf16 STORAGE between bf16-operand weight GEMMs (r3).  GCNX_PREC_BF16 rounds both operands of every product to bf16 when
@@ -1082,7 +1210,9 @@ int gcnx_gemm_fwd_bf16(gcnx_ctx* ctx, const void* x16, int64_t ldx, const float*
   GCNX_REQUIRE(ctx, act == GCNX_ACT_NONE || act == GCNX_ACT_RELU, "gcnx_gemm_fwd_bf16: activation %d not supported here", act);
   GCNX_REQUIRE(ctx, !relu_bits || act == GCNX_ACT_RELU, "gcnx_gemm_fwd_bf16: the bit image is that of a ReLU output");
   if (fi != 256 || fo != 256 || (bias && !gcnx_aligned16(bias))) return GCNX_ERR_UNSUPPORTED;
-  return gcnx_gemm_stream_bf16(ctx, x16, ldx, w, fi, fo, 1, out, ldo, out_bf16, n, bias, act, nullptr, nullptr, relu_bits, wimg);
+  GemmStreamCall sc = stream_call(ctx, x16, ldx, w, fi, fo, 1, out, ldo, n);
+  sc.c_bf16 = out_bf16; sc.bias = bias; sc.act = act; sc.bits_out = relu_bits; sc.wimg = wimg;
+  return gcnx_gemm_stream_bf16(sc);
 }
 
 int gcnx_gemm_dx_bf16(gcnx_ctx* ctx, const void* dh16, int64_t lddh, const float* w, void* dx, int64_t lddx, int dx_bf16, int64_t n,
@@ -1093,7 +1223,9 @@ int gcnx_gemm_dx_bf16(gcnx_ctx* ctx, const void* dh16, int64_t lddh, const float
   GCNX_REQUIRE(ctx, dh16 && w && dx, "gcnx_gemm_dx_bf16: NULL pointer");
   GCNX_REQUIRE(ctx, lddh >= fo && lddx >= fi, "gcnx_gemm_dx_bf16: leading dimension too small");
   if (fi != 256 || fo != 256) return GCNX_ERR_UNSUPPORTED;
-  return gcnx_gemm_stream_bf16(ctx, dh16, lddh, w, fi, fo, 0, dx, lddx, dx_bf16, n, nullptr, GCNX_ACT_NONE, db, mask_bits, nullptr, wimg);
+  GemmStreamCall sc = stream_call(ctx, dh16, lddh, w, fi, fo, 0, dx, lddx, n);
+  sc.c_bf16 = dx_bf16; sc.colsum_out = db; sc.mask_bits = mask_bits; sc.wimg = wimg;
+  return gcnx_gemm_stream_bf16(sc);
 }
 
 int gcnx_gemm_dw_bf16(gcnx_ctx* ctx, const void* x16, int64_t ldx, const void* dh16, int64_t lddh, float* dw, int64_t n,
@@ -1104,16 +1236,7 @@ int gcnx_gemm_dw_bf16(gcnx_ctx* ctx, const void* x16, int64_t ldx, const void* d
   GCNX_REQUIRE(ctx, x16 && dh16 && dw, "gcnx_gemm_dw_bf16: NULL pointer");
   GCNX_REQUIRE(ctx, ldx >= fi && lddh >= fo, "gcnx_gemm_dw_bf16: leading dimension too small");
   if (fi != 256 || fo != 256 || n < 32 * 1024 || !ctx->knob_gemm_stream || !gcnx_aligned16(dw)) return GCNX_ERR_UNSUPPORTED;
-  const int max_slices = ctx->num_cus;
-  int rc = gcnx_ws_reserve(ctx, (size_t)max_slices * 65536 * sizeof(float));
-  if (rc) return rc;
-  const int ns = gcnx_gemm_dw_stream16(ctx, x16, ldx, dh16, lddh, (float*)ctx->ws, n, fi, fo, max_slices);
-  if (ns < 0) return gcnx_fail(ctx, GCNX_ERR_HIP, "gcnx_gemm_dw_bf16: streaming kernel launch failed");
-  if (ns == 0) return GCNX_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(splitk_reduce_wide_kernel, dim3(gcnx_cdiv(65536, 256)), dim3(256), 0, ctx->stream, (const float*)ctx->ws, (int64_t)65536,
-                     ns, dw, (int64_t)65536);
-  GCNX_LAUNCH_OK(ctx);
-  return GCNX_OK;
+  return dw_streamed_tall(ctx, "gcnx_gemm_dw_bf16", x16, ldx, dh16, lddh, true, GCNX_PREC_BF16, dw, n, fi, fo);
 }
 
 int gcnx_gemm_dx(gcnx_ctx* ctx, const float* dh, int64_t lddh, const float* w, float* dx, int64_t lddx, int64_t n,
@@ -1130,8 +1253,8 @@ int gcnx_gemm_dx(gcnx_ctx* ctx, const float* dh, int64_t lddh, const float* w, f
   GCNX_REQUIRE(ctx, dh && w && dx, "gcnx_gemm_dx: NULL pointer");
   GCNX_REQUIRE(ctx, lddh >= fo && lddx >= fi && (!y_mask || ldy >= fi), "gcnx_gemm_dx: leading dimension too small");
   // dX[n, i] = sum_o dH[n, o] * W[i, o]:  A = dH (k contiguous), B[k=o][j=i] = W[i*fo + o] (k contiguous).
-  Epilogue ep{nullptr, nullptr, y_mask, ldy, GCNX_ACT_NONE, accumulate,
-              gcnx_aligned16(dx) && lddx % 4 == 0 && (!y_mask || (gcnx_aligned16(y_mask) && ldy % 4 == 0))};
+  Epilogue ep = epi_mask(y_mask, ldy, accumulate,
+                         gcnx_aligned16(dx) && lddx % 4 == 0 && (!y_mask || (gcnx_aligned16(y_mask) && ldy % 4 == 0)), nullptr);
   if (prec != GCNX_PREC_F32) {
     int db_done = 0;
     int rc = launch_bf16_nn(ctx, dh, lddh, w, fi, fo, 0, dx, lddx, n, prec, ep, db, &db_done);
@@ -1175,21 +1298,14 @@ int gcnx_gemm_dx(gcnx_ctx* ctx, const float* dh, int64_t lddh, const float* w, f
 
 }  // extern "C"
 
-// nsplit / kchunk of the dW part of the fused dense backward (shared by the sizing helper and the launcher)
-static int dense_bwd_split(const gcnx_ctx* ctx, int64_t n, int32_t fi, int32_t fo, int64_t* kchunk_out) {
-  const int64_t gy = gcnx_cdiv(n, BM);
-  const int n_dx = (int)gy * (fi / BN);
-  const int tiles = gcnx_cdiv(fi, BM) * gcnx_cdiv(fo, BN);
+// The split-K plan of the dW part of the fused dense backward (shared by the sizing helper and the launcher): as many
+// slices as fit the resident-workgroup slots (4 per CU) that the dX tiles' last round leaves -- a limit, so rounded down.
+static GcnxSplit dense_bwd_split(const gcnx_ctx* ctx, int64_t n, int32_t fi, int32_t fo) {
+  const int n_dx = gcnx_cdiv(n, BM) * (fi / BN);
   const int slots = 4 * ctx->num_cus;
   int spare = slots - n_dx % slots;
   if (spare < slots / 4) spare += slots;
-  int nsplit = spare / tiles;
-  const int64_t ksteps = (n + BK - 1) / BK;
-  if (nsplit > ksteps / kMinSliceSteps) nsplit = (int)(ksteps / kMinSliceSteps);
-  if (nsplit < 1) nsplit = 1;
-  const int64_t kchunk = ((ksteps + nsplit - 1) / nsplit) * BK;
-  if (kchunk_out) *kchunk_out = kchunk;
-  return (int)((n + kchunk - 1) / kchunk);
+  return splitk_plan_f32(spare / dw_tiles(fi, fo), n);
 }
 
 static int dense_bwd_impl(gcnx_ctx* ctx, const float* x, int64_t ldx, const float* dh, int64_t lddh, const float* w, int64_t n,
@@ -1206,7 +1322,7 @@ int gcnx_dense_bwd(gcnx_ctx* ctx, const float* x, int64_t ldx, const float* dh, 
 
 int64_t gcnx_dense_bwd_scratch_floats(gcnx_ctx* ctx, int64_t n, int32_t fi, int32_t fo) {
   if (!ctx || n <= 0 || fi <= 0 || fo <= 0 || fi % BN != 0) return 0;
-  const int nsplit = dense_bwd_split(ctx, n, fi, fo, nullptr);
+  const int nsplit = dense_bwd_split(ctx, n, fi, fo).nsplit;
   return ((2 * (int64_t)gcnx_cdiv(n, BM) * fi + 63) & ~(int64_t)63) + (int64_t)nsplit * fi * fo;
 }
 
@@ -1243,8 +1359,8 @@ static int dense_bwd_impl(gcnx_ctx* ctx, const float* x, int64_t ldx, const floa
   GCNX_REQUIRE(ctx, ldx >= fi && lddh >= fo && lddx >= fi && (!y_mask || ldy >= fi), "gcnx_dense_bwd: leading dimension too small");
   // dX tiles, then as many dW split-K slices as fill the rest of the resident-workgroup slots (4 per CU)
   const int n_dx = (int)gy * (fi / BN);
-  int64_t kchunk = 0;
-  const int nsplit = dense_bwd_split(ctx, n, fi, fo, &kchunk);
+  const GcnxSplit plan = dense_bwd_split(ctx, n, fi, fo);
+  const int nsplit = plan.nsplit;
   // partial results: [dX column-sum partials (2 per row tile) | dW slabs] -- in the ctx workspace, or (deferred
   // reduction) in the caller's scratch, where they stay until gcnx_gemm_dw_sgd folds them
   const int64_t prow = db_prev ? 2 * gy : 0;
@@ -1262,28 +1378,20 @@ static int dense_bwd_impl(gcnx_ctx* ctx, const float* x, int64_t ldx, const floa
   }
   float* colpart = db_prev ? base : nullptr;
   float* slabs = base + part_floats;
-  GemmJob jx{dh, lddh, w, (int64_t)fo, dx, lddx, n, fi, (int64_t)fo, (int64_t)fo + BK,
-             Epilogue{nullptr, nullptr, y_mask, ldy, GCNX_ACT_NONE, 0, 1, colpart},
+  GemmJob jx{dh, lddh, w, (int64_t)fo, dx, lddx, n, fi, (int64_t)fo, (int64_t)fo + BK, epi_mask(y_mask, ldy, 0, 1, colpart),
              gcnx_aligned16(dh) && lddh % 4 == 0, gcnx_aligned16(w) && fo % 4 == 0, fi / BN, (int)gy, 1};
-  GemmJob jw{x, ldx, dh, lddh, nsplit > 1 ? slabs : dw, (int64_t)fo, (int64_t)fi, fo, n, kchunk,
-             Epilogue{nullptr, nullptr, nullptr, 0, GCNX_ACT_NONE, 0, nsplit > 1 || gcnx_aligned16(dw), nullptr},
-             gcnx_aligned16(x) && ldx % 4 == 0, gcnx_aligned16(dh) && lddh % 4 == 0, gcnx_cdiv(fo, BN), gcnx_cdiv(fi, BM), nsplit};
+  const GemmJob jw = dw_job(x, ldx, dh, lddh, nsplit > 1 ? slabs : dw, fi, fo, n, plan, nsplit > 1 || gcnx_aligned16(dw));
   hipLaunchKernelGGL(gemm_f32_duo_kernel, dim3(n_dx + jw.gx * jw.gy * jw.gz), dim3(256), 0, ctx->stream, jx, jw, n_dx);
   GCNX_LAUNCH_OK(ctx);
-  const int n_c = db_prev ? gcnx_cdiv(fi, 8) : 0;
+  // what is left to reduce: run now, or handed to the caller
   const int64_t total = (int64_t)fi * fo;
-  const int n_s = nsplit > 1 ? gcnx_cdiv(total, 64) : 0;
+  const gcnx_pending_reduce rest{colpart, prow, db_prev ? fi : 0, db_prev, nsplit > 1 ? slabs : nullptr,
+                                 nsplit > 1 ? total : 0, nsplit > 1 ? nsplit : 0, nsplit > 1 ? dw : nullptr};
   if (defer) {
-    *pending = gcnx_pending_reduce{colpart, prow, db_prev ? fi : 0, db_prev, nsplit > 1 ? slabs : nullptr,
-                                   nsplit > 1 ? total : 0, nsplit > 1 ? nsplit : 0, nsplit > 1 ? dw : nullptr};
+    *pending = rest;
     return GCNX_OK;
   }
-  if (n_c + n_s > 0) {
-    hipLaunchKernelGGL(reduce_duo_kernel, dim3(n_c + n_s), dim3(256), 0, ctx->stream, (const float*)colpart, prow, fi,
-                       db_prev, n_c, (const float*)slabs, total, nsplit, dw, total);
-    GCNX_LAUNCH_OK(ctx);
-  }
-  return GCNX_OK;
+  return flush_pending(ctx, &rest);
 }
 
 extern "C" {
@@ -1302,38 +1410,21 @@ int gcnx_gemm_dw(gcnx_ctx* ctx, const float* x, int64_t ldx, const float* dh, in
   }
   GCNX_REQUIRE(ctx, x && dh, "gcnx_gemm_dw: NULL pointer");
   GCNX_REQUIRE(ctx, ldx >= fi && lddh >= fo, "gcnx_gemm_dw: leading dimension too small");
-  // dW[i, o] = sum_n X[n, i] * dH[n, o]: A[i][k=n] = X[n*ldx + i], B[k=n][o] = dH[n*lddh + o].
+  const int64_t total = (int64_t)fi * fo;
   if (prec != GCNX_PREC_F32) {
     if (fi == 256 && fo == 256 && n >= 32 * 1024 && ctx->knob_gemm_stream) {   // tall: one slice per CU, whole product in registers
-      const int max_slices = ctx->num_cus;
-      int rc = gcnx_ws_reserve(ctx, (size_t)max_slices * 65536 * sizeof(float));
-      if (rc) return rc;
-      const int ns = gcnx_gemm_dw_stream(ctx, x, ldx, dh, lddh, (float*)ctx->ws, n, fi, fo, prec, max_slices);
-      if (ns < 0) return gcnx_fail(ctx, GCNX_ERR_HIP, "gcnx_gemm_dw: streaming kernel launch failed");
-      if (ns > 0) {
-        if (gcnx_aligned16(dw))
-          hipLaunchKernelGGL(splitk_reduce_wide_kernel, dim3(gcnx_cdiv(65536, 256)), dim3(256), 0, ctx->stream, (const float*)ctx->ws,
-                             (int64_t)65536, ns, dw, (int64_t)65536);
-        else
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(gcnx_cdiv(65536, 64)), dim3(256), 0, ctx->stream, (const float*)ctx->ws,
-                           (int64_t)65536, ns, dw, (int64_t)65536);
-        GCNX_LAUNCH_OK(ctx);
-        return GCNX_OK;
-      }
+      const int rc = dw_streamed_tall(ctx, "gcnx_gemm_dw", x, ldx, dh, lddh, false, prec, dw, n, fi, fo);
+      if (rc != GCNX_ERR_UNSUPPORTED) return rc;
     }
     if (n < 32 * 1024 || fi != 256) {      // mid-size batches / wide inputs (GeneralGNN): panels of the streaming kernel
       const int pr = gcnx_gemm_dw_panels(ctx, x, ldx, dh, lddh, dw, n, fi, fo, prec);
       if (pr < 0) return gcnx_fail(ctx, GCNX_ERR_HIP, "gcnx_gemm_dw: streaming kernel (panels) launch failed");
       if (pr > 0) return GCNX_OK;
     }
-    const int tiles_h = gcnx_cdiv(fi, HM) * gcnx_cdiv(fo, HN);
-    int ns = (int)((4LL * ctx->num_cus + tiles_h - 1) / tiles_h);
-    const int64_t ksteps_h = (n + HK - 1) / HK;
-    if (ns > ksteps_h) ns = (int)ksteps_h;
-    if (ns < 1) ns = 1;
-    const int64_t kchunk_h = ((ksteps_h + ns - 1) / ns) * HK;
-    ns = (int)((n + kchunk_h - 1) / kchunk_h);
-    Epilogue eph{nullptr, nullptr, nullptr, 0, GCNX_ACT_NONE, 0, fo % 4 == 0 && (ns > 1 || gcnx_aligned16(dw))};
+    // the 128 x 128 tile kernel: ~4 workgroups per CU, slices of whole 32-row steps with no minimum depth
+    const GcnxSplit ph = gcnx_split_rows(splitk_fill(ctx, gcnx_cdiv(fi, HM) * gcnx_cdiv(fo, HN)), n, HK, 1);
+    const int ns = ph.nsplit;
+    const Epilogue eph = epi_plain(fo % 4 == 0 && (ns > 1 || gcnx_aligned16(dw)));
     float* tgt = dw;
     if (ns > 1) {
       int rc = gcnx_ws_reserve(ctx, (size_t)ns * fi * fo * sizeof(float));
@@ -1342,61 +1433,24 @@ int gcnx_gemm_dw(gcnx_ctx* ctx, const float* x, int64_t ldx, const float* dh, in
     }
     dim3 gridh(gcnx_cdiv(fo, HN), gcnx_cdiv(fi, HM), ns);
     const int vah = gcnx_aligned16(x) && ldx % 4 == 0, vbh = gcnx_aligned16(dh) && lddh % 4 == 0;
-    if (prec == GCNX_PREC_BF16X3)
-      hipLaunchKernelGGL((gemm_bf16_kernel<1, true>), gridh, dim3(256), 0, ctx->stream, x, ldx, dh, lddh,
-                         (const __bf16*)nullptr, (const __bf16*)nullptr, 0, tgt, (int64_t)fo, (int64_t)fi, fo, n, kchunk_h,
-                         eph, vah, vbh);
-    else
-      hipLaunchKernelGGL((gemm_bf16_kernel<1, false>), gridh, dim3(256), 0, ctx->stream, x, ldx, dh, lddh,
-                         (const __bf16*)nullptr, (const __bf16*)nullptr, 0, tgt, (int64_t)fo, (int64_t)fi, fo, n, kchunk_h,
-                         eph, vah, vbh);
+#define GCNX_DW_K(X3)                                                                                              \
+  hipLaunchKernelGGL((gemm_bf16_kernel<1, X3>), gridh, dim3(256), 0, ctx->stream, x, ldx, dh, lddh, (const __bf16*)nullptr, \
+                     (const __bf16*)nullptr, 0, tgt, (int64_t)fo, (int64_t)fi, fo, n, ph.kchunk, eph, vah, vbh)
+    GCNX_BF16_PAIR(prec, GCNX_DW_K, false, true);
+#undef GCNX_DW_K
     GCNX_LAUNCH_OK(ctx);
-    if (ns > 1) {
-      const int64_t total = (int64_t)fi * fo;
-      hipLaunchKernelGGL(splitk_reduce_kernel, dim3(gcnx_cdiv(total, 64)), dim3(256), 0, ctx->stream, (const float*)ctx->ws,
-                         total, ns, dw, total);
-      GCNX_LAUNCH_OK(ctx);
-    }
-    return GCNX_OK;
+    return ns > 1 ? launch_splitk_reduce(ctx, (const float*)ctx->ws, total, ns, dw, false) : GCNX_OK;
   }
-  const int tiles = gcnx_cdiv(fi, BM) * gcnx_cdiv(fo, BN);
-  int nsplit = (int)((4LL * ctx->num_cus + tiles - 1) / tiles);   // ~4 workgroups per CU
-  const int64_t ksteps = (n + BK - 1) / BK;
-  if (nsplit > ksteps / kMinSliceSteps) nsplit = (int)(ksteps / kMinSliceSteps);
-  if (nsplit < 1) nsplit = 1;
-  const int64_t kchunk = ((ksteps + nsplit - 1) / nsplit) * BK;
-  nsplit = (int)((n + kchunk - 1) / kchunk);
-  Epilogue ep{nullptr, nullptr, nullptr, 0, GCNX_ACT_NONE, 0, 0};
-  const int va = gcnx_aligned16(x) && ldx % 4 == 0, vb = gcnx_aligned16(dh) && lddh % 4 == 0;
+  const GcnxSplit plan = splitk_plan_f32(splitk_fill(ctx, dw_tiles(fi, fo)), n);
   float* target = dw;
-  ep.vec_c = fo % 4 == 0 && (nsplit > 1 || gcnx_aligned16(dw));   // partial slabs live in the 256-byte aligned workspace
-  if (nsplit > 1) {
-    int rc = gcnx_ws_reserve(ctx, (size_t)nsplit * fi * fo * sizeof(float));
+  if (plan.nsplit > 1) {   // partial slabs live in the 256-byte aligned workspace
+    int rc = gcnx_ws_reserve(ctx, (size_t)plan.nsplit * fi * fo * sizeof(float));
     if (rc) return rc;
     target = (float*)ctx->ws;
   }
-  dim3 grid(gcnx_cdiv(fo, BN), gcnx_cdiv(fi, BM), nsplit);
-  hipLaunchKernelGGL((gemm_f32_kernel<false, false>), grid, dim3(256), 0, ctx->stream, x, ldx, dh, lddh, target,
-                     (int64_t)fo, (int64_t)fi, fo, n, kchunk, ep, va, vb);
-  GCNX_LAUNCH_OK(ctx);
-  if (nsplit > 1) {
-    const int64_t total = (int64_t)fi * fo;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(gcnx_cdiv(total, 64)), dim3(256), 0, ctx->stream,
-                       (const float*)ctx->ws, total, nsplit, dw, total);
-    GCNX_LAUNCH_OK(ctx);
-  }
-  return GCNX_OK;
-}
-
-// Runs a pending reduction on its own (the fallback paths of gcnx_gemm_dw_sgd).
-static int flush_pending(gcnx_ctx* ctx, const gcnx_pending_reduce* pd) {
-  if (!pd || (!pd->colpart && !pd->slabs)) return GCNX_OK;
-  const int n_c = pd->colpart ? gcnx_cdiv(pd->cf, 8) : 0;
-  const int n_s = pd->slabs ? gcnx_cdiv(pd->total, 64) : 0;
-  hipLaunchKernelGGL(reduce_duo_kernel, dim3(n_c + n_s), dim3(256), 0, ctx->stream, pd->colpart, pd->crows, pd->cf, pd->cout,
-                     n_c, pd->slabs, pd->total, pd->nsplit, pd->out, pd->total);
-  GCNX_LAUNCH_OK(ctx);
-  return GCNX_OK;
+  int rc = launch_dw_job(ctx, dw_job(x, ldx, dh, lddh, target, fi, fo, n, plan, fo % 4 == 0 && (plan.nsplit > 1 || gcnx_aligned16(dw))));
+  if (rc || plan.nsplit <= 1) return rc;
+  return launch_splitk_reduce(ctx, (const float*)ctx->ws, total, plan.nsplit, dw, false);
 }
 
 int gcnx_gemm_dw_sgd(gcnx_ctx* ctx, const float* x, int64_t ldx, const float* dh, int64_t lddh, float* dw, int64_t n,
@@ -1405,31 +1459,19 @@ int gcnx_gemm_dw_sgd(gcnx_ctx* ctx, const float* x, int64_t ldx, const float* dh
   GCNX_CHECK_CTX(ctx);
   GCNX_RANGE(ctx, "weight GEMM (dW) + update");
   if (pending && !pending->colpart && !pending->slabs) pending = nullptr;
-  if (pending) {
-    GCNX_REQUIRE(ctx, !pending->colpart || (pending->cout >= grads && pending->cout + pending->cf <= grads + n_params &&
-                                            pending->cf % 4 == 0 && gcnx_aligned16(pending->cout)),
-                 "gcnx_gemm_dw_sgd: the pending column sums must land (16-byte aligned) inside the flat gradient buffer");
-    GCNX_REQUIRE(ctx, !pending->slabs || (pending->out >= grads && pending->out + pending->total <= grads + n_params),
-                 "gcnx_gemm_dw_sgd: the pending split-K result must land inside the flat gradient buffer");
-  }
+  if (int rc = pending_colsums_land(ctx, "gcnx_gemm_dw_sgd", pending, grads, n_params)) return rc;
+  GCNX_REQUIRE(ctx, !pending || !pending->slabs || (pending->out >= grads && pending->out + pending->total <= grads + n_params),
+               "gcnx_gemm_dw_sgd: the pending split-K result must land inside the flat gradient buffer");
   GCNX_REQUIRE(ctx, n >= 0 && fi >= 0 && fo >= 0 && n_params >= 0, "gcnx_gemm_dw_sgd: negative size");
   GCNX_REQUIRE(ctx, prec >= GCNX_PREC_F32 && prec <= GCNX_PREC_BF16X3, "gcnx_gemm_dw_sgd: unknown precision %d", prec);
   GCNX_REQUIRE(ctx, n_params == 0 || (params && grads), "gcnx_gemm_dw_sgd: NULL pointer");
   const int64_t total = (int64_t)fi * fo;
   GCNX_REQUIRE(ctx, total == 0 || (dw >= grads && dw + total <= grads + n_params),
                "gcnx_gemm_dw_sgd: dw must lie inside the flat gradient buffer");
-  // split-K as gcnx_gemm_dw (the same slices, so the same dW bits)
-  int nsplit = 1;
-  int64_t kchunk = 0;
-  if (prec == GCNX_PREC_F32 && n > 0 && total > 0) {
-    const int tiles = gcnx_cdiv(fi, BM) * gcnx_cdiv(fo, BN);
-    nsplit = (int)((4LL * ctx->num_cus + tiles - 1) / tiles);
-    const int64_t ksteps = (n + BK - 1) / BK;
-    if (nsplit > ksteps / kMinSliceSteps) nsplit = (int)(ksteps / kMinSliceSteps);
-    if (nsplit < 1) nsplit = 1;
-    kchunk = ((ksteps + nsplit - 1) / nsplit) * BK;
-    nsplit = (int)((n + kchunk - 1) / kchunk);
-  }
+  // split-K as gcnx_gemm_dw: the same plan call, so the same slices and the same dW bits
+  GcnxSplit plan{1, 0};
+  if (prec == GCNX_PREC_F32 && n > 0 && total > 0) plan = splitk_plan_f32(splitk_fill(ctx, dw_tiles(fi, fo)), n);
+  const int nsplit = plan.nsplit;
   if (nsplit <= 1 || fo % 4 != 0) {   // nothing to reduce (or bf16 / ragged): the separate calls
     int rc = flush_pending(ctx, pending);
     if (rc) return rc;
@@ -1441,19 +1483,9 @@ int gcnx_gemm_dw_sgd(gcnx_ctx* ctx, const float* x, int64_t ldx, const float* dh
   GCNX_REQUIRE(ctx, ldx >= fi && lddh >= fo, "gcnx_gemm_dw_sgd: leading dimension too small");
   int rc = gcnx_ws_reserve(ctx, (size_t)nsplit * total * sizeof(float));
   if (rc) return rc;
-  Epilogue ep{nullptr, nullptr, nullptr, 0, GCNX_ACT_NONE, 0, 1};
-  const int va = gcnx_aligned16(x) && ldx % 4 == 0, vb = gcnx_aligned16(dh) && lddh % 4 == 0;
-  dim3 grid(gcnx_cdiv(fo, BN), gcnx_cdiv(fi, BM), nsplit);
-  hipLaunchKernelGGL((gemm_f32_kernel<false, false>), grid, dim3(256), 0, ctx->stream, x, ldx, dh, lddh, (float*)ctx->ws,
-                     (int64_t)fo, (int64_t)fi, fo, n, kchunk, ep, va, vb);
-  GCNX_LAUNCH_OK(ctx);
-  SgdPending pd{nullptr, 0, 0, 0, nullptr, 0, 0, 0, 0, 0};
-  if (pending) {
-    if (pending->colpart) { pd.cpart = pending->colpart; pd.crows = pending->crows; pd.cf = pending->cf;
-                            pd.coff = pending->cout - grads; pd.n_pc = gcnx_cdiv(pending->cf, 8); }
-    if (pending->slabs) { pd.slabs = pending->slabs; pd.total = pending->total; pd.nsplit = pending->nsplit;
-                          pd.soff = pending->out - grads; pd.n_ps = gcnx_cdiv(pending->total, 64); }
-  }
+  rc = launch_dw_job(ctx, dw_job(x, ldx, dh, lddh, (float*)ctx->ws, fi, fo, n, plan, 1));   // (fo % 4 == 0, aligned workspace)
+  if (rc) return rc;
+  const SgdPending pd = sgd_pending(pending, grads);
   const int n_s = gcnx_cdiv(total, 64), n_o = gcnx_cdiv(n_params, 256);
   hipLaunchKernelGGL(reduce_sgd_kernel, dim3(n_s + pd.n_pc + pd.n_ps + n_o), dim3(256), 0, ctx->stream, (const float*)ctx->ws,
                      total, nsplit, total, n_s, params, grads, (int64_t)(dw - grads), n_params, lr, pd, ctx->lr_dev);
@@ -1486,23 +1518,13 @@ int gcnx_gemm_dw2(gcnx_ctx* ctx, const float* xa, int64_t ldxa, const float* dha
     GCNX_REQUIRE(ctx, (ta == 0 || (dwa >= grads && dwa + ta <= grads + n_params)) &&
                           (tb == 0 || (dwb >= grads && dwb + tb <= grads + n_params)),
                  "gcnx_gemm_dw2: both gradients must lie inside the flat gradient buffer");
-    GCNX_REQUIRE(ctx, !pending || !pending->colpart || (pending->cout >= grads && pending->cout + pending->cf <= grads + n_params &&
-                                                        pending->cf % 4 == 0 && gcnx_aligned16(pending->cout)),
-                 "gcnx_gemm_dw2: the pending column sums must land (16-byte aligned) inside the flat gradient buffer");
+    if (int rc = pending_colsums_land(ctx, "gcnx_gemm_dw2", pending, grads, n_params)) return rc;
   }
-  int nsplit = 1;
-  int64_t kchunk = 0;
   const bool shapes_ok = prec == GCNX_PREC_F32 && n > 0 && ta > 0 && tb > 0 && foa % 4 == 0 && fob % 4 == 0 &&
                          (!pending || !pending->slabs);
-  if (shapes_ok) {
-    const int tiles = gcnx_cdiv(fia, BM) * gcnx_cdiv(foa, BN) + gcnx_cdiv(fib, BM) * gcnx_cdiv(fob, BN);
-    nsplit = (int)((4LL * ctx->num_cus + tiles - 1) / tiles);   // ~4 workgroups per CU over both products
-    const int64_t ksteps = (n + BK - 1) / BK;
-    if (nsplit > ksteps / kMinSliceSteps) nsplit = (int)(ksteps / kMinSliceSteps);
-    if (nsplit < 1) nsplit = 1;
-    kchunk = ((ksteps + nsplit - 1) / nsplit) * BK;
-    nsplit = (int)((n + kchunk - 1) / kchunk);
-  }
+  GcnxSplit plan{1, 0};
+  if (shapes_ok) plan = splitk_plan_f32(splitk_fill(ctx, dw_tiles(fia, foa) + dw_tiles(fib, fob)), n);   // ~4 workgroups per CU over both products
+  const int nsplit = plan.nsplit;
   if (!shapes_ok || nsplit <= 1) {   // bf16 precisions, empty or short inputs: the separate calls
     int rc = flush_pending(ctx, pending);
     if (rc) return rc;
@@ -1520,11 +1542,8 @@ int gcnx_gemm_dw2(gcnx_ctx* ctx, const float* xa, int64_t ldxa, const float* dha
   if (rc) return rc;
   float* sa = (float*)ctx->ws;
   float* sb = sa + slab_a;
-  const Epilogue ep{nullptr, nullptr, nullptr, 0, GCNX_ACT_NONE, 0, 1, nullptr};
-  GemmJob ja{xa, ldxa, dha, lddha, sa, (int64_t)foa, (int64_t)fia, foa, n, kchunk, ep,
-             gcnx_aligned16(xa) && ldxa % 4 == 0, gcnx_aligned16(dha) && lddha % 4 == 0, gcnx_cdiv(foa, BN), gcnx_cdiv(fia, BM), nsplit};
-  GemmJob jb{xb, ldxb, dhb, lddhb, sb, (int64_t)fob, (int64_t)fib, fob, n, kchunk, ep,
-             gcnx_aligned16(xb) && ldxb % 4 == 0, gcnx_aligned16(dhb) && lddhb % 4 == 0, gcnx_cdiv(fob, BN), gcnx_cdiv(fib, BM), nsplit};
+  const GemmJob ja = dw_job(xa, ldxa, dha, lddha, sa, fia, foa, n, plan, 1);
+  const GemmJob jb = dw_job(xb, ldxb, dhb, lddhb, sb, fib, fob, n, plan, 1);
   const int n_a = ja.gx * ja.gy * ja.gz, n_b = jb.gx * jb.gy * jb.gz;
   const bool want_db = leaf && leaf->db_relu;
   const bool merged = leaf && leaf->c == 2 && gcnx_head::head_lds_floats(leaf->h, leaf->c, want_db) <= (size_t)kDw2HeadLds &&
@@ -1548,12 +1567,11 @@ int gcnx_gemm_dw2(gcnx_ctx* ctx, const float* xa, int64_t ldxa, const float* dha
     hipLaunchKernelGGL(gemm_f32_dw2_kernel, dim3(n_a + n_b), dim3(256), 0, ctx->stream, ja, jb, n_a);
   }
   GCNX_LAUNCH_OK(ctx);
-  // one reduction launch either way: with params == NULL reduce_sgd_kernel only folds (offsets relative to `base`)
+  // one reduction launch either way: with params == NULL reduce_sgd_kernel only folds (offsets relative to `base`).
+  // Product a is the launch's own reduction, product b rides in the pending split-K slot (free: shapes_ok).
   float* base = params ? grads : std::min(dwa, dwb);
   if (!params && pending && pending->colpart) base = std::min(base, pending->cout);
-  SgdPending pd{nullptr, 0, 0, 0, nullptr, 0, 0, 0, 0, 0};
-  if (pending && pending->colpart) { pd.cpart = pending->colpart; pd.crows = pending->crows; pd.cf = pending->cf;
-                                     pd.coff = pending->cout - base; pd.n_pc = gcnx_cdiv(pending->cf, 8); }
+  SgdPending pd = sgd_pending(pending, base);
   pd.slabs = sb; pd.total = tb; pd.nsplit = nsplit; pd.soff = dwb - base; pd.n_ps = gcnx_cdiv(tb, 64);
   const int n_s = gcnx_cdiv(ta, 64), n_o = params ? gcnx_cdiv(n_params, 256) : 0;
   hipLaunchKernelGGL(reduce_sgd_kernel, dim3(n_s + pd.n_pc + pd.n_ps + n_o), dim3(256), 0, ctx->stream, (const float*)sa,

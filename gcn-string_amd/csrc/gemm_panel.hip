@@ -504,7 +504,7 @@ int gcnx_gemm_wimage(gcnx_ctx* ctx, const float* x, int64_t ldx, const void* img
   GCNX_REQUIRE(ctx, x && img && out, "gcnx_gemm_wimage: NULL pointer");
   GCNX_REQUIRE(ctx, ldx >= K && ldo >= nc, "gcnx_gemm_wimage: leading dimension too small");
   // what the kernel is built for (the caller falls back to gcnx_gemm / gcnx_gemm_dx otherwise; no message: an answer)
-  if (nc % 16 != 0 || K % 4 != 0 || ldx % 4 != 0 || !gcnx_aligned16(x) || !gcnx_aligned16(img) || (uint64_t)n * (uint64_t)ldx * 4u >= 0xFFFFFF00ull)
+  if (nc % 16 != 0 || K % 4 != 0 || ldx % 4 != 0 || !gcnx_aligned16(x) || !gcnx_aligned16(img) || !gcnx_fits_buffer(n, ldx, 4))
     return GCNX_ERR_UNSUPPORTED;
   GCNX_REQUIRE(ctx, !bn_parts || n_parts, "gcnx_gemm_wimage: bn_parts needs n_parts");
   const int ntiles = gcnx_cdiv(n, kTileRows);
@@ -513,31 +513,21 @@ int gcnx_gemm_wimage(gcnx_ctx* ctx, const float* x, int64_t ldx, const void* img
   GCNX_REQUIRE(ctx, !bn_parts || nc <= kPanel, "gcnx_gemm_wimage: batch-norm statistics need a single column panel (fo <= 256)");
   if (n_parts) *n_parts = groups * gx;
   const PanelEpi ep{bias, accumulate ? 1 : 0, bn_parts};
+  const int np = prec == GCNX_PREC_BF16X3 ? 2 : 1;         // LDS planes per operand image
+#define GCNX_PANEL_K(KERNEL_NP)                                                                                               \
+  GCNX_HIP(ctx, gcnx_launch_dyn_lds<&KERNEL_NP>(grid, dim3(512), lds, ctx->stream, x, ldx, (const __bf16*)img, out, ldo, n, K, nc, ep, \
+                                                ntiles))
   if (K <= 2 * kKPanel && nc > kPanel && !bn_parts) {      // wide outputs of a short reduction: the A operand resident in LDS
-    const int lds_np = prec == GCNX_PREC_BF16X3 ? 2 : 1;
-    const int lds = kWideTiles * 2 * lds_np * kKS * 2 * 1024;
-    if (prec == GCNX_PREC_BF16X3) {
-      static bool set = false;
-      if (!set) { GCNX_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_panel_wide_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds)); set = true; }
-      hipLaunchKernelGGL((gemm_panel_wide_kernel<2>), dim3(gx), dim3(512), lds, ctx->stream, x, ldx, (const __bf16*)img, out, ldo, n, K, nc, ep, ntiles);
-    } else {
-      static bool set = false;
-      if (!set) { GCNX_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_panel_wide_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds)); set = true; }
-      hipLaunchKernelGGL((gemm_panel_wide_kernel<1>), dim3(gx), dim3(512), lds, ctx->stream, x, ldx, (const __bf16*)img, out, ldo, n, K, nc, ep, ntiles);
-    }
+    const int lds = kWideTiles * 2 * np * kKS * 2 * 1024;
+    const dim3 grid(gx);
+    GCNX_BF16_PAIR(prec, GCNX_PANEL_K, gemm_panel_wide_kernel<1>, gemm_panel_wide_kernel<2>);
     GCNX_LAUNCH_OK(ctx);
     return GCNX_OK;
   }
+  const int lds = 2 * np * kKS * 2 * 1024;
   const dim3 grid(gx, gcnx_cdiv(nc, kPanel));
-  if (prec == GCNX_PREC_BF16X3) {
-    constexpr int lds = 2 * 2 * kKS * 2 * 1024;
-    static bool set = false;
-    if (!set) { GCNX_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_panel_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds)); set = true; }
-    hipLaunchKernelGGL((gemm_panel_kernel<2>), grid, dim3(512), lds, ctx->stream, x, ldx, (const __bf16*)img, out, ldo, n, K, nc, ep, ntiles);
-  } else {
-    constexpr int lds = 2 * 1 * kKS * 2 * 1024;
-    hipLaunchKernelGGL((gemm_panel_kernel<1>), grid, dim3(512), lds, ctx->stream, x, ldx, (const __bf16*)img, out, ldo, n, K, nc, ep, ntiles);
-  }
+  GCNX_BF16_PAIR(prec, GCNX_PANEL_K, gemm_panel_kernel<1>, gemm_panel_kernel<2>);
+#undef GCNX_PANEL_K
   GCNX_LAUNCH_OK(ctx);
   return GCNX_OK;
 }

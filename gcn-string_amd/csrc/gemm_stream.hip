@@ -485,22 +485,24 @@ int launch_stream(gcnx_ctx* ctx, const float* a, int64_t lda, const __bf16* img,
 
 // X W (transpose = 1) / dH W^T (transpose = 0) on the streaming kernel.  Returns GCNX_ERR_UNSUPPORTED (without
 // setting an error message) when the shape is not one it is built for; the caller then takes the tiled kernel.
-int gcnx_gemm_stream_nn(gcnx_ctx* ctx, const float* a, int64_t lda, const float* w, int fi, int fo, int transpose, float* c,
-                        int64_t ldc, int64_t m, int prec, const float* bias, const float* alpha, int act, const float* mask,
-                        int64_t ldmask, int accumulate, float* colsum_out, const void* mask_bits, void* bits_out) {
-  const int ncol = transpose ? fo : fi, K = transpose ? fi : fo;
-  const int np = prec == GCNX_PREC_BF16X3 ? 2 : 1;
+int gcnx_gemm_stream_nn(const GemmStreamCall& sc) {
+  gcnx_ctx* ctx = sc.ctx;
+  const float* a = (const float*)sc.a;
+  float* c = (float*)sc.c;
+  const int64_t lda = sc.lda, ldc = sc.ldc, m = sc.m;
+  float* colsum_out = sc.colsum_out;
+  const int ncol = sc.transpose ? sc.fo : sc.fi, K = sc.transpose ? sc.fi : sc.fo;
+  const int np = sc.prec == GCNX_PREC_BF16X3 ? 2 : 1;
   // the bit image of a ReLU output (bits_out: written; mask_bits: read instead of `mask`): full-width outputs only (both
   // launches of a pair must split the columns the same way), 64 bytes per row reserved
-  if ((mask_bits || bits_out) && (ncol != 256 || (reinterpret_cast<uintptr_t>(mask_bits) & 7) || (reinterpret_cast<uintptr_t>(bits_out) & 7) ||
-                                  (uint64_t)m * 64u >= 0xFFFFFF00ull))
+  if ((sc.mask_bits || sc.bits_out) && (ncol != 256 || !gcnx_aligned8(sc.mask_bits) || !gcnx_aligned8(sc.bits_out) || !gcnx_fits_buffer(m, 64, 1)))
     return GCNX_ERR_UNSUPPORTED;
-  if (accumulate) return GCNX_ERR_UNSUPPORTED;   // (a read-modify-write epilogue would drain the prefetch ring: tiled kernel)
+  if (sc.accumulate) return GCNX_ERR_UNSUPPORTED;   // (a read-modify-write epilogue would drain the prefetch ring: tiled kernel)
   if (ctx->knob_gemm_stream == 0) return GCNX_ERR_UNSUPPORTED;
   const bool shape_ok = K == 256 && ncol % 4 == 0 && ncol <= 256 && ncol >= 64 && m >= 32 * 1024 &&
-                        lda % 4 == 0 && ldc % 4 == 0 && gcnx_aligned16(a) && gcnx_aligned16(c) && (uint64_t)m * (uint64_t)lda * 4u < 0xFFFFFF00ull &&
-                        (uint64_t)m * (uint64_t)ldc * 4u < 0xFFFFFF00ull &&
-                        (!mask || (ldmask % 4 == 0 && gcnx_aligned16(mask) && (uint64_t)m * (uint64_t)ldmask * 4u < 0xFFFFFF00ull));
+                        lda % 4 == 0 && ldc % 4 == 0 && gcnx_aligned16(a) && gcnx_aligned16(c) && gcnx_fits_buffer(m, lda, 4) &&
+                        gcnx_fits_buffer(m, ldc, 4) &&
+                        (!sc.mask || (sc.ldmask % 4 == 0 && gcnx_aligned16(sc.mask) && gcnx_fits_buffer(m, sc.ldmask, 4)));
   if (!shape_ok) return GCNX_ERR_UNSUPPORTED;
   // bf16x3: hi + lo planes of 256 k x 128 columns = 128 KiB of LDS, wider outputs as two column halves on
   // XCD-neighbouring workgroups, 32 rows per wave.  bf16: one plane of 256 k x 256 columns = 128 KiB, every
@@ -522,11 +524,11 @@ int gcnx_gemm_stream_nn(gcnx_ctx* ctx, const float* a, int64_t lda, const float*
   int rc = gcnx_ws_reserve(ctx, part_bytes + img_elems * sizeof(__bf16) + 256);
   if (rc) return rc;
   __bf16* img = (__bf16*)((char*)ctx->ws + part_bytes);
-  hipLaunchKernelGGL(stream_wprep_kernel, dim3(gcnx_cdiv((long long)img_elems, 256)), dim3(256), 0, ctx->stream, w, fi, fo, transpose,
-                     np, cw, ksteps, ncol, img);
+  hipLaunchKernelGGL(stream_wprep_kernel, dim3(gcnx_cdiv((long long)img_elems, 256)), dim3(256), 0, ctx->stream, sc.w, sc.fi, sc.fo,
+                     sc.transpose, np, cw, ksteps, ncol, img);
   GCNX_LAUNCH_OK(ctx);
-  const StreamEpi ep{bias, alpha, mask_bits ? nullptr : mask, ldmask, act, accumulate, colsum_out ? (float*)ctx->ws : nullptr,
-                     (const unsigned long long*)mask_bits, (unsigned long long*)bits_out};
+  const StreamEpi ep{sc.bias, sc.alpha, sc.mask_bits ? nullptr : sc.mask, sc.ldmask, sc.act, sc.accumulate,
+                     colsum_out ? (float*)ctx->ws : nullptr, (const unsigned long long*)sc.mask_bits, (unsigned long long*)sc.bits_out};
   rc = np == 2 ? launch_stream<2, 128, 2, 8>(ctx, a, lda, img, c, ldc, m, ncol, ep, halves)
                : launch_stream<1, 256, 1, 8>(ctx, a, lda, img, c, ldc, m, ncol, ep, halves);
   if (rc || !colsum_out) return rc;
@@ -564,14 +566,17 @@ int launch_stream16(gcnx_ctx* ctx, const void* a, int64_t lda, const __bf16* img
 // X W (transpose = 1) / dH W^T (transpose = 0) with the streamed operand stored as bf16 and the result stored as bf16
 // (c_bf16) or fp32: plain bf16 products, K = 256, 256 output columns, tall inputs.  The entry point checks the arguments;
 // this returns GCNX_ERR_UNSUPPORTED without a message for shapes outside the kernel.
-int gcnx_gemm_stream_bf16(gcnx_ctx* ctx, const void* a16, int64_t lda, const float* w, int fi, int fo, int transpose, void* c,
-                          int64_t ldc, int c_bf16, int64_t m, const float* bias, int act, float* colsum_out, const void* mask_bits,
-                          void* bits_out, const void* wimg) {
-  const int ncol = transpose ? fo : fi, K = transpose ? fi : fo;
+int gcnx_gemm_stream_bf16(const GemmStreamCall& sc) {
+  gcnx_ctx* ctx = sc.ctx;
+  const void* a16 = sc.a;
+  void* c = sc.c;
+  const int64_t lda = sc.lda, ldc = sc.ldc, m = sc.m;
+  float* colsum_out = sc.colsum_out;
+  const int ncol = sc.transpose ? sc.fo : sc.fi, K = sc.transpose ? sc.fi : sc.fo;
   if (ctx->knob_gemm_stream == 0 || K != 256 || ncol != 256 || m < 32 * 1024) return GCNX_ERR_UNSUPPORTED;
-  if (lda % 8 || ldc % 4 || !gcnx_aligned16(a16) || !gcnx_aligned16(c) || (uint64_t)m * (uint64_t)lda * 2u >= 0xFFFFFF00ull ||
-      (uint64_t)m * (uint64_t)ldc * (c_bf16 ? 2u : 4u) >= 0xFFFFFF00ull || (uint64_t)m * 64u >= 0xFFFFFF00ull ||
-      (reinterpret_cast<uintptr_t>(mask_bits) & 7) || (reinterpret_cast<uintptr_t>(bits_out) & 7))
+  if (lda % 8 || ldc % 4 || !gcnx_aligned16(a16) || !gcnx_aligned16(c) || !gcnx_fits_buffer(m, lda, 2) ||
+      !gcnx_fits_buffer(m, ldc, sc.c_bf16 ? 2 : 4) || !gcnx_fits_buffer(m, 64, 1) || !gcnx_aligned8(sc.mask_bits) ||
+      !gcnx_aligned8(sc.bits_out))
     return GCNX_ERR_UNSUPPORTED;
   if (colsum_out && !gcnx_aligned16(colsum_out)) return GCNX_ERR_UNSUPPORTED;
   const size_t img_elems = (size_t)8 * 256 * 32;
@@ -579,17 +584,17 @@ int gcnx_gemm_stream_bf16(gcnx_ctx* ctx, const void* a16, int64_t lda, const flo
   const size_t part_bytes = colsum_out ? ((gcnx_colsum_partials_ws(prow, ncol) + 255) & ~(size_t)255) : 0;
   int rc = gcnx_ws_reserve(ctx, part_bytes + img_elems * sizeof(__bf16) + 256);
   if (rc) return rc;
-  const __bf16* img = (const __bf16*)wimg;            // the caller's image of this operand (gcnx_gemm_stream_images) ...
+  const __bf16* img = (const __bf16*)sc.wimg;         // the caller's image of this operand (gcnx_gemm_stream_images) ...
   if (!img) {                                         // ... or one built here
     __bf16* own = (__bf16*)((char*)ctx->ws + part_bytes);
-    hipLaunchKernelGGL(stream_wprep_kernel, dim3(gcnx_cdiv((long long)img_elems, 256)), dim3(256), 0, ctx->stream, w, fi, fo, transpose,
-                       1, 256, 8, ncol, own);
+    hipLaunchKernelGGL(stream_wprep_kernel, dim3(gcnx_cdiv((long long)img_elems, 256)), dim3(256), 0, ctx->stream, sc.w, sc.fi, sc.fo,
+                       sc.transpose, 1, 256, 8, ncol, own);
     GCNX_LAUNCH_OK(ctx);
     img = own;
   }
-  const StreamEpi ep{bias, nullptr, nullptr, 0, act, 0, colsum_out ? (float*)ctx->ws : nullptr,
-                     (const unsigned long long*)mask_bits, (unsigned long long*)bits_out};
-  rc = c_bf16 ? launch_stream16<true>(ctx, a16, lda, img, c, ldc, m, ncol, ep) : launch_stream16<false>(ctx, a16, lda, img, c, ldc, m, ncol, ep);
+  const StreamEpi ep{sc.bias, nullptr, nullptr, 0, sc.act, 0, colsum_out ? (float*)ctx->ws : nullptr,
+                     (const unsigned long long*)sc.mask_bits, (unsigned long long*)sc.bits_out};
+  rc = sc.c_bf16 ? launch_stream16<true>(ctx, a16, lda, img, c, ldc, m, ncol, ep) : launch_stream16<false>(ctx, a16, lda, img, c, ldc, m, ncol, ep);
   if (rc || !colsum_out) return rc;
   return gcnx_colsum_partials(ctx, prow, ncol, colsum_out);
 }
@@ -806,36 +811,44 @@ __global__ __launch_bounds__(256) void dw_panel_reduce_kernel(const float* __res
   }
 }
 
+// What the three launchers below share.  Operands: rows of 16 bytes' worth of elements, 16-byte aligned, each matrix
+// inside one buffer descriptor.
+static bool dw_stream_operands_ok(const void* x, int64_t ldx, const void* dh, int64_t lddh, int64_t n, int elem_bytes) {
+  const int per16 = 16 / elem_bytes;
+  return ldx % per16 == 0 && lddh % per16 == 0 && gcnx_aligned16(x) && gcnx_aligned16(dh) && gcnx_fits_buffer(n, ldx, elem_bytes) &&
+         gcnx_fits_buffer(n, lddh, elem_bytes);
+}
+// Row slices: one workgroup per CU (at most max_wgs) over `panels` column panels, slices of whole 32-row steps and none
+// shorter than min_steps.
+static GcnxSplit dw_stream_slices(int max_wgs, int panels, int64_t n, int64_t min_steps) {
+  return gcnx_split_rows(max_wgs / panels, n, 32, min_steps);
+}
+// The launch (the dynamic-LDS limit is raised once per instantiation).  True when the attribute call succeeded; the
+// callers map that and the launch error to their return conventions (common.h).
+template <int NP, bool IN16>
+static bool dw_stream_launch(gcnx_ctx* ctx, dim3 grid, const void* x, int64_t ldx, const void* dh, int64_t lddh, float* slabs, int64_t n,
+                             int64_t rows_per) {
+  return gcnx_launch_dyn_lds<&gemm_dw_stream_kernel<NP, IN16>>(grid, dim3(512), DwLds<NP>::total, ctx->stream, (const float*)x, ldx,
+                                                               (const float*)dh, lddh, slabs, n, rows_per) == hipSuccess;
+}
+#define GCNX_DW_STREAM(NP) ok = dw_stream_launch<NP, false>(ctx, grid, x, ldx, dh, lddh, slabs, n, sl.kchunk)
+
 // dW[fi, 256] = X^T dH for fi = 256 p (p <= 8) at mid-size batches (GeneralGNN: n = 22 576): the streaming kernel over
 // (row slices) x (256-column panels of x), one workgroup per CU in all, then one reduction launch.  Returns 1 when it
 // ran, 0 when the shape is not served (the caller takes gcnx_gemm_dw's tiled path), < 0 on a launch error.
 int gcnx_gemm_dw_panels(gcnx_ctx* ctx, const float* x, int64_t ldx, const float* dh, int64_t lddh, float* dw, int64_t n,
                         int32_t fi, int32_t fo, int prec) {
   if (ctx->knob_gemm_stream == 0 || fo != 256 || fi % 256 != 0 || fi < 256 || fi > 2048 || n < 2048 || prec == GCNX_PREC_F32) return 0;
-  if (ldx % 4 || lddh % 4 || !gcnx_aligned16(x) || !gcnx_aligned16(dh) || !gcnx_aligned16(dw) || (uint64_t)n * (uint64_t)ldx * 4u >= 0xFFFFFF00ull ||
-      (uint64_t)n * (uint64_t)lddh * 4u >= 0xFFFFFF00ull)
-    return 0;
+  if (!dw_stream_operands_ok(x, ldx, dh, lddh, n, 4) || !gcnx_aligned16(dw)) return 0;
   const int panels = fi / 256;
-  const int64_t steps = (n + 31) / 32;
-  int slices = ctx->num_cus / panels;                       // one workgroup per CU over all panels ...
-  if (slices > steps / 6) slices = (int)(steps / 6);        // ... but no slice shorter than 6 steps (fill / drain of the pipeline)
-  if (slices < 1) slices = 1;
-  const int64_t rows_per = ((steps + slices - 1) / slices) * 32;
-  slices = (int)((n + rows_per - 1) / rows_per);
-  if (gcnx_ws_reserve(ctx, (size_t)panels * slices * 65536 * sizeof(float))) return -1;
-  const int np = prec == GCNX_PREC_BF16X3 ? 2 : 1;
-  const dim3 grid(slices, panels);
-  if (np == 2) {
-    static bool set2 = false;
-    if (!set2) { if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_dw_stream_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, DwLds<2>::total) != hipSuccess) return -1; set2 = true; }
-    hipLaunchKernelGGL((gemm_dw_stream_kernel<2>), grid, dim3(512), DwLds<2>::total, ctx->stream, x, ldx, dh, lddh, (float*)ctx->ws, n, rows_per);
-  } else {
-    static bool set1 = false;
-    if (!set1) { if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_dw_stream_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, DwLds<1>::total) != hipSuccess) return -1; set1 = true; }
-    hipLaunchKernelGGL((gemm_dw_stream_kernel<1>), grid, dim3(512), DwLds<1>::total, ctx->stream, x, ldx, dh, lddh, (float*)ctx->ws, n, rows_per);
-  }
-  if (hipGetLastError() != hipSuccess) return -1;
-  hipLaunchKernelGGL(dw_panel_reduce_kernel, dim3(65536 / 4 / 64, panels), dim3(256), 0, ctx->stream, (const float*)ctx->ws, slices, dw);
+  const GcnxSplit sl = dw_stream_slices(ctx->num_cus, panels, n, 6);   // (6 steps: fill / drain of the pipeline)
+  if (gcnx_ws_reserve(ctx, (size_t)panels * sl.nsplit * 65536 * sizeof(float))) return -1;
+  float* slabs = (float*)ctx->ws;
+  const dim3 grid(sl.nsplit, panels);
+  bool ok = false;
+  GCNX_BF16_PAIR(prec, GCNX_DW_STREAM, 1, 2);
+  if (!ok || hipGetLastError() != hipSuccess) return -1;
+  hipLaunchKernelGGL(dw_panel_reduce_kernel, dim3(65536 / 4 / 64, panels), dim3(256), 0, ctx->stream, (const float*)slabs, sl.nsplit, dw);
   return hipGetLastError() == hipSuccess ? 1 : -1;
 }
 
@@ -843,44 +856,24 @@ int gcnx_gemm_dw_panels(gcnx_ctx* ctx, const float* x, int64_t ldx, const float*
 int gcnx_gemm_dw_stream16(gcnx_ctx* ctx, const void* x16, int64_t ldx, const void* dh16, int64_t lddh, float* slabs, int64_t n,
                           int32_t fi, int32_t fo, int max_slices) {
   if (ctx->knob_gemm_stream == 0 || fi != 256 || fo != 256 || n < 32 * 1024) return 0;
-  if (ldx % 8 || lddh % 8 || !gcnx_aligned16(x16) || !gcnx_aligned16(dh16) || (uint64_t)n * (uint64_t)ldx * 2u >= 0xFFFFFF00ull ||
-      (uint64_t)n * (uint64_t)lddh * 2u >= 0xFFFFFF00ull)
-    return 0;
-  int slices = ctx->num_cus < max_slices ? ctx->num_cus : max_slices;
-  const int64_t steps = (n + 31) / 32;
-  if (slices > steps) slices = (int)steps;
-  const int64_t rows_per = ((steps + slices - 1) / slices) * 32;
-  slices = (int)((n + rows_per - 1) / rows_per);
-  static bool set16 = false;
-  if (!set16) { if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_dw_stream_kernel<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, DwLds<1>::total) != hipSuccess) return 0; set16 = true; }
-  hipLaunchKernelGGL((gemm_dw_stream_kernel<1, true>), dim3(slices), dim3(512), DwLds<1>::total, ctx->stream, (const float*)x16, ldx,
-                     (const float*)dh16, lddh, slabs, n, rows_per);
-  return hipGetLastError() == hipSuccess ? slices : -1;
+  if (!dw_stream_operands_ok(x16, ldx, dh16, lddh, n, 2)) return 0;
+  const GcnxSplit sl = dw_stream_slices(ctx->num_cus < max_slices ? ctx->num_cus : max_slices, 1, n, 1);
+  if (!dw_stream_launch<1, true>(ctx, dim3(sl.nsplit), x16, ldx, dh16, lddh, slabs, n, sl.kchunk)) return 0;
+  return hipGetLastError() == hipSuccess ? sl.nsplit : -1;
 }
 
 int gcnx_gemm_dw_stream(gcnx_ctx* ctx, const float* x, int64_t ldx, const float* dh, int64_t lddh, float* slabs, int64_t n,
                         int32_t fi, int32_t fo, int prec, int max_slices) {
   if (ctx->knob_gemm_stream == 0 || fi != 256 || fo != 256 || n < 32 * 1024 || prec == GCNX_PREC_F32) return 0;
-  if (ldx % 4 || lddh % 4 || !gcnx_aligned16(x) || !gcnx_aligned16(dh) || (uint64_t)n * (uint64_t)ldx * 4u >= 0xFFFFFF00ull ||
-      (uint64_t)n * (uint64_t)lddh * 4u >= 0xFFFFFF00ull)
-    return 0;
-  int slices = ctx->num_cus < max_slices ? ctx->num_cus : max_slices;
-  const int64_t steps = (n + 31) / 32;
-  if (slices > steps) slices = (int)steps;
-  const int64_t rows_per = ((steps + slices - 1) / slices) * 32;
-  slices = (int)((n + rows_per - 1) / rows_per);
-  const int np = prec == GCNX_PREC_BF16X3 ? 2 : 1;
-  if (np == 2) {
-    static bool set2 = false;
-    if (!set2) { if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_dw_stream_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, DwLds<2>::total) != hipSuccess) return 0; set2 = true; }
-    hipLaunchKernelGGL((gemm_dw_stream_kernel<2>), dim3(slices), dim3(512), DwLds<2>::total, ctx->stream, x, ldx, dh, lddh, slabs, n, rows_per);
-  } else {
-    static bool set1 = false;
-    if (!set1) { if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_dw_stream_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, DwLds<1>::total) != hipSuccess) return 0; set1 = true; }
-    hipLaunchKernelGGL((gemm_dw_stream_kernel<1>), dim3(slices), dim3(512), DwLds<1>::total, ctx->stream, x, ldx, dh, lddh, slabs, n, rows_per);
-  }
-  return hipGetLastError() == hipSuccess ? slices : -1;
+  if (!dw_stream_operands_ok(x, ldx, dh, lddh, n, 4)) return 0;
+  const GcnxSplit sl = dw_stream_slices(ctx->num_cus < max_slices ? ctx->num_cus : max_slices, 1, n, 1);
+  const dim3 grid(sl.nsplit);
+  bool ok = false;
+  GCNX_BF16_PAIR(prec, GCNX_DW_STREAM, 1, 2);
+  if (!ok) return 0;
+  return hipGetLastError() == hipSuccess ? sl.nsplit : -1;
 }
+#undef GCNX_DW_STREAM
 
 // The images of up to four 256 x 256 weight operands for gcnx_gemm_fwd_bf16 (transpose = 1: X W) / gcnx_gemm_dx_bf16
 // (transpose = 0: dH W^T), 128 KiB each, in one launch.

@@ -804,6 +804,45 @@ def test_gemm_bf16_streaming_kernel(ctx, n, fi, fo, monkeypatch):
         c2.close()
 
 
+_tall_dw = {}
+
+
+def _tall_dw_case():
+    """n = 32 768, fi = fo = 256 (the smallest shape the streaming dW kernel takes): operands and, per precision, the float64
+    product they are held to (bf16: of the bf16-rounded operands, as test_gemm_bf16_mfma_paths)."""
+    if not _tall_dw:
+        rng = np.random.default_rng(32768)
+        x = rng.standard_normal((32768, 256), dtype=np.float32)
+        dh = rng.standard_normal((32768, 256), dtype=np.float32)
+        _tall_dw.update(x=x, dh=dh, bf16x3=x.astype(np.float64).T @ dh.astype(np.float64),
+                        bf16=_bf16_round(x).astype(np.float64).T @ _bf16_round(dh).astype(np.float64))
+    return _tall_dw
+
+
+@pytest.mark.parametrize("prec,tol", [("bf16", 2e-5), ("bf16x3", TOL)])
+def test_gemm_dw_tall_streamed_same_bits_aligned_and_unaligned(ctx, prec, tol):
+    """The tall streamed dW (one slab per CU, then one reduction) folds its slabs with the float4 kernel when dw is 16-byte
+    aligned and with the one-output-per-thread kernel when it is not; both sum in the same order.  dw inside a frame of
+    sentinels at a float offset of 4 (wide) and of 1 (narrow): the same 65 536 bit patterns, both frames intact, and the
+    result within the precision's tolerance of float64."""
+    from gcnx import device as D
+    case = _tall_dw_case()
+    n, f = case["x"].shape
+    d_x, d_dh = ctx.to_device(case["x"]), ctx.to_device(case["dh"])
+    got = {}
+    for off in (4, 1):
+        frame = ctx.to_device(np.full(f * f + 8, 12345.0, np.float32))
+        assert frame.ptr % 16 == 0
+        D.gemm_dw(ctx, d_x, d_dh, frame.flat(off, f * f, (f, f)), prec=prec)
+        h = frame.numpy()
+        assert (h[:off] == 12345.0).all() and (h[off + f * f:] == 12345.0).all(), off
+        got[off] = h[off:off + f * f].copy()
+    assert np.array_equal(got[4].view(np.uint32), got[1].view(np.uint32))
+    err = rel_err(got[4].reshape(f, f), case[prec])
+    print(f"{prec}: rel err {err:.3e} (tolerance {tol})")
+    assert err < tol
+
+
 @pytest.mark.parametrize("f", [64, 128, 256])
 @pytest.mark.parametrize("weighted", [False, True])
 def test_spmm_bf16_features(ctx, f, weighted):

@@ -138,6 +138,63 @@ def test_gemm_dw2_sums_in_the_documented_order(ctx, s, with_params):
         assert np.array_equal(_bits(params.numpy()), _bits(p0 - LR * g))
 
 
+@pytest.mark.parametrize("s", [2, 3, 5, 7, 17, 65])
+def test_dense_bwd_sums_dw_in_the_documented_order(ctx, s):
+    """gcnx_dense_bwd plans its dW slices by another slot rule than gcnx_gemm_dw: the slices fill the resident-workgroup
+    slots (4 per CU) that the dX tiles leave.  With fi = fo = 64 and n = 320 s there are n_dx = 5 s dX tiles and one dW
+    tile; spare = 4 CUs - 5 s (1024 - 5 s on the 256-CU device, never under a quarter of the slots, i.e. at least 256
+    there), ksteps = 10 s, so nsplit = min(spare, ksteps / 10) = s and kchunk = 320: slice j is exactly the rows
+    [320 j, 320 (j + 1)), as above, and dW must carry the bits of the documented sum.  w is an integer matrix in
+    [-3, 3] and y_mask = x: every entry of dX is an integer of at most 576 and every partial sum of a column of dX an
+    integer below 2^24, so dX and db are exact whatever the order.  Scratch: 2 * 5 s partial rows of 64 floats + s slabs
+    of 4096.  The deferred route (gcnx_dense_bwd_deferred, finished by gcnx_gemm_dw_sgd's reduction launch) must give the
+    same dW and db bits, and the update p0 - lr g for every parameter."""
+    from gcnx import device as D
+    x, dhs, slabs = _case(s)
+    n = 320 * s
+    w = np.random.default_rng(300 + s).integers(-3, 4, (F, F)).astype(np.float32)
+    dx64 = (dhs[0].astype(np.float64) @ w.astype(np.float64).T) * (x > 0)
+    assert np.abs(dx64).sum(0).max() < 2 ** 24
+    want_dw, want_db = _documented_sum(slabs[0]), dx64.sum(0)
+    xd, dhd, wd = ctx.to_device(x), ctx.to_device(dhs[0]), ctx.to_device(w)
+    layout = [("pad0", 12), ("db", F), ("gap", 20), ("dw", F * F), ("gap2", 8), ("dw0", F * F), ("pad1", 12)]
+
+    def check(g, dxbuf, names):
+        assert np.array_equal(_bits(g[at["dw"]:at["dw"] + F * F]), _bits(want_dw))
+        assert np.array_equal(g[at["db"]:at["db"] + F].astype(np.float64), want_db)
+        inside = np.zeros(size, bool)
+        for name in names:
+            inside[at[name]:at[name] + (F if name == "db" else F * F)] = True
+        assert (g[~inside] == SENTINEL).all()
+        dxh = dxbuf.numpy()
+        assert np.array_equal(dxh[8:8 + n * F].reshape(n, F).astype(np.float64), dx64)
+        assert (dxh[:8] == SENTINEL).all() and (dxh[8 + n * F:] == SENTINEL).all()
+
+    assert D.dense_bwd_scratch_floats(ctx, n, F, F) == 640 * s + 4096 * s
+    buf, at, size = _framed(ctx, layout)
+    dxbuf = ctx.to_device(np.full(n * F + 16, SENTINEL, np.float32))
+    D.dense_bwd(ctx, xd, dhd, wd, dxbuf.flat(8, n * F, (n, F)), buf.flat(at["dw"], F * F, (F, F)), y_mask=xd,
+                db_prev=buf.flat(at["db"], F))
+    first = buf.numpy()
+    check(first, dxbuf, ("db", "dw"))
+    # deferred: the partials stay in the caller's scratch until the step's last launch folds them and applies the update
+    grads, at, size = _framed(ctx, layout)
+    dxbuf = ctx.to_device(np.full(n * F + 16, SENTINEL, np.float32))
+    p0 = np.random.default_rng(400 + s).standard_normal(size, dtype=np.float32)
+    params = ctx.to_device(p0)
+    scratch = ctx.empty(640 * s + 4096 * s)
+    pend = D.dense_bwd_deferred(ctx, xd, dhd, wd, dxbuf.flat(8, n * F, (n, F)), grads.flat(at["dw"], F * F, (F, F)), scratch,
+                                y_mask=xd, db_prev=grads.flat(at["db"], F))
+    assert pend.colpart and pend.crows == 10 * s and pend.slabs and pend.nsplit == s
+    D.gemm_dw_sgd(ctx, xd, ctx.to_device(dhs[1]), grads.flat(at["dw0"], F * F, (F, F)), params, grads, float(LR), pending=pend)
+    g = grads.numpy()
+    check(g, dxbuf, ("db", "dw", "dw0"))
+    assert np.array_equal(_bits(g[at["dw"]:at["dw"] + F * F]), _bits(first[at["dw"]:at["dw"] + F * F]))
+    assert np.array_equal(_bits(g[at["db"]:at["db"] + F]), _bits(first[at["db"]:at["db"] + F]))
+    assert np.array_equal(_bits(g[at["dw0"]:at["dw0"] + F * F]), _bits(_documented_sum(slabs[1])))
+    assert np.array_equal(_bits(params.numpy()), _bits(p0 - LR * g))
+
+
 def _partial_rows(rows, f, seed):
     """Partial rows of ordinary floats: every addition rounds, so the column sums show the order."""
     return np.random.default_rng(seed).standard_normal((rows, f), dtype=np.float32)
