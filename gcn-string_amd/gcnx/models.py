@@ -15,7 +15,9 @@ Linear·BatchNorm1d·PReLU twice, one logit with BCEWithLogitsLoss (eager launch
 """
 from __future__ import annotations
 
+import contextlib
 import os
+import sys
 
 import numpy as np
 
@@ -112,12 +114,145 @@ class _Capacity:
         return D.DeviceArray._view(cur, 0, (int(rows), int(width)))
 
 
+_CAPTURE_FAILED_GCN2 = ("gcnx: RCCL all-reduce could not be captured into the step graph ({}); falling back to an eager "
+                        "collective between two graphs")
+_CAPTURE_FAILED_SYNC_BN = "gcnx: the sync-BN step could not be captured with its collectives ({}); running it eagerly"
+
+
 class _GraphRunner:
-    """Runs a fixed call sequence eagerly once (sizes the workspace), captures it into a HIP graph on the second
-    use and replays it afterwards -- the role tf.function plays at gcn.py:328.  Graphs hold the pointers of one
-    batch and are dropped when the batch changes."""
+    """The training-step protocol of the four models (GCN2, GeneralGNN, GCN, ECCNet), and the graph replay under it.
+
+    A model provides:
+      __init__          ctx, comm (or None), use_graph, prec, cce_train / cce_eval, built = False, _bufs = None, _graphs = {}
+      build             its parameters: _alloc_flat(entries, align), or its own placement in flat_p / flat_g (+ 2 floats)
+      _as_batch         its own lines around _adopt (what it passes to DeviceBatch.from_host, what it checks)
+      _ensure           the buffer list of one batch shape, as views from _views()
+      _forward, _backward                       the launches
+      __call__, loss_and_grads, train_step, evaluate_batch     the sequence of the above; public signatures are the model's
+      get_weights, set_weights, gradients, trainable_variables
+      uses_edge_features = True                 if it reads DeviceBatch.e
+    and inherits:
+      _adopt            a DeviceBatch as it is (labels attached late), host inputs through DeviceBatch.from_host
+      _views            the grow-only capacity behind the per-batch views (self._cap)
+      _alloc_flat       n_params, flat_p, flat_g, p, g, loss_acc: packed, or every tensor on a 4-float boundary
+      _bind, _run, _drop_graphs                 eager once, then capture, then replay; graphs die with their batch
+      _lr_key           the learning rate as a device scalar
+      _multi, _comm_in_graph                    more than one rank; the collectives recorded into the step graph
+      _run_with_comm_fallback                   _run; a capture that fails with the collectives inside falls back for good
+      _global_counts_cached, _global_graphs     sync-BN: the global (N, B, ...) of a batch, one host all-reduce per batch
+      _apply_sgd        the one update launch
+      _finish_step, fetch_metrics, _loss_acc_host, stash_metrics, collect_metrics     what a step and an evaluation return
+      losses            [] (no regularisers: gcn.py:335 adds sum(model.losses))"""
 
     use_graph = True
+    uses_edge_features = False           # ECCNet: True.  Everyone else takes (x, a, e, i) and drops e (_adopt, gcnx.fit / gcnx.evaluate)
+    comm = None
+    _cap = None
+    _counts_uid = None
+    _comm_capture_failed = False
+
+    # ---- batches, storage, parameters ---------------------------------------------------------------------------------
+    def _adopt(self, inputs, target=None, **from_host_kw):
+        """A DeviceBatch as it is (``target`` uploaded if it carries no labels yet); host inputs through DeviceBatch.from_host."""
+        if isinstance(inputs, DeviceBatch):
+            if target is not None and inputs.y is None:
+                inputs.y = self.ctx.to_device(target, np.float32)
+            return inputs
+        if not self.uses_edge_features:
+            inputs = _without_e(inputs)
+        return DeviceBatch.from_host(self.ctx, inputs, target, **from_host_kw)
+
+    def _views(self):
+        """``view(name, rows, width, dtype, zero)`` of this model's grow-only storage (created on first use)."""
+        if self._cap is None:
+            self._cap = _Capacity(self.ctx)
+        return self._cap.view
+
+    def _alloc_flat(self, entries, align=1):
+        """One flat parameter and one flat gradient buffer (single all-reduce, single SGD launch); the tensors of ``entries``
+        -- ordered (key, shape) -- are views p[key] / g[key], each on a multiple of ``align`` floats (padding has zero gradients:
+        the update leaves it at zero).  The gradients end in two extra floats, ``loss_acc`` = (loss sum, correct count), which
+        so ride in the same all-reduce.  Returns {key: offset}."""
+        offs, off = {}, 0
+        for k, shape in entries:
+            offs[k] = off
+            off += -(-int(np.prod(shape)) // align) * align
+        self.n_params = off
+        self.flat_p = self.ctx.zeros(off)
+        self.flat_g = self.ctx.zeros(off + 2)
+        self.p, self.g = {}, {}
+        for k, shape in entries:
+            n = int(np.prod(shape))
+            self.p[k] = self.flat_p.flat(offs[k], n, shape)
+            self.g[k] = self.flat_g.flat(offs[k], n, shape)
+        self.loss_acc = self.flat_g.flat(off, 2)
+        return offs
+
+    @property
+    def losses(self):
+        return []  # no regularisers (gcn.py:335 adds sum(model.losses))
+
+    # ---- more than one rank --------------------------------------------------------------------------------------------
+    def _multi(self):
+        return self.comm is not None and self.comm.world_size > 1
+
+    def _comm_in_graph(self):
+        """Multi-GPU: the step's collectives are recorded INTO the step graph (RCCL enqueues on the ctx stream and
+        supports stream capture), so a sharded step is one graph launch -- gradient kernels, ncclAllReduce, SGD --
+        instead of graph | eager collective | graph (two graph boundaries around a 0.14 ms step).  Falls back to
+        that form if the communicator cannot be captured (the thread-rank test transport) or a capture
+        with a collective inside ever fails."""
+        return (self.use_graph and self._multi() and getattr(self.comm, "capturable", False)
+                and not self._comm_capture_failed)
+
+    def _run_with_comm_fallback(self, tag, seq, fused_comm, message, retry):
+        """_run(tag, seq).  If it raises with the collectives inside (``fused_comm``): from now on they stay outside the
+        graphs (every rank runs the same software, so every rank lands here together) -- returns ``retry()``, the step
+        entered again; None if the step ran."""
+        try:
+            self._run(tag, seq)
+        except Exception as e:
+            if not fused_comm:
+                raise
+            print(message.format(e), file=sys.stderr)
+            self._comm_capture_failed = True
+            self._drop_graphs()
+            return retry()
+        return None
+
+    def _global_counts_cached(self, batch, values):
+        """Sync-BN: [n, b(, ranks without a graph)] of this rank's shard summed over the ranks, as {"n", "b"(, "empty")}:
+        one host round trip per BATCH (cached by its uid), not per step."""
+        if self._counts_uid != batch.uid:
+            tot = self.comm.allreduce_host(values, "sum")
+            self._counts = {k: float(t) for k, t in zip(("n", "b", "empty"), tot)}
+            self._counts_uid = batch.uid
+        return self._counts
+
+    def _global_graphs(self, batch):
+        """Graphs of the whole batch: what the cached global counts say where the batch is a rank's shard."""
+        return self._counts["b"] if self._multi() else batch.n_graphs
+
+    # ---- the end of a step ---------------------------------------------------------------------------------------------
+    def _apply_sgd(self, lr):
+        D.sgd(self.ctx, self.flat_p, self.flat_g.flat(0, self.n_params), lr)
+
+    def _finish_step(self, fetch, n_graphs):
+        """What train_step returns.  fetch: True -> (loss, acc); False -> None; "stash" -> None, the metrics kept on the
+        device for collect_metrics()."""
+        if fetch == "stash":
+            self.stash_metrics(n_graphs)
+            return None
+        if not fetch:
+            return None
+        return self.fetch_metrics(n_graphs)
+
+    def fetch_metrics(self, n_graphs):
+        """(loss, accuracy over ``n_graphs``) of the last step or evaluation: one device -> host copy, which waits for it."""
+        la = self.loss_acc.numpy()
+        return float(la[0]), float(la[1]) / float(n_graphs)
+
+    _loss_acc_host = fetch_metrics                           # (evaluate_batch's name for the same read)
 
     def _bind(self, batch):
         """Captured graphs hold the pointers of one batch: drop them when the batch changes."""
@@ -244,19 +379,7 @@ class GCN2(_GraphRunner):
         c = self.n_labels
         self.f_in, self.hidden = f_in, h
         shapes = {"w1": (f_in, h), "b1": (h,), "w2": (h, h), "b2": (h,), "w3": (h, c), "b3": (c,)}
-        self.n_params = sum(int(np.prod(s)) for s in shapes.values())
-        # grads carries two extra floats (loss sum, correct count) so that they ride in the
-        # same all-reduce as the gradients.
-        self.flat_p = self.ctx.zeros(self.n_params)
-        self.flat_g = self.ctx.zeros(self.n_params + 2)
-        self.p, self.g = {}, {}
-        off = 0
-        for k in self.PARAM_ORDER:
-            n = int(np.prod(shapes[k]))
-            self.p[k] = self.flat_p.flat(off, n, shapes[k])
-            self.g[k] = self.flat_g.flat(off, n, shapes[k])
-            off += n
-        self.loss_acc = self.flat_g.flat(off, 2)
+        self._alloc_flat([(k, shapes[k]) for k in self.PARAM_ORDER])       # packed: _bucket_split() counts on it
         init = {"w1": glorot_uniform(self._rng, f_in, h), "w2": glorot_uniform(self._rng, h, h),
                 "w3": glorot_uniform(self._rng, h, c)}
         for k, v in init.items():
@@ -274,10 +397,6 @@ class GCN2(_GraphRunner):
     def trainable_variables(self):
         return [self.p[k] for k in self.PARAM_ORDER]
 
-    @property
-    def losses(self):
-        return []  # no regularisers (gcn.py:335 adds sum(model.losses))
-
     # ---- buffers for one batch shape ---------------------------------------------------------
     def _ensure(self, batch):
         """Activation buffers for this batch shape.  Storage is grow-only capacity (a streamed epoch brings a new
@@ -291,9 +410,7 @@ class GCN2(_GraphRunner):
         n, b, h, c = batch.n, batch.n_graphs, self.hidden, self.n_labels
         self._drop_graphs()
         self._s1_uid = None                                     # new views, possibly new storage: no S1 is kept across this
-        if getattr(self, "_cap", None) is None:
-            self._cap = _Capacity(self.ctx)
-        v = self._cap.view
+        v = self._views()
         self._bufs = {"key": key}
         for k in ("h", "y1", "y2", "dz", "h2", "dz2"):          # h2 / dz2: the side section still reads h / dz
             self._bufs[k] = v(k, n, h)
@@ -506,7 +623,6 @@ class GCN2(_GraphRunner):
         # leaves.  With layer 1 in (A X) W1 order the chain is dX -> dW1, streaming GEMMs that share one bound (HBM, or
         # the fp32 MFMA) with dW2: on one stream the step measured 1-3 % faster at config 3 in every precision (4.12
         # against 4.21-4.25 ms in bf16), the same at config 5.
-        import contextlib
         if act16 and not dh16_done:
             D.to_bf16_into(ctx, bufs["h"], dh16)                                # (dH2 came from an fp32 path: the same rounding)
         with (contextlib.nullcontext() if "s1" in bufs else ctx.side()):
@@ -554,7 +670,6 @@ class GCN2(_GraphRunner):
     def _allreduce_tail_bucket(self):
         """{dW2, db2, dW3, db3, loss, #correct}: on the side stream (a second branch of a captured step) when the transport
         enqueues on a stream; in line otherwise."""
-        import contextlib
         off = self._bucket_split()
         tail = self.flat_g.flat(off, self.n_params + 2 - off)
         with (self.ctx.side() if getattr(self.comm, "capturable", False) else contextlib.nullcontext()):
@@ -620,7 +735,6 @@ class GCN2(_GraphRunner):
 
     def _backward_knob(self, batch, bufs, side):
         """The same backward with individual side sections switched off (GCNX_SIDE bits; measurement only)."""
-        import contextlib
         ctx, p, g, prec = self.ctx, self.p, self.g, self.prec
         at = batch.a.transpose()
         sec = lambda on: ctx.side() if on else contextlib.nullcontext()
@@ -639,16 +753,9 @@ class GCN2(_GraphRunner):
         D.gemm_dw(ctx, batch.x, bufs["h"], g["w1"], prec=prec)
         ctx.join()
 
-    def _world(self):
-        return self.comm.world_size if self.comm is not None else 1
-
     # ---- public surface: model(inputs, training=...) and train_step ------------------------
     def _as_batch(self, inputs, target=None):
-        if isinstance(inputs, DeviceBatch):
-            if target is not None and inputs.y is None:
-                inputs.y = self.ctx.to_device(target, np.float32)
-            return inputs
-        return DeviceBatch.from_host(self.ctx, _without_e(inputs), target)
+        return self._adopt(inputs, target)                       # (the adjacency's values are read: weighted)
 
     def __call__(self, inputs, training=False):
         """model([x, a, i], training=False) -> probabilities [B, C] (gcn.py:351)."""
@@ -658,21 +765,12 @@ class GCN2(_GraphRunner):
         self._run(("fwd", batch.uid), lambda: self._forward(batch, bufs, False, None))
         return bufs["probs"].numpy()
 
-    def _comm_in_graph(self):
-        """Multi-GPU: the gradient all-reduce is recorded INTO the step graph (RCCL enqueues on the ctx stream and
-        supports stream capture), so a sharded step is one graph launch -- gradient kernels, ncclAllReduce, SGD --
-        instead of graph | eager collective | graph (two graph boundaries around a 0.14 ms step).  Falls back to
-        that three-part form if the communicator cannot be captured (the thread-rank test transport) or a capture
-        with the collective inside ever fails."""
-        return (self.use_graph and self._world() > 1 and getattr(self.comm, "capturable", False)
-                and not getattr(self, "_comm_capture_failed", False))
-
     def loss_and_grads(self, inputs, target, global_batch=None, _lr=None):
         """Forward + loss + every gradient (no update unless ``_lr``).  Returns the device batch."""
         batch = self._as_batch(inputs, target)
         bufs = self._ensure(batch)
         denom = float(global_batch or batch.n_graphs)
-        multi = self._world() > 1
+        multi = self._multi()
         if self._graph_opt == "auto":
             self.use_graph = bool(multi or not (self._fused(batch) and self._head_late(batch)))
         fused_comm = multi and _lr is not None and self._comm_in_graph()
@@ -689,23 +787,16 @@ class GCN2(_GraphRunner):
                 self.comm.allreduce_sum(self.flat_g)
             if _lr is not None and (fused_comm or not multi):
                 # the update rides in the same captured graph (one graph launch per step)
-                D.sgd(self.ctx, self.flat_p, self.flat_g.flat(0, self.n_params), _lr)
+                self._apply_sgd(_lr)
         self._bind(batch)
         self._step_applied = fused_comm or not multi
         lr_key = self._lr_key(_lr)
-        try:
-            self._run(("grad", batch.uid, denom, lr_key if self._step_applied else None), seq)
-        except Exception as e:
-            if not fused_comm:
-                raise
-            # capture with the collective inside failed: from now on graph | all-reduce | graph (every rank runs the
-            # same software, so every rank lands here together)
-            import sys
-            print(f"gcnx: RCCL all-reduce could not be captured into the step graph ({e}); falling back to an eager "
-                  f"collective between two graphs", file=sys.stderr)
-            self._comm_capture_failed = True
-            self._drop_graphs()
-            return self.loss_and_grads(batch, None, global_batch, _lr)
+        # (a failed capture with the collective inside: from now on graph | all-reduce | graph)
+        again = self._run_with_comm_fallback(
+            ("grad", batch.uid, denom, lr_key if self._step_applied else None), seq, fused_comm, _CAPTURE_FAILED_GCN2,
+            fused_comm and (lambda: self.loss_and_grads(batch, None, global_batch=global_batch, _lr=_lr)))
+        if again is not None:
+            return again
         if multi and not fused_comm and not self._reduced_in_backward:
             self.comm.allreduce_sum(self.flat_g)
         self._last_batch = batch
@@ -717,26 +808,16 @@ class GCN2(_GraphRunner):
         this rank's shard and ``global_batch`` the number of graphs over all ranks."""
         batch = self.loss_and_grads(inputs, target, global_batch, _lr=float(lr))
         if not self._step_applied:
-            self._run(("sgd", self._lr_key(float(lr))), lambda: D.sgd(self.ctx, self.flat_p, self.flat_g.flat(0, self.n_params), lr))
+            self._run(("sgd", self._lr_key(float(lr))), lambda: self._apply_sgd(lr))
             self.ctx.set_lr_source(None)
-        if fetch == "stash":
-            self.stash_metrics(global_batch or batch.n_graphs)
-            return None
-        if not fetch:
-            return None
-        return self.fetch_metrics(global_batch or batch.n_graphs)
-
-    def fetch_metrics(self, n_graphs):
-        la = self.loss_acc.numpy()
-        return float(la[0]), float(la[1]) / float(n_graphs)
+        return self._finish_step(fetch, global_batch or batch.n_graphs)
 
     def evaluate_batch(self, inputs, target):
         """Forward + loss/acc only (the body of evaluate(), gcn.py:350-357)."""
         batch = self._as_batch(inputs, target)
         bufs = self._ensure(batch)
         self._forward(batch, bufs, True, float(batch.n_graphs))
-        la = self.loss_acc.numpy()
-        return float(la[0]), float(la[1]) / batch.n_graphs, bufs["probs"].numpy()
+        return (*self._loss_acc_host(batch.n_graphs), bufs["probs"].numpy())
 
     def gradients(self):
         return {k: self.g[k].numpy() for k in self.PARAM_ORDER}
@@ -846,7 +927,6 @@ class GeneralGNN(_GraphRunner):
                 L["g_" + name] = self.flat_g.flat(off, n, shape)
                 off += n
             L["sums"], L["scratch"] = ctx.zeros(2 * fo), ctx.zeros(3 * fo)
-            from .layers import glorot_uniform
             L["kernel"].copy_from_host(glorot_uniform(self._rng, fi, fo))
             if bn:
                 L["moving_mean"] = self.flat_s.flat(soff, fo); L["moving_var"] = self.flat_s.flat(soff + fo, fo); soff += 2 * fo
@@ -917,10 +997,6 @@ class GeneralGNN(_GraphRunner):
     def trainable_variables(self):
         return [L[k] for L in self.layers for k in ("kernel", "bias", "gamma", "beta", "alpha") if k in L]
 
-    @property
-    def losses(self):
-        return []
-
     # ---- buffers ---------------------------------------------------------------------------------
     def _ensure(self, batch):
         if not self.built:
@@ -931,9 +1007,7 @@ class GeneralGNN(_GraphRunner):
         ctx, n, b, h = self.ctx, batch.n, batch.n_graphs, self.hidden
         self._drop_graphs()
         wcat = h * (self.mp + 1)
-        if getattr(self, "_cap", None) is None:
-            self._cap = _Capacity(ctx)
-        v = self._cap.view
+        v = self._views()
         wp = self._wpool
         bufs = {"key": key, "cat": v("cat", n, wcat), "dcat": v("dcat", n, wcat), "h": v("h", n, h), "dh": v("dh", n, h),
                 "pooled": v("pooled", b, wp), "dpooled": v("dpooled", b, wp), "probs": v("probs", b, self.output),
@@ -944,9 +1018,6 @@ class GeneralGNN(_GraphRunner):
             bufs[f"y{i}"] = v(f"y{i}", rows, L["fo"])             # layer output where it is not a slice of `cat`
         self._bufs = bufs
         return bufs
-
-    def _multi(self):
-        return self.comm is not None and self.comm.world_size > 1
 
     def _drop(self, L, t):
         """The layer's Dropout factor applied to t in place (forward: the activation's output -- act(s u) = s act(u) for the
@@ -1035,9 +1106,7 @@ class GeneralGNN(_GraphRunner):
                     D.add(self.ctx, new, inp, new)
             li += 1
         if self.pool == "max":
-            if getattr(self, "_cap", None) is None:
-                self._cap = _Capacity(self.ctx)
-            bufs["pool_arg"] = self._cap.view("pool_arg", bufs["pooled"].shape[0], bufs["pooled"].shape[1], np.int32)
+            bufs["pool_arg"] = self._views()("pool_arg", bufs["pooled"].shape[0], bufs["pooled"].shape[1], np.int32)
         D.segment_pool(self.ctx, batch.seg, cat.cols(0, h) if sumc else cat, bufs["pooled"], self.pool,
                        bufs.get("pool_arg") if self.pool == "max" else None)
         x = bufs["pooled"]
@@ -1162,21 +1231,15 @@ class GeneralGNN(_GraphRunner):
 
     def _tmp(self, bufs, key, shape):
         if key not in bufs or bufs[key].shape != tuple(shape):
-            if getattr(self, "_cap", None) is None:
-                self._cap = _Capacity(self.ctx)
             shape = tuple(shape) if len(shape) == 2 else (1, int(np.prod(shape)))
-            bufs[key] = self._cap.view("tmp_" + key, shape[0], shape[1])
+            bufs[key] = self._views()("tmp_" + key, shape[0], shape[1])
             if len(shape) != 2:
                 bufs[key] = bufs[key].flat(0, shape[1])
         return bufs[key]
 
     # ---- public surface ----------------------------------------------------------------------------
     def _as_batch(self, inputs, target=None):
-        if isinstance(inputs, DeviceBatch):
-            if target is not None and inputs.y is None:
-                inputs.y = self.ctx.to_device(target, np.float32)
-            return inputs
-        return DeviceBatch.from_host(self.ctx, _without_e(inputs), target, weighted=False)
+        return self._adopt(inputs, target, weighted=False)       # (GeneralConv ignores the adjacency's values)
 
     def __call__(self, inputs, training=False):
         batch = self._as_batch(inputs)
@@ -1199,16 +1262,11 @@ class GeneralGNN(_GraphRunner):
         multi = self._multi()
         denom = float(global_batch or batch.n_graphs)
         if multi:
-            # global row / graph counts for sync-BN: one host round trip per BATCH (cached by its uid), not per step
-            if getattr(self, "_counts_uid", None) != batch.uid:
-                tot = self.comm.allreduce_host([batch.n, batch.n_graphs], "sum")
-                self._counts = {"n": float(tot[0]), "b": float(tot[1])}
-                self._counts_uid = batch.uid
-            denom = float(global_batch or self._counts["b"])
+            counts = self._global_counts_cached(batch, [batch.n, batch.n_graphs])      # sync-BN reads them (self._counts)
+            denom = float(global_batch or counts["b"])
         # with a capturable communicator (RCCL) the whole sync-BN step -- 2 small all-reduces per layer forward, 1 per
         # layer backward, the gradient all-reduce and SGD -- is recorded into ONE HIP graph
-        fused_comm = (multi and _lr is not None and self.use_graph and getattr(self.comm, "capturable", False)
-                      and not getattr(self, "_comm_capture_failed", False))
+        fused_comm = multi and _lr is not None and self._comm_in_graph()
 
         def seq():
             self._prepare_images()
@@ -1219,7 +1277,7 @@ class GeneralGNN(_GraphRunner):
             if fused_comm:
                 self.comm.allreduce_sum(self.flat_g)
             if _lr is not None and (fused_comm or not multi):   # the update rides in the same captured graph
-                D.sgd(self.ctx, self.flat_p, self.flat_g.flat(0, self.n_params), _lr)
+                self._apply_sgd(_lr)
             if self.dropout > 0.0:
                 D.counter_add(self.ctx, self._step_dev, 1)     # the next step draws new Dropout masks (also from a replayed graph)
         self._bind(batch)
@@ -1229,17 +1287,11 @@ class GeneralGNN(_GraphRunner):
             seq()                                          # host-mediated collectives inside: not captured
             self.comm.allreduce_sum(self.flat_g)
         else:
-            try:
-                self._run(("grad", batch.uid, lr_key, denom), seq)
-            except Exception as e:
-                if not fused_comm:
-                    raise
-                import sys
-                print(f"gcnx: the sync-BN step could not be captured with its collectives ({e}); running it eagerly",
-                      file=sys.stderr)
-                self._comm_capture_failed = True
-                self._drop_graphs()
-                return self.loss_and_grads(batch, None, _lr, global_batch)
+            again = self._run_with_comm_fallback(
+                ("grad", batch.uid, lr_key, denom), seq, fused_comm, _CAPTURE_FAILED_SYNC_BN,
+                fused_comm and (lambda: self.loss_and_grads(batch, None, _lr=_lr, global_batch=global_batch)))
+            if again is not None:
+                return again
         self.ctx.set_lr_source(None)
         return batch
 
@@ -1247,15 +1299,8 @@ class GeneralGNN(_GraphRunner):
         """gcn.py:330-340 for the live model: forward(training=True), CCE, gradients, SGD, accuracy."""
         batch = self.loss_and_grads(inputs, target, _lr=float(lr), global_batch=global_batch)
         if not self._step_applied:
-            D.sgd(self.ctx, self.flat_p, self.flat_g.flat(0, self.n_params), lr)
-        n_graphs = global_batch or (self._counts["b"] if self._multi() else batch.n_graphs)
-        if fetch == "stash":
-            self.stash_metrics(n_graphs)
-            return None
-        if not fetch:
-            return None
-        la = self.loss_acc.numpy()
-        return float(la[0]), float(la[1]) / float(n_graphs)
+            self._apply_sgd(lr)
+        return self._finish_step(fetch, global_batch or self._global_graphs(batch))
 
     def evaluate_batch(self, inputs, target):
         batch = self._as_batch(inputs, target)
@@ -1264,8 +1309,7 @@ class GeneralGNN(_GraphRunner):
         logits = self._forward(batch, bufs, False)
         self.loss_acc.fill_zero()
         D.softmax_cce(self.ctx, logits, batch.y, bufs["probs"], self.loss_acc, None, batch.n_graphs, cce=self.cce_eval)
-        la = self.loss_acc.numpy()
-        return float(la[0]), float(la[1]) / batch.n_graphs, (logits if self.activation is None else bufs["probs"]).numpy()
+        return (*self._loss_acc_host(batch.n_graphs), (logits if self.activation is None else bufs["probs"]).numpy())
 
     def gradients(self):
         return [{k[2:]: L[k].numpy() for k in L if k.startswith("g_")} for L in self.layers]
@@ -1369,19 +1413,7 @@ class GCN(_GraphRunner):
         self.f_in = int(f_in)
         # every parameter starts on a 16-byte boundary (the one-launch GCNConv reads W and b as float4); the padding
         # floats have zero gradients, so the single SGD launch over the whole buffer leaves them at zero
-        offs, off = {}, 0
-        for k in self.PARAM_ORDER:
-            offs[k] = off
-            off += -(-int(np.prod(shapes[k])) // 4) * 4
-        self.n_params = off
-        self.flat_p = self.ctx.zeros(self.n_params)
-        self.flat_g = self.ctx.zeros(self.n_params + 2)
-        self.p, self.g = {}, {}
-        for k in self.PARAM_ORDER:
-            n = int(np.prod(shapes[k]))
-            self.p[k] = self.flat_p.flat(offs[k], n, shapes[k])
-            self.g[k] = self.flat_g.flat(offs[k], n, shapes[k])
-        self.loss_acc = self.flat_g.flat(self.n_params, 2)
+        self._alloc_flat([(k, shapes[k]) for k in self.PARAM_ORDER], align=4)
         rng, lim = self._rng, 1.0 / np.sqrt(h)
         init = {"w1": glorot_uniform(rng, f_in, h), "w2": glorot_uniform(rng, h, h),
                 "w3": rng.uniform(-lim, lim, (h, h)), "b3": rng.uniform(-lim, lim, h),
@@ -1428,20 +1460,13 @@ class GCN(_GraphRunner):
     def trainable_variables(self):
         return [self.p[k] for _, k, _ in self.TORCH_KEYS]
 
-    @property
-    def losses(self):
-        return []
-
     # ---- batches ------------------------------------------------------------------------------------------------------
     def _as_batch(self, inputs, target=None):
-        if isinstance(inputs, DeviceBatch):
-            if target is not None and inputs.y is None:
-                inputs.y = self.ctx.to_device(target, np.float32)
-            return inputs
-        x, a, i = _without_e(inputs)
-        if not isinstance(a, D.DeviceCSR):
-            a = _with_remaining_self_loops(a, np.asarray(x).shape[0])
-        return DeviceBatch.from_host(self.ctx, (x, a, i), target, weighted=False)
+        if not isinstance(inputs, DeviceBatch):
+            x, a, i = _without_e(inputs)
+            if not isinstance(a, D.DeviceCSR):                   # a host matrix: PyG's add_remaining_self_loops
+                inputs = (x, _with_remaining_self_loops(a, np.asarray(x).shape[0]), i)
+        return self._adopt(inputs, target, weighted=False)
 
     def _op(self, batch):
         """A^ = D^-1/2 (A + I_missing) D^-1/2 of the batch, values ignored (built once per batch object)."""
@@ -1450,17 +1475,11 @@ class GCN(_GraphRunner):
             self._op_cache = (batch.uid, a_hat, a_hat.transpose())
         return self._op_cache[1], self._op_cache[2]
 
-    def _multi(self):
-        return self.comm is not None and self.comm.world_size > 1
-
     def _global_counts(self, batch):
         """(N, B) of the whole sharded batch: one host all-reduce per batch (cached by its uid).  Every rank raises the same
         ValueError when a rank holds no graph or the whole batch holds fewer than 2 graphs (or rows)."""
-        if getattr(self, "_counts_uid", None) != batch.uid:
-            tot = self.comm.allreduce_host([batch.n, batch.n_graphs, 1.0 if batch.n_graphs == 0 else 0.0], "sum")
-            self._counts = (float(tot[0]), float(tot[1]), int(tot[2]))
-            self._counts_uid = batch.uid
-        n, b, empty_ranks = self._counts
+        tot = self._global_counts_cached(batch, [batch.n, batch.n_graphs, 1.0 if batch.n_graphs == 0 else 0.0])
+        n, b, empty_ranks = tot["n"], tot["b"], int(tot["empty"])
         if b < 2 or n < 2:
             raise ValueError(f"Expected more than 1 value per channel when training, got input size [{int(b)}, {self.hidden}]: "
                              "BatchNorm1d(track_running_stats=False) needs at least 2 graphs per batch")
@@ -1481,9 +1500,7 @@ class GCN(_GraphRunner):
         key = (batch.n, batch.n_graphs) + (("sync-BN",) if sharded else ())
         if self._bufs is not None and self._bufs["key"] == key:
             return self._bufs
-        if getattr(self, "_cap", None) is None:
-            self._cap = _Capacity(self.ctx)
-        v, n, b, h = self._cap.view, batch.n, batch.n_graphs, self.hidden
+        v, n, b, h = self._views(), batch.n, batch.n_graphs, self.hidden
         bufs = {"key": key}
         for k in ("h1", "z1", "y1", "z2", "y2", "dz2", "t", "dy1", "dz1", "s2"):
             bufs[k] = v(k, n, h)
@@ -1641,7 +1658,7 @@ class GCN(_GraphRunner):
         if counts is not None:
             self.comm.allreduce_sum(self.flat_g)
         if _lr is not None:
-            D.sgd(self.ctx, self.flat_p, self.flat_g.flat(0, self.n_params), _lr)
+            self._apply_sgd(_lr)
         self._last_batch = batch
         return batch
 
@@ -1649,25 +1666,14 @@ class GCN(_GraphRunner):
         """One optimisation step: loss, gradients, p -= lr * g.  fetch: True -> (loss, acc); False -> None; "stash" ->
         None, metrics kept on the device for collect_metrics()."""
         batch = self.loss_and_grads(inputs, target, global_batch, _lr=float(lr))
-        n_graphs = global_batch or (self._counts[1] if self._multi() else batch.n_graphs)
-        if fetch == "stash":
-            self.stash_metrics(n_graphs)
-            return None
-        if not fetch:
-            return None
-        return self.fetch_metrics(n_graphs)
-
-    def fetch_metrics(self, n_graphs):
-        la = self.loss_acc.numpy()
-        return float(la[0]), float(la[1]) / float(n_graphs)
+        return self._finish_step(fetch, global_batch or self._global_graphs(batch))
 
     def evaluate_batch(self, inputs, target):
         """(loss, accuracy, probabilities [B, 1]) without gradients (BatchNorm on batch statistics, as torch's eval here)."""
         batch = self._as_batch(inputs, target)
         bufs = self._ensure(batch)
         self._forward(batch, bufs, "loss", float(batch.n_graphs))
-        la = self.loss_acc.numpy()
-        return float(la[0]), float(la[1]) / batch.n_graphs, bufs["probs"].numpy()
+        return (*self._loss_acc_host(batch.n_graphs), bufs["probs"].numpy())
 
 
 class ECCNet(_GraphRunner):
@@ -1769,21 +1775,12 @@ class ECCNet(_GraphRunner):
     def trainable_variables(self):
         return self.conv1.trainable_variables + self.conv2.trainable_variables + [self.p["dense_kernel"], self.p["dense_bias"]]
 
-    @property
-    def losses(self):
-        return []
-
     # ---- batches -------------------------------------------------------------------------------------------------------
     def _as_batch(self, inputs, target=None):
-        if isinstance(inputs, DeviceBatch):
-            if target is not None and inputs.y is None:
-                inputs.y = self.ctx.to_device(target, np.float32)
-            batch = inputs
-        else:
-            if len(inputs) != 4:
-                raise ValueError("gcnx.ECCNet takes (x, a, e, i): build the graphs with edge features (Graph(e=...), "
-                                 "from_networkx(use_edge_data='entries'))")
-            batch = DeviceBatch.from_host(self.ctx, inputs, target, weighted=False)
+        if not isinstance(inputs, DeviceBatch) and len(inputs) != 4:
+            raise ValueError("gcnx.ECCNet takes (x, a, e, i): build the graphs with edge features (Graph(e=...), "
+                             "from_networkx(use_edge_data='entries'))")
+        batch = self._adopt(inputs, target, weighted=False)
         if batch.e is None:
             raise ValueError("gcnx.ECCNet: the batch carries no edge features (DeviceBatch.e)")
         return batch
@@ -1796,9 +1793,7 @@ class ECCNet(_GraphRunner):
         key = (batch.n, batch.n_graphs)
         if self._bufs is not None and self._bufs["key"] == key:
             return self._bufs
-        if getattr(self, "_cap", None) is None:
-            self._cap = _Capacity(self.ctx)
-        v, n, b, h, c = self._cap.view, batch.n, batch.n_graphs, self.channels, self.n_labels
+        v, n, b, h, c = self._views(), batch.n, batch.n_graphs, self.channels, self.n_labels
         self._bufs = {"key": key, "y1": v("y1", n, h), "y2": v("y2", n, h), "dy2": v("dy2", n, h),
                       "pooled": v("pooled", b, h), "dpooled": v("dpooled", b, h), "probs": v("probs", b, c)}
         return self._bufs
@@ -1842,7 +1837,7 @@ class ECCNet(_GraphRunner):
         self._forward(batch, bufs, "grads", float(global_batch or batch.n_graphs))
         self._backward(batch, bufs)
         if _lr is not None:
-            D.sgd(self.ctx, self.flat_p, self.flat_g.flat(0, self.n_params), _lr)
+            self._apply_sgd(_lr)
         self._last_batch = batch
         return batch
 
@@ -1850,22 +1845,11 @@ class ECCNet(_GraphRunner):
         """One optimisation step (gcn.py:330-340): loss, gradients, p -= lr * g.  fetch: True -> (loss, acc); False -> None;
         "stash" -> None, metrics kept on the device for collect_metrics()."""
         batch = self.loss_and_grads(inputs, target, global_batch, _lr=float(lr))
-        n_graphs = global_batch or batch.n_graphs
-        if fetch == "stash":
-            self.stash_metrics(n_graphs)
-            return None
-        if not fetch:
-            return None
-        return self.fetch_metrics(n_graphs)
-
-    def fetch_metrics(self, n_graphs):
-        la = self.loss_acc.numpy()
-        return float(la[0]), float(la[1]) / float(n_graphs)
+        return self._finish_step(fetch, global_batch or batch.n_graphs)
 
     def evaluate_batch(self, inputs, target):
         """(loss, accuracy, probabilities) without gradients (the body of evaluate(), gcn.py:350-357; loss by cce_eval)."""
         batch = self._as_batch(inputs, target)
         bufs = self._ensure(batch)
         self._forward(batch, bufs, "loss", float(batch.n_graphs))
-        la = self.loss_acc.numpy()
-        return float(la[0]), float(la[1]) / batch.n_graphs, bufs["probs"].numpy()
+        return (*self._loss_acc_host(batch.n_graphs), bufs["probs"].numpy())

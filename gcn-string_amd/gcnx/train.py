@@ -42,9 +42,9 @@ def _as_batch(model, inputs, target, normalize):
     from .models import DeviceBatch
     if isinstance(inputs, DeviceBatch):
         return inputs
-    if len(inputs) == 4 and not getattr(model, "uses_edge_features", False):
-        inputs = (inputs[0], inputs[1], inputs[-1])       # (x, a, e, i) for a model that does not read e
-    return DeviceBatch.from_host(model.ctx, inputs, target, normalize=normalize)
+    # model._adopt, not model._as_batch: e dropped for a model that does not read it (uses_edge_features), the matrix uploaded as
+    # the loader gave it.  (GCN._as_batch adds the remaining self loops to a host matrix; fit / evaluate never did: kept so.)
+    return model._adopt(inputs, target, normalize=normalize)
 
 
 def evaluate(model, loader, normalize=None):

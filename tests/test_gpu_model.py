@@ -1547,3 +1547,78 @@ def test_config4_shards_of_the_1m_node_batch_sum_to_the_full_batch_step(ctx, pre
             off += sizes[k]
         assert abs(total[off] - full[off]) <= 2e-5 * abs(full[off]), (world, "loss")
         assert total[off + 1] == full[off + 1], (world, "#correct")
+
+
+_FALLBACK_TEXT = {
+    "gcn2": "gcnx: RCCL all-reduce could not be captured into the step graph (stub: not capturable); falling back to an eager "
+            "collective between two graphs",
+    "generalgnn": "gcnx: the sync-BN step could not be captured with its collectives (stub: not capturable); running it eagerly"}
+
+
+def _tiny_chain_batch(n_graphs=6, f=32, seed=4):
+    """Graphs of 5 to 12 nodes: a chain with +-1 / +-2 contacts, self loops, gcn_filter values."""
+    from gcnx import synth
+    rng = np.random.default_rng(seed)
+    sizes = rng.integers(5, 13, n_graphs)
+    gp = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+    us, vs = [], []
+    for g in range(n_graphs):
+        idx = np.arange(gp[g], gp[g + 1], dtype=np.int64)
+        for d in (1, 2):
+            us.append(idx[:-d]); vs.append(idx[d:])
+    rowptr, colidx = synth._csr_from_pairs(int(gp[-1]), np.concatenate(us), np.concatenate(vs))
+    x = rng.standard_normal((int(gp[-1]), f), dtype=np.float32)
+    return synth.HostBatch(x, rowptr, colidx, synth.gcn_norm_host(rowptr, colidx), gp, synth._labels(rng, n_graphs))
+
+
+@pytest.mark.parametrize("kind", ["gcn2", "generalgnn"])
+def test_capture_fallback_lands_on_the_three_part_step(ctx, kind, capsys):
+    """A communicator that says it can be captured and then cannot (its first collective inside the capturing call raises):
+    the model prints its message once, sets _comm_capture_failed, drops the graphs and runs that step -- and every later
+    one -- in the form it takes with a communicator that is not capturable from the start.  Weights, loss / hits and
+    gradients after four steps (eager, the failed capture, capture, replay) are those of that twin, bit for bit."""
+    import os, sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from thread_comm import StubCommunicator
+    from gcnx.device import DeviceCSR, Segments
+    from gcnx.models import DeviceBatch, GeneralGNN
+    hb = _tiny_chain_batch()
+    assert hb.n_graphs == 6 and 5 <= np.diff(hb.graph_ptr).min() and np.diff(hb.graph_ptr).max() <= 12
+
+    def run(capturable, fail_at):
+        a = DeviceCSR.from_host_csr(ctx, hb.rowptr, hb.colidx, hb.vals, hb.graph_ptr)
+        batch = DeviceBatch(ctx, ctx.to_device(hb.x), a, Segments(ctx, hb.graph_ptr), ctx.to_device(hb.y))
+        comm = StubCommunicator(capturable)
+        if kind == "gcn2":
+            m = GCN2(ctx, 2, hidden=32, seed=5, use_graph=True, comm=comm)
+        else:
+            m = GeneralGNN(ctx, 2, activation="softmax", hidden=16, message_passing=1, pre_process=1, post_process=1,
+                           use_graph=True, seed=5, comm=comm)
+            assert m.dropout == 0.0                       # (the default: neither twin draws anything)
+        for step in range(4):
+            comm.fail_once = step == fail_at
+            m.train_step(batch, None, lr=0.05, global_batch=12, fetch=False)
+            assert not comm.fail_once
+        return m, comm
+
+    capsys.readouterr()
+    ma, ca = run(True, 1)                                 # step 1 is the capturing call
+    err = capsys.readouterr().err
+    assert err.count(_FALLBACK_TEXT[kind]) == 1 and err.count("gcnx:") == 1, err
+    assert ma._comm_capture_failed is True
+    if kind == "gcn2":
+        assert not ma._comm_in_graph()
+    mb, cb = run(False, None)
+    assert not capsys.readouterr().err and not getattr(mb, "_comm_capture_failed", False)
+    # GCN2: graph | all-reduce | graph -- one collective per step, the one that raised is not counted; GeneralGNN: the
+    # eager warm-up ran the fused form once, with the same collectives in it as the eager form
+    assert ca.calls == cb.calls and (kind != "gcn2" or ca.calls == 4)
+    for wa, wb in zip(ma.get_weights(), mb.get_weights()):
+        assert np.array_equal(wa, wb)
+    assert np.array_equal(ma.loss_acc.numpy(), mb.loss_acc.numpy())
+    assert np.array_equal(ma.flat_g.numpy(), mb.flat_g.numpy())
+    ga, gb = ma.gradients(), mb.gradients()
+    if kind == "gcn2":
+        assert all(np.array_equal(ga[k], gb[k]) for k in ORDER)
+    else:
+        assert all(np.array_equal(la[k], lb[k]) for la, lb in zip(ga, gb) for k in la)

@@ -72,3 +72,29 @@ class ThreadCommunicator:
 
     def close(self):
         pass
+
+
+class StubCommunicator:
+    """One process posing as rank 0 of a world of two: every collective is the identity.  ``capturable`` is set by the
+    test (True: the models record their collectives into the step graph).  ``fail_once``: the next allreduce_sum raises
+    before it does anything -- a Python exception between two library calls, nothing on the device fails -- and the
+    switch clears itself: what a transport that cannot be captured after all looks like to the model."""
+    rank, world_size = 0, 2
+
+    def __init__(self, capturable):
+        self.capturable, self.fail_once, self.calls = capturable, False, 0
+
+    def allreduce_sum(self, arr, n=None):
+        if self.fail_once:
+            self.fail_once = False
+            raise RuntimeError("stub: not capturable")
+        self.calls += 1
+
+    def allreduce_host(self, values, op="max"):
+        return np.asarray(values, np.float32).ravel()
+
+    def barrier(self):
+        pass
+
+    def close(self):
+        pass
