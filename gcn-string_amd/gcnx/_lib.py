@@ -155,6 +155,8 @@ SIGNATURES = {
                                      _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _int, _vp],
     "gcnx_gemm_dw2": [_vp, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _i64, _int, _vp, _vp,
                       _i64, _f32, _vp, _vp],
+    "gcnx_sage_conv_ok": [_i64, _i32, _i32, _i64],
+    "gcnx_sage_conv": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _int, _vp, _vp, _i64, _vp, _i64],
     "gcnx_comm_unique_id": [C.c_char_p],
     "gcnx_comm_init_rank": [_vp, C.c_char_p, _int, _int, C.POINTER(_vp)],
     "gcnx_comm_destroy": [_vp],

@@ -774,6 +774,23 @@ def gcn_conv_fwd_pre(ctx, s, w, bias, out, act="relu", prec="f32"):
     return out
 
 
+def sage_conv_ok(ctx, n, fi, fo, ldx=None):
+    """True if sage_conv serves these shapes (gcnx_sage_conv_ok)."""
+    return bool(ctx.lib.gcnx_sage_conv_ok(int(n), int(fi), int(fo), int(ldx if ldx is not None else fi)))
+
+
+def sage_conv(ctx, a, x, w_nb, w_root, bias, out, s=None, w_transposed=False):
+    """out = (A x) w_nb + x w_root + bias in one launch; s (optional) receives A x (gcnx_sage_conv).  w_transposed: both
+    weights are [fo, fi] -- the backward form dX = (A^T dZ) W_nb^T + dZ W_root^T with the layer's weights as stored."""
+    n, fi = x.shape
+    fo = w_nb.shape[0] if w_transposed else w_nb.shape[1]
+    assert a.n == n and w_nb.shape == w_root.shape == ((fo, fi) if w_transposed else (fi, fo)) and w_nb.contiguous and w_root.contiguous
+    assert out.shape == (n, fo) and (s is None or s.shape == (n, fi)) and (bias is None or bias.shape == (fo,))
+    ctx._ck(ctx.lib.gcnx_sage_conv(ctx.h, a.rowptr.ptr, a.colidx.ptr, _p(a.vals), _p(x), x.ld, n, fi, _p(w_nb), _p(w_root), fo,
+                                   1 if w_transposed else 0, _p(bias), _p(s), s.ld if s is not None else 0, _p(out), out.ld))
+    return out
+
+
 def to_bf16(ctx, x):
     """bf16 copy (uint16 bit patterns, round to nearest even) of a contiguous fp32 array (gcnx_f32_to_bf16)."""
     assert x.contiguous and x.dtype == np.float32

@@ -5,6 +5,8 @@ kernel_initializer="glorot_uniform", bias_initializer="zeros")`` called as ``lay
 ``GCNConv.preprocess(a)``; ``GlobalSumPool()([x, i])`` (+ Avg/Max); ``Dense(units, activation)``.
 Reference topology: GCNConv -> GCNConv -> global pool -> Linear (gcn_utills.py:805-808,
 832-842); live model ctor gcn.py:320, forward gcn.py:334/351, gradients gcn.py:337.
+``SAGEConv(channels, root_weight=True, use_bias=True)`` is PyG's layer of that name (aggr="mean"), which the reference
+names as its next step (gcn_utills.py:804-806).
 
 There is no autograd here: every layer has ``backward(dy)`` that returns dx and leaves the
 parameter gradients in ``layer.grads`` (what tape.gradient, gcn.py:337, would produce).
@@ -168,6 +170,94 @@ class GCNConv(Layer):
             return None
         dx = self._buf("dx", (n, self.in_dim))
         D.gemm_dx(self.ctx, dh, self.params["kernel"], dx, prec=self.prec)
+        return dx
+
+
+def _aligned16(*arrays):
+    return all(a is None or a.ptr % 16 == 0 for a in arrays)
+
+
+class SAGEConv(Layer):
+    """torch_geometric.nn.SAGEConv(in, channels, aggr="mean"), the layer the reference's torch model names as its next step
+    (gcn_utills.py:804-806):   out_i = mean_{j in N(i)} x_j W_l + b + x_i W_r
+
+    ``SAGEConv(channels, root_weight=True, use_bias=True, activation=None)``, called as ``layer([x, a_mean])`` with
+    ``a_mean = SAGEConv.preprocess(a)``: the stored pattern of ``a`` with 1 / (entries of the row) on every entry -- the
+    adjacency is used exactly as stored, no loop is added or removed, values are ignored; a row without entries
+    aggregates to 0.  Parameters under PyG's names and in its named_parameters() order: ``lin_l.weight``, ``lin_l.bias``,
+    ``lin_r.weight``; the weights are stored [in, channels] (PyG: [channels, in]), initialised U(+-1/sqrt(in)) as torch's
+    Linear.  ``backward(dy)`` returns dx and leaves the three gradients in ``grads``.
+
+    One launch per direction where gcnx_sage_conv serves the shapes (csrc/sage.hip): the forward keeps S = A x, both weight
+    gradients are one gcnx_gemm_dw2 (S^T dY, x^T dY), dx is the same kernel on the transposed operator with the weights as
+    stored.  Otherwise (root_weight=False, widths the kernel refuses) the composed route: gcnx_spmm_csr, gcnx_gemm
+    (twice, + gcnx_add) forward; gcnx_gemm_dx, gcnx_spmm_csr, gcnx_gemm_dx(accumulate) backward."""
+
+    def __init__(self, channels, root_weight=True, use_bias=True, activation=None, fused=True, **kw):
+        super().__init__(**kw)
+        if activation not in (None, "linear"):
+            raise NotImplementedError(f"SAGEConv activation {activation!r}: the layer is linear (follow it with BatchNorm1d / PReLU)")
+        self.channels, self.root_weight, self.use_bias, self.activation = int(channels), bool(root_weight), bool(use_bias), activation
+        self.fused = bool(fused)
+
+    @staticmethod
+    def preprocess(a):
+        """The row-mean operator of a DeviceCSR: same pattern, 1 / (entries of the row) on every entry."""
+        return a.unweighted().row_mean()
+
+    def _param_spec(self, in_dim):
+        lim, c = 1.0 / np.sqrt(in_dim), self.channels
+        u = lambda *s: self._rng.uniform(-lim, lim, s).astype(np.float32)
+        spec = [("lin_l.weight", (in_dim, c), u(in_dim, c))]
+        if self.use_bias:
+            spec.append(("lin_l.bias", (c,), u(c)))
+        if self.root_weight:
+            spec.append(("lin_r.weight", (in_dim, c), u(in_dim, c)))
+        return spec
+
+    def _one_launch(self, x, fo, *others):
+        return (self.fused and self.root_weight and D.sage_conv_ok(self.ctx, x.shape[0], x.shape[1], fo, x.ld)
+                and _aligned16(x, self.params["lin_l.weight"], self.params["lin_r.weight"], *others))
+
+    def call(self, inputs, out=None):
+        x, a = inputs
+        if not self.built:
+            self.build(x.ctx, x.shape[1])
+        ctx, n, c, p = self.ctx, x.shape[0], self.channels, self.params
+        y = out if out is not None else self._buf("y", (n, c))
+        s = self._buf("s", (n, x.shape[1]))
+        if self._one_launch(x, c, y, s):
+            D.sage_conv(ctx, a, x, p["lin_l.weight"], p["lin_r.weight"], p.get("lin_l.bias"), y, s=s)
+        else:
+            D.spmm(ctx, a, x, None, s)
+            D.gemm(ctx, s, p["lin_l.weight"], p.get("lin_l.bias"), y)
+            if self.root_weight:
+                h = self._buf("h", (n, c))
+                D.gemm(ctx, x, p["lin_r.weight"], None, h)
+                D.add(ctx, y, h, y)
+        self._saved = (x, a, s)
+        return y
+
+    def backward(self, dy, need_dx=True):
+        x, a, s = self._saved
+        ctx, p, g = self.ctx, self.params, self.grads
+        if self.use_bias:
+            D.act_bias_grad(ctx, dy, None, dy, None, db=g["lin_l.bias"])            # column sums of dy
+        if self.root_weight:
+            D.gemm_dw2(ctx, s, dy, g["lin_l.weight"], x, dy, g["lin_r.weight"])      # dW_l = S^T dY, dW_r = x^T dY
+        else:
+            D.gemm_dw(ctx, s, dy, g["lin_l.weight"])
+        if not need_dx:
+            return None
+        dx = self._buf("dx", x.shape)
+        if self._one_launch(dy, self.in_dim, dx):
+            D.sage_conv(ctx, a.transpose(), dy, p["lin_l.weight"], p["lin_r.weight"], None, dx, w_transposed=True)
+            return dx
+        t = self._buf("t", x.shape)
+        D.gemm_dx(ctx, dy, p["lin_l.weight"], t)
+        D.spmm(ctx, a.transpose(), t, None, dx)                                     # A^T (dY W_l^T)
+        if self.root_weight:
+            D.gemm_dx(ctx, dy, p["lin_r.weight"], dx, accumulate=True)              # + dY W_r^T
         return dx
 
 

@@ -12,6 +12,9 @@ is captured into a HIP graph (the role tf.function plays at gcn.py:328) and repl
 
 ``GCN``: the reference's torch class (gcn_utills.py:795-853): GCNConv·BatchNorm1d·PReLU twice, global_max_pool,
 Linear·BatchNorm1d·PReLU twice, one logit with BCEWithLogitsLoss (eager launches).
+
+``SAGE``: ``GCN`` with PyG's SAGEConv(aggr="mean") in the place of both GCNConv layers, the step the reference's author notes
+above them (gcn_utills.py:804-806); one launch per convolution (csrc/sage.hip).
 """
 from __future__ import annotations
 
@@ -1368,6 +1371,7 @@ class GCN(_GraphRunner):
                   ("batch_norm_2.weight", "g2", False), ("batch_norm_2.bias", "be2", False),
                   ("batch_norm_3.weight", "g3", False), ("batch_norm_3.bias", "be3", False),
                   ("batch_norm_4.weight", "g4", False), ("batch_norm_4.bias", "be4", False))
+    PROBE_KEY = "conv1.lin.weight"       # the state_dict tensor whose second dimension is the input width
     EPS = D.TORCH_BN_EPS
 
     def __init__(self, *args, **kw):
@@ -1433,7 +1437,7 @@ class GCN(_GraphRunner):
     def load_state_dict(self, d):
         """Inverse of state_dict (a converted torch checkpoint: tensors as NumPy arrays).  Builds the model if needed."""
         if not self.built:
-            self.build(int(np.asarray(d["conv1.lin.weight"]).shape[1]))
+            self.build(int(np.asarray(d[self.PROBE_KEY]).shape[1]))
         missing = [tk for tk, _, _ in self.TORCH_KEYS if tk not in d]
         if missing:
             raise KeyError(f"gcnx.GCN.load_state_dict: missing {missing}")
@@ -1530,6 +1534,36 @@ class GCN(_GraphRunner):
         D.spmm(ctx, a_hat, h_tmp, bias, out)
         return False
 
+    # the two convolutions of the forward and their backward segments: what a subclass with another convolution replaces
+    def _conv1(self, a_hat, batch, bufs, mode):
+        p = self.p
+        self._conv(a_hat, batch.x, p["w1"], p["b1"], bufs["z1"], bufs["h1"])
+
+    def _conv2(self, a_hat, bufs, mode):
+        p = self.p
+        bufs["s2_ok"] = self._conv(a_hat, bufs["y1"], p["w2"], p["b2"], bufs["z2"], bufs["h1"],
+                                   s=bufs["s2"] if mode == "grads" else None)
+
+    def _conv2_bwd(self, a_t, bufs):
+        """dZ2 -> conv2's gradients and dY1."""
+        ctx, p, g = self.ctx, self.p, self.g
+        D.act_bias_grad(ctx, bufs["dz2"], None, bufs["dz2"], None, db=g["b2"])       # conv2.bias: column sums of dZ2
+        if bufs["s2_ok"]:                                   # forward was (A^ Y1) W2: the association of GCNConv.backward
+            D.gemm_dw(ctx, bufs["s2"], bufs["dz2"], g["w2"])                        # dW2 = S2^T dZ2
+            D.gemm_dx(ctx, bufs["dz2"], p["w2"], bufs["t"])                         # dZ2 W2^T
+            D.spmm(ctx, a_t, bufs["t"], None, bufs["dy1"])                          # dY1 = A^T (dZ2 W2^T)
+        else:
+            D.spmm(ctx, a_t, bufs["dz2"], None, bufs["t"])                          # A^T dZ2
+            D.gemm_dw(ctx, bufs["y1"], bufs["t"], g["w2"])                          # dW2 = Y1^T (A^T dZ2)
+            D.gemm_dx(ctx, bufs["t"], p["w2"], bufs["dy1"])                         # dY1 = (A^T dZ2) W2^T
+
+    def _conv1_bwd(self, a_t, batch, bufs):
+        """dZ1 -> conv1's gradients (the input carries no gradient)."""
+        ctx, g = self.ctx, self.g
+        D.act_bias_grad(ctx, bufs["dz1"], None, bufs["dz1"], None, db=g["b1"])
+        D.spmm(ctx, a_t, bufs["dz1"], None, bufs["t"])
+        D.gemm_dw(ctx, batch.x, bufs["t"], g["w1"])
+
     def _moments(self, z, mean, inv, bufs, counts):
         """Training-mode BatchNorm statistics over the rows of z; with counts (sync-BN) over every rank's rows: the two moment
         passes with their column sums all-reduced and the global row count."""
@@ -1550,11 +1584,10 @@ class GCN(_GraphRunner):
         global (N, B) of a sync-BN training step over graph shards (None: this batch's own statistics)."""
         ctx, p, e = self.ctx, self.p, self.EPS
         a_hat, _ = self._op(batch)
-        self._conv(a_hat, batch.x, p["w1"], p["b1"], bufs["z1"], bufs["h1"])
+        self._conv1(a_hat, batch, bufs, mode)
         self._moments(bufs["z1"], bufs["m1"], bufs["i1"], bufs, counts)
         D.bn_act(ctx, bufs["z1"], bufs["m1"], bufs["i1"], p["g1"], p["be1"], bufs["y1"], act="prelu_shared", alpha=p["a1"])
-        bufs["s2_ok"] = self._conv(a_hat, bufs["y1"], p["w2"], p["b2"], bufs["z2"], bufs["h1"],
-                                   s=bufs["s2"] if mode == "grads" else None)
+        self._conv2(a_hat, bufs, mode)
         self._moments(bufs["z2"], bufs["m2"], bufs["i2"], bufs, counts)
         if self._bn_pool:
             D.bn_act_pool(ctx, batch.seg, bufs["z2"], bufs["m2"], bufs["i2"], p["g2"], p["be2"], bufs["pooled"], bufs["arg"],
@@ -1607,20 +1640,10 @@ class GCN(_GraphRunner):
             D.segment_pool_bwd(ctx, batch.seg, bufs["dpooled"], bufs["y2"], "max", bufs["arg"])
             self._bn_bwd(bufs["y2"], bufs["z2"], bufs["m2"], bufs["i2"], p["g2"], p["be2"], p["a2"], bufs["dz2"], g["g2"], g["be2"],
                          g["a2"], bufs, counts)
-        D.act_bias_grad(ctx, bufs["dz2"], None, bufs["dz2"], None, db=g["b2"])       # conv2.bias: column sums of dZ2
-        if bufs["s2_ok"]:                                   # forward was (A^ Y1) W2: the association of GCNConv.backward
-            D.gemm_dw(ctx, bufs["s2"], bufs["dz2"], g["w2"])                        # dW2 = S2^T dZ2
-            D.gemm_dx(ctx, bufs["dz2"], p["w2"], bufs["t"])                         # dZ2 W2^T
-            D.spmm(ctx, a_t, bufs["t"], None, bufs["dy1"])                          # dY1 = A^T (dZ2 W2^T)
-        else:
-            D.spmm(ctx, a_t, bufs["dz2"], None, bufs["t"])                          # A^T dZ2
-            D.gemm_dw(ctx, bufs["y1"], bufs["t"], g["w2"])                          # dW2 = Y1^T (A^T dZ2)
-            D.gemm_dx(ctx, bufs["t"], p["w2"], bufs["dy1"])                         # dY1 = (A^T dZ2) W2^T
+        self._conv2_bwd(a_t, bufs)
         self._bn_bwd(bufs["dy1"], bufs["z1"], bufs["m1"], bufs["i1"], p["g1"], p["be1"], p["a1"], bufs["dz1"], g["g1"], g["be1"],
                      g["a1"], bufs, counts)
-        D.act_bias_grad(ctx, bufs["dz1"], None, bufs["dz1"], None, db=g["b1"])
-        D.spmm(ctx, a_t, bufs["dz1"], None, bufs["t"])
-        D.gemm_dw(ctx, batch.x, bufs["t"], g["w1"])
+        self._conv1_bwd(a_t, batch, bufs)
 
     # ---- public surface ---------------------------------------------------------------------------------------------
     def __call__(self, inputs, training=False):
@@ -1674,6 +1697,127 @@ class GCN(_GraphRunner):
         bufs = self._ensure(batch)
         self._forward(batch, bufs, "loss", float(batch.n_graphs))
         return (*self._loss_acc_host(batch.n_graphs), bufs["probs"].numpy())
+
+
+class SAGE(GCN):
+    """``GCN`` with its two GCNConv layers replaced by PyG's SAGEConv(aggr="mean"), the step the reference's author notes above
+    them ("consider using class SAGEConv instead", gcn_utills.py:804-806):
+
+        SAGEConv(F->H)·BN·PReLU -> SAGEConv(H->H)·BN·PReLU -> global_max_pool -> Linear(H->H)·BN·PReLU -> Linear(H->1)·BN·PReLU
+
+    out_i = mean_{j in N(i)} x_j W_l + b + x_i W_r on the adjacency exactly as stored: no self-loop is added or removed, values
+    are ignored, a node without stored entries aggregates to 0.  ``forward(x, edge_index, batch)`` counts duplicate edges
+    once, as ``GCN`` does (PyG would count them twice in the mean: a deviation).  Everything behind the convolutions is
+    ``GCN``'s: BN·PReLU, the fused max-pool pair, the one-launch BCE head, sync-BN over shards (``comm=``), ``fit``.
+
+    Hot path: gcnx_sage_conv, one launch per convolution and one for conv2's dX (csrc/sage.hip), gcnx_gemm_dw2 for each
+    layer's two weight gradients.  GCNX_SAGE_FUSED=0 (read at construction), and any shape gcnx_sage_conv refuses (hidden >
+    128), takes the composed route instead: gcnx_spmm_csr, gcnx_gemm twice, gcnx_add; gcnx_gemm_dx, gcnx_spmm_csr,
+    gcnx_gemm_dx(accumulate) backward.
+
+    Weights: torch key names ``conv{1,2}.lin_l.weight``, ``conv{1,2}.lin_l.bias``, ``conv{1,2}.lin_r.weight`` in
+    ``state_dict()`` ([out, in], as torch; stored [in, out] here), listed by ``get_weights()`` in PyG 2.x's
+    named_parameters() order (lin_l before lin_r).  Initialisation U(+-1/sqrt(fan_in)) as torch's Linear.  Neither the
+    order nor the initialisation was confirmed against a live torch_geometric: prefer the named dicts."""
+
+    PARAM_ORDER = ("wl1", "b1", "wr1", "g1", "be1", "a1", "wl2", "b2", "wr2", "g2", "be2", "a2",
+                   "w3", "b3", "g3", "be3", "a3", "w4", "b4", "g4", "be4", "a4")
+    TORCH_KEYS = (("conv1.lin_l.weight", "wl1", True), ("conv1.lin_l.bias", "b1", False), ("conv1.lin_r.weight", "wr1", True),
+                  ("conv2.lin_l.weight", "wl2", True), ("conv2.lin_l.bias", "b2", False), ("conv2.lin_r.weight", "wr2", True)) + \
+        GCN.TORCH_KEYS[4:]
+    PROBE_KEY = "conv1.lin_l.weight"
+
+    def _init(self, ctx, hidden_channels=64, num_classes=1, seed=0, comm=None):
+        super()._init(ctx, hidden_channels, num_classes, seed, comm)
+        self._fused = os.environ.get("GCNX_SAGE_FUSED", "1") != "0"    # knob, read once
+
+    def _shapes(self, f_in):
+        h = self.hidden
+        s = super()._shapes(f_in)
+        del s["w1"], s["w2"]
+        s.update(wl1=(f_in, h), wr1=(f_in, h), wl2=(h, h), wr2=(h, h))
+        return s
+
+    def build(self, f_in):
+        h = self.hidden
+        if h > 256:
+            raise NotImplementedError("gcnx.SAGE: hidden_channels <= 256 (the one-workgroup head)")
+        shapes = self._shapes(f_in)
+        self.f_in = int(f_in)
+        # every parameter starts on a 16-byte boundary (gcnx_sage_conv needs its weights there); the padding floats have zero
+        # gradients, so the single SGD launch over the whole buffer leaves them at zero
+        self._alloc_flat([(k, shapes[k]) for k in self.PARAM_ORDER], align=4)
+        rng = self._rng
+        u = lambda fan_in, *s: rng.uniform(-1.0 / np.sqrt(fan_in), 1.0 / np.sqrt(fan_in), s)
+        init = {"wl1": u(f_in, f_in, h), "b1": u(f_in, h), "wr1": u(f_in, f_in, h),
+                "wl2": u(h, h, h), "b2": u(h, h), "wr2": u(h, h, h),
+                "w3": u(h, h, h), "b3": u(h, h), "w4": u(h, 1, h), "b4": u(h, 1)}
+        for k in ("g1", "g2", "g3", "g4"):
+            init[k] = np.ones(shapes[k])
+        for k in ("a1", "a2", "a3", "a4"):
+            init[k] = np.full(1, 0.25)
+        for k, v in init.items():
+            self.p[k].copy_from_host(np.asarray(v, np.float32))
+        self.built = True
+
+    def _as_batch(self, inputs, target=None):
+        return self._adopt(inputs, target, weighted=False)       # the adjacency as stored: no loops added
+
+    def _op(self, batch):
+        """The row-mean operator of the batch and its transpose (built once per batch object)."""
+        if self._op_cache is None or self._op_cache[0] != batch.uid:
+            a_mean = batch.a.unweighted().row_mean()
+            self._op_cache = (batch.uid, a_mean, a_mean.transpose())
+        return self._op_cache[1], self._op_cache[2]
+
+    def _ensure(self, batch, sharded=False):
+        bufs = super()._ensure(batch, sharded)
+        if "s1" not in bufs:
+            bufs["s1"] = self._views()("s1", batch.n, batch.f)
+        return bufs
+
+    def _one_launch(self, x, fo, *others):
+        return (self._fused and D.sage_conv_ok(self.ctx, x.shape[0], x.shape[1], fo, x.ld)
+                and all(a.ptr % 16 == 0 for a in (x,) + others))
+
+    def _conv(self, a_mean, x, w_nb, w_root, bias, out, s, h_tmp):
+        """out = (A x) W_nb + x W_root + b, s = A x (the operand of dW_nb): one launch, or the composed route."""
+        ctx = self.ctx
+        if self._one_launch(x, w_nb.shape[1], out, s):
+            D.sage_conv(ctx, a_mean, x, w_nb, w_root, bias, out, s=s)
+            return
+        D.spmm(ctx, a_mean, x, None, s)
+        D.gemm(ctx, s, w_nb, bias, out)
+        D.gemm(ctx, x, w_root, None, h_tmp)
+        D.add(ctx, out, h_tmp, out)
+
+    def _conv1(self, a_mean, batch, bufs, mode):
+        p = self.p
+        self._conv(a_mean, batch.x, p["wl1"], p["wr1"], p["b1"], bufs["z1"], bufs["s1"], bufs["h1"])
+
+    def _conv2(self, a_mean, bufs, mode):
+        p = self.p
+        self._conv(a_mean, bufs["y1"], p["wl2"], p["wr2"], p["b2"], bufs["z2"], bufs["s2"], bufs["h1"])
+
+    def _conv2_bwd(self, a_t, bufs):
+        """dZ2 -> conv2's gradients and dY1 = (A^T dZ2) W_l2^T + dZ2 W_r2^T."""
+        ctx, p, g = self.ctx, self.p, self.g
+        dz2 = bufs["dz2"]
+        D.act_bias_grad(ctx, dz2, None, dz2, None, db=g["b2"])                      # conv2.lin_l.bias: column sums of dZ2
+        D.gemm_dw2(ctx, bufs["s2"], dz2, g["wl2"], bufs["y1"], dz2, g["wr2"])        # dW_l2 = S2^T dZ2, dW_r2 = Y1^T dZ2
+        if self._one_launch(dz2, self.hidden, bufs["dy1"]):
+            D.sage_conv(ctx, a_t, dz2, p["wl2"], p["wr2"], None, bufs["dy1"], w_transposed=True)
+            return
+        D.gemm_dx(ctx, dz2, p["wl2"], bufs["t"])
+        D.spmm(ctx, a_t, bufs["t"], None, bufs["dy1"])
+        D.gemm_dx(ctx, dz2, p["wr2"], bufs["dy1"], accumulate=True)
+
+    def _conv1_bwd(self, a_t, batch, bufs):
+        """dZ1 -> conv1's gradients (the input carries no gradient)."""
+        ctx, g = self.ctx, self.g
+        dz1 = bufs["dz1"]
+        D.act_bias_grad(ctx, dz1, None, dz1, None, db=g["b1"])
+        D.gemm_dw2(ctx, bufs["s1"], dz1, g["wl1"], batch.x, dz1, g["wr1"])           # dW_l1 = S1^T dZ1, dW_r1 = x^T dZ1
 
 
 class ECCNet(_GraphRunner):

@@ -747,6 +747,27 @@ GCNX_API int gcnx_gemm_dw2(gcnx_ctx* ctx, const float* xa, int64_t ldxa, const f
                       float* dwb, int32_t fib, int32_t fob, int64_t n, int prec, float* params, float* grads,
                       int64_t n_params, float lr, const gcnx_pending_reduce* pending, const gcnx_head_args* leaf);
 
+/* ---- SAGEConv as one launch, small-feature regime (F <= 128) ---------------------------------------------------
+ * The GraphSAGE layer the reference's torch model names as its next step ("consider using class SAGEConv instead",
+ * gcn_utills.py:804-806): out = mean_{j in N(i)} x_j W_nb + x_i W_root + b, evaluated as [A x | x] [W_nb ; W_root] so that one
+ * workgroup owns 32 rows from the neighbour gather to the bias -- one launch instead of gcnx_spmm_csr + two gcnx_gemm +
+ * gcnx_add and no [N, F] intermediate between them.  fp32, exact fp32 products on the fp32 MFMA, no atomics: the same
+ * bits on every call.  Nothing is allocated: the call can be captured.
+ * gcnx_sage_conv_ok: 1 if the shapes are served (fi in {16, 32, 64, 128}, fo a multiple of 16 up to 128, ldx >= fi,
+ * ldx % 4 == 0, n * ldx * 4 < 2^32); gcnx_sage_conv returns GCNX_ERR_UNSUPPORTED otherwise, and for x, w_nb, w_root, s or out
+ * off a 16-byte boundary (lds >= fi, ldo >= fo, both multiples of 4 floats), with nothing launched -- use the four calls then. */
+GCNX_API int gcnx_sage_conv_ok(int64_t n, int32_t fi, int32_t fo, int64_t ldx);
+/* out[n, fo] = (A x) w_nb + x w_root + bias, A in CSR with per-entry vals (NULL: all ones) -- the row-mean operator and its
+ * transpose are passed as values, like every other aggregation here.  bias may be NULL.  s (may be NULL) receives
+ * S = A x [n, fi], the operand of dW_nb = S^T dZ (dW_root = x^T dZ: both are one gcnx_gemm_dw2).  A row without entries
+ * gets an S row of exact zeros and out = x w_root + bias.  w_transposed == 0: both weights [fi, fo], row-major and
+ * contiguous; w_transposed == 1: both [fo, fi] -- the layer's backward then passes its weights as stored:
+ * dX = (A^T dZ) W_nb^T + dZ W_root^T is this call with x = dZ, A = the transposed operator, fi = the layer's output width
+ * and fo = its input width.  n == 0 succeeds and writes nothing. */
+GCNX_API int gcnx_sage_conv(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, const float* vals,
+                      const float* x, int64_t ldx, int32_t n, int32_t fi, const float* w_nb, const float* w_root,
+                      int32_t fo, int w_transposed, const float* bias, float* s, int64_t lds, float* out, int64_t ldo);
+
 /* ---- aggregation with bf16 features ("fp32 and bf16 both reported") ----
  * out[t, :] = bf16(act(sum_e vals[e] * h[colidx[e], :] + bias)): GCNConv.call's / GeneralConv's aggregation (gcn.py:334) on
  * activations stored as bf16 (uint16_t bit patterns), fp32 accumulation, round-to-nearest-even on the way out; bias fp32
