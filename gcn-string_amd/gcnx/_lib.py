@@ -157,6 +157,11 @@ SIGNATURES = {
                       _i64, _f32, _vp, _vp],
     "gcnx_sage_conv_ok": [_i64, _i32, _i32, _i64],
     "gcnx_sage_conv": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _int, _vp, _vp, _i64, _vp, _i64],
+    "gcnx_topk_select_ok": [_i64, _i32],
+    "gcnx_topk_select": [_vp, _vp, _vp, _i32, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _vp],
+    "gcnx_topk_gather": [_vp, _vp, _i64, _vp, _vp, _i32, _i32, _int, _vp, _i64],
+    "gcnx_topk_bwd": [_vp, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _int, _vp, _i64, _vp, _i64, _vp],
+    "gcnx_csr_induce": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp],
     "gcnx_comm_unique_id": [C.c_char_p],
     "gcnx_comm_init_rank": [_vp, C.c_char_p, _int, _int, C.POINTER(_vp)],
     "gcnx_comm_destroy": [_vp],

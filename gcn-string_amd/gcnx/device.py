@@ -791,6 +791,69 @@ def sage_conv(ctx, a, x, w_nb, w_root, bias, out, s=None, w_transposed=False):
     return out
 
 
+def topk_select_ok(ctx, max_graph_rows, f):
+    """True if topk_select serves a batch whose largest graph has this many rows (gcnx_topk_select_ok)."""
+    return bool(ctx.lib.gcnx_topk_select_ok(int(max_graph_rows), int(f)))
+
+
+def topk_kept_ptr(graph_ptr_host, ratio):
+    """graph_ptr' of TopKPool(ratio): the prefix sums of k_g = ceil(ratio * n_g), in float64 on the host (an empty graph
+    keeps nothing) -- N' = graph_ptr'[-1] is known without reading anything back."""
+    n_g = np.diff(np.asarray(graph_ptr_host, np.int64))
+    k = np.minimum(np.ceil(np.float64(ratio) * n_g.astype(np.float64)).astype(np.int64), n_g)
+    return np.concatenate([[0], np.cumsum(np.maximum(k, 0))]).astype(np.int32)
+
+
+def topk_select(ctx, seg, kept_ptr, n_kept, x, p, y, idx, pos):
+    """y = x p / ||p||; idx = the kept rows (kept_ptr[g + 1] - kept_ptr[g] of graph g with the largest y, in row order),
+    pos = their new row numbers, -1 for dropped rows (gcnx_topk_select).  kept_ptr: int32[B + 1] on the device, n_kept its
+    last element (what idx has to hold).
+    NotImplementedError where the batch is not served (a graph of more than 16384 rows): there is no other route."""
+    n, f = x.shape
+    big = _max_block(seg.host)
+    assert seg.n == n and p.size == f and p.contiguous and y.shape == (n,) and pos.shape == (n,) and kept_ptr.shape == (seg.n_graphs + 1,)
+    assert y.dtype == np.float32 and idx.dtype == np.int32 and pos.dtype == np.int32 and kept_ptr.dtype == np.int32
+    assert 0 <= n_kept <= n and idx.size >= n_kept
+    if not topk_select_ok(ctx, big, f):
+        raise NotImplementedError(f"gcnx_topk_select: a graph of {big} rows (f={f}) is not served (one workgroup ranks a graph: up to 16384 rows)")
+    ctx._ck(ctx.lib.gcnx_topk_select(ctx.h, seg.dev.ptr, kept_ptr.ptr, seg.n_graphs, big, _p(x), x.ld, f, _p(p), y.ptr, idx.ptr, pos.ptr))
+    return y, idx, pos
+
+
+def topk_gather(ctx, x, y, idx, n_kept, out, sigmoid_gating=False):
+    """out[r] = x[idx[r]] * gate(y[idx[r]]) for r < n_kept (gcnx_topk_gather); gate = tanh, or sigmoid."""
+    f = x.shape[1]
+    assert out.shape == (n_kept, f) and idx.dtype == np.int32 and idx.size >= n_kept and y.shape == (x.shape[0],)
+    ctx._ck(ctx.lib.gcnx_topk_gather(ctx.h, _p(x), x.ld, _p(y), idx.ptr, int(n_kept), f, 1 if sigmoid_gating else 0, _p(out), out.ld))
+    return out
+
+
+def topk_bwd(ctx, x, y, pos, p, dxo, dx, dp, sigmoid_gating=False):
+    """dx (every row: zeros for dropped rows) and dp from dxo = dLoss / dX' (gcnx_topk_bwd)."""
+    n, f = x.shape
+    assert dx.shape == (n, f) and dxo.shape[1] == f and pos.shape == (n,) and pos.dtype == np.int32 and p.size == f and dp.size == f
+    assert p.contiguous and dp.contiguous
+    ctx._ck(ctx.lib.gcnx_topk_bwd(ctx.h, _p(x), x.ld, _p(y), pos.ptr, _p(p), n, f, 1 if sigmoid_gating else 0, _p(dxo), dxo.ld,
+                                  _p(dx), dx.ld, _p(dp)))
+    return dx, dp
+
+
+def csr_induce(ctx, a, idx, pos, n_kept, rowptr_out, colidx_out, vals_out=None):
+    """A[idx][:, idx] of a DeviceCSR into the given arrays (gcnx_csr_induce): rowptr_out int32[n_kept + 1], colidx_out /
+    vals_out with room for a.nnz entries.  Nothing is read back: nnz' is rowptr_out[n_kept]."""
+    assert rowptr_out.size >= n_kept + 1 and colidx_out.size >= a.nnz and (a.vals is None) == (vals_out is None)
+    assert idx.dtype == np.int32 and pos.dtype == np.int32 and pos.shape == (a.n,) and rowptr_out.dtype == colidx_out.dtype == np.int32
+    ctx._ck(ctx.lib.gcnx_csr_induce(ctx.h, a.rowptr.ptr, a.colidx.ptr, _p(a.vals), idx.ptr, pos.ptr, int(n_kept), rowptr_out.ptr,
+                                    colidx_out.ptr, _p(vals_out)))
+
+
+def read_int32(ctx, arr, index):
+    """One int32 of a device array on the host: a 4-byte copy, which waits for the stream (gcnx_d2h)."""
+    out = np.empty(1, np.int32)
+    ctx._ck(ctx.lib.gcnx_d2h(ctx.h, out.ctypes.data, arr.ptr + 4 * int(index), 4))
+    return int(out[0])
+
+
 def to_bf16(ctx, x):
     """bf16 copy (uint16 bit patterns, round to nearest even) of a contiguous fp32 array (gcnx_f32_to_bf16)."""
     assert x.contiguous and x.dtype == np.float32

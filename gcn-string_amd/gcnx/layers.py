@@ -6,7 +6,8 @@ kernel_initializer="glorot_uniform", bias_initializer="zeros")`` called as ``lay
 Reference topology: GCNConv -> GCNConv -> global pool -> Linear (gcn_utills.py:805-808,
 832-842); live model ctor gcn.py:320, forward gcn.py:334/351, gradients gcn.py:337.
 ``SAGEConv(channels, root_weight=True, use_bias=True)`` is PyG's layer of that name (aggr="mean"), which the reference
-names as its next step (gcn_utills.py:804-806).
+names as its next step (gcn_utills.py:804-806).  ``TopKPool(ratio)`` is Spektral's pooling layer of that name, which the
+reference's script imports (gcn.py:10), called as ``layer([x, a, seg])``.
 
 There is no autograd here: every layer has ``backward(dy)`` that returns dx and leaves the
 parameter gradients in ``layer.grads`` (what tape.gradient, gcn.py:337, would produce).
@@ -458,6 +459,105 @@ class GlobalAvgPool(_GlobalPool):
 class GlobalMaxPool(_GlobalPool):
     """global_max_pool of the reference's torch topology (gcn_utills.py:842)."""
     mode = "max"
+
+
+class TopKPool(Layer):
+    """spektral.layers.pooling.TopKPool in disjoint mode, the one Spektral layer the reference's script imports (gcn.py:10)
+    besides the ones above: hierarchical pooling that keeps the ceil(ratio * n_g) highest-scoring nodes of every graph.
+
+        y = X p / ||p||        idx = the k_g rows of graph g with the largest y        X' = (X * gate(y))[idx]
+        A' = A[idx][:, idx]    values copied, NOT renormalised (as Spektral)           graph_ptr' = prefix sums of k_g
+
+    ``TopKPool(ratio, return_selection=False, return_score=False, sigmoid_gating=False, kernel_initializer="glorot_uniform")``,
+    called as ``layer([x, a, seg])`` with a DeviceCSR and a Segments; returns ``(x', a', seg')`` (+ ``idx`` int32[N'] and / or
+    ``y`` [N] if asked, in that order).  One parameter, ``kernel`` [F, 1]; gate = tanh, or sigmoid with ``sigmoid_gating``.
+    ``backward(dx')`` returns dx [N, F] (zero rows for dropped nodes) and leaves d kernel in ``grads``; nothing flows through
+    the selection or through the values of A'.
+
+    Two decisions that differ from, or go beyond, Spektral:
+      1. Kept rows stay in their ORIGINAL relative order (Spektral and PyG order them by descending score).  Every layer that
+         can follow (GCNConv, SAGEConv, the global pools) is permutation-equivariant or -invariant, so model outputs and all
+         gradients are the same; the map old -> new is monotone, so A' keeps sorted columns and its diagonal blocks, and a
+         symmetric A gives a symmetric A' (the flag is passed on, nothing is inspected per step).
+      2. Scores compare as IEEE numbers (-0.0 equals +0.0); among equal scores the LOWER row index wins.  NaN scores are
+         outside the contract: all that is promised then is k_g distinct rows of every graph.
+
+    k_g is computed on the host in float64 from ``seg.host``, so N' and graph_ptr' are known up front; the one
+    synchronisation of the layer is the 4-byte read-back of nnz' = rowptr'[N'].  colidx' / vals' live in buffers sized for the
+    parent's nnz (no allocation per step) and ``a'.nnz`` is set from the read-back.  x', a', seg' and idx are views of the
+    layer's buffers: valid until its next call.  Launches: gcnx_topk_select, gcnx_csr_induce (3), gcnx_topk_gather;
+    backward gcnx_topk_bwd (2) -- csrc/topk.hip.  A graph of more than 16384 rows raises NotImplementedError."""
+
+    def __init__(self, ratio, return_selection=False, return_score=False, sigmoid_gating=False,
+                 kernel_initializer="glorot_uniform", **kw):
+        super().__init__(**kw)
+        if not (isinstance(ratio, (int, float, np.integer, np.floating)) and 0.0 < float(ratio) <= 1.0):
+            raise ValueError(f"TopKPool(ratio={ratio!r}): a number in (0, 1]")
+        if kernel_initializer != "glorot_uniform":
+            raise NotImplementedError("only the glorot_uniform initialiser (the Spektral default)")
+        self.ratio, self.return_selection, self.return_score = float(ratio), bool(return_selection), bool(return_score)
+        self.sigmoid_gating = bool(sigmoid_gating)
+        self._store, self._kept = {}, None
+
+    def _param_spec(self, in_dim):
+        return [("kernel", (in_dim, 1), glorot_uniform(self._rng, in_dim, 1))]
+
+    def _cap(self, key, shape, dtype=np.float32):
+        """Grow-only storage behind a view of ``shape`` (a streamed epoch brings a new N with every batch)."""
+        shape = tuple(int(s) for s in shape)
+        need = int(np.prod(shape))
+        cur = self._store.get(key)
+        if cur is None or cur.size < need:
+            cur = self.ctx.empty(max(need, int(1.25 * cur.size) if cur is not None else 0, 4), dtype)
+            self._store[key] = cur
+        return D.DeviceArray._view(cur, 0, shape)
+
+    def _segments(self, seg):
+        """(graph_ptr' on the host, Segments'), kept while the same Segments object comes back."""
+        if self._kept is None or self._kept[0] is not seg:
+            kp = D.topk_kept_ptr(seg.host, self.ratio)
+            self._kept = (seg, kp, D.Segments.from_device(self.ctx, self.ctx.to_device(kp, np.int32), kp))
+        return self._kept[1], self._kept[2]
+
+    def call(self, inputs, out=None):
+        x, a, seg = inputs
+        if not self.built:
+            self.build(x.ctx, x.shape[1])
+        ctx, (n, f) = self.ctx, x.shape
+        if a.n != n or seg.n != n:
+            raise ValueError(f"TopKPool: x has {n} rows, a {a.n}, the segments {seg.n}")
+        kp, seg2 = self._segments(seg)
+        nk = int(kp[-1])
+        y, pos, idx = self._cap("y", (n,)), self._cap("pos", (n,), np.int32), self._cap("idx", (nk,), np.int32)
+        D.topk_select(ctx, seg, seg2.dev, nk, x, self.params["kernel"], y, idx, pos)
+        rp = self._cap("rowptr", (nk + 1,), np.int32)
+        ci = self._cap("colidx", (max(a.nnz, 1),), np.int32)
+        v = self._cap("vals", (max(a.nnz, 1),)) if a.vals is not None else None
+        D.csr_induce(ctx, a, idx, pos, nk, rp, ci, v)
+        x2 = out if out is not None else self._cap("x2", (nk, f))
+        D.topk_gather(ctx, x, y, idx, nk, x2, self.sigmoid_gating)
+        nnz2 = D.read_int32(ctx, rp, nk)                       # the layer's one synchronisation
+        a2 = D.DeviceCSR(ctx, nk, nnz2, rp, ci, v, seg2.dev, seg2.n_graphs, a.symmetric, D._max_block(kp))
+        # The buffers behind a' are reused from step to step, and a transposed CSR built for last step's a' may have been freed
+        # and its address handed out again: a plan kept on graph_ptr' forgets every row order it holds and learns the new rows.
+        plan = getattr(seg2.dev, "_spmm_plan", None)
+        if plan is not None:
+            plan.bound.clear()
+        a2.rebind()
+        self._saved = (x, y, pos, nk, idx)
+        res = (x2, a2, seg2)
+        if self.return_selection:
+            res += (idx,)
+        if self.return_score:
+            res += (y,)
+        return res
+
+    def backward(self, dy, need_dx=True):
+        x, y, pos, nk, _ = self._saved
+        assert dy.shape == (nk, x.shape[1])
+        dx = self._cap("dx", x.shape)
+        D.topk_bwd(self.ctx, x, y, pos, self.params["kernel"], dy, dx, self.grads["kernel"], self.sigmoid_gating)
+        return dx if need_dx else None
 
 
 class BatchNorm1d(Layer):

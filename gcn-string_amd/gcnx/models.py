@@ -15,6 +15,9 @@ Linear·BatchNorm1d·PReLU twice, one logit with BCEWithLogitsLoss (eager launch
 
 ``SAGE``: ``GCN`` with PyG's SAGEConv(aggr="mean") in the place of both GCNConv layers, the step the reference's author notes
 above them (gcn_utills.py:804-806); one launch per convolution (csrc/sage.hip).
+
+``TopKNet``: GCNConv -> TopKPool -> GCNConv -> global pool -> Dense(softmax), with the pooling layer the reference's script imports
+(gcn.py:10); selection, gather and the induced adjacency on the device (csrc/topk.hip), eager launches.
 """
 from __future__ import annotations
 
@@ -1969,6 +1972,170 @@ class ECCNet(_GraphRunner):
     # ---- public surface ----------------------------------------------------------------------------------------------------
     def __call__(self, inputs, training=False):
         """model((x, a, e, i), training=False) -> probabilities [B, n_labels]."""
+        batch = self._as_batch(inputs)
+        bufs = self._ensure(batch)
+        self._forward(batch, bufs, "fwd")
+        return bufs["probs"].numpy()
+
+    def loss_and_grads(self, inputs, target=None, global_batch=None, _lr=None):
+        """Forward + loss + every gradient (+ the SGD update with ``_lr``).  Returns the device batch."""
+        batch = self._as_batch(inputs, target)
+        bufs = self._ensure(batch)
+        self._forward(batch, bufs, "grads", float(global_batch or batch.n_graphs))
+        self._backward(batch, bufs)
+        if _lr is not None:
+            self._apply_sgd(_lr)
+        self._last_batch = batch
+        return batch
+
+    def train_step(self, inputs, target=None, lr=0.02, fetch=True, global_batch=None):
+        """One optimisation step (gcn.py:330-340): loss, gradients, p -= lr * g.  fetch: True -> (loss, acc); False -> None;
+        "stash" -> None, metrics kept on the device for collect_metrics()."""
+        batch = self.loss_and_grads(inputs, target, global_batch, _lr=float(lr))
+        return self._finish_step(fetch, global_batch or batch.n_graphs)
+
+    def evaluate_batch(self, inputs, target):
+        """(loss, accuracy, probabilities) without gradients (the body of evaluate(), gcn.py:350-357; loss by cce_eval)."""
+        batch = self._as_batch(inputs, target)
+        bufs = self._ensure(batch)
+        self._forward(batch, bufs, "loss", float(batch.n_graphs))
+        return (*self._loss_acc_host(batch.n_graphs), bufs["probs"].numpy())
+
+
+class TopKNet(_GraphRunner):
+    """Hierarchical pooling between two convolutions, with the one Spektral layer the reference's script imports and the flat
+    models cannot express (``from spektral.layers.pooling import TopKPool``, gcn.py:10):
+
+        GCNConv(hidden, relu) -> TopKPool(ratio) -> GCNConv(hidden, relu) -> GlobalSumPool | GlobalAvgPool -> Dense(n_labels, softmax)
+
+    with the categorical cross-entropy and one-hot labels of gcn.py:259-262,326 and plain SGD.  ``TopKNet([ctx,] n_labels=2,
+    hidden=64, ratio=0.5, pool="sum", sigmoid_gating=False, seed=0)``; inputs are ``(x, a, i)`` as DisjointLoader yields them
+    (an ``e`` is dropped) or a DeviceBatch; the adjacency is used with its values (pass normalize= / GCNConv.preprocess for
+    gcn_filter), and the pooled operator A[idx][:, idx] keeps them without renormalising, as Spektral does.
+
+    Follows the ECCNet protocol (model(inputs, training=), loss_and_grads, train_step(fetch=True | False | "stash"),
+    evaluate_batch, collect_metrics; one flat parameter buffer with every tensor on a multiple of 4 floats, one SGD launch),
+    so gcnx.fit / gcnx.evaluate drive it.  fp32, one device, eager launches: TopKPool reads nnz' back (4 bytes) in the middle
+    of the forward pass, so the step cannot be captured (DESIGN.md §4.9 lists one step's launches).
+
+    Weights: ``get_weights()`` lists PARAM_ORDER (conv1 kernel, bias; the pool's kernel [hidden, 1]; conv2 kernel, bias; the
+    Dense pair); ``get_weights(as_dict=True)``, ``set_weights(dict)`` and ``gradients()`` use those names."""
+
+    PARAM_ORDER = ("conv1_kernel", "conv1_bias", "pool_kernel", "conv2_kernel", "conv2_bias", "dense_kernel", "dense_bias")
+
+    @D.with_default_context
+    def __init__(self, ctx, n_labels=2, hidden=64, ratio=0.5, pool="sum", sigmoid_gating=False, seed=0, comm=None, prec="f32",
+                 cce_train="logits", cce_eval="probs"):
+        from .layers import GCNConv, TopKPool
+        if comm is not None:
+            raise NotImplementedError("gcnx.TopKNet runs on one device (comm is not supported)")
+        if prec not in ("f32", "fp32"):
+            raise NotImplementedError(f"gcnx.TopKNet: prec={prec!r}; fp32 only")
+        if pool not in ("sum", "avg", "mean"):
+            raise NotImplementedError(f"gcnx.TopKNet: pool={pool!r}; 'sum' (the default) or 'avg'")
+        if int(n_labels) < 1 or int(hidden) < 1:
+            raise ValueError(f"gcnx.TopKNet(n_labels={n_labels!r}, hidden={hidden!r})")
+        self.ctx, self.n_labels, self.hidden, self.pool = ctx, int(n_labels), int(hidden), "avg" if pool == "mean" else pool
+        self.cce_train, self.cce_eval = cce_train, cce_eval
+        self.comm, self.prec = None, "f32"
+        self.use_graph = False                                  # eager: the pool's read-back sits inside the forward pass
+        rng = np.random.default_rng(seed)
+        s1, sp, s2, self._head_seed = (int(v) for v in rng.integers(0, 2 ** 31, 4))
+        self.conv1 = GCNConv(self.hidden, activation="relu", seed=s1)
+        self.topk = TopKPool(ratio, sigmoid_gating=sigmoid_gating, seed=sp)          # (validates ratio)
+        self.conv2 = GCNConv(self.hidden, activation="relu", seed=s2)
+        self.ratio, self.sigmoid_gating = self.topk.ratio, self.topk.sigmoid_gating
+        self.built = False
+        self._bufs = None
+        self._graphs = {}
+
+    # ---- parameters: one flat buffer (one SGD launch), every tensor on a 4-float boundary ----------------------------------
+    def build(self, f_in):
+        h, c = self.hidden, self.n_labels
+        self.f_in = int(f_in)
+        head = np.random.default_rng(self._head_seed)
+        inits = {}
+        for tag, layer, fi in (("conv1", self.conv1, self.f_in), ("pool", self.topk, h), ("conv2", self.conv2, h)):
+            layer.ctx, layer.in_dim, layer.built = self.ctx, fi, True
+            for name, _, init in layer._param_spec(fi):
+                inits[f"{tag}_{name}"] = (layer, name, init)
+        inits["dense_kernel"] = (None, None, glorot_uniform(head, h, c))
+        inits["dense_bias"] = (None, None, np.zeros(c, np.float32))
+        self._alloc_flat([(k, inits[k][2].shape) for k in self.PARAM_ORDER], align=4)
+        for k in self.PARAM_ORDER:
+            layer, name, init = inits[k]
+            self.p[k].copy_from_host(init)
+            if layer is not None:
+                layer.params[name], layer.grads[name] = self.p[k], self.g[k]
+        self.built = True
+
+    def get_weights(self, as_dict=False):
+        d = {k: self.p[k].numpy() for k in self.PARAM_ORDER}
+        return d if as_dict else [d[k] for k in self.PARAM_ORDER]
+
+    def set_weights(self, weights):
+        if not self.built:
+            raise ValueError("gcnx.TopKNet.set_weights: build(f_in) first (or run a batch)")
+        if not isinstance(weights, dict):
+            weights = dict(zip(self.PARAM_ORDER, weights))
+        for k in self.PARAM_ORDER:
+            self.p[k].copy_from_host(np.asarray(weights[k], np.float32).reshape(self.p[k].shape))
+
+    def gradients(self):
+        """Gradients of the last loss_and_grads / train_step, named as get_weights(as_dict=True)."""
+        return {k: self.g[k].numpy() for k in self.PARAM_ORDER}
+
+    @property
+    def trainable_variables(self):
+        return [self.p[k] for k in self.PARAM_ORDER]
+
+    # ---- batches -------------------------------------------------------------------------------------------------------
+    def _as_batch(self, inputs, target=None):
+        return self._adopt(inputs, target)                       # (the adjacency's values are read: weighted)
+
+    def _ensure(self, batch):
+        if not self.built:
+            self.build(batch.f)
+        if batch.f != self.f_in:
+            raise ValueError(f"gcnx.TopKNet was built for {self.f_in} node features, got {batch.f}")
+        key = (batch.n, batch.n_graphs, batch.seg)              # (the Segments object: N' depends on every graph's size)
+        if self._bufs is not None and self._bufs["key"] == key:
+            return self._bufs
+        v, n, b, h, c = self._views(), batch.n, batch.n_graphs, self.hidden, self.n_labels
+        nk = int(D.topk_kept_ptr(batch.seg.host, self.ratio)[-1])
+        self._bufs = {"key": key, "y1": v("y1", n, h), "x2": v("x2", nk, h), "y2": v("y2", nk, h), "dy2": v("dy2", nk, h),
+                      "pooled": v("pooled", b, h), "dpooled": v("dpooled", b, h), "probs": v("probs", b, c)}
+        return self._bufs
+
+    # ---- the call sequences ------------------------------------------------------------------------------------------------
+    def _forward(self, batch, bufs, mode, denom=None):
+        """mode: "fwd" (probabilities), "loss" (+ loss and hits, cce_eval), "grads" (+ dPooled and the head's gradients, cce_train)."""
+        ctx, p, g = self.ctx, self.p, self.g
+        self.conv1([batch.x, batch.a], out=bufs["y1"])
+        x2, a2, seg2 = self.topk([bufs["y1"], batch.a, batch.seg], out=bufs["x2"])
+        self.conv2([x2, a2], out=bufs["y2"])
+        self._seg2 = seg2
+        D.segment_pool(ctx, seg2, bufs["y2"], bufs["pooled"], self.pool)
+        if mode != "fwd" and batch.y is None:
+            raise ValueError("gcnx.TopKNet: labels are needed for the loss")
+        if mode == "grads":
+            D.dense_softmax_cce(ctx, bufs["pooled"], p["dense_kernel"], p["dense_bias"], batch.y, bufs["probs"], self.loss_acc, denom,
+                                dw=g["dense_kernel"], db=g["dense_bias"], dpooled=bufs["dpooled"], cce=self.cce_train)
+        elif mode == "loss":
+            D.dense_softmax_cce(ctx, bufs["pooled"], p["dense_kernel"], p["dense_bias"], batch.y, bufs["probs"], self.loss_acc, denom,
+                                cce=self.cce_eval)
+        else:
+            D.dense_softmax_cce(ctx, bufs["pooled"], p["dense_kernel"], p["dense_bias"], None, bufs["probs"])
+
+    def _backward(self, batch, bufs):
+        D.segment_pool_bwd(self.ctx, self._seg2, bufs["dpooled"], bufs["dy2"], self.pool)
+        dx2 = self.conv2.backward(bufs["dy2"])
+        dy1 = self.topk.backward(dx2)
+        self.conv1.backward(dy1, need_dx=False)
+
+    # ---- public surface ----------------------------------------------------------------------------------------------------
+    def __call__(self, inputs, training=False):
+        """model((x, a, i), training=False) -> probabilities [B, n_labels]."""
         batch = self._as_batch(inputs)
         bufs = self._ensure(batch)
         self._forward(batch, bufs, "fwd")

@@ -768,6 +768,43 @@ GCNX_API int gcnx_sage_conv(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t*
                       const float* x, int64_t ldx, int32_t n, int32_t fi, const float* w_nb, const float* w_root,
                       int32_t fo, int w_transposed, const float* bias, float* s, int64_t lds, float* out, int64_t ldo);
 
+/* ---- TopKPool: per-graph top-k selection, gated gather, induced sub-CSR ------------------------------------------
+ * spektral.layers.pooling.TopKPool, the one layer the reference's training script imports (gcn.py:10) that had no kernels
+ * here, in disjoint mode: y = X p / ||p||, the k_g rows of every graph with the largest y are kept, X' = (X * gate(y))[idx],
+ * A' = A[idx][:, idx] with the values copied (not renormalised).  Kept rows stay in their original relative order (Spektral
+ * orders them by score; every layer downstream is permutation-equivariant), so A' keeps sorted columns and its diagonal
+ * blocks.  Scores compare as IEEE numbers (-0.0 == +0.0), among equal scores the lower row wins; with a NaN score the only
+ * promise is k_g distinct rows of graph g.  fp32, no atomics: the same bits on every call.
+ * gcnx_topk_select_ok (gcn.py:10): 1 if a batch whose largest graph has max_graph_rows rows and f features is served (one
+ * workgroup ranks a graph's 8-byte keys in LDS: up to 16384 rows; f > 0); answers without a context. */
+GCNX_API int gcnx_topk_select_ok(int64_t max_graph_rows, int32_t f);
+/* gcn.py:10 -- scores and selection.  graph_ptr int32[b+1]; kept_ptr int32[b+1] = graph_ptr', the prefix sums of the k_g the
+ * CALLER chose (0 <= k_g <= n_g; TopKPool: ceil(ratio n_g)), so that N' = kept_ptr[b] is known without a read-back;
+ * max_graph_rows >= every n_g (sizes the LDS; a larger graph is left untouched).  x [N, f] (row stride ldx), p [f].
+ * Writes y [N], idx [N'] (kept rows, global row numbers, ascending) and pos [N] (new row number, or -1).
+ * GCNX_ERR_UNSUPPORTED, with nothing launched, where gcnx_topk_select_ok says 0. */
+GCNX_API int gcnx_topk_select(gcnx_ctx* ctx, const int32_t* graph_ptr, const int32_t* kept_ptr, int32_t b,
+                     int32_t max_graph_rows, const float* x, int64_t ldx, int32_t f, const float* p, float* y,
+                     int32_t* idx, int32_t* pos);
+/* gcn.py:10 -- out[r, :] = x[idx[r], :] * gate(y[idx[r]]), r < n_kept; gate = tanh, or the logistic function with
+ * sigmoid_gating != 0.  out must not alias x. */
+GCNX_API int gcnx_topk_gather(gcnx_ctx* ctx, const float* x, int64_t ldx, const float* y, const int32_t* idx,
+                     int32_t n_kept, int32_t f, int sigmoid_gating, float* out, int64_t ldo);
+/* gcn.py:10 -- the adjoint of gcnx_topk_gather and of the score.  dxo [N', f] = dLoss/dX'.  For a kept row i (r = pos[i]):
+ * dy_i = gate'(y_i) <dxo_r, x_i>, dx_i = gate(y_i) dxo_r + dy_i p / ||p||; a dropped row gets dx_i = 0 -- every row of
+ * dx [n, f] is written.  dp [f] = (I - p^ p^T)(X^T dy) / ||p||, p^ = p / ||p||, summed in a fixed order (per-tile parts in
+ * the ctx workspace, then one workgroup).  Nothing flows through the selection.  dx must not alias x or dxo. */
+GCNX_API int gcnx_topk_bwd(gcnx_ctx* ctx, const float* x, int64_t ldx, const float* y, const int32_t* pos, const float* p,
+                  int32_t n, int32_t f, int sigmoid_gating, const float* dxo, int64_t lddxo, float* dx, int64_t lddx,
+                  float* dp);
+/* gcn.py:10 -- A' = A[idx][:, idx] for idx / pos as gcnx_topk_select writes them (any ascending idx with its inverse pos
+ * does): rowptr_out int32[n_kept + 1], colidx_out = pos[col] of the surviving entries in their stored order (sorted rows stay
+ * sorted), vals_out their values; vals == NULL <=> vals_out == NULL.  colidx_out / vals_out need room for the parent's nnz
+ * at most; nnz' = rowptr_out[n_kept] is the caller's to read back.  Three launches, the block totals in the ctx workspace. */
+GCNX_API int gcnx_csr_induce(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, const float* vals,
+                    const int32_t* idx, const int32_t* pos, int32_t n_kept, int32_t* rowptr_out, int32_t* colidx_out,
+                    float* vals_out);
+
 /* ---- aggregation with bf16 features ("fp32 and bf16 both reported") ----
  * out[t, :] = bf16(act(sum_e vals[e] * h[colidx[e], :] + bias)): GCNConv.call's / GeneralConv's aggregation (gcn.py:334) on
  * activations stored as bf16 (uint16_t bit patterns), fp32 accumulation, round-to-nearest-even on the way out; bias fp32
