@@ -140,6 +140,22 @@ __device__ __forceinline__ void store_tile(float (*s)[LD], int tid, const float4
   }
 }
 
+// Tuning builds only (make TUNING=1): where a tile workgroup of the dW1 + dW2 launch spends its time.  Thread 0 of a
+// workgroup leaves four s_memrealtime readings (100 MHz) in g_dw2_stamps[blockIdx.x][4]: 0 entry, 1 operands of K step 0
+// in LDS (the loop's first barrier is next), 2 last MFMA issued, 3 the tile's stores have landed.  NULL = off;
+// gcnx_gemm_dw2 sets the pointer and prints the reduction (GCNX_DW2_STAMPS).
+#ifdef GCNX_TUNING
+constexpr int kDw2StampWgs = 4096;
+__device__ unsigned long long* g_dw2_stamps = nullptr;
+#define GCNX_DWSTAMP(K_)                                                                                      \
+  if (g_dw2_stamps && threadIdx.x == 0 && blockIdx.x < kDw2StampWgs && blockIdx.y == 0 && blockIdx.z == 0) {  \
+    if ((K_) == 3) __builtin_amdgcn_s_waitcnt(0);                                                             \
+    g_dw2_stamps[blockIdx.x * 4 + (K_)] = __builtin_amdgcn_s_memrealtime();                                   \
+  }
+#else
+#define GCNX_DWSTAMP(K_)
+#endif
+
 // One 64x64 tile (bx, by) of C[M,Nc] = op(A) op(B) over k in [bz*kchunk, min(K,(bz+1)*kchunk)); bz = split-K slice
 // (of nz).  With split-K (nz > 1) the raw partial tile goes to c + bz*M*ldc (a [S][M][ldc] slab).
 template <bool A_KCONTIG, bool B_KCONTIG>
@@ -163,6 +179,7 @@ __device__ __forceinline__ void gemm_f32_tile(const float* __restrict__ a, int64
 
   const int fr = lane & 31, fk = lane >> 5;
   const bool interior = vec_a && vec_b && m0 + BM <= M && n0 + BN <= Nc && kbeg < kend && (kend - kbeg) % BK == 0;
+  GCNX_DWSTAMP(0)
   if (interior) {            // uniform per workgroup
     float4 a0 = fetch_one<A_KCONTIG>(a, lda, m0, kbeg, tid), a1 = fetch_one<A_KCONTIG>(a, lda, m0, kbeg, tid + 256);
     float4 b0 = fetch_one<B_KCONTIG>(b, ldb, n0, kbeg, tid), b1 = fetch_one<B_KCONTIG>(b, ldb, n0, kbeg, tid + 256);
@@ -173,6 +190,7 @@ __device__ __forceinline__ void gemm_f32_tile(const float* __restrict__ a, int64
       b0 = fetch_one<B_KCONTIG>(b, ldb, n0, kbeg + BK, tid); b1 = fetch_one<B_KCONTIG>(b, ldb, n0, kbeg + BK, tid + 256);
     }
     int cur = 0;
+    GCNX_DWSTAMP(1)
     for (int64_t k0 = kbeg; k0 < kend; k0 += BK) {
       __syncthreads();
       if (k0 + BK < kend) {
@@ -191,6 +209,7 @@ __device__ __forceinline__ void gemm_f32_tile(const float* __restrict__ a, int64
       }
       cur ^= 1;
     }
+    GCNX_DWSTAMP(2)
   } else {
   float4 ra[2], rb[2];
   if (kbeg < kend) {
@@ -276,6 +295,7 @@ __device__ __forceinline__ void gemm_f32_tile(const float* __restrict__ a, int64
       }
       if (lane < 8) *reinterpret_cast<float4*>(ep.colpart + ((int64_t)by * 2 + wm) * Nc + gcol) = csum;
     }
+    GCNX_DWSTAMP(3)
     return;
   }
   const int64_t col = n0 + wn * 32 + fr;
@@ -294,6 +314,94 @@ __device__ __forceinline__ void gemm_f32_tile(const float* __restrict__ a, int64
     if (ep.accumulate) v += *dst;
     *dst = v;
   }
+}
+
+// The interior tiles of the dW1 + dW2 launch (gcnx_gemm_dw2): gemm_f32_tile<false, false>'s interior branch cut down to what
+// a dW job needs.  A config-2 launch is 520 workgroups that are all resident at once (two per CU) and walk 11 K steps in
+// step with one another, so what a workgroup spends outside its K loop is launch time:
+//   prologue  the global loads of steps 0 and 1 are in flight together (gemm_f32_tile waits for step 0 and stores it
+//             before it issues step 1: two round trips in a row);
+//   epilogue  the float4 staging epilogue without gemm_f32_tile's run-time choices (bias, activation, mask, accumulate,
+//             column sums, row guards): 1.0 us from the last MFMA to the landed stores instead of 1.9.
+// The K loop is gemm_f32_tile's: operand pairs read from LDS right in front of their two MFMAs.  Holding a whole step's
+// 32 operand values in registers (16 ds_read2_b32 behind the barrier, the stores and loads of the next steps between the
+// two halves) was measured and is slower -- K loop 13.4 us against 12.6 at config 2, 231-239 against 222-229 us at
+// 20 498 x 1024 x 256: the second wave of the SIMD already covers the LDS round trips (LOG.md Round 14).
+// Same slices, same LDS images, same lane -> (k, row) operand mapping, same instruction with k ascending on the one
+// accumulator, same staging epilogue: every result bit is gemm_f32_tile's (tests/test_gpu_dw2_feed.py).  The caller
+// checks eligibility (dw_tile below).
+__device__ __forceinline__ float4 dw_ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+
+__device__ __forceinline__ void dw_tile_interior(const float* __restrict__ a, int64_t lda, const float* __restrict__ b,
+                                                 int64_t ldb, float* __restrict__ c, int64_t ldc, int64_t M, int64_t kbeg,
+                                                 int64_t kend, int bx, int by, int bz, int nz, float (*As)[BK][LD],
+                                                 float (*Bs)[BK][LD]) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int64_t m0 = (int64_t)by * BM, n0 = (int64_t)bx * BN;
+  const int fr = lane & 31, fk = lane >> 5;
+  GCNX_DWSTAMP(0)
+
+  f32x16 acc;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+
+  // This thread's two float4 of a K step and of each operand (fetch_one<false> / store_one<false> at idx = tid and
+  // tid + 256): rows k = lk and lk + 16, columns li .. li + 3.
+  const int lk = tid >> 4, li = (tid & 15) * 4;
+  const int64_t ha = 16 * lda, hb = 16 * ldb;                    // half a K step
+  const float* pa = a + (kbeg + lk) * lda + m0 + li;
+  const float* pb = b + (kbeg + lk) * ldb + n0 + li;
+  float4 a0 = dw_ld4(pa), a1 = dw_ld4(pa + ha), b0 = dw_ld4(pb), b1 = dw_ld4(pb + hb);
+  __builtin_amdgcn_sched_barrier(0);                             // step 0 first: its stores wait for four loads, not eight
+  if (kbeg + BK < kend) { pa += 2 * ha; pb += 2 * hb; }          // (a slice of one step loads it twice: no branch, no
+  float4 na0 = dw_ld4(pa), na1 = dw_ld4(pa + ha), nb0 = dw_ld4(pb), nb1 = dw_ld4(pb + hb);   // row past the slice)
+  __builtin_amdgcn_sched_barrier(0);                             // eight loads in flight before the first store waits
+  *reinterpret_cast<float4*>(&As[0][lk][li]) = a0; *reinterpret_cast<float4*>(&As[0][lk + 16][li]) = a1;
+  *reinterpret_cast<float4*>(&Bs[0][lk][li]) = b0; *reinterpret_cast<float4*>(&Bs[0][lk + 16][li]) = b1;
+  pa += 2 * ha; pb += 2 * hb;                                    // -> step 2
+
+  int cur = 0;
+  GCNX_DWSTAMP(1)
+  for (int64_t k0 = kbeg; k0 < kend; k0 += BK) {
+    __syncthreads();        // image `cur` is complete; everybody has finished reading image cur^1 (step t-1)
+    if (k0 + BK < kend) {   // registers hold step t+1: into the other image, then fetch step t+2
+      *reinterpret_cast<float4*>(&As[cur ^ 1][lk][li]) = na0; *reinterpret_cast<float4*>(&As[cur ^ 1][lk + 16][li]) = na1;
+      *reinterpret_cast<float4*>(&Bs[cur ^ 1][lk][li]) = nb0; *reinterpret_cast<float4*>(&Bs[cur ^ 1][lk + 16][li]) = nb1;
+      if (k0 + 2 * BK < kend) {
+        na0 = dw_ld4(pa); na1 = dw_ld4(pa + ha); nb0 = dw_ld4(pb); nb1 = dw_ld4(pb + hb);
+        pa += 2 * ha; pb += 2 * hb;
+      }
+    }
+#pragma unroll
+    for (int kk = 0; kk < BK / 2; ++kk) {
+      const float av = As[cur][2 * kk + fk][wm * 32 + fr];
+      const float bv = Bs[cur][2 * kk + fk][wn * 32 + fr];
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc, 0, 0, 0);
+    }
+    cur ^= 1;
+  }
+  GCNX_DWSTAMP(2)
+
+  // gemm_f32_tile's float4 epilogue at epi_plain (a zero bias is added there, so it is here): each wave passes its
+  // 32 x 32 tile through LDS and writes four store instructions of eight full 128-byte row segments.
+  float* cz = c + (nz > 1 ? (int64_t)bz * M * ldc : 0);
+  const int64_t tr0 = m0 + wm * 32, tc0 = n0 + wn * 32;
+  __syncthreads();
+  float(*st)[36] = reinterpret_cast<float(*)[36]>(wave < 2 ? &As[0][0][0] : &Bs[0][0][0]) + (wave & 1) * 32;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) st[(r & 3) + 8 * (r >> 2) + 4 * fk][fr] = acc[r];
+  __builtin_amdgcn_s_waitcnt(0xc07f);          // lgkmcnt(0): the wave's own LDS writes have landed
+  __builtin_amdgcn_wave_barrier();
+  const int ec = (lane & 7) * 4, er = lane >> 3;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int lr = q * 8 + er;
+    float4 v = *reinterpret_cast<const float4*>(&st[lr][ec]);
+    v.x += 0.f; v.y += 0.f; v.z += 0.f; v.w += 0.f;
+    *reinterpret_cast<float4*>(cz + (tr0 + lr) * ldc + tc0 + ec) = v;
+  }
+  GCNX_DWSTAMP(3)
 }
 
 template <bool A_KCONTIG, bool B_KCONTIG>
@@ -337,22 +445,29 @@ __global__ __launch_bounds__(256) void gemm_f32_duo_kernel(GemmJob dx, GemmJob d
   }
 }
 
+// Tile `bid` of a dW job (dw_job) in the dW1 + dW2 launch.  feed (the context's knob_dw2_feed): the tiles that take
+// gemm_f32_tile's interior branch -- both operands 16-byte aligned with ld % 4 == 0, a full 64 x 64 tile, a slice of whole
+// K steps; float4 slab stores -- run dw_tile_interior, every other tile (ragged edges, the short last slice) and every
+// tile with feed == 0 gemm_f32_tile as before.  Uniform per workgroup.
+__device__ __forceinline__ void dw_tile(const GemmJob& j, int bid, int feed, float (*As)[BK][LD], float (*Bs)[BK][LD]) {
+  const int bx = bid % j.gx, t = bid / j.gx, by = t % j.gy, bz = t / j.gy;
+  const int64_t kbeg = (int64_t)bz * j.kchunk, kend = min(j.K, kbeg + j.kchunk);
+  if (feed && j.vec_a && j.vec_b && j.ep.vec_c && (int64_t)(by + 1) * BM <= j.M && (bx + 1) * BN <= j.Nc && kbeg < kend &&
+      (kend - kbeg) % BK == 0)
+    dw_tile_interior(j.a, j.lda, j.b, j.ldb, j.c, j.ldc, j.M, kbeg, kend, bx, by, bz, j.gz, As, Bs);
+  else
+    gemm_f32_tile<false, false>(j.a, j.lda, j.b, j.ldb, j.c, j.ldc, j.M, j.Nc, j.K, j.kchunk, j.ep, j.vec_a, j.vec_b, bx, by, bz,
+                                j.gz, As, Bs);
+}
+
 // Two weight gradients X^T dH over the same rows in one launch (gcnx_gemm_dw2): workgroups [0, n_a) are the split-K
 // tiles of job a, the rest those of job b.
-__global__ __launch_bounds__(256) void gemm_f32_dw2_kernel(GemmJob ja, GemmJob jb, int n_a) {
+__global__ __launch_bounds__(256) void gemm_f32_dw2_kernel(GemmJob ja, GemmJob jb, int n_a, int feed) {
   __shared__ __attribute__((aligned(16))) float As[2][BK][LD];
   __shared__ __attribute__((aligned(16))) float Bs[2][BK][LD];
-  int bid = blockIdx.x;                      // uniform per workgroup
-  if (bid < n_a) {
-    const int bx = bid % ja.gx, t = bid / ja.gx;
-    gemm_f32_tile<false, false>(ja.a, ja.lda, ja.b, ja.ldb, ja.c, ja.ldc, ja.M, ja.Nc, ja.K, ja.kchunk, ja.ep, ja.vec_a,
-                                ja.vec_b, bx, t % ja.gy, t / ja.gy, ja.gz, As, Bs);
-  } else {
-    bid -= n_a;
-    const int bx = bid % jb.gx, t = bid / jb.gx;
-    gemm_f32_tile<false, false>(jb.a, jb.lda, jb.b, jb.ldb, jb.c, jb.ldc, jb.M, jb.Nc, jb.K, jb.kchunk, jb.ep, jb.vec_a,
-                                jb.vec_b, bx, t % jb.gy, t / jb.gy, jb.gz, As, Bs);
-  }
+  const int bid = blockIdx.x;                // uniform per workgroup
+  if (bid < n_a) dw_tile(ja, bid, feed, As, Bs);
+  else dw_tile(jb, bid - n_a, feed, As, Bs);
 }
 
 // gcnx_gemm_dw2 with the classifier head's leaves (gcnx_head_args): the FIRST n_head workgroups of the launch run the head
@@ -367,8 +482,10 @@ struct HeadLeaf {
 constexpr int kDw2HeadLds = 9216;          // floats: >= 2 x 2 x BK x LD (8704) and the head's staged operands at h = 128, c = 2 (9024)
 
 // (The head body's combine runs with ZU = 1: at its stand-alone unroll the body holds 208 VGPRs and the WHOLE launch drops
-// to two waves per SIMD -- the tiles then take 24.2 us instead of 22.3.  106 VGPRs as built; check after any change.)
-__global__ __launch_bounds__(256) void gemm_f32_dw2_head_kernel(GemmJob ja, GemmJob jb, int n_a, HeadLeaf hl, int n_head) {
+// to two waves per SIMD -- the tiles then take 24.2 us instead of 22.3.  As built: 106 VGPRs + 16 AGPRs (128 are the
+// limit of four waves per SIMD), no scratch, 39 684 B of LDS; gemm_f32_dw2_kernel: 55 + 16.  tests/test_dw2_feed_resources.py
+// holds both kernels to four waves per SIMD and four workgroups per CU.)
+__global__ __launch_bounds__(256) void gemm_f32_dw2_head_kernel(GemmJob ja, GemmJob jb, int n_a, HeadLeaf hl, int n_head, int feed) {
   struct Lds { float As[2][BK][LD]; float Bs[2][BK][LD]; float pad[kDw2HeadLds - 2 * 2 * BK * LD]; };
   __shared__ __attribute__((aligned(16))) Lds sm;
   static_assert(2 * 2 * BK * LD <= kDw2HeadLds, "tile images");
@@ -383,16 +500,8 @@ __global__ __launch_bounds__(256) void gemm_f32_dw2_head_kernel(GemmJob ja, Gemm
     return;
   }
   bid -= n_head;
-  if (bid < n_a) {
-    const int bx = bid % ja.gx, t = bid / ja.gx;
-    gemm_f32_tile<false, false>(ja.a, ja.lda, ja.b, ja.ldb, ja.c, ja.ldc, ja.M, ja.Nc, ja.K, ja.kchunk, ja.ep, ja.vec_a,
-                                ja.vec_b, bx, t % ja.gy, t / ja.gy, ja.gz, sm.As, sm.Bs);
-  } else {
-    bid -= n_a;
-    const int bx = bid % jb.gx, t = bid / jb.gx;
-    gemm_f32_tile<false, false>(jb.a, jb.lda, jb.b, jb.ldb, jb.c, jb.ldc, jb.M, jb.Nc, jb.K, jb.kchunk, jb.ep, jb.vec_a,
-                                jb.vec_b, bx, t % jb.gy, t / jb.gy, jb.gz, sm.As, sm.Bs);
-  }
+  if (bid < n_a) dw_tile(ja, bid, feed, sm.As, sm.Bs);
+  else dw_tile(jb, bid - n_a, feed, sm.As, sm.Bs);
 }
 
 // Second stage of the deterministic split-K: out[i] = sum_s part[s][i].  Block = 64 outputs x 4
@@ -1549,11 +1658,23 @@ int gcnx_gemm_dw2(gcnx_ctx* ctx, const float* xa, int64_t ldxa, const float* dha
   const bool merged = leaf && leaf->c == 2 && gcnx_head::head_lds_floats(leaf->h, leaf->c, want_db) <= (size_t)kDw2HeadLds &&
                       leaf->b <= gcnx_head::kHeadRows;
   if (leaf && !merged) { rc = gcnx_head_from_parts(ctx, leaf); if (rc) return rc; }   // (many graphs / wide operands: its own launch)
+  const int feed = ctx->knob_dw2_feed != 0;        // GCNX_DW2_FEED=0: every tile through gemm_f32_tile
 #ifdef GCNX_TUNING
   const char* dbg_env = getenv("GCNX_DW2_DBG");          // 1: no tile launch -- the reduction launch alone, on whatever the
-  const bool tiles_off = dbg_env && atoi(dbg_env) == 1;  // workspace holds (results wrong by design; scripts/fused_bench.py)
+  const bool tiles_off = dbg_env && atoi(dbg_env) == 1;  // workspace holds; 2: the tile launch alone, no reduction (results
+  const bool reduce_off = dbg_env && atoi(dbg_env) == 2; // wrong by design; scripts/fused_bench.py)
+  // GCNX_DW2_STAMPS=k: the k-th call of the process stamps its tile workgroups (GCNX_DWSTAMP) and prints the phase split
+  static unsigned long long* stamp_buf = nullptr;
+  static int stamp_calls = 0;
+  const char* stamp_env = getenv("GCNX_DW2_STAMPS");
+  const bool stamp_now = stamp_env && !ctx->capturing && ++stamp_calls == atoi(stamp_env);
+  if (stamp_now) {
+    if (!stamp_buf) (void)hipMalloc((void**)&stamp_buf, (size_t)kDw2StampWgs * 4 * sizeof(unsigned long long));
+    (void)hipMemsetAsync(stamp_buf, 0, (size_t)kDw2StampWgs * 4 * sizeof(unsigned long long), ctx->stream);
+    (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(g_dw2_stamps), &stamp_buf, sizeof(stamp_buf), 0, hipMemcpyHostToDevice, ctx->stream);
+  }
 #else
-  constexpr bool tiles_off = false;
+  constexpr bool tiles_off = false, reduce_off = false;
 #endif
   if (tiles_off) {
   } else if (merged) {
@@ -1562,11 +1683,36 @@ int gcnx_gemm_dw2(gcnx_ctx* ctx, const float* xa, int64_t ldxa, const float* dha
                 gcnx_head::PoolParts{leaf->pool_sum, leaf->graph_ptr, leaf->pooled, 1, leaf->pool_mode == GCNX_POOL_AVG ? 1 : 0,
                                      want_db ? leaf->pool_cnt : nullptr, want_db ? leaf->db_relu : nullptr},
                 leaf->cce_mode == GCNX_CCE_LOGITS ? 1 : 0};
-    hipLaunchKernelGGL(gemm_f32_dw2_head_kernel, dim3(1 + n_a + n_b), dim3(256), 0, ctx->stream, ja, jb, n_a, hl, 1);
+    hipLaunchKernelGGL(gemm_f32_dw2_head_kernel, dim3(1 + n_a + n_b), dim3(256), 0, ctx->stream, ja, jb, n_a, hl, 1, feed);
   } else {
-    hipLaunchKernelGGL(gemm_f32_dw2_kernel, dim3(n_a + n_b), dim3(256), 0, ctx->stream, ja, jb, n_a);
+    hipLaunchKernelGGL(gemm_f32_dw2_kernel, dim3(n_a + n_b), dim3(256), 0, ctx->stream, ja, jb, n_a, feed);
   }
   GCNX_LAUNCH_OK(ctx);
+#ifdef GCNX_TUNING
+  if (stamp_now) {     // per phase: mean and max over the tile workgroups, and the launch's span (first entry -> last store)
+    const int first = merged ? 1 : 0, nwg = std::min(first + n_a + n_b, kDw2StampWgs);
+    std::vector<unsigned long long> h((size_t)nwg * 4);
+    unsigned long long* off = nullptr;
+    (void)hipMemcpyAsync(h.data(), stamp_buf, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream);
+    (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(g_dw2_stamps), &off, sizeof(off), 0, hipMemcpyHostToDevice, ctx->stream);
+    (void)hipStreamSynchronize(ctx->stream);
+    double sum[3] = {0, 0, 0}, mx[3] = {0, 0, 0};
+    unsigned long long t_first = ~0ull, t_last = 0;
+    int cnt = 0;
+    for (int w = first; w < nwg; ++w) {
+      const unsigned long long* t = &h[(size_t)w * 4];
+      if (!t[0] || !t[1] || !t[2] || !t[3]) continue;        // (ragged tiles: gemm_f32_tile's guarded loop leaves no phase stamps)
+      for (int k = 0; k < 3; ++k) { const double d = (double)(t[k + 1] - t[k]) * 0.01; sum[k] += d; mx[k] = std::max(mx[k], d); }
+      t_first = std::min(t_first, t[0]); t_last = std::max(t_last, t[3]);
+      ++cnt;
+    }
+    fprintf(stderr, "[dw2 stamps feed %d] %d interior tile workgroups (%d slices x %d tiles), us mean / max:  entry -> step 0 in LDS %.2f / %.2f"
+            "  K loop %.2f / %.2f  loop end -> stores landed %.2f / %.2f  whole %.2f;  first entry -> last store %.2f us\n",
+            feed, cnt, nsplit, (n_a + n_b) / nsplit, sum[0] / cnt, mx[0], sum[1] / cnt, mx[1], sum[2] / cnt, mx[2],
+            (sum[0] + sum[1] + sum[2]) / cnt, cnt ? (double)(t_last - t_first) * 0.01 : 0.0);
+  }
+#endif
+  if (reduce_off) return GCNX_OK;
   // one reduction launch either way: with params == NULL reduce_sgd_kernel only folds (offsets relative to `base`).
   // Product a is the launch's own reduction, product b rides in the pending split-K slot (free: shapes_ok).
   float* base = params ? grads : std::min(dwa, dwb);

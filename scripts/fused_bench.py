@@ -2,7 +2,7 @@
 """Fused GCNConv launch times at config-2 shapes (tuning aid): forward, backward, the two-gradient GEMM; HIP events.
 GCNX_FUSED_DBG (tuning build only) ablates phases: 1 no gather, 2 no MFMA, 4 no weight load.  The backward is timed in its
 fp32-row form and in its byte-mask form (gcn_conv_bwd_pool(mask8=...)).  GCNX_DW2_DBG=1 (tuning build, set here) leaves the
-two-gradient GEMM's reduction launch on its own; that line needs GCNX_LIB=.../libgcnx_tuning.so (scripts/build_tuning.sh)."""
+two-gradient GEMM's reduction launch on its own, =2 its tile launch (timed with the knob dw2_feed on and off); those lines need GCNX_LIB=.../libgcnx_tuning.so (scripts/build_tuning.sh)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "gcn-string_amd"))
@@ -57,7 +57,19 @@ if os.environ.get("GCNX_LIB", "").endswith("tuning.so"):
     print("dw2 + reduce + sgd: %.1f us" % timeit(dw2_sgd))
     os.environ["GCNX_DW2_DBG"] = "1"
     print("reduce + sgd alone (%d partial rows): %.1f us" % (pend.crows, timeit(dw2_sgd)))
+    # the tile launch alone (GCNX_DW2_DBG=2 drops the reduction) with dw_tile_interior and with gemm_f32_tile (knob dw2_feed),
+    # alternated in this process on the same operands: five readings a side
+    os.environ["GCNX_DW2_DBG"] = "2"
+    tiles = {1: [], 0: []}
+    for _ in range(5):
+        for feed in (1, 0):
+            ctx.set_tuning("dw2_feed", feed)
+            tiles[feed].append(timeit(dw2_sgd, iters=200))
+    ctx.set_tuning("dw2_feed", 1)
     del os.environ["GCNX_DW2_DBG"]
+    fmt = lambda v: " ".join("%.2f" % t for t in v) + "  (median %.2f)" % float(np.median(v))
+    print("dw2 tiles alone, dw_tile_interior: %s us" % fmt(tiles[1]))
+    print("dw2 tiles alone, gemm_f32_tile   : %s us" % fmt(tiles[0]))
 h = ctx.empty((hb.n, f))
 print("gemm + spmm      : %.1f us" % timeit(lambda: (D.gemm(ctx, x, w, None, h), D.spmm(ctx, a, h, b, out, act="relu"))))
 ctx.close()

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""GEMM microbenchmark (tuning aid): the three GCNConv/Dense GEMM entry points over a list of shapes.
+"""GEMM microbenchmark (tuning aid): the GCNConv/Dense GEMM entry points (and the two-gradient launch) over a list of shapes.
     python scripts/gemm_bench.py [--n 20498] [--prec f32] [--iters 20]"""
 import argparse, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -22,17 +22,21 @@ for sh in args.shapes.split(","):
     w = ctx.to_device((rng.standard_normal((fi, fo)) / np.sqrt(fi)).astype(np.float32))
     dh = ctx.to_device(rng.standard_normal((n, fo), dtype=np.float32))
     out, dx, dw, dbv = ctx.empty((n, fo)), ctx.empty((n, fi)), ctx.empty((fi, fo)), ctx.empty(fi)
+    g2 = ctx.empty(2 * fi * fo)
     res = []
     for name, fn in (("fwd", lambda: D.gemm(ctx, x, w, None, out, prec=args.prec)),
                      ("dx", lambda: D.gemm_dx(ctx, dh, w, dx, prec=args.prec)),
                      ("dx+mask", lambda: D.gemm_dx(ctx, dh, w, dx, prec=args.prec, y_mask=x)),
                      ("dx+mask+db", lambda: D.gemm_dx(ctx, dh, w, dx, prec=args.prec, y_mask=x, db=dbv)),
-                     ("dw", lambda: D.gemm_dw(ctx, x, dh, dw, prec=args.prec))):
+                     ("dw", lambda: D.gemm_dw(ctx, x, dh, dw, prec=args.prec)),
+                     # two products in one launch + their reduction (gcnx_gemm_dw2); TF/s counts both
+                     ("dw2", lambda: D.gemm_dw2(ctx, x, dh, g2.flat(0, fi * fo, (fi, fo)), x, dh, g2.flat(fi * fo, fi * fo, (fi, fo)),
+                                                prec=args.prec, grads=g2))):
         for _ in range(3): fn()
         e0 = ctx.event().record()
         for _ in range(args.iters): fn()
         e1 = ctx.event().record()
         us = e1.elapsed_ms_since(e0) / args.iters * 1e3
-        res.append(f"{name} {us:7.1f} us {2.0*n*fi*fo/us/1e6:6.1f} TF/s")
+        res.append(f"{name} {us:7.1f} us {(2 if name == 'dw2' else 1)*2.0*n*fi*fo/us/1e6:6.1f} TF/s")
     print(f"N={n} {fi:4d}x{fo:<4d} {args.prec}: " + "   ".join(res), flush=True)
 ctx.close()
