@@ -11,7 +11,7 @@ from .loader import Dataset, DisjointLoader, Graph, ListDataset, NetworkxDataset
 from .train import PiecewiseConstantDecay, auc, binary_acc, fit, roc_curve
 
 __all__ = ["Dataset", "DisjointLoader", "Graph", "ListDataset", "NetworkxDataset", "from_networkx", "entry_edge_features", "format_graph", "SparseTensor", "Context", "default_context", "GCNConv", "GeneralConv",
-           "ECCConv", "SAGEConv", "TopKPool", "GlobalSumPool", "GlobalAvgPool", "GlobalMaxPool", "Dense", "BatchNorm1d", "PReLU", "GCN2", "GCN", "SAGE", "GeneralGNN", "ECCNet", "TopKNet", "DeviceBatch",
+           "ECCConv", "SAGEConv", "GATConv", "TopKPool", "GlobalSumPool", "GlobalAvgPool", "GlobalMaxPool", "Dense", "BatchNorm1d", "PReLU", "GCN2", "GCN", "SAGE", "GAT", "GeneralGNN", "ECCNet", "TopKNet", "DeviceBatch",
            "save_to_npz", "load_weights_npz", "best_epoch", "DeviceDataset", "DeviceDisjointLoader",
            "PiecewiseConstantDecay", "fit", "roc_curve", "auc", "binary_acc"]
 
@@ -20,13 +20,13 @@ def __getattr__(name):  # device-side names load libgcnx lazily, host-only use n
     if name in ("Context", "default_context", "DeviceArray", "DeviceCSR", "Segments"):
         from . import device
         return getattr(device, name)
-    if name in ("GCNConv", "GeneralConv", "ECCConv", "SAGEConv", "TopKPool", "GlobalSumPool", "GlobalAvgPool", "GlobalMaxPool", "Dense", "BatchNorm1d", "PReLU"):
+    if name in ("GCNConv", "GeneralConv", "ECCConv", "SAGEConv", "GATConv", "TopKPool", "GlobalSumPool", "GlobalAvgPool", "GlobalMaxPool", "Dense", "BatchNorm1d", "PReLU"):
         from . import layers
         return getattr(layers, name)
     if name in ("DeviceDataset", "DeviceDisjointLoader", "collate_on_device"):
         from . import device_loader
         return getattr(device_loader, name)
-    if name in ("GCN2", "GCN", "SAGE", "GeneralGNN", "ECCNet", "TopKNet", "DeviceBatch", "evaluate"):
+    if name in ("GCN2", "GCN", "SAGE", "GAT", "GeneralGNN", "ECCNet", "TopKNet", "DeviceBatch", "evaluate"):
         from . import models
         return getattr(models, name)
     raise AttributeError(name)

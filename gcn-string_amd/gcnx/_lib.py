@@ -157,6 +157,13 @@ SIGNATURES = {
                       _i64, _f32, _vp, _vp],
     "gcnx_sage_conv_ok": [_i64, _i32, _i32, _i64],
     "gcnx_sage_conv": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _int, _vp, _vp, _i64, _vp, _i64],
+    "gcnx_gat_conv_ok": [_i64, _i32, _i32, _i64],
+    "gcnx_gat_scores": [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp],
+    "gcnx_gat_aggregate": [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _f32, _vp, _i64, _vp, _vp, _i64],
+    "gcnx_gat_bwd_edges": [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _f32, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp],
+    "gcnx_gat_bwd_scratch_floats": [_i64, _i32, _i32],
+    "gcnx_gat_bwd_nodes": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp,
+                           _vp, _vp],
     "gcnx_topk_select_ok": [_i64, _i32],
     "gcnx_topk_select": [_vp, _vp, _vp, _i32, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _vp],
     "gcnx_topk_gather": [_vp, _vp, _i64, _vp, _vp, _i32, _i32, _int, _vp, _i64],
@@ -169,7 +176,7 @@ SIGNATURES = {
 }
 _RESTYPE = {"gcnx_last_error": C.c_char_p, "gcnx_dense_bwd_scratch_floats": C.c_int64, "gcnx_bce_head_scratch_floats": C.c_int64,
             "gcnx_bce_head_phase_scratch_floats": C.c_int64, "gcnx_bce_head_phase_red_floats": C.c_int64,
-            "gcnx_gcn_conv_bwd_scratch_floats": C.c_int64, "gcnx_wimage_elems": C.c_int64, "gcnx_gemm_wimage_parts": C.c_int64}
+            "gcnx_gcn_conv_bwd_scratch_floats": C.c_int64, "gcnx_gat_bwd_scratch_floats": C.c_int64, "gcnx_wimage_elems": C.c_int64, "gcnx_gemm_wimage_parts": C.c_int64}
 
 
 class WimageJob(C.Structure):

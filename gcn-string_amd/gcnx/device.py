@@ -791,6 +791,64 @@ def sage_conv(ctx, a, x, w_nb, w_root, bias, out, s=None, w_transposed=False):
     return out
 
 
+def gat_conv_ok(ctx, n, heads, c, ldh=None):
+    """True if the GATConv kernels serve these shapes (gcnx_gat_conv_ok)."""
+    return bool(ctx.lib.gcnx_gat_conv_ok(int(n), int(heads), int(c), int(ldh if ldh is not None else heads * c)))
+
+
+def gat_bwd_scratch_floats(ctx, n, heads, c):
+    return int(ctx.lib.gcnx_gat_bwd_scratch_floats(int(n), int(heads), int(c)))
+
+
+def gat_scores(ctx, hf, att_src, att_dst, a_src, a_dst):
+    """a_src[j, h] = <hf[j, h, :], att_src[h, :]>, a_dst likewise (gcnx_gat_scores).  att_*: [heads, c]; a_*: [n, heads]."""
+    n, (heads, c) = hf.shape[0], att_src.shape
+    assert hf.shape[1] == heads * c and att_dst.shape == (heads, c) and a_src.shape == a_dst.shape == (n, heads)
+    assert att_src.contiguous and att_dst.contiguous and a_src.contiguous and a_dst.contiguous
+    ctx._ck(ctx.lib.gcnx_gat_scores(ctx.h, _p(hf), hf.ld, n, heads, c, _p(att_src), _p(att_dst), _p(a_src), _p(a_dst)))
+    return a_src, a_dst
+
+
+def gat_aggregate(ctx, a, hf, a_src, a_dst, bias, out, alpha=None, o_pre=None, slope=0.2):
+    """out = softmax-weighted gather of hf over the stored entries of ``a`` (row = target) + bias; alpha [nnz, heads] and
+    o_pre (the result before the bias) are stored if given (gcnx_gat_aggregate)."""
+    n, heads = a_src.shape
+    hc = hf.shape[1]
+    assert a.n == n == hf.shape[0] and hc % heads == 0 and a_dst.shape == (n, heads) and out.shape == (n, hc)
+    assert (alpha is None or (alpha.shape == (a.nnz, heads) and alpha.contiguous)) and (o_pre is None or o_pre.shape == (n, hc))
+    assert (bias is None or bias.shape == (hc,)) and a_src.contiguous and a_dst.contiguous
+    ctx._ck(ctx.lib.gcnx_gat_aggregate(ctx.h, a.rowptr.ptr, a.colidx.ptr, _p(hf), hf.ld, n, heads, hc // heads, _p(a_src), _p(a_dst),
+                                       _p(bias), float(slope), _p(out), out.ld, _p(alpha), _p(o_pre),
+                                       o_pre.ld if o_pre is not None else 0))
+    return out
+
+
+def gat_bwd_edges(ctx, a, hf, a_src, a_dst, alpha, dout, o, dz, da_dst, o_bias=None, slope=0.2):
+    """dz [nnz, heads] (the CSR's entry order) and da_dst [n, heads] from dout and O = o (- o_bias) (gcnx_gat_bwd_edges)."""
+    n, heads = a_src.shape
+    hc = hf.shape[1]
+    assert a.n == n and dout.shape == o.shape == (n, hc) and alpha.shape == dz.shape == (a.nnz, heads) and da_dst.shape == (n, heads)
+    assert alpha.contiguous and dz.contiguous and da_dst.contiguous and a_src.contiguous and a_dst.contiguous
+    ctx._ck(ctx.lib.gcnx_gat_bwd_edges(ctx.h, a.rowptr.ptr, a.colidx.ptr, _p(hf), hf.ld, n, heads, hc // heads, _p(a_src), _p(a_dst),
+                                       float(slope), _p(alpha), _p(dout), dout.ld, _p(o), o.ld, _p(o_bias), _p(dz), _p(da_dst)))
+    return dz, da_dst
+
+
+def gat_bwd_nodes(ctx, a, alpha, dz, dout, hf, da_dst, att_src, att_dst, dhf, da_src, datt_src, datt_dst, scratch):
+    """dhf, da_src, datt_src, datt_dst on the transposed pattern of ``a`` with its entry permutation (a.transpose_perm();
+    gcnx_gat_bwd_nodes).  scratch: gat_bwd_scratch_floats floats."""
+    n, (heads, c) = a.n, att_src.shape
+    assert dout.shape == hf.shape == dhf.shape == (n, heads * c) and alpha.shape == dz.shape == (a.nnz, heads)
+    assert da_dst.shape == da_src.shape == (n, heads) and datt_src.shape == datt_dst.shape == att_dst.shape == (heads, c)
+    assert scratch.size >= gat_bwd_scratch_floats(ctx, n, heads, c)
+    assert all(t.contiguous for t in (alpha, dz, da_dst, da_src, att_src, att_dst, datt_src, datt_dst))
+    rp, ci, pm = a.transpose_perm()
+    ctx._ck(ctx.lib.gcnx_gat_bwd_nodes(ctx.h, rp.ptr, ci.ptr, pm.ptr, n, heads, c, _p(alpha), _p(dz), _p(dout), dout.ld, _p(hf), hf.ld,
+                                       _p(da_dst), _p(att_src), _p(att_dst), _p(dhf), dhf.ld, _p(da_src), _p(datt_src), _p(datt_dst),
+                                       _p(scratch)))
+    return dhf
+
+
 def topk_select_ok(ctx, max_graph_rows, f):
     """True if topk_select serves a batch whose largest graph has this many rows (gcnx_topk_select_ok)."""
     return bool(ctx.lib.gcnx_topk_select_ok(int(max_graph_rows), int(f)))

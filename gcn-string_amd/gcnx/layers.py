@@ -6,7 +6,8 @@ kernel_initializer="glorot_uniform", bias_initializer="zeros")`` called as ``lay
 Reference topology: GCNConv -> GCNConv -> global pool -> Linear (gcn_utills.py:805-808,
 832-842); live model ctor gcn.py:320, forward gcn.py:334/351, gradients gcn.py:337.
 ``SAGEConv(channels, root_weight=True, use_bias=True)`` is PyG's layer of that name (aggr="mean"), which the reference
-names as its next step (gcn_utills.py:804-806).  ``TopKPool(ratio)`` is Spektral's pooling layer of that name, which the
+names as its next step (gcn_utills.py:804-806); ``GATConv(channels, heads=1)`` is PyG's attention layer for the same slot.
+``TopKPool(ratio)`` is Spektral's pooling layer of that name, which the
 reference's script imports (gcn.py:10), called as ``layer([x, a, seg])``.
 
 There is no autograd here: every layer has ``backward(dy)`` that returns dx and leaves the
@@ -259,6 +260,97 @@ class SAGEConv(Layer):
         D.spmm(ctx, a.transpose(), t, None, dx)                                     # A^T (dY W_l^T)
         if self.root_weight:
             D.gemm_dx(ctx, dy, p["lin_r.weight"], dx, accumulate=True)              # + dY W_r^T
+        return dx
+
+
+class GATConv(Layer):
+    """torch_geometric.nn.GATConv(in, channels, heads, concat=True, negative_slope=0.2, dropout=0.0, bias=True) -- the attention
+    layer for the slot the reference's author marked as open (gcn_utills.py:804-806); spektral.layers.GATConv is the same layer:
+
+        Hf = x W    e_ij,h = LeakyReLU(<Hf[j,h,:], att_src[h,:]> + <Hf[i,h,:], att_dst[h,:]>)    alpha = softmax over the row's entries
+        out[i,h,:] = sum_j alpha_ij,h Hf[j,h,:] + bias
+
+    ``GATConv(channels, heads=1, concat=True, negative_slope=0.2, use_bias=True, activation=None)``, called as ``layer([x, a])``
+    with ``a = GATConv.preprocess(a)``: the stored pattern of ``a`` (row = target), values ignored, no loop added or removed; a
+    row without entries gives the bias.  Parameters under PyG's names and in its named_parameters() order: ``att_src``,
+    ``att_dst`` (stored [heads, channels]; ``state_dict()`` gives PyG's [1, heads, channels]), ``bias`` [heads * channels],
+    ``lin.weight`` (stored [in, heads * channels]; PyG: [heads * channels, in]); glorot-uniform as PyG, the bias zero.
+    ``backward(dy, need_dx=True)`` returns dx (None with need_dx=False) and leaves the four gradients in ``grads``.
+
+    Launches (csrc/gat.hip): gcnx_gemm, gcnx_gat_scores, gcnx_gat_aggregate forward; gcnx_act_bias_grad, gcnx_gat_bwd_edges,
+    gcnx_gat_bwd_nodes, gcnx_gemm_dw, gcnx_gemm_dx backward.  There is no composed route: what the kernels do not serve
+    (concat=False, attention dropout, edge features, shapes gcnx_gat_conv_ok refuses) raises NotImplementedError."""
+
+    def __init__(self, channels, heads=1, concat=True, negative_slope=0.2, use_bias=True, activation=None, dropout=0.0, edge_dim=None,
+                 **kw):
+        super().__init__(**kw)
+        if not concat:
+            raise NotImplementedError("GATConv concat=False (the mean over heads) has no kernel: only concat=True")
+        if dropout:
+            raise NotImplementedError(f"GATConv dropout={dropout}: attention dropout has no kernel (only dropout=0)")
+        if edge_dim is not None:
+            raise NotImplementedError("GATConv edge features (edge_dim / lin_edge) have no kernel")
+        if activation not in (None, "linear"):
+            raise NotImplementedError(f"GATConv activation {activation!r}: the layer is linear (follow it with BatchNorm1d / PReLU)")
+        self.channels, self.heads, self.negative_slope = int(channels), int(heads), float(negative_slope)
+        self.concat, self.use_bias, self.activation = True, bool(use_bias), activation
+
+    @staticmethod
+    def preprocess(a):
+        """The unweighted view of a DeviceCSR: the pattern as stored, no loop added or removed."""
+        return a.unweighted()
+
+    def _param_spec(self, in_dim):
+        h, c = self.heads, self.channels
+        lim = np.sqrt(6.0 / (h + c))                       # PyG's glorot on the [1, heads, channels] tensor
+        att = lambda: self._rng.uniform(-lim, lim, (h, c)).astype(np.float32)
+        spec = [("att_src", (h, c), att()), ("att_dst", (h, c), att())]
+        if self.use_bias:
+            spec.append(("bias", (h * c,), np.zeros(h * c, np.float32)))
+        spec.append(("lin.weight", (in_dim, h * c), glorot_uniform(self._rng, in_dim, h * c)))
+        return spec
+
+    def state_dict(self):
+        """{PyG name: array in PyG's layout}: att_* [1, heads, channels], lin.weight [heads * channels, in]."""
+        d = {k: v.numpy() for k, v in self.params.items()}
+        d["att_src"], d["att_dst"], d["lin.weight"] = d["att_src"][None], d["att_dst"][None], d["lin.weight"].T.copy()
+        return d
+
+    def call(self, inputs, out=None):
+        if len(inputs) != 2:
+            raise NotImplementedError("GATConv takes [x, a]: edge features have no kernel")
+        x, a = inputs
+        h, c = self.heads, self.channels
+        if not D.gat_conv_ok(x.ctx, x.shape[0], h, c):
+            raise NotImplementedError(f"GATConv heads={h} channels={c} on {x.shape[0]} rows: the kernels serve heads in {{1, 2, 4, 8}}, "
+                                      "heads * channels in {16, 32, 64, 128}, channels >= 4 and rows * heads * channels * 4 < 2^32")
+        if not self.built:
+            self.build(x.ctx, x.shape[1])
+        ctx, n, p = self.ctx, x.shape[0], self.params
+        y = out if out is not None else self._buf("y", (n, h * c))
+        hf, o = self._buf("hf", (n, h * c)), self._buf("o", (n, h * c))
+        asrc, adst, alpha = self._buf("asrc", (n, h)), self._buf("adst", (n, h)), self._buf("alpha", (a.nnz, h))
+        D.gemm(ctx, x, p["lin.weight"], None, hf)
+        D.gat_scores(ctx, hf, p["att_src"], p["att_dst"], asrc, adst)
+        D.gat_aggregate(ctx, a, hf, asrc, adst, p.get("bias"), y, alpha=alpha, o_pre=o, slope=self.negative_slope)
+        self._saved = (x, a, hf, asrc, adst, alpha, o)
+        return y
+
+    def backward(self, dy, need_dx=True):
+        x, a, hf, asrc, adst, alpha, o = self._saved
+        ctx, p, g, h, c, n = self.ctx, self.params, self.grads, self.heads, self.channels, x.shape[0]
+        if self.use_bias:
+            D.act_bias_grad(ctx, dy, None, dy, None, db=g["bias"])                  # column sums of dy
+        dz, dadst, dasrc = self._buf("dz", (a.nnz, h)), self._buf("dadst", (n, h)), self._buf("dasrc", (n, h))
+        dhf = self._buf("dhf", (n, h * c))
+        scratch = self._buf("scratch", (max(D.gat_bwd_scratch_floats(ctx, n, h, c), 1),))
+        D.gat_bwd_edges(ctx, a, hf, asrc, adst, alpha, dy, o, dz, dadst, slope=self.negative_slope)
+        D.gat_bwd_nodes(ctx, a, alpha, dz, dy, hf, dadst, p["att_src"], p["att_dst"], dhf, dasrc, g["att_src"], g["att_dst"], scratch)
+        D.gemm_dw(ctx, x, dhf, g["lin.weight"])                                     # dW = x^T dHf
+        if not need_dx:
+            return None
+        dx = self._buf("dx", x.shape)
+        D.gemm_dx(ctx, dhf, p["lin.weight"], dx)                                    # dx = dHf W^T
         return dx
 
 

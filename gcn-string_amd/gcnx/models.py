@@ -16,6 +16,9 @@ Linear·BatchNorm1d·PReLU twice, one logit with BCEWithLogitsLoss (eager launch
 ``SAGE``: ``GCN`` with PyG's SAGEConv(aggr="mean") in the place of both GCNConv layers, the step the reference's author notes
 above them (gcn_utills.py:804-806); one launch per convolution (csrc/sage.hip).
 
+``GAT``: ``GCN`` with PyG's GATConv(heads, concat=True) in the place of both GCNConv layers: a softmax over the stored
+entries of every row with learned scores (csrc/gat.hip).
+
 ``TopKNet``: GCNConv -> TopKPool -> GCNConv -> global pool -> Dense(softmax), with the pooling layer the reference's script imports
 (gcn.py:10); selection, gather and the induced adjacency on the device (csrc/topk.hip), eager launches.
 """
@@ -1821,6 +1824,156 @@ class SAGE(GCN):
         dz1 = bufs["dz1"]
         D.act_bias_grad(ctx, dz1, None, dz1, None, db=g["b1"])
         D.gemm_dw2(ctx, bufs["s1"], dz1, g["wl1"], batch.x, dz1, g["wr1"])           # dW_l1 = S1^T dZ1, dW_r1 = x^T dZ1
+
+
+class GAT(GCN):
+    """``GCN`` with its two GCNConv layers replaced by PyG's GATConv(heads=H, concat=True, negative_slope=0.2, dropout=0), the
+    attention layer for the slot the reference's author marked as open (gcn_utills.py:804-806):
+
+        GATConv(F->H/heads, heads)·BN·PReLU -> GATConv(H->H/heads, heads)·BN·PReLU -> global_max_pool -> Linear(H->H)·BN·PReLU
+        -> Linear(H->1)·BN·PReLU
+
+    ``GAT([ctx,] hidden_channels=64, heads=1, num_classes=1, seed=0, comm=None)``; hidden_channels in {16, 32, 64, 128}, a
+    multiple of heads in {1, 2, 4, 8} with at least 4 channels per head (what csrc/gat.hip serves; there is no composed route).
+    A host adjacency gets PyG's remaining self-loops, as ``GCN`` (GATConv's remove-then-add gives the same pattern once values
+    are ignored); a DeviceCSR is used as stored.  ``forward(x, edge_index, batch)`` counts duplicate edges once, as ``GCN``
+    does -- PyG would give a duplicated edge two softmax terms: a deviation.  Everything behind the convolutions is ``GCN``'s:
+    BN·PReLU, the fused max-pool pair, the one-launch BCE head, sync-BN over shards (``comm=``; attention never leaves a
+    graph), ``fit``.
+
+    Hot path per convolution: gcnx_gemm (Hf = x W), gcnx_gat_scores, gcnx_gat_aggregate; backward gcnx_act_bias_grad,
+    gcnx_gat_bwd_edges (forward CSR), gcnx_gat_bwd_nodes (transposed pattern + entry permutation, built once per batch),
+    gcnx_gemm_dw, gcnx_gemm_dx.
+
+    Weights: PyG's key names ``conv{1,2}.att_src``, ``.att_dst`` ([1, heads, C]), ``.bias``, ``.lin.weight`` ([out, in], as
+    torch; stored [in, out] here) in ``state_dict()``, listed by ``get_weights()`` in named_parameters() order.  That order
+    follows PyG 2.x's source; neither torch_geometric nor a checkpoint was available to confirm it against a live module, so
+    prefer the named dicts.  Initialisation: glorot-uniform for the attention vectors and the weights, zero bias, as PyG."""
+
+    PARAM_ORDER = ("as1", "ad1", "b1", "w1", "as2", "ad2", "b2", "w2", "g1", "be1", "a1", "g2", "be2", "a2",
+                   "w3", "b3", "g3", "be3", "a3", "w4", "b4", "g4", "be4", "a4")
+    TORCH_KEYS = (("conv1.att_src", "as1", False), ("conv1.att_dst", "ad1", False), ("conv1.bias", "b1", False),
+                  ("conv1.lin.weight", "w1", True),
+                  ("conv2.att_src", "as2", False), ("conv2.att_dst", "ad2", False), ("conv2.bias", "b2", False),
+                  ("conv2.lin.weight", "w2", True)) + GCN.TORCH_KEYS[4:]
+    PROBE_KEY = "conv1.lin.weight"
+    ATT_KEYS = ("conv1.att_src", "conv1.att_dst", "conv2.att_src", "conv2.att_dst")
+    SLOPE = 0.2
+
+    def _init(self, ctx, hidden_channels=64, heads=1, num_classes=1, seed=0, comm=None):
+        h, heads = int(hidden_channels), int(heads)
+        if heads not in (1, 2, 4, 8) or h % heads != 0:
+            raise NotImplementedError(f"gcnx.GAT: heads={heads} must be 1, 2, 4 or 8 and divide hidden_channels={h}")
+        if h not in (16, 32, 64, 128) or h // heads < 4:
+            raise NotImplementedError(f"gcnx.GAT: hidden_channels={h} must be 16, 32, 64 or 128 with at least 4 channels per head "
+                                      "(the widths the GATConv kernels serve; there is no composed route)")
+        super()._init(ctx, h, num_classes, seed, comm)
+        self.heads = heads
+
+    def _shapes(self, f_in):
+        s = super()._shapes(f_in)
+        hc = (self.heads, self.hidden // self.heads)
+        s.update(as1=hc, ad1=hc, as2=hc, ad2=hc)
+        return s
+
+    def build(self, f_in):
+        h, heads = self.hidden, self.heads
+        shapes = self._shapes(f_in)
+        self.f_in = int(f_in)
+        # every parameter starts on a 16-byte boundary (the kernels read att_*, the bias and W as float4); the padding floats
+        # have zero gradients, so the single SGD launch over the whole buffer leaves them at zero
+        self._alloc_flat([(k, shapes[k]) for k in self.PARAM_ORDER], align=4)
+        rng, lim, alim = self._rng, 1.0 / np.sqrt(h), np.sqrt(6.0 / (heads + h // heads))
+        att = lambda: rng.uniform(-alim, alim, shapes["as1"])
+        init = {"as1": att(), "ad1": att(), "w1": glorot_uniform(rng, f_in, h), "as2": att(), "ad2": att(), "w2": glorot_uniform(rng, h, h),
+                "w3": rng.uniform(-lim, lim, (h, h)), "b3": rng.uniform(-lim, lim, h),
+                "w4": rng.uniform(-lim, lim, (1, h)), "b4": rng.uniform(-lim, lim, 1)}
+        for k in ("g1", "g2", "g3", "g4"):
+            init[k] = np.ones(shapes[k])
+        for k in ("a1", "a2", "a3", "a4"):
+            init[k] = np.full(1, 0.25)
+        for k, v in init.items():
+            self.p[k].copy_from_host(np.asarray(v, np.float32))
+        self.built = True
+
+    # the attention vectors are [1, heads, C] in PyG's layout and [heads, C] here
+    def state_dict(self):
+        d = super().state_dict()
+        d.update({k: d[k][None] for k in self.ATT_KEYS})
+        return d
+
+    def gradients(self):
+        d = super().gradients()
+        d.update({k: d[k][None] for k in self.ATT_KEYS})
+        return d
+
+    def load_state_dict(self, d):
+        d = dict(d)
+        for k in self.ATT_KEYS:
+            if k in d and np.ndim(d[k]) == 3 and np.shape(d[k])[0] == 1:
+                d[k] = np.asarray(d[k])[0]
+        super().load_state_dict(d)
+
+    def _op(self, batch):
+        """The unweighted pattern of the batch, twice: the backward walks its transposed pattern through the entry permutation
+        (DeviceCSR.transpose_perm, built here, once per batch object)."""
+        if self._op_cache is None or self._op_cache[0] != batch.uid:
+            a = batch.a.unweighted()
+            a.transpose_perm()
+            self._op_cache = (batch.uid, a, a)
+        return self._op_cache[1], self._op_cache[2]
+
+    def _ensure(self, batch, sharded=False):
+        bufs = super()._ensure(batch, sharded)
+        nnz = batch.a.nnz
+        if bufs.get("gat_key") != (batch.n, batch.n_graphs, nnz):          # the edge buffers follow nnz as well as (n, b)
+            v, n, h, heads = self._views(), batch.n, self.hidden, self.heads
+            if not D.gat_conv_ok(self.ctx, n, heads, h // heads):
+                raise NotImplementedError(f"gcnx.GAT: a batch of {n} rows at hidden_channels={h} is beyond the GATConv kernels")
+            for k in ("hf1", "hf2", "o1", "o2", "dhf"):
+                bufs[k] = v(k, n, h)
+            for k in ("asrc1", "adst1", "asrc2", "adst2", "dadst", "dasrc"):
+                bufs[k] = v(k, n, heads)
+            for k in ("alpha1", "alpha2", "dz"):
+                bufs[k] = v(k, nnz, heads)
+            ns = max(D.gat_bwd_scratch_floats(self.ctx, n, heads, h // heads), 1)
+            bufs["scratch"] = v("gat_scratch", 1, ns).flat(0, ns)
+            bufs["gat_key"] = (batch.n, batch.n_graphs, nnz)
+        return bufs
+
+    def _gat_fwd(self, a, x, k, bufs, keep):
+        """z_k = GATConv_k(x): Hf, the score halves, the softmax-weighted gather; keep: alpha and O for the backward."""
+        ctx, p = self.ctx, self.p
+        hf, asrc, adst = bufs[f"hf{k}"], bufs[f"asrc{k}"], bufs[f"adst{k}"]
+        D.gemm(ctx, x, p[f"w{k}"], None, hf)
+        D.gat_scores(ctx, hf, p[f"as{k}"], p[f"ad{k}"], asrc, adst)
+        D.gat_aggregate(ctx, a, hf, asrc, adst, p[f"b{k}"], bufs[f"z{k}"], alpha=bufs[f"alpha{k}"] if keep else None,
+                        o_pre=bufs[f"o{k}"] if keep else None, slope=self.SLOPE)
+
+    def _gat_bwd(self, a, x, k, dzk, bufs, dx):
+        """dZ_k -> the four gradients of GATConv_k and, with dx, the gradient of its input."""
+        ctx, p, g = self.ctx, self.p, self.g
+        hf, alpha = bufs[f"hf{k}"], bufs[f"alpha{k}"]
+        D.act_bias_grad(ctx, dzk, None, dzk, None, db=g[f"b{k}"])                    # conv_k.bias: column sums of dZ_k
+        D.gat_bwd_edges(ctx, a, hf, bufs[f"asrc{k}"], bufs[f"adst{k}"], alpha, dzk, bufs[f"o{k}"], bufs["dz"], bufs["dadst"],
+                        slope=self.SLOPE)
+        D.gat_bwd_nodes(ctx, a, alpha, bufs["dz"], dzk, hf, bufs["dadst"], p[f"as{k}"], p[f"ad{k}"], bufs["dhf"], bufs["dasrc"],
+                        g[f"as{k}"], g[f"ad{k}"], bufs["scratch"])
+        D.gemm_dw(ctx, x, bufs["dhf"], g[f"w{k}"])                                   # dW_k = x^T dHf
+        if dx is not None:
+            D.gemm_dx(ctx, bufs["dhf"], p[f"w{k}"], dx)                              # dx = dHf W_k^T
+
+    def _conv1(self, a, batch, bufs, mode):
+        self._gat_fwd(a, batch.x, 1, bufs, mode == "grads")
+
+    def _conv2(self, a, bufs, mode):
+        self._gat_fwd(a, bufs["y1"], 2, bufs, mode == "grads")
+
+    def _conv2_bwd(self, a_t, bufs):
+        self._gat_bwd(a_t, bufs["y1"], 2, bufs["dz2"], bufs, bufs["dy1"])
+
+    def _conv1_bwd(self, a_t, batch, bufs):
+        self._gat_bwd(a_t, batch.x, 1, bufs["dz1"], bufs, None)                     # (the input carries no gradient)
 
 
 class ECCNet(_GraphRunner):

@@ -768,6 +768,55 @@ GCNX_API int gcnx_sage_conv(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t*
                       const float* x, int64_t ldx, int32_t n, int32_t fi, const float* w_nb, const float* w_root,
                       int32_t fo, int w_transposed, const float* bias, float* s, int64_t lds, float* out, int64_t ldo);
 
+/* ---- GATConv: edge-softmax attention, small-feature regime (heads * c <= 128) -------------------------------------
+ * PyG's GATConv(in, c, heads, concat=True, negative_slope, dropout=0, bias=True), the attention layer for the slot the
+ * reference's author marked as open ("consider using class SAGEConv instead", gcn_utills.py:804-806).  CSR row i is the
+ * target, its stored entries j the sources, values are ignored.  With Hf = x W [n, heads * c] from gcnx_gemm (head h owns
+ * columns [h c, h c + c)):
+ *     a_src[j,h] = <Hf[j,h,:], att_src[h,:]>   a_dst[i,h] = <Hf[i,h,:], att_dst[h,:]>
+ *     z = a_src[j,h] + a_dst[i,h] (one fp32 add)   e = z > 0 ? z : slope z   alpha = exp(e - m_i) / l_i (m: row max, l: row sum)
+ *     O[i,h,:] = sum_j alpha Hf[j,h,:]   out = O + bias   (a row without entries: O = 0, out = bias)
+ * fp32, no float atomics, fixed summation order: the same bits on every call, eager or replayed from a captured graph.
+ * Nothing is allocated.  32 rows per workgroup, heads * c / 4 lanes per row; 1024 CSR entries of a tile are staged in LDS,
+ * longer tiles read the rest from global memory.
+ * gcnx_gat_conv_ok (gcn_utills.py:804-806): 1 if the shapes are served: heads in {1, 2, 4, 8}, heads * c in {16, 32, 64, 128},
+ * c >= 4, ldh >= heads * c, ldh % 4 == 0, n * ldh * 4 < 2^32.  Every call below returns GCNX_ERR_UNSUPPORTED otherwise (ldh: the
+ * leading dimension of the operand it gathers), and for float4 operands off a 16-byte boundary or leading dimensions that
+ * are not multiples of 4 floats >= heads * c, with nothing launched and nothing written.  n == 0 succeeds and writes
+ * nothing; negative sizes and NULL mandatory pointers are GCNX_ERR_INVALID. */
+GCNX_API int gcnx_gat_conv_ok(int64_t n, int32_t heads, int32_t c, int64_t ldh);
+/* gcn_utills.py:804-806 -- a_src, a_dst [n, heads] from hf [n, heads * c] (ldh) and att_src, att_dst [heads, c]: one pass over hf. */
+GCNX_API int gcnx_gat_scores(gcnx_ctx* ctx, const float* hf, int64_t ldh, int32_t n, int32_t heads, int32_t c,
+                       const float* att_src, const float* att_dst, float* a_src, float* a_dst);
+/* gcn_utills.py:804-806 -- out [n, heads * c] (ldo) = softmax-weighted gather + bias (bias may be NULL).  alpha [nnz, heads]
+ * (may be NULL: not stored) receives the attention coefficients in the CSR's entry order; o_pre (ldp; may be NULL) receives
+ * O, the result before the bias -- without it the backward takes out and bias.  The row maximum is subtracted before the
+ * exponential: no score overflows, no row divides 0 by 0. */
+GCNX_API int gcnx_gat_aggregate(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, const float* hf, int64_t ldh,
+                       int32_t n, int32_t heads, int32_t c, const float* a_src, const float* a_dst, const float* bias,
+                       float slope, float* out, int64_t ldo, float* alpha, float* o_pre, int64_t ldp);
+/* gcn_utills.py:804-806 -- backward, the pass over the forward CSR.  d_out = dLoss/dout [n, heads * c] (ldd); o (ldo) is O, or
+ * out with o_bias = the bias that was added (O = o - o_bias).  With r[i,h] = <d_out[i,h,:], O[i,h,:]>:
+ *     dz[e,h] = alpha[e,h] (<d_out[i,h,:], hf[j,h,:]> - r[i,h]) (z > 0 ? 1 : slope)      da_dst[i,h] = sum over the row of dz
+ * dz [nnz, heads] in the CSR's entry order, da_dst [n, heads].  a_src / a_dst decide the side of z only. */
+GCNX_API int gcnx_gat_bwd_edges(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, const float* hf, int64_t ldh,
+                       int32_t n, int32_t heads, int32_t c, const float* a_src, const float* a_dst, float slope,
+                       const float* alpha, const float* d_out, int64_t ldd, const float* o, int64_t ldo, const float* o_bias,
+                       float* dz, float* da_dst);
+/* gcn_utills.py:804-806 -- floats of caller scratch gcnx_gat_bwd_nodes needs (per-workgroup parts of datt_src / datt_dst). */
+GCNX_API int64_t gcnx_gat_bwd_scratch_floats(int64_t n, int32_t heads, int32_t c);
+/* gcn_utills.py:804-806 -- backward, the pass over the transposed pattern (rowptr_t, colidx_t, perm_t of
+ * gcnx_csr_transpose_perm: perm_t[p] = the forward entry behind entry p; needed for a symmetric pattern too):
+ *     dhf[j,h,:] = sum_i alpha[ij,h] d_out[i,h,:] + da_src[j,h] att_src[h,:] + da_dst[j,h] att_dst[h,:]     da_src[j,h] = sum_i dz[ij,h]
+ *     datt_src[h,:] = sum_j da_src[j,h] hf[j,h,:]      datt_dst[h,:] = sum_j da_dst[j,h] hf[j,h,:]
+ * dhf [n, heads * c] (ldg), da_src [n, heads], datt_src / datt_dst [heads, c].  The datt sums go through per-workgroup parts in
+ * scratch and a second small launch inside this call (fixed order, no atomics).  dbias, dW and dx of the layer are
+ * gcnx_act_bias_grad, gcnx_gemm_dw and gcnx_gemm_dx. */
+GCNX_API int gcnx_gat_bwd_nodes(gcnx_ctx* ctx, const int32_t* rowptr_t, const int32_t* colidx_t, const int32_t* perm_t,
+                       int32_t n, int32_t heads, int32_t c, const float* alpha, const float* dz, const float* d_out, int64_t ldd,
+                       const float* hf, int64_t ldh, const float* da_dst, const float* att_src, const float* att_dst,
+                       float* dhf, int64_t ldg, float* da_src, float* datt_src, float* datt_dst, float* scratch);
+
 /* ---- TopKPool: per-graph top-k selection, gated gather, induced sub-CSR ------------------------------------------
  * spektral.layers.pooling.TopKPool, the one layer the reference's training script imports (gcn.py:10) that had no kernels
  * here, in disjoint mode: y = X p / ||p||, the k_g rows of every graph with the largest y are kept, X' = (X * gate(y))[idx],
