@@ -6,6 +6,7 @@ hand-written HIP kernels in libgcnx.so (C ABI: include/gcnx.h), bound with ctype
 No PyTorch, no TensorFlow, no CPU fallback.
 """
 from . import _lib
+from .optim import SGD, Adam
 from .io import best_epoch, load_weights_npz, save_to_npz
 from .loader import Dataset, DisjointLoader, Graph, ListDataset, NetworkxDataset, SparseTensor, entry_edge_features, format_graph, from_networkx
 from .train import PiecewiseConstantDecay, auc, binary_acc, fit, roc_curve
@@ -13,7 +14,7 @@ from .train import PiecewiseConstantDecay, auc, binary_acc, fit, roc_curve
 __all__ = ["Dataset", "DisjointLoader", "Graph", "ListDataset", "NetworkxDataset", "from_networkx", "entry_edge_features", "format_graph", "SparseTensor", "Context", "default_context", "GCNConv", "GeneralConv",
            "ECCConv", "SAGEConv", "GATConv", "TopKPool", "GlobalSumPool", "GlobalAvgPool", "GlobalMaxPool", "Dense", "BatchNorm1d", "PReLU", "GCN2", "GCN", "SAGE", "GAT", "GeneralGNN", "ECCNet", "TopKNet", "DeviceBatch",
            "save_to_npz", "load_weights_npz", "best_epoch", "DeviceDataset", "DeviceDisjointLoader",
-           "PiecewiseConstantDecay", "fit", "roc_curve", "auc", "binary_acc"]
+           "PiecewiseConstantDecay", "Adam", "SGD", "fit", "roc_curve", "auc", "binary_acc"]
 
 
 def __getattr__(name):  # device-side names load libgcnx lazily, host-only use needs no .so

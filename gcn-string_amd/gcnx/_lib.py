@@ -127,6 +127,9 @@ SIGNATURES = {
     "gcnx_bce_head_phase_red_floats": [_i32],
     "gcnx_bce_head_phase": [_vp, _vp, _i32, _f32, _vp],
     "gcnx_sgd": [_vp, _vp, _vp, _i64, _f32],
+    "gcnx_grad_sqnorm": [_vp, _vp, _i64, _vp, _i32],
+    "gcnx_adam": [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _f32, _f32, _f32, _f32, _f32, _vp, _i32, _f32, _vp],
+    "gcnx_sgd_momentum": [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _int, _vp, _i32, _f32, _vp],
     "gcnx_dropout": [_vp, _vp, _i64, _i64, _i32, _f32, C.c_uint32, C.c_uint32, _vp, _vp, _i64],
     "gcnx_counter_add": [_vp, _vp, C.c_uint32],
     "gcnx_add": [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32],

@@ -1104,6 +1104,40 @@ def sgd(ctx, params, grads, lr):
     ctx._ck(ctx.lib.gcnx_sgd(ctx.h, _p(params), _p(grads), params.size, float(lr)))
 
 
+OPTIM_MAX_PARTIALS = 256             # GCNX_OPTIM_MAX_PARTIALS
+
+
+def grad_sqnorm_partials(n):
+    """Workgroups (= partial sums) gcnx_grad_sqnorm is launched with for n gradients: one per 256, at most 256."""
+    return max(1, min(OPTIM_MAX_PARTIALS, -(-int(n) // 256)))
+
+
+def grad_sqnorm(ctx, grads, partials, n_partials=None):
+    """partials[:n_partials] = the workgroups' shares of sum g^2 in a fixed order (gcnx_grad_sqnorm); returns n_partials --
+    what the update launch is told.  No host read: adam / sgd_momentum finish the sum."""
+    k = grad_sqnorm_partials(grads.size) if n_partials is None else int(n_partials)
+    assert partials.size >= min(k, OPTIM_MAX_PARTIALS)
+    ctx._ck(ctx.lib.gcnx_grad_sqnorm(ctx.h, _p(grads), grads.size, _p(partials), k))
+    return k
+
+
+def adam(ctx, params, grads, m, v, t, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, partials=None, n_partials=0,
+         clipnorm=None, norm_out=None):
+    """One Adam / AdamW step over flat buffers (gcnx_adam).  t: the uint32 device step count, already advanced
+    (counter_add).  clipnorm needs the partials of grad_sqnorm; norm_out (1 float) receives the gradient norm."""
+    assert grads.size == m.size == v.size == params.size
+    ctx._ck(ctx.lib.gcnx_adam(ctx.h, _p(params), _p(grads), _p(m), _p(v), params.size, _p(t), float(lr), float(beta1), float(beta2),
+                              float(eps), float(weight_decay), _p(partials), int(n_partials), float(clipnorm or 0.0), _p(norm_out)))
+
+
+def sgd_momentum(ctx, params, grads, vel, lr, momentum=0.0, nesterov=False, partials=None, n_partials=0, clipnorm=None,
+                 norm_out=None):
+    """One Keras SGD(momentum, nesterov) step over flat buffers (gcnx_sgd_momentum); clipping as in adam."""
+    assert grads.size == vel.size == params.size
+    ctx._ck(ctx.lib.gcnx_sgd_momentum(ctx.h, _p(params), _p(grads), _p(vel), params.size, float(lr), float(momentum), int(bool(nesterov)),
+                                      _p(partials), int(n_partials), float(clipnorm or 0.0), _p(norm_out)))
+
+
 BN_EPS, BN_MOMENTUM = 1e-3, 0.99     # Keras BatchNormalization defaults (SURVEY 8.A.5)
 
 

@@ -149,7 +149,7 @@ class _GraphRunner:
       _multi, _comm_in_graph                    more than one rank; the collectives recorded into the step graph
       _run_with_comm_fallback                   _run; a capture that fails with the collectives inside falls back for good
       _global_counts_cached, _global_graphs     sync-BN: the global (N, B, ...) of a batch, one host all-reduce per batch
-      _apply_sgd        the one update launch
+      set_optimizer, _apply_sgd                 the update: one gcnx_sgd launch, or the launches of a gcnx.optim optimizer
       _finish_step, fetch_metrics, _loss_acc_host, stash_metrics, collect_metrics     what a step and an evaluation return
       losses            [] (no regularisers: gcn.py:335 adds sum(model.losses))"""
 
@@ -243,8 +243,24 @@ class _GraphRunner:
         return self._counts["b"] if self._multi() else batch.n_graphs
 
     # ---- the end of a step ---------------------------------------------------------------------------------------------
+    _opt = None                          # a gcnx.optim optimizer (set_optimizer), or None: plain SGD
+
+    def set_optimizer(self, opt):
+        """Put a gcnx.Adam / gcnx.SGD behind this model's update (None: plain SGD again, the launches of a model that never
+        had one).  Before or after build(); the optimizer's state is allocated once the model is built.  Captured graphs
+        hold the state pointers and the update's launches: they are dropped."""
+        self._opt = opt
+        self._drop_graphs()
+        if opt is not None and self.built:
+            opt.bind(self)
+
     def _apply_sgd(self, lr):
-        D.sgd(self.ctx, self.flat_p, self.flat_g.flat(0, self.n_params), lr)
+        """The update of a step.  Without an optimizer the one gcnx_sgd launch; with one its step count, the norm launch if it
+        clips, and its update launch (gcnx.optim), on the gradients every rank holds after the all-reduce."""
+        if self._opt is None:
+            D.sgd(self.ctx, self.flat_p, self.flat_g.flat(0, self.n_params), lr)
+        else:
+            self._opt.step(self, lr)
 
     def _finish_step(self, fetch, n_graphs):
         """What train_step returns.  fetch: True -> (loss, acc); False -> None; "stash" -> None, the metrics kept on the
@@ -790,7 +806,8 @@ class GCN2(_GraphRunner):
 
         def seq():
             self._forward(batch, bufs, "grads", denom, train=_lr is not None)
-            if self._backward(batch, bufs, None if multi else _lr, buckets=buckets):
+            # (an optimizer with state: the gradients-only route, then its own launches -- as the multi-rank step does)
+            if self._backward(batch, bufs, None if (multi or self._opt is not None) else _lr, buckets=buckets):
                 return
             if fused_comm and not self._reduced_in_backward:
                 self.comm.allreduce_sum(self.flat_g)

@@ -64,11 +64,14 @@ def evaluate(model, loader, normalize=None):
     return tuple(np.average(output[:, :-1], 0, weights=output[:, -1])), preds
 
 
-def fit(model, loader_tr, loader_te=None, epochs=1, schedule=None, normalize=None, verbose=True):
+def fit(model, loader_tr, loader_te=None, epochs=1, schedule=None, normalize=None, verbose=True, optimizer=None):
     """gcn.py:364-385.  ``loader_tr`` must have been built with the same ``epochs`` (it ends the loop, as in the
     reference).  Returns {"history": [(train_loss, train_acc, test_loss, test_acc) per epoch], "weights": [...],
-    "performance": [test_acc per epoch]}."""
+    "performance": [test_acc per epoch]}.  optimizer: a gcnx.Adam / gcnx.SGD handed to model.set_optimizer (None: the model as
+    it is -- plain SGD unless it was given one); the schedule stays the rate either way."""
     schedule = schedule or PiecewiseConstantDecay.reference(epochs)
+    if optimizer is not None:
+        model.set_optimizer(optimizer)
     epoch = step = 0
     it = 0                                             # optimizer iterations: the schedule's argument
     results, history, weights, performance = [], [], [], []

@@ -615,6 +615,32 @@ GCNX_API int gcnx_sgd(gcnx_ctx* ctx, float* params, const float* grads, int64_t 
  * source the same captured step serves every value of a schedule -- keras.optimizers.schedules.*, gcn.py:321-325 -- and
  * the host only rewrites 4 bytes (gcnx_h2d_async) when the value changes.  Not callable inside a capture. */
 GCNX_API int gcnx_set_lr_source(gcnx_ctx* ctx, const float* lr_dev);
+
+/* ---- optimisers with state (csrc/optim.hip) ---------------------------------- */
+/* A step on one stream: gcnx_counter_add(t, 1) -> [gcnx_grad_sqnorm] -> gcnx_adam | gcnx_sgd_momentum.  The step count and
+ * the clip factor stay on the device, so a captured step replays unchanged.  Both updates read the learning rate as
+ * gcnx_sgd does (gcnx_set_lr_source) and never write g.  n == 0: nothing is launched. */
+#define GCNX_OPTIM_MAX_PARTIALS 256
+/* partials[b], b < n_partials (1 .. GCNX_OPTIM_MAX_PARTIALS): workgroup b's share of sum g[i]^2, fp32, in a fixed order without
+ * atomics (an eager call and a graph replay give the same bits): thread j of workgroup b adds the rounded squares of
+ * i = 256 b + j, + 256 n_partials, ... ascending from +0; a wave folds lane += lane + off for off = 32 .. 1; the four wave
+ * sums are added as ((s0 + s1) + s2) + s3.  Not followed by a host read: the update launch finishes the sum. */
+GCNX_API int gcnx_grad_sqnorm(gcnx_ctx* ctx, const float* g, int64_t n, float* partials, int32_t n_partials);
+/* torch.optim.Adam / AdamW (decoupled weight_decay; 0: none) in one launch, t = *t_dev >= 1 already advanced for this step:
+ *   s = clipnorm > 0 ? min(1, clipnorm / (sqrt(sum partials) + 1e-6)) : 1        (torch.nn.utils.clip_grad_norm_)
+ *   g' = s g;  p = p (1 - lr weight_decay);  m = beta1 m + (1 - beta1) g';  v = beta2 v + (1 - beta2) g' g'
+ *   p = p - (lr / (1 - beta1^t)) m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
+ * Every workgroup folds the partials itself, in gcnx_grad_sqnorm's lane and wave order; workgroup 0 stores sqrt(sum) to
+ * norm_out (may be NULL).  partials may be NULL when clipnorm <= 0 (then no norm is formed).  The bias corrections are formed
+ * in fp64 from the fp32 betas, everything per element in fp32.  float4 accesses where p, g, m, v are 16-byte aligned.
+ * GCNX_ERR_INVALID: NULL p / g / m / v / t_dev, n < 0, a beta outside [0, 1), n_partials > GCNX_OPTIM_MAX_PARTIALS. */
+GCNX_API int gcnx_adam(gcnx_ctx* ctx, float* p, const float* g, float* m, float* v, int64_t n, const uint32_t* t_dev, float lr,
+                       float beta1, float beta2, float eps, float weight_decay, const float* partials, int32_t n_partials,
+                       float clipnorm, float* norm_out);
+/* tf.keras.optimizers.SGD(momentum, nesterov) (gcn.py:325): vel = momentum vel - lr g'; p += vel, with nesterov
+ * p += momentum vel - lr g'.  Clipping, norm_out and the learning rate as in gcnx_adam; momentum in [0, 1). */
+GCNX_API int gcnx_sgd_momentum(gcnx_ctx* ctx, float* p, const float* g, float* vel, int64_t n, float lr, float momentum,
+                               int nesterov, const float* partials, int32_t n_partials, float clipnorm, float* norm_out);
 /* A reduction that gcnx_dense_bwd_deferred left undone: column-sum partial rows -> cout[cf] and split-K slabs ->
  * out[total], both still in the caller's scratch buffer.  All zeros = nothing pending.  Plain data, no ownership. */
 typedef struct gcnx_pending_reduce {
