@@ -167,6 +167,13 @@ SIGNATURES = {
     "gcnx_gat_bwd_scratch_floats": [_i64, _i32, _i32],
     "gcnx_gat_bwd_nodes": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp,
                            _vp, _vp],
+    "gcnx_gatv2_conv_ok": [_i64, _i32, _i32, _i64, _i32],
+    "gcnx_gatv2_aggregate": [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _f32, _vp, _i64, _vp, _vp, _i64],
+    "gcnx_gatv2_bwd_scratch_floats": [_i64, _i32, _i32, _i32],
+    "gcnx_gatv2_bwd_edges": [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _i64, _i32, _vp, _vp, _f32, _vp, _vp, _i64, _vp, _i64, _vp,
+                             _vp, _i64, _vp, _vp, _vp],
+    "gcnx_gatv2_bwd_nodes": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _i64, _i32, _vp, _vp, _f32, _vp, _vp, _vp, _i64, _vp,
+                             _i64],
     "gcnx_topk_select_ok": [_i64, _i32],
     "gcnx_topk_select": [_vp, _vp, _vp, _i32, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _vp],
     "gcnx_topk_gather": [_vp, _vp, _i64, _vp, _vp, _i32, _i32, _int, _vp, _i64],
@@ -179,7 +186,7 @@ SIGNATURES = {
 }
 _RESTYPE = {"gcnx_last_error": C.c_char_p, "gcnx_dense_bwd_scratch_floats": C.c_int64, "gcnx_bce_head_scratch_floats": C.c_int64,
             "gcnx_bce_head_phase_scratch_floats": C.c_int64, "gcnx_bce_head_phase_red_floats": C.c_int64,
-            "gcnx_gcn_conv_bwd_scratch_floats": C.c_int64, "gcnx_gat_bwd_scratch_floats": C.c_int64, "gcnx_wimage_elems": C.c_int64, "gcnx_gemm_wimage_parts": C.c_int64}
+            "gcnx_gcn_conv_bwd_scratch_floats": C.c_int64, "gcnx_gat_bwd_scratch_floats": C.c_int64, "gcnx_gatv2_bwd_scratch_floats": C.c_int64, "gcnx_wimage_elems": C.c_int64, "gcnx_gemm_wimage_parts": C.c_int64}
 
 
 class WimageJob(C.Structure):

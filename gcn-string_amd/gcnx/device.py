@@ -849,6 +849,69 @@ def gat_bwd_nodes(ctx, a, alpha, dz, dout, hf, da_dst, att_src, att_dst, dhf, da
     return dhf
 
 
+def gatv2_conv_ok(ctx, n, heads, c, ldx=None, edge_dim=0):
+    """True if the GATv2Conv kernels serve these shapes (gcnx_gatv2_conv_ok); ldx: the leading dimension of Xl | Xr."""
+    return bool(ctx.lib.gcnx_gatv2_conv_ok(int(n), int(heads), int(c), int(ldx if ldx is not None else 2 * heads * c), int(edge_dim)))
+
+
+def gatv2_bwd_scratch_floats(ctx, n, heads, c, edge_dim=0):
+    return int(ctx.lib.gcnx_gatv2_bwd_scratch_floats(int(n), int(heads), int(c), int(edge_dim)))
+
+
+def _gatv2_edge(a, e, w_e, hc):
+    """(e pointer, lde, edge_dim, w_e pointer) of the optional edge operands: e [nnz, D] (any ld), w_e [D, heads * c]."""
+    if e is None:
+        assert w_e is None
+        return None, 0, 0, None
+    d = e.shape[1]
+    assert e.shape[0] == a.nnz and w_e is not None and w_e.shape == (d, hc) and w_e.contiguous
+    return _p(e), e.ld, d, _p(w_e)
+
+
+def gatv2_aggregate(ctx, a, xlr, att, bias, out, e=None, w_e=None, alpha=None, o_pre=None, slope=0.2):
+    """out = softmax-weighted sum of Xl over the stored entries of ``a`` (row = target) + bias, the scores from
+    LeakyReLU(Xl[j] + Xr[i] + e_ij w_e) . att (gcnx_gatv2_aggregate).  xlr = Xl | Xr [n, 2 heads c]; att [heads, c]; alpha
+    [nnz, heads] and o_pre (the result before the bias) are stored if given."""
+    heads, c = att.shape
+    hc, n = heads * c, xlr.shape[0]
+    assert a.n == n and xlr.shape[1] == 2 * hc and out.shape == (n, hc) and att.contiguous and (bias is None or bias.shape == (hc,))
+    assert (alpha is None or (alpha.shape == (a.nnz, heads) and alpha.contiguous)) and (o_pre is None or o_pre.shape == (n, hc))
+    ep, lde, d, wp = _gatv2_edge(a, e, w_e, hc)
+    ctx._ck(ctx.lib.gcnx_gatv2_aggregate(ctx.h, a.rowptr.ptr, a.colidx.ptr, _p(xlr), xlr.ld, n, heads, c, ep, lde, d, wp, _p(att), _p(bias),
+                                         float(slope), _p(out), out.ld, _p(alpha), _p(o_pre), o_pre.ld if o_pre is not None else 0))
+    return out
+
+
+def gatv2_bwd_edges(ctx, a, xlr, att, alpha, dout, o, dscore, dxr, datt, scratch, e=None, w_e=None, dw_e=None, slope=0.2):
+    """dscore [nnz, heads] (the CSR's entry order), dxr [n, heads c], datt [heads, c] and dw_e [D, heads c] from dout and O = o
+    (gcnx_gatv2_bwd_edges).  scratch: gatv2_bwd_scratch_floats floats."""
+    heads, c = att.shape
+    hc, n = heads * c, xlr.shape[0]
+    assert a.n == n and xlr.shape[1] == 2 * hc and dout.shape == o.shape == dxr.shape == (n, hc)
+    assert alpha.shape == dscore.shape == (a.nnz, heads) and datt.shape == (heads, c)
+    assert att.contiguous and alpha.contiguous and dscore.contiguous and datt.contiguous
+    ep, lde, d, wp = _gatv2_edge(a, e, w_e, hc)
+    assert (dw_e is None) == (d == 0) and (dw_e is None or (dw_e.shape == (d, hc) and dw_e.contiguous))
+    assert scratch.size >= gatv2_bwd_scratch_floats(ctx, n, heads, c, d)
+    ctx._ck(ctx.lib.gcnx_gatv2_bwd_edges(ctx.h, a.rowptr.ptr, a.colidx.ptr, _p(xlr), xlr.ld, n, heads, c, ep, lde, d, wp, _p(att),
+                                         float(slope), _p(alpha), _p(dout), dout.ld, _p(o), o.ld, _p(dscore), _p(dxr), dxr.ld, _p(datt),
+                                         _p(dw_e), _p(scratch)))
+    return dscore, dxr
+
+
+def gatv2_bwd_nodes(ctx, a, xlr, att, alpha, dscore, dout, dxl, e=None, w_e=None, slope=0.2):
+    """dxl [n, heads c] on the transposed pattern of ``a`` with its entry permutation (a.transpose_perm(); gcnx_gatv2_bwd_nodes)."""
+    heads, c = att.shape
+    hc, n = heads * c, xlr.shape[0]
+    assert a.n == n and xlr.shape[1] == 2 * hc and dout.shape == dxl.shape == (n, hc)
+    assert alpha.shape == dscore.shape == (a.nnz, heads) and att.contiguous and alpha.contiguous and dscore.contiguous
+    ep, lde, d, wp = _gatv2_edge(a, e, w_e, hc)
+    rp, ci, pm = a.transpose_perm()
+    ctx._ck(ctx.lib.gcnx_gatv2_bwd_nodes(ctx.h, rp.ptr, ci.ptr, pm.ptr, _p(xlr), xlr.ld, n, heads, c, ep, lde, d, wp, _p(att), float(slope),
+                                         _p(alpha), _p(dscore), _p(dout), dout.ld, _p(dxl), dxl.ld))
+    return dxl
+
+
 def topk_select_ok(ctx, max_graph_rows, f):
     """True if topk_select serves a batch whose largest graph has this many rows (gcnx_topk_select_ok)."""
     return bool(ctx.lib.gcnx_topk_select_ok(int(max_graph_rows), int(f)))

@@ -7,6 +7,7 @@ Reference topology: GCNConv -> GCNConv -> global pool -> Linear (gcn_utills.py:8
 832-842); live model ctor gcn.py:320, forward gcn.py:334/351, gradients gcn.py:337.
 ``SAGEConv(channels, root_weight=True, use_bias=True)`` is PyG's layer of that name (aggr="mean"), which the reference
 names as its next step (gcn_utills.py:804-806); ``GATConv(channels, heads=1)`` is PyG's attention layer for the same slot.
+``GATv2Conv(channels, heads=1, edge_dim=None)`` is PyG's GATv2Conv: attention whose scores read the edge features (gcn.py:71).
 ``TopKPool(ratio)`` is Spektral's pooling layer of that name, which the
 reference's script imports (gcn.py:10), called as ``layer([x, a, seg])``.
 
@@ -351,6 +352,164 @@ class GATConv(Layer):
             return None
         dx = self._buf("dx", x.shape)
         D.gemm_dx(ctx, dhf, p["lin.weight"], dx)                                    # dx = dHf W^T
+        return dx
+
+
+class GATv2Conv(Layer):
+    """torch_geometric.nn.GATv2Conv(in, channels, heads, concat=True, negative_slope=0.2, dropout=0.0, add_self_loops=False,
+    edge_dim=D, bias=True, share_weights=False) (Brody et al.) -- attention whose scores read the edge features, the dca /
+    proximity values the reference computes and its model drops (gcn_utills.py:319-443; gcn.py:71):
+
+        Xl = x W_l + b_l    Xr = x W_r + b_r    s_ij = Xl[j] + Xr[i] + e_ij W_e    score_ij,h = <att[h,:], LeakyReLU(s_ij)[h,:]>
+        alpha = softmax over the row's entries       out[i,h,:] = sum_j alpha_ij,h Xl[j,h,:] + bias
+
+    The LeakyReLU comes before the dot with att: the score depends jointly on target, source and edge (GATConv's ordering of
+    the sources is the same for every target).  ``GATv2Conv(channels, heads=1, ..., edge_dim=None)``, called as ``layer([x, a])``
+    or, with edge_dim, ``layer([x, a, e])`` with ``a = GATv2Conv.preprocess(a)`` and e [nnz, edge_dim] in the entry order of a:
+    the stored pattern (row = target) and e as stored, values ignored, no loop added or removed; a row without entries gives
+    the bias.  Parameters under PyG's names and in this order: ``att`` (stored [heads, channels]), ``bias``, ``lin_l.weight``,
+    ``lin_l.bias``, ``lin_r.weight``, ``lin_r.bias``, ``lin_edge.weight`` (with edge_dim).  The two lin weights are the column
+    halves of ONE stacked tensor [in, 2 heads channels] (``lin_weight``; PyG: two [heads channels, in]) and the two biases the
+    halves of ``lin_bias``: Xl | Xr is one gcnx_gemm, the layer's backward one gcnx_gemm_dw, one column sum, one gcnx_gemm_dx.
+    ``params`` / ``grads`` hold per-name views; ``state_dict()`` gives PyG's layouts.  glorot-uniform as PyG, biases zero.
+    ``backward(dy, need_dx=True)`` returns dx (None with need_dx=False) and leaves the gradients in ``grads``.
+
+    Launches (csrc/gatv2.hip): gcnx_gemm, gcnx_gatv2_aggregate forward; gcnx_act_bias_grad, gcnx_gatv2_bwd_edges,
+    gcnx_gatv2_bwd_nodes, gcnx_gemm_dw, gcnx_act_bias_grad, gcnx_gemm_dx backward.  There is no composed route: what the kernels
+    do not serve (concat=False, attention dropout, share_weights=True, shapes gcnx_gatv2_conv_ok refuses) raises
+    NotImplementedError."""
+
+    def __init__(self, channels, heads=1, concat=True, negative_slope=0.2, use_bias=True, activation=None, dropout=0.0, edge_dim=None,
+                 share_weights=False, **kw):
+        super().__init__(**kw)
+        if not concat:
+            raise NotImplementedError("GATv2Conv concat=False (the mean over heads) has no kernel: only concat=True")
+        if dropout:
+            raise NotImplementedError(f"GATv2Conv dropout={dropout}: attention dropout has no kernel (only dropout=0)")
+        if share_weights:
+            raise NotImplementedError("GATv2Conv share_weights=True has no kernel: lin_l and lin_r are separate")
+        if activation not in (None, "linear"):
+            raise NotImplementedError(f"GATv2Conv activation {activation!r}: the layer is linear (follow it with BatchNorm1d / PReLU)")
+        if edge_dim is not None and not 1 <= int(edge_dim) <= 8:
+            raise NotImplementedError(f"GATv2Conv edge_dim={edge_dim}: the kernels serve 1 to 8 edge features (or None)")
+        self.channels, self.heads, self.negative_slope = int(channels), int(heads), float(negative_slope)
+        self.concat, self.use_bias, self.activation = True, bool(use_bias), activation
+        self.edge_dim = None if edge_dim is None else int(edge_dim)
+
+    @staticmethod
+    def preprocess(a):
+        """The unweighted view of a DeviceCSR: the pattern as stored, no loop added or removed."""
+        return a.unweighted()
+
+    def _param_spec(self, in_dim):
+        """PyG's names in its named_parameters() order, with the stored shapes ([in, heads * channels] weights)."""
+        h, c, d = self.heads, self.channels, self.edge_dim or 0
+        hc, rng = h * c, self._rng
+        u = lambda lim, *s: rng.uniform(-lim, lim, s).astype(np.float32)
+        spec = [("att", (h, c), u(np.sqrt(6.0 / (h + c)), h, c))]             # PyG's glorot on the [1, heads, channels] tensor
+        if self.use_bias:
+            spec.append(("bias", (hc,), np.zeros(hc, np.float32)))
+        for k in ("lin_l", "lin_r"):
+            spec += [(k + ".weight", (in_dim, hc), glorot_uniform(rng, in_dim, hc)), (k + ".bias", (hc,), np.zeros(hc, np.float32))]
+        if d:
+            spec.append(("lin_edge.weight", (d, hc), glorot_uniform(rng, d, hc)))
+        return spec
+
+    def build(self, ctx, in_dim, p_store=None, g_store=None, offset=0):
+        """Storage order: att, bias, the stacked weight [in, 2 heads channels], the stacked bias, lin_edge.weight -- every
+        tensor on a 16-byte boundary when ``offset`` is."""
+        self.ctx = ctx
+        hc = self.heads * self.channels
+        spec = {name: (shape, init) for name, shape, init in self._param_spec(in_dim)}
+        total = sum(int(np.prod(s)) for s, _ in spec.values())
+        if p_store is None:
+            p_store, g_store, offset = ctx.zeros(total), ctx.zeros(total), 0
+        off = offset
+
+        def take(shape, init):
+            nonlocal off
+            n = int(np.prod(shape))
+            pv, gv = p_store.flat(off, n, shape), g_store.flat(off, n, shape)
+            pv.copy_from_host(init)
+            off += n
+            return pv, gv
+
+        p, g = self.params, self.grads
+        p["att"], g["att"] = take(*spec["att"])
+        if self.use_bias:
+            p["bias"], g["bias"] = take(*spec["bias"])
+        self.lin_weight, self.lin_weight_grad = take((in_dim, 2 * hc), np.concatenate([spec["lin_l.weight"][1], spec["lin_r.weight"][1]], axis=1))
+        self.lin_bias, self.lin_bias_grad = take((2 * hc,), np.concatenate([spec["lin_l.bias"][1], spec["lin_r.bias"][1]]))
+        for t, w, b in ((p, self.lin_weight, self.lin_bias), (g, self.lin_weight_grad, self.lin_bias_grad)):
+            t["lin_l.weight"], t["lin_l.bias"] = w.cols(0, hc), b.flat(0, hc)
+            t["lin_r.weight"], t["lin_r.bias"] = w.cols(hc, 2 * hc), b.flat(hc, hc)
+        if "lin_edge.weight" in spec:
+            p["lin_edge.weight"], g["lin_edge.weight"] = take(*spec["lin_edge.weight"])
+        self.in_dim, self.built = in_dim, True
+        return off
+
+    def set_weights(self, weights):
+        """Arrays in the order and the stored layouts of ``params`` (att [heads, channels], lin_*.weight [in, heads channels])."""
+        w = {k: np.asarray(v, np.float32) for k, v in zip(self.params, weights)}
+        for k in ("att", "bias", "lin_edge.weight"):
+            if k in w:
+                self.params[k].copy_from_host(w[k].reshape(self.params[k].shape))
+        self.lin_weight.copy_from_host(np.concatenate([w["lin_l.weight"], w["lin_r.weight"]], axis=1))
+        self.lin_bias.copy_from_host(np.concatenate([w["lin_l.bias"], w["lin_r.bias"]]))
+
+    def state_dict(self):
+        """{PyG name: array in PyG's layout}: att [1, heads, channels], lin_l / lin_r / lin_edge .weight [heads * channels, in]."""
+        d = {k: v.numpy() for k, v in self.params.items()}
+        d["att"] = d["att"][None]
+        for k in d:
+            if k.endswith(".weight"):
+                d[k] = d[k].T.copy()
+        return d
+
+    def call(self, inputs, out=None):
+        if len(inputs) not in (2, 3):
+            raise ValueError("GATv2Conv takes [x, a] or [x, a, e]")
+        x, a = inputs[:2]
+        e = inputs[2] if len(inputs) == 3 else None
+        h, c, d = self.heads, self.channels, self.edge_dim
+        if e is not None and d is None:
+            raise ValueError("GATv2Conv: edge features given to a layer built without edge_dim")
+        if e is None and d is not None:
+            raise ValueError(f"GATv2Conv(edge_dim={d}) takes [x, a, e]")
+        if e is not None and (len(e.shape) != 2 or e.shape != (a.nnz, d)):
+            raise ValueError(f"GATv2Conv(edge_dim={d}): e must be [{a.nnz}, {d}] (one row per stored entry), got {list(e.shape)}")
+        if not D.gatv2_conv_ok(x.ctx, x.shape[0], h, c, edge_dim=d or 0):
+            raise NotImplementedError(f"GATv2Conv heads={h} channels={c} on {x.shape[0]} rows: the kernels serve heads in {{1, 2, 4, 8}}, "
+                                      "heads * channels in {16, 32, 64, 128}, channels >= 4 and rows * heads * channels * 8 < 2^32")
+        if not self.built:
+            self.build(x.ctx, x.shape[1])
+        ctx, n, p = self.ctx, x.shape[0], self.params
+        y = out if out is not None else self._buf("y", (n, h * c))
+        xlr, o, alpha = self._buf("xlr", (n, 2 * h * c)), self._buf("o", (n, h * c)), self._buf("alpha", (a.nnz, h))
+        D.gemm(ctx, x, self.lin_weight, self.lin_bias, xlr)                         # Xl | Xr
+        D.gatv2_aggregate(ctx, a, xlr, p["att"], p.get("bias"), y, e=e, w_e=p.get("lin_edge.weight"), alpha=alpha, o_pre=o,
+                          slope=self.negative_slope)
+        self._saved = (x, a, e, xlr, alpha, o)
+        return y
+
+    def backward(self, dy, need_dx=True):
+        x, a, e, xlr, alpha, o = self._saved
+        ctx, p, g, h, c, n = self.ctx, self.params, self.grads, self.heads, self.channels, x.shape[0]
+        hc = h * c
+        if self.use_bias:
+            D.act_bias_grad(ctx, dy, None, dy, None, db=g["bias"])                  # column sums of dy
+        dscore, dxlr = self._buf("dscore", (a.nnz, h)), self._buf("dxlr", (n, 2 * hc))
+        scratch = self._buf("scratch", (max(D.gatv2_bwd_scratch_floats(ctx, n, h, c, self.edge_dim or 0), 1),))
+        w_e = p.get("lin_edge.weight")
+        D.gatv2_bwd_edges(ctx, a, xlr, p["att"], alpha, dy, o, dscore, dxlr.cols(hc, 2 * hc), g["att"], scratch, e=e, w_e=w_e,
+                          dw_e=g.get("lin_edge.weight"), slope=self.negative_slope)
+        D.gatv2_bwd_nodes(ctx, a, xlr, p["att"], alpha, dscore, dy, dxlr.cols(0, hc), e=e, w_e=w_e, slope=self.negative_slope)
+        D.gemm_dw(ctx, x, dxlr, self.lin_weight_grad)                               # dW_l | dW_r = x^T (dXl | dXr)
+        D.act_bias_grad(ctx, dxlr, None, dxlr, None, db=self.lin_bias_grad)         # db_l | db_r: column sums
+        if not need_dx:
+            return None
+        dx = self._buf("dx", x.shape)
+        D.gemm_dx(ctx, dxlr, self.lin_weight, dx)                                   # dx = dXl W_l^T + dXr W_r^T
         return dx
 
 

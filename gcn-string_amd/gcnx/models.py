@@ -19,6 +19,9 @@ above them (gcn_utills.py:804-806); one launch per convolution (csrc/sage.hip).
 ``GAT``: ``GCN`` with PyG's GATConv(heads, concat=True) in the place of both GCNConv layers: a softmax over the stored
 entries of every row with learned scores (csrc/gat.hip).
 
+``GATv2``: ``GCN`` with PyG's GATv2Conv(heads, concat=True, edge_dim) in the place of both GCNConv layers: attention whose scores
+read the dca / proximity edge features (csrc/gatv2.hip); trains from DeviceDataset(edge_features=True) batches.
+
 ``TopKNet``: GCNConv -> TopKPool -> GCNConv -> global pool -> Dense(softmax), with the pooling layer the reference's script imports
 (gcn.py:10); selection, gather and the induced adjacency on the device (csrc/topk.hip), eager launches.
 """
@@ -1361,6 +1364,32 @@ def _with_remaining_self_loops(a, n):
     return SparseTensor(idx[order], vals[order], (n, n))
 
 
+def _with_mean_self_loops(a, e, n):
+    """PyG's add_self_loops=True of GATv2Conv on the batch adjacency (host, COO or scipy; row = target): the stored loops
+    are removed, one loop per node is added, and with edge features e [nnz, S] (one row per stored entry, row-major) the
+    loop of node i carries the mean of the feature rows of row i's remaining entries -- zeros if it has none
+    (fill_value="mean").  Returns (SparseTensor with unit values, e' in its entry order or None)."""
+    from .loader import sp_matrix_to_sp_tensor
+    if not isinstance(a, SparseTensor):
+        a = sp_matrix_to_sp_tensor(a)
+    idx = np.asarray(a.indices, np.int64).reshape(-1, 2)
+    keep = idx[:, 0] != idx[:, 1]
+    rows = idx[keep, 0]
+    loops = np.arange(n, dtype=np.int64)
+    idx = np.concatenate([idx[keep], np.stack([loops, loops], 1)])
+    order = np.lexsort((idx[:, 1], idx[:, 0]))
+    if e is not None:
+        e = np.asarray(e)
+        if e.ndim != 2 or e.shape[0] != keep.size:
+            raise ValueError(f"edge features e have shape {e.shape}: expected one row per stored entry of the adjacency ({keep.size})")
+        e = e.astype(np.float64)
+        fill = np.zeros((n, e.shape[1]))
+        np.add.at(fill, rows, e[keep])
+        fill /= np.maximum(np.bincount(rows, minlength=n), 1)[:, None]
+        e = np.concatenate([e[keep], fill])[order].astype(np.float32)
+    return SparseTensor(idx[order], np.ones(order.size), (n, n)), e
+
+
 class GCN(_GraphRunner):
     """The reference's torch class ``GCN`` (src/utilities/gcn_utills.py:795-853), BASELINE config 1's topology:
 
@@ -1991,6 +2020,209 @@ class GAT(GCN):
 
     def _conv1_bwd(self, a_t, batch, bufs):
         self._gat_bwd(a_t, batch.x, 1, bufs["dz1"], bufs, None)                     # (the input carries no gradient)
+
+
+class GATv2(GCN):
+    """``GCN`` with its two GCNConv layers replaced by PyG's GATv2Conv(heads=H, concat=True, negative_slope=0.2, dropout=0,
+    edge_dim=D, share_weights=False): attention whose scores read the edge features -- the dca / proximity values the
+    reference computes on every contact and bridge and its model drops (gcn_utills.py:319-443; gcn.py:71):
+
+        GATv2Conv(F->H/heads, heads)·BN·PReLU -> GATv2Conv(H->H/heads, heads)·BN·PReLU -> global_max_pool -> Linear(H->H)·BN·PReLU
+        -> Linear(H->1)·BN·PReLU
+
+    ``GATv2([ctx,] hidden_channels=64, heads=1, edge_dim=None, num_classes=1, seed=0)``; hidden_channels in {16, 32, 64, 128}, a
+    multiple of heads in {1, 2, 4, 8} with at least 4 channels per head, edge_dim None or 1 .. 8 (what csrc/gatv2.hip serves;
+    there is no composed route).  With edge_dim the model reads ``batch.e`` (``uses_edge_features``): inputs are (x, a, e, i),
+    a DeviceBatch that carries e, or the batches of DeviceDisjointLoader(DeviceDataset(..., edge_features=True)), which arrive
+    with e and the transposed pattern gathered on the device (nothing is downloaded or sorted per batch).  A DeviceCSR / a
+    DeviceBatch is used as stored, pattern and e (PyG's add_self_loops=False; the reference's graphs carry every loop).  A host
+    adjacency gets PyG's add_self_loops=True: stored loops removed, one loop per node added, its features the mean over the
+    row's remaining entries (fill_value="mean"; _with_mean_self_loops).  Everything behind the convolutions is ``GCN``'s:
+    BN·PReLU, the fused max-pool pair, the one-launch BCE head, ``fit``, the optimizers of gcnx.optim.  One device: ``comm`` is
+    refused.
+
+    Hot path per convolution: gcnx_gemm (Xl | Xr = x [W_l | W_r] + [b_l | b_r], one launch), gcnx_gatv2_aggregate; backward
+    gcnx_act_bias_grad, gcnx_gatv2_bwd_edges (forward CSR), gcnx_gatv2_bwd_nodes (transposed pattern + entry permutation),
+    gcnx_gemm_dw, gcnx_act_bias_grad, gcnx_gemm_dx.
+
+    Weights: PyG's key names ``conv{1,2}.att`` ([1, heads, C]), ``.bias``, ``.lin_l.weight`` / ``.lin_r.weight`` ([out, in], as
+    torch), ``.lin_l.bias`` / ``.lin_r.bias``, ``.lin_edge.weight`` ([out, edge_dim]; with edge_dim) in ``state_dict()``; stored
+    as one stacked [in, 2 out] weight and one stacked bias per convolution, the named tensors are views.  The order follows
+    PyG 2.x's source, not a live module: prefer the named dicts.  Initialisation: glorot-uniform, zero biases, as PyG."""
+
+    PROBE_KEY = "conv1.lin_l.weight"
+    SLOPE = 0.2
+
+    def _init(self, ctx, hidden_channels=64, heads=1, edge_dim=None, num_classes=1, seed=0, comm=None):
+        h, heads = int(hidden_channels), int(heads)
+        if comm is not None:
+            raise NotImplementedError("gcnx.GATv2 runs on one device (comm is not supported)")
+        if heads not in (1, 2, 4, 8) or h % heads != 0:
+            raise NotImplementedError(f"gcnx.GATv2: heads={heads} must be 1, 2, 4 or 8 and divide hidden_channels={h}")
+        if h not in (16, 32, 64, 128) or h // heads < 4:
+            raise NotImplementedError(f"gcnx.GATv2: hidden_channels={h} must be 16, 32, 64 or 128 with at least 4 channels per head "
+                                      "(the widths the GATv2Conv kernels serve; there is no composed route)")
+        if edge_dim is not None and not 1 <= int(edge_dim) <= 8:
+            raise NotImplementedError(f"gcnx.GATv2: edge_dim={edge_dim} must be None or 1 .. 8 (what the GATv2Conv kernels serve)")
+        super()._init(ctx, h, num_classes, seed, None)
+        self.heads, self.edge_dim = heads, None if edge_dim is None else int(edge_dim)
+        self.uses_edge_features = edge_dim is not None
+        conv = lambda k: (f"att{k}", f"b{k}", f"w{k}", f"lb{k}") + ((f"we{k}",) if self.edge_dim else ())
+        self.PARAM_ORDER = conv(1) + conv(2) + ("g1", "be1", "a1", "g2", "be2", "a2") + GCN.PARAM_ORDER[10:]
+        keys = lambda k: ((f"conv{k}.att", f"att{k}", False), (f"conv{k}.bias", f"b{k}", False),
+                          (f"conv{k}.lin_l.weight", f"wl{k}", True), (f"conv{k}.lin_l.bias", f"bl{k}", False),
+                          (f"conv{k}.lin_r.weight", f"wr{k}", True), (f"conv{k}.lin_r.bias", f"br{k}", False)) + \
+            (((f"conv{k}.lin_edge.weight", f"we{k}", True),) if self.edge_dim else ())
+        self.TORCH_KEYS = keys(1) + keys(2) + GCN.TORCH_KEYS[4:]
+        self.ATT_KEYS = ("conv1.att", "conv2.att")
+
+    def _shapes(self, f_in):
+        s = super()._shapes(f_in)
+        h, d = self.hidden, self.edge_dim or 0
+        hc = (self.heads, h // self.heads)
+        s.update(att1=hc, att2=hc, w1=(f_in, 2 * h), w2=(h, 2 * h), lb1=(2 * h,), lb2=(2 * h,), we1=(d, h), we2=(d, h))
+        return s
+
+    def build(self, f_in):
+        h, heads, d = self.hidden, self.heads, self.edge_dim or 0
+        shapes = self._shapes(f_in)
+        self.f_in = int(f_in)
+        # every parameter starts on a 16-byte boundary (the kernels read att, the bias, W_e and W as float4); the padding floats
+        # have zero gradients, so the single update launch over the whole buffer leaves them at zero
+        self._alloc_flat([(k, shapes[k]) for k in self.PARAM_ORDER], align=4)
+        for t in (self.p, self.g):                      # PyG's names: the column halves of the stacked weight, the halves of the bias
+            for k in (1, 2):
+                t[f"wl{k}"], t[f"wr{k}"] = t[f"w{k}"].cols(0, h), t[f"w{k}"].cols(h, 2 * h)
+                t[f"bl{k}"], t[f"br{k}"] = t[f"lb{k}"].flat(0, h), t[f"lb{k}"].flat(h, h)
+        rng, lim, alim = self._rng, 1.0 / np.sqrt(h), np.sqrt(6.0 / (heads + h // heads))
+        att = lambda: rng.uniform(-alim, alim, shapes["att1"])
+        lin = lambda fi: np.concatenate([glorot_uniform(rng, fi, h), glorot_uniform(rng, fi, h)], axis=1)
+        init = {"att1": att(), "w1": lin(f_in), "att2": att(), "w2": lin(h),
+                "w3": rng.uniform(-lim, lim, (h, h)), "b3": rng.uniform(-lim, lim, h),
+                "w4": rng.uniform(-lim, lim, (1, h)), "b4": rng.uniform(-lim, lim, 1)}
+        if d:
+            init.update(we1=glorot_uniform(rng, d, h), we2=glorot_uniform(rng, d, h))
+        for k in ("g1", "g2", "g3", "g4"):
+            init[k] = np.ones(shapes[k])
+        for k in ("a1", "a2", "a3", "a4"):
+            init[k] = np.full(1, 0.25)
+        for k, v in init.items():
+            self.p[k].copy_from_host(np.asarray(v, np.float32))
+        self.built = True
+
+    # the attention vectors are [1, heads, C] in PyG's layout and [heads, C] here
+    def state_dict(self):
+        d = super().state_dict()
+        d.update({k: d[k][None] for k in self.ATT_KEYS})
+        return d
+
+    def gradients(self):
+        d = super().gradients()
+        d.update({k: d[k][None] for k in self.ATT_KEYS})
+        return d
+
+    def load_state_dict(self, d):
+        """Inverse of state_dict; the lin_l / lin_r halves are written into the stacked tensors.  Builds the model if needed."""
+        d = dict(d)
+        if not self.built:
+            self.build(int(np.asarray(d[self.PROBE_KEY]).shape[1]))
+        missing = [tk for tk, _, _ in self.TORCH_KEYS if tk not in d]
+        if missing:
+            raise KeyError(f"gcnx.GATv2.load_state_dict: missing {missing}")
+        host = {}
+        for tk, k, tr in self.TORCH_KEYS:
+            v = np.asarray(d[tk], np.float32)
+            if tk in self.ATT_KEYS and v.ndim == 3 and v.shape[0] == 1:
+                v = v[0]
+            v = v.T if tr else v
+            if v.shape != self.p[k].shape:
+                raise ValueError(f"{tk}: shape {np.asarray(d[tk]).shape} does not fit this model")
+            host[k] = v
+        for k in (1, 2):
+            host[f"w{k}"] = np.concatenate([host.pop(f"wl{k}"), host.pop(f"wr{k}")], axis=1)
+            host[f"lb{k}"] = np.concatenate([host.pop(f"bl{k}"), host.pop(f"br{k}")])
+        for k, v in host.items():
+            self.p[k].copy_from_host(np.ascontiguousarray(v))
+
+    def _as_batch(self, inputs, target=None):
+        if not isinstance(inputs, DeviceBatch):
+            if self.uses_edge_features and len(inputs) != 4:
+                raise ValueError(f"gcnx.GATv2(edge_dim={self.edge_dim}) takes (x, a, e, i): build the graphs with edge features "
+                                 "(Graph(e=...), from_networkx(use_edge_data='entries'))")
+            x, a, i = _without_e(inputs)
+            e = inputs[2] if self.uses_edge_features else None
+            if not isinstance(a, D.DeviceCSR):                   # a host matrix: PyG's add_self_loops=True, fill_value="mean"
+                a, e = _with_mean_self_loops(a, e, np.asarray(x).shape[0])
+            inputs = (x, a, e, i) if e is not None else (x, a, i)
+        batch = self._adopt(inputs, target, weighted=False)
+        if self.uses_edge_features and batch.e is None:
+            raise ValueError("gcnx.GATv2: the batch carries no edge features (DeviceBatch.e)")
+        return batch
+
+    def _op(self, batch):
+        """The unweighted pattern of the batch, twice: the backward walks its transposed pattern through the entry permutation
+        (DeviceCSR.transpose_perm: the one a device loader's batch arrives with, or built here, once per batch object)."""
+        if self._op_cache is None or self._op_cache[0] != batch.uid:
+            a = batch.a.unweighted()
+            a.transpose_perm()
+            self._op_cache = (batch.uid, a, a)
+        return self._op_cache[1], self._op_cache[2]
+
+    def _ensure(self, batch, sharded=False):
+        bufs = super()._ensure(batch, sharded)
+        d = self.edge_dim or 0
+        if d and (batch.e is None or batch.e.shape != (batch.a.nnz, d)):
+            raise ValueError(f"gcnx.GATv2(edge_dim={d}): the batch's edge features must be [{batch.a.nnz}, {d}], got "
+                             f"{None if batch.e is None else list(batch.e.shape)}")
+        nnz = batch.a.nnz
+        if bufs.get("gatv2_key") != (batch.n, batch.n_graphs, nnz):        # the edge buffers follow nnz as well as (n, b)
+            v, n, h, heads = self._views(), batch.n, self.hidden, self.heads
+            if not D.gatv2_conv_ok(self.ctx, n, heads, h // heads, edge_dim=d):
+                raise NotImplementedError(f"gcnx.GATv2: a batch of {n} rows at hidden_channels={h} is beyond the GATv2Conv kernels")
+            for k in ("xlr1", "xlr2", "dxlr"):
+                bufs[k] = v(k, n, 2 * h)
+            for k in ("o1", "o2"):
+                bufs[k] = v(k, n, h)
+            for k in ("alpha1", "alpha2", "dscore"):
+                bufs[k] = v(k, nnz, heads)
+            ns = max(D.gatv2_bwd_scratch_floats(self.ctx, n, heads, h // heads, d), 1)
+            bufs["scratch"] = v("gatv2_scratch", 1, ns).flat(0, ns)
+            bufs["gatv2_key"] = (batch.n, batch.n_graphs, nnz)
+        return bufs
+
+    def _v2_fwd(self, a, x, e, k, bufs, keep):
+        """z_k = GATv2Conv_k(x): Xl | Xr in one product, then scores, softmax and weighted sum in one launch; keep: alpha and O."""
+        ctx, p = self.ctx, self.p
+        xlr = bufs[f"xlr{k}"]
+        D.gemm(ctx, x, p[f"w{k}"], p[f"lb{k}"], xlr)
+        D.gatv2_aggregate(ctx, a, xlr, p[f"att{k}"], p[f"b{k}"], bufs[f"z{k}"], e=e, w_e=p.get(f"we{k}"),
+                          alpha=bufs[f"alpha{k}"] if keep else None, o_pre=bufs[f"o{k}"] if keep else None, slope=self.SLOPE)
+
+    def _v2_bwd(self, a, x, e, k, dzk, bufs, dx):
+        """dZ_k -> the gradients of GATv2Conv_k and, with dx, the gradient of its input."""
+        ctx, p, g, h = self.ctx, self.p, self.g, self.hidden
+        xlr, alpha, dxlr, w_e = bufs[f"xlr{k}"], bufs[f"alpha{k}"], bufs["dxlr"], p.get(f"we{k}")
+        D.act_bias_grad(ctx, dzk, None, dzk, None, db=g[f"b{k}"])                    # conv_k.bias: column sums of dZ_k
+        D.gatv2_bwd_edges(ctx, a, xlr, p[f"att{k}"], alpha, dzk, bufs[f"o{k}"], bufs["dscore"], dxlr.cols(h, 2 * h), g[f"att{k}"],
+                          bufs["scratch"], e=e, w_e=w_e, dw_e=g.get(f"we{k}"), slope=self.SLOPE)
+        D.gatv2_bwd_nodes(ctx, a, xlr, p[f"att{k}"], alpha, bufs["dscore"], dzk, dxlr.cols(0, h), e=e, w_e=w_e, slope=self.SLOPE)
+        D.gemm_dw(ctx, x, dxlr, g[f"w{k}"])                                          # dW_l | dW_r = x^T (dXl | dXr)
+        D.act_bias_grad(ctx, dxlr, None, dxlr, None, db=g[f"lb{k}"])                 # db_l | db_r
+        if dx is not None:
+            D.gemm_dx(ctx, dxlr, p[f"w{k}"], dx)                                     # dx = dXl W_l^T + dXr W_r^T
+
+    def _conv1(self, a, batch, bufs, mode):
+        bufs["e"] = batch.e if self.uses_edge_features else None                    # (conv2 and the backward read the same rows)
+        self._v2_fwd(a, batch.x, bufs["e"], 1, bufs, mode == "grads")
+
+    def _conv2(self, a, bufs, mode):
+        self._v2_fwd(a, bufs["y1"], bufs["e"], 2, bufs, mode == "grads")
+
+    def _conv2_bwd(self, a_t, bufs):
+        self._v2_bwd(a_t, bufs["y1"], bufs["e"], 2, bufs["dz2"], bufs, bufs["dy1"])
+
+    def _conv1_bwd(self, a_t, batch, bufs):
+        self._v2_bwd(a_t, batch.x, bufs["e"], 1, bufs["dz1"], bufs, None)            # (the input carries no gradient)
 
 
 class ECCNet(_GraphRunner):

@@ -843,6 +843,61 @@ GCNX_API int gcnx_gat_bwd_nodes(gcnx_ctx* ctx, const int32_t* rowptr_t, const in
                        const float* hf, int64_t ldh, const float* da_dst, const float* att_src, const float* att_dst,
                        float* dhf, int64_t ldg, float* da_src, float* datt_src, float* datt_dst, float* scratch);
 
+/* ---- GATv2Conv: attention whose scores read the edge features, small-feature regime (heads * c <= 128) ---------------
+ * PyG's GATv2Conv(in, c, heads, concat=True, negative_slope, dropout=0, add_self_loops=False, edge_dim, bias=True,
+ * share_weights=False) (Brody et al.): the LeakyReLU comes before the dot with att, so the score depends jointly on target,
+ * source and edge -- the layer that can weigh an entry by the dca / proximity features the reference computes and its model
+ * drops (gcn_utills.py:319-443; gcn.py:71).  CSR row i is the target, its stored entries j the sources, values are ignored,
+ * the pattern and e are used as stored.  xlr = Xl | Xr [n, 2 heads c] (ldx) is ONE array from one gcnx_gemm with the stacked
+ * weight and bias (head h owns columns [h c, h c + c) of each half); e [nnz, edge_dim] (lde) holds the entries' features in
+ * the CSR's entry order, w_e [edge_dim, heads c], att [heads, c]:
+ *     t_ij[h,c] = sum_d e_ij[d] w_e[d, h c + c]     s_ij = (Xl[j] + Xr[i]) + t_ij     g = s > 0 ? s : slope s
+ *     score_ij,h = <att[h,:], g_ij[h,:]>   alpha = softmax over the stored entries of row i   O[i,h,:] = sum_j alpha Xl[j,h,:]
+ *     out = O + bias      (a row without entries: O = 0, out = bias)
+ * s is stored nowhere; every kernel recomputes it in fp32 EXACTLY as written (contract): t starts from the rounded product
+ * of d = 0 and adds the separately rounded products of d = 1 .. edge_dim - 1 in that order (no FMA; edge_dim = 0: t = 0), one
+ * add forms Xl + Xr, one more adds t; the positive side is s > 0.  All kernels therefore agree on the side of every kink,
+ * and float32 arithmetic on the stored operands reproduces it.
+ * fp32, no float atomics, fixed summation order: the same bits on every call.  Nothing is allocated.
+ * gcnx_gatv2_conv_ok (gcn.py:71): 1 if the shapes are served: heads in {1, 2, 4, 8}, heads * c in {16, 32, 64, 128}, c >= 4,
+ * ldx >= 2 heads c, ldx % 4 == 0, n * ldx * 4 < 2^32, 0 <= edge_dim <= 8.  Every call below returns GCNX_ERR_UNSUPPORTED
+ * otherwise, and for float4 operands (everything but e, alpha, dscore and the index arrays) off a 16-byte boundary or leading
+ * dimensions that are not multiples of 4 floats >= heads * c, with nothing launched and nothing written.  n == 0 succeeds and
+ * writes nothing; negative sizes and NULL mandatory pointers are GCNX_ERR_INVALID; e, w_e (and dw_e) may be NULL only with
+ * edge_dim == 0. */
+GCNX_API int gcnx_gatv2_conv_ok(int64_t n, int32_t heads, int32_t c, int64_t ldx, int32_t edge_dim);
+/* gcn.py:71 -- out [n, heads * c] (ldo) = softmax-weighted sum of Xl over the row's entries + bias (bias may be NULL), from ONE
+ * gather of Xl[j] per entry: a running row maximum with a rescaled accumulator (one rescale per four entries, CSR order);
+ * the maximum is subtracted before every exponential and the row sum is >= 1: no overflow, no 0 / 0.  alpha [nnz, heads]
+ * (may be NULL) receives the attention coefficients in the CSR's entry order, o_pre (ldp; may be NULL) O before the bias
+ * (the backward needs both). */
+GCNX_API int gcnx_gatv2_aggregate(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, const float* xlr, int64_t ldx,
+                       int32_t n, int32_t heads, int32_t c, const float* e, int64_t lde, int32_t edge_dim, const float* w_e,
+                       const float* att, const float* bias, float slope, float* out, int64_t ldo, float* alpha, float* o_pre,
+                       int64_t ldp);
+/* gcn.py:71 -- floats of caller scratch gcnx_gatv2_bwd_edges needs (per-workgroup parts of datt | dw_e). */
+GCNX_API int64_t gcnx_gatv2_bwd_scratch_floats(int64_t n, int32_t heads, int32_t c, int32_t edge_dim);
+/* gcn.py:71 -- backward, the pass over the forward CSR.  d_out = dLoss/dout [n, heads * c] (ldd), o (ldo) = O as o_pre
+ * received it.  With r[i,h] = <d_out[i,h,:], O[i,h,:]>:
+ *     dscore[ij,h] = alpha[ij,h] (<d_out[i,h,:], Xl[j,h,:]> - r[i,h])       ds_ij = dscore att (s > 0 ? 1 : slope)
+ *     dxr[i] = sum_j ds_ij     datt[h,:] = sum_ij dscore g_ij[h,:]     dw_e[d,:] = sum_ij e_ij[d] ds_ij
+ * dscore [nnz, heads] in the CSR's entry order, dxr [n, heads * c] (ldg: e.g. the right half of a dXl | dXr array), datt
+ * [heads, c], dw_e [edge_dim, heads * c].  The datt / dw_e sums go through per-workgroup parts in scratch (row-then-entry
+ * order inside a workgroup) and a second small launch inside this call (fixed order, no atomics). */
+GCNX_API int gcnx_gatv2_bwd_edges(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, const float* xlr, int64_t ldx,
+                       int32_t n, int32_t heads, int32_t c, const float* e, int64_t lde, int32_t edge_dim, const float* w_e,
+                       const float* att, float slope, const float* alpha, const float* d_out, int64_t ldd, const float* o,
+                       int64_t ldo, float* dscore, float* dxr, int64_t ldg, float* datt, float* dw_e, float* scratch);
+/* gcn.py:71 -- backward, the pass over the transposed pattern (rowptr_t, colidx_t, perm_t of gcnx_csr_transpose_perm:
+ * perm_t[p] = the forward entry behind entry p; needed for a symmetric pattern too).  alpha, dscore and e are read in the
+ * forward entry order through perm_t:
+ *     dxl[j] = sum_i (alpha[ij] d_out[i] + ds_ij)                 [n, heads * c] (ldg: e.g. the left half of dXl | dXr)
+ * dW, db and dx of the layer are gcnx_gemm_dw, gcnx_act_bias_grad and gcnx_gemm_dx on dXl | dXr. */
+GCNX_API int gcnx_gatv2_bwd_nodes(gcnx_ctx* ctx, const int32_t* rowptr_t, const int32_t* colidx_t, const int32_t* perm_t,
+                       const float* xlr, int64_t ldx, int32_t n, int32_t heads, int32_t c, const float* e, int64_t lde,
+                       int32_t edge_dim, const float* w_e, const float* att, float slope, const float* alpha,
+                       const float* dscore, const float* d_out, int64_t ldd, float* dxl, int64_t ldg);
+
 /* ---- TopKPool: per-graph top-k selection, gated gather, induced sub-CSR ------------------------------------------
  * spektral.layers.pooling.TopKPool, the one layer the reference's training script imports (gcn.py:10) that had no kernels
  * here, in disjoint mode: y = X p / ||p||, the k_g rows of every graph with the largest y are kept, X' = (X * gate(y))[idx],
