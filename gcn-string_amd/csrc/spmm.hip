@@ -1753,6 +1753,8 @@ struct gcnx_spmm_plan {
   int32_t* gids = nullptr;              // graph index of the n1 + n2 tile records (the folded backward's dPooled row)
   int32_t* tall_gids = nullptr;         // the graphs taller than a tile (their rows go through the row chunks), ascending
   int ntall = 0;
+  int32_t* empty_gids = nullptr;        // the graphs without rows: no list above holds them (gcnx_spmm_csr_relu_bits_pool zeroes their rows)
+  int nempty = 0;
   PipeItem* items = nullptr;            // pipelined kernel: graphs, tallest first: [n16 graphs of 625..1024 rows | n32 of <= 624]
   int nitems = 0, n16 = 0;
   int2* pipe_chunks = nullptr;          // ... and the 32-row chunks of the graphs too tall for it (> 1248 rows), for the rows kernel
@@ -1783,6 +1785,7 @@ static void plan_free(gcnx_spmm_plan* p) {
   if (p->dev) (void)hipFree(p->dev);
   if (p->gids) (void)hipFree(p->gids);
   if (p->tall_gids) (void)hipFree(p->tall_gids);
+  if (p->empty_gids) (void)hipFree(p->empty_gids);
   if (p->items) (void)hipFree(p->items);
   if (p->pipe_chunks) (void)hipFree(p->pipe_chunks);
   if (p->rest) (void)hipFree(p->rest);
@@ -2314,9 +2317,13 @@ int gcnx_spmm_plan_create(gcnx_ctx* ctx, const int32_t* block_ptr, int32_t nbloc
     std::vector<int32_t> tall_gids;
     for (int g = 0; g < nblocks; ++g) if (bp[g + 1] - bp[g] > cap2) tall_gids.push_back(g);
     p->ntall = (int)tall_gids.size();
+    std::vector<int32_t> empty_gids;
+    for (int g = 0; g < nblocks; ++g) if (bp[g + 1] == bp[g]) empty_gids.push_back(g);
+    p->nempty = (int)empty_gids.size();
     hipError_t e = plan_upload(ctx, &p->dev, all);
     if (e == hipSuccess) e = plan_upload(ctx, &p->gids, gids);
     if (e == hipSuccess) e = plan_upload(ctx, &p->tall_gids, tall_gids);
+    if (e == hipSuccess) e = plan_upload(ctx, &p->empty_gids, empty_gids);
     if (e == hipSuccess) e = plan_upload(ctx, &p->pipe_chunks, tall);
     if (e == hipSuccess) e = plan_upload(ctx, &p->items, items);
     if (e == hipSuccess) e = plan_upload(ctx, &p->rest, rest);
@@ -2363,6 +2370,9 @@ static int spmm_csr_impl(const SpmmCall& c, const gcnx_spmm_plan* plan, uint32_t
   GCNX_REQUIRE(ctx, c.h != c.out, "gcnx_spmm_csr: in-place aggregation is not possible");
   const bool vec = spmm_vec_ok(c);
   if (c.out16 && !vec) return GCNX_ERR_UNSUPPORTED;
+  if (relu_bits && !vec)     // (the scalar kernel writes no bit image: an answer, as for every other call the tile kernels do not serve)
+    return gcnx_fail(ctx, GCNX_ERR_UNSUPPORTED, "gcnx_spmm_csr_relu_bits: the bit image is written by the tile kernels only "
+                     "(needs 16-byte aligned operands and leading dimensions in multiples of 4 floats): use gcnx_spmm_csr");
   if (!vec) {
     hipLaunchKernelGGL(spmm_scalar_kernel, dim3(gcnx_cdiv(c.n, 4)), dim3(256), 0, ctx->stream, c.rowptr, c.colidx, c.vals,
                        c.h, c.ldh, c.bias, c.out, c.ldo, c.n, c.f, c.act);
@@ -2473,6 +2483,18 @@ __global__ __launch_bounds__(256) void pool_parts_reduce_kernel(const float* __r
   *reinterpret_cast<float4*>(cnt + (int64_t)g * f + c) = k;
 }
 
+// pooled / cnt rows of the graphs without rows: zeros, what gcnx_segment_pool gives for an empty segment (SUM and AVG alike)
+__global__ __launch_bounds__(256) void pool_empty_rows_kernel(const int32_t* __restrict__ gids, int nempty, int32_t f,
+                                                              float* __restrict__ pooled, int64_t ldp, float* __restrict__ cnt) {
+  const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+  if (i >= (int64_t)nempty * f) return;
+  const int t = (int)(i / f), c = (int)(i - (int64_t)t * f);
+  const int g = gids[t];
+  const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+  *reinterpret_cast<float4*>(pooled + (int64_t)g * ldp + c) = z;
+  *reinterpret_cast<float4*>(cnt + (int64_t)g * f + c) = z;
+}
+
 // The pooled GCNConv's forward for a training step on a tile plan WITHOUT its output (see kDuoBitsPool): relu_bits, the
 // graphs' pooled rows and positive counts.  Graphs taller than a tile keep the old form -- their rows of `out` are written
 // by the row chunks (the folded backward gathers them) and pooled by the pool kernel over the plan's list of such graphs.
@@ -2509,6 +2531,11 @@ int gcnx_spmm_csr_relu_bits_pool(gcnx_ctx* ctx, const int32_t* rowptr, const int
                      (const float*)cpart, (const int32_t*)(plan->gids + plan->n1), graph_ptr, plan->n2, f, pool_mode == GCNX_POOL_AVG ? 1 : 0,
                      pooled, ldp, cnt);
   GCNX_LAUNCH_OK(ctx);
+  if (plan->nempty > 0) {       // graphs without rows are in neither list: their pooled / cnt rows are zeros, as gcnx_segment_pool's
+    hipLaunchKernelGGL(pool_empty_rows_kernel, dim3(gcnx_cdiv((long long)plan->nempty * f / 4, 256)), dim3(256), 0, ctx->stream,
+                       (const int32_t*)plan->empty_gids, plan->nempty, f, pooled, ldp, cnt);
+    GCNX_LAUNCH_OK(ctx);
+  }
   if (plan->nchunks > 0) {      // graphs taller than a tile: rows of `out` from the row chunks, then the pool over those graphs
     dispatch_rows(c, plan->dev + plan->n1 + plan->n2, plan->nchunks, plan->chunk_rpc, 0);
     GCNX_LAUNCH_OK(ctx);

@@ -424,7 +424,8 @@ GCNX_API int gcnx_spmm_csr_pool_bwd(gcnx_ctx* ctx, const int32_t* rowptr, const 
  * serves with a tile (graphs taller than a tile get no bits; gcnx_spmm_csr_pool_bwd folds their rows from `out`).
  * gcnx_spmm_csr_pool_bwd(..., y_bits = relu_bits) then expands the words into its 0 / 1 tile instead of reading y:
  * 4 bytes per row and slab instead of 128.  GCNX_ERR_UNSUPPORTED when gcnx_spmm_csr would not take the tile kernels
- * (no plan, too few tile units, f % 32 != 0): call gcnx_spmm_csr then and pass y_bits = NULL. */
+ * (no plan, too few tile units, f % 32 != 0, an operand that is not 16-byte aligned or a leading dimension that is no multiple
+ * of 4 floats): nothing is launched; call gcnx_spmm_csr then and pass y_bits = NULL. */
 GCNX_API int gcnx_spmm_csr_relu_bits(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, const float* vals,
                            const float* h, int64_t ldh, const float* bias, float* out, int64_t ldo, int32_t n, int32_t f,
                            const gcnx_spmm_plan* plan, void* relu_bits);
@@ -434,7 +435,9 @@ GCNX_API int gcnx_spmm_csr_relu_bits(gcnx_ctx* ctx, const int32_t* rowptr, const
  * (the layer's bias gradient).  On graphs that fit an LDS tile all three leave the aggregation's epilogue: their rows of
  * `out` are NOT written and no pool launch reads them back (2 GB of the config-3 step).  Graphs taller than a tile keep
  * the two-launch form: their rows of `out` ARE written (the folded backward gathers them) and pooled from there.
- * pooled [b, ldp], cnt [b, f].  GCNX_ERR_UNSUPPORTED (nothing launched) when the tile kernels do not serve the batch:
+ * pooled [b, ldp], cnt [b, f]: EVERY row is written -- a graph without rows (graph_ptr[g] == graph_ptr[g + 1]) gets zeros in
+ * both, what gcnx_segment_pool gives for an empty segment in SUM and AVG mode.
+ * GCNX_ERR_UNSUPPORTED (nothing launched) when the tile kernels do not serve the batch:
  * gcnx_spmm_csr_relu_bits / gcnx_spmm_csr + gcnx_pool_dense_softmax_cce then. */
 GCNX_API int gcnx_spmm_csr_relu_bits_pool(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, const float* vals, const float* h,
                         int64_t ldh, const float* bias, float* out, int64_t ldo, int32_t n, int32_t f, const gcnx_spmm_plan* plan,
