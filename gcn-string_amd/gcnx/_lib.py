@@ -160,6 +160,10 @@ SIGNATURES = {
                       _i64, _f32, _vp, _vp],
     "gcnx_sage_conv_ok": [_i64, _i32, _i32, _i64],
     "gcnx_sage_conv": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _int, _vp, _vp, _i64, _vp, _i64],
+    "gcnx_gin_conv_ok": [_i64, _i32, _i32, _i32, _i64],
+    "gcnx_gin_conv": [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _int, _vp, _i64, _vp, _i64, _vp, _i64],
+    "gcnx_gin_aggregate": [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32],
+    "gcnx_gin_eps_grad": [_vp, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _vp],
     "gcnx_gat_conv_ok": [_i64, _i32, _i32, _i64],
     "gcnx_gat_scores": [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp],
     "gcnx_gat_aggregate": [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _f32, _vp, _i64, _vp, _vp, _i64],

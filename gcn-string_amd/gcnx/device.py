@@ -791,6 +791,52 @@ def sage_conv(ctx, a, x, w_nb, w_root, bias, out, s=None, w_transposed=False):
     return out
 
 
+def gin_conv_ok(ctx, n, k0, k1, k2=0, ldx=None):
+    """True if gin_conv serves these shapes (gcnx_gin_conv_ok); k2 = 0: the single-stage form."""
+    return bool(ctx.lib.gcnx_gin_conv_ok(int(n), int(k0), int(k1), int(k2), int(ldx if ldx is not None else k0)))
+
+
+def gin_conv(ctx, a, x, eps, w_a, b_a, w_b, b_b, out, t=None, u=None, w_transposed=False):
+    """out = relu(T w_a + b_a) w_b + b_b with T = (1 + eps) x + A x in one launch (gcnx_gin_conv); A = the stored pattern of
+    ``a``, its values are not read.  eps: a device array of one float, or None (0).  t / u (optional) receive T and
+    relu(T w_a + b_a).  w_b None: the single-stage form out = T w_a (+ b_a), no ReLU (u and b_b must be None).
+    w_transposed: the weights are [out, in] -- the backward form dX = ((1 + eps) dU + A^T dU) W_a^T with the layer's weight
+    as stored."""
+    n, k0 = x.shape
+    k1 = w_a.shape[0] if w_transposed else w_a.shape[1]
+    k2 = 0 if w_b is None else (w_b.shape[0] if w_transposed else w_b.shape[1])
+    assert a.n == n and w_a.shape == ((k1, k0) if w_transposed else (k0, k1)) and w_a.contiguous
+    assert w_b is None or (w_b.shape == ((k2, k1) if w_transposed else (k1, k2)) and w_b.contiguous)
+    assert out.shape == (n, k2 or k1) and (t is None or t.shape == (n, k0)) and (u is None or u.shape == (n, k1))
+    assert (b_a is None or b_a.shape == (k1,)) and (b_b is None or b_b.shape == (k2,)) and (eps is None or eps.size == 1)
+    ctx._ck(ctx.lib.gcnx_gin_conv(ctx.h, a.rowptr.ptr, a.colidx.ptr, _p(x), x.ld, n, k0, _p(eps), _p(w_a), _p(b_a), k1, _p(w_b),
+                                  _p(b_b), k2, 1 if w_transposed else 0, _p(t), t.ld if t is not None else 0, _p(u),
+                                  u.ld if u is not None else 0, _p(out), out.ld))
+    return out
+
+
+def gin_aggregate(ctx, a, x, eps, out):
+    """out = (1 + eps) x + A x for any width (gcnx_gin_aggregate); A = the stored pattern of ``a``; eps: a device array of one
+    float, or None (0).  out must not alias x."""
+    n, f = x.shape
+    assert a.n == n and out.shape == (n, f) and (eps is None or eps.size == 1)
+    ctx._ck(ctx.lib.gcnx_gin_aggregate(ctx.h, a.rowptr.ptr, a.colidx.ptr, _p(x), x.ld, _p(eps), _p(out), out.ld, n, f))
+    return out
+
+
+def gin_eps_grad_parts(n):
+    """Floats of scratch gin_eps_grad needs for n rows (one partial sum per 64 rows)."""
+    return max((int(n) + 63) // 64, 1)
+
+
+def gin_eps_grad(ctx, x, dt, parts, deps):
+    """deps[0] = sum_i <x_i, dt_i> in a fixed order (gcnx_gin_eps_grad); parts: gin_eps_grad_parts(n) floats of scratch."""
+    n, f = x.shape
+    assert dt.shape == (n, f) and parts.size >= gin_eps_grad_parts(n) and deps.size == 1
+    ctx._ck(ctx.lib.gcnx_gin_eps_grad(ctx.h, _p(x), x.ld, _p(dt), dt.ld, n, f, _p(parts), _p(deps)))
+    return deps
+
+
 def gat_conv_ok(ctx, n, heads, c, ldh=None):
     """True if the GATConv kernels serve these shapes (gcnx_gat_conv_ok)."""
     return bool(ctx.lib.gcnx_gat_conv_ok(int(n), int(heads), int(c), int(ldh if ldh is not None else heads * c)))

@@ -7,6 +7,7 @@ Reference topology: GCNConv -> GCNConv -> global pool -> Linear (gcn_utills.py:8
 832-842); live model ctor gcn.py:320, forward gcn.py:334/351, gradients gcn.py:337.
 ``SAGEConv(channels, root_weight=True, use_bias=True)`` is PyG's layer of that name (aggr="mean"), which the reference
 names as its next step (gcn_utills.py:804-806); ``GATConv(channels, heads=1)`` is PyG's attention layer for the same slot.
+``GINConv(channels, mlp_hidden=None, eps=0.0, train_eps=False)`` is PyG's / Spektral's Graph Isomorphism Network layer for it.
 ``GATv2Conv(channels, heads=1, edge_dim=None)`` is PyG's GATv2Conv: attention whose scores read the edge features (gcn.py:71).
 ``TopKPool(ratio)`` is Spektral's pooling layer of that name, which the
 reference's script imports (gcn.py:10), called as ``layer([x, a, seg])``.
@@ -261,6 +262,126 @@ class SAGEConv(Layer):
         D.spmm(ctx, a.transpose(), t, None, dx)                                     # A^T (dY W_l^T)
         if self.root_weight:
             D.gemm_dx(ctx, dy, p["lin_r.weight"], dx, accumulate=True)              # + dY W_r^T
+        return dx
+
+
+class GINConv(Layer):
+    """torch_geometric.nn.GINConv(Sequential(Linear(in, mlp_hidden), ReLU(), Linear(mlp_hidden, channels)), eps, train_eps) --
+    spektral.layers.GINConv(channels, mlp_hidden=[mlp_hidden]) is the same layer -- for the slot the reference's author left
+    open (gcn_utills.py:804-806):   out_i = MLP((1 + eps) x_i + sum_{j in N(i)} x_j),   MLP = Linear -> ReLU -> Linear
+
+    ``GINConv(channels, mlp_hidden=None, eps=0.0, train_eps=False, use_bias=True, activation=None, fused=True)``, called as
+    ``layer([x, a])`` with ``a = GINConv.preprocess(a)``: the stored pattern of ``a``, unweighted -- the adjacency is used
+    exactly as stored, no loop is added or removed (a stored self-loop counts as one more neighbour), values are ignored.
+    ``mlp_hidden`` defaults to ``channels``.  Parameters under PyG's names and in its named_parameters() order: ``eps`` (only
+    with train_eps; a device scalar either way), ``nn.0.weight``, ``nn.0.bias``, ``nn.2.weight``, ``nn.2.bias``; the weights
+    are stored [in, out] (PyG: [out, in]), initialised U(+-1/sqrt(fan_in)) as torch's Linear.  When the layer allocates its own storage every
+    tensor starts on a 4-float boundary (what gcnx_gin_conv needs of the weights); in a caller's ``p_store`` the tensors are
+    packed as the base class packs them, and a call whose weights are then off a 16-byte boundary takes the composed route.
+    ``backward(dy, need_dx=True)`` returns dx (None with need_dx=False) and leaves every
+    gradient in ``grads``.
+
+    Forward: one gcnx_gin_conv launch where it serves the shapes (csrc/gin.hip), which keeps T = (1 + eps) x + A x and
+    U = relu(T W_a + b_a); otherwise gcnx_gin_aggregate, gcnx_gemm(act=relu), gcnx_gemm.  Backward, both routes:
+    gcnx_act_bias_grad (db_b), gcnx_gemm_dx(dZ, W_b, y_mask=U, db=db_a) -> dU, gcnx_gemm_dw2 (dW_b = U^T dZ, dW_a = T^T dU).
+    dX without train_eps: the single-stage gcnx_gin_conv on the transposed pattern with x = dU and W_a as stored, or
+    gcnx_gemm_dx(dU, W_a) -> dT and gcnx_gin_aggregate(A^T, dT).  With train_eps dT = dU W_a^T is formed anyway for
+    d eps = sum <x, dT> (gcnx_gin_eps_grad), and dX takes gcnx_gin_aggregate(A^T, dT): no second gather-and-product launch."""
+
+    def __init__(self, channels, mlp_hidden=None, eps=0.0, train_eps=False, use_bias=True, activation=None, fused=True, **kw):
+        super().__init__(**kw)
+        if activation not in (None, "linear"):
+            raise NotImplementedError(f"GINConv activation {activation!r}: the layer ends in its MLP's second Linear (follow it with "
+                                      "BatchNorm1d / PReLU)")
+        self.channels = int(channels)
+        self.mlp_hidden = int(mlp_hidden) if mlp_hidden is not None else self.channels
+        self.eps, self.train_eps, self.use_bias, self.activation = float(eps), bool(train_eps), bool(use_bias), activation
+        self.fused = bool(fused)
+        self._eps_dev = None
+
+    @staticmethod
+    def preprocess(a):
+        """The stored pattern of a DeviceCSR, unweighted."""
+        return a.unweighted()
+
+    def _param_spec(self, in_dim):
+        c, m = self.channels, self.mlp_hidden
+        u = lambda fan_in, *s: self._rng.uniform(-1.0 / np.sqrt(fan_in), 1.0 / np.sqrt(fan_in), s).astype(np.float32)
+        spec = [("eps", (1,), np.full(1, self.eps, np.float32))] if self.train_eps else []
+        spec.append(("nn.0.weight", (in_dim, m), u(in_dim, in_dim, m)))
+        if self.use_bias:
+            spec.append(("nn.0.bias", (m,), u(in_dim, m)))
+        spec.append(("nn.2.weight", (m, c), u(m, m, c)))
+        if self.use_bias:
+            spec.append(("nn.2.bias", (c,), u(m, c)))
+        return spec
+
+    def build(self, ctx, in_dim, p_store=None, g_store=None, offset=0):
+        if p_store is not None:
+            off = super().build(ctx, in_dim, p_store, g_store, offset)
+        else:                                   # own storage: every tensor on a 4-float boundary (gcnx_gin_conv's weights)
+            self.ctx = ctx
+            spec = self._param_spec(in_dim)
+            pad = lambda shape: -(-int(np.prod(shape)) // 4) * 4
+            total = sum(pad(s) for _, s, _ in spec)
+            p_store, g_store, off = ctx.zeros(total), ctx.zeros(total), 0
+            for name, shape, init in spec:
+                n = int(np.prod(shape))
+                self.params[name] = p_store.flat(off, n, shape)
+                self.grads[name] = g_store.flat(off, n, shape)
+                self.params[name].copy_from_host(init)
+                off += pad(shape)
+            self.in_dim, self.built = in_dim, True
+        if not self.train_eps and self.eps != 0.0:
+            self._eps_dev = ctx.to_device(np.full(1, self.eps, np.float32))
+        return off
+
+    def _eps(self):
+        return self.params["eps"] if self.train_eps else self._eps_dev
+
+    def _one_launch(self, x, k1, k2, *others):
+        p = self.params
+        return (self.fused and D.gin_conv_ok(self.ctx, x.shape[0], x.shape[1], k1, k2, x.ld)
+                and _aligned16(x, p["nn.0.weight"], p["nn.2.weight"], *others)
+                and all(o is None or o.ld % 4 == 0 for o in others))
+
+    def call(self, inputs, out=None):
+        x, a = inputs
+        if not self.built:
+            self.build(x.ctx, x.shape[1])
+        ctx, n, c, m, p = self.ctx, x.shape[0], self.channels, self.mlp_hidden, self.params
+        y = out if out is not None else self._buf("y", (n, c))
+        t, u = self._buf("t", (n, x.shape[1])), self._buf("u", (n, m))
+        if self._one_launch(x, m, c, y, t, u):
+            D.gin_conv(ctx, a, x, self._eps(), p["nn.0.weight"], p.get("nn.0.bias"), p["nn.2.weight"], p.get("nn.2.bias"), y, t=t, u=u)
+        else:
+            D.gin_aggregate(ctx, a, x, self._eps(), t)
+            D.gemm(ctx, t, p["nn.0.weight"], p.get("nn.0.bias"), u, act="relu")
+            D.gemm(ctx, u, p["nn.2.weight"], p.get("nn.2.bias"), y)
+        self._saved = (x, a, t, u)
+        return y
+
+    def backward(self, dy, need_dx=True):
+        x, a, t, u = self._saved
+        ctx, p, g, n = self.ctx, self.params, self.grads, x.shape[0]
+        if self.use_bias:
+            D.act_bias_grad(ctx, dy, None, dy, None, db=g["nn.2.bias"])             # db_b: column sums of dy
+        du = self._buf("du", u.shape)
+        D.gemm_dx(ctx, dy, p["nn.2.weight"], du, y_mask=u, db=g.get("nn.0.bias"))    # dU = (dy W_b^T) * [U > 0], db_a
+        D.gemm_dw2(ctx, u, dy, g["nn.2.weight"], t, du, g["nn.0.weight"])            # dW_b = U^T dY, dW_a = T^T dU
+        if not (need_dx or self.train_eps):
+            return None
+        dx = self._buf("dx", x.shape) if need_dx else None
+        if not self.train_eps and self._one_launch(du, self.in_dim, 0, dx):
+            D.gin_conv(ctx, a.transpose(), du, self._eps(), p["nn.0.weight"], None, None, None, dx, w_transposed=True)
+            return dx
+        dt = self._buf("dt", x.shape)
+        D.gemm_dx(ctx, du, p["nn.0.weight"], dt)                                    # dT = dU W_a^T
+        if self.train_eps:
+            parts = self._buf("eps_parts", (D.gin_eps_grad_parts(n),))
+            D.gin_eps_grad(ctx, x, dt, parts, g["eps"])                             # d eps = sum <x, dT>
+        if need_dx:
+            D.gin_aggregate(ctx, a.transpose(), dt, self._eps(), dx)                # dX = (1 + eps) dT + A^T dT
         return dx
 
 

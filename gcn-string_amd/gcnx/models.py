@@ -16,6 +16,9 @@ Linear·BatchNorm1d·PReLU twice, one logit with BCEWithLogitsLoss (eager launch
 ``SAGE``: ``GCN`` with PyG's SAGEConv(aggr="mean") in the place of both GCNConv layers, the step the reference's author notes
 above them (gcn_utills.py:804-806); one launch per convolution (csrc/sage.hip).
 
+``GIN``: ``GCN`` with PyG's GINConv(Sequential(Linear, ReLU, Linear), train_eps) in the place of both GCNConv layers: sum
+aggregation and a two-layer MLP, one launch per convolution (csrc/gin.hip).
+
 ``GAT``: ``GCN`` with PyG's GATConv(heads, concat=True) in the place of both GCNConv layers: a softmax over the stored
 entries of every row with learned scores (csrc/gat.hip).
 
@@ -1870,6 +1873,179 @@ class SAGE(GCN):
         dz1 = bufs["dz1"]
         D.act_bias_grad(ctx, dz1, None, dz1, None, db=g["b1"])
         D.gemm_dw2(ctx, bufs["s1"], dz1, g["wl1"], batch.x, dz1, g["wr1"])           # dW_l1 = S1^T dZ1, dW_r1 = x^T dZ1
+
+
+class GIN(GCN):
+    """``GCN`` with its two GCNConv layers replaced by PyG's GINConv(Sequential(Linear, ReLU, Linear), train_eps), the Graph
+    Isomorphism Network convolution, in the slot the reference's author left open (gcn_utills.py:804-806):
+
+        GINConv(F->H)·BN·PReLU -> GINConv(H->H)·BN·PReLU -> global_max_pool -> Linear(H->H)·BN·PReLU -> Linear(H->1)·BN·PReLU
+
+    ``GIN([ctx,] hidden_channels=64, train_eps=False, num_classes=1, seed=0, comm=None)``; both MLP layers of both
+    convolutions are H wide.  out_i = MLP((1 + eps) x_i + sum_{j in N(i)} x_j) on the adjacency exactly as stored: no
+    self-loop is added or removed (a stored one counts as one more neighbour), values are ignored.
+    ``forward(x, edge_index, batch)`` counts duplicate edges once, as ``GCN`` does (PyG's sum would count them twice: a
+    deviation).  Everything behind the convolutions is ``GCN``'s: BN·PReLU, the fused max-pool pair, the one-launch BCE head,
+    sync-BN over shards (``comm=``), ``set_optimizer``, ``fit``.
+
+    Hot path: gcnx_gin_conv, one launch per convolution (csrc/gin.hip), which keeps T = (1 + eps) x + A x and
+    U = relu(T W_a + b_a); backward gcnx_act_bias_grad, gcnx_gemm_dx(y_mask=U, db) and gcnx_gemm_dw2 per convolution, and for
+    conv2's dX the single-stage gcnx_gin_conv on the transposed pattern.  With train_eps, dT = dU W_a^T is formed for
+    d eps = sum <x, dT> (gcnx_gin_eps_grad) and conv2's dX is gcnx_gin_aggregate(A^T, dT) instead.  GCNX_GIN_FUSED=0 (read at
+    construction), and any shape gcnx_gin_conv refuses (hidden > 128; a width outside {16, 32, 64, 128} on the gathered side),
+    takes the composed route per launch: gcnx_gin_aggregate, gcnx_gemm(relu), gcnx_gemm; gcnx_gemm_dx, gcnx_gin_aggregate.
+
+    Weights: torch key names ``conv{1,2}.eps`` [1], ``conv{1,2}.nn.0.weight``, ``.nn.0.bias``, ``.nn.2.weight``, ``.nn.2.bias``
+    in ``state_dict()`` ([out, in], as torch; stored [in, out] here).  ``conv{1,2}.eps`` is always in ``state_dict()`` /
+    ``load_state_dict()`` -- PyG registers it as a parameter or as a buffer -- and in ``get_weights()`` / ``gradients()`` /
+    the flat buffer only with train_eps (one float padded to four, like every tensor).  Initialisation U(+-1/sqrt(fan_in)) as
+    torch's Linear, eps 0.  The key order follows PyG 2.x's source (eps before nn.*); it was not confirmed against a live
+    torch_geometric: prefer the named dicts."""
+
+    PROBE_KEY = "conv1.nn.0.weight"
+
+    def _init(self, ctx, hidden_channels=64, train_eps=False, num_classes=1, seed=0, comm=None):
+        super()._init(ctx, hidden_channels, num_classes, seed, comm)
+        self.train_eps = bool(train_eps)
+        self._fused = os.environ.get("GCNX_GIN_FUSED", "1") != "0"     # knob, read once
+        conv = lambda k: ((f"e{k}",) if self.train_eps else ()) + (f"wa{k}", f"ba{k}", f"wb{k}", f"bb{k}", f"g{k}", f"be{k}", f"a{k}")
+        self.PARAM_ORDER = conv(1) + conv(2) + GCN.PARAM_ORDER[10:]
+        self.EPS_KEYS = (("conv1.eps", "e1", False), ("conv2.eps", "e2", False))
+        keys = lambda k: (self.EPS_KEYS[k - 1:k] if self.train_eps else ()) + (
+            (f"conv{k}.nn.0.weight", f"wa{k}", True), (f"conv{k}.nn.0.bias", f"ba{k}", False),
+            (f"conv{k}.nn.2.weight", f"wb{k}", True), (f"conv{k}.nn.2.bias", f"bb{k}", False))
+        self.TORCH_KEYS = keys(1) + keys(2) + GCN.TORCH_KEYS[4:]      # the trainable tensors, named_parameters() order
+        self._eps_fixed = None
+
+    def _shapes(self, f_in):
+        h = self.hidden
+        s = super()._shapes(f_in)
+        for k in ("w1", "b1", "w2", "b2"):
+            del s[k]
+        s.update(e1=(1,), e2=(1,), wa1=(f_in, h), wb1=(h, h), wa2=(h, h), wb2=(h, h), ba1=(h,), bb1=(h,), ba2=(h,), bb2=(h,))
+        return s
+
+    def build(self, f_in):
+        h = self.hidden
+        if h > 256:
+            raise NotImplementedError("gcnx.GIN: hidden_channels <= 256 (the one-workgroup head)")
+        shapes = self._shapes(f_in)
+        self.f_in = int(f_in)
+        # every parameter starts on a 16-byte boundary (gcnx_gin_conv needs its weights there); the padding floats have zero
+        # gradients, so the single SGD launch over the whole buffer leaves them at zero
+        self._alloc_flat([(k, shapes[k]) for k in self.PARAM_ORDER], align=4)
+        if not self.train_eps:                  # eps stays a device scalar (a loaded checkpoint may carry a value), outside the
+            self._eps_fixed = self.ctx.zeros(8)                       # flat buffers: no gradient, no update
+        rng = self._rng
+        u = lambda fan_in, *s: rng.uniform(-1.0 / np.sqrt(fan_in), 1.0 / np.sqrt(fan_in), s)
+        init = {"wa1": u(f_in, f_in, h), "ba1": u(f_in, h), "wb1": u(h, h, h), "bb1": u(h, h),
+                "wa2": u(h, h, h), "ba2": u(h, h), "wb2": u(h, h, h), "bb2": u(h, h),
+                "w3": u(h, h, h), "b3": u(h, h), "w4": u(h, 1, h), "b4": u(h, 1)}
+        for k in ("g1", "g2", "g3", "g4"):
+            init[k] = np.ones(shapes[k])
+        for k in ("a1", "a2", "a3", "a4"):
+            init[k] = np.full(1, 0.25)
+        for k, v in init.items():
+            self.p[k].copy_from_host(np.asarray(v, np.float32))
+        self.built = True
+
+    def _eps(self, k):
+        """conv k's eps as a device array of one float: a parameter with train_eps, a constant otherwise."""
+        return self.p[f"e{k}"] if self.train_eps else self._eps_fixed.flat(4 * (k - 1), 1)
+
+    def state_dict(self):
+        d = super().state_dict()
+        if self.train_eps:
+            return d
+        fixed = self._eps_fixed.numpy()          # both constants in one copy: conv k's at float 4 (k - 1)
+        out = {}
+        for tk, v in d.items():                 # conv{k}.eps in front of conv{k}.nn.0.weight, as PyG lists its buffer
+            for k, (ek, _, _) in enumerate(self.EPS_KEYS):
+                if tk == f"conv{k + 1}.nn.0.weight":
+                    out[ek] = fixed[4 * k:4 * k + 1].copy()
+            out[tk] = v
+        return out
+
+    def load_state_dict(self, d):
+        super().load_state_dict(d)
+        if not self.train_eps:
+            missing = [tk for tk, _, _ in self.EPS_KEYS if tk not in d]
+            if missing:
+                raise KeyError(f"gcnx.GIN.load_state_dict: missing {missing}")
+            for tk, k, _ in self.EPS_KEYS:
+                self._eps(int(k[1])).copy_from_host(np.asarray(d[tk], np.float32).reshape(1))
+
+    def _as_batch(self, inputs, target=None):
+        return self._adopt(inputs, target, weighted=False)       # the adjacency as stored: no loops added
+
+    def _op(self, batch):
+        """The unweighted pattern of the batch and its transpose (built once per batch object)."""
+        if self._op_cache is None or self._op_cache[0] != batch.uid:
+            a = batch.a.unweighted()
+            self._op_cache = (batch.uid, a, a.transpose())
+        return self._op_cache[1], self._op_cache[2]
+
+    def _ensure(self, batch, sharded=False):
+        bufs = super()._ensure(batch, sharded)
+        if "t1" not in bufs:
+            v, n, h = self._views(), batch.n, self.hidden
+            bufs["t1"], bufs["u1"], bufs["u2"] = v("t1", n, batch.f), v("u1", n, h), v("u2", n, h)
+            if self.train_eps:
+                bufs["dt1"] = v("dt1", n, batch.f)
+                np_ = D.gin_eps_grad_parts(n)
+                bufs["eps_parts"] = v("eps_parts", 1, np_).flat(0, np_)
+        return bufs
+
+    def _one_launch(self, x, k1, k2, *others):
+        return (self._fused and D.gin_conv_ok(self.ctx, x.shape[0], x.shape[1], k1, k2, x.ld)
+                and all(a.ptr % 16 == 0 and a.ld % 4 == 0 for a in (x,) + others))
+
+    def _conv(self, a, x, k, out, t, u, keep):
+        """out = relu(T W_a + b_a) W_b + b_b, T = (1 + eps) x + A x: one launch, or the composed route.  t and u: room for T and
+        the ReLU output (the operands of the weight gradients, and the mask), which the one launch stores only with ``keep``
+        (a step that goes on to the gradients); the composed route passes through them either way."""
+        ctx, p = self.ctx, self.p
+        wa, ba, wb, bb = p[f"wa{k}"], p[f"ba{k}"], p[f"wb{k}"], p[f"bb{k}"]
+        if self._one_launch(x, wa.shape[1], wb.shape[1], out, t, u):
+            D.gin_conv(ctx, a, x, self._eps(k), wa, ba, wb, bb, out, t=t if keep else None, u=u if keep else None)
+            return
+        D.gin_aggregate(ctx, a, x, self._eps(k), t)
+        D.gemm(ctx, t, wa, ba, u, act="relu")
+        D.gemm(ctx, u, wb, bb, out)
+
+    def _conv_bwd(self, a_t, x, k, dz, t, u, bufs, dx, dt):
+        """dZ_k -> conv k's gradients and, with dx, the gradient of its input.  dt: room for dT = dU W_a^T (train_eps, or the
+        composed dX)."""
+        ctx, p, g = self.ctx, self.p, self.g
+        du = bufs["h1"]                                                             # (forward scratch of the base class: free here)
+        D.act_bias_grad(ctx, dz, None, dz, None, db=g[f"bb{k}"])                     # db_b: column sums of dZ
+        D.gemm_dx(ctx, dz, p[f"wb{k}"], du, y_mask=u, db=g[f"ba{k}"])                # dU = (dZ W_b^T) * [U > 0], db_a
+        D.gemm_dw2(ctx, u, dz, g[f"wb{k}"], t, du, g[f"wa{k}"])                      # dW_b = U^T dZ, dW_a = T^T dU
+        if self.train_eps:
+            D.gemm_dx(ctx, du, p[f"wa{k}"], dt)                                     # dT = dU W_a^T
+            D.gin_eps_grad(ctx, x, dt, bufs["eps_parts"], g[f"e{k}"])                # d eps = sum <x, dT>
+            if dx is not None:
+                D.gin_aggregate(ctx, a_t, dt, self._eps(k), dx)                     # dX = (1 + eps) dT + A^T dT
+        elif dx is not None:
+            if self._one_launch(du, x.shape[1], 0, dx):
+                D.gin_conv(ctx, a_t, du, self._eps(k), p[f"wa{k}"], None, None, None, dx, w_transposed=True)
+                return
+            D.gemm_dx(ctx, du, p[f"wa{k}"], dt)
+            D.gin_aggregate(ctx, a_t, dt, self._eps(k), dx)
+
+    def _conv1(self, a, batch, bufs, mode):
+        self._conv(a, batch.x, 1, bufs["z1"], bufs["t1"], bufs["u1"], mode == "grads")
+
+    def _conv2(self, a, bufs, mode):
+        self._conv(a, bufs["y1"], 2, bufs["z2"], bufs["s2"], bufs["u2"], mode == "grads")
+
+    def _conv2_bwd(self, a_t, bufs):
+        """dZ2 -> conv2's gradients and dY1."""
+        self._conv_bwd(a_t, bufs["y1"], 2, bufs["dz2"], bufs["s2"], bufs["u2"], bufs, bufs["dy1"], bufs["t"])
+
+    def _conv1_bwd(self, a_t, batch, bufs):
+        """dZ1 -> conv1's gradients (the input carries no gradient)."""
+        self._conv_bwd(a_t, batch.x, 1, bufs["dz1"], bufs["t1"], bufs["u1"], bufs, None, bufs.get("dt1"))
 
 
 class GAT(GCN):

@@ -797,6 +797,51 @@ GCNX_API int gcnx_sage_conv(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t*
                       const float* x, int64_t ldx, int32_t n, int32_t fi, const float* w_nb, const float* w_root,
                       int32_t fo, int w_transposed, const float* bias, float* s, int64_t lds, float* out, int64_t ldo);
 
+/* ---- GINConv: sum aggregation + two-layer MLP as one launch, small-feature regime (widths <= 128) ----------------------
+ * The Graph Isomorphism Network convolution (PyG GINConv(Sequential(Linear, ReLU, Linear)), Spektral GINConv(mlp_hidden)) for
+ * the slot the reference's author left open (gcn_utills.py:804-806):
+ *     T = (1 + *eps) x + A x                 A = the stored pattern as all ones: values are not an operand
+ *     U = relu(T w_a + b_a)                  [n, k1]
+ *     out = U w_b + b_b                      [n, k2]
+ * One workgroup owns 32 rows from the neighbour gather to the second bias: two chained fp32 MFMA products behind the gather,
+ * the first one's accumulators handed over through an LDS tile -- one launch instead of gcnx_gin_aggregate + two gcnx_gemm
+ * and no [N, F] intermediate between them.  Exact fp32 products, no atomics, every row summed in CSR order from +0: the same
+ * bits on every call.  Nothing is allocated: the call can be captured.
+ * gcnx_gin_conv_ok: 1 if the shapes are served (k0 in {16, 32, 64, 128}, k1 a multiple of 16 up to 128, k2 = 0 (single
+ * stage) or a multiple of 16 up to 128, ldx >= k0, ldx % 4 == 0, n * ldx * 4 < 2^32). */
+GCNX_API int gcnx_gin_conv_ok(int64_t n, int32_t k0, int32_t k1, int32_t k2, int64_t ldx);
+/* eps: DEVICE pointer to one float (NULL: 0) -- it lives in the model's flat parameter buffer, so optimizers and captured
+ * steps see its updates without a host round trip.  b_a, b_b may be NULL.  t [n, k0] and u [n, k1] (may be NULL) receive
+ * T and U: the operands of dW_a = T^T dU and dW_b = U^T dZ; U is also the ReLU mask.  A row without entries has
+ * T = (1 + eps) x exactly.  Rows of the last tile at or past n are never stored.
+ * Single stage: w_b == NULL and k2 == 0 gives out [n, k1] = T w_a (+ b_a) with no ReLU; u and b_b must then be NULL.
+ * w_transposed == 0: w_a [k0, k1], w_b [k1, k2], row-major and contiguous; w_transposed == 1: w_a [k1, k0], w_b [k2, k1] --
+ * the layer's backward then passes its weights as stored: dX = ((1 + eps) dU + A^T dU) W_a^T is the single-stage call on the
+ * transposed pattern with x = dU, k0 = the layer's hidden width and k1 = its input width.
+ * GCNX_ERR_UNSUPPORTED, with nothing launched or written: shapes gcnx_gin_conv_ok refuses; x, w_a, w_b, t, u or out off a
+ * 16-byte boundary; ldt < k0, ldu < k1, ldo < the width of out, or one of them not a multiple of 4 floats -- use
+ * gcnx_gin_aggregate + gcnx_gemm then.  GCNX_ERR_INVALID: a negative size, w_b / k2 not given together, u or b_b given without
+ * a second stage, a NULL mandatory pointer (rowptr, colidx, x, w_a, out), outputs that alias x or each other.
+ * n == 0 succeeds and writes nothing. */
+GCNX_API int gcnx_gin_conv(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, const float* x, int64_t ldx, int32_t n,
+                      int32_t k0, const float* eps, const float* w_a, const float* b_a, int32_t k1, const float* w_b,
+                      const float* b_b, int32_t k2, int w_transposed, float* t, int64_t ldt, float* u, int64_t ldu, float* out,
+                      int64_t ldo);
+/* out[n, f] = (1 + *eps) x + A x for ANY f >= 1 and any leading dimensions >= f (eps: device pointer, NULL = 0): the first step
+ * of the composed route, the route for widths gcnx_gin_conv refuses and, on the transposed pattern, the last step of the
+ * composed backward.  float4 lanes when f % 4 == 0 and x, out, ldx, ldo allow 16-byte accesses (then the bits of
+ * gcnx_gin_conv's t), scalar lanes otherwise.  Every row is written; a row's entries are added in CSR order from +0:
+ * deterministic.  out must not alias x (GCNX_ERR_INVALID, as for f < 1, ld < f, negative n or NULL pointers).  n == 0
+ * succeeds and writes nothing. */
+GCNX_API int gcnx_gin_aggregate(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, const float* x, int64_t ldx,
+                      const float* eps, float* out, int64_t ldo, int32_t n, int32_t f);
+/* *deps = sum_i <x_i, dt_i> over the n rows of x, dt [n, f]: the gradient with respect to eps from dT = dU W_a^T.  Written,
+ * never accumulated; n == 0 writes 0.  Two launches, no atomics, a fixed summation order: workgroup g sums rows
+ * [64 g, 64 g + 64) into parts[g], then one workgroup sums the parts.  parts: caller-provided room for (n + 63) / 64 floats
+ * (may be NULL when n == 0); deps: device pointer to one float. */
+GCNX_API int gcnx_gin_eps_grad(gcnx_ctx* ctx, const float* x, int64_t ldx, const float* dt, int64_t lddt, int64_t n, int32_t f,
+                      float* parts, float* deps);
+
 /* ---- GATConv: edge-softmax attention, small-feature regime (heads * c <= 128) -------------------------------------
  * PyG's GATConv(in, c, heads, concat=True, negative_slope, dropout=0, bias=True), the attention layer for the slot the
  * reference's author marked as open ("consider using class SAGEConv instead", gcn_utills.py:804-806).  CSR row i is the
