@@ -1255,8 +1255,8 @@ int gcnx_gemm(gcnx_ctx* ctx, const float* x, int64_t ldx, const float* w, const 
 }
 
 // The ReLU mask of a Dense layer as a BIT IMAGE between its forward and its backward product (large batches on the
-// streaming bf16 kernel): gcnx_gemm_relu_bits is gcnx_gemm(act = RELU) that also writes [out > 0] -- 32 bytes per row, in
-// the kernel's lane order (private to the pair) -- and gcnx_gemm_dx_bits masks dX with it instead of reading the saved
+// streaming bf16 kernel): gcnx_gemm_relu_bits is gcnx_gemm(act = RELU) that also writes [out > 0] -- 32 bytes per row (bf16x3,
+// whose column halves each keep their own: 64; gcnx.h reserves 64 for both), in the kernel's lane order (private to the pair) -- and gcnx_gemm_dx_bits masks dX with it instead of reading the saved
 // activation again: 1 GB -> 32 MB per step at config 3.  GCNX_ERR_UNSUPPORTED (no launch) when the shape / precision is
 // not the streaming kernel's one-plane form: use gcnx_gemm / gcnx_gemm_dx then.
 int gcnx_gemm_relu_bits(gcnx_ctx* ctx, const float* x, int64_t ldx, const float* w, const float* bias, float* out, int64_t ldo,
