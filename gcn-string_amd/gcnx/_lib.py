@@ -164,6 +164,9 @@ SIGNATURES = {
     "gcnx_gin_conv": [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _int, _vp, _i64, _vp, _i64, _vp, _i64],
     "gcnx_gin_aggregate": [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32],
     "gcnx_gin_eps_grad": [_vp, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _vp],
+    "gcnx_pna_aggregate": [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _f32, _vp, _i64, _vp, _i64, _i32, _i32],
+    "gcnx_pna_bwd_scratch_floats": [_i64, _i32, C.POINTER(_i64)],
+    "gcnx_pna_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _f32, _vp, _i64, _vp, _i32, _i32],
     "gcnx_gat_conv_ok": [_i64, _i32, _i32, _i64],
     "gcnx_gat_scores": [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp],
     "gcnx_gat_aggregate": [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _f32, _vp, _i64, _vp, _vp, _i64],

@@ -837,6 +837,35 @@ def gin_eps_grad(ctx, x, dt, parts, deps):
     return deps
 
 
+def pna_aggregate(ctx, a, x, pq, avg_deg_log, c, stats=None):
+    """c [n, 13f] = [x | A | s_amp A | s_att A], A = [mean | min | max | std] of the messages P_i + Q_j over the stored
+    entries of every row of ``a`` (gcnx_pna_aggregate); pq [n, 2f] = P | Q.  stats [n, 6f] (optional) receives
+    meanQ | minQ | maxQ | std | cmin | cmax for pna_bwd.  The values of ``a`` are not read."""
+    n, f = x.shape
+    assert a.n == n and pq.shape == (n, 2 * f) and c.shape == (n, 13 * f) and (stats is None or stats.shape == (n, 6 * f))
+    ctx._ck(ctx.lib.gcnx_pna_aggregate(ctx.h, a.rowptr.ptr, a.colidx.ptr, _p(x), x.ld, _p(pq), pq.ld, float(avg_deg_log), _p(c), c.ld,
+                                       _p(stats), stats.ld if stats is not None else 0, n, f))
+    return c
+
+
+def pna_bwd_scratch_floats(ctx, n, f):
+    """Floats of scratch pna_bwd needs for n rows of width f (gcnx_pna_bwd_scratch_floats)."""
+    out = C.c_int64()
+    ctx._ck(ctx.lib.gcnx_pna_bwd_scratch_floats(int(n), int(f), C.byref(out)))
+    return int(out.value)
+
+
+def pna_bwd(ctx, a, a_t, pq, stats, dc, avg_deg_log, dpq, scratch):
+    """dpq [n, 2f] = dP | dQ from dc [n, 13f] (gcnx_pna_bwd); a_t = a.transpose(); pq and stats as pna_aggregate read and
+    wrote them.  Block 0 of dc (the direct dX) is not touched.  scratch: pna_bwd_scratch_floats floats."""
+    n, f = pq.shape[0], pq.shape[1] // 2
+    assert a.n == n and a_t.n == n and pq.shape == (n, 2 * f) and stats.shape == (n, 6 * f) and dc.shape == (n, 13 * f)
+    assert dpq.shape == (n, 2 * f) and scratch.contiguous and scratch.size >= 4 * n * f
+    ctx._ck(ctx.lib.gcnx_pna_bwd(ctx.h, a.rowptr.ptr, a.colidx.ptr, a_t.rowptr.ptr, a_t.colidx.ptr, _p(pq), pq.ld, _p(stats), stats.ld,
+                                 _p(dc), dc.ld, float(avg_deg_log), _p(dpq), dpq.ld, _p(scratch), n, f))
+    return dpq
+
+
 def gat_conv_ok(ctx, n, heads, c, ldh=None):
     """True if the GATConv kernels serve these shapes (gcnx_gat_conv_ok)."""
     return bool(ctx.lib.gcnx_gat_conv_ok(int(n), int(heads), int(c), int(ldh if ldh is not None else heads * c)))

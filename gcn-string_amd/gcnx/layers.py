@@ -8,6 +8,7 @@ Reference topology: GCNConv -> GCNConv -> global pool -> Linear (gcn_utills.py:8
 ``SAGEConv(channels, root_weight=True, use_bias=True)`` is PyG's layer of that name (aggr="mean"), which the reference
 names as its next step (gcn_utills.py:804-806); ``GATConv(channels, heads=1)`` is PyG's attention layer for the same slot.
 ``GINConv(channels, mlp_hidden=None, eps=0.0, train_eps=False)`` is PyG's / Spektral's Graph Isomorphism Network layer for it.
+``PNAConv(channels, deg=None, avg_deg_log=None)`` is PyG's PNAConv with the mean / min / max / std aggregators and the three degree scalers.
 ``GATv2Conv(channels, heads=1, edge_dim=None)`` is PyG's GATv2Conv: attention whose scores read the edge features (gcn.py:71).
 ``TopKPool(ratio)`` is Spektral's pooling layer of that name, which the
 reference's script imports (gcn.py:10), called as ``layer([x, a, seg])``.
@@ -383,6 +384,170 @@ class GINConv(Layer):
         if need_dx:
             D.gin_aggregate(ctx, a.transpose(), dt, self._eps(), dx)                # dX = (1 + eps) dT + A^T dT
         return dx
+
+
+PNA_AGGREGATORS = ("mean", "min", "max", "std")
+PNA_SCALERS = ("identity", "amplification", "attenuation")
+
+
+def pna_avg_deg_log(deg):
+    """delta of PyG's DegreeScalerAggregation from its in-degree histogram: sum_d hist[d] log(d + 1) / sum_d hist[d]."""
+    hist = np.asarray(deg, np.float64).ravel()
+    if hist.size == 0 or hist.sum() <= 0 or np.any(hist < 0):
+        raise ValueError("PNAConv: deg must be a non-empty histogram of node counts per in-degree")
+    return float((hist * np.log(np.arange(hist.size) + 1.0)).sum() / hist.sum())
+
+
+def pna_delta(who, deg, avg_deg_log):
+    """The one delta of a PNA layer: exactly one of the histogram and the value is given."""
+    if (deg is None) == (avg_deg_log is None):
+        raise ValueError(f"{who}: give exactly one of deg (the in-degree histogram) and avg_deg_log")
+    delta = pna_avg_deg_log(deg) if deg is not None else float(avg_deg_log)
+    if not (delta > 0.0 and np.isfinite(delta)):
+        raise ValueError(f"{who}: avg_deg_log must be positive and finite, got {delta} (a training set without edges?)")
+    return delta
+
+
+def pna_refuse(who, aggregators=None, scalers=None, towers=1, pre_layers=1, post_layers=1, divide_input=False, edge_dim=None,
+               train_norm=False):
+    """NotImplementedError for every PNAConv option beside the one configuration csrc/pna.hip serves."""
+    if aggregators is not None and tuple(aggregators) != PNA_AGGREGATORS:
+        raise NotImplementedError(f"{who}: aggregators must be {list(PNA_AGGREGATORS)} (one gather computes exactly these)")
+    if scalers is not None and tuple(scalers) != PNA_SCALERS:
+        raise NotImplementedError(f"{who}: scalers must be {list(PNA_SCALERS)}")
+    if int(towers) != 1 or int(pre_layers) != 1 or int(post_layers) != 1 or divide_input:
+        raise NotImplementedError(f"{who}: towers = pre_layers = post_layers = 1 and divide_input = False only")
+    if edge_dim is not None:
+        raise NotImplementedError(f"{who}: edge features (edge_dim) are not supported")
+    if train_norm:
+        raise NotImplementedError(f"{who}: train_norm is not supported (avg_deg_log is a constant)")
+
+
+class PNAConv(Layer):
+    """torch_geometric.nn.PNAConv(in, channels, aggregators=['mean', 'min', 'max', 'std'], scalers=['identity', 'amplification',
+    'attenuation'], deg, towers=1, pre_layers=1, post_layers=1, divide_input=False, edge_dim=None, train_norm=False): Principal
+    Neighbourhood Aggregation, four statistics of the same messages, each scaled by the node's degree:
+
+        M_ij = [x_i | x_j] W_pre + b_pre = P_i + Q_j              P = x W_pre[:F] + b_pre,  Q = x W_pre[F:]
+        A_i  = [mean_j M_ij | min_j M_ij | max_j M_ij | sqrt(relu(var_j M_ij) + 1e-5)]     (a row without entries: [0 | 0 | 0 | sqrt(1e-5)])
+        C_i  = [x_i | A_i | s_amp,i A_i | s_att,i A_i],  s_amp,i = log(max(d_i, 1) + 1) / delta = 1 / s_att,i
+        out  = (C W_post + b_post) W_lin + b_lin
+
+    ``PNAConv(channels, deg=None, avg_deg_log=None, use_bias=True, seed=0)``, called as ``layer([x, a])`` with
+    ``a = PNAConv.preprocess(a)``: the stored pattern of ``a``, row = target -- used exactly as stored, no loop added or removed,
+    values ignored.  Exactly one of ``deg`` (PyG's in-degree histogram; delta = sum hist[d] log(d + 1) / sum hist) and
+    ``avg_deg_log`` (delta itself) is required.  Any other aggregator or scaler set, towers, edge_dim or train_norm raises
+    NotImplementedError.  Parameters under PyG's names: ``pre_nns.0.0.weight`` (stored [2F, F]; PyG: [F, 2F]),
+    ``pre_nns.0.0.bias``, ``post_nns.0.0.weight`` (stored [13F, H]; PyG: [H, 13F]), ``post_nns.0.0.bias``, ``lin.weight``,
+    ``lin.bias``; initialised U(+-1/sqrt(fan_in)) as torch's Linear.
+
+    Forward: gcnx_gemm twice into the halves of one [N, 2F] array (the pre weight's row halves are contiguous views),
+    gcnx_pna_aggregate (csrc/pna.hip: one gather for the four statistics, all 13 blocks of C), gcnx_gemm twice.  Backward:
+    gcnx_act_bias_grad (db_lin), gcnx_gemm_dx (dT, db_post), gcnx_gemm_dw2 (dW_lin = T^T dZ, dW_post = C^T dT), gcnx_gemm_dx
+    (dC), gcnx_pna_bwd (dP | dQ), gcnx_act_bias_grad (db_pre), gcnx_gemm_dw2 (dW_pre = x^T [dP | dQ]), and for dx two
+    gcnx_gemm_dx and a gcnx_add of dC's first block.  ``backward(dy, need_dx=True)`` returns dx."""
+
+    def __init__(self, channels, deg=None, avg_deg_log=None, use_bias=True, aggregators=None, scalers=None, towers=1, pre_layers=1,
+                 post_layers=1, divide_input=False, edge_dim=None, train_norm=False, **kw):
+        super().__init__(**kw)
+        pna_refuse("PNAConv", aggregators, scalers, towers, pre_layers, post_layers, divide_input, edge_dim, train_norm)
+        self.channels, self.use_bias = int(channels), bool(use_bias)
+        self.avg_deg_log = pna_delta("PNAConv", deg, avg_deg_log)
+
+    @staticmethod
+    def preprocess(a):
+        """The stored pattern of a DeviceCSR, unweighted."""
+        return a.unweighted()
+
+    def _param_spec(self, in_dim):
+        f, h = in_dim, self.channels
+        u = lambda fan_in, *s: self._rng.uniform(-1.0 / np.sqrt(fan_in), 1.0 / np.sqrt(fan_in), s).astype(np.float32)
+        spec = []
+        for name, fi, fo in (("pre_nns.0.0", 2 * f, f), ("post_nns.0.0", 13 * f, h), ("lin", h, h)):
+            spec.append((name + ".weight", (fi, fo), u(fi, fi, fo)))
+            if self.use_bias:
+                spec.append((name + ".bias", (fo,), u(fi, fo)))
+        return spec
+
+    def build(self, ctx, in_dim, p_store=None, g_store=None, offset=0):
+        if p_store is not None:
+            return super().build(ctx, in_dim, p_store, g_store, offset)
+        self.ctx = ctx                          # own storage: every tensor on a 4-float boundary (float4 lanes, the dW launches)
+        spec = self._param_spec(in_dim)
+        pad = lambda shape: -(-int(np.prod(shape)) // 4) * 4
+        total = sum(pad(s) for _, s, _ in spec)
+        p_store, g_store, off = ctx.zeros(total), ctx.zeros(total), 0
+        for name, shape, init in spec:
+            n = int(np.prod(shape))
+            self.params[name] = p_store.flat(off, n, shape)
+            self.grads[name] = g_store.flat(off, n, shape)
+            self.params[name].copy_from_host(init)
+            off += pad(shape)
+        self.in_dim, self.built = in_dim, True
+        return off
+
+    def call(self, inputs, out=None, training=True):
+        x, a = inputs
+        if not self.built:
+            self.build(x.ctx, x.shape[1])
+        ctx, p, n, f, h = self.ctx, self.params, x.shape[0], x.shape[1], self.channels
+        y = out if out is not None else self._buf("y", (n, h))
+        pq, c, t = self._buf("pq", (n, 2 * f)), self._buf("c", (n, 13 * f)), self._buf("t", (n, h))
+        stats = self._buf("stats", (n, 6 * f)) if training else None
+        pna_forward(ctx, a, x, p["pre_nns.0.0.weight"], p.get("pre_nns.0.0.bias"), p["post_nns.0.0.weight"], p.get("post_nns.0.0.bias"),
+                    p["lin.weight"], p.get("lin.bias"), self.avg_deg_log, pq, c, stats, t, y)
+        self._saved = (x, a, pq, c, stats, t)
+        return y
+
+    def backward(self, dy, need_dx=True):
+        x, a, pq, c, stats, t = self._saved
+        if stats is None:
+            raise RuntimeError("PNAConv.backward: the forward ran with training=False (no statistics were kept)")
+        ctx, p, g, n, f, h = self.ctx, self.params, self.grads, x.shape[0], x.shape[1], self.channels
+        ns = D.pna_bwd_scratch_floats(ctx, n, f)
+        dx = self._buf("dx", (n, f)) if need_dx else None
+        pna_backward(ctx, a, a.transpose(), x, pq, c, stats, t, dy, p["pre_nns.0.0.weight"], p["post_nns.0.0.weight"], p["lin.weight"],
+                     g["pre_nns.0.0.weight"], g.get("pre_nns.0.0.bias"), g["post_nns.0.0.weight"], g.get("post_nns.0.0.bias"),
+                     g["lin.weight"], g.get("lin.bias"), self.avg_deg_log, self._buf("dt", (n, h)), self._buf("dc", (n, 13 * f)),
+                     self._buf("dpq", (n, 2 * f)), self._buf("coef", (ns,)), dx)
+        return dx
+
+
+def pna_forward(ctx, a, x, w_pre, b_pre, w_post, b_post, w_lin, b_lin, delta, pq, c, stats, t, out):
+    """One PNAConv forward (PNAConv.call and gcnx.PNA share it): pq = P | Q, c = the 13 blocks, t = C W_post + b_post,
+    out = t W_lin + b_lin.  Weights stored [in, out]; stats None: no backward follows."""
+    f = x.shape[1]
+    D.gemm(ctx, x, w_pre.flat(0, f * f, (f, f)), b_pre, pq.cols(0, f))                      # P = x W_pre[:F] + b_pre
+    D.gemm(ctx, x, w_pre.flat(f * f, f * f, (f, f)), None, pq.cols(f, 2 * f))               # Q = x W_pre[F:]
+    D.pna_aggregate(ctx, a, x, pq, delta, c, stats)
+    D.gemm(ctx, c, w_post, b_post, t)
+    D.gemm(ctx, t, w_lin, b_lin, out)
+
+
+def pna_backward(ctx, a, a_t, x, pq, c, stats, t, dz, w_pre, w_post, w_lin, g_w_pre, g_b_pre, g_w_post, g_b_post, g_w_lin, g_b_lin,
+                 delta, dt, dc, dpq, coef, dx):
+    """One PNAConv backward from dz = dLoss / dout: every parameter gradient, and into dx (None: not needed) the gradient of
+    the layer's input.  dt [n, H], dc [n, 13F], dpq [n, 2F] and coef (pna_bwd_scratch_floats) are scratch."""
+    f = x.shape[1]
+    if g_b_lin is not None:
+        D.act_bias_grad(ctx, dz, None, dz, None, db=g_b_lin)                               # db_lin: column sums of dZ
+    D.gemm_dx(ctx, dz, w_lin, dt, db=g_b_post)                                             # dT = dZ W_lin^T, db_post
+    D.gemm_dw2(ctx, t, dz, g_w_lin, c, dt, g_w_post)                                       # dW_lin = T^T dZ, dW_post = C^T dT
+    D.gemm_dx(ctx, dt, w_post, dc)                                                         # dC = dT W_post^T
+    D.pna_bwd(ctx, a, a_t, pq, stats, dc, delta, dpq, coef)                                # dP | dQ (block 0 of dC untouched)
+    dp, dq = dpq.cols(0, f), dpq.cols(f, 2 * f)
+    if g_b_pre is not None:
+        D.act_bias_grad(ctx, dp, None, dp, None, db=g_b_pre)                               # db_pre: column sums of dP
+    g_top, g_bot = g_w_pre.flat(0, f * f, (f, f)), g_w_pre.flat(f * f, f * f, (f, f))
+    if f % 4 == 0:
+        D.gemm_dw2(ctx, x, dp, g_top, x, dq, g_bot)                                        # dW_pre = x^T [dP | dQ]
+    else:                                       # (the lower half starts off a 16-byte boundary: one launch each)
+        D.gemm_dw(ctx, x, dp, g_top)
+        D.gemm_dw(ctx, x, dq, g_bot)
+    if dx is not None:                          # dx = dC[:, :F] + dP W_pre[:F]^T + dQ W_pre[F:]^T
+        D.gemm_dx(ctx, dp, w_pre.flat(0, f * f, (f, f)), dx)
+        D.gemm_dx(ctx, dq, w_pre.flat(f * f, f * f, (f, f)), dx, accumulate=True)
+        D.add(ctx, dx, dc.cols(0, f), dx)
 
 
 class GATConv(Layer):

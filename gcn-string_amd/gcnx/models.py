@@ -19,6 +19,9 @@ above them (gcn_utills.py:804-806); one launch per convolution (csrc/sage.hip).
 ``GIN``: ``GCN`` with PyG's GINConv(Sequential(Linear, ReLU, Linear), train_eps) in the place of both GCNConv layers: sum
 aggregation and a two-layer MLP, one launch per convolution (csrc/gin.hip).
 
+``PNA``: ``GCN`` with PyG's PNAConv(mean / min / max / std, identity / amplification / attenuation) in the place of both
+GCNConv layers: four statistics of every neighbourhood from one gather (csrc/pna.hip).
+
 ``GAT``: ``GCN`` with PyG's GATConv(heads, concat=True) in the place of both GCNConv layers: a softmax over the stored
 entries of every row with learned scores (csrc/gat.hip).
 
@@ -2046,6 +2049,174 @@ class GIN(GCN):
     def _conv1_bwd(self, a_t, batch, bufs):
         """dZ1 -> conv1's gradients (the input carries no gradient)."""
         self._conv_bwd(a_t, batch.x, 1, bufs["dz1"], bufs["t1"], bufs["u1"], bufs, None, bufs.get("dt1"))
+
+
+class PNA(GCN):
+    """``GCN`` with its two GCNConv layers replaced by PyG's PNAConv(aggregators=['mean', 'min', 'max', 'std'],
+    scalers=['identity', 'amplification', 'attenuation'], deg, towers=1, pre_layers=1, post_layers=1, divide_input=False),
+    Principal Neighbourhood Aggregation -- four statistics of every neighbourhood, each scaled by the node's degree:
+
+        PNAConv(F->H)·BN·PReLU -> PNAConv(H->H)·BN·PReLU -> global_max_pool -> Linear(H->H)·BN·PReLU -> Linear(H->1)·BN·PReLU
+
+    ``PNA([ctx,] hidden_channels=64, deg=None, avg_deg_log=None, num_classes=1, seed=0, comm=None)``: exactly one of ``deg``
+    (PyG's in-degree histogram, ``PNA.degree_histogram(graphs)``) and ``avg_deg_log`` (delta, the mean of log(d + 1) over the
+    training set's nodes) is required.  The adjacency is used exactly as stored (row = target): no self-loop is added or
+    removed, values are ignored; a row without entries aggregates to [0 | 0 | 0 | sqrt(1e-5)] (gcnx.layers.PNAConv has the
+    formulas).  ``forward(x, edge_index, batch)`` counts duplicate edges once, as ``GCN`` does (a deviation from PyG).
+    Everything behind the convolutions is ``GCN``'s: BN·PReLU, the fused max-pool pair, the one-launch BCE head, sync-BN over
+    shards (``comm=``), ``set_optimizer``, ``fit``.
+
+    Hot path per convolution: gcnx_gemm twice (P | Q), gcnx_pna_aggregate (csrc/pna.hip: one gather for the four statistics
+    and all 13 blocks of C; the statistics are stored only in a step that computes gradients), gcnx_gemm twice; backward
+    gcnx_act_bias_grad, gcnx_gemm_dx, gcnx_gemm_dw2, gcnx_gemm_dx, gcnx_pna_bwd, gcnx_act_bias_grad, gcnx_gemm_dw2, and for
+    conv2's dY1 = dC[:, :H] + [dP | dQ] W_pre^T two gcnx_gemm_dx and a gcnx_add.  The 13 H wide products go through the
+    general GEMM kernels, which take any width; hidden_channels > 256 is refused (the one-workgroup head).
+
+    Weights: torch key names ``conv{1,2}.pre_nns.0.0.weight`` [F, 2F], ``.pre_nns.0.0.bias``, ``.post_nns.0.0.weight``
+    [H, 13F], ``.post_nns.0.0.bias``, ``.lin.weight``, ``.lin.bias`` in ``state_dict()`` ([out, in], as torch; stored [in, out]
+    here); initialisation U(+-1/sqrt(fan_in)) as torch's Linear.  ``conv{1,2}.aggr_module.avg_deg_log`` [1] is in
+    ``state_dict()`` too and ``load_state_dict()`` takes it when present: a constant -- not in ``get_weights()`` /
+    ``gradients()`` / the flat buffers, no gradient.  That key name and the key order follow PyG 2.3's source
+    (DegreeScalerAggregation registers the buffer; aggr_module comes before pre_nns); neither was confirmed against a live
+    torch_geometric: prefer the named dicts."""
+
+    PROBE_KEY = None                      # no tensor has the input width second: load_state_dict reads pre_nns.0.0.weight [F, 2F]
+
+    def _init(self, ctx, hidden_channels=64, deg=None, avg_deg_log=None, num_classes=1, seed=0, comm=None, **pna_options):
+        from .layers import pna_delta, pna_refuse
+        pna_refuse("gcnx.PNA", **pna_options)
+        super()._init(ctx, hidden_channels, num_classes, seed, comm)
+        delta = pna_delta("gcnx.PNA", deg, avg_deg_log)
+        self.avg_deg_log = [delta, delta]                             # conv1's, conv2's (a loaded checkpoint may carry two)
+        conv = lambda k: (f"wpre{k}", f"bpre{k}", f"wpost{k}", f"bpost{k}", f"wlin{k}", f"blin{k}", f"g{k}", f"be{k}", f"a{k}")
+        self.PARAM_ORDER = conv(1) + conv(2) + GCN.PARAM_ORDER[10:]
+        keys = lambda k: ((f"conv{k}.pre_nns.0.0.weight", f"wpre{k}", True), (f"conv{k}.pre_nns.0.0.bias", f"bpre{k}", False),
+                          (f"conv{k}.post_nns.0.0.weight", f"wpost{k}", True), (f"conv{k}.post_nns.0.0.bias", f"bpost{k}", False),
+                          (f"conv{k}.lin.weight", f"wlin{k}", True), (f"conv{k}.lin.bias", f"blin{k}", False))
+        self.TORCH_KEYS = keys(1) + keys(2) + GCN.TORCH_KEYS[4:]      # the trainable tensors, named_parameters() order
+        self.DELTA_KEYS = ("conv1.aggr_module.avg_deg_log", "conv2.aggr_module.avg_deg_log")
+
+    @staticmethod
+    def degree_histogram(graphs):
+        """PyG's ``deg`` argument from a dataset: hist[d] = the number of rows (target nodes) with d stored entries, over every
+        graph of ``graphs`` (objects with an adjacency ``.a``, or the adjacencies themselves: scipy sparse or dense)."""
+        import scipy.sparse as sp
+        hist = np.zeros(1, np.int64)
+        for g in graphs:
+            a = sp.csr_matrix(getattr(g, "a", g))
+            d = np.bincount(np.diff(a.indptr))
+            if d.size > hist.size:
+                hist = np.concatenate([hist, np.zeros(d.size - hist.size, np.int64)])
+            hist[:d.size] += d
+        return hist
+
+    def _shapes(self, f_in):
+        h = self.hidden
+        s = super()._shapes(f_in)
+        for k in ("w1", "b1", "w2", "b2"):
+            del s[k]
+        s.update(wpre1=(2 * f_in, f_in), bpre1=(f_in,), wpost1=(13 * f_in, h), bpost1=(h,), wlin1=(h, h), blin1=(h,),
+                 wpre2=(2 * h, h), bpre2=(h,), wpost2=(13 * h, h), bpost2=(h,), wlin2=(h, h), blin2=(h,))
+        return s
+
+    def build(self, f_in):
+        h = self.hidden
+        if h > 256:
+            raise NotImplementedError("gcnx.PNA: hidden_channels <= 256 (the one-workgroup head; the 13 H wide products "
+                                      "themselves go through the general GEMM kernels)")
+        shapes = self._shapes(f_in)
+        self.f_in = int(f_in)
+        # every parameter starts on a 16-byte boundary (float4 lanes of the GEMMs and of the dW reductions); the padding floats
+        # have zero gradients, so the single SGD launch over the whole buffer leaves them at zero
+        self._alloc_flat([(k, shapes[k]) for k in self.PARAM_ORDER], align=4)
+        rng = self._rng
+        u = lambda fan_in, *s: rng.uniform(-1.0 / np.sqrt(fan_in), 1.0 / np.sqrt(fan_in), s)
+        init = {"w3": u(h, h, h), "b3": u(h, h), "w4": u(h, 1, h), "b4": u(h, 1)}
+        for k, f in ((1, f_in), (2, h)):
+            init[f"wpre{k}"], init[f"bpre{k}"] = u(2 * f, 2 * f, f), u(2 * f, f)
+            init[f"wpost{k}"], init[f"bpost{k}"] = u(13 * f, 13 * f, h), u(13 * f, h)
+            init[f"wlin{k}"], init[f"blin{k}"] = u(h, h, h), u(h, h)
+        for k in ("g1", "g2", "g3", "g4"):
+            init[k] = np.ones(shapes[k])
+        for k in ("a1", "a2", "a3", "a4"):
+            init[k] = np.full(1, 0.25)
+        for k, v in init.items():
+            self.p[k].copy_from_host(np.asarray(v, np.float32))
+        self.built = True
+
+    def state_dict(self):
+        d = super().state_dict()
+        out = {}
+        for tk, v in d.items():                 # conv{k}.aggr_module.avg_deg_log in front of conv{k}.pre_nns.0.0.weight
+            for k, dk in enumerate(self.DELTA_KEYS):
+                if tk == f"conv{k + 1}.pre_nns.0.0.weight":
+                    out[dk] = np.full(1, self.avg_deg_log[k], np.float32)
+            out[tk] = v
+        return out
+
+    def load_state_dict(self, d):
+        if not self.built:                      # pre_nns.0.0.weight is [F, 2F]
+            self.build(int(np.asarray(d["conv1.pre_nns.0.0.weight"]).shape[0]))
+        super().load_state_dict(d)
+        for k, dk in enumerate(self.DELTA_KEYS):
+            if dk in d:
+                delta = float(np.asarray(d[dk], np.float64).reshape(-1)[0])
+                if not (delta > 0.0 and np.isfinite(delta)):
+                    raise ValueError(f"{dk}: must be positive and finite, got {delta}")
+                self.avg_deg_log[k] = delta
+
+    def _as_batch(self, inputs, target=None):
+        return self._adopt(inputs, target, weighted=False)       # the adjacency as stored: no loops added
+
+    def _op(self, batch):
+        """The unweighted pattern of the batch and its transpose (built once per batch object)."""
+        if self._op_cache is None or self._op_cache[0] != batch.uid:
+            a = batch.a.unweighted()
+            self._op_cache = (batch.uid, a, a.transpose())
+        return self._op_cache[1], self._op_cache[2]
+
+    def _ensure(self, batch, sharded=False):
+        bufs = super()._ensure(batch, sharded)
+        if "pq1" not in bufs:
+            v, n, h, f = self._views(), batch.n, self.hidden, batch.f
+            for k, w in ((1, f), (2, h)):
+                bufs[f"pq{k}"], bufs[f"c{k}"], bufs[f"st{k}"] = v(f"pq{k}", n, 2 * w), v(f"c{k}", n, 13 * w), v(f"st{k}", n, 6 * w)
+                bufs[f"tc{k}"] = v(f"tc{k}", n, h)
+            # backward scratch, shared by the two convolutions (conv2's runs first): sized for the wider one, viewed per width
+            wmax = max(f, h)
+            v("pna_dc", n, 13 * wmax), v("pna_dpq", n, 2 * wmax), v("pna_coef", n, 4 * wmax)
+            for k, w in ((1, f), (2, h)):
+                bufs[f"dc{k}"], bufs[f"dpq{k}"] = v("pna_dc", n, 13 * w), v("pna_dpq", n, 2 * w)
+                bufs[f"coef{k}"] = v("pna_coef", n, 4 * w).flat(0, 4 * n * w)
+        return bufs
+
+    def _pna_fwd(self, a, x, k, bufs, out, keep):
+        from .layers import pna_forward
+        p = self.p
+        bufs["a"] = a                           # the forward pattern: gcnx_pna_bwd reads its degrees
+        pna_forward(self.ctx, a, x, p[f"wpre{k}"], p[f"bpre{k}"], p[f"wpost{k}"], p[f"bpost{k}"], p[f"wlin{k}"], p[f"blin{k}"],
+                    self.avg_deg_log[k - 1], bufs[f"pq{k}"], bufs[f"c{k}"], bufs[f"st{k}"] if keep else None, bufs[f"tc{k}"], out)
+
+    def _pna_bwd(self, a_t, x, k, dz, bufs, dx):
+        from .layers import pna_backward
+        p, g = self.p, self.g
+        pna_backward(self.ctx, bufs["a"], a_t, x, bufs[f"pq{k}"], bufs[f"c{k}"], bufs[f"st{k}"], bufs[f"tc{k}"], dz, p[f"wpre{k}"],
+                     p[f"wpost{k}"], p[f"wlin{k}"], g[f"wpre{k}"], g[f"bpre{k}"], g[f"wpost{k}"], g[f"bpost{k}"], g[f"wlin{k}"],
+                     g[f"blin{k}"], self.avg_deg_log[k - 1], bufs["t"], bufs[f"dc{k}"], bufs[f"dpq{k}"], bufs[f"coef{k}"], dx)
+
+    def _conv1(self, a, batch, bufs, mode):
+        self._pna_fwd(a, batch.x, 1, bufs, bufs["z1"], mode == "grads")
+
+    def _conv2(self, a, bufs, mode):
+        self._pna_fwd(a, bufs["y1"], 2, bufs, bufs["z2"], mode == "grads")
+
+    def _conv2_bwd(self, a_t, bufs):
+        """dZ2 -> conv2's gradients and dY1."""
+        self._pna_bwd(a_t, bufs["y1"], 2, bufs["dz2"], bufs, bufs["dy1"])
+
+    def _conv1_bwd(self, a_t, batch, bufs):
+        """dZ1 -> conv1's gradients (the input carries no gradient)."""
+        self._pna_bwd(a_t, batch.x, 1, bufs["dz1"], bufs, None)
 
 
 class GAT(GCN):

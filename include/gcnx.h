@@ -842,6 +842,48 @@ GCNX_API int gcnx_gin_aggregate(gcnx_ctx* ctx, const int32_t* rowptr, const int3
 GCNX_API int gcnx_gin_eps_grad(gcnx_ctx* ctx, const float* x, int64_t ldx, const float* dt, int64_t lddt, int64_t n, int32_t f,
                       float* parts, float* deps);
 
+/* ---- PNAConv: mean, min, max and std of the neighbours' messages from one gather ------------------------------------------
+ * PyG's PNAConv(aggregators = [mean, min, max, std], scalers = [identity, amplification, attenuation], deg, towers = 1,
+ * pre_layers = post_layers = 1, divide_input = False, edge_dim = None, train_norm = False).  CSR row i is the target, its
+ * stored entries j are the sources; values are not an operand, no self-loop is added or removed.  The message
+ * M_ij = [x_i | x_j] W_pre + b_pre is linear, so the caller forms it per node: pq [n, 2f] = P | Q with
+ * P = x W_pre[:f] + b_pre and Q = x W_pre[f:] (column views of one array), M_ij = P_i + Q_j.  With d_i the number of stored
+ * entries of row i and delta = avg_deg_log (the mean of log(d + 1) over the training set's nodes; > 0):
+ *     A_i = [ P_i + mean_j Q_j | P_i + min_j Q_j | P_i + max_j Q_j | sqrt(relu(var_j Q_j) + 1e-5) ]   (biased variance)
+ *     d_i = 0:  A_i = [ 0 | 0 | 0 | sqrt(1e-5) ]                                                      (PyG's scatter)
+ *     c_i = [ x_i | A_i | s_amp,i A_i | s_att,i A_i ]        s_amp,i = log(max(d_i, 1) + 1) / delta,  s_att,i = 1 / s_amp,i
+ * c is [n, 13f]: scaler-major, aggregator-minor, x in front, as PyG concatenates.  All 13 blocks are written, the copy of x
+ * included.  stats (may be NULL: evaluation) receives [n, 6f] = meanQ | minQ | maxQ | std | cmin | cmax for the backward;
+ * cmin / cmax count the entries of the row that attain the extremum, per column (as floats); a row without entries stores
+ * 0 | 0 | 0 | sqrt(1e-5) | 0 | 0.  c holds the same bits with and without stats.
+ * One pass gathers each Q row once.  The variance is formed on values shifted by the row's first gathered entry K:
+ * s1 = sum (Q_j - K), s2 = sum (Q_j - K)^2, meanQ = K + s1 / d, var = s2 / d - (s1 / d)^2, and is 0 exactly where the
+ * row's minimum equals its maximum (so a d = 1 row has std = sqrt(1e-5f) to the bit).  fp32, no atomics, every sum in CSR
+ * order: the same bits on every call.  Any f >= 1 and any leading dimensions (ldx >= f, ldpq >= 2f, ldc >= 13f, lds >= 6f):
+ * float4 lanes when f % 4 == 0 and x, pq, c, stats and their leading dimensions allow 16-byte accesses, scalar lanes
+ * otherwise.  Rows of any length.  GCNX_ERR_INVALID: f < 1, a negative n, a small leading dimension, avg_deg_log <= 0, a NULL
+ * mandatory pointer, outputs that alias an input or each other.  n == 0 succeeds and writes nothing. */
+GCNX_API int gcnx_pna_aggregate(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, const float* x, int64_t ldx,
+                      const float* pq, int64_t ldpq, float avg_deg_log, float* c, int64_t ldc, float* stats, int64_t lds,
+                      int32_t n, int32_t f);
+/* *out = the floats of scratch gcnx_pna_bwd needs for n rows of width f (4 n f: four coefficient rows per target). */
+GCNX_API int gcnx_pna_bwd_scratch_floats(int64_t n, int32_t f, int64_t* out);
+/* The backward of gcnx_pna_aggregate with respect to P and Q: dpq [n, 2f] = dP | dQ from dc [n, 13f] = dLoss / dc.  Block 0
+ * of dc (the gradient that reaches x directly) is neither read nor written: it stays the caller's.  rowptr / colidx: the
+ * forward pattern (only its degrees are read); rowptr_t / colidx_t: its transpose (rows = sources, entries = their targets);
+ * pq and stats: what the forward read and wrote.  Two launches, no atomics:
+ *   per target i   (g_mean, g_min, g_max, g_std) = dc_id + s_amp,i dc_amp + s_att,i dc_att;
+ *                  dP_i = g_mean + g_min + g_max (0 for d_i = 0); four coefficient rows into scratch
+ *   per source j   dQ_j = sum over the targets i of row j of the transposed pattern, in its stored order, of
+ *                  g_mean,i / d_i + g_min,i [Q_j = minQ_i] / cmin_i + g_max,i [Q_j = maxQ_i] / cmax_i
+ *                  + g_std,i [var_i > 0] (Q_j - meanQ_i) / (d_i std_i)
+ * Ties share the gradient evenly, as torch.scatter_reduce("amin" / "amax") does; [var_i > 0] is [maxQ_i > minQ_i].
+ * scratch: gcnx_pna_bwd_scratch_floats(n, f) floats, 16-byte aligned for the float4 lanes.  Same widths, leading dimensions
+ * and errors as the forward (lddc >= 13f, lddpq >= 2f); dpq and scratch must not alias an input or each other. */
+GCNX_API int gcnx_pna_bwd(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, const int32_t* rowptr_t,
+                      const int32_t* colidx_t, const float* pq, int64_t ldpq, const float* stats, int64_t lds, const float* dc,
+                      int64_t lddc, float avg_deg_log, float* dpq, int64_t lddpq, float* scratch, int32_t n, int32_t f);
+
 /* ---- GATConv: edge-softmax attention, small-feature regime (heads * c <= 128) -------------------------------------
  * PyG's GATConv(in, c, heads, concat=True, negative_slope, dropout=0, bias=True), the attention layer for the slot the
  * reference's author marked as open ("consider using class SAGEConv instead", gcn_utills.py:804-806).  CSR row i is the
