@@ -987,6 +987,65 @@ def gatv2_bwd_nodes(ctx, a, xlr, att, alpha, dscore, dout, dxl, e=None, w_e=None
     return dxl
 
 
+def resgated_conv_ok(ctx, n, h, ldp=None, edge_dim=0):
+    """True if the ResGatedGraphConv kernels serve these shapes (gcnx_resgated_conv_ok); ldp: the leading dimension of K | Q | V."""
+    return bool(ctx.lib.gcnx_resgated_conv_ok(int(n), int(h), int(ldp if ldp is not None else 3 * h), int(edge_dim)))
+
+
+def resgated_bwd_scratch_floats(ctx, n, h, edge_dim=0):
+    """Floats of scratch resgated_bwd_targets needs (gcnx_resgated_bwd_scratch_floats)."""
+    out = C.c_int64()
+    ctx._ck(ctx.lib.gcnx_resgated_bwd_scratch_floats(int(n), int(h), int(edge_dim), C.byref(out)))
+    return int(out.value)
+
+
+def _resgated_edge(a, e, w_e, h):
+    """(e pointer, lde, edge_dim, w_e pointer) of the optional edge operands: e [nnz, D] (any ld), w_e [D, 3 h]."""
+    if e is None:
+        assert w_e is None
+        return None, 0, 0, None
+    d = e.shape[1]
+    assert e.shape[0] == a.nnz and w_e is not None and w_e.shape == (d, 3 * h) and w_e.contiguous
+    return _p(e), e.ld, d, _p(w_e)
+
+
+def resgated_aggregate(ctx, a, p, out, e=None, w_e=None, skip=None, bias=None):
+    """out = skip + bias + sum over the stored entries of ``a`` (row = target) of sigmoid(K[i] + Q[j] + e_ij (W_ke + W_qe)) *
+    (V[j] + e_ij W_ve) (gcnx_resgated_aggregate).  p = K | Q | V in its first 3 h columns; w_e [D, 3 h] = W_ke | W_qe | W_ve."""
+    n, h = out.shape
+    assert a.n == n and p.shape[0] == n and p.shape[1] >= 3 * h and (bias is None or bias.shape == (h,))
+    assert skip is None or skip.shape == (n, h)
+    ep, lde, d, wp = _resgated_edge(a, e, w_e, h)
+    ctx._ck(ctx.lib.gcnx_resgated_aggregate(ctx.h, a.rowptr.ptr, a.colidx.ptr, _p(p), p.ld, n, h, ep, lde, d, wp, _p(skip),
+                                            skip.ld if skip is not None else 0, _p(bias), _p(out), out.ld))
+    return out
+
+
+def resgated_bwd_targets(ctx, a, p, dout, dk, scratch=None, ds=None, e=None, w_e=None, dw_e=None):
+    """dk [n, h] = dK, ds (if given) = dout, dw_e [D, 3 h] on the forward pattern of ``a`` (gcnx_resgated_bwd_targets).
+    scratch: resgated_bwd_scratch_floats floats (None with no edge features)."""
+    n, h = dout.shape
+    assert a.n == n and p.shape[0] == n and p.shape[1] >= 3 * h and dk.shape == (n, h) and (ds is None or ds.shape == (n, h))
+    ep, lde, d, wp = _resgated_edge(a, e, w_e, h)
+    assert (dw_e is None) == (d == 0) and (dw_e is None or (dw_e.shape == (d, 3 * h) and dw_e.contiguous))
+    assert d == 0 or scratch.size >= resgated_bwd_scratch_floats(ctx, n, h, d)
+    ctx._ck(ctx.lib.gcnx_resgated_bwd_targets(ctx.h, a.rowptr.ptr, a.colidx.ptr, _p(p), p.ld, n, h, ep, lde, d, wp, _p(dout), dout.ld,
+                                              _p(dk), dk.ld, _p(ds), ds.ld if ds is not None else 0, _p(dw_e), _p(scratch)))
+    return dk
+
+
+def resgated_bwd_sources(ctx, a, p, dout, dqv, e=None, w_e=None):
+    """dqv [n, 2 h] = dQ | dV on the transposed pattern of ``a`` with its entry permutation (a.transpose_perm();
+    gcnx_resgated_bwd_sources)."""
+    n, h = dout.shape
+    assert a.n == n and p.shape[0] == n and p.shape[1] >= 3 * h and dqv.shape == (n, 2 * h)
+    ep, lde, d, wp = _resgated_edge(a, e, w_e, h)
+    rp, ci, pm = a.transpose_perm()
+    ctx._ck(ctx.lib.gcnx_resgated_bwd_sources(ctx.h, rp.ptr, ci.ptr, pm.ptr, _p(p), p.ld, n, h, ep, lde, d, wp, _p(dout), dout.ld,
+                                              _p(dqv), dqv.ld))
+    return dqv
+
+
 def topk_select_ok(ctx, max_graph_rows, f):
     """True if topk_select serves a batch whose largest graph has this many rows (gcnx_topk_select_ok)."""
     return bool(ctx.lib.gcnx_topk_select_ok(int(max_graph_rows), int(f)))

@@ -10,6 +10,7 @@ names as its next step (gcn_utills.py:804-806); ``GATConv(channels, heads=1)`` i
 ``GINConv(channels, mlp_hidden=None, eps=0.0, train_eps=False)`` is PyG's / Spektral's Graph Isomorphism Network layer for it.
 ``PNAConv(channels, deg=None, avg_deg_log=None)`` is PyG's PNAConv with the mean / min / max / std aggregators and the three degree scalers.
 ``GATv2Conv(channels, heads=1, edge_dim=None)`` is PyG's GATv2Conv: attention whose scores read the edge features (gcn.py:71).
+``ResGatedGraphConv(channels, edge_dim=None, root_weight=True)`` is PyG's gated layer: per-channel sigmoid gates that read the edge features.
 ``TopKPool(ratio)`` is Spektral's pooling layer of that name, which the
 reference's script imports (gcn.py:10), called as ``layer([x, a, seg])``.
 
@@ -796,6 +797,199 @@ class GATv2Conv(Layer):
             return None
         dx = self._buf("dx", x.shape)
         D.gemm_dx(ctx, dxlr, self.lin_weight, dx)                                   # dx = dXl W_l^T + dXr W_r^T
+        return dx
+
+
+class ResGatedGraphConv(Layer):
+    """torch_geometric.nn.ResGatedGraphConv(in, channels, act=Sigmoid(), edge_dim=D, root_weight=True, bias=True) (Bresson &
+    Laurent's GatedGCN), aggr = add -- every message multiplied channel by channel by a sigmoid gate that reads target, source
+    and the edge features, the dca / proximity values the reference computes and its model drops (gcn_utills.py:319-443;
+    gcn.py:71).  With z_ij = [x ‖ e_ij] fed to lin_key / lin_query / lin_value (each Linear(in + D, channels) with bias):
+
+        out_i = lin_skip(x_i) + bias + sum_j sigmoid(lin_key([x_i ‖ e_ij]) + lin_query([x_j ‖ e_ij])) * lin_value([x_j ‖ e_ij])
+
+    No softmax: a row's messages do not compete.  ``ResGatedGraphConv(channels, edge_dim=None, root_weight=True, use_bias=True)``,
+    called as ``layer([x, a])`` or, with edge_dim, ``layer([x, a, e])`` with ``a = ResGatedGraphConv.preprocess(a)`` and e
+    [nnz, edge_dim] in the entry order of a: the stored pattern (row = target) and e as stored, values ignored, no loop added
+    or removed; a row without entries gives lin_skip(x_i) + bias.
+
+    Parameters under PyG's names, ``_param_spec`` in its named_parameters() order and layouts: ``bias``, ``lin_key.weight``
+    [channels, in + D], ``lin_key.bias``, ``lin_query.*``, ``lin_value.*``, ``lin_skip.weight`` [channels, in] (no bias).  The
+    names and layouts follow PyG 2.3+'s source, not a live module (neither torch_geometric nor a checkpoint was available).
+    Every Linear of a concatenation is a sum of two products, so the layer STORES (``params`` / ``grads``) ``bias``; ``weight``
+    [in, 4 channels] = the node blocks W_k | W_q | W_v | W_s (3 channels wide without root_weight); ``lin_bias`` [3 channels] =
+    b_k | b_q | b_v; ``edge_weight`` [D, 3 channels] = the edge blocks W_ke | W_qe | W_ve: P = K | Q | V | S is one gcnx_gemm,
+    the layer's backward one gcnx_gemm_dw, one column sum, one gcnx_gemm_dx.  ``state_dict()`` / ``gradients()`` join them into
+    PyG's tensors (dW_ke and dW_qe are the same numbers), ``load_state_dict()`` splits them.  Initialisation as torch's Linear:
+    U(+-1 / sqrt(fan_in)) for every weight and bias (fan_in = in + D for key / query / value), ``bias`` zero.
+    ``backward(dy, need_dx=True)`` returns dx (None with need_dx=False) and leaves the gradients in ``grads``.
+
+    Launches (csrc/resgated.hip): gcnx_gemm, gcnx_resgated_aggregate forward; gcnx_act_bias_grad, gcnx_resgated_bwd_targets,
+    gcnx_resgated_bwd_sources, gcnx_gemm_dw, gcnx_act_bias_grad, gcnx_gemm_dx backward.  There is no composed route: what the
+    kernels do not serve (a gate other than the sigmoid, bipartite inputs, shapes gcnx_resgated_conv_ok refuses) raises
+    NotImplementedError."""
+
+    LINS = ("lin_key", "lin_query", "lin_value")
+
+    def __init__(self, channels, edge_dim=None, root_weight=True, use_bias=True, activation=None, act="sigmoid", **kw):
+        super().__init__(**kw)
+        if not (isinstance(act, str) and act.lower() == "sigmoid"):
+            raise NotImplementedError(f"ResGatedGraphConv act={act!r}: the gate of the kernels is the sigmoid")
+        if activation not in (None, "linear"):
+            raise NotImplementedError(f"ResGatedGraphConv activation {activation!r}: the layer is linear (follow it with BatchNorm1d / PReLU)")
+        if edge_dim is not None and not 1 <= int(edge_dim) <= 8:
+            raise NotImplementedError(f"ResGatedGraphConv edge_dim={edge_dim}: the kernels serve 1 to 8 edge features (or None)")
+        if int(channels) not in (16, 32, 64, 128):
+            raise NotImplementedError(f"ResGatedGraphConv channels={channels}: the kernels serve 16, 32, 64 and 128 (there is no composed route)")
+        self.channels, self.root_weight, self.use_bias, self.activation = int(channels), bool(root_weight), bool(use_bias), activation
+        self.edge_dim = None if edge_dim is None else int(edge_dim)
+
+    @staticmethod
+    def preprocess(a):
+        """The unweighted view of a DeviceCSR: the pattern as stored, no loop added or removed."""
+        return a.unweighted()
+
+    def _param_spec(self, in_dim):
+        """PyG's names in its named_parameters() order and its layouts ([channels, in + D] weights)."""
+        h, d, rng = self.channels, self.edge_dim or 0, self._rng
+        u = lambda fan_in, *s: rng.uniform(-1.0 / np.sqrt(fan_in), 1.0 / np.sqrt(fan_in), s).astype(np.float32)
+        spec = [("bias", (h,), np.zeros(h, np.float32))] if self.use_bias else []
+        for k in self.LINS:
+            spec += [(k + ".weight", (h, in_dim + d), u(in_dim + d, h, in_dim + d)), (k + ".bias", (h,), u(in_dim + d, h))]
+        if self.root_weight:
+            spec.append(("lin_skip.weight", (h, in_dim), u(in_dim, h, in_dim)))
+        return spec
+
+    def _width(self):
+        return (4 if self.root_weight else 3) * self.channels
+
+    def n_params(self, in_dim):
+        """Floats of storage: the named tensors and, with root_weight, the zero bias of the S block (channels floats)."""
+        return super().n_params(in_dim) + (self.channels if self.root_weight else 0)
+
+    def build(self, ctx, in_dim, p_store=None, g_store=None, offset=0):
+        """Storage order: bias, weight [in, 4 channels], lin_bias [3 channels] and the zero bias of the S block behind it (the
+        product's bias is the two together; its gradient is never written), edge_weight -- every tensor on a 16-byte boundary
+        when ``offset`` is."""
+        self.ctx = ctx
+        h, d, w = self.channels, self.edge_dim or 0, self._width()
+        total = self.n_params(in_dim)
+        if p_store is None:
+            p_store, g_store, offset = ctx.zeros(total), ctx.zeros(total), 0
+        off = offset
+
+        def take(name, shape):
+            nonlocal off
+            n = int(np.prod(shape))
+            self.params[name], self.grads[name] = p_store.flat(off, n, shape), g_store.flat(off, n, shape)
+            off += n
+
+        if self.use_bias:
+            take("bias", (h,))
+        take("weight", (in_dim, w))
+        self._gemm_bias = p_store.flat(off, w)
+        take("lin_bias", (3 * h,))
+        off += w - 3 * h
+        if d:
+            take("edge_weight", (d, 3 * h))
+        self.in_dim, self.built = in_dim, True
+        self.load_state_dict({name: init for name, _, init in self._param_spec(in_dim)})
+        return off
+
+    def load_state_dict(self, d):
+        """{PyG name: array in PyG's layout}: the [channels, in + D] tensors are split into their node and edge blocks."""
+        h, ed, f = self.channels, self.edge_dim or 0, self.in_dim
+        names = self._names()
+        missing = [n for n in names if n not in d]
+        if missing:
+            raise KeyError(f"ResGatedGraphConv.load_state_dict: missing {missing}")
+        t = {n: np.asarray(d[n], np.float32) for n in names}
+        for n in self.LINS:
+            if t[n + ".weight"].shape != (h, f + ed) or t[n + ".bias"].shape != (h,):
+                raise ValueError(f"{n}: shapes {t[n + '.weight'].shape}, {t[n + '.bias'].shape} do not fit this layer")
+        blocks = [t[n + ".weight"][:, :f].T for n in self.LINS]
+        if self.root_weight:
+            if t["lin_skip.weight"].shape != (h, f):
+                raise ValueError(f"lin_skip.weight: shape {t['lin_skip.weight'].shape} does not fit this layer")
+            blocks.append(t["lin_skip.weight"].T)
+        self.params["weight"].copy_from_host(np.concatenate(blocks, axis=1))
+        self.params["lin_bias"].copy_from_host(np.concatenate([t[n + ".bias"] for n in self.LINS]))
+        if ed:
+            self.params["edge_weight"].copy_from_host(np.concatenate([t[n + ".weight"][:, f:].T for n in self.LINS], axis=1))
+        if self.use_bias:
+            self.params["bias"].copy_from_host(t["bias"].reshape(h))
+
+    def _names(self):
+        """PyG's names in _param_spec's order (without drawing the initial values)."""
+        return (["bias"] if self.use_bias else []) + [k + t for k in self.LINS for t in (".weight", ".bias")] + \
+            (["lin_skip.weight"] if self.root_weight else [])
+
+    def _joined(self, t):
+        h, ed = self.channels, self.edge_dim or 0
+        w, b = t["weight"].numpy(), t["lin_bias"].numpy()
+        we = t["edge_weight"].numpy() if ed else np.zeros((0, 3 * h), np.float32)
+        d = {"bias": t["bias"].numpy()} if self.use_bias else {}
+        for i, n in enumerate(self.LINS):
+            d[n + ".weight"] = np.concatenate([w[:, i * h:(i + 1) * h].T, we[:, i * h:(i + 1) * h].T], axis=1)
+            d[n + ".bias"] = b[i * h:(i + 1) * h].copy()
+        if self.root_weight:
+            d["lin_skip.weight"] = w[:, 3 * h:].T.copy()
+        return d
+
+    def state_dict(self):
+        """{PyG name: array in PyG's layout}: lin_key / lin_query / lin_value .weight [channels, in + D] = [node block ‖ edge block]."""
+        return self._joined(self.params)
+
+    def gradients(self):
+        """The gradients of the last backward under the names and in the layouts of state_dict()."""
+        return self._joined(self.grads)
+
+    def call(self, inputs, out=None):
+        if len(inputs) not in (2, 3):
+            raise ValueError("ResGatedGraphConv takes [x, a] or [x, a, e]")
+        x, a = inputs[:2]
+        if isinstance(x, (tuple, list)):
+            raise NotImplementedError("ResGatedGraphConv: bipartite inputs (x_source, x_target) have no kernel")
+        e = inputs[2] if len(inputs) == 3 else None
+        h, d = self.channels, self.edge_dim
+        if e is not None and d is None:
+            raise ValueError("ResGatedGraphConv: edge features given to a layer built without edge_dim")
+        if e is None and d is not None:
+            raise ValueError(f"ResGatedGraphConv(edge_dim={d}) takes [x, a, e]")
+        if e is not None and (len(e.shape) != 2 or e.shape != (a.nnz, d)):
+            raise ValueError(f"ResGatedGraphConv(edge_dim={d}): e must be [{a.nnz}, {d}] (one row per stored entry), got {list(e.shape)}")
+        w = self._width()
+        if not D.resgated_conv_ok(x.ctx, x.shape[0], h, ldp=w, edge_dim=d or 0):
+            raise NotImplementedError(f"ResGatedGraphConv channels={h} on {x.shape[0]} rows: the kernels serve channels in "
+                                      "{16, 32, 64, 128} and rows * channels * 16 < 2^32")
+        if not self.built:
+            self.build(x.ctx, x.shape[1])
+        ctx, n, p = self.ctx, x.shape[0], self.params
+        y = out if out is not None else self._buf("y", (n, h))
+        pk = self._buf("p", (n, w))
+        D.gemm(ctx, x, p["weight"], self._gemm_bias, pk)                            # K | Q | V | S
+        D.resgated_aggregate(ctx, a, pk, y, e=e, w_e=p.get("edge_weight"), skip=pk.cols(3 * h, w) if self.root_weight else None,
+                             bias=p.get("bias"))
+        self._saved = (x, a, e, pk)
+        return y
+
+    def backward(self, dy, need_dx=True):
+        x, a, e, pk = self._saved
+        ctx, p, g, h, n, w = self.ctx, self.params, self.grads, self.channels, x.shape[0], self._width()
+        if self.use_bias:
+            D.act_bias_grad(ctx, dy, None, dy, None, db=g["bias"])                  # column sums of dy
+        dp = self._buf("dp", (n, w))
+        scratch = self._buf("scratch", (max(D.resgated_bwd_scratch_floats(ctx, n, h, self.edge_dim or 0), 1),))
+        w_e = p.get("edge_weight")
+        D.resgated_bwd_targets(ctx, a, pk, dy, dp.cols(0, h), scratch, ds=dp.cols(3 * h, w) if self.root_weight else None, e=e, w_e=w_e,
+                               dw_e=g.get("edge_weight"))
+        D.resgated_bwd_sources(ctx, a, pk, dy, dp.cols(h, 3 * h), e=e, w_e=w_e)
+        D.gemm_dw(ctx, x, dp, g["weight"])                                          # dW_k | dW_q | dW_v | dW_s = x^T dP
+        D.act_bias_grad(ctx, dp.cols(0, 3 * h), None, dp.cols(0, 3 * h), None, db=g["lin_bias"])     # db_k | db_q | db_v: column sums
+        if not need_dx:
+            return None
+        dx = self._buf("dx", x.shape)
+        D.gemm_dx(ctx, dp, p["weight"], dx)                                         # dx = dP [W_k | W_q | W_v | W_s]^T
         return dx
 
 

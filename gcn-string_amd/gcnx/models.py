@@ -27,6 +27,8 @@ entries of every row with learned scores (csrc/gat.hip).
 
 ``GATv2``: ``GCN`` with PyG's GATv2Conv(heads, concat=True, edge_dim) in the place of both GCNConv layers: attention whose scores
 read the dca / proximity edge features (csrc/gatv2.hip); trains from DeviceDataset(edge_features=True) batches.
+``ResGated``: ``GCN`` with PyG's ResGatedGraphConv(edge_dim, root_weight) in the place of both GCNConv layers: per-channel sigmoid
+gates that read target, source and edge features (csrc/resgated.hip); trains from the same batches.
 
 ``TopKNet``: GCNConv -> TopKPool -> GCNConv -> global pool -> Dense(softmax), with the pooling layer the reference's script imports
 (gcn.py:10); selection, gather and the induced adjacency on the device (csrc/topk.hip), eager launches.
@@ -2570,6 +2572,217 @@ class GATv2(GCN):
 
     def _conv1_bwd(self, a_t, batch, bufs):
         self._v2_bwd(a_t, batch.x, bufs["e"], 1, bufs["dz1"], bufs, None)            # (the input carries no gradient)
+
+
+class ResGated(GCN):
+    """``GCN`` with its two GCNConv layers replaced by PyG's ResGatedGraphConv(act=Sigmoid(), edge_dim=D, root_weight, bias=True)
+    (Bresson & Laurent's GatedGCN), aggr = add: every message is multiplied channel by channel by a sigmoid gate that reads
+    target, source and the edge features -- the dca / proximity values the reference computes on every contact and bridge and
+    its model drops (gcn_utills.py:319-443; gcn.py:71).  No softmax: a row's messages do not compete.
+
+        ResGatedGraphConv(F->H)·BN·PReLU -> ResGatedGraphConv(H->H)·BN·PReLU -> global_max_pool -> Linear(H->H)·BN·PReLU
+        -> Linear(H->1)·BN·PReLU
+
+    ``ResGated([ctx,] hidden_channels=64, edge_dim=None, root_weight=True, num_classes=1, seed=0)``; hidden_channels in {16, 32,
+    64, 128}, edge_dim None or 1 .. 8 (what csrc/resgated.hip serves; there is no composed route).  With edge_dim the model
+    reads ``batch.e`` (``uses_edge_features``): inputs are (x, a, e, i), a DeviceBatch that carries e, or the batches of
+    DeviceDisjointLoader(DeviceDataset(..., edge_features=True)), which arrive with e and the transposed pattern gathered on the
+    device.  The pattern and e are used as stored on every route -- host, device or loader: no self-loop is added or removed
+    (the reference's graphs carry every loop).  Everything behind the convolutions is ``GCN``'s: BN·PReLU, the fused max-pool
+    pair, the one-launch BCE head, ``fit``, the optimizers of gcnx.optim.  One device: ``comm`` is refused.
+
+    Hot path per convolution: gcnx_gemm (P = K | Q | V | S = x [W_k | W_q | W_v | W_s] + [b_k | b_q | b_v | 0], one launch),
+    gcnx_resgated_aggregate; backward gcnx_act_bias_grad, gcnx_resgated_bwd_targets (forward CSR), gcnx_resgated_bwd_sources
+    (transposed pattern + entry permutation), gcnx_gemm_dw, gcnx_act_bias_grad over the 3 H biased columns, gcnx_gemm_dx.
+
+    Weights: PyG's key names ``conv{1,2}.bias``, ``.lin_key.weight`` / ``.lin_query.weight`` / ``.lin_value.weight`` ([out, in + D] =
+    [node block ‖ edge block], as torch), their ``.bias``, ``.lin_skip.weight`` ([out, in], with root_weight) in ``state_dict()``;
+    stored as one stacked [in, 4 out] weight (3 out without root_weight), one stacked [3 out] bias and one [D, 3 out] edge weight
+    per convolution -- ``load_state_dict`` splits PyG's tensors, ``state_dict`` joins them, ``gradients()`` returns dW_ke and
+    dW_qe as the same numbers.  The names and the order follow PyG 2.3+'s source, not a live module (neither torch_geometric
+    nor a checkpoint was available): prefer the named dicts.  Initialisation as torch's Linear: U(+-1 / sqrt(fan_in)) for every
+    weight and bias, the conv ``bias`` zero."""
+
+    PROBE_KEY = None                      # conv1.lin_key.weight is [H, F + D]: load_state_dict subtracts D itself
+    LINS = (("lin_key", "k"), ("lin_query", "q"), ("lin_value", "v"))
+
+    def _init(self, ctx, hidden_channels=64, edge_dim=None, root_weight=True, num_classes=1, seed=0, comm=None):
+        h = int(hidden_channels)
+        if comm is not None:
+            raise NotImplementedError("gcnx.ResGated runs on one device (comm is not supported)")
+        if h not in (16, 32, 64, 128):
+            raise NotImplementedError(f"gcnx.ResGated: hidden_channels={h} must be 16, 32, 64 or 128 (the widths the ResGatedGraphConv "
+                                      "kernels serve; there is no composed route)")
+        if edge_dim is not None and not 1 <= int(edge_dim) <= 8:
+            raise NotImplementedError(f"gcnx.ResGated: edge_dim={edge_dim} must be None or 1 .. 8 (what the ResGatedGraphConv kernels serve)")
+        super()._init(ctx, h, num_classes, seed, None)
+        self.edge_dim, self.root_weight = None if edge_dim is None else int(edge_dim), bool(root_weight)
+        self.uses_edge_features = edge_dim is not None
+        self.width = (4 if self.root_weight else 3) * h
+        # lz: the zero bias of the S block, directly behind the stacked bias (the product's bias is the two together)
+        conv = lambda k: (f"b{k}", f"w{k}", f"lb{k}") + ((f"lz{k}",) if self.root_weight else ()) + ((f"we{k}",) if self.edge_dim else ())
+        self.PARAM_ORDER = conv(1) + conv(2) + ("g1", "be1", "a1", "g2", "be2", "a2") + GCN.PARAM_ORDER[10:]
+        # the views behind PyG's names: the node blocks wk / wq / wv / ws [in, H]; with edge_dim the state_dict joins the
+        # edge blocks wke / wqe / wve [D, H] to the first three
+        keys = lambda k: ((f"conv{k}.bias", f"b{k}", False),) + \
+            tuple(t for n, s in self.LINS for t in ((f"conv{k}.{n}.weight", f"w{s}{k}", True), (f"conv{k}.{n}.bias", f"b{s}{k}", False))) + \
+            (((f"conv{k}.lin_skip.weight", f"ws{k}", True),) if self.root_weight else ())
+        self.TORCH_KEYS = keys(1) + keys(2) + GCN.TORCH_KEYS[4:]
+
+    def _shapes(self, f_in):
+        s = super()._shapes(f_in)
+        h, d, w = self.hidden, self.edge_dim or 0, self.width
+        s.update(w1=(f_in, w), w2=(h, w), lb1=(3 * h,), lb2=(3 * h,), lz1=(h,), lz2=(h,), we1=(d, 3 * h), we2=(d, 3 * h))
+        return s
+
+    def build(self, f_in):
+        h, d, w = self.hidden, self.edge_dim or 0, self.width
+        shapes = self._shapes(f_in)
+        self.f_in = int(f_in)
+        # every parameter starts on a 16-byte boundary (the kernels read the bias, W_e and W as float4); the padding floats and
+        # lz have zero gradients, so the single update launch over the whole buffer leaves them at zero
+        offs = self._alloc_flat([(k, shapes[k]) for k in self.PARAM_ORDER], align=4)
+        self._gemm_bias = {}
+        for k in (1, 2):
+            assert not self.root_weight or offs[f"lz{k}"] == offs[f"lb{k}"] + 3 * h
+            self._gemm_bias[k] = self.flat_p.flat(offs[f"lb{k}"], w)
+        for t in (self.p, self.g):                      # PyG's names: the column blocks of the stacked tensors
+            for k in (1, 2):
+                for i, (_, s) in enumerate(self.LINS):
+                    t[f"w{s}{k}"], t[f"b{s}{k}"] = t[f"w{k}"].cols(i * h, (i + 1) * h), t[f"lb{k}"].flat(i * h, h)
+                    if d:
+                        t[f"w{s}e{k}"] = t[f"we{k}"].cols(i * h, (i + 1) * h)
+                if self.root_weight:
+                    t[f"ws{k}"] = t[f"w{k}"].cols(3 * h, 4 * h)
+        rng, lim = self._rng, 1.0 / np.sqrt(h)
+        u = lambda fan_in, *s: rng.uniform(-1.0 / np.sqrt(fan_in), 1.0 / np.sqrt(fan_in), s)
+        init = {"w3": rng.uniform(-lim, lim, (h, h)), "b3": rng.uniform(-lim, lim, h),
+                "w4": rng.uniform(-lim, lim, (1, h)), "b4": rng.uniform(-lim, lim, 1)}
+        for k, f in ((1, f_in), (2, h)):                # torch's Linear on [x ‖ e]: fan_in = in + D for key / query / value
+            blocks = [u(f + d, f, 3 * h)] + ([u(f, f, h)] if self.root_weight else [])
+            init[f"w{k}"], init[f"lb{k}"] = np.concatenate(blocks, axis=1), u(f + d, 3 * h)
+            if d:
+                init[f"we{k}"] = u(f + d, d, 3 * h)
+        for k in ("g1", "g2", "g3", "g4"):
+            init[k] = np.ones(shapes[k])
+        for k in ("a1", "a2", "a3", "a4"):
+            init[k] = np.full(1, 0.25)
+        for k, v in init.items():
+            self.p[k].copy_from_host(np.asarray(v, np.float32))
+        self.built = True
+
+    def _joined(self, d, t):
+        """PyG's [H, in + D] tensors: the edge block of ``t`` (self.p or self.g) joined to the node block the base class returned."""
+        if self.edge_dim:
+            for k in (1, 2):
+                for n, s in self.LINS:
+                    d[f"conv{k}.{n}.weight"] = np.concatenate([d[f"conv{k}.{n}.weight"], t[f"w{s}e{k}"].numpy().T], axis=1)
+        return d
+
+    def state_dict(self):
+        """{PyG key: array in PyG's layout}: conv*.lin_key / lin_query / lin_value .weight [H, in + D] = [node block ‖ edge block]."""
+        return self._joined(super().state_dict(), self.p)
+
+    def gradients(self):
+        return self._joined(super().gradients(), self.g)
+
+    def load_state_dict(self, d):
+        """Inverse of state_dict: the [H, in + D] tensors are split into the node blocks of the stacked weight and the edge
+        blocks of the edge weight.  Builds the model if needed."""
+        d, ed = dict(d), self.edge_dim or 0
+        if not self.built:
+            self.build(int(np.asarray(d["conv1.lin_key.weight"]).shape[1]) - ed)
+        missing = [tk for tk, _, _ in self.TORCH_KEYS if tk not in d]
+        if missing:
+            raise KeyError(f"gcnx.ResGated.load_state_dict: missing {missing}")
+        host = {}
+        for tk, k, tr in self.TORCH_KEYS:
+            v = np.asarray(d[tk], np.float32)
+            v = v.T if tr else v
+            if ed and tk.startswith("conv") and tk.endswith(".weight") and "lin_skip" not in tk:
+                if v.ndim != 2 or v.shape[0] <= ed:
+                    raise ValueError(f"{tk}: shape {np.asarray(d[tk]).shape} does not fit this model")
+                host[k[:2] + "e" + k[2:]], v = v[-ed:], v[:-ed]           # wk1 -> wke1
+            if v.shape != self.p[k].shape:
+                raise ValueError(f"{tk}: shape {np.asarray(d[tk]).shape} does not fit this model")
+            host[k] = v
+        for k in (1, 2):
+            node = [host.pop(f"w{s}{k}") for _, s in self.LINS] + ([host.pop(f"ws{k}")] if self.root_weight else [])
+            host[f"w{k}"] = np.concatenate(node, axis=1)
+            host[f"lb{k}"] = np.concatenate([host.pop(f"b{s}{k}") for _, s in self.LINS])
+            if ed:
+                host[f"we{k}"] = np.concatenate([host.pop(f"w{s}e{k}") for _, s in self.LINS], axis=1)
+        for k, v in host.items():
+            self.p[k].copy_from_host(np.ascontiguousarray(v))
+
+    def _as_batch(self, inputs, target=None):
+        if not isinstance(inputs, DeviceBatch):
+            if self.uses_edge_features and len(inputs) != 4:
+                raise ValueError(f"gcnx.ResGated(edge_dim={self.edge_dim}) takes (x, a, e, i): build the graphs with edge features "
+                                 "(Graph(e=...), from_networkx(use_edge_data='entries'))")
+        batch = self._adopt(inputs, target, weighted=False)      # the adjacency and e as stored: no loop added or removed
+        if self.uses_edge_features and batch.e is None:
+            raise ValueError("gcnx.ResGated: the batch carries no edge features (DeviceBatch.e)")
+        return batch
+
+    def _op(self, batch):
+        """The unweighted pattern of the batch, twice: the backward walks its transposed pattern through the entry permutation
+        (DeviceCSR.transpose_perm: the one a device loader's batch arrives with, or built here, once per batch object)."""
+        if self._op_cache is None or self._op_cache[0] != batch.uid:
+            a = batch.a.unweighted()
+            a.transpose_perm()
+            self._op_cache = (batch.uid, a, a)
+        return self._op_cache[1], self._op_cache[2]
+
+    def _ensure(self, batch, sharded=False):
+        bufs = super()._ensure(batch, sharded)
+        d = self.edge_dim or 0
+        if d and (batch.e is None or batch.e.shape != (batch.a.nnz, d)):
+            raise ValueError(f"gcnx.ResGated(edge_dim={d}): the batch's edge features must be [{batch.a.nnz}, {d}], got "
+                             f"{None if batch.e is None else list(batch.e.shape)}")
+        if "p1" not in bufs:
+            v, n, h, w = self._views(), batch.n, self.hidden, self.width
+            if not D.resgated_conv_ok(self.ctx, n, h, ldp=w, edge_dim=d):
+                raise NotImplementedError(f"gcnx.ResGated: a batch of {n} rows at hidden_channels={h} is beyond the ResGatedGraphConv kernels")
+            for k in ("p1", "p2", "dp"):
+                bufs[k] = v("rg_" + k, n, w)
+            ns = max(D.resgated_bwd_scratch_floats(self.ctx, n, h, d), 1)
+            bufs["scratch"] = v("rg_scratch", 1, ns).flat(0, ns)
+        return bufs
+
+    def _rg_fwd(self, a, x, e, k, bufs):
+        """z_k = ResGatedGraphConv_k(x): K | Q | V | S in one product, then gates, messages and their sum in one launch."""
+        ctx, p, h, w = self.ctx, self.p, self.hidden, self.width
+        pk = bufs[f"p{k}"]
+        D.gemm(ctx, x, p[f"w{k}"], self._gemm_bias[k], pk)
+        D.resgated_aggregate(ctx, a, pk, bufs[f"z{k}"], e=e, w_e=p.get(f"we{k}"), skip=pk.cols(3 * h, w) if self.root_weight else None,
+                             bias=p[f"b{k}"])
+
+    def _rg_bwd(self, a, x, e, k, dzk, bufs, dx):
+        """dZ_k -> the gradients of ResGatedGraphConv_k and, with dx, the gradient of its input."""
+        ctx, p, g, h, w = self.ctx, self.p, self.g, self.hidden, self.width
+        pk, dp, w_e = bufs[f"p{k}"], bufs["dp"], p.get(f"we{k}")
+        D.act_bias_grad(ctx, dzk, None, dzk, None, db=g[f"b{k}"])                    # conv_k.bias: column sums of dZ_k
+        D.resgated_bwd_targets(ctx, a, pk, dzk, dp.cols(0, h), bufs["scratch"], ds=dp.cols(3 * h, w) if self.root_weight else None,
+                               e=e, w_e=w_e, dw_e=g.get(f"we{k}"))
+        D.resgated_bwd_sources(ctx, a, pk, dzk, dp.cols(h, 3 * h), e=e, w_e=w_e)
+        D.gemm_dw(ctx, x, dp, g[f"w{k}"])                                            # dW_k | dW_q | dW_v | dW_s = x^T dP
+        D.act_bias_grad(ctx, dp.cols(0, 3 * h), None, dp.cols(0, 3 * h), None, db=g[f"lb{k}"])       # db_k | db_q | db_v
+        if dx is not None:
+            D.gemm_dx(ctx, dp, p[f"w{k}"], dx)                                       # dx = dP [W_k | W_q | W_v | W_s]^T
+
+    def _conv1(self, a, batch, bufs, mode):
+        bufs["e"] = batch.e if self.uses_edge_features else None                    # (conv2 and the backward read the same rows)
+        self._rg_fwd(a, batch.x, bufs["e"], 1, bufs)
+
+    def _conv2(self, a, bufs, mode):
+        self._rg_fwd(a, bufs["y1"], bufs["e"], 2, bufs)
+
+    def _conv2_bwd(self, a_t, bufs):
+        self._rg_bwd(a_t, bufs["y1"], bufs["e"], 2, bufs["dz2"], bufs, bufs["dy1"])
+
+    def _conv1_bwd(self, a_t, batch, bufs):
+        self._rg_bwd(a_t, batch.x, bufs["e"], 1, bufs["dz1"], bufs, None)            # (the input carries no gradient)
 
 
 class ECCNet(_GraphRunner):

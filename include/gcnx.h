@@ -988,6 +988,57 @@ GCNX_API int gcnx_gatv2_bwd_nodes(gcnx_ctx* ctx, const int32_t* rowptr_t, const 
                        int32_t edge_dim, const float* w_e, const float* att, float slope, const float* alpha,
                        const float* dscore, const float* d_out, int64_t ldd, float* dxl, int64_t ldg);
 
+/* ---- ResGatedGraphConv: per-channel sigmoid edge gates, small-feature regime (h <= 128) --------------------------------
+ * PyG's ResGatedGraphConv(in, h, act=Sigmoid(), edge_dim, root_weight, bias) (Bresson & Laurent's GatedGCN), aggr = add: each
+ * message is multiplied channel by channel by a gate that reads target, source and edge together -- the gated, per-channel
+ * way to use the dca / proximity features the reference computes and its model drops (gcn_utills.py:319-443; gcn.py:71).
+ * No softmax: a row's messages do not compete.  CSR row i is the target, its stored entries j the sources, values are
+ * ignored, no self-loops are added, the pattern and e are used as stored.  p = K | Q | V [n, >= 3 h] (ldp) is ONE array from one
+ * gcnx_gemm with the stacked weight and bias (x [W_k | W_q | W_v | W_s] + [b_k | b_q | b_v | 0]: the node halves of PyG's
+ * lin_key / lin_query / lin_value, and lin_skip behind them); e [nnz, edge_dim] (lde) holds the entries' features in the
+ * CSR's entry order, w_e [edge_dim, 3 h] = W_ke | W_qe | W_ve the edge halves of the three Linears:
+ *     a_ij = K[i] + Q[j] + sum_d e_ij[d] (W_ke[d] + W_qe[d])    g_ij = sigmoid(a_ij)    m_ij = V[j] + sum_d e_ij[d] W_ve[d]
+ *     out[i] = S[i] + bias + sum_j g_ij * m_ij                  (a row without entries: out = S[i] + bias)
+ * and with dO = dLoss/dout:
+ *     da_ij = dO[i] * m_ij * g_ij (1 - g_ij)        dm_ij = dO[i] * g_ij
+ *     dK[i] = sum_j da_ij      dS = dO      dbias = column sums of dO
+ *     dQ[j] = sum_i da_ij      dV[j] = sum_i dm_ij                          (over the transposed pattern)
+ *     dW_ke[d] = dW_qe[d] = sum_ij e_ij[d] da_ij      dW_ve[d] = sum_ij e_ij[d] dm_ij
+ * g and m are stored nowhere: the backward recomputes them.  sigmoid(a) = 1 / (1 + exp(-a)) with the overflow to inf
+ * resolving to 0: every finite a gives a finite g in [0, 1] and a finite g (1 - g), no 0 * inf, no NaN.
+ * fp32, no float atomics, fixed summation order: the same bits on every call.  Nothing is allocated.
+ * gcnx_resgated_conv_ok (gcn.py:71): 1 if the shapes are served: h in {16, 32, 64, 128}, 0 <= edge_dim <= 8, ldp % 4 == 0,
+ * ldp >= 3 h, n * ldp * 4 < 2^32.  Every call below returns GCNX_ERR_UNSUPPORTED otherwise, and for float4 operands
+ * (everything but e and the index arrays) off a 16-byte boundary or leading dimensions that are not multiples of 4 floats
+ * >= their width, with nothing launched and nothing written.  n == 0 succeeds and writes nothing; negative sizes and NULL
+ * mandatory pointers are GCNX_ERR_INVALID; e, w_e (and dw_e, scratch) may be NULL only with edge_dim == 0. */
+GCNX_API int gcnx_resgated_conv_ok(int64_t n, int32_t h, int64_t ldp, int32_t edge_dim);
+/* gcn.py:71 -- out [n, h] (ldo) from ONE gather of the contiguous Q[j] | V[j] per entry, summed in CSR order.  skip (lds; may be
+ * NULL: root_weight=False) is S, typically p + 3 h; bias [h] may be NULL.  Nothing is saved for the backward. */
+GCNX_API int gcnx_resgated_aggregate(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, const float* p, int64_t ldp,
+                       int32_t n, int32_t h, const float* e, int64_t lde, int32_t edge_dim, const float* w_e,
+                       const float* skip, int64_t lds, const float* bias, float* out, int64_t ldo);
+/* gcn.py:71 -- *out = floats of caller scratch gcnx_resgated_bwd_targets needs (per-workgroup parts of dw_e; 0 with
+ * edge_dim == 0).  Answers without a context; h <= 0, n < 0, edge_dim < 0 and out == NULL are GCNX_ERR_INVALID. */
+GCNX_API int gcnx_resgated_bwd_scratch_floats(int64_t n, int32_t h, int32_t edge_dim, int64_t* out);
+/* gcn.py:71 -- backward, the pass over the forward CSR.  d_out = dLoss/dout [n, h] (ldd).  Writes dk [n, h] (ldg) = dK; with ds
+ * non-NULL copies d_out into ds [n, h] (ldgs) = dS, so that ONE gcnx_gemm_dw / gcnx_gemm_dx serves a dK | dQ | dV | dS array;
+ * dw_e [edge_dim, 3 h] = dW_ke | dW_qe | dW_ve with its first two blocks equal.  The dw_e sums go through per-workgroup
+ * parts in scratch (row-then-entry order inside a workgroup) and a second small launch inside this call (fixed order, no
+ * atomics). */
+GCNX_API int gcnx_resgated_bwd_targets(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, const float* p, int64_t ldp,
+                       int32_t n, int32_t h, const float* e, int64_t lde, int32_t edge_dim, const float* w_e,
+                       const float* d_out, int64_t ldd, float* dk, int64_t ldg, float* ds, int64_t ldgs, float* dw_e,
+                       float* scratch);
+/* gcn.py:71 -- backward, the pass over the transposed pattern (rowptr_t, colidx_t, perm_t of gcnx_csr_transpose_perm:
+ * perm_t[p] = the forward entry behind entry p; needed for a symmetric pattern too).  e is read in the forward entry order
+ * through perm_t; for source j and each of its targets i the kernel gathers K[i] and d_out[i] (n * ldd * 4 < 2^32).  Writes
+ * dqv [n, 2 h] (ldg) = dQ | dV, e.g. columns [h, 3 h) of dK | dQ | dV | dS.  dW, db and dx of the layer are gcnx_gemm_dw,
+ * gcnx_act_bias_grad (over the 3 h biased columns) and gcnx_gemm_dx on that array. */
+GCNX_API int gcnx_resgated_bwd_sources(gcnx_ctx* ctx, const int32_t* rowptr_t, const int32_t* colidx_t, const int32_t* perm_t,
+                       const float* p, int64_t ldp, int32_t n, int32_t h, const float* e, int64_t lde, int32_t edge_dim,
+                       const float* w_e, const float* d_out, int64_t ldd, float* dqv, int64_t ldg);
+
 /* ---- TopKPool: per-graph top-k selection, gated gather, induced sub-CSR ------------------------------------------
  * spektral.layers.pooling.TopKPool, the one layer the reference's training script imports (gcn.py:10) that had no kernels
  * here, in disjoint mode: y = X p / ||p||, the k_g rows of every graph with the largest y are kept, X' = (X * gate(y))[idx],
