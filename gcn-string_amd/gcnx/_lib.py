@@ -186,6 +186,14 @@ SIGNATURES = {
     "gcnx_resgated_bwd_scratch_floats": [_i64, _i32, _i32, C.POINTER(_i64)],
     "gcnx_resgated_bwd_targets": [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp],
     "gcnx_resgated_bwd_sources": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _i32, _vp, _vp, _i64, _vp, _i64],
+    "gcnx_transformer_conv_ok": [_i64, _i32, _i32, _i64, _i32],
+    "gcnx_transformer_aggregate": [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp,
+                                   _i64],
+    "gcnx_transformer_bwd_scratch_floats": [_i64, _i32, _i32, _i32, _i32, C.POINTER(_i64)],
+    "gcnx_transformer_beta_bwd": [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _vp],
+    "gcnx_transformer_bwd_targets": [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp,
+                                     _vp, _i64, _vp, _i64, _vp, _vp],
+    "gcnx_transformer_bwd_sources": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _i64],
     "gcnx_topk_select_ok": [_i64, _i32],
     "gcnx_topk_select": [_vp, _vp, _vp, _i32, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _vp],
     "gcnx_topk_gather": [_vp, _vp, _i64, _vp, _vp, _i32, _i32, _int, _vp, _i64],

@@ -1046,6 +1046,85 @@ def resgated_bwd_sources(ctx, a, p, dout, dqv, e=None, w_e=None):
     return dqv
 
 
+def transformer_conv_ok(ctx, n, heads, c, ldp=None, edge_dim=0):
+    """True if the TransformerConv kernels serve these shapes (gcnx_transformer_conv_ok); ldp: the leading dimension of Q | K | V."""
+    return bool(ctx.lib.gcnx_transformer_conv_ok(int(n), int(heads), int(c), int(ldp if ldp is not None else 3 * heads * c), int(edge_dim)))
+
+
+def transformer_bwd_scratch_floats(ctx, n, heads, c, edge_dim=0, beta=False):
+    """Floats of scratch transformer_bwd_targets and transformer_beta_bwd need (gcnx_transformer_bwd_scratch_floats)."""
+    out = C.c_int64()
+    ctx._ck(ctx.lib.gcnx_transformer_bwd_scratch_floats(int(n), int(heads), int(c), int(edge_dim), int(bool(beta)), C.byref(out)))
+    return int(out.value)
+
+
+def _transformer_edge(a, e, w_e, hc):
+    """(e pointer, lde, edge_dim, w_e pointer) of the optional edge operands: e [nnz, D] (any ld), w_e [D, heads * c]."""
+    if e is None:
+        assert w_e is None
+        return None, 0, 0, None
+    d = e.shape[1]
+    assert e.shape[0] == a.nnz and w_e is not None and w_e.shape == (d, hc) and w_e.contiguous
+    return _p(e), e.ld, d, _p(w_e)
+
+
+def transformer_aggregate(ctx, a, p, out, heads, e=None, w_e=None, skip=None, w_beta=None, alpha=None, o_pre=None):
+    """out = O (+ skip, or the beta-gated mix of skip and O with w_beta [3 heads c]); O = softmax-weighted sum of V[j] + e_ij w_e
+    over the stored entries of ``a`` (row = target), the scores <Q[i], K[j] + e_ij w_e> / sqrt(c) per head
+    (gcnx_transformer_aggregate).  p = Q | K | V in its first 3 heads c columns; alpha [nnz, heads] and o_pre = O are stored if
+    given."""
+    n, hc = out.shape
+    c = hc // heads
+    assert a.n == n and heads * c == hc and p.shape[0] == n and p.shape[1] >= 3 * hc
+    assert (skip is None or skip.shape == (n, hc)) and (w_beta is None or (w_beta.shape == (3 * hc,) and w_beta.contiguous))
+    assert (alpha is None or (alpha.shape == (a.nnz, heads) and alpha.contiguous)) and (o_pre is None or o_pre.shape == (n, hc))
+    ep, lde, d, wp = _transformer_edge(a, e, w_e, hc)
+    ctx._ck(ctx.lib.gcnx_transformer_aggregate(ctx.h, a.rowptr.ptr, a.colidx.ptr, _p(p), p.ld, n, heads, c, ep, lde, d, wp, _p(skip),
+                                               skip.ld if skip is not None else 0, _p(w_beta), _p(out), out.ld, _p(alpha), _p(o_pre),
+                                               o_pre.ld if o_pre is not None else 0))
+    return out
+
+
+def transformer_beta_bwd(ctx, dout, o, skip, w_beta, d_o, d_s, dw_beta, scratch):
+    """d_o = dO, d_s = dS [n, hc] and dw_beta [3 hc] of the beta gate from dout, O = o and S = skip (gcnx_transformer_beta_bwd).
+    scratch: transformer_bwd_scratch_floats(beta=True) floats."""
+    n, hc = dout.shape
+    assert o.shape == skip.shape == d_o.shape == d_s.shape == (n, hc) and w_beta.shape == dw_beta.shape == (3 * hc,)
+    assert w_beta.contiguous and dw_beta.contiguous
+    ctx._ck(ctx.lib.gcnx_transformer_beta_bwd(ctx.h, _p(dout), dout.ld, _p(o), o.ld, _p(skip), skip.ld, _p(w_beta), n, hc, _p(d_o),
+                                              d_o.ld, _p(d_s), d_s.ld, _p(dw_beta), _p(scratch)))
+    return d_o, d_s
+
+
+def transformer_bwd_targets(ctx, a, p, alpha, d_o, o, dscore, dq, heads, scratch=None, ds=None, e=None, w_e=None, dw_e=None):
+    """dscore [nnz, heads] (the CSR's entry order), dq [n, heads c] = dQ, ds (if given) = d_o and dw_e [D, heads c] on the forward
+    pattern of ``a`` (gcnx_transformer_bwd_targets).  scratch: transformer_bwd_scratch_floats floats (None with no edge features)."""
+    n, hc = d_o.shape
+    c = hc // heads
+    assert a.n == n and heads * c == hc and p.shape[0] == n and p.shape[1] >= 3 * hc and o.shape == dq.shape == (n, hc)
+    assert (ds is None or ds.shape == (n, hc)) and alpha.shape == dscore.shape == (a.nnz, heads) and alpha.contiguous and dscore.contiguous
+    ep, lde, d, wp = _transformer_edge(a, e, w_e, hc)
+    assert (dw_e is None) == (d == 0) and (dw_e is None or (dw_e.shape == (d, hc) and dw_e.contiguous))
+    assert d == 0 or scratch.size >= transformer_bwd_scratch_floats(ctx, n, heads, c, d)
+    ctx._ck(ctx.lib.gcnx_transformer_bwd_targets(ctx.h, a.rowptr.ptr, a.colidx.ptr, _p(p), p.ld, n, heads, c, ep, lde, d, wp, _p(alpha),
+                                                 _p(d_o), d_o.ld, _p(o), o.ld, _p(dscore), _p(dq), dq.ld, _p(ds),
+                                                 ds.ld if ds is not None else 0, _p(dw_e), _p(scratch)))
+    return dscore, dq
+
+
+def transformer_bwd_sources(ctx, a, p, alpha, dscore, d_o, dkv, heads):
+    """dkv [n, 2 heads c] = dK | dV on the transposed pattern of ``a`` with its entry permutation (a.transpose_perm();
+    gcnx_transformer_bwd_sources)."""
+    n, hc = d_o.shape
+    c = hc // heads
+    assert a.n == n and heads * c == hc and p.shape[0] == n and p.shape[1] >= 3 * hc and dkv.shape == (n, 2 * hc)
+    assert alpha.shape == dscore.shape == (a.nnz, heads) and alpha.contiguous and dscore.contiguous
+    rp, ci, pm = a.transpose_perm()
+    ctx._ck(ctx.lib.gcnx_transformer_bwd_sources(ctx.h, rp.ptr, ci.ptr, pm.ptr, _p(p), p.ld, n, heads, c, _p(alpha), _p(dscore), _p(d_o),
+                                                 d_o.ld, _p(dkv), dkv.ld))
+    return dkv
+
+
 def topk_select_ok(ctx, max_graph_rows, f):
     """True if topk_select serves a batch whose largest graph has this many rows (gcnx_topk_select_ok)."""
     return bool(ctx.lib.gcnx_topk_select_ok(int(max_graph_rows), int(f)))

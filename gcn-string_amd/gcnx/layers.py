@@ -11,6 +11,7 @@ names as its next step (gcn_utills.py:804-806); ``GATConv(channels, heads=1)`` i
 ``PNAConv(channels, deg=None, avg_deg_log=None)`` is PyG's PNAConv with the mean / min / max / std aggregators and the three degree scalers.
 ``GATv2Conv(channels, heads=1, edge_dim=None)`` is PyG's GATv2Conv: attention whose scores read the edge features (gcn.py:71).
 ``ResGatedGraphConv(channels, edge_dim=None, root_weight=True)`` is PyG's gated layer: per-channel sigmoid gates that read the edge features.
+``TransformerConv(channels, heads=1, beta=False, edge_dim=None, root_weight=True)`` is PyG's dot-product attention with edge features in keys and values.
 ``TopKPool(ratio)`` is Spektral's pooling layer of that name, which the
 reference's script imports (gcn.py:10), called as ``layer([x, a, seg])``.
 
@@ -990,6 +991,226 @@ class ResGatedGraphConv(Layer):
             return None
         dx = self._buf("dx", x.shape)
         D.gemm_dx(ctx, dp, p["weight"], dx)                                         # dx = dP [W_k | W_q | W_v | W_s]^T
+        return dx
+
+
+class TransformerConv(Layer):
+    """torch_geometric.nn.TransformerConv(in, channels, heads=H, concat=True, beta, dropout=0, edge_dim=D, bias, root_weight)
+    (Shi et al., UniMP) -- scaled dot-product attention whose keys and values carry the edge features, the dca / proximity
+    values the reference computes and its model drops (gcn_utills.py:319-443; gcn.py:71).  Per head h, with C = channels:
+
+        t_ij = lin_edge(e_ij)        k_ij = lin_key(x_j) + t_ij        v_ij = lin_value(x_j) + t_ij
+        alpha_ij = softmax_j(<lin_query(x_i), k_ij> / sqrt(C))         O_i = sum_j alpha_ij v_ij
+        out_i = O_i + lin_skip(x_i)                                    (root_weight; beta=False)
+        out_i = b_i lin_skip(x_i) + (1 - b_i) O_i,  b_i = sigmoid(lin_beta([O_i ‖ S_i ‖ O_i - S_i]))       (beta=True)
+
+    ``TransformerConv(channels, heads=1, concat=True, beta=False, dropout=0.0, edge_dim=None, use_bias=True, root_weight=True)``,
+    called as ``layer([x, a])`` or, with edge_dim, ``layer([x, a, e])`` with ``a = TransformerConv.preprocess(a)`` and e
+    [nnz, edge_dim] in the entry order of a: the stored pattern (row = target) and e as stored, values ignored, no loop added
+    or removed (TransformerConv has no add_self_loops); a row without entries has O = 0.
+
+    Parameters under PyG's names in its named_parameters() order: ``lin_key.weight`` / ``.bias``, ``lin_query.*``,
+    ``lin_value.*``, ``lin_edge.weight`` (no bias), ``lin_skip.*``, ``lin_beta.weight`` (no bias).  ``use_bias=False`` drops all
+    four biases, as PyG >= 2.5's ``bias=False`` does (older releases kept lin_skip's).  The names and layouts follow PyG's
+    source, not a live module (torch_geometric was not available).  STORED are ONE stacked weight [in, 4 heads channels] =
+    W_q | W_k | W_v | W_s (3 blocks without root_weight) and ONE stacked bias; ``params`` / ``grads`` hold per-name views
+    ([in, heads channels] weights, lin_edge.weight [D, heads channels], lin_beta.weight [3 heads channels]).  ``state_dict()`` /
+    ``gradients()`` give PyG's layouts ([out, in]; lin_beta.weight [1, 3 heads channels]), ``load_state_dict()`` takes them.
+    Initialisation as torch's Linear: U(+-1 / sqrt(fan_in)) for every weight and bias.
+    ``backward(dy, need_dx=True)`` returns dx (None with need_dx=False) and leaves the gradients in ``grads``.
+
+    Launches (csrc/transformer.hip): gcnx_gemm, gcnx_transformer_aggregate forward; gcnx_transformer_beta_bwd (beta only),
+    gcnx_transformer_bwd_targets, gcnx_transformer_bwd_sources, gcnx_gemm_dw, gcnx_act_bias_grad, gcnx_gemm_dx backward.  There
+    is no composed route: what the kernels do not serve (concat=False, attention dropout, bipartite inputs, beta without
+    root_weight, shapes gcnx_transformer_conv_ok refuses) raises NotImplementedError."""
+
+    BLOCKS = ("lin_query", "lin_key", "lin_value", "lin_skip")         # the stacked tensors' column blocks, in storage order
+
+    def __init__(self, channels, heads=1, concat=True, beta=False, dropout=0.0, edge_dim=None, use_bias=True, root_weight=True,
+                 activation=None, **kw):
+        super().__init__(**kw)
+        if not concat:
+            raise NotImplementedError("TransformerConv concat=False (the mean over heads) has no kernel: only concat=True")
+        if dropout:
+            raise NotImplementedError(f"TransformerConv dropout={dropout}: attention dropout has no kernel (only dropout=0)")
+        if beta and not root_weight:
+            raise NotImplementedError("TransformerConv beta=True gates the root connection: it needs root_weight=True")
+        if activation not in (None, "linear"):
+            raise NotImplementedError(f"TransformerConv activation {activation!r}: the layer is linear (follow it with BatchNorm1d / PReLU)")
+        if edge_dim is not None and not 1 <= int(edge_dim) <= 8:
+            raise NotImplementedError(f"TransformerConv edge_dim={edge_dim}: the kernels serve 1 to 8 edge features (or None)")
+        h, c = int(heads), int(channels)
+        if h not in (1, 2, 4, 8) or h * c not in (16, 32, 64, 128) or c < 4:
+            raise NotImplementedError(f"TransformerConv heads={heads} channels={channels}: the kernels serve heads in {{1, 2, 4, 8}}, "
+                                      "heads * channels in {16, 32, 64, 128} and channels >= 4 (there is no composed route)")
+        self.channels, self.heads, self.beta, self.root_weight = c, h, bool(beta), bool(root_weight)
+        self.concat, self.use_bias, self.activation = True, bool(use_bias), activation
+        self.edge_dim = None if edge_dim is None else int(edge_dim)
+
+    @staticmethod
+    def preprocess(a):
+        """The unweighted view of a DeviceCSR: the pattern as stored, no loop added or removed."""
+        return a.unweighted()
+
+    def _blocks(self):
+        return self.BLOCKS if self.root_weight else self.BLOCKS[:3]
+
+    def _names(self):
+        """PyG's names in its named_parameters() order."""
+        lin = lambda k: [k + ".weight"] + ([k + ".bias"] if self.use_bias else [])
+        return lin("lin_key") + lin("lin_query") + lin("lin_value") + (["lin_edge.weight"] if self.edge_dim else []) + \
+            (lin("lin_skip") if self.root_weight else []) + (["lin_beta.weight"] if self.beta else [])
+
+    def _param_spec(self, in_dim):
+        """PyG's names in its named_parameters() order, with the stored shapes ([in, heads * channels] weights)."""
+        hc, d, rng = self.heads * self.channels, self.edge_dim or 0, self._rng
+        u = lambda fan_in, *s: rng.uniform(-1.0 / np.sqrt(fan_in), 1.0 / np.sqrt(fan_in), s).astype(np.float32)
+        shapes = {"lin_edge.weight": ((d, hc), d), "lin_beta.weight": ((3 * hc,), 3 * hc)}
+        spec = []
+        for name in self._names():
+            shape, fan_in = shapes.get(name, ((in_dim, hc) if name.endswith(".weight") else (hc,), in_dim))
+            spec.append((name, shape, u(fan_in, *shape)))
+        return spec
+
+    def _width(self):
+        return len(self._blocks()) * self.heads * self.channels
+
+    def build(self, ctx, in_dim, p_store=None, g_store=None, offset=0):
+        """Storage order: the stacked weight [in, 4 heads channels], the stacked bias, lin_edge.weight, lin_beta.weight -- every
+        tensor on a 16-byte boundary when ``offset`` is."""
+        self.ctx = ctx
+        hc, w = self.heads * self.channels, self._width()
+        spec = {name: (shape, init) for name, shape, init in self._param_spec(in_dim)}
+        total = sum(int(np.prod(s)) for s, _ in spec.values())
+        if p_store is None:
+            p_store, g_store, offset = ctx.zeros(total), ctx.zeros(total), 0
+        off = offset
+
+        def take(shape, init):
+            nonlocal off
+            n = int(np.prod(shape))
+            pv, gv = p_store.flat(off, n, shape), g_store.flat(off, n, shape)
+            pv.copy_from_host(init)
+            off += n
+            return pv, gv
+
+        blocks = self._blocks()
+        self.lin_weight, self.lin_weight_grad = take((in_dim, w), np.concatenate([spec[k + ".weight"][1] for k in blocks], axis=1))
+        self.lin_bias = self.lin_bias_grad = None
+        if self.use_bias:
+            self.lin_bias, self.lin_bias_grad = take((w,), np.concatenate([spec[k + ".bias"][1] for k in blocks]))
+        views = [{}, {}]
+        for t, wt, b in ((views[0], self.lin_weight, self.lin_bias), (views[1], self.lin_weight_grad, self.lin_bias_grad)):
+            for i, k in enumerate(blocks):
+                t[k + ".weight"] = wt.cols(i * hc, (i + 1) * hc)
+                if b is not None:
+                    t[k + ".bias"] = b.flat(i * hc, hc)
+        for k in ("lin_edge.weight", "lin_beta.weight"):
+            if k in spec:
+                views[0][k], views[1][k] = take(*spec[k])
+        for name in self._names():                                                  # PyG's order
+            self.params[name], self.grads[name] = views[0][name], views[1][name]
+        self.in_dim, self.built = in_dim, True
+        return off
+
+    def set_weights(self, weights):
+        """Arrays in the order and the stored layouts of ``params`` (weights [in, heads channels])."""
+        self._load({k: np.asarray(v, np.float32) for k, v in zip(self.params, weights)})
+
+    def _load(self, t):
+        blocks = self._blocks()
+        for k, v in t.items():
+            if v.shape != self.params[k].shape:
+                raise ValueError(f"{k}: shape {v.shape} does not fit this layer ({self.params[k].shape})")
+        self.lin_weight.copy_from_host(np.concatenate([t[k + ".weight"] for k in blocks], axis=1))
+        if self.use_bias:
+            self.lin_bias.copy_from_host(np.concatenate([t[k + ".bias"] for k in blocks]))
+        for k in ("lin_edge.weight", "lin_beta.weight"):
+            if k in self.params:
+                self.params[k].copy_from_host(t[k])
+
+    def load_state_dict(self, d):
+        """{PyG name: array in PyG's layout ([out, in] weights, lin_beta.weight [1, 3 heads channels])}."""
+        missing = [n for n in self._names() if n not in d]
+        if missing:
+            raise KeyError(f"TransformerConv.load_state_dict: missing {missing}")
+        t = {n: np.asarray(d[n], np.float32) for n in self._names()}
+        for n in t:
+            if n == "lin_beta.weight":
+                t[n] = t[n].reshape(-1)
+            elif n.endswith(".weight"):
+                t[n] = np.ascontiguousarray(t[n].T)
+        self._load(t)
+
+    @staticmethod
+    def _pyg(t):
+        d = {k: v.numpy() for k, v in t.items()}
+        for k in d:
+            if k == "lin_beta.weight":
+                d[k] = d[k][None].copy()
+            elif k.endswith(".weight"):
+                d[k] = d[k].T.copy()
+        return d
+
+    def state_dict(self):
+        """{PyG name: array in PyG's layout}: weights [heads * channels, in], lin_edge.weight [heads * channels, D],
+        lin_beta.weight [1, 3 heads * channels]."""
+        return self._pyg(self.params)
+
+    def gradients(self):
+        """The gradients of the last backward under the names and in the layouts of state_dict()."""
+        return self._pyg(self.grads)
+
+    def call(self, inputs, out=None):
+        if len(inputs) not in (2, 3):
+            raise ValueError("TransformerConv takes [x, a] or [x, a, e]")
+        x, a = inputs[:2]
+        if isinstance(x, (tuple, list)):
+            raise NotImplementedError("TransformerConv: bipartite inputs (x_source, x_target) have no kernel")
+        e = inputs[2] if len(inputs) == 3 else None
+        h, c, d = self.heads, self.channels, self.edge_dim
+        if e is not None and d is None:
+            raise ValueError("TransformerConv: edge features given to a layer built without edge_dim")
+        if e is None and d is not None:
+            raise ValueError(f"TransformerConv(edge_dim={d}) takes [x, a, e]")
+        if e is not None and (len(e.shape) != 2 or e.shape != (a.nnz, d)):
+            raise ValueError(f"TransformerConv(edge_dim={d}): e must be [{a.nnz}, {d}] (one row per stored entry), got {list(e.shape)}")
+        hc, w = h * c, self._width()
+        if not D.transformer_conv_ok(x.ctx, x.shape[0], h, c, ldp=w, edge_dim=d or 0):
+            raise NotImplementedError(f"TransformerConv heads={h} channels={c} on {x.shape[0]} rows: the kernels serve heads in "
+                                      "{1, 2, 4, 8}, heads * channels in {16, 32, 64, 128}, channels >= 4 and rows * heads * channels * 16 < 2^32")
+        if not self.built:
+            self.build(x.ctx, x.shape[1])
+        ctx, n, p = self.ctx, x.shape[0], self.params
+        y = out if out is not None else self._buf("y", (n, hc))
+        pk, o, alpha = self._buf("p", (n, w)), self._buf("o", (n, hc)), self._buf("alpha", (a.nnz, h))
+        D.gemm(ctx, x, self.lin_weight, self.lin_bias, pk)                          # Q | K | V | S
+        D.transformer_aggregate(ctx, a, pk, y, h, e=e, w_e=p.get("lin_edge.weight"), skip=pk.cols(3 * hc, w) if self.root_weight else None,
+                                w_beta=p.get("lin_beta.weight"), alpha=alpha, o_pre=o)
+        self._saved = (x, a, e, pk, alpha, o)
+        return y
+
+    def backward(self, dy, need_dx=True):
+        x, a, e, pk, alpha, o = self._saved
+        ctx, p, g, h, c, n = self.ctx, self.params, self.grads, self.heads, self.channels, x.shape[0]
+        hc, w, ed = h * c, self._width(), self.edge_dim or 0
+        dp, dscore = self._buf("dp", (n, w)), self._buf("dscore", (a.nnz, h))       # dQ | dK | dV | dS
+        scratch = self._buf("scratch", (max(D.transformer_bwd_scratch_floats(ctx, n, h, c, ed, self.beta), 1),))
+        d_o, ds = dy, (dp.cols(3 * hc, w) if self.root_weight else None)
+        if self.beta:
+            d_o = self._buf("d_o", (n, hc))
+            D.transformer_beta_bwd(ctx, dy, o, pk.cols(3 * hc, w), p["lin_beta.weight"], d_o, ds, g["lin_beta.weight"], scratch)
+            ds = None
+        D.transformer_bwd_targets(ctx, a, pk, alpha, d_o, o, dscore, dp.cols(0, hc), h, scratch, ds=ds, e=e, w_e=p.get("lin_edge.weight"),
+                                  dw_e=g.get("lin_edge.weight"))
+        D.transformer_bwd_sources(ctx, a, pk, alpha, dscore, d_o, dp.cols(hc, 3 * hc), h)
+        D.gemm_dw(ctx, x, dp, self.lin_weight_grad)                                 # dW_q | dW_k | dW_v | dW_s = x^T dP
+        if self.use_bias:
+            D.act_bias_grad(ctx, dp, None, dp, None, db=self.lin_bias_grad)         # the four biases: column sums
+        if not need_dx:
+            return None
+        dx = self._buf("dx", x.shape)
+        D.gemm_dx(ctx, dp, self.lin_weight, dx)                                     # dx = dP [W_q | W_k | W_v | W_s]^T
         return dx
 
 

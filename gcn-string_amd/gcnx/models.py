@@ -29,6 +29,8 @@ entries of every row with learned scores (csrc/gat.hip).
 read the dca / proximity edge features (csrc/gatv2.hip); trains from DeviceDataset(edge_features=True) batches.
 ``ResGated``: ``GCN`` with PyG's ResGatedGraphConv(edge_dim, root_weight) in the place of both GCNConv layers: per-channel sigmoid
 gates that read target, source and edge features (csrc/resgated.hip); trains from the same batches.
+``Transformer``: ``GCN`` with PyG's TransformerConv(heads, beta, edge_dim, root_weight) in the place of both GCNConv layers: scaled
+dot-product attention whose keys and values carry the edge features (csrc/transformer.hip); trains from the same batches.
 
 ``TopKNet``: GCNConv -> TopKPool -> GCNConv -> global pool -> Dense(softmax), with the pooling layer the reference's script imports
 (gcn.py:10); selection, gather and the induced adjacency on the device (csrc/topk.hip), eager launches.
@@ -2783,6 +2785,218 @@ class ResGated(GCN):
 
     def _conv1_bwd(self, a_t, batch, bufs):
         self._rg_bwd(a_t, batch.x, bufs["e"], 1, bufs["dz1"], bufs, None)            # (the input carries no gradient)
+
+
+class Transformer(GCN):
+    """``GCN`` with its two GCNConv layers replaced by PyG's TransformerConv(heads=H, concat=True, beta, dropout=0, edge_dim=D,
+    bias=True, root_weight) (Shi et al., UniMP): scaled dot-product attention whose keys and values carry the edge features --
+    the dca / proximity values the reference computes on every contact and bridge and its model drops (gcn_utills.py:319-443;
+    gcn.py:71):
+
+        TransformerConv(F->H/heads, heads)·BN·PReLU -> TransformerConv(H->H/heads, heads)·BN·PReLU -> global_max_pool
+        -> Linear(H->H)·BN·PReLU -> Linear(H->1)·BN·PReLU
+
+    ``Transformer([ctx,] hidden_channels=64, heads=1, edge_dim=None, beta=False, root_weight=True, num_classes=1, seed=0)``;
+    hidden_channels in {16, 32, 64, 128}, a multiple of heads in {1, 2, 4, 8} with at least 4 channels per head, edge_dim None
+    or 1 .. 8 (what csrc/transformer.hip serves; there is no composed route); beta needs root_weight.  With edge_dim the model
+    reads ``batch.e`` (``uses_edge_features``): inputs are (x, a, e, i), a DeviceBatch that carries e, or the batches of
+    DeviceDisjointLoader(DeviceDataset(..., edge_features=True)), which arrive with e and the transposed pattern gathered on the
+    device.  The pattern and e are used as stored on every route -- host, device or loader: no self-loop is added or removed
+    (TransformerConv has no add_self_loops; the reference's graphs carry every loop).  Everything behind the convolutions is
+    ``GCN``'s: BN·PReLU, the fused max-pool pair, the one-launch BCE head, ``fit``, the optimizers of gcnx.optim.  One device:
+    ``comm`` is refused.
+
+    Hot path per convolution: gcnx_gemm (P = Q | K | V | S = x [W_q | W_k | W_v | W_s] + [b_q | b_k | b_v | b_s], one launch),
+    gcnx_transformer_aggregate; backward gcnx_transformer_beta_bwd (beta only), gcnx_transformer_bwd_targets (forward CSR),
+    gcnx_transformer_bwd_sources (transposed pattern + entry permutation), gcnx_gemm_dw, gcnx_act_bias_grad, gcnx_gemm_dx.
+
+    Weights: PyG's key names ``conv{1,2}.lin_key.weight`` / ``.bias``, ``.lin_query.*``, ``.lin_value.*``, ``.lin_edge.weight``
+    ([out, edge_dim]; with edge_dim), ``.lin_skip.*`` (with root_weight), ``.lin_beta.weight`` ([1, 3 out]; with beta) in
+    ``state_dict()``, weights [out, in] as torch; stored as one stacked [in, 4 out] weight (3 out without root_weight) and one
+    stacked bias per convolution, the named tensors are views.  The gradient of lin_key.bias is analytically zero (a common
+    shift of all keys cancels in the softmax).  The order follows PyG 2.x's source, not a live module: prefer the named dicts.
+    Initialisation as torch's Linear: U(+-1 / sqrt(fan_in)) for every weight and bias."""
+
+    PROBE_KEY = "conv1.lin_key.weight"
+    BLOCKS = (("lin_query", "q"), ("lin_key", "k"), ("lin_value", "v"), ("lin_skip", "s"))       # storage order of the column blocks
+
+    def _init(self, ctx, hidden_channels=64, heads=1, edge_dim=None, beta=False, root_weight=True, num_classes=1, seed=0, comm=None):
+        h, heads = int(hidden_channels), int(heads)
+        if comm is not None:
+            raise NotImplementedError("gcnx.Transformer runs on one device (comm is not supported)")
+        if heads not in (1, 2, 4, 8) or h % heads != 0:
+            raise NotImplementedError(f"gcnx.Transformer: heads={heads} must be 1, 2, 4 or 8 and divide hidden_channels={h}")
+        if h not in (16, 32, 64, 128) or h // heads < 4:
+            raise NotImplementedError(f"gcnx.Transformer: hidden_channels={h} must be 16, 32, 64 or 128 with at least 4 channels per head "
+                                      "(the widths the TransformerConv kernels serve; there is no composed route)")
+        if edge_dim is not None and not 1 <= int(edge_dim) <= 8:
+            raise NotImplementedError(f"gcnx.Transformer: edge_dim={edge_dim} must be None or 1 .. 8 (what the TransformerConv kernels serve)")
+        if beta and not root_weight:
+            raise NotImplementedError("gcnx.Transformer: beta=True gates the root connection and needs root_weight=True")
+        super()._init(ctx, h, num_classes, seed, None)
+        self.heads, self.edge_dim = heads, None if edge_dim is None else int(edge_dim)
+        self.beta, self.root_weight = bool(beta), bool(root_weight)
+        self.uses_edge_features = edge_dim is not None
+        self.blocks = self.BLOCKS if self.root_weight else self.BLOCKS[:3]
+        self.width = len(self.blocks) * h
+        conv = lambda k: (f"w{k}", f"lb{k}") + ((f"we{k}",) if self.edge_dim else ()) + ((f"wb{k}",) if self.beta else ())
+        self.PARAM_ORDER = conv(1) + conv(2) + ("g1", "be1", "a1", "g2", "be2", "a2") + GCN.PARAM_ORDER[10:]
+        lin = lambda k, n, s: ((f"conv{k}.{n}.weight", f"w{s}{k}", True), (f"conv{k}.{n}.bias", f"b{s}{k}", False))
+        keys = lambda k: lin(k, "lin_key", "k") + lin(k, "lin_query", "q") + lin(k, "lin_value", "v") + \
+            (((f"conv{k}.lin_edge.weight", f"we{k}", True),) if self.edge_dim else ()) + \
+            (lin(k, "lin_skip", "s") if self.root_weight else ()) + (((f"conv{k}.lin_beta.weight", f"wb{k}", False),) if self.beta else ())
+        self.TORCH_KEYS = keys(1) + keys(2) + GCN.TORCH_KEYS[4:]
+        self.BETA_KEYS = ("conv1.lin_beta.weight", "conv2.lin_beta.weight") if self.beta else ()
+
+    def _shapes(self, f_in):
+        s = super()._shapes(f_in)
+        h, d, w = self.hidden, self.edge_dim or 0, self.width
+        s.update(w1=(f_in, w), w2=(h, w), lb1=(w,), lb2=(w,), we1=(d, h), we2=(d, h), wb1=(3 * h,), wb2=(3 * h,))
+        return s
+
+    def build(self, f_in):
+        h, d, w = self.hidden, self.edge_dim or 0, self.width
+        shapes = self._shapes(f_in)
+        self.f_in = int(f_in)
+        # every parameter starts on a 16-byte boundary (the kernels read W_e, w_beta and W as float4); the padding floats have
+        # zero gradients, so the single update launch over the whole buffer leaves them at zero
+        self._alloc_flat([(k, shapes[k]) for k in self.PARAM_ORDER], align=4)
+        for t in (self.p, self.g):                      # PyG's names: the column blocks of the stacked weight and bias
+            for k in (1, 2):
+                for i, (_, s) in enumerate(self.blocks):
+                    t[f"w{s}{k}"], t[f"b{s}{k}"] = t[f"w{k}"].cols(i * h, (i + 1) * h), t[f"lb{k}"].flat(i * h, h)
+        rng, lim = self._rng, 1.0 / np.sqrt(h)
+        u = lambda fan_in, *s: rng.uniform(-1.0 / np.sqrt(fan_in), 1.0 / np.sqrt(fan_in), s)
+        init = {"w3": rng.uniform(-lim, lim, (h, h)), "b3": rng.uniform(-lim, lim, h),
+                "w4": rng.uniform(-lim, lim, (1, h)), "b4": rng.uniform(-lim, lim, 1)}
+        for k, f in ((1, f_in), (2, h)):
+            init[f"w{k}"], init[f"lb{k}"] = u(f, f, w), u(f, w)
+            if d:
+                init[f"we{k}"] = u(d, d, h)
+            if self.beta:
+                init[f"wb{k}"] = u(3 * h, 3 * h)
+        for k in ("g1", "g2", "g3", "g4"):
+            init[k] = np.ones(shapes[k])
+        for k in ("a1", "a2", "a3", "a4"):
+            init[k] = np.full(1, 0.25)
+        for k, v in init.items():
+            self.p[k].copy_from_host(np.asarray(v, np.float32))
+        self.built = True
+
+    # lin_beta.weight is [1, 3 H] in PyG's layout and [3 H] here
+    def state_dict(self):
+        d = super().state_dict()
+        d.update({k: d[k][None] for k in self.BETA_KEYS})
+        return d
+
+    def gradients(self):
+        d = super().gradients()
+        d.update({k: d[k][None] for k in self.BETA_KEYS})
+        return d
+
+    def load_state_dict(self, d):
+        """Inverse of state_dict; the four Linears' tensors are written into the stacked ones.  Builds the model if needed."""
+        d = dict(d)
+        if not self.built:
+            self.build(int(np.asarray(d[self.PROBE_KEY]).shape[1]))
+        missing = [tk for tk, _, _ in self.TORCH_KEYS if tk not in d]
+        if missing:
+            raise KeyError(f"gcnx.Transformer.load_state_dict: missing {missing}")
+        host = {}
+        for tk, k, tr in self.TORCH_KEYS:
+            v = np.asarray(d[tk], np.float32)
+            if tk in self.BETA_KEYS and v.ndim == 2 and v.shape[0] == 1:
+                v = v[0]
+            v = v.T if tr else v
+            if v.shape != self.p[k].shape:
+                raise ValueError(f"{tk}: shape {np.asarray(d[tk]).shape} does not fit this model")
+            host[k] = v
+        for k in (1, 2):
+            host[f"w{k}"] = np.concatenate([host.pop(f"w{s}{k}") for _, s in self.blocks], axis=1)
+            host[f"lb{k}"] = np.concatenate([host.pop(f"b{s}{k}") for _, s in self.blocks])
+        for k, v in host.items():
+            self.p[k].copy_from_host(np.ascontiguousarray(v))
+
+    def _as_batch(self, inputs, target=None):
+        if not isinstance(inputs, DeviceBatch):
+            if self.uses_edge_features and len(inputs) != 4:
+                raise ValueError(f"gcnx.Transformer(edge_dim={self.edge_dim}) takes (x, a, e, i): build the graphs with edge features "
+                                 "(Graph(e=...), from_networkx(use_edge_data='entries'))")
+        batch = self._adopt(inputs, target, weighted=False)      # the adjacency and e as stored: no loop added or removed
+        if self.uses_edge_features and batch.e is None:
+            raise ValueError("gcnx.Transformer: the batch carries no edge features (DeviceBatch.e)")
+        return batch
+
+    def _op(self, batch):
+        """The unweighted pattern of the batch, twice: the backward walks its transposed pattern through the entry permutation
+        (DeviceCSR.transpose_perm: the one a device loader's batch arrives with, or built here, once per batch object)."""
+        if self._op_cache is None or self._op_cache[0] != batch.uid:
+            a = batch.a.unweighted()
+            a.transpose_perm()
+            self._op_cache = (batch.uid, a, a)
+        return self._op_cache[1], self._op_cache[2]
+
+    def _ensure(self, batch, sharded=False):
+        bufs = super()._ensure(batch, sharded)
+        d = self.edge_dim or 0
+        if d and (batch.e is None or batch.e.shape != (batch.a.nnz, d)):
+            raise ValueError(f"gcnx.Transformer(edge_dim={d}): the batch's edge features must be [{batch.a.nnz}, {d}], got "
+                             f"{None if batch.e is None else list(batch.e.shape)}")
+        nnz = batch.a.nnz
+        if bufs.get("tf_key") != (batch.n, batch.n_graphs, nnz):           # the edge buffers follow nnz as well as (n, b)
+            v, n, h, heads, w = self._views(), batch.n, self.hidden, self.heads, self.width
+            if not D.transformer_conv_ok(self.ctx, n, heads, h // heads, ldp=w, edge_dim=d):
+                raise NotImplementedError(f"gcnx.Transformer: a batch of {n} rows at hidden_channels={h} is beyond the TransformerConv kernels")
+            for k in ("p1", "p2", "dp"):
+                bufs[k] = v("tf_" + k, n, w)
+            for k in ("o1", "o2", "d_o"):
+                bufs[k] = v("tf_" + k, n, h)
+            for k in ("alpha1", "alpha2", "dscore"):
+                bufs[k] = v("tf_" + k, nnz, heads)
+            ns = max(D.transformer_bwd_scratch_floats(self.ctx, n, heads, h // heads, d, self.beta), 1)
+            bufs["scratch"] = v("tf_scratch", 1, ns).flat(0, ns)
+            bufs["tf_key"] = (batch.n, batch.n_graphs, nnz)
+        return bufs
+
+    def _tf_fwd(self, a, x, e, k, bufs, keep):
+        """z_k = TransformerConv_k(x): Q | K | V | S in one product, then scores, softmax, weighted sum and the root connection
+        (with its beta gate) in one launch; keep: alpha and O."""
+        ctx, p, h, w = self.ctx, self.p, self.hidden, self.width
+        pk = bufs[f"p{k}"]
+        D.gemm(ctx, x, p[f"w{k}"], p[f"lb{k}"], pk)
+        D.transformer_aggregate(ctx, a, pk, bufs[f"z{k}"], self.heads, e=e, w_e=p.get(f"we{k}"),
+                                skip=pk.cols(3 * h, w) if self.root_weight else None, w_beta=p.get(f"wb{k}"),
+                                alpha=bufs[f"alpha{k}"] if keep else None, o_pre=bufs[f"o{k}"] if keep else None)
+
+    def _tf_bwd(self, a, x, e, k, dzk, bufs, dx):
+        """dZ_k -> the gradients of TransformerConv_k and, with dx, the gradient of its input."""
+        ctx, p, g, h, w = self.ctx, self.p, self.g, self.hidden, self.width
+        pk, dp, alpha, o = bufs[f"p{k}"], bufs["dp"], bufs[f"alpha{k}"], bufs[f"o{k}"]
+        d_o, ds = dzk, (dp.cols(3 * h, w) if self.root_weight else None)
+        if self.beta:
+            d_o = bufs["d_o"]
+            D.transformer_beta_bwd(ctx, dzk, o, pk.cols(3 * h, w), p[f"wb{k}"], d_o, ds, g[f"wb{k}"], bufs["scratch"])
+            ds = None
+        D.transformer_bwd_targets(ctx, a, pk, alpha, d_o, o, bufs["dscore"], dp.cols(0, h), self.heads, bufs["scratch"], ds=ds, e=e,
+                                  w_e=p.get(f"we{k}"), dw_e=g.get(f"we{k}"))
+        D.transformer_bwd_sources(ctx, a, pk, alpha, bufs["dscore"], d_o, dp.cols(h, 3 * h), self.heads)
+        D.gemm_dw(ctx, x, dp, g[f"w{k}"])                                            # dW_q | dW_k | dW_v | dW_s = x^T dP
+        D.act_bias_grad(ctx, dp, None, dp, None, db=g[f"lb{k}"])                     # db_q | db_k | db_v | db_s
+        if dx is not None:
+            D.gemm_dx(ctx, dp, p[f"w{k}"], dx)                                       # dx = dP [W_q | W_k | W_v | W_s]^T
+
+    def _conv1(self, a, batch, bufs, mode):
+        bufs["e"] = batch.e if self.uses_edge_features else None                    # (conv2 and the backward read the same rows)
+        self._tf_fwd(a, batch.x, bufs["e"], 1, bufs, mode == "grads")
+
+    def _conv2(self, a, bufs, mode):
+        self._tf_fwd(a, bufs["y1"], bufs["e"], 2, bufs, mode == "grads")
+
+    def _conv2_bwd(self, a_t, bufs):
+        self._tf_bwd(a_t, bufs["y1"], bufs["e"], 2, bufs["dz2"], bufs, bufs["dy1"])
+
+    def _conv1_bwd(self, a_t, batch, bufs):
+        self._tf_bwd(a_t, batch.x, bufs["e"], 1, bufs["dz1"], bufs, None)            # (the input carries no gradient)
 
 
 class ECCNet(_GraphRunner):

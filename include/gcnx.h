@@ -1039,6 +1039,83 @@ GCNX_API int gcnx_resgated_bwd_sources(gcnx_ctx* ctx, const int32_t* rowptr_t, c
                        const float* p, int64_t ldp, int32_t n, int32_t h, const float* e, int64_t lde, int32_t edge_dim,
                        const float* w_e, const float* d_out, int64_t ldd, float* dqv, int64_t ldg);
 
+/* ---- TransformerConv: scaled dot-product edge attention, small-feature regime (heads * c <= 128) ------------------------
+ * PyG's TransformerConv(in, c, heads, concat=True, beta, dropout=0, edge_dim, bias, root_weight) (Shi et al., UniMP): the
+ * dot-product way to use the dca / proximity features the reference computes and its model drops (gcn_utills.py:319-443;
+ * gcn.py:71).  CSR row i is the target, its stored entries j the sources, values are ignored, no self-loops are added or
+ * removed, the pattern and e are used as stored.  Head h owns columns [h c, h c + c) of every heads * c = HC wide block.
+ * p = Q | K | V (| S) [n, >= 3 HC] (ldp) is ONE array from one gcnx_gemm with the stacked weight and bias
+ * (x [W_q | W_k | W_v | W_s] + [b_q | b_k | b_v | b_s]: lin_query, lin_key, lin_value and lin_skip); e [nnz, edge_dim] (lde)
+ * holds the entries' features in the CSR's entry order, w_e [edge_dim, HC] is lin_edge (no bias):
+ *     T_ij = sum_d e_ij[d] W_e[d, :]        k_ij = K[j] + T_ij        v_ij = V[j] + T_ij     (T = 0 with edge_dim = 0)
+ *     score_ij,h = <Q[i,h,:], k_ij[h,:]> * s          s = fp32(1 / sqrt(c))
+ *     alpha = softmax over the stored entries of row i       O[i,h,:] = sum_j alpha_ij,h v_ij[h,:]   (no entries: O = 0)
+ *     no root_weight:          out = O
+ *     root_weight, beta=False: out = O + S
+ *     root_weight, beta=True:  b_i = sigmoid(<w1, O_i> + <w2, S_i> + <w3, O_i - S_i>)    out_i = b_i S_i + (1 - b_i) O_i
+ *                              (w_beta = lin_beta.weight = w1 | w2 | w3 [3 HC], no bias)
+ * and with d_out = dLoss/dout:
+ *     beta=False: dO = d_out,  dS = d_out
+ *     beta=True:  g_i = <d_out_i, S_i - O_i> b_i (1 - b_i)
+ *                 dO_i = (1 - b_i) d_out_i + g_i (w1 + w3)      dS_i = b_i d_out_i + g_i (w2 - w3)
+ *                 dw1 = sum_i g_i O_i     dw2 = sum_i g_i S_i     dw3 = sum_i g_i (O_i - S_i)
+ *     r[i,h] = <dO[i,h,:], O[i,h,:]>       dscore_ij,h = alpha_ij,h (<dO[i,h,:], v_ij[h,:]> - r[i,h])
+ *     dQ[i] = s sum_j dscore_ij k_ij                                            (forward CSR)
+ *     dK[j] = s sum_i dscore_ij Q[i]        dV[j] = sum_i alpha_ij dO[i]        (transposed pattern; needs no e and no W_e)
+ *     dW_e[d,h,:] = sum_i ( s Q[i,h,:] A_i[d,h] + dO[i,h,:] B_i[d,h] )
+ *                   A_i[d,h] = sum_j e_ij[d] dscore_ij,h     B_i[d,h] = sum_j e_ij[d] alpha_ij,h
+ * d b_k is analytically zero: a common shift of all keys moves every score of a row by the same amount.  The row maximum
+ * is subtracted before every exponential and the softmax denominator is >= 1: no overflow, no 0 / 0.  sigmoid(a) =
+ * 1 / (1 + exp(-a)) with the overflow to inf resolving to 0: every finite a gives a finite b and a finite b (1 - b).
+ * fp32, no float atomics, fixed summation order: the same bits on every call.  Nothing is allocated.
+ * gcnx_transformer_conv_ok (gcn.py:71): 1 if the shapes are served: heads in {1, 2, 4, 8}, heads * c in {16, 32, 64, 128},
+ * c >= 4, 0 <= edge_dim <= 8, ldp % 4 == 0, ldp >= 3 * heads * c, n * ldp * 4 < 2^32.  Every call below returns
+ * GCNX_ERR_UNSUPPORTED otherwise, and for float4 operands (everything but e, alpha, dscore and the index arrays) off a
+ * 16-byte boundary or leading dimensions that are not multiples of 4 floats >= their width, with nothing launched and
+ * nothing written.  n == 0 succeeds and writes nothing; negative sizes and NULL mandatory pointers are GCNX_ERR_INVALID;
+ * e, w_e (and dw_e) may be NULL only with edge_dim == 0. */
+GCNX_API int gcnx_transformer_conv_ok(int64_t n, int32_t heads, int32_t c, int64_t ldp, int32_t edge_dim);
+/* gcn.py:71 -- out [n, HC] (ldo) from ONE gather of the contiguous K[j] | V[j] per entry, with a running row maximum and a
+ * rescaled accumulator, summed in CSR order.  skip (lds; may be NULL: root_weight=False) is S, typically p + 3 HC; w_beta
+ * [3 HC] (may be NULL: beta=False) applies the gate in the epilogue, the row's dot a butterfly over the lane group; w_beta
+ * without skip is GCNX_ERR_INVALID.  A row without entries: O = 0 exactly, and out = S bit for bit without beta.  alpha
+ * [nnz, heads] and o_pre [n, HC] (ldpre) = O save what the backward needs; both may be NULL (inference). */
+GCNX_API int gcnx_transformer_aggregate(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, const float* p,
+                       int64_t ldp, int32_t n, int32_t heads, int32_t c, const float* e, int64_t lde, int32_t edge_dim,
+                       const float* w_e, const float* skip, int64_t lds, const float* w_beta, float* out, int64_t ldo,
+                       float* alpha, float* o_pre, int64_t ldpre);
+/* gcn.py:71 -- *out = floats of caller scratch the backward needs: per-workgroup parts of dw_e (gcnx_transformer_bwd_targets)
+ * and, with beta != 0, of dw_beta (gcnx_transformer_beta_bwd); the two calls run one after the other and may share it
+ * (the larger of the two; 0 with edge_dim == 0 and beta == 0).  Answers without a context; heads <= 0, c <= 0, n < 0,
+ * edge_dim < 0 and out == NULL are GCNX_ERR_INVALID. */
+GCNX_API int gcnx_transformer_bwd_scratch_floats(int64_t n, int32_t heads, int32_t c, int32_t edge_dim, int32_t beta,
+                       int64_t* out);
+/* gcn.py:71 -- backward of the beta gate (called only with beta=True), row by row: b is recomputed from o = O (ldo) and skip =
+ * S (lds).  d_out [n, hc] (ldd) -> d_o [n, hc] (ldgo) = dO, d_s [n, hc] (ldgs) = dS, dw_beta [3 hc] = dw1 | dw2 | dw3.
+ * hc in {16, 32, 64, 128}.  dw_beta goes through per-workgroup parts in scratch and a second small launch inside this
+ * call (fixed order, no atomics). */
+GCNX_API int gcnx_transformer_beta_bwd(gcnx_ctx* ctx, const float* d_out, int64_t ldd, const float* o, int64_t ldo,
+                       const float* skip, int64_t lds, const float* w_beta, int32_t n, int32_t hc, float* d_o, int64_t ldgo,
+                       float* d_s, int64_t ldgs, float* dw_beta, float* scratch);
+/* gcn.py:71 -- backward, the pass over the forward CSR.  d_o = dO [n, HC] (ldd), o = O (ldo), alpha from the forward.
+ * Writes dscore [nnz, heads] in entry order, dq [n, HC] (ldg) = dQ and dw_e [edge_dim, HC]; with ds non-NULL copies d_o
+ * into ds [n, HC] (ldgs) = dS, the beta=False root path, so that ONE gcnx_gemm_dw / gcnx_gemm_dx serves a dQ | dK | dV | dS
+ * array.  The dw_e sums go through per-workgroup parts in scratch (2 edge_dim scalars per row and head, the outer products
+ * formed once per row) and a second small launch inside this call (fixed order, no atomics). */
+GCNX_API int gcnx_transformer_bwd_targets(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, const float* p,
+                       int64_t ldp, int32_t n, int32_t heads, int32_t c, const float* e, int64_t lde, int32_t edge_dim,
+                       const float* w_e, const float* alpha, const float* d_o, int64_t ldd, const float* o, int64_t ldo,
+                       float* dscore, float* dq, int64_t ldg, float* ds, int64_t ldgs, float* dw_e, float* scratch);
+/* gcn.py:71 -- backward, the pass over the transposed pattern (rowptr_t, colidx_t, perm_t of gcnx_csr_transpose_perm:
+ * perm_t[p] = the forward entry behind entry p; needed for a symmetric pattern too).  alpha and dscore are read in the
+ * forward entry order through perm_t; for source j and each of its targets i the kernel gathers Q[i] and d_o[i]
+ * (n * ldd * 4 < 2^32); it reads neither e nor w_e.  Writes dkv [n, 2 HC] (ldg) = dK | dV, e.g. columns [HC, 3 HC) of
+ * dQ | dK | dV | dS.  dW, db and dx of the layer are gcnx_gemm_dw, gcnx_act_bias_grad (over the biased columns) and
+ * gcnx_gemm_dx on that array. */
+GCNX_API int gcnx_transformer_bwd_sources(gcnx_ctx* ctx, const int32_t* rowptr_t, const int32_t* colidx_t,
+                       const int32_t* perm_t, const float* p, int64_t ldp, int32_t n, int32_t heads, int32_t c,
+                       const float* alpha, const float* dscore, const float* d_o, int64_t ldd, float* dkv, int64_t ldg);
+
 /* ---- TopKPool: per-graph top-k selection, gated gather, induced sub-CSR ------------------------------------------
  * spektral.layers.pooling.TopKPool, the one layer the reference's training script imports (gcn.py:10) that had no kernels
  * here, in disjoint mode: y = X p / ||p||, the k_g rows of every graph with the largest y are kept, X' = (X * gate(y))[idx],
