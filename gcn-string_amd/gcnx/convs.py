@@ -1,0 +1,151 @@
+"""The launch sequences of the convolutions that a layer (gcnx.layers) and a model (gcnx.models) both run: PNAConv, GATConv,
+GATv2Conv, ResGatedGraphConv and TransformerConv.  This is the one place they are written down.
+
+One forward and one backward function per convolution, plain functions over operands: ``ctx``, the pattern, the operands, the
+parameter views, the gradient views, every scratch and output buffer, then the scalars.  The caller owns the storage, the
+shape checks (``*_conv_ok``) and the scratch sizes (``*_scratch_floats``); nothing here allocates, looks a name up or
+validates.  An optional operand is ``None`` and drops exactly its launch or argument: no ``bias``, no ``e`` / ``w_e`` /
+``g_w_e``, ``alpha`` / ``o_pre`` not kept (a forward no backward follows), no ``w_beta``, ``dx`` not wanted.  Weights are
+stored [in, out].  ``h`` below is the convolution's output width (heads * channels); whether a stacked P = ... | S carries the
+root block S is read off its width (4 h, or 3 h without root_weight).
+
+SAGEConv and GINConv are not here: layer and model choose their one-launch route by different predicates."""
+from __future__ import annotations
+
+from . import device as D
+
+
+# ---- PNAConv -----------------------------------------------------------------------------------------------------------------
+def pna_forward(ctx, a, x, w_pre, b_pre, w_post, b_post, w_lin, b_lin, delta, pq, c, stats, t, out):
+    """pq = P | Q, c = the 13 blocks, t = C W_post + b_post, out = t W_lin + b_lin.  stats None: no backward follows."""
+    f = x.shape[1]
+    D.gemm(ctx, x, w_pre.flat(0, f * f, (f, f)), b_pre, pq.cols(0, f))                      # P = x W_pre[:F] + b_pre
+    D.gemm(ctx, x, w_pre.flat(f * f, f * f, (f, f)), None, pq.cols(f, 2 * f))               # Q = x W_pre[F:]
+    D.pna_aggregate(ctx, a, x, pq, delta, c, stats)
+    D.gemm(ctx, c, w_post, b_post, t)
+    D.gemm(ctx, t, w_lin, b_lin, out)
+
+
+def pna_backward(ctx, a, a_t, x, pq, c, stats, t, dz, w_pre, w_post, w_lin, g_w_pre, g_b_pre, g_w_post, g_b_post, g_w_lin, g_b_lin,
+                 delta, dt, dc, dpq, coef, dx):
+    """From dz = dLoss / dout: every parameter gradient, and into dx (None: not needed) the gradient of the layer's input.
+    dt [n, H], dc [n, 13F], dpq [n, 2F] and coef (pna_bwd_scratch_floats) are scratch."""
+    f = x.shape[1]
+    if g_b_lin is not None:
+        D.act_bias_grad(ctx, dz, None, dz, None, db=g_b_lin)                               # db_lin: column sums of dZ
+    D.gemm_dx(ctx, dz, w_lin, dt, db=g_b_post)                                             # dT = dZ W_lin^T, db_post
+    D.gemm_dw2(ctx, t, dz, g_w_lin, c, dt, g_w_post)                                       # dW_lin = T^T dZ, dW_post = C^T dT
+    D.gemm_dx(ctx, dt, w_post, dc)                                                         # dC = dT W_post^T
+    D.pna_bwd(ctx, a, a_t, pq, stats, dc, delta, dpq, coef)                                # dP | dQ (block 0 of dC untouched)
+    dp, dq = dpq.cols(0, f), dpq.cols(f, 2 * f)
+    if g_b_pre is not None:
+        D.act_bias_grad(ctx, dp, None, dp, None, db=g_b_pre)                               # db_pre: column sums of dP
+    g_top, g_bot = g_w_pre.flat(0, f * f, (f, f)), g_w_pre.flat(f * f, f * f, (f, f))
+    if f % 4 == 0:
+        D.gemm_dw2(ctx, x, dp, g_top, x, dq, g_bot)                                        # dW_pre = x^T [dP | dQ]
+    else:                                       # (the lower half starts off a 16-byte boundary: one launch each)
+        D.gemm_dw(ctx, x, dp, g_top)
+        D.gemm_dw(ctx, x, dq, g_bot)
+    if dx is not None:                          # dx = dC[:, :F] + dP W_pre[:F]^T + dQ W_pre[F:]^T
+        D.gemm_dx(ctx, dp, w_pre.flat(0, f * f, (f, f)), dx)
+        D.gemm_dx(ctx, dq, w_pre.flat(f * f, f * f, (f, f)), dx, accumulate=True)
+        D.add(ctx, dx, dc.cols(0, f), dx)
+
+
+# ---- GATConv -----------------------------------------------------------------------------------------------------------------
+def gat_forward(ctx, a, x, w, att_src, att_dst, bias, hf, asrc, adst, alpha, o_pre, out, slope):
+    """hf = x W, the score halves asrc / adst [n, heads], then the softmax-weighted gather into out (+ bias).  alpha
+    [nnz, heads] and o_pre (out before the bias) are what the backward reads."""
+    D.gemm(ctx, x, w, None, hf)
+    D.gat_scores(ctx, hf, att_src, att_dst, asrc, adst)
+    D.gat_aggregate(ctx, a, hf, asrc, adst, bias, out, alpha=alpha, o_pre=o_pre, slope=slope)
+
+
+def gat_backward(ctx, a, x, hf, asrc, adst, alpha, o_pre, dz, w, att_src, att_dst, g_w, g_att_src, g_att_dst, g_bias, dscore, dadst,
+                 dasrc, dhf, scratch, dx, slope):
+    """From dz: the four gradients and, with dx, the gradient of the input.  a carries its transposed pattern
+    (DeviceCSR.transpose_perm); dscore [nnz, heads], dadst / dasrc [n, heads], dhf [n, h], scratch (gat_bwd_scratch_floats)."""
+    if g_bias is not None:
+        D.act_bias_grad(ctx, dz, None, dz, None, db=g_bias)                                # column sums of dZ
+    D.gat_bwd_edges(ctx, a, hf, asrc, adst, alpha, dz, o_pre, dscore, dadst, slope=slope)
+    D.gat_bwd_nodes(ctx, a, alpha, dscore, dz, hf, dadst, att_src, att_dst, dhf, dasrc, g_att_src, g_att_dst, scratch)
+    D.gemm_dw(ctx, x, dhf, g_w)                                                            # dW = x^T dHf
+    if dx is not None:
+        D.gemm_dx(ctx, dhf, w, dx)                                                         # dx = dHf W^T
+
+
+# ---- GATv2Conv ---------------------------------------------------------------------------------------------------------------
+def gatv2_forward(ctx, a, x, e, w, lin_bias, att, bias, w_e, xlr, alpha, o_pre, out, slope):
+    """xlr = Xl | Xr = x [W_l | W_r] + [b_l | b_r] in one product, then scores, softmax and weighted sum in one launch."""
+    D.gemm(ctx, x, w, lin_bias, xlr)
+    D.gatv2_aggregate(ctx, a, xlr, att, bias, out, e=e, w_e=w_e, alpha=alpha, o_pre=o_pre, slope=slope)
+
+
+def gatv2_backward(ctx, a, x, e, xlr, alpha, o_pre, dz, w, att, w_e, g_w, g_lin_bias, g_att, g_bias, g_w_e, dscore, dxlr, scratch,
+                   dx, slope):
+    """From dz: the gradients of the stacked weight and bias, att, the conv bias and W_e, and with dx the gradient of the input.
+    dxlr [n, 2 h] = dXl | dXr: the forward CSR writes dXr, the transposed pattern dXl."""
+    h = dz.shape[1]
+    if g_bias is not None:
+        D.act_bias_grad(ctx, dz, None, dz, None, db=g_bias)                                # column sums of dZ
+    D.gatv2_bwd_edges(ctx, a, xlr, att, alpha, dz, o_pre, dscore, dxlr.cols(h, 2 * h), g_att, scratch, e=e, w_e=w_e, dw_e=g_w_e,
+                      slope=slope)
+    D.gatv2_bwd_nodes(ctx, a, xlr, att, alpha, dscore, dz, dxlr.cols(0, h), e=e, w_e=w_e, slope=slope)
+    D.gemm_dw(ctx, x, dxlr, g_w)                                                           # dW_l | dW_r = x^T (dXl | dXr)
+    D.act_bias_grad(ctx, dxlr, None, dxlr, None, db=g_lin_bias)                            # db_l | db_r: column sums
+    if dx is not None:
+        D.gemm_dx(ctx, dxlr, w, dx)                                                        # dx = dXl W_l^T + dXr W_r^T
+
+
+# ---- ResGatedGraphConv -------------------------------------------------------------------------------------------------------
+def resgated_forward(ctx, a, x, e, w, gemm_bias, bias, w_e, pk, out):
+    """pk = K | Q | V | S = x [W_k | W_q | W_v | W_s] + gemm_bias in one product (gemm_bias: b_k | b_q | b_v and zeros under S),
+    then gates, messages and their sum in one launch."""
+    h, wd = out.shape[1], pk.shape[1]
+    D.gemm(ctx, x, w, gemm_bias, pk)
+    D.resgated_aggregate(ctx, a, pk, out, e=e, w_e=w_e, skip=pk.cols(3 * h, wd) if wd > 3 * h else None, bias=bias)
+
+
+def resgated_backward(ctx, a, x, e, pk, dz, w, w_e, g_w, g_lin_bias, g_bias, g_w_e, dp, scratch, dx):
+    """From dz: the gradients of the stacked weight, of b_k | b_q | b_v, of the conv bias and of the edge weight, and with dx the
+    gradient of the input.  dp = dK | dQ | dV | dS as pk; scratch: resgated_bwd_scratch_floats."""
+    h, wd = dz.shape[1], dp.shape[1]
+    if g_bias is not None:
+        D.act_bias_grad(ctx, dz, None, dz, None, db=g_bias)                                # column sums of dZ
+    D.resgated_bwd_targets(ctx, a, pk, dz, dp.cols(0, h), scratch, ds=dp.cols(3 * h, wd) if wd > 3 * h else None, e=e, w_e=w_e,
+                           dw_e=g_w_e)
+    D.resgated_bwd_sources(ctx, a, pk, dz, dp.cols(h, 3 * h), e=e, w_e=w_e)
+    D.gemm_dw(ctx, x, dp, g_w)                                                             # dW_k | dW_q | dW_v | dW_s = x^T dP
+    dkqv = dp.cols(0, 3 * h)
+    D.act_bias_grad(ctx, dkqv, None, dkqv, None, db=g_lin_bias)                            # db_k | db_q | db_v: column sums
+    if dx is not None:
+        D.gemm_dx(ctx, dp, w, dx)                                                          # dx = dP [W_k | W_q | W_v | W_s]^T
+
+
+# ---- TransformerConv ---------------------------------------------------------------------------------------------------------
+def transformer_forward(ctx, a, x, e, w, lin_bias, w_e, w_beta, pk, alpha, o_pre, out, heads):
+    """pk = Q | K | V | S in one product, then scores, softmax, weighted sum and the root connection (with its beta gate) in one
+    launch."""
+    h, wd = out.shape[1], pk.shape[1]
+    D.gemm(ctx, x, w, lin_bias, pk)
+    D.transformer_aggregate(ctx, a, pk, out, heads, e=e, w_e=w_e, skip=pk.cols(3 * h, wd) if wd > 3 * h else None, w_beta=w_beta,
+                            alpha=alpha, o_pre=o_pre)
+
+
+def transformer_backward(ctx, a, x, e, pk, alpha, o_pre, dz, w, w_e, w_beta, g_w, g_lin_bias, g_w_e, g_w_beta, dp, dscore, d_o,
+                         scratch, dx, heads):
+    """From dz: the gradients of the stacked weight and bias, W_e and w_beta, and with dx the gradient of the input.
+    dp = dQ | dK | dV | dS as pk; d_o [n, h] is needed with w_beta only: the gate's backward writes dO there and dS itself, so
+    the targets' launch then reads d_o in the place of dz and is handed no ds."""
+    h, wd = dz.shape[1], dp.shape[1]
+    ds = dp.cols(3 * h, wd) if wd > 3 * h else None
+    if w_beta is not None:
+        D.transformer_beta_bwd(ctx, dz, o_pre, pk.cols(3 * h, wd), w_beta, d_o, ds, g_w_beta, scratch)
+        dz, ds = d_o, None
+    D.transformer_bwd_targets(ctx, a, pk, alpha, dz, o_pre, dscore, dp.cols(0, h), heads, scratch, ds=ds, e=e, w_e=w_e, dw_e=g_w_e)
+    D.transformer_bwd_sources(ctx, a, pk, alpha, dscore, dz, dp.cols(h, 3 * h), heads)
+    D.gemm_dw(ctx, x, dp, g_w)                                                             # dW_q | dW_k | dW_v | dW_s = x^T dP
+    if g_lin_bias is not None:
+        D.act_bias_grad(ctx, dp, None, dp, None, db=g_lin_bias)                            # the stacked bias: column sums
+    if dx is not None:
+        D.gemm_dx(ctx, dp, w, dx)                                                          # dx = dP [W_q | W_k | W_v | W_s]^T

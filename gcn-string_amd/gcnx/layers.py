@@ -25,7 +25,9 @@ import os
 
 import numpy as np
 
+from . import convs
 from . import device as D
+from .convs import pna_backward, pna_forward     # (the models and the tests import the two from here)
 
 _FUSED_KNOB = os.environ.get("GCNX_FUSED", "1") != "0"     # tuning knob, read once at import (diagnostics)
 
@@ -443,6 +445,7 @@ class PNAConv(Layer):
     ``pre_nns.0.0.bias``, ``post_nns.0.0.weight`` (stored [13F, H]; PyG: [H, 13F]), ``post_nns.0.0.bias``, ``lin.weight``,
     ``lin.bias``; initialised U(+-1/sqrt(fan_in)) as torch's Linear.
 
+    Launches (pna_forward / pna_backward of gcnx/convs.py, which gcnx.PNA runs too).
     Forward: gcnx_gemm twice into the halves of one [N, 2F] array (the pre weight's row halves are contiguous views),
     gcnx_pna_aggregate (csrc/pna.hip: one gather for the four statistics, all 13 blocks of C), gcnx_gemm twice.  Backward:
     gcnx_act_bias_grad (db_lin), gcnx_gemm_dx (dT, db_post), gcnx_gemm_dw2 (dW_lin = T^T dZ, dW_post = C^T dT), gcnx_gemm_dx
@@ -515,43 +518,6 @@ class PNAConv(Layer):
         return dx
 
 
-def pna_forward(ctx, a, x, w_pre, b_pre, w_post, b_post, w_lin, b_lin, delta, pq, c, stats, t, out):
-    """One PNAConv forward (PNAConv.call and gcnx.PNA share it): pq = P | Q, c = the 13 blocks, t = C W_post + b_post,
-    out = t W_lin + b_lin.  Weights stored [in, out]; stats None: no backward follows."""
-    f = x.shape[1]
-    D.gemm(ctx, x, w_pre.flat(0, f * f, (f, f)), b_pre, pq.cols(0, f))                      # P = x W_pre[:F] + b_pre
-    D.gemm(ctx, x, w_pre.flat(f * f, f * f, (f, f)), None, pq.cols(f, 2 * f))               # Q = x W_pre[F:]
-    D.pna_aggregate(ctx, a, x, pq, delta, c, stats)
-    D.gemm(ctx, c, w_post, b_post, t)
-    D.gemm(ctx, t, w_lin, b_lin, out)
-
-
-def pna_backward(ctx, a, a_t, x, pq, c, stats, t, dz, w_pre, w_post, w_lin, g_w_pre, g_b_pre, g_w_post, g_b_post, g_w_lin, g_b_lin,
-                 delta, dt, dc, dpq, coef, dx):
-    """One PNAConv backward from dz = dLoss / dout: every parameter gradient, and into dx (None: not needed) the gradient of
-    the layer's input.  dt [n, H], dc [n, 13F], dpq [n, 2F] and coef (pna_bwd_scratch_floats) are scratch."""
-    f = x.shape[1]
-    if g_b_lin is not None:
-        D.act_bias_grad(ctx, dz, None, dz, None, db=g_b_lin)                               # db_lin: column sums of dZ
-    D.gemm_dx(ctx, dz, w_lin, dt, db=g_b_post)                                             # dT = dZ W_lin^T, db_post
-    D.gemm_dw2(ctx, t, dz, g_w_lin, c, dt, g_w_post)                                       # dW_lin = T^T dZ, dW_post = C^T dT
-    D.gemm_dx(ctx, dt, w_post, dc)                                                         # dC = dT W_post^T
-    D.pna_bwd(ctx, a, a_t, pq, stats, dc, delta, dpq, coef)                                # dP | dQ (block 0 of dC untouched)
-    dp, dq = dpq.cols(0, f), dpq.cols(f, 2 * f)
-    if g_b_pre is not None:
-        D.act_bias_grad(ctx, dp, None, dp, None, db=g_b_pre)                               # db_pre: column sums of dP
-    g_top, g_bot = g_w_pre.flat(0, f * f, (f, f)), g_w_pre.flat(f * f, f * f, (f, f))
-    if f % 4 == 0:
-        D.gemm_dw2(ctx, x, dp, g_top, x, dq, g_bot)                                        # dW_pre = x^T [dP | dQ]
-    else:                                       # (the lower half starts off a 16-byte boundary: one launch each)
-        D.gemm_dw(ctx, x, dp, g_top)
-        D.gemm_dw(ctx, x, dq, g_bot)
-    if dx is not None:                          # dx = dC[:, :F] + dP W_pre[:F]^T + dQ W_pre[F:]^T
-        D.gemm_dx(ctx, dp, w_pre.flat(0, f * f, (f, f)), dx)
-        D.gemm_dx(ctx, dq, w_pre.flat(f * f, f * f, (f, f)), dx, accumulate=True)
-        D.add(ctx, dx, dc.cols(0, f), dx)
-
-
 class GATConv(Layer):
     """torch_geometric.nn.GATConv(in, channels, heads, concat=True, negative_slope=0.2, dropout=0.0, bias=True) -- the attention
     layer for the slot the reference's author marked as open (gcn_utills.py:804-806); spektral.layers.GATConv is the same layer:
@@ -566,7 +532,8 @@ class GATConv(Layer):
     ``lin.weight`` (stored [in, heads * channels]; PyG: [heads * channels, in]); glorot-uniform as PyG, the bias zero.
     ``backward(dy, need_dx=True)`` returns dx (None with need_dx=False) and leaves the four gradients in ``grads``.
 
-    Launches (csrc/gat.hip): gcnx_gemm, gcnx_gat_scores, gcnx_gat_aggregate forward; gcnx_act_bias_grad, gcnx_gat_bwd_edges,
+    Launches (gat_forward / gat_backward of gcnx/convs.py, which the model runs too; csrc/gat.hip):
+    gcnx_gemm, gcnx_gat_scores, gcnx_gat_aggregate forward; gcnx_act_bias_grad, gcnx_gat_bwd_edges,
     gcnx_gat_bwd_nodes, gcnx_gemm_dw, gcnx_gemm_dx backward.  There is no composed route: what the kernels do not serve
     (concat=False, attention dropout, edge features, shapes gcnx_gat_conv_ok refuses) raises NotImplementedError."""
 
@@ -619,27 +586,20 @@ class GATConv(Layer):
         y = out if out is not None else self._buf("y", (n, h * c))
         hf, o = self._buf("hf", (n, h * c)), self._buf("o", (n, h * c))
         asrc, adst, alpha = self._buf("asrc", (n, h)), self._buf("adst", (n, h)), self._buf("alpha", (a.nnz, h))
-        D.gemm(ctx, x, p["lin.weight"], None, hf)
-        D.gat_scores(ctx, hf, p["att_src"], p["att_dst"], asrc, adst)
-        D.gat_aggregate(ctx, a, hf, asrc, adst, p.get("bias"), y, alpha=alpha, o_pre=o, slope=self.negative_slope)
+        convs.gat_forward(ctx, a, x, p["lin.weight"], p["att_src"], p["att_dst"], p.get("bias"), hf, asrc, adst, alpha, o, y,
+                          self.negative_slope)
         self._saved = (x, a, hf, asrc, adst, alpha, o)
         return y
 
     def backward(self, dy, need_dx=True):
         x, a, hf, asrc, adst, alpha, o = self._saved
         ctx, p, g, h, c, n = self.ctx, self.params, self.grads, self.heads, self.channels, x.shape[0]
-        if self.use_bias:
-            D.act_bias_grad(ctx, dy, None, dy, None, db=g["bias"])                  # column sums of dy
         dz, dadst, dasrc = self._buf("dz", (a.nnz, h)), self._buf("dadst", (n, h)), self._buf("dasrc", (n, h))
         dhf = self._buf("dhf", (n, h * c))
         scratch = self._buf("scratch", (max(D.gat_bwd_scratch_floats(ctx, n, h, c), 1),))
-        D.gat_bwd_edges(ctx, a, hf, asrc, adst, alpha, dy, o, dz, dadst, slope=self.negative_slope)
-        D.gat_bwd_nodes(ctx, a, alpha, dz, dy, hf, dadst, p["att_src"], p["att_dst"], dhf, dasrc, g["att_src"], g["att_dst"], scratch)
-        D.gemm_dw(ctx, x, dhf, g["lin.weight"])                                     # dW = x^T dHf
-        if not need_dx:
-            return None
-        dx = self._buf("dx", x.shape)
-        D.gemm_dx(ctx, dhf, p["lin.weight"], dx)                                    # dx = dHf W^T
+        dx = self._buf("dx", x.shape) if need_dx else None
+        convs.gat_backward(ctx, a, x, hf, asrc, adst, alpha, o, dy, p["lin.weight"], p["att_src"], p["att_dst"], g["lin.weight"],
+                           g["att_src"], g["att_dst"], g.get("bias"), dz, dadst, dasrc, dhf, scratch, dx, self.negative_slope)
         return dx
 
 
@@ -662,7 +622,8 @@ class GATv2Conv(Layer):
     ``params`` / ``grads`` hold per-name views; ``state_dict()`` gives PyG's layouts.  glorot-uniform as PyG, biases zero.
     ``backward(dy, need_dx=True)`` returns dx (None with need_dx=False) and leaves the gradients in ``grads``.
 
-    Launches (csrc/gatv2.hip): gcnx_gemm, gcnx_gatv2_aggregate forward; gcnx_act_bias_grad, gcnx_gatv2_bwd_edges,
+    Launches (gatv2_forward / gatv2_backward of gcnx/convs.py, which the model runs too; csrc/gatv2.hip):
+    gcnx_gemm, gcnx_gatv2_aggregate forward; gcnx_act_bias_grad, gcnx_gatv2_bwd_edges,
     gcnx_gatv2_bwd_nodes, gcnx_gemm_dw, gcnx_act_bias_grad, gcnx_gemm_dx backward.  There is no composed route: what the kernels
     do not serve (concat=False, attention dropout, share_weights=True, shapes gcnx_gatv2_conv_ok refuses) raises
     NotImplementedError."""
@@ -774,30 +735,20 @@ class GATv2Conv(Layer):
         ctx, n, p = self.ctx, x.shape[0], self.params
         y = out if out is not None else self._buf("y", (n, h * c))
         xlr, o, alpha = self._buf("xlr", (n, 2 * h * c)), self._buf("o", (n, h * c)), self._buf("alpha", (a.nnz, h))
-        D.gemm(ctx, x, self.lin_weight, self.lin_bias, xlr)                         # Xl | Xr
-        D.gatv2_aggregate(ctx, a, xlr, p["att"], p.get("bias"), y, e=e, w_e=p.get("lin_edge.weight"), alpha=alpha, o_pre=o,
-                          slope=self.negative_slope)
+        convs.gatv2_forward(ctx, a, x, e, self.lin_weight, self.lin_bias, p["att"], p.get("bias"), p.get("lin_edge.weight"), xlr, alpha,
+                            o, y, self.negative_slope)
         self._saved = (x, a, e, xlr, alpha, o)
         return y
 
     def backward(self, dy, need_dx=True):
         x, a, e, xlr, alpha, o = self._saved
         ctx, p, g, h, c, n = self.ctx, self.params, self.grads, self.heads, self.channels, x.shape[0]
-        hc = h * c
-        if self.use_bias:
-            D.act_bias_grad(ctx, dy, None, dy, None, db=g["bias"])                  # column sums of dy
-        dscore, dxlr = self._buf("dscore", (a.nnz, h)), self._buf("dxlr", (n, 2 * hc))
+        dscore, dxlr = self._buf("dscore", (a.nnz, h)), self._buf("dxlr", (n, 2 * h * c))
         scratch = self._buf("scratch", (max(D.gatv2_bwd_scratch_floats(ctx, n, h, c, self.edge_dim or 0), 1),))
-        w_e = p.get("lin_edge.weight")
-        D.gatv2_bwd_edges(ctx, a, xlr, p["att"], alpha, dy, o, dscore, dxlr.cols(hc, 2 * hc), g["att"], scratch, e=e, w_e=w_e,
-                          dw_e=g.get("lin_edge.weight"), slope=self.negative_slope)
-        D.gatv2_bwd_nodes(ctx, a, xlr, p["att"], alpha, dscore, dy, dxlr.cols(0, hc), e=e, w_e=w_e, slope=self.negative_slope)
-        D.gemm_dw(ctx, x, dxlr, self.lin_weight_grad)                               # dW_l | dW_r = x^T (dXl | dXr)
-        D.act_bias_grad(ctx, dxlr, None, dxlr, None, db=self.lin_bias_grad)         # db_l | db_r: column sums
-        if not need_dx:
-            return None
-        dx = self._buf("dx", x.shape)
-        D.gemm_dx(ctx, dxlr, self.lin_weight, dx)                                   # dx = dXl W_l^T + dXr W_r^T
+        dx = self._buf("dx", x.shape) if need_dx else None
+        convs.gatv2_backward(ctx, a, x, e, xlr, alpha, o, dy, self.lin_weight, p["att"], p.get("lin_edge.weight"), self.lin_weight_grad,
+                             self.lin_bias_grad, g["att"], g.get("bias"), g.get("lin_edge.weight"), dscore, dxlr, scratch, dx,
+                             self.negative_slope)
         return dx
 
 
@@ -825,7 +776,8 @@ class ResGatedGraphConv(Layer):
     U(+-1 / sqrt(fan_in)) for every weight and bias (fan_in = in + D for key / query / value), ``bias`` zero.
     ``backward(dy, need_dx=True)`` returns dx (None with need_dx=False) and leaves the gradients in ``grads``.
 
-    Launches (csrc/resgated.hip): gcnx_gemm, gcnx_resgated_aggregate forward; gcnx_act_bias_grad, gcnx_resgated_bwd_targets,
+    Launches (resgated_forward / resgated_backward of gcnx/convs.py, which the model runs too; csrc/resgated.hip):
+    gcnx_gemm, gcnx_resgated_aggregate forward; gcnx_act_bias_grad, gcnx_resgated_bwd_targets,
     gcnx_resgated_bwd_sources, gcnx_gemm_dw, gcnx_act_bias_grad, gcnx_gemm_dx backward.  There is no composed route: what the
     kernels do not serve (a gate other than the sigmoid, bipartite inputs, shapes gcnx_resgated_conv_ok refuses) raises
     NotImplementedError."""
@@ -968,29 +920,18 @@ class ResGatedGraphConv(Layer):
         ctx, n, p = self.ctx, x.shape[0], self.params
         y = out if out is not None else self._buf("y", (n, h))
         pk = self._buf("p", (n, w))
-        D.gemm(ctx, x, p["weight"], self._gemm_bias, pk)                            # K | Q | V | S
-        D.resgated_aggregate(ctx, a, pk, y, e=e, w_e=p.get("edge_weight"), skip=pk.cols(3 * h, w) if self.root_weight else None,
-                             bias=p.get("bias"))
+        convs.resgated_forward(ctx, a, x, e, p["weight"], self._gemm_bias, p.get("bias"), p.get("edge_weight"), pk, y)
         self._saved = (x, a, e, pk)
         return y
 
     def backward(self, dy, need_dx=True):
         x, a, e, pk = self._saved
         ctx, p, g, h, n, w = self.ctx, self.params, self.grads, self.channels, x.shape[0], self._width()
-        if self.use_bias:
-            D.act_bias_grad(ctx, dy, None, dy, None, db=g["bias"])                  # column sums of dy
         dp = self._buf("dp", (n, w))
         scratch = self._buf("scratch", (max(D.resgated_bwd_scratch_floats(ctx, n, h, self.edge_dim or 0), 1),))
-        w_e = p.get("edge_weight")
-        D.resgated_bwd_targets(ctx, a, pk, dy, dp.cols(0, h), scratch, ds=dp.cols(3 * h, w) if self.root_weight else None, e=e, w_e=w_e,
-                               dw_e=g.get("edge_weight"))
-        D.resgated_bwd_sources(ctx, a, pk, dy, dp.cols(h, 3 * h), e=e, w_e=w_e)
-        D.gemm_dw(ctx, x, dp, g["weight"])                                          # dW_k | dW_q | dW_v | dW_s = x^T dP
-        D.act_bias_grad(ctx, dp.cols(0, 3 * h), None, dp.cols(0, 3 * h), None, db=g["lin_bias"])     # db_k | db_q | db_v: column sums
-        if not need_dx:
-            return None
-        dx = self._buf("dx", x.shape)
-        D.gemm_dx(ctx, dp, p["weight"], dx)                                         # dx = dP [W_k | W_q | W_v | W_s]^T
+        dx = self._buf("dx", x.shape) if need_dx else None
+        convs.resgated_backward(ctx, a, x, e, pk, dy, p["weight"], p.get("edge_weight"), g["weight"], g["lin_bias"], g.get("bias"),
+                                g.get("edge_weight"), dp, scratch, dx)
         return dx
 
 
@@ -1019,7 +960,8 @@ class TransformerConv(Layer):
     Initialisation as torch's Linear: U(+-1 / sqrt(fan_in)) for every weight and bias.
     ``backward(dy, need_dx=True)`` returns dx (None with need_dx=False) and leaves the gradients in ``grads``.
 
-    Launches (csrc/transformer.hip): gcnx_gemm, gcnx_transformer_aggregate forward; gcnx_transformer_beta_bwd (beta only),
+    Launches (transformer_forward / transformer_backward of gcnx/convs.py, which the model runs too; csrc/transformer.hip):
+    gcnx_gemm, gcnx_transformer_aggregate forward; gcnx_transformer_beta_bwd (beta only),
     gcnx_transformer_bwd_targets, gcnx_transformer_bwd_sources, gcnx_gemm_dw, gcnx_act_bias_grad, gcnx_gemm_dx backward.  There
     is no composed route: what the kernels do not serve (concat=False, attention dropout, bipartite inputs, beta without
     root_weight, shapes gcnx_transformer_conv_ok refuses) raises NotImplementedError."""
@@ -1184,9 +1126,8 @@ class TransformerConv(Layer):
         ctx, n, p = self.ctx, x.shape[0], self.params
         y = out if out is not None else self._buf("y", (n, hc))
         pk, o, alpha = self._buf("p", (n, w)), self._buf("o", (n, hc)), self._buf("alpha", (a.nnz, h))
-        D.gemm(ctx, x, self.lin_weight, self.lin_bias, pk)                          # Q | K | V | S
-        D.transformer_aggregate(ctx, a, pk, y, h, e=e, w_e=p.get("lin_edge.weight"), skip=pk.cols(3 * hc, w) if self.root_weight else None,
-                                w_beta=p.get("lin_beta.weight"), alpha=alpha, o_pre=o)
+        convs.transformer_forward(ctx, a, x, e, self.lin_weight, self.lin_bias, p.get("lin_edge.weight"), p.get("lin_beta.weight"), pk,
+                                  alpha, o, y, h)
         self._saved = (x, a, e, pk, alpha, o)
         return y
 
@@ -1196,21 +1137,11 @@ class TransformerConv(Layer):
         hc, w, ed = h * c, self._width(), self.edge_dim or 0
         dp, dscore = self._buf("dp", (n, w)), self._buf("dscore", (a.nnz, h))       # dQ | dK | dV | dS
         scratch = self._buf("scratch", (max(D.transformer_bwd_scratch_floats(ctx, n, h, c, ed, self.beta), 1),))
-        d_o, ds = dy, (dp.cols(3 * hc, w) if self.root_weight else None)
-        if self.beta:
-            d_o = self._buf("d_o", (n, hc))
-            D.transformer_beta_bwd(ctx, dy, o, pk.cols(3 * hc, w), p["lin_beta.weight"], d_o, ds, g["lin_beta.weight"], scratch)
-            ds = None
-        D.transformer_bwd_targets(ctx, a, pk, alpha, d_o, o, dscore, dp.cols(0, hc), h, scratch, ds=ds, e=e, w_e=p.get("lin_edge.weight"),
-                                  dw_e=g.get("lin_edge.weight"))
-        D.transformer_bwd_sources(ctx, a, pk, alpha, dscore, d_o, dp.cols(hc, 3 * hc), h)
-        D.gemm_dw(ctx, x, dp, self.lin_weight_grad)                                 # dW_q | dW_k | dW_v | dW_s = x^T dP
-        if self.use_bias:
-            D.act_bias_grad(ctx, dp, None, dp, None, db=self.lin_bias_grad)         # the four biases: column sums
-        if not need_dx:
-            return None
-        dx = self._buf("dx", x.shape)
-        D.gemm_dx(ctx, dp, self.lin_weight, dx)                                     # dx = dP [W_q | W_k | W_v | W_s]^T
+        d_o = self._buf("d_o", (n, hc)) if self.beta else None
+        dx = self._buf("dx", x.shape) if need_dx else None
+        convs.transformer_backward(ctx, a, x, e, pk, alpha, o, dy, self.lin_weight, p.get("lin_edge.weight"), p.get("lin_beta.weight"),
+                                   self.lin_weight_grad, self.lin_bias_grad, g.get("lin_edge.weight"), g.get("lin_beta.weight"), dp,
+                                   dscore, d_o, scratch, dx, h)
         return dx
 
 

@@ -43,6 +43,7 @@ import sys
 
 import numpy as np
 
+from . import convs
 from . import device as D
 from .layers import glorot_uniform
 from .loader import SparseTensor
@@ -1400,6 +1401,11 @@ def _with_mean_self_loops(a, e, n):
     return SparseTensor(idx[order], np.ones(order.size), (n, n)), e
 
 
+def _conv_keys(*names):
+    """{k: the names with the convolution's number k appended} -- formatted once per class: the conv hooks run every step."""
+    return {k: tuple(f"{name}{k}" for name in names) for k in (1, 2)}
+
+
 class GCN(_GraphRunner):
     """The reference's torch class ``GCN`` (src/utilities/gcn_utills.py:795-853), BASELINE config 1's topology:
 
@@ -1435,6 +1441,14 @@ class GCN(_GraphRunner):
                   ("batch_norm_4.weight", "g4", False), ("batch_norm_4.bias", "be4", False))
     PROBE_KEY = "conv1.lin.weight"       # the state_dict tensor whose second dimension is the input width
     EPS = D.TORCH_BN_EPS
+    # ---- what a subclass with another convolution sets (and the hooks _initial, _conv_fwd, _conv_bwd, _stack) -----------------
+    OPERATOR = "gcn"                     # _op: "gcn" | "mean" | "pattern" | "perm"
+    SELF_LOOPS = True                    # a host adjacency gets PyG's add_remaining_self_loops (False: used as stored)
+    LEADING_AXIS = ()                    # state_dict keys that carry a leading axis of 1 in PyG ([1, heads, C], [1, 3H])
+    KERNELS = "GCNConv"                  # the kernel family, as the constructor's messages name it
+    HEAD_NOTE = "the one-workgroup head"
+    edge_dim = None
+    _KEYS = _conv_keys("w", "b", "z")
 
     def __init__(self, *args, **kw):
         """GCN([ctx,] hidden_channels=64, num_classes=1, seed=0): the reference's constructor behind an optional ctx."""
@@ -1443,6 +1457,28 @@ class GCN(_GraphRunner):
         else:
             ctx = kw.pop("ctx", None)
         self._init(ctx, *args, **kw)
+
+    @property
+    def _name(self):
+        return "gcnx." + type(self).__name__
+
+    def _check_heads(self, h, heads):
+        """The heads / hidden_channels pairs the attention kernels serve."""
+        if heads not in (1, 2, 4, 8) or h % heads != 0:
+            raise NotImplementedError(f"{self._name}: heads={heads} must be 1, 2, 4 or 8 and divide hidden_channels={h}")
+        if h not in (16, 32, 64, 128) or h // heads < 4:
+            raise NotImplementedError(f"{self._name}: hidden_channels={h} must be 16, 32, 64 or 128 with at least 4 channels per head "
+                                      f"(the widths the {self.KERNELS} kernels serve; there is no composed route)")
+
+    def _check_edge_dim(self, edge_dim):
+        """edge_dim as the model keeps it: None or an int in 1 .. 8."""
+        if edge_dim is not None and not 1 <= int(edge_dim) <= 8:
+            raise NotImplementedError(f"{self._name}: edge_dim={edge_dim} must be None or 1 .. 8 (what the {self.KERNELS} kernels serve)")
+        return None if edge_dim is None else int(edge_dim)
+
+    def _one_device(self, comm):
+        if comm is not None:
+            raise NotImplementedError(f"{self._name} runs on one device (comm is not supported)")
 
     def _init(self, ctx, hidden_channels=64, num_classes=1, seed=0, comm=None):
         if int(num_classes) != 1:
@@ -1472,42 +1508,77 @@ class GCN(_GraphRunner):
         return s
 
     def build(self, f_in):
-        h = self.hidden
-        if h > 256:
-            raise NotImplementedError("gcnx.GCN: hidden_channels <= 256 (the one-workgroup head)")
+        if self.hidden > 256:
+            raise NotImplementedError(f"{self._name}: hidden_channels <= 256 ({self.HEAD_NOTE})")
         shapes = self._shapes(f_in)
         self.f_in = int(f_in)
-        # every parameter starts on a 16-byte boundary (the one-launch GCNConv reads W and b as float4); the padding
-        # floats have zero gradients, so the single SGD launch over the whole buffer leaves them at zero
-        self._alloc_flat([(k, shapes[k]) for k in self.PARAM_ORDER], align=4)
-        rng, lim = self._rng, 1.0 / np.sqrt(h)
-        init = {"w1": glorot_uniform(rng, f_in, h), "w2": glorot_uniform(rng, h, h),
-                "w3": rng.uniform(-lim, lim, (h, h)), "b3": rng.uniform(-lim, lim, h),
-                "w4": rng.uniform(-lim, lim, (1, h)), "b4": rng.uniform(-lim, lim, 1)}
-        for k in ("g1", "g2", "g3", "g4"):
-            init[k] = np.ones(shapes[k])
-        for k in ("a1", "a2", "a3", "a4"):
-            init[k] = np.full(1, 0.25)
-        for k, v in init.items():
+        # every parameter starts on a 16-byte boundary (the kernels read the weights, biases and attention vectors as float4);
+        # the padding floats have zero gradients, so the single update launch over the whole buffer leaves them at zero
+        offs = self._alloc_flat([(k, shapes[k]) for k in self.PARAM_ORDER], align=4)
+        for k, v in self._initial(f_in, shapes, offs).items():
             self.p[k].copy_from_host(np.asarray(v, np.float32))
         self.built = True
 
+    def _initial(self, f_in, shapes, offs):
+        """{key: initial value}, drawn from self._rng in the model's own fixed order (what ``seed`` means); a subclass also
+        makes its named views of stacked tensors here."""
+        h, rng = self.hidden, self._rng
+        return {"w1": glorot_uniform(rng, f_in, h), "w2": glorot_uniform(rng, h, h), **self._head_initial(shapes)}
+
+    def _uniform(self, fan_in, *shape):
+        """torch's Linear initialisation: U(+-1 / sqrt(fan_in))."""
+        lim = 1.0 / np.sqrt(fan_in)
+        return self._rng.uniform(-lim, lim, shape)
+
+    def _head_initial(self, shapes):
+        """What every model has behind its convolutions: the head's two Linears, drawn w3, b3, w4, b4 at the point of the model's
+        draw order where it calls this; every BatchNorm weight 1, every PReLU slope 0.25."""
+        h, u = self.hidden, self._uniform
+        init = {"w3": u(h, h, h), "b3": u(h, h), "w4": u(h, 1, h), "b4": u(h, 1)}
+        init.update({k: np.ones(shapes[k]) for k in ("g1", "g2", "g3", "g4")})
+        init.update({k: np.full(1, 0.25) for k in ("a1", "a2", "a3", "a4")})
+        return init
+
+    def _named(self, t):
+        d = {tk: (t[k].numpy().T.copy() if tr else t[k].numpy()) for tk, k, tr in self.TORCH_KEYS}
+        d.update({tk: d[tk][None] for tk in self.LEADING_AXIS})
+        return d
+
     def state_dict(self):
         """{torch key: array in torch's layout}: conv*.lin.weight [out, in], linear_*.weight [out, in], prelu_*.weight [1]."""
-        return {tk: (self.p[k].numpy().T.copy() if tr else self.p[k].numpy()) for tk, k, tr in self.TORCH_KEYS}
+        return self._named(self.p)
+
+    def _probe_f_in(self, d):
+        return int(np.asarray(d[self.PROBE_KEY]).shape[1])
+
+    def _host_state(self, d):
+        """The checked {internal key: array in the stored layout} of a state dict (builds the model if needed): every key
+        present, weights transposed, the leading axis of LEADING_AXIS keys dropped, every shape that of its view."""
+        if not self.built:
+            self.build(self._probe_f_in(d))
+        missing = [tk for tk, _, _ in self.TORCH_KEYS if tk not in d]
+        if missing:
+            raise KeyError(f"{self._name}.load_state_dict: missing {missing}")
+        host = {}
+        for tk, k, tr in self.TORCH_KEYS:
+            v = np.asarray(d[tk], np.float32)
+            if tk in self.LEADING_AXIS and v.ndim == len(self.p[k].shape) + 1 and v.shape[0] == 1:
+                v = v[0]
+            v = self._node_block(tk, k, v.T if tr else v, host)
+            if v.shape != self.p[k].shape:
+                raise ValueError(f"{tk}: shape {np.asarray(d[tk]).shape} does not fit this model")
+            host[k] = v
+        return host
+
+    def _node_block(self, tk, k, v, host):
+        return v                          # (ResGated splits the edge block of a [in + D, H] tensor off into ``host``)
+
+    def _stack(self, host):
+        return host                       # (the models that store stacked tensors concatenate their named blocks)
 
     def load_state_dict(self, d):
         """Inverse of state_dict (a converted torch checkpoint: tensors as NumPy arrays).  Builds the model if needed."""
-        if not self.built:
-            self.build(int(np.asarray(d[self.PROBE_KEY]).shape[1]))
-        missing = [tk for tk, _, _ in self.TORCH_KEYS if tk not in d]
-        if missing:
-            raise KeyError(f"gcnx.GCN.load_state_dict: missing {missing}")
-        for tk, k, tr in self.TORCH_KEYS:
-            v = np.asarray(d[tk], np.float32)
-            v = v.T if tr else v
-            if v.shape != self.p[k].shape:
-                raise ValueError(f"{tk}: shape {np.asarray(d[tk]).shape} does not fit this model")
+        for k, v in self._stack(self._host_state(d)).items():
             self.p[k].copy_from_host(np.ascontiguousarray(v))
 
     def get_weights(self):
@@ -1520,7 +1591,7 @@ class GCN(_GraphRunner):
 
     def gradients(self):
         """{torch key: gradient of the last loss_and_grads / train_step} in torch's layouts."""
-        return {tk: (self.g[k].numpy().T.copy() if tr else self.g[k].numpy()) for tk, k, tr in self.TORCH_KEYS}
+        return self._named(self.g)
 
     @property
     def trainable_variables(self):
@@ -1529,16 +1600,44 @@ class GCN(_GraphRunner):
     # ---- batches ------------------------------------------------------------------------------------------------------
     def _as_batch(self, inputs, target=None):
         if not isinstance(inputs, DeviceBatch):
+            if self.uses_edge_features and len(inputs) != 4:
+                raise ValueError(f"{self._name}(edge_dim={self.edge_dim}) takes (x, a, e, i): build the graphs with edge features "
+                                 "(Graph(e=...), from_networkx(use_edge_data='entries'))")
+            inputs = self._host_inputs(inputs)
+        batch = self._adopt(inputs, target, weighted=False)
+        if self.uses_edge_features and batch.e is None:
+            raise ValueError(f"{self._name}: the batch carries no edge features (DeviceBatch.e)")
+        return batch
+
+    def _host_inputs(self, inputs):
+        """Host inputs as from_host takes them.  SELF_LOOPS: a host matrix gets PyG's add_remaining_self_loops; otherwise the
+        adjacency (and e) go in as stored, no loop added or removed."""
+        if self.SELF_LOOPS:
             x, a, i = _without_e(inputs)
-            if not isinstance(a, D.DeviceCSR):                   # a host matrix: PyG's add_remaining_self_loops
+            if not isinstance(a, D.DeviceCSR):
                 inputs = (x, _with_remaining_self_loops(a, np.asarray(x).shape[0]), i)
-        return self._adopt(inputs, target, weighted=False)
+        return inputs
+
+    def _check_e(self, batch):
+        d = self.edge_dim or 0
+        if d and (batch.e is None or batch.e.shape != (batch.a.nnz, d)):
+            raise ValueError(f"{self._name}(edge_dim={d}): the batch's edge features must be [{batch.a.nnz}, {d}], got "
+                             f"{None if batch.e is None else list(batch.e.shape)}")
 
     def _op(self, batch):
-        """A^ = D^-1/2 (A + I_missing) D^-1/2 of the batch, values ignored (built once per batch object)."""
+        """The operator of the batch's unweighted pattern and what the backward walks, built once per batch object.  OPERATOR:
+        "gcn": A^ = D^-1/2 (A + I_missing) D^-1/2 and its transpose; "mean": the row-mean operator and its transpose; "pattern":
+        the pattern and its transpose; "perm": the pattern twice -- the backward walks its transposed pattern through the entry
+        permutation (DeviceCSR.transpose_perm: the one a device loader's batch arrives with, or built here)."""
         if self._op_cache is None or self._op_cache[0] != batch.uid:
-            a_hat = batch.a.unweighted().gcn_norm("pyg")
-            self._op_cache = (batch.uid, a_hat, a_hat.transpose())
+            a, kind = batch.a.unweighted(), self.OPERATOR
+            if kind == "perm":
+                a.transpose_perm()
+                a_t = a
+            else:
+                a = a.gcn_norm("pyg") if kind == "gcn" else a.row_mean() if kind == "mean" else a
+                a_t = a.transpose()
+            self._op_cache = (batch.uid, a, a_t)
         return self._op_cache[1], self._op_cache[2]
 
     def _global_counts(self, batch):
@@ -1596,35 +1695,43 @@ class GCN(_GraphRunner):
         D.spmm(ctx, a_hat, h_tmp, bias, out)
         return False
 
-    # the two convolutions of the forward and their backward segments: what a subclass with another convolution replaces
-    def _conv1(self, a_hat, batch, bufs, mode):
-        p = self.p
-        self._conv(a_hat, batch.x, p["w1"], p["b1"], bufs["z1"], bufs["h1"])
+    # the two convolutions of the forward and their backward segments, in terms of the two hooks a subclass with another
+    # convolution replaces: conv k reads x and writes bufs["z{k}"]; its backward reads dzk = bufs["dz{k}"] and writes dx if given
+    def _conv1(self, a, batch, bufs, mode):
+        bufs["e"] = batch.e if self.uses_edge_features else None                    # (conv2 and the backward read the same rows)
+        self._conv_fwd(a, batch.x, 1, bufs, mode == "grads")
 
-    def _conv2(self, a_hat, bufs, mode):
-        p = self.p
-        bufs["s2_ok"] = self._conv(a_hat, bufs["y1"], p["w2"], p["b2"], bufs["z2"], bufs["h1"],
-                                   s=bufs["s2"] if mode == "grads" else None)
+    def _conv2(self, a, bufs, mode):
+        self._conv_fwd(a, bufs["y1"], 2, bufs, mode == "grads")
 
     def _conv2_bwd(self, a_t, bufs):
         """dZ2 -> conv2's gradients and dY1."""
-        ctx, p, g = self.ctx, self.p, self.g
-        D.act_bias_grad(ctx, bufs["dz2"], None, bufs["dz2"], None, db=g["b2"])       # conv2.bias: column sums of dZ2
-        if bufs["s2_ok"]:                                   # forward was (A^ Y1) W2: the association of GCNConv.backward
-            D.gemm_dw(ctx, bufs["s2"], bufs["dz2"], g["w2"])                        # dW2 = S2^T dZ2
-            D.gemm_dx(ctx, bufs["dz2"], p["w2"], bufs["t"])                         # dZ2 W2^T
-            D.spmm(ctx, a_t, bufs["t"], None, bufs["dy1"])                          # dY1 = A^T (dZ2 W2^T)
-        else:
-            D.spmm(ctx, a_t, bufs["dz2"], None, bufs["t"])                          # A^T dZ2
-            D.gemm_dw(ctx, bufs["y1"], bufs["t"], g["w2"])                          # dW2 = Y1^T (A^T dZ2)
-            D.gemm_dx(ctx, bufs["t"], p["w2"], bufs["dy1"])                         # dY1 = (A^T dZ2) W2^T
+        self._conv_bwd(a_t, bufs["y1"], 2, bufs["dz2"], bufs, bufs["dy1"])
 
     def _conv1_bwd(self, a_t, batch, bufs):
         """dZ1 -> conv1's gradients (the input carries no gradient)."""
-        ctx, g = self.ctx, self.g
-        D.act_bias_grad(ctx, bufs["dz1"], None, bufs["dz1"], None, db=g["b1"])
-        D.spmm(ctx, a_t, bufs["dz1"], None, bufs["t"])
-        D.gemm_dw(ctx, batch.x, bufs["t"], g["w1"])
+        self._conv_bwd(a_t, batch.x, 1, bufs["dz1"], bufs, None)
+
+    def _conv_fwd(self, a_hat, x, k, bufs, keep):
+        p = self.p
+        w, b, z = self._KEYS[k]
+        ok = self._conv(a_hat, x, p[w], p[b], bufs[z], bufs["h1"], s=bufs["s2"] if keep and k == 2 else None)
+        if k == 2:
+            bufs["s2_ok"] = ok
+
+    def _conv_bwd(self, a_t, x, k, dzk, bufs, dx):
+        ctx, p, g = self.ctx, self.p, self.g
+        w, b, _ = self._KEYS[k]
+        D.act_bias_grad(ctx, dzk, None, dzk, None, db=g[b])                          # conv_k.bias: column sums of dZ_k
+        if dx is not None and bufs["s2_ok"]:                # forward was (A^ Y1) W2: the association of GCNConv.backward
+            D.gemm_dw(ctx, bufs["s2"], dzk, g["w2"])                                # dW2 = S2^T dZ2
+            D.gemm_dx(ctx, dzk, p["w2"], bufs["t"])                                 # dZ2 W2^T
+            D.spmm(ctx, a_t, bufs["t"], None, dx)                                   # dY1 = A^T (dZ2 W2^T)
+            return
+        D.spmm(ctx, a_t, dzk, None, bufs["t"])                                      # A^T dZ_k
+        D.gemm_dw(ctx, x, bufs["t"], g[w])                                          # dW_k = x^T (A^T dZ_k)
+        if dx is not None:
+            D.gemm_dx(ctx, bufs["t"], p[w], dx)                                     # dY1 = (A^T dZ2) W2^T
 
     def _moments(self, z, mean, inv, bufs, counts):
         """Training-mode BatchNorm statistics over the rows of z; with counts (sync-BN) over every rank's rows: the two moment
@@ -1788,6 +1895,8 @@ class SAGE(GCN):
                   ("conv2.lin_l.weight", "wl2", True), ("conv2.lin_l.bias", "b2", False), ("conv2.lin_r.weight", "wr2", True)) + \
         GCN.TORCH_KEYS[4:]
     PROBE_KEY = "conv1.lin_l.weight"
+    OPERATOR, SELF_LOOPS, KERNELS = "mean", False, "SAGEConv"
+    _KEYS = _conv_keys("wl", "wr", "b", "z", "s")
 
     def _init(self, ctx, hidden_channels=64, num_classes=1, seed=0, comm=None):
         super()._init(ctx, hidden_channels, num_classes, seed, comm)
@@ -1800,37 +1909,10 @@ class SAGE(GCN):
         s.update(wl1=(f_in, h), wr1=(f_in, h), wl2=(h, h), wr2=(h, h))
         return s
 
-    def build(self, f_in):
-        h = self.hidden
-        if h > 256:
-            raise NotImplementedError("gcnx.SAGE: hidden_channels <= 256 (the one-workgroup head)")
-        shapes = self._shapes(f_in)
-        self.f_in = int(f_in)
-        # every parameter starts on a 16-byte boundary (gcnx_sage_conv needs its weights there); the padding floats have zero
-        # gradients, so the single SGD launch over the whole buffer leaves them at zero
-        self._alloc_flat([(k, shapes[k]) for k in self.PARAM_ORDER], align=4)
-        rng = self._rng
-        u = lambda fan_in, *s: rng.uniform(-1.0 / np.sqrt(fan_in), 1.0 / np.sqrt(fan_in), s)
-        init = {"wl1": u(f_in, f_in, h), "b1": u(f_in, h), "wr1": u(f_in, f_in, h),
-                "wl2": u(h, h, h), "b2": u(h, h), "wr2": u(h, h, h),
-                "w3": u(h, h, h), "b3": u(h, h), "w4": u(h, 1, h), "b4": u(h, 1)}
-        for k in ("g1", "g2", "g3", "g4"):
-            init[k] = np.ones(shapes[k])
-        for k in ("a1", "a2", "a3", "a4"):
-            init[k] = np.full(1, 0.25)
-        for k, v in init.items():
-            self.p[k].copy_from_host(np.asarray(v, np.float32))
-        self.built = True
-
-    def _as_batch(self, inputs, target=None):
-        return self._adopt(inputs, target, weighted=False)       # the adjacency as stored: no loops added
-
-    def _op(self, batch):
-        """The row-mean operator of the batch and its transpose (built once per batch object)."""
-        if self._op_cache is None or self._op_cache[0] != batch.uid:
-            a_mean = batch.a.unweighted().row_mean()
-            self._op_cache = (batch.uid, a_mean, a_mean.transpose())
-        return self._op_cache[1], self._op_cache[2]
+    def _initial(self, f_in, shapes, offs):
+        h, u = self.hidden, self._uniform
+        return {"wl1": u(f_in, f_in, h), "b1": u(f_in, h), "wr1": u(f_in, f_in, h),
+                "wl2": u(h, h, h), "b2": u(h, h), "wr2": u(h, h, h), **self._head_initial(shapes)}
 
     def _ensure(self, batch, sharded=False):
         bufs = super()._ensure(batch, sharded)
@@ -1842,44 +1924,33 @@ class SAGE(GCN):
         return (self._fused and D.sage_conv_ok(self.ctx, x.shape[0], x.shape[1], fo, x.ld)
                 and all(a.ptr % 16 == 0 for a in (x,) + others))
 
-    def _conv(self, a_mean, x, w_nb, w_root, bias, out, s, h_tmp):
-        """out = (A x) W_nb + x W_root + b, s = A x (the operand of dW_nb): one launch, or the composed route."""
-        ctx = self.ctx
+    def _conv_fwd(self, a_mean, x, k, bufs, keep):
+        """z_k = (A x) W_l + x W_r + b, s_k = A x (the operand of dW_l): one launch, or the composed route."""
+        ctx, p = self.ctx, self.p
+        wl, wr, b, z, s = self._KEYS[k]
+        w_nb, w_root, bias, out, s = p[wl], p[wr], p[b], bufs[z], bufs[s]
         if self._one_launch(x, w_nb.shape[1], out, s):
             D.sage_conv(ctx, a_mean, x, w_nb, w_root, bias, out, s=s)
             return
         D.spmm(ctx, a_mean, x, None, s)
         D.gemm(ctx, s, w_nb, bias, out)
-        D.gemm(ctx, x, w_root, None, h_tmp)
-        D.add(ctx, out, h_tmp, out)
+        D.gemm(ctx, x, w_root, None, bufs["h1"])
+        D.add(ctx, out, bufs["h1"], out)
 
-    def _conv1(self, a_mean, batch, bufs, mode):
-        p = self.p
-        self._conv(a_mean, batch.x, p["wl1"], p["wr1"], p["b1"], bufs["z1"], bufs["s1"], bufs["h1"])
-
-    def _conv2(self, a_mean, bufs, mode):
-        p = self.p
-        self._conv(a_mean, bufs["y1"], p["wl2"], p["wr2"], p["b2"], bufs["z2"], bufs["s2"], bufs["h1"])
-
-    def _conv2_bwd(self, a_t, bufs):
-        """dZ2 -> conv2's gradients and dY1 = (A^T dZ2) W_l2^T + dZ2 W_r2^T."""
+    def _conv_bwd(self, a_t, x, k, dzk, bufs, dx):
+        """dZ_k -> conv k's gradients and, with dx, dx = (A^T dZ_k) W_l^T + dZ_k W_r^T."""
         ctx, p, g = self.ctx, self.p, self.g
-        dz2 = bufs["dz2"]
-        D.act_bias_grad(ctx, dz2, None, dz2, None, db=g["b2"])                      # conv2.lin_l.bias: column sums of dZ2
-        D.gemm_dw2(ctx, bufs["s2"], dz2, g["wl2"], bufs["y1"], dz2, g["wr2"])        # dW_l2 = S2^T dZ2, dW_r2 = Y1^T dZ2
-        if self._one_launch(dz2, self.hidden, bufs["dy1"]):
-            D.sage_conv(ctx, a_t, dz2, p["wl2"], p["wr2"], None, bufs["dy1"], w_transposed=True)
+        wl, wr, b, _, s = self._KEYS[k]
+        D.act_bias_grad(ctx, dzk, None, dzk, None, db=g[b])                          # conv_k.lin_l.bias: column sums of dZ_k
+        D.gemm_dw2(ctx, bufs[s], dzk, g[wl], x, dzk, g[wr])                          # dW_l = S_k^T dZ_k, dW_r = x^T dZ_k
+        if dx is None:
             return
-        D.gemm_dx(ctx, dz2, p["wl2"], bufs["t"])
-        D.spmm(ctx, a_t, bufs["t"], None, bufs["dy1"])
-        D.gemm_dx(ctx, dz2, p["wr2"], bufs["dy1"], accumulate=True)
-
-    def _conv1_bwd(self, a_t, batch, bufs):
-        """dZ1 -> conv1's gradients (the input carries no gradient)."""
-        ctx, g = self.ctx, self.g
-        dz1 = bufs["dz1"]
-        D.act_bias_grad(ctx, dz1, None, dz1, None, db=g["b1"])
-        D.gemm_dw2(ctx, bufs["s1"], dz1, g["wl1"], batch.x, dz1, g["wr1"])           # dW_l1 = S1^T dZ1, dW_r1 = x^T dZ1
+        if self._one_launch(dzk, self.hidden, dx):
+            D.sage_conv(ctx, a_t, dzk, p[wl], p[wr], None, dx, w_transposed=True)
+            return
+        D.gemm_dx(ctx, dzk, p[wl], bufs["t"])
+        D.spmm(ctx, a_t, bufs["t"], None, dx)
+        D.gemm_dx(ctx, dzk, p[wr], dx, accumulate=True)
 
 
 class GIN(GCN):
@@ -1910,6 +1981,8 @@ class GIN(GCN):
     torch_geometric: prefer the named dicts."""
 
     PROBE_KEY = "conv1.nn.0.weight"
+    OPERATOR, SELF_LOOPS, KERNELS = "pattern", False, "GINConv"
+    _KEYS = _conv_keys("wa", "ba", "wb", "bb", "z", "t", "u", "dt", "e")
 
     def _init(self, ctx, hidden_channels=64, train_eps=False, num_classes=1, seed=0, comm=None):
         super()._init(ctx, hidden_channels, num_classes, seed, comm)
@@ -1932,29 +2005,12 @@ class GIN(GCN):
         s.update(e1=(1,), e2=(1,), wa1=(f_in, h), wb1=(h, h), wa2=(h, h), wb2=(h, h), ba1=(h,), bb1=(h,), ba2=(h,), bb2=(h,))
         return s
 
-    def build(self, f_in):
-        h = self.hidden
-        if h > 256:
-            raise NotImplementedError("gcnx.GIN: hidden_channels <= 256 (the one-workgroup head)")
-        shapes = self._shapes(f_in)
-        self.f_in = int(f_in)
-        # every parameter starts on a 16-byte boundary (gcnx_gin_conv needs its weights there); the padding floats have zero
-        # gradients, so the single SGD launch over the whole buffer leaves them at zero
-        self._alloc_flat([(k, shapes[k]) for k in self.PARAM_ORDER], align=4)
+    def _initial(self, f_in, shapes, offs):
         if not self.train_eps:                  # eps stays a device scalar (a loaded checkpoint may carry a value), outside the
             self._eps_fixed = self.ctx.zeros(8)                       # flat buffers: no gradient, no update
-        rng = self._rng
-        u = lambda fan_in, *s: rng.uniform(-1.0 / np.sqrt(fan_in), 1.0 / np.sqrt(fan_in), s)
-        init = {"wa1": u(f_in, f_in, h), "ba1": u(f_in, h), "wb1": u(h, h, h), "bb1": u(h, h),
-                "wa2": u(h, h, h), "ba2": u(h, h), "wb2": u(h, h, h), "bb2": u(h, h),
-                "w3": u(h, h, h), "b3": u(h, h), "w4": u(h, 1, h), "b4": u(h, 1)}
-        for k in ("g1", "g2", "g3", "g4"):
-            init[k] = np.ones(shapes[k])
-        for k in ("a1", "a2", "a3", "a4"):
-            init[k] = np.full(1, 0.25)
-        for k, v in init.items():
-            self.p[k].copy_from_host(np.asarray(v, np.float32))
-        self.built = True
+        h, u = self.hidden, self._uniform
+        return {"wa1": u(f_in, f_in, h), "ba1": u(f_in, h), "wb1": u(h, h, h), "bb1": u(h, h),
+                "wa2": u(h, h, h), "ba2": u(h, h), "wb2": u(h, h, h), "bb2": u(h, h), **self._head_initial(shapes)}
 
     def _eps(self, k):
         """conv k's eps as a device array of one float: a parameter with train_eps, a constant otherwise."""
@@ -1978,25 +2034,16 @@ class GIN(GCN):
         if not self.train_eps:
             missing = [tk for tk, _, _ in self.EPS_KEYS if tk not in d]
             if missing:
-                raise KeyError(f"gcnx.GIN.load_state_dict: missing {missing}")
+                raise KeyError(f"{self._name}.load_state_dict: missing {missing}")
             for tk, k, _ in self.EPS_KEYS:
                 self._eps(int(k[1])).copy_from_host(np.asarray(d[tk], np.float32).reshape(1))
-
-    def _as_batch(self, inputs, target=None):
-        return self._adopt(inputs, target, weighted=False)       # the adjacency as stored: no loops added
-
-    def _op(self, batch):
-        """The unweighted pattern of the batch and its transpose (built once per batch object)."""
-        if self._op_cache is None or self._op_cache[0] != batch.uid:
-            a = batch.a.unweighted()
-            self._op_cache = (batch.uid, a, a.transpose())
-        return self._op_cache[1], self._op_cache[2]
 
     def _ensure(self, batch, sharded=False):
         bufs = super()._ensure(batch, sharded)
         if "t1" not in bufs:
             v, n, h = self._views(), batch.n, self.hidden
             bufs["t1"], bufs["u1"], bufs["u2"] = v("t1", n, batch.f), v("u1", n, h), v("u2", n, h)
+            bufs["t2"], bufs["dt2"] = bufs["s2"], bufs["t"]             # (conv2's T and dT in the base class's buffers)
             if self.train_eps:
                 bufs["dt1"] = v("dt1", n, batch.f)
                 np_ = D.gin_eps_grad_parts(n)
@@ -2007,12 +2054,13 @@ class GIN(GCN):
         return (self._fused and D.gin_conv_ok(self.ctx, x.shape[0], x.shape[1], k1, k2, x.ld)
                 and all(a.ptr % 16 == 0 and a.ld % 4 == 0 for a in (x,) + others))
 
-    def _conv(self, a, x, k, out, t, u, keep):
-        """out = relu(T W_a + b_a) W_b + b_b, T = (1 + eps) x + A x: one launch, or the composed route.  t and u: room for T and
-        the ReLU output (the operands of the weight gradients, and the mask), which the one launch stores only with ``keep``
+    def _conv_fwd(self, a, x, k, bufs, keep):
+        """z_k = relu(T W_a + b_a) W_b + b_b, T = (1 + eps) x + A x: one launch, or the composed route.  t_k and u_k: room for T
+        and the ReLU output (the operands of the weight gradients, and the mask), which the one launch stores only with ``keep``
         (a step that goes on to the gradients); the composed route passes through them either way."""
         ctx, p = self.ctx, self.p
-        wa, ba, wb, bb = p[f"wa{k}"], p[f"ba{k}"], p[f"wb{k}"], p[f"bb{k}"]
+        wa, ba, wb, bb, z, t, u, _, _ = self._KEYS[k]
+        wa, ba, wb, bb, out, t, u = p[wa], p[ba], p[wb], p[bb], bufs[z], bufs[t], bufs[u]
         if self._one_launch(x, wa.shape[1], wb.shape[1], out, t, u):
             D.gin_conv(ctx, a, x, self._eps(k), wa, ba, wb, bb, out, t=t if keep else None, u=u if keep else None)
             return
@@ -2020,39 +2068,27 @@ class GIN(GCN):
         D.gemm(ctx, t, wa, ba, u, act="relu")
         D.gemm(ctx, u, wb, bb, out)
 
-    def _conv_bwd(self, a_t, x, k, dz, t, u, bufs, dx, dt):
-        """dZ_k -> conv k's gradients and, with dx, the gradient of its input.  dt: room for dT = dU W_a^T (train_eps, or the
+    def _conv_bwd(self, a_t, x, k, dz, bufs, dx):
+        """dZ_k -> conv k's gradients and, with dx, the gradient of its input.  dt_k: room for dT = dU W_a^T (train_eps, or the
         composed dX)."""
         ctx, p, g = self.ctx, self.p, self.g
+        wa, ba, wb, bb, _, t, u, dt, e = self._KEYS[k]
+        t, u, dt = bufs[t], bufs[u], bufs.get(dt)
         du = bufs["h1"]                                                             # (forward scratch of the base class: free here)
-        D.act_bias_grad(ctx, dz, None, dz, None, db=g[f"bb{k}"])                     # db_b: column sums of dZ
-        D.gemm_dx(ctx, dz, p[f"wb{k}"], du, y_mask=u, db=g[f"ba{k}"])                # dU = (dZ W_b^T) * [U > 0], db_a
-        D.gemm_dw2(ctx, u, dz, g[f"wb{k}"], t, du, g[f"wa{k}"])                      # dW_b = U^T dZ, dW_a = T^T dU
+        D.act_bias_grad(ctx, dz, None, dz, None, db=g[bb])                           # db_b: column sums of dZ
+        D.gemm_dx(ctx, dz, p[wb], du, y_mask=u, db=g[ba])                            # dU = (dZ W_b^T) * [U > 0], db_a
+        D.gemm_dw2(ctx, u, dz, g[wb], t, du, g[wa])                                  # dW_b = U^T dZ, dW_a = T^T dU
         if self.train_eps:
-            D.gemm_dx(ctx, du, p[f"wa{k}"], dt)                                     # dT = dU W_a^T
-            D.gin_eps_grad(ctx, x, dt, bufs["eps_parts"], g[f"e{k}"])                # d eps = sum <x, dT>
+            D.gemm_dx(ctx, du, p[wa], dt)                                           # dT = dU W_a^T
+            D.gin_eps_grad(ctx, x, dt, bufs["eps_parts"], g[e])                      # d eps = sum <x, dT>
             if dx is not None:
                 D.gin_aggregate(ctx, a_t, dt, self._eps(k), dx)                     # dX = (1 + eps) dT + A^T dT
         elif dx is not None:
             if self._one_launch(du, x.shape[1], 0, dx):
-                D.gin_conv(ctx, a_t, du, self._eps(k), p[f"wa{k}"], None, None, None, dx, w_transposed=True)
+                D.gin_conv(ctx, a_t, du, self._eps(k), p[wa], None, None, None, dx, w_transposed=True)
                 return
-            D.gemm_dx(ctx, du, p[f"wa{k}"], dt)
+            D.gemm_dx(ctx, du, p[wa], dt)
             D.gin_aggregate(ctx, a_t, dt, self._eps(k), dx)
-
-    def _conv1(self, a, batch, bufs, mode):
-        self._conv(a, batch.x, 1, bufs["z1"], bufs["t1"], bufs["u1"], mode == "grads")
-
-    def _conv2(self, a, bufs, mode):
-        self._conv(a, bufs["y1"], 2, bufs["z2"], bufs["s2"], bufs["u2"], mode == "grads")
-
-    def _conv2_bwd(self, a_t, bufs):
-        """dZ2 -> conv2's gradients and dY1."""
-        self._conv_bwd(a_t, bufs["y1"], 2, bufs["dz2"], bufs["s2"], bufs["u2"], bufs, bufs["dy1"], bufs["t"])
-
-    def _conv1_bwd(self, a_t, batch, bufs):
-        """dZ1 -> conv1's gradients (the input carries no gradient)."""
-        self._conv_bwd(a_t, batch.x, 1, bufs["dz1"], bufs["t1"], bufs["u1"], bufs, None, bufs.get("dt1"))
 
 
 class PNA(GCN):
@@ -2070,7 +2106,8 @@ class PNA(GCN):
     Everything behind the convolutions is ``GCN``'s: BN·PReLU, the fused max-pool pair, the one-launch BCE head, sync-BN over
     shards (``comm=``), ``set_optimizer``, ``fit``.
 
-    Hot path per convolution: gcnx_gemm twice (P | Q), gcnx_pna_aggregate (csrc/pna.hip: one gather for the four statistics
+    Hot path per convolution (pna_forward / pna_backward of gcnx/convs.py, the one place the sequence is written; gcnx.PNAConv
+    runs the same two functions): gcnx_gemm twice (P | Q), gcnx_pna_aggregate (csrc/pna.hip: one gather for the four statistics
     and all 13 blocks of C; the statistics are stored only in a step that computes gradients), gcnx_gemm twice; backward
     gcnx_act_bias_grad, gcnx_gemm_dx, gcnx_gemm_dw2, gcnx_gemm_dx, gcnx_pna_bwd, gcnx_act_bias_grad, gcnx_gemm_dw2, and for
     conv2's dY1 = dC[:, :H] + [dP | dQ] W_pre^T two gcnx_gemm_dx and a gcnx_add.  The 13 H wide products go through the
@@ -2085,6 +2122,9 @@ class PNA(GCN):
     torch_geometric: prefer the named dicts."""
 
     PROBE_KEY = None                      # no tensor has the input width second: load_state_dict reads pre_nns.0.0.weight [F, 2F]
+    OPERATOR, SELF_LOOPS, KERNELS = "pattern", False, "PNAConv"
+    HEAD_NOTE = "the one-workgroup head; the 13 H wide products themselves go through the general GEMM kernels"
+    _KEYS = _conv_keys("wpre", "bpre", "wpost", "bpost", "wlin", "blin", "pq", "c", "st", "tc", "z", "dc", "dpq", "coef")
 
     def _init(self, ctx, hidden_channels=64, deg=None, avg_deg_log=None, num_classes=1, seed=0, comm=None, **pna_options):
         from .layers import pna_delta, pna_refuse
@@ -2123,30 +2163,14 @@ class PNA(GCN):
                  wpre2=(2 * h, h), bpre2=(h,), wpost2=(13 * h, h), bpost2=(h,), wlin2=(h, h), blin2=(h,))
         return s
 
-    def build(self, f_in):
-        h = self.hidden
-        if h > 256:
-            raise NotImplementedError("gcnx.PNA: hidden_channels <= 256 (the one-workgroup head; the 13 H wide products "
-                                      "themselves go through the general GEMM kernels)")
-        shapes = self._shapes(f_in)
-        self.f_in = int(f_in)
-        # every parameter starts on a 16-byte boundary (float4 lanes of the GEMMs and of the dW reductions); the padding floats
-        # have zero gradients, so the single SGD launch over the whole buffer leaves them at zero
-        self._alloc_flat([(k, shapes[k]) for k in self.PARAM_ORDER], align=4)
-        rng = self._rng
-        u = lambda fan_in, *s: rng.uniform(-1.0 / np.sqrt(fan_in), 1.0 / np.sqrt(fan_in), s)
-        init = {"w3": u(h, h, h), "b3": u(h, h), "w4": u(h, 1, h), "b4": u(h, 1)}
+    def _initial(self, f_in, shapes, offs):
+        h, u = self.hidden, self._uniform
+        init = self._head_initial(shapes)
         for k, f in ((1, f_in), (2, h)):
             init[f"wpre{k}"], init[f"bpre{k}"] = u(2 * f, 2 * f, f), u(2 * f, f)
             init[f"wpost{k}"], init[f"bpost{k}"] = u(13 * f, 13 * f, h), u(13 * f, h)
             init[f"wlin{k}"], init[f"blin{k}"] = u(h, h, h), u(h, h)
-        for k in ("g1", "g2", "g3", "g4"):
-            init[k] = np.ones(shapes[k])
-        for k in ("a1", "a2", "a3", "a4"):
-            init[k] = np.full(1, 0.25)
-        for k, v in init.items():
-            self.p[k].copy_from_host(np.asarray(v, np.float32))
-        self.built = True
+        return init
 
     def state_dict(self):
         d = super().state_dict()
@@ -2158,9 +2182,10 @@ class PNA(GCN):
             out[tk] = v
         return out
 
+    def _probe_f_in(self, d):
+        return int(np.asarray(d["conv1.pre_nns.0.0.weight"]).shape[0])       # [F, 2F]
+
     def load_state_dict(self, d):
-        if not self.built:                      # pre_nns.0.0.weight is [F, 2F]
-            self.build(int(np.asarray(d["conv1.pre_nns.0.0.weight"]).shape[0]))
         super().load_state_dict(d)
         for k, dk in enumerate(self.DELTA_KEYS):
             if dk in d:
@@ -2168,16 +2193,6 @@ class PNA(GCN):
                 if not (delta > 0.0 and np.isfinite(delta)):
                     raise ValueError(f"{dk}: must be positive and finite, got {delta}")
                 self.avg_deg_log[k] = delta
-
-    def _as_batch(self, inputs, target=None):
-        return self._adopt(inputs, target, weighted=False)       # the adjacency as stored: no loops added
-
-    def _op(self, batch):
-        """The unweighted pattern of the batch and its transpose (built once per batch object)."""
-        if self._op_cache is None or self._op_cache[0] != batch.uid:
-            a = batch.a.unweighted()
-            self._op_cache = (batch.uid, a, a.transpose())
-        return self._op_cache[1], self._op_cache[2]
 
     def _ensure(self, batch, sharded=False):
         bufs = super()._ensure(batch, sharded)
@@ -2194,33 +2209,19 @@ class PNA(GCN):
                 bufs[f"coef{k}"] = v("pna_coef", n, 4 * w).flat(0, 4 * n * w)
         return bufs
 
-    def _pna_fwd(self, a, x, k, bufs, out, keep):
-        from .layers import pna_forward
+    def _conv_fwd(self, a, x, k, bufs, keep):
         p = self.p
+        wpre, bpre, wpost, bpost, wlin, blin, pq, c, st, tc, z, _, _, _ = self._KEYS[k]
         bufs["a"] = a                           # the forward pattern: gcnx_pna_bwd reads its degrees
-        pna_forward(self.ctx, a, x, p[f"wpre{k}"], p[f"bpre{k}"], p[f"wpost{k}"], p[f"bpost{k}"], p[f"wlin{k}"], p[f"blin{k}"],
-                    self.avg_deg_log[k - 1], bufs[f"pq{k}"], bufs[f"c{k}"], bufs[f"st{k}"] if keep else None, bufs[f"tc{k}"], out)
+        convs.pna_forward(self.ctx, a, x, p[wpre], p[bpre], p[wpost], p[bpost], p[wlin], p[blin], self.avg_deg_log[k - 1], bufs[pq],
+                          bufs[c], bufs[st] if keep else None, bufs[tc], bufs[z])
 
-    def _pna_bwd(self, a_t, x, k, dz, bufs, dx):
-        from .layers import pna_backward
+    def _conv_bwd(self, a_t, x, k, dzk, bufs, dx):
         p, g = self.p, self.g
-        pna_backward(self.ctx, bufs["a"], a_t, x, bufs[f"pq{k}"], bufs[f"c{k}"], bufs[f"st{k}"], bufs[f"tc{k}"], dz, p[f"wpre{k}"],
-                     p[f"wpost{k}"], p[f"wlin{k}"], g[f"wpre{k}"], g[f"bpre{k}"], g[f"wpost{k}"], g[f"bpost{k}"], g[f"wlin{k}"],
-                     g[f"blin{k}"], self.avg_deg_log[k - 1], bufs["t"], bufs[f"dc{k}"], bufs[f"dpq{k}"], bufs[f"coef{k}"], dx)
-
-    def _conv1(self, a, batch, bufs, mode):
-        self._pna_fwd(a, batch.x, 1, bufs, bufs["z1"], mode == "grads")
-
-    def _conv2(self, a, bufs, mode):
-        self._pna_fwd(a, bufs["y1"], 2, bufs, bufs["z2"], mode == "grads")
-
-    def _conv2_bwd(self, a_t, bufs):
-        """dZ2 -> conv2's gradients and dY1."""
-        self._pna_bwd(a_t, bufs["y1"], 2, bufs["dz2"], bufs, bufs["dy1"])
-
-    def _conv1_bwd(self, a_t, batch, bufs):
-        """dZ1 -> conv1's gradients (the input carries no gradient)."""
-        self._pna_bwd(a_t, batch.x, 1, bufs["dz1"], bufs, None)
+        wpre, bpre, wpost, bpost, wlin, blin, pq, c, st, tc, _, dc, dpq, coef = self._KEYS[k]
+        convs.pna_backward(self.ctx, bufs["a"], a_t, x, bufs[pq], bufs[c], bufs[st], bufs[tc], dzk, p[wpre], p[wpost], p[wlin], g[wpre],
+                           g[bpre], g[wpost], g[bpost], g[wlin], g[blin], self.avg_deg_log[k - 1], bufs["t"], bufs[dc], bufs[dpq],
+                           bufs[coef], dx)
 
 
 class GAT(GCN):
@@ -2238,7 +2239,8 @@ class GAT(GCN):
     BN·PReLU, the fused max-pool pair, the one-launch BCE head, sync-BN over shards (``comm=``; attention never leaves a
     graph), ``fit``.
 
-    Hot path per convolution: gcnx_gemm (Hf = x W), gcnx_gat_scores, gcnx_gat_aggregate; backward gcnx_act_bias_grad,
+    Hot path per convolution (gat_forward / gat_backward of gcnx/convs.py, the one place the sequence is written; gcnx.GATConv
+    runs the same two functions): gcnx_gemm (Hf = x W), gcnx_gat_scores, gcnx_gat_aggregate; backward gcnx_act_bias_grad,
     gcnx_gat_bwd_edges (forward CSR), gcnx_gat_bwd_nodes (transposed pattern + entry permutation, built once per batch),
     gcnx_gemm_dw, gcnx_gemm_dx.
 
@@ -2254,16 +2256,14 @@ class GAT(GCN):
                   ("conv2.att_src", "as2", False), ("conv2.att_dst", "ad2", False), ("conv2.bias", "b2", False),
                   ("conv2.lin.weight", "w2", True)) + GCN.TORCH_KEYS[4:]
     PROBE_KEY = "conv1.lin.weight"
-    ATT_KEYS = ("conv1.att_src", "conv1.att_dst", "conv2.att_src", "conv2.att_dst")
+    LEADING_AXIS = ("conv1.att_src", "conv1.att_dst", "conv2.att_src", "conv2.att_dst")      # [1, heads, C] in PyG, [heads, C] here
+    OPERATOR, KERNELS = "perm", "GATConv"
+    _KEYS = _conv_keys("w", "as", "ad", "b", "hf", "asrc", "adst", "alpha", "o", "z")
     SLOPE = 0.2
 
     def _init(self, ctx, hidden_channels=64, heads=1, num_classes=1, seed=0, comm=None):
         h, heads = int(hidden_channels), int(heads)
-        if heads not in (1, 2, 4, 8) or h % heads != 0:
-            raise NotImplementedError(f"gcnx.GAT: heads={heads} must be 1, 2, 4 or 8 and divide hidden_channels={h}")
-        if h not in (16, 32, 64, 128) or h // heads < 4:
-            raise NotImplementedError(f"gcnx.GAT: hidden_channels={h} must be 16, 32, 64 or 128 with at least 4 channels per head "
-                                      "(the widths the GATConv kernels serve; there is no composed route)")
+        self._check_heads(h, heads)
         super()._init(ctx, h, num_classes, seed, comm)
         self.heads = heads
 
@@ -2273,52 +2273,12 @@ class GAT(GCN):
         s.update(as1=hc, ad1=hc, as2=hc, ad2=hc)
         return s
 
-    def build(self, f_in):
-        h, heads = self.hidden, self.heads
-        shapes = self._shapes(f_in)
-        self.f_in = int(f_in)
-        # every parameter starts on a 16-byte boundary (the kernels read att_*, the bias and W as float4); the padding floats
-        # have zero gradients, so the single SGD launch over the whole buffer leaves them at zero
-        self._alloc_flat([(k, shapes[k]) for k in self.PARAM_ORDER], align=4)
-        rng, lim, alim = self._rng, 1.0 / np.sqrt(h), np.sqrt(6.0 / (heads + h // heads))
+    def _initial(self, f_in, shapes, offs):
+        h, heads, rng = self.hidden, self.heads, self._rng
+        alim = np.sqrt(6.0 / (heads + h // heads))
         att = lambda: rng.uniform(-alim, alim, shapes["as1"])
-        init = {"as1": att(), "ad1": att(), "w1": glorot_uniform(rng, f_in, h), "as2": att(), "ad2": att(), "w2": glorot_uniform(rng, h, h),
-                "w3": rng.uniform(-lim, lim, (h, h)), "b3": rng.uniform(-lim, lim, h),
-                "w4": rng.uniform(-lim, lim, (1, h)), "b4": rng.uniform(-lim, lim, 1)}
-        for k in ("g1", "g2", "g3", "g4"):
-            init[k] = np.ones(shapes[k])
-        for k in ("a1", "a2", "a3", "a4"):
-            init[k] = np.full(1, 0.25)
-        for k, v in init.items():
-            self.p[k].copy_from_host(np.asarray(v, np.float32))
-        self.built = True
-
-    # the attention vectors are [1, heads, C] in PyG's layout and [heads, C] here
-    def state_dict(self):
-        d = super().state_dict()
-        d.update({k: d[k][None] for k in self.ATT_KEYS})
-        return d
-
-    def gradients(self):
-        d = super().gradients()
-        d.update({k: d[k][None] for k in self.ATT_KEYS})
-        return d
-
-    def load_state_dict(self, d):
-        d = dict(d)
-        for k in self.ATT_KEYS:
-            if k in d and np.ndim(d[k]) == 3 and np.shape(d[k])[0] == 1:
-                d[k] = np.asarray(d[k])[0]
-        super().load_state_dict(d)
-
-    def _op(self, batch):
-        """The unweighted pattern of the batch, twice: the backward walks its transposed pattern through the entry permutation
-        (DeviceCSR.transpose_perm, built here, once per batch object)."""
-        if self._op_cache is None or self._op_cache[0] != batch.uid:
-            a = batch.a.unweighted()
-            a.transpose_perm()
-            self._op_cache = (batch.uid, a, a)
-        return self._op_cache[1], self._op_cache[2]
+        return {"as1": att(), "ad1": att(), "w1": glorot_uniform(rng, f_in, h), "as2": att(), "ad2": att(), "w2": glorot_uniform(rng, h, h),
+                **self._head_initial(shapes)}
 
     def _ensure(self, batch, sharded=False):
         bufs = super()._ensure(batch, sharded)
@@ -2338,39 +2298,17 @@ class GAT(GCN):
             bufs["gat_key"] = (batch.n, batch.n_graphs, nnz)
         return bufs
 
-    def _gat_fwd(self, a, x, k, bufs, keep):
-        """z_k = GATConv_k(x): Hf, the score halves, the softmax-weighted gather; keep: alpha and O for the backward."""
-        ctx, p = self.ctx, self.p
-        hf, asrc, adst = bufs[f"hf{k}"], bufs[f"asrc{k}"], bufs[f"adst{k}"]
-        D.gemm(ctx, x, p[f"w{k}"], None, hf)
-        D.gat_scores(ctx, hf, p[f"as{k}"], p[f"ad{k}"], asrc, adst)
-        D.gat_aggregate(ctx, a, hf, asrc, adst, p[f"b{k}"], bufs[f"z{k}"], alpha=bufs[f"alpha{k}"] if keep else None,
-                        o_pre=bufs[f"o{k}"] if keep else None, slope=self.SLOPE)
+    def _conv_fwd(self, a, x, k, bufs, keep):
+        p = self.p
+        w, as_, ad, b, hf, asrc, adst, alpha, o, z = self._KEYS[k]
+        convs.gat_forward(self.ctx, a, x, p[w], p[as_], p[ad], p[b], bufs[hf], bufs[asrc], bufs[adst], bufs[alpha] if keep else None,
+                          bufs[o] if keep else None, bufs[z], self.SLOPE)
 
-    def _gat_bwd(self, a, x, k, dzk, bufs, dx):
-        """dZ_k -> the four gradients of GATConv_k and, with dx, the gradient of its input."""
-        ctx, p, g = self.ctx, self.p, self.g
-        hf, alpha = bufs[f"hf{k}"], bufs[f"alpha{k}"]
-        D.act_bias_grad(ctx, dzk, None, dzk, None, db=g[f"b{k}"])                    # conv_k.bias: column sums of dZ_k
-        D.gat_bwd_edges(ctx, a, hf, bufs[f"asrc{k}"], bufs[f"adst{k}"], alpha, dzk, bufs[f"o{k}"], bufs["dz"], bufs["dadst"],
-                        slope=self.SLOPE)
-        D.gat_bwd_nodes(ctx, a, alpha, bufs["dz"], dzk, hf, bufs["dadst"], p[f"as{k}"], p[f"ad{k}"], bufs["dhf"], bufs["dasrc"],
-                        g[f"as{k}"], g[f"ad{k}"], bufs["scratch"])
-        D.gemm_dw(ctx, x, bufs["dhf"], g[f"w{k}"])                                   # dW_k = x^T dHf
-        if dx is not None:
-            D.gemm_dx(ctx, bufs["dhf"], p[f"w{k}"], dx)                              # dx = dHf W_k^T
-
-    def _conv1(self, a, batch, bufs, mode):
-        self._gat_fwd(a, batch.x, 1, bufs, mode == "grads")
-
-    def _conv2(self, a, bufs, mode):
-        self._gat_fwd(a, bufs["y1"], 2, bufs, mode == "grads")
-
-    def _conv2_bwd(self, a_t, bufs):
-        self._gat_bwd(a_t, bufs["y1"], 2, bufs["dz2"], bufs, bufs["dy1"])
-
-    def _conv1_bwd(self, a_t, batch, bufs):
-        self._gat_bwd(a_t, batch.x, 1, bufs["dz1"], bufs, None)                     # (the input carries no gradient)
+    def _conv_bwd(self, a, x, k, dzk, bufs, dx):
+        p, g = self.p, self.g
+        w, as_, ad, b, hf, asrc, adst, alpha, o, _ = self._KEYS[k]
+        convs.gat_backward(self.ctx, a, x, bufs[hf], bufs[asrc], bufs[adst], bufs[alpha], bufs[o], dzk, p[w], p[as_], p[ad], g[w], g[as_],
+                           g[ad], g[b], bufs["dz"], bufs["dadst"], bufs["dasrc"], bufs["dhf"], bufs["scratch"], dx, self.SLOPE)
 
 
 class GATv2(GCN):
@@ -2392,7 +2330,8 @@ class GATv2(GCN):
     BN·PReLU, the fused max-pool pair, the one-launch BCE head, ``fit``, the optimizers of gcnx.optim.  One device: ``comm`` is
     refused.
 
-    Hot path per convolution: gcnx_gemm (Xl | Xr = x [W_l | W_r] + [b_l | b_r], one launch), gcnx_gatv2_aggregate; backward
+    Hot path per convolution (gatv2_forward / gatv2_backward of gcnx/convs.py, the one place the sequence is written;
+    gcnx.GATv2Conv runs the same two functions): gcnx_gemm (Xl | Xr = x [W_l | W_r] + [b_l | b_r], one launch), gcnx_gatv2_aggregate; backward
     gcnx_act_bias_grad, gcnx_gatv2_bwd_edges (forward CSR), gcnx_gatv2_bwd_nodes (transposed pattern + entry permutation),
     gcnx_gemm_dw, gcnx_act_bias_grad, gcnx_gemm_dx.
 
@@ -2402,22 +2341,17 @@ class GATv2(GCN):
     PyG 2.x's source, not a live module: prefer the named dicts.  Initialisation: glorot-uniform, zero biases, as PyG."""
 
     PROBE_KEY = "conv1.lin_l.weight"
+    OPERATOR, KERNELS = "perm", "GATv2Conv"
+    _KEYS = _conv_keys("w", "lb", "att", "b", "we", "xlr", "alpha", "o", "z")
     SLOPE = 0.2
 
     def _init(self, ctx, hidden_channels=64, heads=1, edge_dim=None, num_classes=1, seed=0, comm=None):
         h, heads = int(hidden_channels), int(heads)
-        if comm is not None:
-            raise NotImplementedError("gcnx.GATv2 runs on one device (comm is not supported)")
-        if heads not in (1, 2, 4, 8) or h % heads != 0:
-            raise NotImplementedError(f"gcnx.GATv2: heads={heads} must be 1, 2, 4 or 8 and divide hidden_channels={h}")
-        if h not in (16, 32, 64, 128) or h // heads < 4:
-            raise NotImplementedError(f"gcnx.GATv2: hidden_channels={h} must be 16, 32, 64 or 128 with at least 4 channels per head "
-                                      "(the widths the GATv2Conv kernels serve; there is no composed route)")
-        if edge_dim is not None and not 1 <= int(edge_dim) <= 8:
-            raise NotImplementedError(f"gcnx.GATv2: edge_dim={edge_dim} must be None or 1 .. 8 (what the GATv2Conv kernels serve)")
+        self._one_device(comm)
+        self._check_heads(h, heads)
+        self.edge_dim = self._check_edge_dim(edge_dim)
         super()._init(ctx, h, num_classes, seed, None)
-        self.heads, self.edge_dim = heads, None if edge_dim is None else int(edge_dim)
-        self.uses_edge_features = edge_dim is not None
+        self.heads, self.uses_edge_features = heads, edge_dim is not None
         conv = lambda k: (f"att{k}", f"b{k}", f"w{k}", f"lb{k}") + ((f"we{k}",) if self.edge_dim else ())
         self.PARAM_ORDER = conv(1) + conv(2) + ("g1", "be1", "a1", "g2", "be2", "a2") + GCN.PARAM_ORDER[10:]
         keys = lambda k: ((f"conv{k}.att", f"att{k}", False), (f"conv{k}.bias", f"b{k}", False),
@@ -2425,7 +2359,7 @@ class GATv2(GCN):
                           (f"conv{k}.lin_r.weight", f"wr{k}", True), (f"conv{k}.lin_r.bias", f"br{k}", False)) + \
             (((f"conv{k}.lin_edge.weight", f"we{k}", True),) if self.edge_dim else ())
         self.TORCH_KEYS = keys(1) + keys(2) + GCN.TORCH_KEYS[4:]
-        self.ATT_KEYS = ("conv1.att", "conv2.att")
+        self.LEADING_AXIS = ("conv1.att", "conv2.att")                 # [1, heads, C] in PyG, [heads, C] here
 
     def _shapes(self, f_in):
         s = super()._shapes(f_in)
@@ -2434,98 +2368,38 @@ class GATv2(GCN):
         s.update(att1=hc, att2=hc, w1=(f_in, 2 * h), w2=(h, 2 * h), lb1=(2 * h,), lb2=(2 * h,), we1=(d, h), we2=(d, h))
         return s
 
-    def build(self, f_in):
-        h, heads, d = self.hidden, self.heads, self.edge_dim or 0
-        shapes = self._shapes(f_in)
-        self.f_in = int(f_in)
-        # every parameter starts on a 16-byte boundary (the kernels read att, the bias, W_e and W as float4); the padding floats
-        # have zero gradients, so the single update launch over the whole buffer leaves them at zero
-        self._alloc_flat([(k, shapes[k]) for k in self.PARAM_ORDER], align=4)
+    def _initial(self, f_in, shapes, offs):
+        h, heads, d, rng = self.hidden, self.heads, self.edge_dim or 0, self._rng
         for t in (self.p, self.g):                      # PyG's names: the column halves of the stacked weight, the halves of the bias
             for k in (1, 2):
                 t[f"wl{k}"], t[f"wr{k}"] = t[f"w{k}"].cols(0, h), t[f"w{k}"].cols(h, 2 * h)
                 t[f"bl{k}"], t[f"br{k}"] = t[f"lb{k}"].flat(0, h), t[f"lb{k}"].flat(h, h)
-        rng, lim, alim = self._rng, 1.0 / np.sqrt(h), np.sqrt(6.0 / (heads + h // heads))
+        alim = np.sqrt(6.0 / (heads + h // heads))
         att = lambda: rng.uniform(-alim, alim, shapes["att1"])
         lin = lambda fi: np.concatenate([glorot_uniform(rng, fi, h), glorot_uniform(rng, fi, h)], axis=1)
-        init = {"att1": att(), "w1": lin(f_in), "att2": att(), "w2": lin(h),
-                "w3": rng.uniform(-lim, lim, (h, h)), "b3": rng.uniform(-lim, lim, h),
-                "w4": rng.uniform(-lim, lim, (1, h)), "b4": rng.uniform(-lim, lim, 1)}
+        init = {"att1": att(), "w1": lin(f_in), "att2": att(), "w2": lin(h), **self._head_initial(shapes)}
         if d:
             init.update(we1=glorot_uniform(rng, d, h), we2=glorot_uniform(rng, d, h))
-        for k in ("g1", "g2", "g3", "g4"):
-            init[k] = np.ones(shapes[k])
-        for k in ("a1", "a2", "a3", "a4"):
-            init[k] = np.full(1, 0.25)
-        for k, v in init.items():
-            self.p[k].copy_from_host(np.asarray(v, np.float32))
-        self.built = True
+        return init
 
-    # the attention vectors are [1, heads, C] in PyG's layout and [heads, C] here
-    def state_dict(self):
-        d = super().state_dict()
-        d.update({k: d[k][None] for k in self.ATT_KEYS})
-        return d
-
-    def gradients(self):
-        d = super().gradients()
-        d.update({k: d[k][None] for k in self.ATT_KEYS})
-        return d
-
-    def load_state_dict(self, d):
-        """Inverse of state_dict; the lin_l / lin_r halves are written into the stacked tensors.  Builds the model if needed."""
-        d = dict(d)
-        if not self.built:
-            self.build(int(np.asarray(d[self.PROBE_KEY]).shape[1]))
-        missing = [tk for tk, _, _ in self.TORCH_KEYS if tk not in d]
-        if missing:
-            raise KeyError(f"gcnx.GATv2.load_state_dict: missing {missing}")
-        host = {}
-        for tk, k, tr in self.TORCH_KEYS:
-            v = np.asarray(d[tk], np.float32)
-            if tk in self.ATT_KEYS and v.ndim == 3 and v.shape[0] == 1:
-                v = v[0]
-            v = v.T if tr else v
-            if v.shape != self.p[k].shape:
-                raise ValueError(f"{tk}: shape {np.asarray(d[tk]).shape} does not fit this model")
-            host[k] = v
+    def _stack(self, host):
+        """The lin_l / lin_r halves into the stacked tensors."""
         for k in (1, 2):
             host[f"w{k}"] = np.concatenate([host.pop(f"wl{k}"), host.pop(f"wr{k}")], axis=1)
             host[f"lb{k}"] = np.concatenate([host.pop(f"bl{k}"), host.pop(f"br{k}")])
-        for k, v in host.items():
-            self.p[k].copy_from_host(np.ascontiguousarray(v))
+        return host
 
-    def _as_batch(self, inputs, target=None):
-        if not isinstance(inputs, DeviceBatch):
-            if self.uses_edge_features and len(inputs) != 4:
-                raise ValueError(f"gcnx.GATv2(edge_dim={self.edge_dim}) takes (x, a, e, i): build the graphs with edge features "
-                                 "(Graph(e=...), from_networkx(use_edge_data='entries'))")
-            x, a, i = _without_e(inputs)
-            e = inputs[2] if self.uses_edge_features else None
-            if not isinstance(a, D.DeviceCSR):                   # a host matrix: PyG's add_self_loops=True, fill_value="mean"
-                a, e = _with_mean_self_loops(a, e, np.asarray(x).shape[0])
-            inputs = (x, a, e, i) if e is not None else (x, a, i)
-        batch = self._adopt(inputs, target, weighted=False)
-        if self.uses_edge_features and batch.e is None:
-            raise ValueError("gcnx.GATv2: the batch carries no edge features (DeviceBatch.e)")
-        return batch
-
-    def _op(self, batch):
-        """The unweighted pattern of the batch, twice: the backward walks its transposed pattern through the entry permutation
-        (DeviceCSR.transpose_perm: the one a device loader's batch arrives with, or built here, once per batch object)."""
-        if self._op_cache is None or self._op_cache[0] != batch.uid:
-            a = batch.a.unweighted()
-            a.transpose_perm()
-            self._op_cache = (batch.uid, a, a)
-        return self._op_cache[1], self._op_cache[2]
+    def _host_inputs(self, inputs):
+        x, a, i = _without_e(inputs)
+        e = inputs[2] if self.uses_edge_features else None
+        if not isinstance(a, D.DeviceCSR):                       # a host matrix: PyG's add_self_loops=True, fill_value="mean"
+            a, e = _with_mean_self_loops(a, e, np.asarray(x).shape[0])
+        return (x, a, e, i) if e is not None else (x, a, i)
 
     def _ensure(self, batch, sharded=False):
         bufs = super()._ensure(batch, sharded)
-        d = self.edge_dim or 0
-        if d and (batch.e is None or batch.e.shape != (batch.a.nnz, d)):
-            raise ValueError(f"gcnx.GATv2(edge_dim={d}): the batch's edge features must be [{batch.a.nnz}, {d}], got "
-                             f"{None if batch.e is None else list(batch.e.shape)}")
-        nnz = batch.a.nnz
+        self._check_e(batch)
+        nnz, d = batch.a.nnz, self.edge_dim or 0
         if bufs.get("gatv2_key") != (batch.n, batch.n_graphs, nnz):        # the edge buffers follow nnz as well as (n, b)
             v, n, h, heads = self._views(), batch.n, self.hidden, self.heads
             if not D.gatv2_conv_ok(self.ctx, n, heads, h // heads, edge_dim=d):
@@ -2541,39 +2415,17 @@ class GATv2(GCN):
             bufs["gatv2_key"] = (batch.n, batch.n_graphs, nnz)
         return bufs
 
-    def _v2_fwd(self, a, x, e, k, bufs, keep):
-        """z_k = GATv2Conv_k(x): Xl | Xr in one product, then scores, softmax and weighted sum in one launch; keep: alpha and O."""
-        ctx, p = self.ctx, self.p
-        xlr = bufs[f"xlr{k}"]
-        D.gemm(ctx, x, p[f"w{k}"], p[f"lb{k}"], xlr)
-        D.gatv2_aggregate(ctx, a, xlr, p[f"att{k}"], p[f"b{k}"], bufs[f"z{k}"], e=e, w_e=p.get(f"we{k}"),
-                          alpha=bufs[f"alpha{k}"] if keep else None, o_pre=bufs[f"o{k}"] if keep else None, slope=self.SLOPE)
+    def _conv_fwd(self, a, x, k, bufs, keep):
+        p = self.p
+        w, lb, att, b, we, xlr, alpha, o, z = self._KEYS[k]
+        convs.gatv2_forward(self.ctx, a, x, bufs["e"], p[w], p[lb], p[att], p[b], p.get(we), bufs[xlr], bufs[alpha] if keep else None,
+                            bufs[o] if keep else None, bufs[z], self.SLOPE)
 
-    def _v2_bwd(self, a, x, e, k, dzk, bufs, dx):
-        """dZ_k -> the gradients of GATv2Conv_k and, with dx, the gradient of its input."""
-        ctx, p, g, h = self.ctx, self.p, self.g, self.hidden
-        xlr, alpha, dxlr, w_e = bufs[f"xlr{k}"], bufs[f"alpha{k}"], bufs["dxlr"], p.get(f"we{k}")
-        D.act_bias_grad(ctx, dzk, None, dzk, None, db=g[f"b{k}"])                    # conv_k.bias: column sums of dZ_k
-        D.gatv2_bwd_edges(ctx, a, xlr, p[f"att{k}"], alpha, dzk, bufs[f"o{k}"], bufs["dscore"], dxlr.cols(h, 2 * h), g[f"att{k}"],
-                          bufs["scratch"], e=e, w_e=w_e, dw_e=g.get(f"we{k}"), slope=self.SLOPE)
-        D.gatv2_bwd_nodes(ctx, a, xlr, p[f"att{k}"], alpha, bufs["dscore"], dzk, dxlr.cols(0, h), e=e, w_e=w_e, slope=self.SLOPE)
-        D.gemm_dw(ctx, x, dxlr, g[f"w{k}"])                                          # dW_l | dW_r = x^T (dXl | dXr)
-        D.act_bias_grad(ctx, dxlr, None, dxlr, None, db=g[f"lb{k}"])                 # db_l | db_r
-        if dx is not None:
-            D.gemm_dx(ctx, dxlr, p[f"w{k}"], dx)                                     # dx = dXl W_l^T + dXr W_r^T
-
-    def _conv1(self, a, batch, bufs, mode):
-        bufs["e"] = batch.e if self.uses_edge_features else None                    # (conv2 and the backward read the same rows)
-        self._v2_fwd(a, batch.x, bufs["e"], 1, bufs, mode == "grads")
-
-    def _conv2(self, a, bufs, mode):
-        self._v2_fwd(a, bufs["y1"], bufs["e"], 2, bufs, mode == "grads")
-
-    def _conv2_bwd(self, a_t, bufs):
-        self._v2_bwd(a_t, bufs["y1"], bufs["e"], 2, bufs["dz2"], bufs, bufs["dy1"])
-
-    def _conv1_bwd(self, a_t, batch, bufs):
-        self._v2_bwd(a_t, batch.x, bufs["e"], 1, bufs["dz1"], bufs, None)            # (the input carries no gradient)
+    def _conv_bwd(self, a, x, k, dzk, bufs, dx):
+        p, g = self.p, self.g
+        w, lb, att, b, we, xlr, alpha, o, _ = self._KEYS[k]
+        convs.gatv2_backward(self.ctx, a, x, bufs["e"], bufs[xlr], bufs[alpha], bufs[o], dzk, p[w], p[att], p.get(we), g[w], g[lb], g[att],
+                             g[b], g.get(we), bufs["dscore"], bufs["dxlr"], bufs["scratch"], dx, self.SLOPE)
 
 
 class ResGated(GCN):
@@ -2593,8 +2445,9 @@ class ResGated(GCN):
     (the reference's graphs carry every loop).  Everything behind the convolutions is ``GCN``'s: BN·PReLU, the fused max-pool
     pair, the one-launch BCE head, ``fit``, the optimizers of gcnx.optim.  One device: ``comm`` is refused.
 
-    Hot path per convolution: gcnx_gemm (P = K | Q | V | S = x [W_k | W_q | W_v | W_s] + [b_k | b_q | b_v | 0], one launch),
-    gcnx_resgated_aggregate; backward gcnx_act_bias_grad, gcnx_resgated_bwd_targets (forward CSR), gcnx_resgated_bwd_sources
+    Hot path per convolution (resgated_forward / resgated_backward of gcnx/convs.py, the one place the sequence is written;
+    gcnx.ResGatedGraphConv runs the same two functions): gcnx_gemm (P = K | Q | V | S = x [W_k | W_q | W_v | W_s] +
+    [b_k | b_q | b_v | 0], one launch), gcnx_resgated_aggregate; backward gcnx_act_bias_grad, gcnx_resgated_bwd_targets (forward CSR), gcnx_resgated_bwd_sources
     (transposed pattern + entry permutation), gcnx_gemm_dw, gcnx_act_bias_grad over the 3 H biased columns, gcnx_gemm_dx.
 
     Weights: PyG's key names ``conv{1,2}.bias``, ``.lin_key.weight`` / ``.lin_query.weight`` / ``.lin_value.weight`` ([out, in + D] =
@@ -2607,19 +2460,18 @@ class ResGated(GCN):
 
     PROBE_KEY = None                      # conv1.lin_key.weight is [H, F + D]: load_state_dict subtracts D itself
     LINS = (("lin_key", "k"), ("lin_query", "q"), ("lin_value", "v"))
+    OPERATOR, SELF_LOOPS, KERNELS = "perm", False, "ResGatedGraphConv"
+    _KEYS = _conv_keys("w", "lb", "b", "we", "p", "z")
 
     def _init(self, ctx, hidden_channels=64, edge_dim=None, root_weight=True, num_classes=1, seed=0, comm=None):
         h = int(hidden_channels)
-        if comm is not None:
-            raise NotImplementedError("gcnx.ResGated runs on one device (comm is not supported)")
+        self._one_device(comm)
         if h not in (16, 32, 64, 128):
             raise NotImplementedError(f"gcnx.ResGated: hidden_channels={h} must be 16, 32, 64 or 128 (the widths the ResGatedGraphConv "
                                       "kernels serve; there is no composed route)")
-        if edge_dim is not None and not 1 <= int(edge_dim) <= 8:
-            raise NotImplementedError(f"gcnx.ResGated: edge_dim={edge_dim} must be None or 1 .. 8 (what the ResGatedGraphConv kernels serve)")
+        self.edge_dim = self._check_edge_dim(edge_dim)
         super()._init(ctx, h, num_classes, seed, None)
-        self.edge_dim, self.root_weight = None if edge_dim is None else int(edge_dim), bool(root_weight)
-        self.uses_edge_features = edge_dim is not None
+        self.root_weight, self.uses_edge_features = bool(root_weight), edge_dim is not None
         self.width = (4 if self.root_weight else 3) * h
         # lz: the zero bias of the S block, directly behind the stacked bias (the product's bias is the two together)
         conv = lambda k: (f"b{k}", f"w{k}", f"lb{k}") + ((f"lz{k}",) if self.root_weight else ()) + ((f"we{k}",) if self.edge_dim else ())
@@ -2637,14 +2489,9 @@ class ResGated(GCN):
         s.update(w1=(f_in, w), w2=(h, w), lb1=(3 * h,), lb2=(3 * h,), lz1=(h,), lz2=(h,), we1=(d, 3 * h), we2=(d, 3 * h))
         return s
 
-    def build(self, f_in):
-        h, d, w = self.hidden, self.edge_dim or 0, self.width
-        shapes = self._shapes(f_in)
-        self.f_in = int(f_in)
-        # every parameter starts on a 16-byte boundary (the kernels read the bias, W_e and W as float4); the padding floats and
-        # lz have zero gradients, so the single update launch over the whole buffer leaves them at zero
-        offs = self._alloc_flat([(k, shapes[k]) for k in self.PARAM_ORDER], align=4)
-        self._gemm_bias = {}
+    def _initial(self, f_in, shapes, offs):
+        h, d, w, u = self.hidden, self.edge_dim or 0, self.width, self._uniform
+        self._gemm_bias = {}                            # (lz, like the padding, has zero gradients: the update leaves it at zero)
         for k in (1, 2):
             assert not self.root_weight or offs[f"lz{k}"] == offs[f"lb{k}"] + 3 * h
             self._gemm_bias[k] = self.flat_p.flat(offs[f"lb{k}"], w)
@@ -2656,22 +2503,13 @@ class ResGated(GCN):
                         t[f"w{s}e{k}"] = t[f"we{k}"].cols(i * h, (i + 1) * h)
                 if self.root_weight:
                     t[f"ws{k}"] = t[f"w{k}"].cols(3 * h, 4 * h)
-        rng, lim = self._rng, 1.0 / np.sqrt(h)
-        u = lambda fan_in, *s: rng.uniform(-1.0 / np.sqrt(fan_in), 1.0 / np.sqrt(fan_in), s)
-        init = {"w3": rng.uniform(-lim, lim, (h, h)), "b3": rng.uniform(-lim, lim, h),
-                "w4": rng.uniform(-lim, lim, (1, h)), "b4": rng.uniform(-lim, lim, 1)}
+        init = self._head_initial(shapes)
         for k, f in ((1, f_in), (2, h)):                # torch's Linear on [x ‖ e]: fan_in = in + D for key / query / value
             blocks = [u(f + d, f, 3 * h)] + ([u(f, f, h)] if self.root_weight else [])
             init[f"w{k}"], init[f"lb{k}"] = np.concatenate(blocks, axis=1), u(f + d, 3 * h)
             if d:
                 init[f"we{k}"] = u(f + d, d, 3 * h)
-        for k in ("g1", "g2", "g3", "g4"):
-            init[k] = np.ones(shapes[k])
-        for k in ("a1", "a2", "a3", "a4"):
-            init[k] = np.full(1, 0.25)
-        for k, v in init.items():
-            self.p[k].copy_from_host(np.asarray(v, np.float32))
-        self.built = True
+        return init
 
     def _joined(self, d, t):
         """PyG's [H, in + D] tensors: the edge block of ``t`` (self.p or self.g) joined to the node block the base class returned."""
@@ -2688,62 +2526,33 @@ class ResGated(GCN):
     def gradients(self):
         return self._joined(super().gradients(), self.g)
 
-    def load_state_dict(self, d):
-        """Inverse of state_dict: the [H, in + D] tensors are split into the node blocks of the stacked weight and the edge
-        blocks of the edge weight.  Builds the model if needed."""
-        d, ed = dict(d), self.edge_dim or 0
-        if not self.built:
-            self.build(int(np.asarray(d["conv1.lin_key.weight"]).shape[1]) - ed)
-        missing = [tk for tk, _, _ in self.TORCH_KEYS if tk not in d]
-        if missing:
-            raise KeyError(f"gcnx.ResGated.load_state_dict: missing {missing}")
-        host = {}
-        for tk, k, tr in self.TORCH_KEYS:
-            v = np.asarray(d[tk], np.float32)
-            v = v.T if tr else v
-            if ed and tk.startswith("conv") and tk.endswith(".weight") and "lin_skip" not in tk:
-                if v.ndim != 2 or v.shape[0] <= ed:
-                    raise ValueError(f"{tk}: shape {np.asarray(d[tk]).shape} does not fit this model")
-                host[k[:2] + "e" + k[2:]], v = v[-ed:], v[:-ed]           # wk1 -> wke1
-            if v.shape != self.p[k].shape:
-                raise ValueError(f"{tk}: shape {np.asarray(d[tk]).shape} does not fit this model")
-            host[k] = v
+    def _probe_f_in(self, d):
+        return int(np.asarray(d["conv1.lin_key.weight"]).shape[1]) - (self.edge_dim or 0)       # [H, F + D]
+
+    def _node_block(self, tk, k, v, host):
+        """Of a [in + D, H] key / query / value weight: the edge block into ``host`` (wk1 -> wke1), the node block back."""
+        ed = self.edge_dim or 0
+        if ed and tk.startswith("conv") and tk.endswith(".weight") and "lin_skip" not in tk:
+            if v.ndim != 2 or v.shape[0] <= ed:
+                raise ValueError(f"{tk}: shape {v.T.shape} does not fit this model")
+            host[k[:2] + "e" + k[2:]], v = v[-ed:], v[:-ed]
+        return v
+
+    def _stack(self, host):
+        """The node blocks into the stacked weight, the three biases into the stacked bias, the edge blocks into the edge weight."""
         for k in (1, 2):
             node = [host.pop(f"w{s}{k}") for _, s in self.LINS] + ([host.pop(f"ws{k}")] if self.root_weight else [])
             host[f"w{k}"] = np.concatenate(node, axis=1)
             host[f"lb{k}"] = np.concatenate([host.pop(f"b{s}{k}") for _, s in self.LINS])
-            if ed:
+            if self.edge_dim:
                 host[f"we{k}"] = np.concatenate([host.pop(f"w{s}e{k}") for _, s in self.LINS], axis=1)
-        for k, v in host.items():
-            self.p[k].copy_from_host(np.ascontiguousarray(v))
-
-    def _as_batch(self, inputs, target=None):
-        if not isinstance(inputs, DeviceBatch):
-            if self.uses_edge_features and len(inputs) != 4:
-                raise ValueError(f"gcnx.ResGated(edge_dim={self.edge_dim}) takes (x, a, e, i): build the graphs with edge features "
-                                 "(Graph(e=...), from_networkx(use_edge_data='entries'))")
-        batch = self._adopt(inputs, target, weighted=False)      # the adjacency and e as stored: no loop added or removed
-        if self.uses_edge_features and batch.e is None:
-            raise ValueError("gcnx.ResGated: the batch carries no edge features (DeviceBatch.e)")
-        return batch
-
-    def _op(self, batch):
-        """The unweighted pattern of the batch, twice: the backward walks its transposed pattern through the entry permutation
-        (DeviceCSR.transpose_perm: the one a device loader's batch arrives with, or built here, once per batch object)."""
-        if self._op_cache is None or self._op_cache[0] != batch.uid:
-            a = batch.a.unweighted()
-            a.transpose_perm()
-            self._op_cache = (batch.uid, a, a)
-        return self._op_cache[1], self._op_cache[2]
+        return host
 
     def _ensure(self, batch, sharded=False):
         bufs = super()._ensure(batch, sharded)
-        d = self.edge_dim or 0
-        if d and (batch.e is None or batch.e.shape != (batch.a.nnz, d)):
-            raise ValueError(f"gcnx.ResGated(edge_dim={d}): the batch's edge features must be [{batch.a.nnz}, {d}], got "
-                             f"{None if batch.e is None else list(batch.e.shape)}")
+        self._check_e(batch)
         if "p1" not in bufs:
-            v, n, h, w = self._views(), batch.n, self.hidden, self.width
+            v, n, h, w, d = self._views(), batch.n, self.hidden, self.width, self.edge_dim or 0
             if not D.resgated_conv_ok(self.ctx, n, h, ldp=w, edge_dim=d):
                 raise NotImplementedError(f"gcnx.ResGated: a batch of {n} rows at hidden_channels={h} is beyond the ResGatedGraphConv kernels")
             for k in ("p1", "p2", "dp"):
@@ -2752,39 +2561,16 @@ class ResGated(GCN):
             bufs["scratch"] = v("rg_scratch", 1, ns).flat(0, ns)
         return bufs
 
-    def _rg_fwd(self, a, x, e, k, bufs):
-        """z_k = ResGatedGraphConv_k(x): K | Q | V | S in one product, then gates, messages and their sum in one launch."""
-        ctx, p, h, w = self.ctx, self.p, self.hidden, self.width
-        pk = bufs[f"p{k}"]
-        D.gemm(ctx, x, p[f"w{k}"], self._gemm_bias[k], pk)
-        D.resgated_aggregate(ctx, a, pk, bufs[f"z{k}"], e=e, w_e=p.get(f"we{k}"), skip=pk.cols(3 * h, w) if self.root_weight else None,
-                             bias=p[f"b{k}"])
+    def _conv_fwd(self, a, x, k, bufs, keep):
+        p = self.p
+        w, _, b, we, pk, z = self._KEYS[k]
+        convs.resgated_forward(self.ctx, a, x, bufs["e"], p[w], self._gemm_bias[k], p[b], p.get(we), bufs[pk], bufs[z])
 
-    def _rg_bwd(self, a, x, e, k, dzk, bufs, dx):
-        """dZ_k -> the gradients of ResGatedGraphConv_k and, with dx, the gradient of its input."""
-        ctx, p, g, h, w = self.ctx, self.p, self.g, self.hidden, self.width
-        pk, dp, w_e = bufs[f"p{k}"], bufs["dp"], p.get(f"we{k}")
-        D.act_bias_grad(ctx, dzk, None, dzk, None, db=g[f"b{k}"])                    # conv_k.bias: column sums of dZ_k
-        D.resgated_bwd_targets(ctx, a, pk, dzk, dp.cols(0, h), bufs["scratch"], ds=dp.cols(3 * h, w) if self.root_weight else None,
-                               e=e, w_e=w_e, dw_e=g.get(f"we{k}"))
-        D.resgated_bwd_sources(ctx, a, pk, dzk, dp.cols(h, 3 * h), e=e, w_e=w_e)
-        D.gemm_dw(ctx, x, dp, g[f"w{k}"])                                            # dW_k | dW_q | dW_v | dW_s = x^T dP
-        D.act_bias_grad(ctx, dp.cols(0, 3 * h), None, dp.cols(0, 3 * h), None, db=g[f"lb{k}"])       # db_k | db_q | db_v
-        if dx is not None:
-            D.gemm_dx(ctx, dp, p[f"w{k}"], dx)                                       # dx = dP [W_k | W_q | W_v | W_s]^T
-
-    def _conv1(self, a, batch, bufs, mode):
-        bufs["e"] = batch.e if self.uses_edge_features else None                    # (conv2 and the backward read the same rows)
-        self._rg_fwd(a, batch.x, bufs["e"], 1, bufs)
-
-    def _conv2(self, a, bufs, mode):
-        self._rg_fwd(a, bufs["y1"], bufs["e"], 2, bufs)
-
-    def _conv2_bwd(self, a_t, bufs):
-        self._rg_bwd(a_t, bufs["y1"], bufs["e"], 2, bufs["dz2"], bufs, bufs["dy1"])
-
-    def _conv1_bwd(self, a_t, batch, bufs):
-        self._rg_bwd(a_t, batch.x, bufs["e"], 1, bufs["dz1"], bufs, None)            # (the input carries no gradient)
+    def _conv_bwd(self, a, x, k, dzk, bufs, dx):
+        p, g = self.p, self.g
+        w, lb, b, we, pk, _ = self._KEYS[k]
+        convs.resgated_backward(self.ctx, a, x, bufs["e"], bufs[pk], dzk, p[w], p.get(we), g[w], g[lb], g[b], g.get(we), bufs["dp"],
+                                bufs["scratch"], dx)
 
 
 class Transformer(GCN):
@@ -2806,9 +2592,11 @@ class Transformer(GCN):
     ``GCN``'s: BN·PReLU, the fused max-pool pair, the one-launch BCE head, ``fit``, the optimizers of gcnx.optim.  One device:
     ``comm`` is refused.
 
-    Hot path per convolution: gcnx_gemm (P = Q | K | V | S = x [W_q | W_k | W_v | W_s] + [b_q | b_k | b_v | b_s], one launch),
-    gcnx_transformer_aggregate; backward gcnx_transformer_beta_bwd (beta only), gcnx_transformer_bwd_targets (forward CSR),
-    gcnx_transformer_bwd_sources (transposed pattern + entry permutation), gcnx_gemm_dw, gcnx_act_bias_grad, gcnx_gemm_dx.
+    Hot path per convolution (transformer_forward / transformer_backward of gcnx/convs.py, the one place the sequence is written;
+    gcnx.TransformerConv runs the same two functions): gcnx_gemm (P = Q | K | V | S = x [W_q | W_k | W_v | W_s] +
+    [b_q | b_k | b_v | b_s], one launch), gcnx_transformer_aggregate; backward gcnx_transformer_beta_bwd (beta only),
+    gcnx_transformer_bwd_targets (forward CSR), gcnx_transformer_bwd_sources (transposed pattern + entry permutation),
+    gcnx_gemm_dw, gcnx_act_bias_grad, gcnx_gemm_dx.
 
     Weights: PyG's key names ``conv{1,2}.lin_key.weight`` / ``.bias``, ``.lin_query.*``, ``.lin_value.*``, ``.lin_edge.weight``
     ([out, edge_dim]; with edge_dim), ``.lin_skip.*`` (with root_weight), ``.lin_beta.weight`` ([1, 3 out]; with beta) in
@@ -2819,23 +2607,18 @@ class Transformer(GCN):
 
     PROBE_KEY = "conv1.lin_key.weight"
     BLOCKS = (("lin_query", "q"), ("lin_key", "k"), ("lin_value", "v"), ("lin_skip", "s"))       # storage order of the column blocks
+    OPERATOR, SELF_LOOPS, KERNELS = "perm", False, "TransformerConv"
+    _KEYS = _conv_keys("w", "lb", "we", "wb", "p", "alpha", "o", "z")
 
     def _init(self, ctx, hidden_channels=64, heads=1, edge_dim=None, beta=False, root_weight=True, num_classes=1, seed=0, comm=None):
         h, heads = int(hidden_channels), int(heads)
-        if comm is not None:
-            raise NotImplementedError("gcnx.Transformer runs on one device (comm is not supported)")
-        if heads not in (1, 2, 4, 8) or h % heads != 0:
-            raise NotImplementedError(f"gcnx.Transformer: heads={heads} must be 1, 2, 4 or 8 and divide hidden_channels={h}")
-        if h not in (16, 32, 64, 128) or h // heads < 4:
-            raise NotImplementedError(f"gcnx.Transformer: hidden_channels={h} must be 16, 32, 64 or 128 with at least 4 channels per head "
-                                      "(the widths the TransformerConv kernels serve; there is no composed route)")
-        if edge_dim is not None and not 1 <= int(edge_dim) <= 8:
-            raise NotImplementedError(f"gcnx.Transformer: edge_dim={edge_dim} must be None or 1 .. 8 (what the TransformerConv kernels serve)")
+        self._one_device(comm)
+        self._check_heads(h, heads)
+        self.edge_dim = self._check_edge_dim(edge_dim)
         if beta and not root_weight:
             raise NotImplementedError("gcnx.Transformer: beta=True gates the root connection and needs root_weight=True")
         super()._init(ctx, h, num_classes, seed, None)
-        self.heads, self.edge_dim = heads, None if edge_dim is None else int(edge_dim)
-        self.beta, self.root_weight = bool(beta), bool(root_weight)
+        self.heads, self.beta, self.root_weight = heads, bool(beta), bool(root_weight)
         self.uses_edge_features = edge_dim is not None
         self.blocks = self.BLOCKS if self.root_weight else self.BLOCKS[:3]
         self.width = len(self.blocks) * h
@@ -2846,7 +2629,7 @@ class Transformer(GCN):
             (((f"conv{k}.lin_edge.weight", f"we{k}", True),) if self.edge_dim else ()) + \
             (lin(k, "lin_skip", "s") if self.root_weight else ()) + (((f"conv{k}.lin_beta.weight", f"wb{k}", False),) if self.beta else ())
         self.TORCH_KEYS = keys(1) + keys(2) + GCN.TORCH_KEYS[4:]
-        self.BETA_KEYS = ("conv1.lin_beta.weight", "conv2.lin_beta.weight") if self.beta else ()
+        self.LEADING_AXIS = ("conv1.lin_beta.weight", "conv2.lin_beta.weight") if self.beta else ()     # [1, 3 H] in PyG, [3 H] here
 
     def _shapes(self, f_in):
         s = super()._shapes(f_in)
@@ -2854,95 +2637,32 @@ class Transformer(GCN):
         s.update(w1=(f_in, w), w2=(h, w), lb1=(w,), lb2=(w,), we1=(d, h), we2=(d, h), wb1=(3 * h,), wb2=(3 * h,))
         return s
 
-    def build(self, f_in):
-        h, d, w = self.hidden, self.edge_dim or 0, self.width
-        shapes = self._shapes(f_in)
-        self.f_in = int(f_in)
-        # every parameter starts on a 16-byte boundary (the kernels read W_e, w_beta and W as float4); the padding floats have
-        # zero gradients, so the single update launch over the whole buffer leaves them at zero
-        self._alloc_flat([(k, shapes[k]) for k in self.PARAM_ORDER], align=4)
+    def _initial(self, f_in, shapes, offs):
+        h, d, w, u = self.hidden, self.edge_dim or 0, self.width, self._uniform
         for t in (self.p, self.g):                      # PyG's names: the column blocks of the stacked weight and bias
             for k in (1, 2):
                 for i, (_, s) in enumerate(self.blocks):
                     t[f"w{s}{k}"], t[f"b{s}{k}"] = t[f"w{k}"].cols(i * h, (i + 1) * h), t[f"lb{k}"].flat(i * h, h)
-        rng, lim = self._rng, 1.0 / np.sqrt(h)
-        u = lambda fan_in, *s: rng.uniform(-1.0 / np.sqrt(fan_in), 1.0 / np.sqrt(fan_in), s)
-        init = {"w3": rng.uniform(-lim, lim, (h, h)), "b3": rng.uniform(-lim, lim, h),
-                "w4": rng.uniform(-lim, lim, (1, h)), "b4": rng.uniform(-lim, lim, 1)}
+        init = self._head_initial(shapes)
         for k, f in ((1, f_in), (2, h)):
             init[f"w{k}"], init[f"lb{k}"] = u(f, f, w), u(f, w)
             if d:
                 init[f"we{k}"] = u(d, d, h)
             if self.beta:
                 init[f"wb{k}"] = u(3 * h, 3 * h)
-        for k in ("g1", "g2", "g3", "g4"):
-            init[k] = np.ones(shapes[k])
-        for k in ("a1", "a2", "a3", "a4"):
-            init[k] = np.full(1, 0.25)
-        for k, v in init.items():
-            self.p[k].copy_from_host(np.asarray(v, np.float32))
-        self.built = True
+        return init
 
-    # lin_beta.weight is [1, 3 H] in PyG's layout and [3 H] here
-    def state_dict(self):
-        d = super().state_dict()
-        d.update({k: d[k][None] for k in self.BETA_KEYS})
-        return d
-
-    def gradients(self):
-        d = super().gradients()
-        d.update({k: d[k][None] for k in self.BETA_KEYS})
-        return d
-
-    def load_state_dict(self, d):
-        """Inverse of state_dict; the four Linears' tensors are written into the stacked ones.  Builds the model if needed."""
-        d = dict(d)
-        if not self.built:
-            self.build(int(np.asarray(d[self.PROBE_KEY]).shape[1]))
-        missing = [tk for tk, _, _ in self.TORCH_KEYS if tk not in d]
-        if missing:
-            raise KeyError(f"gcnx.Transformer.load_state_dict: missing {missing}")
-        host = {}
-        for tk, k, tr in self.TORCH_KEYS:
-            v = np.asarray(d[tk], np.float32)
-            if tk in self.BETA_KEYS and v.ndim == 2 and v.shape[0] == 1:
-                v = v[0]
-            v = v.T if tr else v
-            if v.shape != self.p[k].shape:
-                raise ValueError(f"{tk}: shape {np.asarray(d[tk]).shape} does not fit this model")
-            host[k] = v
+    def _stack(self, host):
+        """The four Linears' tensors into the stacked ones."""
         for k in (1, 2):
             host[f"w{k}"] = np.concatenate([host.pop(f"w{s}{k}") for _, s in self.blocks], axis=1)
             host[f"lb{k}"] = np.concatenate([host.pop(f"b{s}{k}") for _, s in self.blocks])
-        for k, v in host.items():
-            self.p[k].copy_from_host(np.ascontiguousarray(v))
-
-    def _as_batch(self, inputs, target=None):
-        if not isinstance(inputs, DeviceBatch):
-            if self.uses_edge_features and len(inputs) != 4:
-                raise ValueError(f"gcnx.Transformer(edge_dim={self.edge_dim}) takes (x, a, e, i): build the graphs with edge features "
-                                 "(Graph(e=...), from_networkx(use_edge_data='entries'))")
-        batch = self._adopt(inputs, target, weighted=False)      # the adjacency and e as stored: no loop added or removed
-        if self.uses_edge_features and batch.e is None:
-            raise ValueError("gcnx.Transformer: the batch carries no edge features (DeviceBatch.e)")
-        return batch
-
-    def _op(self, batch):
-        """The unweighted pattern of the batch, twice: the backward walks its transposed pattern through the entry permutation
-        (DeviceCSR.transpose_perm: the one a device loader's batch arrives with, or built here, once per batch object)."""
-        if self._op_cache is None or self._op_cache[0] != batch.uid:
-            a = batch.a.unweighted()
-            a.transpose_perm()
-            self._op_cache = (batch.uid, a, a)
-        return self._op_cache[1], self._op_cache[2]
+        return host
 
     def _ensure(self, batch, sharded=False):
         bufs = super()._ensure(batch, sharded)
-        d = self.edge_dim or 0
-        if d and (batch.e is None or batch.e.shape != (batch.a.nnz, d)):
-            raise ValueError(f"gcnx.Transformer(edge_dim={d}): the batch's edge features must be [{batch.a.nnz}, {d}], got "
-                             f"{None if batch.e is None else list(batch.e.shape)}")
-        nnz = batch.a.nnz
+        self._check_e(batch)
+        nnz, d = batch.a.nnz, self.edge_dim or 0
         if bufs.get("tf_key") != (batch.n, batch.n_graphs, nnz):           # the edge buffers follow nnz as well as (n, b)
             v, n, h, heads, w = self._views(), batch.n, self.hidden, self.heads, self.width
             if not D.transformer_conv_ok(self.ctx, n, heads, h // heads, ldp=w, edge_dim=d):
@@ -2958,45 +2678,17 @@ class Transformer(GCN):
             bufs["tf_key"] = (batch.n, batch.n_graphs, nnz)
         return bufs
 
-    def _tf_fwd(self, a, x, e, k, bufs, keep):
-        """z_k = TransformerConv_k(x): Q | K | V | S in one product, then scores, softmax, weighted sum and the root connection
-        (with its beta gate) in one launch; keep: alpha and O."""
-        ctx, p, h, w = self.ctx, self.p, self.hidden, self.width
-        pk = bufs[f"p{k}"]
-        D.gemm(ctx, x, p[f"w{k}"], p[f"lb{k}"], pk)
-        D.transformer_aggregate(ctx, a, pk, bufs[f"z{k}"], self.heads, e=e, w_e=p.get(f"we{k}"),
-                                skip=pk.cols(3 * h, w) if self.root_weight else None, w_beta=p.get(f"wb{k}"),
-                                alpha=bufs[f"alpha{k}"] if keep else None, o_pre=bufs[f"o{k}"] if keep else None)
+    def _conv_fwd(self, a, x, k, bufs, keep):
+        p = self.p
+        w, lb, we, wb, pk, alpha, o, z = self._KEYS[k]
+        convs.transformer_forward(self.ctx, a, x, bufs["e"], p[w], p[lb], p.get(we), p.get(wb), bufs[pk], bufs[alpha] if keep else None,
+                                  bufs[o] if keep else None, bufs[z], self.heads)
 
-    def _tf_bwd(self, a, x, e, k, dzk, bufs, dx):
-        """dZ_k -> the gradients of TransformerConv_k and, with dx, the gradient of its input."""
-        ctx, p, g, h, w = self.ctx, self.p, self.g, self.hidden, self.width
-        pk, dp, alpha, o = bufs[f"p{k}"], bufs["dp"], bufs[f"alpha{k}"], bufs[f"o{k}"]
-        d_o, ds = dzk, (dp.cols(3 * h, w) if self.root_weight else None)
-        if self.beta:
-            d_o = bufs["d_o"]
-            D.transformer_beta_bwd(ctx, dzk, o, pk.cols(3 * h, w), p[f"wb{k}"], d_o, ds, g[f"wb{k}"], bufs["scratch"])
-            ds = None
-        D.transformer_bwd_targets(ctx, a, pk, alpha, d_o, o, bufs["dscore"], dp.cols(0, h), self.heads, bufs["scratch"], ds=ds, e=e,
-                                  w_e=p.get(f"we{k}"), dw_e=g.get(f"we{k}"))
-        D.transformer_bwd_sources(ctx, a, pk, alpha, bufs["dscore"], d_o, dp.cols(h, 3 * h), self.heads)
-        D.gemm_dw(ctx, x, dp, g[f"w{k}"])                                            # dW_q | dW_k | dW_v | dW_s = x^T dP
-        D.act_bias_grad(ctx, dp, None, dp, None, db=g[f"lb{k}"])                     # db_q | db_k | db_v | db_s
-        if dx is not None:
-            D.gemm_dx(ctx, dp, p[f"w{k}"], dx)                                       # dx = dP [W_q | W_k | W_v | W_s]^T
-
-    def _conv1(self, a, batch, bufs, mode):
-        bufs["e"] = batch.e if self.uses_edge_features else None                    # (conv2 and the backward read the same rows)
-        self._tf_fwd(a, batch.x, bufs["e"], 1, bufs, mode == "grads")
-
-    def _conv2(self, a, bufs, mode):
-        self._tf_fwd(a, bufs["y1"], bufs["e"], 2, bufs, mode == "grads")
-
-    def _conv2_bwd(self, a_t, bufs):
-        self._tf_bwd(a_t, bufs["y1"], bufs["e"], 2, bufs["dz2"], bufs, bufs["dy1"])
-
-    def _conv1_bwd(self, a_t, batch, bufs):
-        self._tf_bwd(a_t, batch.x, bufs["e"], 1, bufs["dz1"], bufs, None)            # (the input carries no gradient)
+    def _conv_bwd(self, a, x, k, dzk, bufs, dx):
+        p, g = self.p, self.g
+        w, lb, we, wb, pk, alpha, o, _ = self._KEYS[k]
+        convs.transformer_backward(self.ctx, a, x, bufs["e"], bufs[pk], bufs[alpha], bufs[o], dzk, p[w], p.get(we), p.get(wb), g[w], g[lb],
+                                   g.get(we), g.get(wb), bufs["dp"], bufs["dscore"], bufs["d_o"], bufs["scratch"], dx, self.heads)
 
 
 class ECCNet(_GraphRunner):
