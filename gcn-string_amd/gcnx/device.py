@@ -658,6 +658,39 @@ def segment_pool_bwd(ctx, seg, dpooled, dx, mode="sum", argmax=None, y=None, db=
     return dx
 
 
+def attn_pool_scratch_floats(ctx, n, b, f, slice_rows=0):
+    """Floats of scratch that serve attn_pool with this slice_rows and attn_pool_bwd (gcnx_attn_pool_scratch_floats)."""
+    return int(ctx.lib.gcnx_attn_pool_scratch_floats(int(n), int(b), int(f), int(slice_rows)))
+
+
+def attn_pool(ctx, seg, x, a, pooled, alpha=None, scratch=None, slice_rows=0):
+    """pooled[g] = sum_i alpha_i x_i, alpha = softmax over the rows of graph g of <x_i, a> (gcnx_attn_pool).  a: [f] or [f, 1];
+    alpha [n] is stored if given.  slice_rows = 0: the library's route (one workgroup per graph without scratch); > 0: graphs
+    cut into slices of that many rows (needs scratch)."""
+    n, f = x.shape
+    b = seg.n_graphs
+    assert seg.n == n and a.size == f and a.contiguous and pooled.shape == (b, f)
+    assert alpha is None or (alpha.size == n and alpha.contiguous)
+    assert scratch is None or scratch.size >= attn_pool_scratch_floats(ctx, n, b, f, slice_rows)
+    ctx._ck(ctx.lib.gcnx_attn_pool(ctx.h, seg.dev.ptr, _p(x), x.ld, _p(a), n, b, f, int(slice_rows), _p(pooled), pooled.ld,
+                                   _p(alpha), _p(scratch)))
+    return pooled
+
+
+def attn_pool_bwd(ctx, seg, x, a, alpha, pooled, dpooled, dx=None, da=None, scratch=None):
+    """dx [n, f] (written, not accumulated) and da (the shape of a) from alpha and pooled as attn_pool wrote them
+    (gcnx_attn_pool_bwd); either may be None.  scratch: attn_pool_scratch_floats floats, needed for da."""
+    n, f = x.shape
+    b = seg.n_graphs
+    assert seg.n == n and a.size == f and a.contiguous and alpha.size == n and alpha.contiguous
+    assert pooled.shape == dpooled.shape == (b, f) and (dx is None or dx.shape == (n, f))
+    assert da is None or (da.size == f and da.contiguous and scratch is not None)
+    assert scratch is None or scratch.size >= attn_pool_scratch_floats(ctx, n, b, f)
+    ctx._ck(ctx.lib.gcnx_attn_pool_bwd(ctx.h, seg.dev.ptr, _p(x), x.ld, _p(a), _p(alpha), _p(pooled), pooled.ld, _p(dpooled),
+                                       dpooled.ld, n, b, f, _p(dx), dx.ld if dx is not None else 0, _p(da), _p(scratch)))
+    return dx, da
+
+
 def pool_dense_softmax_cce(ctx, seg, x, pooled, w, bias, y, probs, loss_acc=None, denom=None, dw=None, db=None,
                            dpooled=None, mode="sum", argmax=None, db_relu=None, cce="logits"):
     """segment_pool + dense_softmax_cce as one call (gcnx_pool_dense_softmax_cce): ``pooled`` is written as well;

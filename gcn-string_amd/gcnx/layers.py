@@ -1344,6 +1344,46 @@ class GlobalMaxPool(_GlobalPool):
     mode = "max"
 
 
+class GlobalAttnSumPool(Layer):
+    """spektral.layers.pooling.GlobalAttnSumPool in disjoint mode, the learned readout of the module the reference imports its
+    pools from (gcn.py:10); PyG's AttentionalAggregation(gate_nn=Linear(F, 1, bias=False)):
+
+        s_i = <x_i, attn_kernel>        alpha = softmax of s over the rows of each graph        P[g] = sum_i alpha_i x_i
+
+    One parameter, ``attn_kernel`` [F, 1], glorot-uniform (``attn_kernel_initializer="glorot_uniform"``, the Spektral default).
+    ``layer((x, seg))`` with graph ids or a Segments returns pooled [B, F]; an empty graph pools to a zero row.
+    ``backward(dp)`` returns dx [N, F] and leaves d attn_kernel in ``grads``.  Launches: gcnx_attn_pool, gcnx_attn_pool_bwd
+    (csrc/attn_pool.hip): one pass over x forward, one backward, each with a small second launch where it sums parts."""
+
+    def __init__(self, attn_kernel_initializer="glorot_uniform", **kw):
+        super().__init__(**kw)
+        if attn_kernel_initializer != "glorot_uniform":
+            raise NotImplementedError("only the glorot_uniform initialiser (the Spektral default)")
+
+    def _param_spec(self, in_dim):
+        return [("attn_kernel", (in_dim, 1), glorot_uniform(self._rng, in_dim, 1))]
+
+    def call(self, inputs, out=None):
+        x, seg = inputs
+        if not isinstance(seg, D.Segments):
+            seg = D.Segments.from_ids(x.ctx, seg)
+        if not self.built:
+            self.build(x.ctx, x.shape[1])
+        n, f = x.shape
+        pooled = out if out is not None else self._buf("p", (seg.n_graphs, f))
+        alpha = self._buf("alpha", (max(n, 1),))
+        scratch = self._buf("scratch", (max(D.attn_pool_scratch_floats(self.ctx, n, seg.n_graphs, f), 4),))
+        D.attn_pool(self.ctx, seg, x, self.params["attn_kernel"], pooled, alpha.flat(0, n), scratch)
+        self._saved = (x, seg, pooled, alpha.flat(0, n), scratch)
+        return pooled
+
+    def backward(self, dp, need_dx=True, out=None):
+        x, seg, pooled, alpha, scratch = self._saved
+        dx = (out if out is not None else self._buf("dx", x.shape)) if need_dx else None
+        D.attn_pool_bwd(self.ctx, seg, x, self.params["attn_kernel"], alpha, pooled, dp, dx, self.grads["attn_kernel"], scratch)
+        return dx
+
+
 class TopKPool(Layer):
     """spektral.layers.pooling.TopKPool in disjoint mode, the one Spektral layer the reference's script imports (gcn.py:10)
     besides the ones above: hierarchical pooling that keeps the ceil(ratio * n_g) highest-scoring nodes of every graph.

@@ -1424,7 +1424,15 @@ class GCN(_GraphRunner):
     Weights: ``state_dict()`` / ``load_state_dict()`` use torch's key names and layouts; ``get_weights()`` lists the same
     tensors in ``named_parameters()`` order (modules in the reference's __init__ order; inside PyG 2.x GCNConv the bias
     is registered before ``lin.weight``).  That order follows PyG 2.x's source; neither torch_geometric nor the
-    reference's checkpoint was available to confirm it against a live module, so prefer the named dicts."""
+    reference's checkpoint was available to confirm it against a live module, so prefer the named dicts.
+
+    ``readout="attention"`` (every model of the family takes it; default ``"max"``) replaces global_max_pool by the learned
+    readout PyG builds as ``self.pool = AttentionalAggregation(gate_nn=Linear(hidden_channels, 1, bias=False))`` and calls as
+    ``self.pool(x, batch)`` -- Spektral's GlobalAttnSumPool: alpha = softmax over each graph's rows of <y2_i, a>, pooled[g] =
+    sum_i alpha_i y2_i.  It adds one tensor, ``pool.gate_nn.weight`` [1, hidden], LAST in ``state_dict()`` /
+    ``get_weights()`` / ``gradients()`` (after the modules above, as a module registered last), initialised as torch's Linear
+    and drawn after every other tensor, so a seed gives all the others the bits it gives without the readout.  Launches:
+    gcnx_bn_act + gcnx_attn_pool, backward gcnx_attn_pool_bwd + the BN·PReLU backward (csrc/attn_pool.hip)."""
 
     PARAM_ORDER = ("w1", "b1", "g1", "be1", "a1", "w2", "b2", "g2", "be2", "a2",
                    "w3", "b3", "g3", "be3", "a3", "w4", "b4", "g4", "be4", "a4")
@@ -1449,6 +1457,8 @@ class GCN(_GraphRunner):
     HEAD_NOTE = "the one-workgroup head"
     edge_dim = None
     _KEYS = _conv_keys("w", "b", "z")
+    READOUTS = ("max", "attention")
+    READOUT_KEY = ("pool.gate_nn.weight", "ar", False)      # readout="attention": the gate's weight, [1, hidden] in torch's layout
 
     def __init__(self, *args, **kw):
         """GCN([ctx,] hidden_channels=64, num_classes=1, seed=0): the reference's constructor behind an optional ctx."""
@@ -1456,7 +1466,15 @@ class GCN(_GraphRunner):
             ctx, args = args[0], args[1:]
         else:
             ctx = kw.pop("ctx", None)
+        readout = kw.pop("readout", "max")
+        if readout not in self.READOUTS:
+            raise NotImplementedError(f"{self._name}: readout={readout!r} must be \"max\" or \"attention\"")
+        self.readout = readout
         self._init(ctx, *args, **kw)
+        if readout == "attention":      # one more tensor behind everything the class lists: every existing view keeps its offset
+            self.PARAM_ORDER = tuple(self.PARAM_ORDER) + (self.READOUT_KEY[1],)
+            self.TORCH_KEYS = tuple(self.TORCH_KEYS) + (self.READOUT_KEY,)
+            self.LEADING_AXIS = tuple(self.LEADING_AXIS) + (self.READOUT_KEY[0],)
 
     @property
     def _name(self):
@@ -1511,11 +1529,17 @@ class GCN(_GraphRunner):
         if self.hidden > 256:
             raise NotImplementedError(f"{self._name}: hidden_channels <= 256 ({self.HEAD_NOTE})")
         shapes = self._shapes(f_in)
+        attention = self.readout == "attention"
+        if attention:
+            shapes["ar"] = (self.hidden,)
         self.f_in = int(f_in)
         # every parameter starts on a 16-byte boundary (the kernels read the weights, biases and attention vectors as float4);
         # the padding floats have zero gradients, so the single update launch over the whole buffer leaves them at zero
         offs = self._alloc_flat([(k, shapes[k]) for k in self.PARAM_ORDER], align=4)
-        for k, v in self._initial(f_in, shapes, offs).items():
+        initial = self._initial(f_in, shapes, offs)
+        if attention:                       # drawn last: every other tensor keeps the bits its seed gives it
+            initial["ar"] = self._uniform(self.hidden, self.hidden)
+        for k, v in initial.items():
             self.p[k].copy_from_host(np.asarray(v, np.float32))
         self.built = True
 
@@ -1680,6 +1704,10 @@ class GCN(_GraphRunner):
         if sharded:
             nh, nr = D.bce_head_phase_scratch_floats(self.ctx, b, h), D.bce_head_phase_red_floats(self.ctx, h)
             bufs["phase"], bufs["red"] = v("phase", 1, nh).flat(0, nh), v("red", 1, nr).flat(0, nr)
+        if self.readout == "attention":
+            ns = max(D.attn_pool_scratch_floats(self.ctx, n, b, h), 4)
+            bufs["dy2"], bufs["alpha"] = v("dy2", n, h), v("alpha", 1, n).flat(0, n)
+            bufs["attn"] = v("attn", 1, ns).flat(0, ns)
         self._bufs = bufs
         return bufs
 
@@ -1758,7 +1786,10 @@ class GCN(_GraphRunner):
         D.bn_act(ctx, bufs["z1"], bufs["m1"], bufs["i1"], p["g1"], p["be1"], bufs["y1"], act="prelu_shared", alpha=p["a1"])
         self._conv2(a_hat, bufs, mode)
         self._moments(bufs["z2"], bufs["m2"], bufs["i2"], bufs, counts)
-        if self._bn_pool:
+        if self.readout == "attention":
+            D.bn_act(ctx, bufs["z2"], bufs["m2"], bufs["i2"], p["g2"], p["be2"], bufs["y2"], act="prelu_shared", alpha=p["a2"])
+            D.attn_pool(ctx, batch.seg, bufs["y2"], p["ar"], bufs["pooled"], bufs["alpha"], bufs["attn"])
+        elif self._bn_pool:
             D.bn_act_pool(ctx, batch.seg, bufs["z2"], bufs["m2"], bufs["i2"], p["g2"], p["be2"], bufs["pooled"], bufs["arg"],
                           alpha=p["a2"])
         else:
@@ -1796,7 +1827,12 @@ class GCN(_GraphRunner):
     def _backward(self, batch, bufs, counts=None):
         ctx, p, g = self.ctx, self.p, self.g
         _, a_t = self._op(batch)
-        if self._bn_pool and counts is not None:
+        if self.readout == "attention":
+            D.attn_pool_bwd(ctx, batch.seg, bufs["y2"], p["ar"], bufs["alpha"], bufs["pooled"], bufs["dpooled"], bufs["dy2"], g["ar"],
+                            bufs["attn"])
+            self._bn_bwd(bufs["dy2"], bufs["z2"], bufs["m2"], bufs["i2"], p["g2"], p["be2"], p["a2"], bufs["dz2"], g["g2"], g["be2"],
+                         g["a2"], bufs, counts)
+        elif self._bn_pool and counts is not None:
             D.bn_act_pool_bwd_stats(ctx, batch.seg, bufs["dpooled"], bufs["arg"], bufs["z2"], bufs["m2"], bufs["i2"], p["g2"],
                                     p["be2"], bufs["sums"], alpha=p["a2"], dgamma=g["g2"], dbeta=g["be2"], dalpha=g["a2"])
             self.comm.allreduce_sum(bufs["sums"], 3 * self.hidden)

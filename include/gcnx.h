@@ -1153,6 +1153,38 @@ GCNX_API int gcnx_csr_induce(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t
                     const int32_t* idx, const int32_t* pos, int32_t n_kept, int32_t* rowptr_out, int32_t* colidx_out,
                     float* vals_out);
 
+/* ---- GlobalAttnSumPool: the learned readout, a softmax over the rows of every graph ---------------------------------
+ * spektral.layers.pooling.GlobalAttnSumPool, from the module the reference's training script imports (gcn.py:10); PyG's
+ * AttentionalAggregation(gate_nn=Linear(f, 1, bias=False)) -- a bias would cancel in the softmax.  For every graph g of a
+ * disjoint batch (graph_ptr int32[b+1], graph_ptr[0] = 0, graph_ptr[b] = n), x [n, f] (ldx), a [f]:
+ *     s_i = <x_i, a>   alpha_i = exp(s_i - m_g) / l_g (m: the graph's largest score, l: its sum)   P[g] = sum_i alpha_i x_i
+ * One pass over x with a running maximum and sum; the maximum is subtracted before any exponential: no score overflows.
+ * fp32, no float atomics, fixed summation order: the same bits on every call, eager or replayed from a captured graph.
+ * Nothing is allocated, nothing synchronises with the host.  1 <= f <= 256 (GCNX_ERR_INVALID above), any ld >= f: float4 lanes
+ * when f and the leading dimensions are multiples of 4 and x, a, pooled (dpooled, dx) are 16-byte aligned, scalar lanes
+ * otherwise.  An empty graph pools to a zero row (as gcnx_segment_pool); a one-row graph has alpha = 1 and P = its row.
+ * n == 0 or b == 0 succeeds and writes nothing; negative sizes and NULL mandatory pointers are GCNX_ERR_INVALID.
+ * gcnx_attn_pool_scratch_floats (gcn.py:10): floats of caller scratch (16-byte aligned) that serve gcnx_attn_pool with this
+ * slice_rows AND gcnx_attn_pool_bwd; answers without a context. */
+GCNX_API int64_t gcnx_attn_pool_scratch_floats(int64_t n, int32_t b, int32_t f, int32_t slice_rows);
+/* gcn.py:10 -- pooled [b, f] (ldp) and alpha [n] (may be NULL: not stored).  Two routes.  whole: one workgroup per graph, its
+ * waves each walk a share of the rows and combine their (m, l, acc[f]) through LDS.  sliced: graphs taller than slice_rows are
+ * cut into row slices across workgroups, each slice writes (m, l, acc[f]) to scratch, and a second launch rescales and adds
+ * the parts in slice order, writes pooled and turns the stored scores into alpha.  slice_rows == 0: the library chooses --
+ * sliced (slices of at least 64 rows, about two per CU) when b < 2 CUs and the graphs average more than 384 rows, whole
+ * otherwise and whenever scratch is NULL; slice_rows > 0 forces that slice height (any positive value; scratch required). */
+GCNX_API int gcnx_attn_pool(gcnx_ctx* ctx, const int32_t* graph_ptr, const float* x, int64_t ldx, const float* a, int32_t n,
+                   int32_t b, int32_t f, int32_t slice_rows, float* pooled, int64_t ldp, float* alpha, float* scratch);
+/* gcn.py:10 -- backward from alpha and pooled as the forward wrote them and dpooled [b, f] (lddp).  With
+ * t_i = <dP[g], x_i - P[g]>:
+ *     dx_i = alpha_i dP[g] + (alpha_i t_i) a          da = sum_i (alpha_i t_i) x_i
+ * dx [n, f] (lddx; may be NULL) is written, not accumulated, and must not alias x; da [f] (may be NULL; needs scratch) goes
+ * through per-workgroup partial rows in scratch and a second small launch inside this call (fixed order, no atomics).  The
+ * grid goes over row blocks regardless of graph boundaries. */
+GCNX_API int gcnx_attn_pool_bwd(gcnx_ctx* ctx, const int32_t* graph_ptr, const float* x, int64_t ldx, const float* a,
+                       const float* alpha, const float* pooled, int64_t ldp, const float* dpooled, int64_t lddp, int32_t n,
+                       int32_t b, int32_t f, float* dx, int64_t lddx, float* da, float* scratch);
+
 /* ---- aggregation with bf16 features ("fp32 and bf16 both reported") ----
  * out[t, :] = bf16(act(sum_e vals[e] * h[colidx[e], :] + bias)): GCNConv.call's / GeneralConv's aggregation (gcn.py:334) on
  * activations stored as bf16 (uint16_t bit patterns), fp32 accumulation, round-to-nearest-even on the way out; bias fp32
