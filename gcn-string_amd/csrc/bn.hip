@@ -817,7 +817,14 @@ int gcnx_bn_act_pool_bwd(gcnx_ctx* ctx, const int32_t* graph_ptr, int32_t b, con
   GCNX_REQUIRE(ctx, b >= 0 && n >= 0 && f >= 0, "gcnx_bn_act_pool_bwd: negative size");
   GCNX_REQUIRE(ctx, act >= GCNX_ACT_NONE && act <= GCNX_ACT_PRELU_SHARED, "gcnx_bn_act_pool_bwd: unknown activation %d", act);
   if (pool_mode != GCNX_POOL_MAX) return gcnx_fail(ctx, GCNX_ERR_UNSUPPORTED, "gcnx_bn_act_pool_bwd: only GCNX_POOL_MAX is served");
-  if (f == 0 || n == 0) return GCNX_OK;
+  if (f == 0) return GCNX_OK;
+  if (n == 0) {   // no rows: the parameter gradients are zero (as gcnx_bn_act_bwd_stats and gcnx_bn_act_pool_bwd_stats give)
+    if (dbeta) GCNX_HIP(ctx, hipMemsetAsync(dbeta, 0, (size_t)f * 4, ctx->stream));
+    if (dgamma) GCNX_HIP(ctx, hipMemsetAsync(dgamma, 0, (size_t)f * 4, ctx->stream));
+    if (dalpha && act >= GCNX_ACT_PRELU)
+      GCNX_HIP(ctx, hipMemsetAsync(dalpha, 0, (size_t)(act == GCNX_ACT_PRELU_SHARED ? 1 : f) * 4, ctx->stream));
+    return GCNX_OK;
+  }
   GCNX_REQUIRE(ctx, b > 0 && graph_ptr && dpooled && argmax && z && mean && inv && gamma && beta && dz, "gcnx_bn_act_pool_bwd: NULL pointer");
   GCNX_REQUIRE(ctx, act < GCNX_ACT_PRELU || alpha, "gcnx_bn_act_pool_bwd: PReLU needs alpha");
   GCNX_REQUIRE(ctx, ldz >= f && lddz >= f && lddp >= f, "gcnx_bn_act_pool_bwd: leading dimension too small");

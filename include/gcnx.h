@@ -507,7 +507,10 @@ GCNX_API int gcnx_bn_act_pool(gcnx_ctx* ctx, const int32_t* graph_ptr, int32_t b
  * mean, inv: dZ [n, f] = gamma * inv * (dzb - sum(dzb) / n - xhat * sum(dzb * xhat) / n) with dzb nonzero only at the
  * argmax rows, and dgamma / dbeta [f], dalpha ([f] for PRELU, [1] for PRELU_SHARED) -- each may be NULL.  Two launches (the
  * three column sums come from the b * f argmax entries alone, then one dense write of dZ).  graph_ptr must cover the rows:
- * graph_ptr[0] = 0, graph_ptr[b] = n (rows outside every graph are not written).  pool_mode: GCNX_POOL_MAX only. */
+ * graph_ptr[0] = 0, graph_ptr[b] = n (rows outside every graph are not written).  pool_mode: GCNX_POOL_MAX only.
+ * n == 0 (an empty shard) with f > 0: nothing is launched and no other pointer is read; dgamma / dbeta and, under
+ * PRELU / PRELU_SHARED, dalpha ([f] / [1]) are set to zero where given, as gcnx_bn_act_bwd_stats does for n == 0 and
+ * gcnx_bn_act_pool_bwd_stats for graphs that are all empty. */
 GCNX_API int gcnx_bn_act_pool_bwd(gcnx_ctx* ctx, const int32_t* graph_ptr, int32_t b, const float* dpooled, int64_t lddp,
                          const int32_t* argmax, const float* z, int64_t ldz, int64_t n, int32_t f, const float* mean,
                          const float* inv, const float* gamma, const float* beta, int act, const float* alpha, int pool_mode,
