@@ -202,6 +202,10 @@ SIGNATURES = {
     "gcnx_attn_pool_scratch_floats": [_i64, _i32, _i32, _i32],
     "gcnx_attn_pool": [_vp, _vp, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp],
     "gcnx_attn_pool_bwd": [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp, _i64, _vp, _vp],
+    "gcnx_graph_norm_scratch_floats": [_i64, _i32, _i32, _i32],
+    "gcnx_graph_norm_act": [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _f32, _int, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp],
+    "gcnx_graph_norm_act_bwd": [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _int, _vp, _i32, _i32, _i32, _i32, _vp, _i64,
+                                _vp, _vp, _vp, _vp, _vp],
     "gcnx_comm_unique_id": [C.c_char_p],
     "gcnx_comm_init_rank": [_vp, C.c_char_p, _int, _int, C.POINTER(_vp)],
     "gcnx_comm_destroy": [_vp],
@@ -210,7 +214,7 @@ SIGNATURES = {
 _RESTYPE = {"gcnx_last_error": C.c_char_p, "gcnx_dense_bwd_scratch_floats": C.c_int64, "gcnx_bce_head_scratch_floats": C.c_int64,
             "gcnx_bce_head_phase_scratch_floats": C.c_int64, "gcnx_bce_head_phase_red_floats": C.c_int64,
             "gcnx_gcn_conv_bwd_scratch_floats": C.c_int64, "gcnx_gat_bwd_scratch_floats": C.c_int64, "gcnx_gatv2_bwd_scratch_floats": C.c_int64, "gcnx_wimage_elems": C.c_int64, "gcnx_gemm_wimage_parts": C.c_int64,
-            "gcnx_attn_pool_scratch_floats": C.c_int64}
+            "gcnx_attn_pool_scratch_floats": C.c_int64, "gcnx_graph_norm_scratch_floats": C.c_int64}
 
 
 class WimageJob(C.Structure):

@@ -1596,6 +1596,42 @@ def spmm_minmax_bwd(ctx, at, h, out, cnt, dy, dh, mode="max"):
 TORCH_BN_EPS = 1e-5                  # torch.nn.BatchNorm1d default
 
 
+def graph_norm_scratch_floats(ctx, n, b, f, slice_rows=0):
+    """Floats of scratch that serve graph_norm_act and graph_norm_act_bwd with this slice_rows (gcnx_graph_norm_scratch_floats)."""
+    return int(ctx.lib.gcnx_graph_norm_scratch_floats(int(n), int(b), int(f), int(slice_rows)))
+
+
+def graph_norm_act(ctx, seg, z, mean_scale, gamma, beta, y, mean, inv, act=None, alpha=None, scratch=None, slice_rows=0,
+                   eps=TORCH_BN_EPS):
+    """y = act(gamma * (z - mean_scale * mu_g) * inv_g + beta) with the statistics of each graph's own rows, and the per-graph
+    mean / inv [b, f] (gcnx_graph_norm_act).  act: None or "prelu_shared" with its slope alpha.  y may be z.  slice_rows = 0:
+    the library's route (one workgroup per graph without scratch); > 0: graphs cut into slices of that many rows (needs scratch)."""
+    n, f = z.shape
+    b = seg.n_graphs
+    assert seg.n == n and y.shape == (n, f) and all(t.size == f and t.contiguous for t in (mean_scale, gamma, beta))
+    assert mean.shape == inv.shape == (b, f) and mean.contiguous and inv.contiguous
+    assert scratch is None or scratch.size >= graph_norm_scratch_floats(ctx, n, b, f, slice_rows)
+    ctx._ck(ctx.lib.gcnx_graph_norm_act(ctx.h, seg.dev.ptr, _p(z), z.ld, _p(mean_scale), _p(gamma), _p(beta), float(eps), L.ACTS[act],
+                                        _p(alpha), n, b, f, int(slice_rows), _p(y), y.ld, _p(mean), _p(inv), _p(scratch)))
+    return y
+
+
+def graph_norm_act_bwd(ctx, seg, dy, z, mean, inv, mean_scale, gamma, beta, dz, act=None, alpha=None, dgamma=None, dbeta=None,
+                       dmean_scale=None, dalpha=None, scratch=None, slice_rows=0):
+    """dz [n, f] (written, not accumulated; may be dy) and the parameter gradients, each of which may be None, from z, mean and
+    inv as graph_norm_act left them (gcnx_graph_norm_act_bwd)."""
+    n, f = z.shape
+    b = seg.n_graphs
+    assert seg.n == n and dy.shape == dz.shape == (n, f) and all(t.size == f and t.contiguous for t in (mean_scale, gamma, beta))
+    assert mean.shape == inv.shape == (b, f) and mean.contiguous and inv.contiguous
+    assert all(t is None or (t.size == f and t.contiguous) for t in (dgamma, dbeta, dmean_scale))
+    assert scratch is None or scratch.size >= graph_norm_scratch_floats(ctx, n, b, f, slice_rows)
+    ctx._ck(ctx.lib.gcnx_graph_norm_act_bwd(ctx.h, seg.dev.ptr, _p(dy), dy.ld, _p(z), z.ld, _p(mean), _p(inv), _p(mean_scale),
+                                            _p(gamma), _p(beta), L.ACTS[act], _p(alpha), n, b, f, int(slice_rows), _p(dz), dz.ld,
+                                            _p(dgamma), _p(dbeta), _p(dmean_scale), _p(dalpha), _p(scratch)))
+    return dz
+
+
 def bn_act_pool(ctx, seg, z, mean, inv, gamma, beta, pooled, argmax, act="prelu_shared", alpha=None, mode="max"):
     """pooled[g] = max over graph g's rows of act(BN(z)) and its argmax rows, in one pass (gcnx_bn_act_pool)."""
     n, f = z.shape

@@ -1517,6 +1517,48 @@ class BatchNorm1d(Layer):
         return dx
 
 
+class GraphNorm(Layer):
+    """torch_geometric.nn.GraphNorm(F, eps=1e-5) (Cai et al. 2021) in disjoint mode: per graph and per channel
+
+        mu = mean_i x_i        o_i = x_i - mean_scale * mu        y_i = weight * o_i / sqrt(mean_i o_i^2 + eps) + bias
+
+    Parameters ``weight`` (1), ``bias`` (0), ``mean_scale`` (1), each [F], in PyG's registration order.  Training and
+    evaluation are the same.  ``layer((x, seg))`` with graph ids or a Segments returns y [N, F]; one row is legal (a one-row
+    graph gives y = bias at mean_scale = 1), an empty graph contributes nothing.  ``backward(dy)`` returns dx [N, F] and leaves
+    the three gradients in ``grads``.  Launches: gcnx_graph_norm_act, gcnx_graph_norm_act_bwd (csrc/graph_norm.hip)."""
+
+    def __init__(self, eps=D.TORCH_BN_EPS, **kw):
+        super().__init__(**kw)
+        self.eps = float(eps)
+
+    def _param_spec(self, in_dim):
+        one = np.ones(in_dim, np.float32)
+        return [("weight", (in_dim,), one), ("bias", (in_dim,), np.zeros(in_dim, np.float32)), ("mean_scale", (in_dim,), one)]
+
+    def call(self, inputs, out=None):
+        x, seg = inputs
+        if not isinstance(seg, D.Segments):
+            seg = D.Segments.from_ids(x.ctx, seg)
+        if not self.built:
+            self.build(x.ctx, x.shape[1])
+        n, f = x.shape
+        b, p = seg.n_graphs, self.params
+        mean, inv = self._buf("mean", (b, f)), self._buf("inv", (b, f))
+        scratch = self._buf("scratch", (max(D.graph_norm_scratch_floats(self.ctx, n, b, f), 4),))
+        y = out if out is not None else self._buf("y", (n, f))
+        D.graph_norm_act(self.ctx, seg, x, p["mean_scale"], p["weight"], p["bias"], y, mean, inv, scratch=scratch, eps=self.eps)
+        self._saved = (x, seg, mean, inv, scratch)
+        return y
+
+    def backward(self, dy, need_dx=True):
+        x, seg, mean, inv, scratch = self._saved
+        p, g = self.params, self.grads
+        dx = self._buf("dx", x.shape)
+        D.graph_norm_act_bwd(self.ctx, seg, dy, x, mean, inv, p["mean_scale"], p["weight"], p["bias"], dx, dgamma=g["weight"],
+                             dbeta=g["bias"], dmean_scale=g["mean_scale"], scratch=scratch)
+        return dx
+
+
 class PReLU(Layer):
     """torch.nn.PReLU(): y = max(0, x) + a * min(0, x) with ONE slope a for every feature (init 0.25);
     ``grads["weight"]`` = sum over all elements of dY * min(x, 0).  Runs on gcnx_bn_act(_bwd) with an identity

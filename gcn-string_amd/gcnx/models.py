@@ -1432,7 +1432,18 @@ class GCN(_GraphRunner):
     sum_i alpha_i y2_i.  It adds one tensor, ``pool.gate_nn.weight`` [1, hidden], LAST in ``state_dict()`` /
     ``get_weights()`` / ``gradients()`` (after the modules above, as a module registered last), initialised as torch's Linear
     and drawn after every other tensor, so a seed gives all the others the bits it gives without the readout.  Launches:
-    gcnx_bn_act + gcnx_attn_pool, backward gcnx_attn_pool_bwd + the BN·PReLU backward (csrc/attn_pool.hip)."""
+    gcnx_bn_act + gcnx_attn_pool, backward gcnx_attn_pool_bwd + the BN·PReLU backward (csrc/attn_pool.hip).
+
+    ``norm="graph"`` (every model of the family takes it; default ``"batch"``) replaces the two node-level norms
+    ``batch_norm_1`` / ``batch_norm_2`` by PyG's ``GraphNorm(hidden_channels)``: statistics per graph and per channel, with a
+    learned share ``mean_scale`` of the mean removed ("GraphNorm"), so the node-level part of a graph's forward no
+    longer depends on which graphs share its batch.  ``batch_norm_3`` / ``batch_norm_4`` run on pooled rows and stay
+    BatchNorm1d, so a batch of one graph still raises.  It adds two tensors, ``batch_norm_{1,2}.mean_scale`` [hidden], each
+    directly behind its ``.bias`` in ``state_dict()`` / ``get_weights()`` / ``gradients()`` and behind the class's list (before
+    the attention gate) in the flat buffer; they start at 1 without a draw, so a seed gives every other tensor the bits it
+    gives with ``norm="batch"``.  Launches: gcnx_graph_norm_act (GraphNorm·PReLU) per norm and gcnx_graph_norm_act_bwd
+    (csrc/graph_norm.hip), the readout as its own launch (gcnx_segment_pool(max) or gcnx_attn_pool).  With ``comm=`` the
+    node norms run on the shard's own rows without an all-reduce: 6 of the 13 all-reduces of a sync-BN step are gone."""
 
     PARAM_ORDER = ("w1", "b1", "g1", "be1", "a1", "w2", "b2", "g2", "be2", "a2",
                    "w3", "b3", "g3", "be3", "a3", "w4", "b4", "g4", "be4", "a4")
@@ -1459,6 +1470,7 @@ class GCN(_GraphRunner):
     _KEYS = _conv_keys("w", "b", "z")
     READOUTS = ("max", "attention")
     READOUT_KEY = ("pool.gate_nn.weight", "ar", False)      # readout="attention": the gate's weight, [1, hidden] in torch's layout
+    NORMS = ("batch", "graph")
 
     def __init__(self, *args, **kw):
         """GCN([ctx,] hidden_channels=64, num_classes=1, seed=0): the reference's constructor behind an optional ctx."""
@@ -1470,7 +1482,19 @@ class GCN(_GraphRunner):
         if readout not in self.READOUTS:
             raise NotImplementedError(f"{self._name}: readout={readout!r} must be \"max\" or \"attention\"")
         self.readout = readout
+        norm = kw.pop("norm", "batch")
+        if norm not in self.NORMS:
+            raise NotImplementedError(f"{self._name}: norm={norm!r} must be \"batch\" or \"graph\"")
+        self.norm = norm
         self._init(ctx, *args, **kw)
+        if norm == "graph":             # batch_norm_{1,2}.mean_scale: behind the class's list, and behind its .bias as torch names them
+            self.PARAM_ORDER = tuple(self.PARAM_ORDER) + ("ms1", "ms2")
+            keys = []
+            for entry in self.TORCH_KEYS:
+                keys.append(entry)
+                if entry[1] in ("be1", "be2"):
+                    keys.append((f"batch_norm_{entry[1][2]}.mean_scale", "ms" + entry[1][2], False))
+            self.TORCH_KEYS = tuple(keys)
         if readout == "attention":      # one more tensor behind everything the class lists: every existing view keeps its offset
             self.PARAM_ORDER = tuple(self.PARAM_ORDER) + (self.READOUT_KEY[1],)
             self.TORCH_KEYS = tuple(self.TORCH_KEYS) + (self.READOUT_KEY,)
@@ -1532,6 +1556,9 @@ class GCN(_GraphRunner):
         attention = self.readout == "attention"
         if attention:
             shapes["ar"] = (self.hidden,)
+        graph_norm = self.norm == "graph"
+        if graph_norm:
+            shapes["ms1"] = shapes["ms2"] = (self.hidden,)
         self.f_in = int(f_in)
         # every parameter starts on a 16-byte boundary (the kernels read the weights, biases and attention vectors as float4);
         # the padding floats have zero gradients, so the single update launch over the whole buffer leaves them at zero
@@ -1539,6 +1566,8 @@ class GCN(_GraphRunner):
         initial = self._initial(f_in, shapes, offs)
         if attention:                       # drawn last: every other tensor keeps the bits its seed gives it
             initial["ar"] = self._uniform(self.hidden, self.hidden)
+        if graph_norm:                      # no draw from the RNG
+            initial["ms1"] = initial["ms2"] = np.ones(self.hidden)
         for k, v in initial.items():
             self.p[k].copy_from_host(np.asarray(v, np.float32))
         self.built = True
@@ -1708,6 +1737,11 @@ class GCN(_GraphRunner):
             ns = max(D.attn_pool_scratch_floats(self.ctx, n, b, h), 4)
             bufs["dy2"], bufs["alpha"] = v("dy2", n, h), v("alpha", 1, n).flat(0, n)
             bufs["attn"] = v("attn", 1, ns).flat(0, ns)
+        if self.norm == "graph":            # the per-graph statistics of both node norms, and one scratch for their launches
+            ns = max(D.graph_norm_scratch_floats(self.ctx, n, b, h), 4)
+            for k in ("gm1", "gi1", "gm2", "gi2"):
+                bufs[k] = v(k, b, h)
+            bufs["gn"] = v("gn", 1, ns).flat(0, ns)
         self._bufs = bufs
         return bufs
 
@@ -1781,20 +1815,31 @@ class GCN(_GraphRunner):
         global (N, B) of a sync-BN training step over graph shards (None: this batch's own statistics)."""
         ctx, p, e = self.ctx, self.p, self.EPS
         a_hat, _ = self._op(batch)
+        graph_norm = self.norm == "graph"
         self._conv1(a_hat, batch, bufs, mode)
-        self._moments(bufs["z1"], bufs["m1"], bufs["i1"], bufs, counts)
-        D.bn_act(ctx, bufs["z1"], bufs["m1"], bufs["i1"], p["g1"], p["be1"], bufs["y1"], act="prelu_shared", alpha=p["a1"])
-        self._conv2(a_hat, bufs, mode)
-        self._moments(bufs["z2"], bufs["m2"], bufs["i2"], bufs, counts)
-        if self.readout == "attention":
-            D.bn_act(ctx, bufs["z2"], bufs["m2"], bufs["i2"], p["g2"], p["be2"], bufs["y2"], act="prelu_shared", alpha=p["a2"])
-            D.attn_pool(ctx, batch.seg, bufs["y2"], p["ar"], bufs["pooled"], bufs["alpha"], bufs["attn"])
-        elif self._bn_pool:
-            D.bn_act_pool(ctx, batch.seg, bufs["z2"], bufs["m2"], bufs["i2"], p["g2"], p["be2"], bufs["pooled"], bufs["arg"],
-                          alpha=p["a2"])
+        if graph_norm:                       # each graph's own statistics: nothing to all-reduce, sharded or not
+            self._graph_norm(batch, bufs, 1)
         else:
-            D.bn_act(ctx, bufs["z2"], bufs["m2"], bufs["i2"], p["g2"], p["be2"], bufs["y2"], act="prelu_shared", alpha=p["a2"])
-            D.segment_pool(ctx, batch.seg, bufs["y2"], bufs["pooled"], "max", bufs["arg"])
+            self._moments(bufs["z1"], bufs["m1"], bufs["i1"], bufs, counts)
+            D.bn_act(ctx, bufs["z1"], bufs["m1"], bufs["i1"], p["g1"], p["be1"], bufs["y1"], act="prelu_shared", alpha=p["a1"])
+        self._conv2(a_hat, bufs, mode)
+        if graph_norm:
+            self._graph_norm(batch, bufs, 2)
+            if self.readout == "attention":
+                D.attn_pool(ctx, batch.seg, bufs["y2"], p["ar"], bufs["pooled"], bufs["alpha"], bufs["attn"])
+            else:
+                D.segment_pool(ctx, batch.seg, bufs["y2"], bufs["pooled"], "max", bufs["arg"])
+        else:
+            self._moments(bufs["z2"], bufs["m2"], bufs["i2"], bufs, counts)
+            if self.readout == "attention":
+                D.bn_act(ctx, bufs["z2"], bufs["m2"], bufs["i2"], p["g2"], p["be2"], bufs["y2"], act="prelu_shared", alpha=p["a2"])
+                D.attn_pool(ctx, batch.seg, bufs["y2"], p["ar"], bufs["pooled"], bufs["alpha"], bufs["attn"])
+            elif self._bn_pool:
+                D.bn_act_pool(ctx, batch.seg, bufs["z2"], bufs["m2"], bufs["i2"], p["g2"], p["be2"], bufs["pooled"], bufs["arg"],
+                              alpha=p["a2"])
+            else:
+                D.bn_act(ctx, bufs["z2"], bufs["m2"], bufs["i2"], p["g2"], p["be2"], bufs["y2"], act="prelu_shared", alpha=p["a2"])
+                D.segment_pool(ctx, batch.seg, bufs["y2"], bufs["pooled"], "max", bufs["arg"])
         y = batch.y if mode != "fwd" else None
         if y is None and mode != "fwd":
             raise ValueError("gcnx.GCN: labels are needed for the loss")
@@ -1812,6 +1857,19 @@ class GCN(_GraphRunner):
             if k < 6:
                 self.comm.allreduce_sum(bufs["red"].flat(*D.bce_head_phase_slice(k, self.hidden)))
 
+    def _graph_norm(self, batch, bufs, k):
+        """GraphNorm_k·PReLU_k: z_k -> y_k, the per-graph mean and inv kept for the backward."""
+        p = self.p
+        D.graph_norm_act(self.ctx, batch.seg, bufs[f"z{k}"], p[f"ms{k}"], p[f"g{k}"], p[f"be{k}"], bufs[f"y{k}"], bufs[f"gm{k}"],
+                         bufs[f"gi{k}"], act="prelu_shared", alpha=p[f"a{k}"], scratch=bufs["gn"], eps=self.EPS)
+
+    def _graph_norm_bwd(self, batch, bufs, k, dy):
+        """dY_k -> dZ_k and the gradients of GraphNorm_k (weight, bias, mean_scale) and PReLU_k."""
+        p, g = self.p, self.g
+        D.graph_norm_act_bwd(self.ctx, batch.seg, dy, bufs[f"z{k}"], bufs[f"gm{k}"], bufs[f"gi{k}"], p[f"ms{k}"], p[f"g{k}"],
+                             p[f"be{k}"], bufs[f"dz{k}"], act="prelu_shared", alpha=p[f"a{k}"], dgamma=g[f"g{k}"], dbeta=g[f"be{k}"],
+                             dmean_scale=g[f"ms{k}"], dalpha=g[f"a{k}"], scratch=bufs["gn"])
+
     def _bn_bwd(self, dy, z, mean, inv, gamma, beta, alpha, dz, g_gamma, g_beta, g_alpha, bufs, counts):
         """BN·PReLU backward over the rows of z; with counts (sync-BN) the column sums all-reduced between the two halves."""
         ctx = self.ctx
@@ -1827,6 +1885,18 @@ class GCN(_GraphRunner):
     def _backward(self, batch, bufs, counts=None):
         ctx, p, g = self.ctx, self.p, self.g
         _, a_t = self._op(batch)
+        if self.norm == "graph":
+            if self.readout == "attention":
+                D.attn_pool_bwd(ctx, batch.seg, bufs["y2"], p["ar"], bufs["alpha"], bufs["pooled"], bufs["dpooled"], bufs["dy2"],
+                                g["ar"], bufs["attn"])
+                self._graph_norm_bwd(batch, bufs, 2, bufs["dy2"])
+            else:
+                D.segment_pool_bwd(ctx, batch.seg, bufs["dpooled"], bufs["y2"], "max", bufs["arg"])
+                self._graph_norm_bwd(batch, bufs, 2, bufs["y2"])
+            self._conv2_bwd(a_t, bufs)
+            self._graph_norm_bwd(batch, bufs, 1, bufs["dy1"])
+            self._conv1_bwd(a_t, batch, bufs)
+            return
         if self.readout == "attention":
             D.attn_pool_bwd(ctx, batch.seg, bufs["y2"], p["ar"], bufs["alpha"], bufs["pooled"], bufs["dpooled"], bufs["dy2"], g["ar"],
                             bufs["attn"])

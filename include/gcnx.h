@@ -1188,6 +1188,47 @@ GCNX_API int gcnx_attn_pool_bwd(gcnx_ctx* ctx, const int32_t* graph_ptr, const f
                        const float* alpha, const float* pooled, int64_t ldp, const float* dpooled, int64_t lddp, int32_t n,
                        int32_t b, int32_t f, float* dx, int64_t lddx, float* da, float* scratch);
 
+/* ---- GraphNorm: per-graph normalisation in the slot of the node-level BatchNorms (gcn_utills.py:816-826) ----
+ * torch_geometric.nn.GraphNorm(f, eps) (Cai et al. 2021) in place of the reference's batch_norm_1 / batch_norm_2
+ * (gcn_utills.py:816-817, applied at 832-838), fused with the PReLU behind them (gcn_utills.py:820-821).  For every graph g of a
+ * disjoint batch (graph_ptr int32[b+1], graph_ptr[0] = 0, graph_ptr[b] = n) with m rows, per channel, with mean_scale a [f],
+ * gamma [f], beta [f]:
+ *     mu = mean_i z_i   o_i = z_i - a mu   v = mean_i o_i^2   r = 1 / sqrt(v + eps)   xh_i = o_i r   y_i = act(gamma xh_i + beta)
+ * Training and evaluation are the same (no running statistics).  v is the mean of the centred squares, from a second walk
+ * over the graph's rows; it is never formed as a difference of moments.  A one-row graph is legal (y = beta exactly at a = 1);
+ * an empty graph has no rows, contributes nothing, and its mean / inv rows are written as zero.
+ * fp32, no float atomics, fixed summation order: the same bits on every call.  Nothing synchronises with the host.
+ * 1 <= f <= 256 (GCNX_ERR_INVALID above), any ld >= f: float4 lanes when f and the leading dimensions are multiples of 4 and
+ * every operand is 16-byte aligned, scalar lanes otherwise.  act: GCNX_ACT_NONE, or GCNX_ACT_PRELU_SHARED with its slope
+ * alpha[1]; any other act is GCNX_ERR_UNSUPPORTED with nothing launched.  n == 0, b == 0 or f == 0 succeeds and writes
+ * nothing; negative sizes and NULL mandatory pointers are GCNX_ERR_INVALID.
+ * Two routes per direction.  whole: one workgroup per graph walks its rows three times forward (sum, centred squares, y) and
+ * twice backward (sums, dz); no scratch.  sliced: slices of slice_rows rows are spread across workgroups, per-slice partial
+ * rows go to scratch and every workgroup of a graph adds them in slice order; three launches forward, two backward.
+ * slice_rows == 0: the library chooses by gcnx_attn_pool's rule -- sliced (slices of at least 64 rows, about two per CU) when
+ * b < 2 CUs and the graphs average more than 384 rows, whole otherwise and whenever scratch is NULL; slice_rows > 0 forces that
+ * slice height (any positive value; scratch required).
+ * gcnx_graph_norm_scratch_floats (gcn_utills.py:816-826): floats of caller scratch (16-byte aligned) that serve both launches
+ * below with this slice_rows; answers without a context. */
+GCNX_API int64_t gcnx_graph_norm_scratch_floats(int64_t n, int32_t b, int32_t f, int32_t slice_rows);
+/* gcn_utills.py:816-826 -- z [n, f] (ldz) -> y [n, f] (ldy; may alias z exactly) and the per-graph mean [b, f], inv [b, f]
+ * (contiguous rows) that the backward reads. */
+GCNX_API int gcnx_graph_norm_act(gcnx_ctx* ctx, const int32_t* graph_ptr, const float* z, int64_t ldz, const float* mean_scale,
+                        const float* gamma, const float* beta, float eps, int act, const float* alpha, int32_t n, int32_t b,
+                        int32_t f, int32_t slice_rows, float* y, int64_t ldy, float* mean, float* inv, float* scratch);
+/* gcn_utills.py:816-826 -- backward from dy [n, f] (lddy) and the saved z, mean, inv; t is recomputed from them as
+ * gcnx_bn_act_bwd does.  With dt_i = dy_i act'(t_i), S1 = sum_i dt_i, S2 = sum_i dt_i xh_i over the graph's m rows:
+ *     D = r gamma (S1 - S2 r mu (1 - a))        dz_i = r gamma (dt_i - xh_i S2 / m) - a D / m
+ *     dgamma = sum_g S2   dbeta = sum_g S1   dmean_scale = - sum_g mu D   dalpha[0] = sum_i dy_i min(t_i, 0)
+ * dz [n, f] (lddz) is written, not accumulated, and may alias dy exactly.  dgamma, dbeta, dmean_scale [f] and dalpha [1] may
+ * each be NULL; they are summed over the graphs from per-graph rows in the ctx workspace by one small launch inside this call
+ * (fixed order, no atomics; dalpha is written as zero for GCNX_ACT_NONE). */
+GCNX_API int gcnx_graph_norm_act_bwd(gcnx_ctx* ctx, const int32_t* graph_ptr, const float* dy, int64_t lddy, const float* z,
+                            int64_t ldz, const float* mean, const float* inv, const float* mean_scale, const float* gamma,
+                            const float* beta, int act, const float* alpha, int32_t n, int32_t b, int32_t f, int32_t slice_rows,
+                            float* dz, int64_t lddz, float* dgamma, float* dbeta, float* dmean_scale, float* dalpha,
+                            float* scratch);
+
 /* ---- aggregation with bf16 features ("fp32 and bf16 both reported") ----
  * out[t, :] = bf16(act(sum_e vals[e] * h[colidx[e], :] + bias)): GCNConv.call's / GeneralConv's aggregation (gcn.py:334) on
  * activations stored as bf16 (uint16_t bit patterns), fp32 accumulation, round-to-nearest-even on the way out; bias fp32
