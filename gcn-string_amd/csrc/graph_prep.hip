@@ -303,7 +303,11 @@ int gcnx_csr_transpose(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* coli
       GCNX_HIP(ctx, hipMemcpyAsync(v.data(), vals, v.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
     }
     GCNX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (rp[n] != nnz) return gcnx_fail(ctx, GCNX_ERR_DATA, "gcnx_csr_transpose: rowptr[n]=%d != nnz=%d", rp[n], nnz);
+    // the counting sort below walks ci[rp[r] .. rp[r + 1]): only over a well-formed rowptr (as gcnx_csr_transpose_perm)
+    if (rp[0] != 0 || rp[n] != nnz)
+      return gcnx_fail(ctx, GCNX_ERR_DATA, "gcnx_csr_transpose: rowptr[0]=%d, rowptr[n]=%d != nnz=%d", rp[0], rp[n], nnz);
+    for (int32_t r = 0; r < n; ++r)
+      if (rp[r + 1] < rp[r]) return gcnx_fail(ctx, GCNX_ERR_DATA, "gcnx_csr_transpose: rowptr decreases at row %d", r);
     for (int32_t e = 0; e < nnz; ++e) {
       if (ci[e] < 0 || ci[e] >= n) return gcnx_fail(ctx, GCNX_ERR_DATA, "gcnx_csr_transpose: colidx[%d]=%d out of range", e, ci[e]);
       rpt[(size_t)ci[e] + 1]++;

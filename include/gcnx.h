@@ -132,7 +132,9 @@ GCNX_API int gcnx_graph_destroy(gcnx_ctx* ctx, gcnx_graph* g);
 /* ---- graph preparation ------------------------------------------------------------------ */
 /* DisjointLoader's SparseTensor (gcn.py:316-317 -> sp_matrix_to_sp_tensor + tf.sparse.reorder):
  * row-major sorted COO int64 (rows[nnz], cols[nnz]) on the DEVICE -> CSR int32.  Synchronises.
- * Fails with GCNX_ERR_DATA if rows are not non-decreasing or an index is outside [0,N). */
+ * Fails with GCNX_ERR_DATA if rows are not non-decreasing or an index is outside [0,N); rowptr[0..N] and colidx[0..nnz)
+ * are then unspecified, and nothing outside them is written in either case.  Duplicate (row, col) pairs are kept as stored.
+ * N and nnz must be below 2^31 - 1 (GCNX_ERR_INVALID before anything is launched); N == 0 writes rowptr[0] = 0. */
 GCNX_API int gcnx_coo_to_csr(gcnx_ctx* ctx, const int64_t* rows, const int64_t* cols, int64_t nnz,
                     int64_t n, int32_t* rowptr, int32_t* colidx);
 /* Device-side collate (what DisjointLoader's collate -- vstack / block_diag / find, gcn.py:316-317,367 -- does on
@@ -141,7 +143,11 @@ GCNX_API int gcnx_coo_to_csr(gcnx_ctx* ctx, const int64_t* rows, const int64_t* 
  * ids (one pad), then the batch's node offsets [b+1], then its entry offsets [b+1] (host prefix sums over the
  * selected sizes).  Writes the batch: o_x[N, f], o_rowptr[N+1], o_colidx / o_vals[nnz], o_y[b, c],
  * o_graph_ptr[b+1], and (o_node_graph may be NULL) DisjointLoader's id vector i[N] = the batch position of every row's
- * graph.  Integer outputs are exact; floats are copies. */
+ * graph.  Integer outputs are exact; floats are copies.  vals / o_vals are given together or both NULL; y == NULL writes no
+ * labels; f == 0 needs no x / o_x.  Nothing else is written: padding columns (ldo > f) and whatever lies past N + 1 / nnz / b
+ * rows stay as they were.  b == 0 writes nothing.  Does not synchronise.
+ * Contract, NOT validated (the arrays live on the device): desc holds graph ids in [0, G) and the prefix sums of exactly
+ * those graphs' sizes, node_ptr / rowptr are well-formed, and the outputs hold N + 1 / nnz / N x ldo / b x c elements. */
 GCNX_API int gcnx_collate(gcnx_ctx* ctx, const int32_t* desc, int32_t b, const int32_t* node_ptr, const int32_t* rowptr,
                  const int32_t* colidx, const float* vals, const float* x, int64_t ldx, int32_t f, const float* y,
                  int32_t c, int32_t* o_rowptr, int32_t* o_colidx, float* o_vals, float* o_x, int64_t ldo, float* o_y,
@@ -168,8 +174,11 @@ GCNX_API int gcnx_collate_edges(gcnx_ctx* ctx, const int32_t* desc, int32_t b, c
 /* Spektral GCNConv.preprocess = gcn_filter on a CSR whose every row stores its
  * diagonal entry (true for the reference's data: gcn_utills.py:224-227 keeps the 0-Angstrom
  * diagonal).  vals_in NULL = ones.  SPEKTRAL: diag += 1; PYG: existing loops kept.
- * vals_out[e] = a~[e] * d^-1/2[row] * d^-1/2[col].  Synchronises; GCNX_ERR_DATA if a row has
- * no stored diagonal. */
+ * vals_out[e] = a~[e] * d^-1/2[row] * d^-1/2[col], d^-1/2 := 0 where the degree is <= 0.  vals_out may be vals_in
+ * (in place: every entry is read and written by the same thread).  Synchronises; GCNX_ERR_DATA if a row has
+ * no stored diagonal (vals_out is then unspecified).  n == 0 returns GCNX_OK and touches nothing.
+ * Contract, NOT validated: rowptr is a well-formed CSR row pointer (rowptr[0] == 0, non-decreasing) and every column
+ * index lies in [0, n) -- what gcnx_coo_to_csr produces; anything else reads out of bounds. */
 GCNX_API int gcnx_gcn_norm(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx,
                   const float* vals_in, int32_t n, int mode, float* vals_out);
 /* What the scheduling shortcuts may assume about a batch adjacency, checked once per batch on the device (the
@@ -180,20 +189,27 @@ GCNX_API int gcnx_gcn_norm(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* 
  *   GCNX_CSR_GRAPH_PTR_OK    graph_ptr[0] == 0, graph_ptr[b] == n, non-decreasing;
  *   GCNX_CSR_BLOCK_DIAGONAL  every entry of a row of graph g has its column in [graph_ptr[g], graph_ptr[g+1]): the
  *                            premise of gcnx_spmm_plan_create and gcnx_spmm_csr_pool_bwd (sp.block_diag).
- * graph_ptr may be NULL (only symmetry is checked).  Synchronises. */
+ * graph_ptr may be NULL (only symmetry is checked).  A graph_ptr that fails GRAPH_PTR_OK also clears BLOCK_DIAGONAL and is not
+ * read any further; SYMMETRIC is still reported as the matrix has it.  A column index outside [0, n) is not followed: it
+ * clears SYMMETRIC and BLOCK_DIAGONAL.  n == 0: every requested bit is reported.  Synchronises.
+ * Contract, NOT validated: rowptr is a well-formed CSR row pointer (rowptr[0] == 0, non-decreasing, rowptr[n] entries
+ * readable in colidx / vals). */
 #define GCNX_CSR_SYMMETRIC 1
 #define GCNX_CSR_BLOCK_DIAGONAL 2
 #define GCNX_CSR_GRAPH_PTR_OK 4
 GCNX_API int gcnx_csr_inspect(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, const float* vals, int32_t n,
                      const int32_t* graph_ptr, int32_t b, int* props);
-/* CSR of the transpose (for the backward SpMM when A^ is not symmetric).  Synchronises. */
+/* CSR of the transpose (for the backward SpMM when A^ is not symmetric).  Stable counting sort on the host: a column's
+ * entries keep their stored order, vals_t follows them bit for bit.  vals and vals_t are given together or both NULL.
+ * Validated on the host before the sort, each GCNX_ERR_DATA with nothing written: rowptr[0] == 0, rowptr non-decreasing,
+ * rowptr[n] == nnz, every column index in [0, n) -- the same checks as gcnx_csr_transpose_perm.  Synchronises. */
 GCNX_API int gcnx_csr_transpose(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx,
                        const float* vals, int32_t n, int32_t nnz, int32_t* rowptr_t,
                        int32_t* colidx_t, float* vals_t);
 /* gcnx_csr_transpose of the pattern that also returns where every transposed entry came from: perm_t[p] = index of the
  * entry of the original CSR that became entry p of the transpose -- the row of per-entry data (edge features) that
  * belongs to it.  Integers throughout (entry numbers carried as float values stop being exact at 2^24).  Stable
- * counting sort; synchronises. */
+ * counting sort; validates rowptr and colidx as gcnx_csr_transpose does (GCNX_ERR_DATA, nothing written); synchronises. */
 GCNX_API int gcnx_csr_transpose_perm(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, int32_t n, int32_t nnz,
                             int32_t* rowptr_t, int32_t* colidx_t, int32_t* perm_t);
 

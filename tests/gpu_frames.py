@@ -1,5 +1,6 @@
 """Helpers shared by the GPU tests that compare bit for bit inside sentinel frames (tests/test_gpu_reduce_routes.py,
-tests/test_gpu_elementwise_routes.py, tests/test_gpu_spmm_routes.py)."""
+tests/test_gpu_elementwise_routes.py, tests/test_gpu_spmm_routes.py, tests/test_gpu_graph_prep.py: there a 1-D array is a one-row
+frame)."""
 import numpy as np
 
 SENTINEL = np.float32(12345.0)
