@@ -164,6 +164,13 @@ SIGNATURES = {
     "gcnx_gin_conv": [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _int, _vp, _i64, _vp, _i64, _vp, _i64],
     "gcnx_gin_aggregate": [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32],
     "gcnx_gin_eps_grad": [_vp, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _vp],
+    "gcnx_gine_conv_ok": [_i64, _i32, _i32, _i32, _i64, _i32],
+    "gcnx_gine_conv": [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _i64,
+                       _vp, _i64, _vp, _i64],
+    "gcnx_gine_aggregate": [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _i32, _i32],
+    "gcnx_gine_bwd_scratch_floats": [_i64, _i32, _i32],
+    "gcnx_gine_bwd_edges": [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp],
+    "gcnx_gine_bwd_nodes": [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _i32],
     "gcnx_pna_aggregate": [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _f32, _vp, _i64, _vp, _i64, _i32, _i32],
     "gcnx_pna_bwd_scratch_floats": [_i64, _i32, C.POINTER(_i64)],
     "gcnx_pna_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _f32, _vp, _i64, _vp, _i32, _i32],
@@ -214,7 +221,8 @@ SIGNATURES = {
 _RESTYPE = {"gcnx_last_error": C.c_char_p, "gcnx_dense_bwd_scratch_floats": C.c_int64, "gcnx_bce_head_scratch_floats": C.c_int64,
             "gcnx_bce_head_phase_scratch_floats": C.c_int64, "gcnx_bce_head_phase_red_floats": C.c_int64,
             "gcnx_gcn_conv_bwd_scratch_floats": C.c_int64, "gcnx_gat_bwd_scratch_floats": C.c_int64, "gcnx_gatv2_bwd_scratch_floats": C.c_int64, "gcnx_wimage_elems": C.c_int64, "gcnx_gemm_wimage_parts": C.c_int64,
-            "gcnx_attn_pool_scratch_floats": C.c_int64, "gcnx_graph_norm_scratch_floats": C.c_int64}
+            "gcnx_attn_pool_scratch_floats": C.c_int64, "gcnx_graph_norm_scratch_floats": C.c_int64,
+            "gcnx_gine_bwd_scratch_floats": C.c_int64}
 
 
 class WimageJob(C.Structure):

@@ -1,5 +1,5 @@
 """The launch sequences of the convolutions that a layer (gcnx.layers) and a model (gcnx.models) both run: PNAConv, GATConv,
-GATv2Conv, ResGatedGraphConv and TransformerConv.  This is the one place they are written down.
+GATv2Conv, ResGatedGraphConv, TransformerConv and GINEConv.  This is the one place they are written down.
 
 One forward and one backward function per convolution, plain functions over operands: ``ctx``, the pattern, the operands, the
 parameter views, the gradient views, every scratch and output buffer, then the scalars.  The caller owns the storage, the
@@ -9,7 +9,8 @@ validates.  An optional operand is ``None`` and drops exactly its launch or argu
 stored [in, out].  ``h`` below is the convolution's output width (heads * channels); whether a stacked P = ... | S carries the
 root block S is read off its width (4 h, or 3 h without root_weight).
 
-SAGEConv and GINConv are not here: layer and model choose their one-launch route by different predicates."""
+SAGEConv and GINConv are not here: layer and model choose their one-launch route by different predicates.  GINEConv's two
+routes are here; the caller decides between them (``one_launch``) by its own predicate."""
 from __future__ import annotations
 
 from . import device as D
@@ -149,3 +150,33 @@ def transformer_backward(ctx, a, x, e, pk, alpha, o_pre, dz, w, w_e, w_beta, g_w
         D.act_bias_grad(ctx, dp, None, dp, None, db=g_lin_bias)                            # the stacked bias: column sums
     if dx is not None:
         D.gemm_dx(ctx, dp, w, dx)                                                          # dx = dP [W_q | W_k | W_v | W_s]^T
+
+
+# ---- GINEConv ----------------------------------------------------------------------------------------------------------------
+def gine_forward(ctx, a, x, e, eps, w_e, b_e, w_a, b_a, w_b, b_b, t, u, out, one_launch, keep=True):
+    """out = relu(T W_a + b_a) W_b + b_b, T = (1 + eps) x + sum_j relu(x_j + e_ij W_e + b_e).  one_launch: gcnx_gine_conv, which
+    stores T and U = relu(T W_a + b_a) into t and u only with ``keep`` (a backward follows); otherwise the composed route, which
+    passes through t and u either way."""
+    if one_launch:
+        D.gine_conv(ctx, a, x, eps, e, w_e, b_e, w_a, b_a, w_b, b_b, out, t=t if keep else None, u=u if keep else None)
+        return
+    D.gine_aggregate(ctx, a, x, eps, e, w_e, b_e, t)
+    D.gemm(ctx, t, w_a, b_a, u, act="relu")
+    D.gemm(ctx, u, w_b, b_b, out)
+
+
+def gine_backward(ctx, a, x, e, eps, t, u, dz, w_e, b_e, w_a, w_b, g_eps, g_w_e, g_b_e, g_w_a, g_b_a, g_w_b, g_b_b, du, dt, scratch,
+                  eps_parts, dx):
+    """From dz: the gradients of both MLP layers, of W_e and b_e, of eps (g_eps None: eps is not trained) and, with dx, the
+    gradient of the input.  a carries its transposed pattern (DeviceCSR.transpose_perm); du [n, k1] and dt [n, k0] are scratch,
+    scratch: gine_bwd_scratch_floats, eps_parts: gin_eps_grad_parts (needed with g_eps only)."""
+    if g_b_b is not None:
+        D.act_bias_grad(ctx, dz, None, dz, None, db=g_b_b)                                 # db_b: column sums of dZ
+    D.gemm_dx(ctx, dz, w_b, du, y_mask=u, db=g_b_a)                                        # dU = (dZ W_b^T) * [U > 0], db_a
+    D.gemm_dw2(ctx, u, dz, g_w_b, t, du, g_w_a)                                            # dW_b = U^T dZ, dW_a = T^T dU
+    D.gemm_dx(ctx, du, w_a, dt)                                                            # dT = dU W_a^T
+    D.gine_bwd_edges(ctx, a, x, e, w_e, b_e, dt, g_w_e, g_b_e, scratch)                    # dW_e, db_e (forward CSR)
+    if g_eps is not None:
+        D.gin_eps_grad(ctx, x, dt, eps_parts, g_eps)                                       # d eps = sum <x, dT>
+    if dx is not None:
+        D.gine_bwd_nodes(ctx, a, x, eps, e, w_e, b_e, dt, dx)                              # dx (transposed pattern + permutation)

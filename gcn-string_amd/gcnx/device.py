@@ -870,6 +870,72 @@ def gin_eps_grad(ctx, x, dt, parts, deps):
     return deps
 
 
+def gine_conv_ok(ctx, n, k0, k1, k2, ldx=None, edge_dim=1):
+    """True if gine_conv serves these shapes (gcnx_gine_conv_ok; answers without a context: ctx only carries the library)."""
+    return bool(ctx.lib.gcnx_gine_conv_ok(int(n), int(k0), int(k1), int(k2), int(ldx if ldx is not None else k0), int(edge_dim)))
+
+
+def _gine_edge(a, e, w_e, b_e, f):
+    """(e pointer, lde, edge_dim, w_e pointer, b_e pointer) of the edge operands: e [nnz, D] (any ld), w_e [D, f], b_e [f] or None."""
+    d = e.shape[1]
+    assert e.shape[0] == a.nnz and w_e.shape == (d, f) and w_e.contiguous and (b_e is None or b_e.shape == (f,))
+    return _p(e), e.ld, d, _p(w_e), _p(b_e)
+
+
+def gine_conv(ctx, a, x, eps, e, w_e, b_e, w_a, b_a, w_b, b_b, out, t=None, u=None):
+    """out = relu(T w_a + b_a) w_b + b_b with T = (1 + eps) x + sum_j relu(x_j + e_ij w_e + b_e) in one launch (gcnx_gine_conv);
+    the sum runs over the stored entries of ``a`` (row = target), its values are not read; e [nnz, D] in the entry order.  eps: a
+    device array of one float, or None (0).  t / u (optional) receive T and relu(T w_a + b_a)."""
+    n, k0 = x.shape
+    k1, k2 = w_a.shape[1], w_b.shape[1]
+    assert a.n == n and w_a.shape == (k0, k1) and w_a.contiguous and w_b.shape == (k1, k2) and w_b.contiguous
+    assert out.shape == (n, k2) and (t is None or t.shape == (n, k0)) and (u is None or u.shape == (n, k1))
+    assert (b_a is None or b_a.shape == (k1,)) and (b_b is None or b_b.shape == (k2,)) and (eps is None or eps.size == 1)
+    ep, lde, d, wp, bp = _gine_edge(a, e, w_e, b_e, k0)
+    ctx._ck(ctx.lib.gcnx_gine_conv(ctx.h, a.rowptr.ptr, a.colidx.ptr, _p(x), x.ld, n, k0, _p(eps), ep, lde, d, wp, bp, _p(w_a), _p(b_a),
+                                   k1, _p(w_b), _p(b_b), k2, _p(t), t.ld if t is not None else 0, _p(u),
+                                   u.ld if u is not None else 0, _p(out), out.ld))
+    return out
+
+
+def gine_aggregate(ctx, a, x, eps, e, w_e, b_e, out):
+    """out = (1 + eps) x + sum_j relu(x_j + e_ij w_e + b_e) for any width (gcnx_gine_aggregate).  out must not alias x."""
+    n, f = x.shape
+    assert a.n == n and out.shape == (n, f) and (eps is None or eps.size == 1)
+    ep, lde, d, wp, bp = _gine_edge(a, e, w_e, b_e, f)
+    ctx._ck(ctx.lib.gcnx_gine_aggregate(ctx.h, a.rowptr.ptr, a.colidx.ptr, _p(x), x.ld, _p(eps), ep, lde, d, wp, bp, _p(out), out.ld, n, f))
+    return out
+
+
+def gine_bwd_scratch_floats(ctx, n, f, edge_dim):
+    """Floats of scratch gine_bwd_edges needs (gcnx_gine_bwd_scratch_floats)."""
+    return int(ctx.lib.gcnx_gine_bwd_scratch_floats(int(n), int(f), int(edge_dim)))
+
+
+def gine_bwd_edges(ctx, a, x, e, w_e, b_e, dt, dw_e, db_e, scratch):
+    """dw_e [D, f] and db_e [f] (None: not wanted) from dt = dT on the forward pattern of ``a`` (gcnx_gine_bwd_edges): written, not
+    accumulated.  scratch: gine_bwd_scratch_floats floats."""
+    n, f = x.shape
+    ep, lde, d, wp, bp = _gine_edge(a, e, w_e, b_e, f)
+    assert a.n == n and dt.shape == (n, f) and dw_e.shape == (d, f) and dw_e.contiguous and (db_e is None or db_e.shape == (f,))
+    assert scratch.size >= gine_bwd_scratch_floats(ctx, n, f, d)
+    ctx._ck(ctx.lib.gcnx_gine_bwd_edges(ctx.h, a.rowptr.ptr, a.colidx.ptr, _p(x), x.ld, ep, lde, d, wp, bp, _p(dt), dt.ld, n, f, _p(dw_e),
+                                        _p(db_e), _p(scratch)))
+    return dw_e
+
+
+def gine_bwd_nodes(ctx, a, x, eps, e, w_e, b_e, dt, dx):
+    """dx = (1 + eps) dT + the masked dT of every target, on the transposed pattern of ``a`` with its entry permutation
+    (a.transpose_perm(); gcnx_gine_bwd_nodes).  dx must not alias dt or x."""
+    n, f = x.shape
+    ep, lde, d, wp, bp = _gine_edge(a, e, w_e, b_e, f)
+    assert a.n == n and dt.shape == dx.shape == (n, f) and (eps is None or eps.size == 1)
+    rp, ci, pm = a.transpose_perm()
+    ctx._ck(ctx.lib.gcnx_gine_bwd_nodes(ctx.h, rp.ptr, ci.ptr, pm.ptr, _p(x), x.ld, _p(eps), ep, lde, d, wp, bp, _p(dt), dt.ld, _p(dx),
+                                        dx.ld, n, f))
+    return dx
+
+
 def pna_aggregate(ctx, a, x, pq, avg_deg_log, c, stats=None):
     """c [n, 13f] = [x | A | s_amp A | s_att A], A = [mean | min | max | std] of the messages P_i + Q_j over the stored
     entries of every row of ``a`` (gcnx_pna_aggregate); pq [n, 2f] = P | Q.  stats [n, 6f] (optional) receives

@@ -8,6 +8,7 @@ Reference topology: GCNConv -> GCNConv -> global pool -> Linear (gcn_utills.py:8
 ``SAGEConv(channels, root_weight=True, use_bias=True)`` is PyG's layer of that name (aggr="mean"), which the reference
 names as its next step (gcn_utills.py:804-806); ``GATConv(channels, heads=1)`` is PyG's attention layer for the same slot.
 ``GINConv(channels, mlp_hidden=None, eps=0.0, train_eps=False)`` is PyG's / Spektral's Graph Isomorphism Network layer for it.
+``GINEConv(channels, edge_dim, mlp_hidden=None, eps=0.0, train_eps=False)`` is PyG's GINEConv: GIN whose neighbour sum reads the edge features (gcn.py:71).
 ``PNAConv(channels, deg=None, avg_deg_log=None)`` is PyG's PNAConv with the mean / min / max / std aggregators and the three degree scalers.
 ``GATv2Conv(channels, heads=1, edge_dim=None)`` is PyG's GATv2Conv: attention whose scores read the edge features (gcn.py:71).
 ``ResGatedGraphConv(channels, edge_dim=None, root_weight=True)`` is PyG's gated layer: per-channel sigmoid gates that read the edge features.
@@ -387,6 +388,83 @@ class GINConv(Layer):
             D.gin_eps_grad(ctx, x, dt, parts, g["eps"])                             # d eps = sum <x, dT>
         if need_dx:
             D.gin_aggregate(ctx, a.transpose(), dt, self._eps(), dx)                # dX = (1 + eps) dT + A^T dT
+        return dx
+
+
+class GINEConv(GINConv):
+    """torch_geometric.nn.GINEConv(Sequential(Linear(in, mlp_hidden), ReLU(), Linear(mlp_hidden, channels)), eps, train_eps,
+    edge_dim) (Hu et al.): GINConv whose neighbour sum reads the edge features -- the dca / proximity values the reference
+    computes on every contact and bridge and its model drops (gcn_utills.py:319-443; gcn.py:71):
+
+        out_i = MLP((1 + eps) x_i + sum_{j in N(i)} relu(x_j + lin(e_ij))),   lin = Linear(edge_dim, in),  MLP = Linear -> ReLU -> Linear
+
+    ``GINEConv(channels, edge_dim, mlp_hidden=None, eps=0.0, train_eps=False, use_bias=True, activation=None, fused=True)``,
+    called as ``layer([x, a, e])`` with ``a = GINEConv.preprocess(a)`` and e [nnz, edge_dim], row k belonging to stored entry k
+    of ``a``: the pattern and e are used as stored, no loop is added or removed, values are ignored.  edge_dim is 1 .. 8;
+    ``edge_dim=None`` (PyG: e already as wide as x) and any activation raise NotImplementedError.  Parameters under PyG's names:
+    ``eps`` (only with train_eps), ``nn.0.weight``, ``nn.0.bias``, ``nn.2.weight``, ``nn.2.bias``, ``lin.weight`` (stored
+    [edge_dim, in]; PyG: [in, edge_dim]), ``lin.bias``; use_bias=False drops the three biases.  The order follows PyG's source
+    (eps, nn.*, lin.*); it was not confirmed against a live torch_geometric: prefer the names.  Initialisation
+    U(+-1/sqrt(fan_in)) as torch's Linear (lin: fan_in = edge_dim).  Own storage starts every tensor on a 4-float boundary, as
+    GINConv's.  ``backward(dy, need_dx=True)`` returns dx (None with need_dx=False) and leaves every gradient in ``grads``.
+
+    Launches (gine_forward / gine_backward of gcnx/convs.py, which the model runs too; csrc/gine.hip): one gcnx_gine_conv where
+    it serves the shapes, otherwise gcnx_gine_aggregate, gcnx_gemm(act=relu), gcnx_gemm; backward gcnx_act_bias_grad,
+    gcnx_gemm_dx(y_mask=U, db), gcnx_gemm_dw2, gcnx_gemm_dx -> dT, gcnx_gine_bwd_edges, gcnx_gin_eps_grad (train_eps),
+    gcnx_gine_bwd_nodes (need_dx)."""
+
+    def __init__(self, channels, edge_dim, mlp_hidden=None, eps=0.0, train_eps=False, use_bias=True, activation=None, fused=True, **kw):
+        if activation not in (None, "linear"):
+            raise NotImplementedError(f"GINEConv activation {activation!r}: the layer ends in its MLP's second Linear (follow it with "
+                                      "BatchNorm1d / PReLU)")
+        if edge_dim is None or not 1 <= int(edge_dim) <= 8:
+            raise NotImplementedError(f"GINEConv edge_dim={edge_dim}: the kernels serve 1 to 8 edge features through lin = "
+                                      "Linear(edge_dim, in) (None, e already as wide as x, has no kernel)")
+        super().__init__(channels, mlp_hidden, eps, train_eps, use_bias, activation, fused, **kw)
+        self.edge_dim = int(edge_dim)
+
+    def _param_spec(self, in_dim):
+        d = self.edge_dim
+        u = lambda *s: self._rng.uniform(-1.0 / np.sqrt(d), 1.0 / np.sqrt(d), s).astype(np.float32)
+        spec = super()._param_spec(in_dim)
+        spec.append(("lin.weight", (d, in_dim), u(d, in_dim)))
+        if self.use_bias:
+            spec.append(("lin.bias", (in_dim,), u(in_dim)))
+        return spec
+
+    def _one_launch(self, x, k1, k2, *others):
+        p = self.params
+        return (self.fused and D.gine_conv_ok(self.ctx, x.shape[0], x.shape[1], k1, k2, x.ld, self.edge_dim)
+                and _aligned16(x, p["nn.0.weight"], p["nn.2.weight"], p["lin.weight"], p.get("lin.bias"), *others)
+                and all(o.ld % 4 == 0 for o in others))
+
+    def call(self, inputs, out=None):
+        if len(inputs) != 3:
+            raise ValueError(f"GINEConv(edge_dim={self.edge_dim}) takes [x, a, e]")
+        x, a, e = inputs
+        if tuple(e.shape) != (a.nnz, self.edge_dim):
+            raise ValueError(f"GINEConv(edge_dim={self.edge_dim}): e must be [{a.nnz}, {self.edge_dim}] (one row per stored entry), "
+                             f"got {list(e.shape)}")
+        if not self.built:
+            self.build(x.ctx, x.shape[1])
+        ctx, n, c, m, p = self.ctx, x.shape[0], self.channels, self.mlp_hidden, self.params
+        y = out if out is not None else self._buf("y", (n, c))
+        t, u = self._buf("t", (n, x.shape[1])), self._buf("u", (n, m))
+        convs.gine_forward(ctx, a, x, e, self._eps(), p["lin.weight"], p.get("lin.bias"), p["nn.0.weight"], p.get("nn.0.bias"),
+                           p["nn.2.weight"], p.get("nn.2.bias"), t, u, y, self._one_launch(x, m, c, y, t, u))
+        self._saved = (x, a, e, t, u)
+        return y
+
+    def backward(self, dy, need_dx=True):
+        x, a, e, t, u = self._saved
+        ctx, p, g, (n, f) = self.ctx, self.params, self.grads, x.shape
+        du, dt = self._buf("du", u.shape), self._buf("dt", x.shape)
+        scratch = self._buf("scratch", (max(D.gine_bwd_scratch_floats(ctx, n, f, self.edge_dim), 4),))
+        parts = self._buf("eps_parts", (D.gin_eps_grad_parts(n),)) if self.train_eps else None
+        dx = self._buf("dx", x.shape) if need_dx else None
+        convs.gine_backward(ctx, a, x, e, self._eps(), t, u, dy, p["lin.weight"], p.get("lin.bias"), p["nn.0.weight"], p["nn.2.weight"],
+                            g.get("eps"), g["lin.weight"], g.get("lin.bias"), g["nn.0.weight"], g.get("nn.0.bias"), g["nn.2.weight"],
+                            g.get("nn.2.bias"), du, dt, scratch, parts, dx)
         return dx
 
 

@@ -18,6 +18,8 @@ above them (gcn_utills.py:804-806); one launch per convolution (csrc/sage.hip).
 
 ``GIN``: ``GCN`` with PyG's GINConv(Sequential(Linear, ReLU, Linear), train_eps) in the place of both GCNConv layers: sum
 aggregation and a two-layer MLP, one launch per convolution (csrc/gin.hip).
+``GINE``: ``GIN`` with PyG's GINEConv(edge_dim): every message is relu(x_j + lin(e_ij)), the cheapest way to read the edge
+features (csrc/gine.hip); trains from the same batches as ``ResGated``.
 
 ``PNA``: ``GCN`` with PyG's PNAConv(mean / min / max / std, identity / amplification / attenuation) in the place of both
 GCNConv layers: four statistics of every neighbourhood from one gather (csrc/pna.hip).
@@ -2195,6 +2197,103 @@ class GIN(GCN):
                 return
             D.gemm_dx(ctx, du, p[wa], dt)
             D.gin_aggregate(ctx, a_t, dt, self._eps(k), dx)
+
+
+class GINE(GIN):
+    """``GIN`` whose neighbour sum reads the edge features: both convolutions are PyG's GINEConv(Sequential(Linear, ReLU, Linear),
+    train_eps, edge_dim=D) (Hu et al.) -- the cheapest way to use the dca / proximity values the reference computes on every
+    contact and bridge and its model drops (gcn_utills.py:319-443; gcn.py:71): one add and one ReLU per gathered element,
+
+        out_i = MLP((1 + eps) x_i + sum_{j in N(i)} relu(x_j + lin(e_ij))),   lin = Linear(D, in)
+
+        GINEConv(F->H)·BN·PReLU -> GINEConv(H->H)·BN·PReLU -> global_max_pool -> Linear(H->H)·BN·PReLU -> Linear(H->1)·BN·PReLU
+
+    ``GINE([ctx,] hidden_channels=64, edge_dim=2, train_eps=False, num_classes=1, seed=0)``; edge_dim 1 .. 8 (None, PyG's "e is
+    already as wide as x", has no kernel).  The model reads ``batch.e`` (``uses_edge_features``): inputs are (x, a, e, i), a
+    DeviceBatch that carries e, or the batches of DeviceDisjointLoader(DeviceDataset(..., edge_features=True)), which arrive
+    with e and the transposed pattern gathered on the device.  The pattern and e are used as stored on every route: no
+    self-loop is added or removed, a stored one is one more neighbour with its own features.  Everything behind the
+    convolutions is ``GCN``'s (readout="attention" and norm="graph" included); eps, its place in ``state_dict()`` and the flat
+    buffer are ``GIN``'s.  One device: ``comm`` is refused.
+
+    Hot path per convolution (gine_forward / gine_backward of gcnx/convs.py, the one place the sequence is written;
+    gcnx.GINEConv runs the same two functions): gcnx_gine_conv, one launch (csrc/gine.hip), which keeps T and U; backward
+    gcnx_act_bias_grad, gcnx_gemm_dx(y_mask=U, db), gcnx_gemm_dw2, gcnx_gemm_dx -> dT, gcnx_gine_bwd_edges (forward CSR: dW_e,
+    db_e), gcnx_gin_eps_grad (train_eps) and, for conv2 only, gcnx_gine_bwd_nodes (transposed pattern + entry permutation).
+    GCNX_GINE_FUSED=0 (read at construction), and any shape gcnx_gine_conv refuses (hidden > 128; a gathered width outside
+    {16, 32, 64, 128}), takes the composed route per launch: gcnx_gine_aggregate, gcnx_gemm(relu), gcnx_gemm.
+
+    Weights: ``GIN``'s keys and, behind each convolution's ``nn.*``, ``conv{1,2}.lin.weight`` ([in, D] as torch; stored [D, in])
+    and ``conv{1,2}.lin.bias``.  The key order follows PyG's source (eps, nn.*, lin.*); it was not confirmed against a live
+    torch_geometric: prefer the named dicts.  Initialisation U(+-1/sqrt(fan_in)) as torch's Linear (lin: fan_in = D), eps 0."""
+
+    OPERATOR, SELF_LOOPS, KERNELS = "perm", False, "GINEConv"
+    _KEYS = _conv_keys("wa", "ba", "wb", "bb", "z", "t", "u", "dt", "e", "we", "bl")
+    uses_edge_features = True
+
+    def _init(self, ctx, hidden_channels=64, edge_dim=2, train_eps=False, num_classes=1, seed=0, comm=None):
+        self._one_device(comm)
+        if edge_dim is None:
+            raise NotImplementedError(f"{self._name}: edge_dim=None (edge features already as wide as the input) has no kernel; "
+                                      "edge_dim must be 1 .. 8")
+        self.edge_dim = self._check_edge_dim(edge_dim)
+        super()._init(ctx, hidden_channels, train_eps, num_classes, seed, None)
+        self._fused = os.environ.get("GCNX_GINE_FUSED", "1") != "0"    # knob, read once
+        conv = lambda k: ((f"e{k}",) if self.train_eps else ()) + (f"wa{k}", f"ba{k}", f"wb{k}", f"bb{k}", f"we{k}", f"bl{k}",
+                                                                   f"g{k}", f"be{k}", f"a{k}")
+        self.PARAM_ORDER = conv(1) + conv(2) + GCN.PARAM_ORDER[10:]
+        keys = lambda k: (self.EPS_KEYS[k - 1:k] if self.train_eps else ()) + (
+            (f"conv{k}.nn.0.weight", f"wa{k}", True), (f"conv{k}.nn.0.bias", f"ba{k}", False),
+            (f"conv{k}.nn.2.weight", f"wb{k}", True), (f"conv{k}.nn.2.bias", f"bb{k}", False),
+            (f"conv{k}.lin.weight", f"we{k}", True), (f"conv{k}.lin.bias", f"bl{k}", False))
+        self.TORCH_KEYS = keys(1) + keys(2) + GCN.TORCH_KEYS[4:]
+
+    def _shapes(self, f_in):
+        s = super()._shapes(f_in)
+        h, d = self.hidden, self.edge_dim
+        s.update(we1=(d, f_in), we2=(d, h), bl1=(f_in,), bl2=(h,))
+        return s
+
+    def _initial(self, f_in, shapes, offs):
+        if not self.train_eps:                  # (as GIN: the two constants outside the flat buffers)
+            self._eps_fixed = self.ctx.zeros(8)
+        h, d, u = self.hidden, self.edge_dim, self._uniform
+        init = {}
+        for k, f in ((1, f_in), (2, h)):        # drawn in PyG's order per convolution: nn.0, nn.2, lin
+            init[f"wa{k}"], init[f"ba{k}"] = u(f, f, h), u(f, h)
+            init[f"wb{k}"], init[f"bb{k}"] = u(h, h, h), u(h, h)
+            init[f"we{k}"], init[f"bl{k}"] = u(d, d, f), u(d, f)
+        init.update(self._head_initial(shapes))
+        return init
+
+    def _ensure(self, batch, sharded=False):
+        bufs = super()._ensure(batch, sharded)
+        self._check_e(batch)
+        if "gine_scratch" not in bufs:
+            v, n = self._views(), batch.n
+            if "dt1" not in bufs:                # (GIN forms dT of conv1 with train_eps only; here dW_e needs it always)
+                bufs["dt1"] = v("dt1", n, batch.f)
+            ns = max(D.gine_bwd_scratch_floats(self.ctx, n, max(batch.f, self.hidden), self.edge_dim), 4)
+            bufs["gine_scratch"] = v("gine_scratch", 1, ns).flat(0, ns)
+        return bufs
+
+    def _one_launch(self, x, k1, k2, *others):
+        return (self._fused and D.gine_conv_ok(self.ctx, x.shape[0], x.shape[1], k1, k2, x.ld, self.edge_dim)
+                and all(a.ptr % 16 == 0 and a.ld % 4 == 0 for a in (x,) + others))
+
+    def _conv_fwd(self, a, x, k, bufs, keep):
+        p = self.p
+        wa, ba, wb, bb, z, t, u, _, _, we, bl = self._KEYS[k]
+        out, t, u = bufs[z], bufs[t], bufs[u]
+        convs.gine_forward(self.ctx, a, x, bufs["e"], self._eps(k), p[we], p[bl], p[wa], p[ba], p[wb], p[bb], t, u, out,
+                           self._one_launch(x, p[wa].shape[1], p[wb].shape[1], out, t, u), keep)
+
+    def _conv_bwd(self, a, x, k, dz, bufs, dx):
+        p, g = self.p, self.g
+        wa, ba, wb, bb, _, t, u, dt, e, we, bl = self._KEYS[k]
+        convs.gine_backward(self.ctx, a, x, bufs["e"], self._eps(k), bufs[t], bufs[u], dz, p[we], p[bl], p[wa], p[wb],
+                            g[e] if self.train_eps else None, g[we], g[bl], g[wa], g[ba], g[wb], g[bb], bufs["h1"], bufs[dt],
+                            bufs["gine_scratch"], bufs.get("eps_parts"), dx)
 
 
 class PNA(GCN):

@@ -861,6 +861,71 @@ GCNX_API int gcnx_gin_aggregate(gcnx_ctx* ctx, const int32_t* rowptr, const int3
 GCNX_API int gcnx_gin_eps_grad(gcnx_ctx* ctx, const float* x, int64_t ldx, const float* dt, int64_t lddt, int64_t n, int32_t f,
                       float* parts, float* deps);
 
+/* ---- GINEConv: GINConv whose neighbour sum reads the edge features, small-feature regime (widths <= 128) ----------------
+ * PyG's GINEConv(nn = Sequential(Linear, ReLU, Linear), eps, train_eps, edge_dim): the cheapest way to put the dca /
+ * proximity features the reference computes on every contact and bridge and its model drops (gcn_utills.py:319-443;
+ * gcn.py:71) into a message -- one add and one ReLU per gathered element, no softmax, no gate, no weight matrix per edge.
+ * CSR row i is the target, its stored entries j are the sources.  Values are ignored; the pattern and e are used as stored: no
+ * loop is added or removed, a stored self-loop is one more neighbour with its own features.  e [nnz, edge_dim] (lde) holds the
+ * entries' features in the CSR's entry order, w_e [edge_dim, k0] and b_e [k0] (may be NULL) are PyG's lin, 1 <= edge_dim <= 8.
+ * Per entry and channel c, in fp32, EXACTLY as written (contract; every product and every sum rounded on its own, no FMA):
+ *     t = rn(e[0] w_e[0,c]);  t = rn(t + rn(e[d] w_e[d,c]))  for d = 1 .. edge_dim - 1, in that order
+ *     v = rn(t + b_e[c])          (b_e NULL: v = t)
+ *     m = rn(x_j[c] + v)          msg = m > 0 ? m : 0     (the positive side is m > 0; m == 0 is the zero side, gradient 0)
+ * m is stored nowhere: gcnx_gine_conv, gcnx_gine_aggregate, gcnx_gine_bwd_edges and gcnx_gine_bwd_nodes recompute it and
+ * therefore agree on the side of every kink, and float32 arithmetic on the stored operands reproduces it.  Forward:
+ *     S_i = sum_j msg_ij          in CSR order from +0
+ *     T_i = fma(1 + *eps, x_i, S_i)       (a row without entries has T = (1 + eps) x exactly)
+ *     U = relu(T w_a + b_a)  [n, k1]      out = U w_b + b_b  [n, k2]
+ * Backward, with dT = dU w_a^T (gcnx_gemm_dx) and g_ij = dT_i * [m_ij > 0]:
+ *     db_e = sum_ij g_ij     dw_e[d,:] = sum_ij e_ij[d] g_ij     dx_j = (1 + eps) dT_j + sum_{i : j in N(i)} g_ij
+ *     d eps = sum_i <x_i, dT_i>   (gcnx_gin_eps_grad)
+ * fp32, no float atomics, fixed summation order: the same bits on every call.  Nothing is allocated: every call can be
+ * captured.  n == 0 succeeds and writes nothing (gcnx_gine_bwd_edges then writes zeros to its two gradients); negative sizes,
+ * NULL mandatory pointers and aliasing are GCNX_ERR_INVALID, as are edge_dim outside 1 .. 8 and lde < edge_dim on the
+ * any-width calls.
+ * gcnx_gine_conv_ok (gcn.py:71): 1 if gcnx_gine_conv serves the shapes: k0 in {16, 32, 64, 128}, k1 and k2 multiples of 16 up
+ * to 128 (k2 >= 16: there is no single-stage form), ldx >= k0, ldx % 4 == 0, n * ldx * 4 < 2^32, 1 <= edge_dim <= 8. */
+GCNX_API int gcnx_gine_conv_ok(int64_t n, int32_t k0, int32_t k1, int32_t k2, int64_t ldx, int32_t edge_dim);
+/* gcn.py:71 -- the convolution as ONE launch: gcnx_gin_conv's workgroup (32 rows from the gather to the second bias, two
+ * chained fp32 MFMA products through LDS tiles) whose gather forms relu(x_j + e_ij w_e + b_e) per entry before the add.
+ * eps: DEVICE pointer to one float (NULL: 0).  b_e, b_a, b_b may be NULL.  t [n, k0] and u [n, k1] (may be NULL) receive T and
+ * U: the operands of dW_a = T^T dU and dW_b = U^T dZ; U is also the inner ReLU mask.  Rows of the last tile at or past n are
+ * never stored.  A tile of 32 rows must hold fewer than 2^32 / (4 lde) entries.
+ * GCNX_ERR_UNSUPPORTED, with nothing launched or written: shapes gcnx_gine_conv_ok refuses; x, w_e, b_e, w_a, w_b, t, u or out
+ * off a 16-byte boundary; ldt < k0, ldu < k1, ldo < k2, or one of them not a multiple of 4 floats -- use gcnx_gine_aggregate +
+ * gcnx_gemm then.  GCNX_ERR_INVALID: a negative size, lde < edge_dim, a NULL mandatory pointer (rowptr, colidx, x, e, w_e,
+ * w_a, w_b, out), outputs that alias x or each other. */
+GCNX_API int gcnx_gine_conv(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, const float* x, int64_t ldx, int32_t n,
+                      int32_t k0, const float* eps, const float* e, int64_t lde, int32_t edge_dim, const float* w_e,
+                      const float* b_e, const float* w_a, const float* b_a, int32_t k1, const float* w_b, const float* b_b,
+                      int32_t k2, float* t, int64_t ldt, float* u, int64_t ldu, float* out, int64_t ldo);
+/* gcn.py:71 -- out [n, f] = T alone for ANY f >= 1 and any leading dimensions >= f (w_e [edge_dim, f], b_e [f] or NULL): the
+ * first step of the composed route (then gcnx_gemm(relu), gcnx_gemm) and the route for every shape gcnx_gine_conv refuses.
+ * float4 lanes when f % 4 == 0 and x, out, w_e, b_e, ldx, ldo allow 16-byte accesses (then the bits of gcnx_gine_conv's t),
+ * scalar lanes otherwise.  Every row is written.  out must not alias x. */
+GCNX_API int gcnx_gine_aggregate(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, const float* x, int64_t ldx,
+                      const float* eps, const float* e, int64_t lde, int32_t edge_dim, const float* w_e, const float* b_e,
+                      float* out, int64_t ldo, int32_t n, int32_t f);
+/* gcn.py:71 -- floats of caller scratch gcnx_gine_bwd_edges needs (per-workgroup parts of db_e | dw_e; 0 for sizes it refuses). */
+GCNX_API int64_t gcnx_gine_bwd_scratch_floats(int64_t n, int32_t k0, int32_t edge_dim);
+/* gcn.py:71 -- backward, the pass over the forward CSR: dw_e [edge_dim, f] and db_e [f] (may be NULL) from x, e, w_e, b_e and
+ * dt = dT [n, f] (lddt), any f >= 1 (float4 lanes where the operands allow them, scalar lanes otherwise).  The sums go through
+ * per-workgroup parts in scratch (32 rows each, row-then-entry order inside a workgroup) and a second small launch inside this
+ * call that adds the parts in a fixed order: no atomics, the same bits on every call.  Written, never accumulated. */
+GCNX_API int gcnx_gine_bwd_edges(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, const float* x, int64_t ldx,
+                      const float* e, int64_t lde, int32_t edge_dim, const float* w_e, const float* b_e, const float* dt,
+                      int64_t lddt, int32_t n, int32_t f, float* dw_e, float* db_e, float* scratch);
+/* gcn.py:71 -- backward, the pass over the transposed pattern (rowptr_t, colidx_t, perm_t of gcnx_csr_transpose_perm:
+ * perm_t[p] = the forward entry behind entry p; needed for a symmetric pattern too, since e is read in the forward entry order
+ * through perm_t).  For source row j, with m recomputed from x_j and e[perm_t[p]]:
+ *     dx_j = fma(1 + *eps, dT_j, sum_p [m > 0] dT_{colidx_t[p]})            the sum in the transposed pattern's order from +0
+ * Any f >= 1.  dx (lddx) must not alias dt or x. */
+GCNX_API int gcnx_gine_bwd_nodes(gcnx_ctx* ctx, const int32_t* rowptr_t, const int32_t* colidx_t, const int32_t* perm_t,
+                      const float* x, int64_t ldx, const float* eps, const float* e, int64_t lde, int32_t edge_dim,
+                      const float* w_e, const float* b_e, const float* dt, int64_t lddt, float* dx, int64_t lddx, int32_t n,
+                      int32_t f);
+
 /* ---- PNAConv: mean, min, max and std of the neighbours' messages from one gather ------------------------------------------
  * PyG's PNAConv(aggregators = [mean, min, max, std], scalers = [identity, amplification, attenuation], deg, towers = 1,
  * pre_layers = post_layers = 1, divide_input = False, edge_dim = None, train_norm = False).  CSR row i is the target, its
