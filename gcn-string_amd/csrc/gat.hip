@@ -11,9 +11,8 @@
 // (fixed coefficients) composes it.  fp32 throughout, no float atomics, every sum in a fixed order: the same call leaves the
 // same bits, eagerly and replayed from a captured graph.
 //
-// Shape of a workgroup (sage.hip's; the device helpers are copied, not shared: that file's and fused.hip's bit-exactness
-// tests are yardsticks and a common header would rebuild them): 32 rows, one lane group of HC / 4 lanes per row with one
-// float4 of the row each -- 8 HC threads.  Head h owns the c / 4 consecutive lanes [h c / 4, (h + 1) c / 4) of a group, always
+// Shape of a workgroup (sage.hip's; the device helpers they share: conv_tile.h): 32 rows, one lane group of HC / 4 lanes per
+// row with one float4 of the row each -- 8 HC threads.  Head h owns the c / 4 consecutive lanes [h c / 4, (h + 1) c / 4) of a group, always
 // inside one wave: per-head dot products, maxima and sums are xor butterflies over those lanes (every lane ends with the same
 // bits), no LDS round trip.  The tile's CSR entries are staged in LDS (1024 of them; a tile with more -- the hub rows of a
 // power-law graph -- reads the rest from global memory, entry by entry, in every pass).  Feature rows are gathered with
@@ -22,25 +21,10 @@
 #include <cmath>
 
 #include "common.h"
+#include "conv_tile.h"
 
 namespace {
 
-typedef float g32x4v __attribute__((ext_vector_type(4)));
-
-constexpr int kGRows = 32;        // rows per workgroup
-constexpr int kGCap = 1024;       // CSR entries of a tile staged in LDS (the rest is read from global memory)
-constexpr int kGU = 4;            // entries per row per trip
-constexpr unsigned kGOut = 0xFFFFFFF0u;   // an offset no descriptor holds
-
-__device__ __forceinline__ float4 gbuf4(__amdgpu_buffer_rsrc_t rs, unsigned off) {
-  const g32x4v r = __builtin_bit_cast(g32x4v, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0));
-  return make_float4(r.x, r.y, r.z, r.w);
-}
-__device__ __forceinline__ float4 g4fma(float v, float4 h, float4 a) {
-  return make_float4(fmaf(v, h.x, a.x), fmaf(v, h.y, a.y), fmaf(v, h.z, a.z), fmaf(v, h.w, a.w));
-}
-__device__ __forceinline__ float gdot4(float4 a, float4 b) { return fmaf(a.w, b.w, fmaf(a.z, b.z, fmaf(a.y, b.y, a.x * b.x))); }
-__device__ __forceinline__ float4 gld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 // over the lph (a power of two) consecutive lanes of a head: every lane gets the same bits
 __device__ __forceinline__ float head_sum(float v, int lph) {
   for (int off = lph >> 1; off > 0; off >>= 1) v += __shfl_xor(v, off);
@@ -66,27 +50,13 @@ __global__ __launch_bounds__(256) void gat_scores_kernel(const float* __restrict
   const int64_t row = (int64_t)blockIdx.x * RPB + tid / LPR;
   const bool live = row < n;
   float4 h = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (live) h = gld4(hf + row * ldh + 4 * sub);
-  const float s = head_sum(gdot4(h, gld4(att_src + 4 * sub)), lph);
-  const float d = head_sum(gdot4(h, gld4(att_dst + 4 * sub)), lph);
+  if (live) h = load4(hf + row * ldh + 4 * sub);
+  const float s = head_sum(dot4(h, load4(att_src + 4 * sub)), lph);
+  const float d = head_sum(dot4(h, load4(att_dst + 4 * sub)), lph);
   if (live && sub % lph == 0) {
     a_src[row * heads + sub / lph] = s;
     a_dst[row * heads + sub / lph] = d;
   }
-}
-
-// ---- what every tile kernel starts with: its rows, their entry range, the staged entries --------------------------------
-struct GatTile {
-  int r0, nr, e0, e1;
-};
-__device__ __forceinline__ GatTile gat_tile(const int32_t* __restrict__ rowptr, int32_t n, int32_t* s_rp) {
-  GatTile t;
-  t.r0 = gcnx_xcd_remap(blockIdx.x, gridDim.x) * kGRows;
-  t.nr = min(n - t.r0, kGRows);
-  if ((int)threadIdx.x <= t.nr) s_rp[threadIdx.x] = rowptr[t.r0 + threadIdx.x];
-  t.e0 = rowptr[t.r0];
-  t.e1 = rowptr[t.r0 + t.nr];
-  return t;
 }
 
 struct GatFwdArgs {
@@ -101,17 +71,17 @@ struct GatFwdArgs {
 };
 
 // ---- softmax over the row's entries + weighted gather -------------------------------------------------------------------
-// dynamic LDS: kGCap * heads floats, the staged entries' scores e, then their weights exp(e - m)
+// dynamic LDS: kTileCap * heads floats, the staged entries' scores e, then their weights exp(e - m)
 template <int HC>
 __global__ __launch_bounds__(8 * HC) void gat_aggregate_kernel(GatFwdArgs p) {
   constexpr int LPR = HC / 4, NT = 8 * HC;
   extern __shared__ float s_w[];
-  __shared__ int32_t s_col[kGCap];
-  __shared__ int32_t s_rp[kGRows + 1];
+  __shared__ int32_t s_col[kTileCap];
+  __shared__ int32_t s_rp[kTileRows + 1];
   const int tid = threadIdx.x, r = tid / LPR, sub = tid % LPR;
   const int heads = p.heads, lph = p.lph, h = sub / lph, k = sub % lph;
-  const GatTile t = gat_tile(p.rowptr, p.n, s_rp);
-  const int staged = min(t.e1 - t.e0, kGCap);
+  const ConvTile t = conv_tile(p.rowptr, p.n, s_rp, kTileRows);
+  const int staged = min(t.e1 - t.e0, kTileCap);
   for (int i = tid; i < staged; i += NT) s_col[i] = p.colidx[t.e0 + i];
   __syncthreads();
   const bool live = r < t.nr;
@@ -122,7 +92,7 @@ __global__ __launch_bounds__(8 * HC) void gat_aggregate_kernel(GatFwdArgs p) {
   // pass 1: the row maximum of e; lane k of the head takes entries k, k + lph, ...
   float m = -INFINITY;
   for (int e = ea + k; e < eb; e += lph) {
-    const bool st = e < kGCap;
+    const bool st = e < kTileCap;
     const int col = st ? s_col[e] : gcol[e];
     const float ev = gscore(p.a_src[(int64_t)col * heads + h], adst, slope);
     if (st) s_w[e * heads + h] = ev;
@@ -132,7 +102,7 @@ __global__ __launch_bounds__(8 * HC) void gat_aggregate_kernel(GatFwdArgs p) {
   // pass 2: the weights exp(e - m) <= 1 and their sum l >= 1 (the maximum's own weight is 1: no overflow, no 0 / 0)
   float l = 0.f;
   for (int e = ea + k; e < eb; e += lph) {
-    const bool st = e < kGCap;
+    const bool st = e < kTileCap;
     const float ev = st ? s_w[e * heads + h] : gscore(p.a_src[(int64_t)gcol[e] * heads + h], adst, slope);
     const float w = expf(ev - m);
     if (st) s_w[e * heads + h] = w;
@@ -143,7 +113,7 @@ __global__ __launch_bounds__(8 * HC) void gat_aggregate_kernel(GatFwdArgs p) {
   if (p.alpha) {
     float* __restrict__ al = p.alpha + (int64_t)t.e0 * heads + h;
     for (int e = ea + k; e < eb; e += lph) {
-      const float w = e < kGCap ? s_w[e * heads + h] : expf(gscore(p.a_src[(int64_t)gcol[e] * heads + h], adst, slope) - m);
+      const float w = e < kTileCap ? s_w[e * heads + h] : expf(gscore(p.a_src[(int64_t)gcol[e] * heads + h], adst, slope) - m);
       al[(int64_t)e * heads] = w * inv;
     }
   }
@@ -154,24 +124,24 @@ __global__ __launch_bounds__(8 * HC) void gat_aggregate_kernel(GatFwdArgs p) {
   const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(
       (void*)p.hf, (short)0, (int)((unsigned)(p.n - 1) * ld4 + (unsigned)HC * 4u), 0x00020000);
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-  const int eaf = min(ea, kGCap), ebf = min(eb, kGCap);
-  for (int e = eaf; e < ebf; e += kGU) {
-    float4 hv[kGU];
-    float wv[kGU];
+  const int eaf = min(ea, kTileCap), ebf = min(eb, kTileCap);
+  for (int e = eaf; e < ebf; e += kTileU) {
+    float4 hv[kTileU];
+    float wv[kTileU];
 #pragma unroll
-    for (int u = 0; u < kGU; ++u) {
+    for (int u = 0; u < kTileU; ++u) {
       const bool ok = e + u < ebf;
       const int ee = ok ? e + u : e;
       wv[u] = ok ? s_w[ee * heads + h] : 0.f;
-      hv[u] = gbuf4(xr, ok ? (unsigned)s_col[ee] * ld4 + sub16 : kGOut);
+      hv[u] = buf4(xr, ok ? (unsigned)s_col[ee] * ld4 + sub16 : kOffOut);
     }
 #pragma unroll
-    for (int u = 0; u < kGU; ++u) acc = g4fma(wv[u], hv[u], acc);
+    for (int u = 0; u < kTileU; ++u) acc = fma4(wv[u], hv[u], acc);
   }
-  for (int e = max(ea, kGCap); e < eb; ++e) {      // rare: entries beyond the staged ones
+  for (int e = max(ea, kTileCap); e < eb; ++e) {      // rare: entries beyond the staged ones
     const int col = gcol[e];
     const float w = expf(gscore(p.a_src[(int64_t)col * heads + h], adst, slope) - m);
-    acc = g4fma(w, gbuf4(xr, (unsigned)col * ld4 + sub16), acc);
+    acc = fma4(w, buf4(xr, (unsigned)col * ld4 + sub16), acc);
   }
   if (!live) return;
   const float4 o = make_float4(acc.x * inv, acc.y * inv, acc.z * inv, acc.w * inv);     // a row without entries: exact zeros
@@ -179,7 +149,7 @@ __global__ __launch_bounds__(8 * HC) void gat_aggregate_kernel(GatFwdArgs p) {
   if (p.o_pre) *reinterpret_cast<float4*>(p.o_pre + row * p.ldp + 4 * sub) = o;
   float4 y = o;
   if (p.bias) {
-    const float4 b = gld4(p.bias + 4 * sub);
+    const float4 b = load4(p.bias + 4 * sub);
     y = eb > ea ? make_float4(o.x + b.x, o.y + b.y, o.z + b.z, o.w + b.w) : b;          // (no entries: the bias, bit for bit)
   }
   *reinterpret_cast<float4*>(p.out + row * p.ldo + 4 * sub) = y;
@@ -201,12 +171,12 @@ struct GatEdgeArgs {
 template <int HC>
 __global__ __launch_bounds__(8 * HC) void gat_bwd_edges_kernel(GatEdgeArgs p) {
   constexpr int LPR = HC / 4, NT = 8 * HC;
-  __shared__ int32_t s_col[kGCap];
-  __shared__ int32_t s_rp[kGRows + 1];
+  __shared__ int32_t s_col[kTileCap];
+  __shared__ int32_t s_rp[kTileRows + 1];
   const int tid = threadIdx.x, r = tid / LPR, sub = tid % LPR;
   const int heads = p.heads, lph = p.lph, h = sub / lph, k = sub % lph;
-  const GatTile t = gat_tile(p.rowptr, p.n, s_rp);
-  const int staged = min(t.e1 - t.e0, kGCap);
+  const ConvTile t = conv_tile(p.rowptr, p.n, s_rp, kTileRows);
+  const int staged = min(t.e1 - t.e0, kTileCap);
   for (int i = tid; i < staged; i += NT) s_col[i] = p.colidx[t.e0 + i];
   __syncthreads();
   const bool live = r < t.nr;
@@ -215,15 +185,15 @@ __global__ __launch_bounds__(8 * HC) void gat_bwd_edges_kernel(GatEdgeArgs p) {
   float4 dO = make_float4(0.f, 0.f, 0.f, 0.f), O = dO;
   float adst = 0.f;
   if (live) {
-    dO = gld4(p.d_out + row * p.ldd + 4 * sub);
-    O = gld4(p.o + row * p.ldo + 4 * sub);
+    dO = load4(p.d_out + row * p.ldd + 4 * sub);
+    O = load4(p.o + row * p.ldo + 4 * sub);
     if (p.o_bias) {
-      const float4 b = gld4(p.o_bias + 4 * sub);
+      const float4 b = load4(p.o_bias + 4 * sub);
       O = make_float4(O.x - b.x, O.y - b.y, O.z - b.z, O.w - b.w);
     }
     adst = p.a_dst[row * heads + h];
   }
-  const float rr = head_sum(gdot4(dO, O), lph);          // = sum_k alpha_ik dalpha_ik: no second pass over the row
+  const float rr = head_sum(dot4(dO, O), lph);          // = sum_k alpha_ik dalpha_ik: no second pass over the row
   const unsigned ld4 = (unsigned)p.ldh * 4u, sub16 = (unsigned)sub * 16u;
   const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(
       (void*)p.hf, (short)0, (int)((unsigned)(p.n - 1) * ld4 + (unsigned)HC * 4u), 0x00020000);
@@ -232,21 +202,21 @@ __global__ __launch_bounds__(8 * HC) void gat_bwd_edges_kernel(GatEdgeArgs p) {
   float* __restrict__ dzo = p.dz + (int64_t)t.e0 * heads + h;
   const float slope = p.slope;
   float dsum = 0.f;
-  for (int e = ea; e < eb; e += kGU) {                   // (the lanes of a row share ea and eb: they shuffle together)
-    float4 hv[kGU];
-    float as[kGU], av[kGU];
+  for (int e = ea; e < eb; e += kTileU) {                   // (the lanes of a row share ea and eb: they shuffle together)
+    float4 hv[kTileU];
+    float as[kTileU], av[kTileU];
 #pragma unroll
-    for (int u = 0; u < kGU; ++u) {
+    for (int u = 0; u < kTileU; ++u) {
       const bool ok = e + u < eb;
       const int ee = ok ? e + u : e;
-      const int col = ee < kGCap ? s_col[ee] : gcol[ee];
-      hv[u] = gbuf4(xr, ok ? (unsigned)col * ld4 + sub16 : kGOut);
+      const int col = ee < kTileCap ? s_col[ee] : gcol[ee];
+      hv[u] = buf4(xr, ok ? (unsigned)col * ld4 + sub16 : kOffOut);
       as[u] = p.a_src[(int64_t)col * heads + h];
       av[u] = al[(int64_t)ee * heads];
     }
 #pragma unroll
-    for (int u = 0; u < kGU; ++u) {
-      const float d = head_sum(gdot4(dO, hv[u]), lph);
+    for (int u = 0; u < kTileU; ++u) {
+      const float d = head_sum(dot4(dO, hv[u]), lph);
       if (e + u < eb) {
         const float z = as[u] + adst;
         const float g = av[u] * (d - rr) * (z > 0.f ? 1.0f : slope);
@@ -274,14 +244,14 @@ struct GatNodeArgs {
 template <int HC>
 __global__ __launch_bounds__(8 * HC) void gat_bwd_nodes_kernel(GatNodeArgs p) {
   constexpr int LPR = HC / 4, NT = 8 * HC;
-  __shared__ int32_t s_col[kGCap];
-  __shared__ int32_t s_q[kGCap];
-  __shared__ int32_t s_rp[kGRows + 1];
-  __shared__ __attribute__((aligned(16))) float4 s_p[2][kGRows][LPR];
+  __shared__ int32_t s_col[kTileCap];
+  __shared__ int32_t s_q[kTileCap];
+  __shared__ int32_t s_rp[kTileRows + 1];
+  __shared__ __attribute__((aligned(16))) float4 s_p[2][kTileRows][LPR];
   const int tid = threadIdx.x, r = tid / LPR, sub = tid % LPR;
   const int heads = p.heads, lph = p.lph, h = sub / lph, k = sub % lph;
-  const GatTile t = gat_tile(p.rowptr, p.n, s_rp);
-  const int staged = min(t.e1 - t.e0, kGCap);
+  const ConvTile t = conv_tile(p.rowptr, p.n, s_rp, kTileRows);
+  const int staged = min(t.e1 - t.e0, kTileCap);
   for (int i = tid; i < staged; i += NT) {
     s_col[i] = p.colidx[t.e0 + i];
     s_q[i] = p.perm[t.e0 + i];
@@ -297,23 +267,23 @@ __global__ __launch_bounds__(8 * HC) void gat_bwd_nodes_kernel(GatNodeArgs p) {
   const int32_t* __restrict__ gq = p.perm + t.e0;
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
   float dsrc = 0.f;
-  for (int e = ea; e < eb; e += kGU) {
-    float4 hv[kGU];
-    float av[kGU], zv[kGU];
+  for (int e = ea; e < eb; e += kTileU) {
+    float4 hv[kTileU];
+    float av[kTileU], zv[kTileU];
 #pragma unroll
-    for (int u = 0; u < kGU; ++u) {
+    for (int u = 0; u < kTileU; ++u) {
       const bool ok = e + u < eb;
       const int ee = ok ? e + u : e;
-      const bool st = ee < kGCap;
+      const bool st = ee < kTileCap;
       const int col = st ? s_col[ee] : gcol[ee];
       const int64_t q = (int64_t)(st ? s_q[ee] : gq[ee]) * heads + h;
-      hv[u] = gbuf4(dr, ok ? (unsigned)col * ld4 + sub16 : kGOut);
+      hv[u] = buf4(dr, ok ? (unsigned)col * ld4 + sub16 : kOffOut);
       av[u] = ok ? p.alpha[q] : 0.f;
       zv[u] = ok ? p.dz[q] : 0.f;
     }
 #pragma unroll
-    for (int u = 0; u < kGU; ++u) {
-      acc = g4fma(av[u], hv[u], acc);
+    for (int u = 0; u < kTileU; ++u) {
+      acc = fma4(av[u], hv[u], acc);
       dsrc += zv[u];                                     // the transposed CSR's order
     }
   }
@@ -321,9 +291,9 @@ __global__ __launch_bounds__(8 * HC) void gat_bwd_nodes_kernel(GatNodeArgs p) {
   float4 own = make_float4(0.f, 0.f, 0.f, 0.f);
   if (live) {
     ddst = p.da_dst[row * heads + h];
-    own = gld4(p.hf + row * p.ldh + 4 * sub);
-    acc = g4fma(dsrc, gld4(p.att_src + 4 * sub), acc);
-    acc = g4fma(ddst, gld4(p.att_dst + 4 * sub), acc);
+    own = load4(p.hf + row * p.ldh + 4 * sub);
+    acc = fma4(dsrc, load4(p.att_src + 4 * sub), acc);
+    acc = fma4(ddst, load4(p.att_dst + 4 * sub), acc);
     *reinterpret_cast<float4*>(p.dhf + row * p.ldg + 4 * sub) = acc;
     if (k == 0) p.da_src[row * heads + h] = dsrc;
   }
@@ -335,11 +305,11 @@ __global__ __launch_bounds__(8 * HC) void gat_bwd_nodes_kernel(GatNodeArgs p) {
     const int which = tid / LPR, c4 = tid % LPR;
     float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll 8
-    for (int i = 0; i < kGRows; ++i) {
+    for (int i = 0; i < kTileRows; ++i) {
       const float4 v = s_p[which][i][c4];
       s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
     }
-    *reinterpret_cast<float4*>(p.part + ((int64_t)(t.r0 / kGRows) * 2 + which) * HC + 4 * c4) = s;
+    *reinterpret_cast<float4*>(p.part + ((int64_t)(t.r0 / kTileRows) * 2 + which) * HC + 4 * c4) = s;
   }
 }
 
@@ -358,7 +328,7 @@ bool gat_shape_ok(int64_t n, int32_t heads, int32_t c, int64_t ldh) {
   return (hc == 16 || hc == 32 || hc == 64 || hc == 128) && ldh >= hc && ldh % 4 == 0 &&
          (uint64_t)n * (uint64_t)ldh * 4u < 0x100000000ull;
 }
-bool gat_ld_ok(int64_t ld, int hc) { return ld >= hc && ld % 4 == 0; }
+bool gat_ld_ok(int64_t ld, int hc) { return ld >= hc && ld % 4 == 0; }     // (conv_ld_ok without its 2^30 bound: what this ABI accepts)
 
 const char* kGatShapes = "needs heads in {1, 2, 4, 8}, heads * c in {16, 32, 64, 128}, c >= 4, ld >= heads * c in multiples of 4 "
                          "floats and n * ld * 4 < 2^32";
@@ -374,7 +344,7 @@ int gcnx_gat_conv_ok(int64_t n, int32_t heads, int32_t c, int64_t ldh) { return 
 
 int64_t gcnx_gat_bwd_scratch_floats(int64_t n, int32_t heads, int32_t c) {
   if (n < 0 || heads < 0 || c < 0) return 0;
-  return (int64_t)gcnx_cdiv(n, kGRows) * 2 * heads * c;
+  return (int64_t)gcnx_cdiv(n, kTileRows) * 2 * heads * c;
 }
 
 int gcnx_gat_scores(gcnx_ctx* ctx, const float* hf, int64_t ldh, int32_t n, int32_t heads, int32_t c, const float* att_src,
@@ -417,8 +387,8 @@ int gcnx_gat_aggregate(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* coli
   GatFwdArgs a{};
   a.rowptr = rowptr; a.colidx = colidx; a.hf = hf; a.ldh = ldh; a.n = n; a.heads = heads; a.lph = c / 4; a.a_src = a_src; a.a_dst = a_dst;
   a.bias = bias; a.slope = slope; a.out = out; a.ldo = ldo; a.alpha = alpha; a.o_pre = o_pre; a.ldp = ldp;
-  const int tiles = gcnx_cdiv(n, kGRows);
-  const size_t dyn = (size_t)kGCap * heads * sizeof(float);
+  const int tiles = gcnx_cdiv(n, kTileRows);
+  const size_t dyn = (size_t)kTileCap * heads * sizeof(float);
 #define GCNX_GAT_AGG(HC_) hipLaunchKernelGGL((gat_aggregate_kernel<HC_>), dim3(tiles), dim3(8 * HC_), dyn, ctx->stream, a)
   GCNX_GAT_DISPATCH(hc, GCNX_GAT_AGG);
 #undef GCNX_GAT_AGG
@@ -444,7 +414,7 @@ int gcnx_gat_bwd_edges(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* coli
   GatEdgeArgs a{};
   a.rowptr = rowptr; a.colidx = colidx; a.hf = hf; a.ldh = ldh; a.n = n; a.heads = heads; a.lph = c / 4; a.a_src = a_src; a.a_dst = a_dst;
   a.slope = slope; a.alpha = alpha; a.d_out = d_out; a.ldd = ldd; a.o = o; a.ldo = ldo; a.o_bias = o_bias; a.dz = dz; a.da_dst = da_dst;
-  const int tiles = gcnx_cdiv(n, kGRows);
+  const int tiles = gcnx_cdiv(n, kTileRows);
 #define GCNX_GAT_BE(HC_) hipLaunchKernelGGL((gat_bwd_edges_kernel<HC_>), dim3(tiles), dim3(8 * HC_), 0, ctx->stream, a)
   GCNX_GAT_DISPATCH(hc, GCNX_GAT_BE);
 #undef GCNX_GAT_BE
@@ -474,7 +444,7 @@ int gcnx_gat_bwd_nodes(gcnx_ctx* ctx, const int32_t* rowptr_t, const int32_t* co
   a.rowptr = rowptr_t; a.colidx = colidx_t; a.perm = perm_t; a.n = n; a.heads = heads; a.lph = c / 4; a.alpha = alpha; a.dz = dz;
   a.d_out = d_out; a.ldd = ldd; a.hf = hf; a.ldh = ldh; a.da_dst = da_dst; a.att_src = att_src; a.att_dst = att_dst; a.dhf = dhf;
   a.ldg = ldg; a.da_src = da_src; a.part = scratch;
-  const int tiles = gcnx_cdiv(n, kGRows);
+  const int tiles = gcnx_cdiv(n, kTileRows);
 #define GCNX_GAT_BN(HC_) hipLaunchKernelGGL((gat_bwd_nodes_kernel<HC_>), dim3(tiles), dim3(8 * HC_), 0, ctx->stream, a)
   GCNX_GAT_DISPATCH(hc, GCNX_GAT_BN);
 #undef GCNX_GAT_BN

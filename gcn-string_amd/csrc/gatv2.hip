@@ -14,9 +14,9 @@
 // products and adds in a fixed order, no FMA -- so they agree on the side of every kink, and NumPy float32 reproduces it.
 // fp32 throughout, no float atomics, every sum in a fixed order: the same call leaves the same bits.
 //
-// Shape of a workgroup (gat.hip's; the device helpers are copied, not shared: that file's, sage.hip's and fused.hip's
-// bit-exactness tests are yardsticks and a common header would rebuild them): 32 rows, one lane group of HC / 4 lanes per row
-// with one float4 of the row each -- 8 HC threads (the two backward kernels at HC = 128: 16 rows, see v2_bwd_rows).  Head h owns the c / 4 consecutive lanes [h c / 4, (h + 1) c / 4) of a group,
+// Shape of a workgroup (gat.hip's; the device helpers they share: conv_tile.h): 32 rows, one lane group of HC / 4 lanes per row
+// with one float4 of the row each -- 8 HC threads (the two backward kernels at HC = 128: 16 rows, see conv_tile_rows).  Head h
+// owns the c / 4 consecutive lanes [h c / 4, (h + 1) c / 4) of a group,
 // always inside one wave: per-head dot products are xor butterflies over those lanes (every lane ends with the same bits).
 // The tile's CSR entries are staged in LDS (1024 of them; a tile with more reads the rest from global memory).  Feature rows
 // are gathered with range-checked buffer loads, slots past a row's end fetch nothing.  W_e sits in registers: E float4 per lane
@@ -32,65 +32,26 @@
 #include <cmath>
 
 #include "common.h"
+#include "conv_tile.h"
 
 namespace {
 
-typedef float v2f32x4v __attribute__((ext_vector_type(4)));
-
-constexpr int kVRows = 32;        // rows per workgroup
-constexpr int kVCap = 1024;       // CSR entries of a tile staged in LDS (the rest is read from global memory)
-constexpr int kVU = 4;            // entries per row per trip
-constexpr int kVEdgeMax = 8;      // edge features served
-constexpr unsigned kVOut = 0xFFFFFFF0u;   // an offset no descriptor holds
-
-__device__ __forceinline__ float4 vbuf4(__amdgpu_buffer_rsrc_t rs, unsigned off) {
-  const v2f32x4v r = __builtin_bit_cast(v2f32x4v, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0));
-  return make_float4(r.x, r.y, r.z, r.w);
-}
-__device__ __forceinline__ float4 v4fma(float v, float4 h, float4 a) {
-  return make_float4(fmaf(v, h.x, a.x), fmaf(v, h.y, a.y), fmaf(v, h.z, a.z), fmaf(v, h.w, a.w));
-}
-__device__ __forceinline__ float4 v4scale(float v, float4 a) { return make_float4(v * a.x, v * a.y, v * a.z, v * a.w); }
-__device__ __forceinline__ float4 v4add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-__device__ __forceinline__ float vdot4(float4 a, float4 b) { return fmaf(a.w, b.w, fmaf(a.z, b.z, fmaf(a.y, b.y, a.x * b.x))); }
-__device__ __forceinline__ float4 vld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ float4 vzero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
 // over the lph (a power of two) consecutive lanes of a head: every lane gets the same bits
 // (the partner lane^off comes from a swizzle with a constant mask -- off = 16, 8, 4 -- or a quad permutation -- off = 2, 1 --
 // under uniform tests of lph: no per-lane address as a shuffle by a run-time offset needs, the same additions in the same order)
-template <int OFF>
-__device__ __forceinline__ float vswz_xor(float v) {
-  return __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v), (OFF << 10) | 0x1F));
-}
-template <int CTRL>
-__device__ __forceinline__ float vquad(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
 __device__ __forceinline__ float vhead_sum(float v, int lph) {
-  if (lph > 16) v += vswz_xor<16>(v);
-  if (lph > 8) v += vswz_xor<8>(v);
-  if (lph > 4) v += vswz_xor<4>(v);
-  if (lph > 2) v += vquad<0x4E>(v);                      // lanes [2, 3, 0, 1] of every quad
-  if (lph > 1) v += vquad<0xB1>(v);                      // lanes [1, 0, 3, 2]
+  if (lph > 16) v += swz_xor<16>(v);
+  if (lph > 8) v += swz_xor<8>(v);
+  if (lph > 4) v += swz_xor<4>(v);
+  if (lph > 2) v += quad_perm<0x4E>(v);                      // lanes [2, 3, 0, 1] of every quad
+  if (lph > 1) v += quad_perm<0xB1>(v);                      // lanes [1, 0, 3, 2]
   return v;
 }
 
-// W_e [edge_dim, HC]: this lane's float4 of every row, rows >= edge_dim zero and never used
-template <int E> struct VEdgeW { float4 w[E > 0 ? E : 1]; };
-template <int E>
-__device__ __forceinline__ VEdgeW<E> vload_we(const float* __restrict__ w_e, int edge_dim, int hc, int sub) {
-  VEdgeW<E> r;
-  r.w[0] = vzero4();
-#pragma unroll
-  for (int d = 0; d < E; ++d) r.w[d] = d < edge_dim ? vld4(w_e + (int64_t)d * hc + 4 * sub) : vzero4();
-  return r;
-}
-// one entry's edge features (uniform over the lane group)
-template <int E> struct VEdgeF { float v[E > 0 ? E : 1]; };
 // the edge features of the U entries of a trip; ok[u] = false: zeros.  Feature d is touched inside the (uniform) test of
 // feature d - 1, so a trip costs edge_dim + 1 branches, not one per (entry, channel, feature), and every index is a constant.
 template <int Dd, int E, int U>
-__device__ __forceinline__ void vload_e_from(VEdgeF<E> (&r)[U], const float* __restrict__ e, int64_t lde, int edge_dim,
+__device__ __forceinline__ void vload_e_from(EdgeF<E> (&r)[U], const float* __restrict__ e, int64_t lde, int edge_dim,
                                              const int64_t (&entry)[U], const bool (&ok)[U]) {
   if constexpr (Dd < E) {
     if (Dd < edge_dim) {
@@ -101,7 +62,7 @@ __device__ __forceinline__ void vload_e_from(VEdgeF<E> (&r)[U], const float* __r
   }
 }
 template <int E, int U>
-__device__ __forceinline__ void vload_e(VEdgeF<E> (&r)[U], const float* __restrict__ e, int64_t lde, int edge_dim, const int64_t (&entry)[U],
+__device__ __forceinline__ void vload_e(EdgeF<E> (&r)[U], const float* __restrict__ e, int64_t lde, int edge_dim, const int64_t (&entry)[U],
                                         const bool (&ok)[U]) {
 #pragma unroll
   for (int u = 0; u < U; ++u)
@@ -120,7 +81,7 @@ __device__ __forceinline__ float4 v4add_rn(float4 a, float4 b) {
 }
 // t of the U entries of a trip (nested as vload_e_from)
 template <int Dd, int E, int U>
-__device__ __forceinline__ void gv2_t_from(float4 (&t)[U], const VEdgeF<E> (&e)[U], const VEdgeW<E>& w, int edge_dim) {
+__device__ __forceinline__ void gv2_t_from(float4 (&t)[U], const EdgeF<E> (&e)[U], const EdgeW<E>& w, int edge_dim) {
   if constexpr (Dd < E) {
     if (Dd < edge_dim) {
 #pragma unroll
@@ -133,16 +94,16 @@ __device__ __forceinline__ void gv2_t_from(float4 (&t)[U], const VEdgeF<E> (&e)[
   }
 }
 template <int E, int U>
-__device__ __forceinline__ void gv2_t(float4 (&t)[U], const VEdgeF<E> (&e)[U], const VEdgeW<E>& w, int edge_dim) {
+__device__ __forceinline__ void gv2_t(float4 (&t)[U], const EdgeF<E> (&e)[U], const EdgeW<E>& w, int edge_dim) {
 #pragma unroll
-  for (int u = 0; u < U; ++u) t[u] = vzero4();
+  for (int u = 0; u < U; ++u) t[u] = zero4();
   gv2_t_from<0, E, U>(t, e, w, edge_dim);
 }
 // t of the U entries of a trip straight from memory, for the kernels that need the features for nothing else: feature d of
 // the U entries is loaded and used inside the test of feature d - 1 (no register copy of e)
 template <int Dd, int E, int U>
 __device__ __forceinline__ void gv2_t_load_from(float4 (&t)[U], const float* __restrict__ e, int64_t lde, const int64_t (&entry)[U],
-                                                const bool (&ok)[U], const VEdgeW<E>& w, int edge_dim) {
+                                                const bool (&ok)[U], const EdgeW<E>& w, int edge_dim) {
   if constexpr (Dd < E) {
     if (Dd < edge_dim) {
       float ev[U];
@@ -159,17 +120,17 @@ __device__ __forceinline__ void gv2_t_load_from(float4 (&t)[U], const float* __r
 }
 template <int E, int U>
 __device__ __forceinline__ void gv2_t_load(float4 (&t)[U], const float* __restrict__ e, int64_t lde, const int64_t (&entry)[U],
-                                           const bool (&ok)[U], const VEdgeW<E>& w, int edge_dim) {
+                                           const bool (&ok)[U], const EdgeW<E>& w, int edge_dim) {
 #pragma unroll
-  for (int u = 0; u < U; ++u) t[u] = vzero4();
+  for (int u = 0; u < U; ++u) t[u] = zero4();
   gv2_t_load_from<0, E, U>(t, e, lde, entry, ok, w, edge_dim);
 }
 // dW_e += e (x) ds of one entry (nested the same way)
 template <int Dd, int E>
-__device__ __forceinline__ void gv2_dwe_from(VEdgeW<E>& dwe, const VEdgeF<E>& e, float4 ds, int edge_dim) {
+__device__ __forceinline__ void gv2_dwe_from(EdgeW<E>& dwe, const EdgeF<E>& e, float4 ds, int edge_dim) {
   if constexpr (Dd < E) {
     if (Dd < edge_dim) {
-      dwe.w[Dd] = v4fma(e.v[Dd], ds, dwe.w[Dd]);
+      dwe.w[Dd] = fma4(e.v[Dd], ds, dwe.w[Dd]);
       gv2_dwe_from<Dd + 1, E>(dwe, e, ds, edge_dim);
     }
   }
@@ -184,20 +145,6 @@ __device__ __forceinline__ float4 gv2_leaky(float4 s, float slope) {
 __device__ __forceinline__ float4 gv2_ds(float dscore, float4 att, float4 s, float slope) {
   return make_float4(dscore * att.x * (s.x > 0.f ? 1.0f : slope), dscore * att.y * (s.y > 0.f ? 1.0f : slope),
                      dscore * att.z * (s.z > 0.f ? 1.0f : slope), dscore * att.w * (s.w > 0.f ? 1.0f : slope));
-}
-
-// ---- what every tile kernel starts with: its rows, their entry range ----------------------------------------------------
-struct V2Tile {
-  int r0, nr, e0, e1;
-};
-__device__ __forceinline__ V2Tile gv2_tile(const int32_t* __restrict__ rowptr, int32_t n, int32_t* s_rp, int rows) {
-  V2Tile t;
-  t.r0 = gcnx_xcd_remap(blockIdx.x, gridDim.x) * rows;
-  t.nr = min(n - t.r0, rows);
-  if ((int)threadIdx.x <= t.nr) s_rp[threadIdx.x] = rowptr[t.r0 + threadIdx.x];
-  t.e0 = rowptr[t.r0];
-  t.e1 = rowptr[t.r0 + t.nr];
-  return t;
 }
 
 struct V2FwdArgs {
@@ -216,13 +163,13 @@ struct V2FwdArgs {
 template <int HC, int E>
 __global__ __launch_bounds__(8 * HC) void gatv2_aggregate_kernel(V2FwdArgs p) {
   constexpr int LPR = HC / 4, NT = 8 * HC;
-  extern __shared__ float s_sc[];                        // with alpha: the staged entries' scores, kVCap * heads floats
-  __shared__ int32_t s_col[kVCap];
-  __shared__ int32_t s_rp[kVRows + 1];
+  extern __shared__ float s_sc[];                        // with alpha: the staged entries' scores, kTileCap * heads floats
+  __shared__ int32_t s_col[kTileCap];
+  __shared__ int32_t s_rp[kTileRows + 1];
   const int tid = threadIdx.x, r = tid / LPR, sub = tid % LPR;
   const int heads = p.heads, lph = p.lph, h = sub / lph, k = sub % lph, ed = p.edge_dim;
-  const V2Tile t = gv2_tile(p.rowptr, p.n, s_rp, kVRows);
-  const int staged = min(t.e1 - t.e0, kVCap);
+  const ConvTile t = conv_tile(p.rowptr, p.n, s_rp, kTileRows);
+  const int staged = min(t.e1 - t.e0, kTileCap);
   for (int i = tid; i < staged; i += NT) s_col[i] = p.colidx[t.e0 + i];
   __syncthreads();
   const bool live = r < t.nr;
@@ -230,52 +177,52 @@ __global__ __launch_bounds__(8 * HC) void gatv2_aggregate_kernel(V2FwdArgs p) {
   const int64_t row = t.r0 + r;
   const float slope = p.slope;
   const int32_t* __restrict__ gcol = p.colidx + t.e0;
-  const float4 att = vld4(p.att + 4 * sub);
-  const VEdgeW<E> we = vload_we<E>(p.w_e, ed, HC, sub);
-  const float4 xr = live ? vld4(p.xlr + row * p.ldx + HC + 4 * sub) : vzero4();
+  const float4 att = load4(p.att + 4 * sub);
+  const EdgeW<E> we = load_edge_w<E>(p.w_e, ed, HC, sub);
+  const float4 xr = live ? load4(p.xlr + row * p.ldx + HC + 4 * sub) : zero4();
   const unsigned ld4 = (unsigned)p.ldx * 4u, sub16 = (unsigned)sub * 16u;
   // the descriptor ends behind the last row's HC columns of Xl (nothing past them is addressed)
   const __amdgpu_buffer_rsrc_t xd = __builtin_amdgcn_make_buffer_rsrc(
       (void*)p.xlr, (short)0, (int)((unsigned)(p.n - 1) * ld4 + (unsigned)HC * 4u), 0x00020000);
   float* __restrict__ al = p.alpha ? p.alpha + (int64_t)t.e0 * heads + h : nullptr;
-  float4 acc = vzero4();
+  float4 acc = zero4();
   float m = -INFINITY, l = 0.f;
-  for (int e = ea; e < eb; e += kVU) {                   // (the lanes of a row share ea and eb: they shuffle together)
-    float4 xv[kVU], tv[kVU];
-    int64_t en[kVU];
-    bool ok[kVU];
+  for (int e = ea; e < eb; e += kTileU) {                   // (the lanes of a row share ea and eb: they shuffle together)
+    float4 xv[kTileU], tv[kTileU];
+    int64_t en[kTileU];
+    bool ok[kTileU];
 #pragma unroll
-    for (int u = 0; u < kVU; ++u) {
+    for (int u = 0; u < kTileU; ++u) {
       ok[u] = e + u < eb;
       const int ee = ok[u] ? e + u : e;
-      const int col = ee < kVCap ? s_col[ee] : gcol[ee];
-      xv[u] = vbuf4(xd, ok[u] ? (unsigned)col * ld4 + sub16 : kVOut);
+      const int col = ee < kTileCap ? s_col[ee] : gcol[ee];
+      xv[u] = buf4(xd, ok[u] ? (unsigned)col * ld4 + sub16 : kOffOut);
       en[u] = (int64_t)t.e0 + ee;
     }
     gv2_t_load(tv, p.e, p.lde, en, ok, we, ed);
-    float sc[kVU];
+    float sc[kTileU];
     float mt = m;
 #pragma unroll
-    for (int u = 0; u < kVU; ++u) {
+    for (int u = 0; u < kTileU; ++u) {
       const float4 g = gv2_leaky(gv2_s(xv[u], xr, tv[u]), slope);
-      sc[u] = vhead_sum(vdot4(att, g), lph);
+      sc[u] = vhead_sum(dot4(att, g), lph);
       if (e + u < eb) {
         mt = fmaxf(mt, sc[u]);
         // the raw score, turned into alpha behind the loop: kept in LDS (a store to global memory here would sit in the
         // gathers' queue); an entry beyond the staged ones goes through alpha itself
         if (al && k == 0) {
-          if (e + u < kVCap) s_sc[(e + u) * heads + h] = sc[u];
+          if (e + u < kTileCap) s_sc[(e + u) * heads + h] = sc[u];
           else al[(int64_t)(e + u) * heads] = sc[u];
         }
       }
     }
     const float scale = expf(m - mt);                    // (first trip: exp(-inf) = 0 on acc = 0, l = 0)
-    acc = v4scale(scale, acc);
+    acc = scale4(scale, acc);
     l *= scale;
 #pragma unroll
-    for (int u = 0; u < kVU; ++u) {
+    for (int u = 0; u < kTileU; ++u) {
       const float w = e + u < eb ? expf(sc[u] - mt) : 0.f;
-      acc = v4fma(w, xv[u], acc);                        // CSR order
+      acc = fma4(w, xv[u], acc);                        // CSR order
       l += w;
     }
     m = mt;
@@ -283,18 +230,18 @@ __global__ __launch_bounds__(8 * HC) void gatv2_aggregate_kernel(V2FwdArgs p) {
   const float inv = eb > ea ? 1.0f / l : 0.f;
   if (p.alpha) {                                         // (uniform)
     __syncthreads();
-    const int ebs = min(eb, kVCap);
+    const int ebs = min(eb, kTileCap);
     for (int e = ea + k; e < ebs; e += lph) al[(int64_t)e * heads] = expf(s_sc[e * heads + h] - m) * inv;     // lane k: entries k, k + lph, ...
     if (k == 0)                                          // rare: this lane's own stores read back
-      for (int e = max(ea, kVCap); e < eb; ++e) al[(int64_t)e * heads] = expf(al[(int64_t)e * heads] - m) * inv;
+      for (int e = max(ea, kTileCap); e < eb; ++e) al[(int64_t)e * heads] = expf(al[(int64_t)e * heads] - m) * inv;
   }
   if (!live) return;
-  const float4 o = v4scale(inv, acc);                    // a row without entries: exact zeros
+  const float4 o = scale4(inv, acc);                    // a row without entries: exact zeros
   if (p.o_pre) *reinterpret_cast<float4*>(p.o_pre + row * p.ldp + 4 * sub) = o;
   float4 y = o;
   if (p.bias) {
-    const float4 b = vld4(p.bias + 4 * sub);
-    y = eb > ea ? v4add(o, b) : b;                       // (no entries: the bias, bit for bit)
+    const float4 b = load4(p.bias + 4 * sub);
+    y = eb > ea ? add4(o, b) : b;                       // (no entries: the bias, bit for bit)
   }
   *reinterpret_cast<float4*>(p.out + row * p.ldo + 4 * sub) = y;
 }
@@ -318,66 +265,66 @@ struct V2EdgeArgs {
 template <int HC, int ROWS, int E>
 __global__ __launch_bounds__(ROWS * HC / 4) void gatv2_bwd_edges_kernel(V2EdgeArgs p) {
   constexpr int LPR = HC / 4, NT = ROWS * LPR;
-  __shared__ int32_t s_col[kVCap];
-  __shared__ int32_t s_rp[kVRows + 1];
+  __shared__ int32_t s_col[kTileCap];
+  __shared__ int32_t s_rp[kTileRows + 1];
   __shared__ __attribute__((aligned(16))) float4 s_p[ROWS][LPR];
   const int tid = threadIdx.x, r = tid / LPR, sub = tid % LPR;
   const int heads = p.heads, lph = p.lph, h = sub / lph, k = sub % lph, ed = p.edge_dim;
-  const V2Tile t = gv2_tile(p.rowptr, p.n, s_rp, ROWS);
-  const int staged = min(t.e1 - t.e0, kVCap);
+  const ConvTile t = conv_tile(p.rowptr, p.n, s_rp, ROWS);
+  const int staged = min(t.e1 - t.e0, kTileCap);
   for (int i = tid; i < staged; i += NT) s_col[i] = p.colidx[t.e0 + i];
   __syncthreads();
   const bool live = r < t.nr;
   const int ea = live ? s_rp[r] - t.e0 : 0, eb = live ? s_rp[r + 1] - t.e0 : 0;
   const int64_t row = t.r0 + r;
   const float slope = p.slope;
-  const float4 att = vld4(p.att + 4 * sub);
-  const VEdgeW<E> we = vload_we<E>(p.w_e, ed, HC, sub);
-  float4 dO = vzero4(), O = dO, xr = dO;
+  const float4 att = load4(p.att + 4 * sub);
+  const EdgeW<E> we = load_edge_w<E>(p.w_e, ed, HC, sub);
+  float4 dO = zero4(), O = dO, xr = dO;
   if (live) {
-    dO = vld4(p.d_out + row * p.ldd + 4 * sub);
-    O = vld4(p.o + row * p.ldo + 4 * sub);
-    xr = vld4(p.xlr + row * p.ldx + HC + 4 * sub);
+    dO = load4(p.d_out + row * p.ldd + 4 * sub);
+    O = load4(p.o + row * p.ldo + 4 * sub);
+    xr = load4(p.xlr + row * p.ldx + HC + 4 * sub);
   }
-  const float rr = vhead_sum(vdot4(dO, O), lph);         // = sum_k alpha_ik dalpha_ik: no second pass over the row
+  const float rr = vhead_sum(dot4(dO, O), lph);         // = sum_k alpha_ik dalpha_ik: no second pass over the row
   const unsigned ld4 = (unsigned)p.ldx * 4u, sub16 = (unsigned)sub * 16u;
   const __amdgpu_buffer_rsrc_t xd = __builtin_amdgcn_make_buffer_rsrc(
       (void*)p.xlr, (short)0, (int)((unsigned)(p.n - 1) * ld4 + (unsigned)HC * 4u), 0x00020000);
   const int32_t* __restrict__ gcol = p.colidx + t.e0;
   const float* __restrict__ al = p.alpha + (int64_t)t.e0 * heads + h;
   float* __restrict__ dso = p.dscore + (int64_t)t.e0 * heads + h;
-  float4 dxr = vzero4(), datt = vzero4();
-  VEdgeW<E> dwe;
+  float4 dxr = zero4(), datt = zero4();
+  EdgeW<E> dwe;
 #pragma unroll
-  for (int d = 0; d < (E > 0 ? E : 1); ++d) dwe.w[d] = vzero4();
-  for (int e = ea; e < eb; e += kVU) {
-    float4 xv[kVU], tv[kVU];
-    VEdgeF<E> ev[kVU];
-    float av[kVU];
-    int64_t en[kVU];
-    bool ok[kVU];
+  for (int d = 0; d < (E > 0 ? E : 1); ++d) dwe.w[d] = zero4();
+  for (int e = ea; e < eb; e += kTileU) {
+    float4 xv[kTileU], tv[kTileU];
+    EdgeF<E> ev[kTileU];
+    float av[kTileU];
+    int64_t en[kTileU];
+    bool ok[kTileU];
 #pragma unroll
-    for (int u = 0; u < kVU; ++u) {
+    for (int u = 0; u < kTileU; ++u) {
       ok[u] = e + u < eb;
       const int ee = ok[u] ? e + u : e;
-      const int col = ee < kVCap ? s_col[ee] : gcol[ee];
-      xv[u] = vbuf4(xd, ok[u] ? (unsigned)col * ld4 + sub16 : kVOut);
+      const int col = ee < kTileCap ? s_col[ee] : gcol[ee];
+      xv[u] = buf4(xd, ok[u] ? (unsigned)col * ld4 + sub16 : kOffOut);
       en[u] = (int64_t)t.e0 + ee;
       av[u] = al[(int64_t)ee * heads];
     }
     vload_e(ev, p.e, p.lde, ed, en, ok);
     gv2_t(tv, ev, we, ed);
 #pragma unroll
-    for (int u = 0; u < kVU; ++u) {
-      const float d = vhead_sum(vdot4(dO, xv[u]), lph);
+    for (int u = 0; u < kTileU; ++u) {
+      const float d = vhead_sum(dot4(dO, xv[u]), lph);
       if (e + u < eb) {
         const float dsc = av[u] * (d - rr);
         if (k == 0) dso[(int64_t)(e + u) * heads] = dsc;
         const float4 s = gv2_s(xv[u], xr, tv[u]);
         const float4 g = gv2_leaky(s, slope);
         const float4 ds = gv2_ds(dsc, att, s, slope);
-        dxr = v4add(dxr, ds);                            // CSR order
-        datt = v4fma(dsc, g, datt);
+        dxr = add4(dxr, ds);                            // CSR order
+        datt = fma4(dsc, g, datt);
         gv2_dwe_from<0, E>(dwe, ev[u], ds, ed);
       }
     }
@@ -391,9 +338,9 @@ __global__ __launch_bounds__(ROWS * HC / 4) void gatv2_bwd_edges_kernel(V2EdgeAr
       s_p[r][sub] = q == 0 ? datt : dwe.w[q > 0 ? q - 1 : 0];
       __syncthreads();
       if (tid < LPR) {
-        float4 s = vzero4();
+        float4 s = zero4();
 #pragma unroll 8
-        for (int i = 0; i < ROWS; ++i) s = v4add(s, s_p[i][tid]);
+        for (int i = 0; i < ROWS; ++i) s = add4(s, s_p[i][tid]);
         *reinterpret_cast<float4*>(part + q * HC + 4 * tid) = s;
       }
       __syncthreads();
@@ -426,13 +373,13 @@ struct V2NodeArgs {
 template <int HC, int ROWS, int E>
 __global__ __launch_bounds__(ROWS * HC / 4) void gatv2_bwd_nodes_kernel(V2NodeArgs p) {
   constexpr int LPR = HC / 4, NT = ROWS * LPR;
-  __shared__ int32_t s_col[kVCap];
-  __shared__ int32_t s_q[kVCap];
-  __shared__ int32_t s_rp[kVRows + 1];
+  __shared__ int32_t s_col[kTileCap];
+  __shared__ int32_t s_q[kTileCap];
+  __shared__ int32_t s_rp[kTileRows + 1];
   const int tid = threadIdx.x, r = tid / LPR, sub = tid % LPR;
   const int heads = p.heads, lph = p.lph, h = sub / lph, ed = p.edge_dim;
-  const V2Tile t = gv2_tile(p.rowptr, p.n, s_rp, ROWS);
-  const int staged = min(t.e1 - t.e0, kVCap);
+  const ConvTile t = conv_tile(p.rowptr, p.n, s_rp, ROWS);
+  const int staged = min(t.e1 - t.e0, kTileCap);
   for (int i = tid; i < staged; i += NT) {
     s_col[i] = p.colidx[t.e0 + i];
     s_q[i] = p.perm[t.e0 + i];
@@ -442,9 +389,9 @@ __global__ __launch_bounds__(ROWS * HC / 4) void gatv2_bwd_nodes_kernel(V2NodeAr
   const int ea = live ? s_rp[r] - t.e0 : 0, eb = live ? s_rp[r + 1] - t.e0 : 0;
   const int64_t row = t.r0 + r;
   const float slope = p.slope;
-  const float4 att = vld4(p.att + 4 * sub);
-  const VEdgeW<E> we = vload_we<E>(p.w_e, ed, HC, sub);
-  const float4 xl = live ? vld4(p.xlr + row * p.ldx + 4 * sub) : vzero4();
+  const float4 att = load4(p.att + 4 * sub);
+  const EdgeW<E> we = load_edge_w<E>(p.w_e, ed, HC, sub);
+  const float4 xl = live ? load4(p.xlr + row * p.ldx + 4 * sub) : zero4();
   const unsigned ldd4 = (unsigned)p.ldd * 4u, ldx4 = (unsigned)p.ldx * 4u, sub16 = (unsigned)sub * 16u;
   const __amdgpu_buffer_rsrc_t dd = __builtin_amdgcn_make_buffer_rsrc(
       (void*)p.d_out, (short)0, (int)((unsigned)(p.n - 1) * ldd4 + (unsigned)HC * 4u), 0x00020000);
@@ -453,30 +400,30 @@ __global__ __launch_bounds__(ROWS * HC / 4) void gatv2_bwd_nodes_kernel(V2NodeAr
       (void*)p.xlr, (short)0, (int)((unsigned)(p.n - 1) * ldx4 + (unsigned)HC * 8u), 0x00020000);
   const int32_t* __restrict__ gcol = p.colidx + t.e0;
   const int32_t* __restrict__ gq = p.perm + t.e0;
-  float4 acc = vzero4();
-  for (int e = ea; e < eb; e += kVU) {
-    float4 dv[kVU], xv[kVU], tv[kVU];
-    float av[kVU], zv[kVU];
-    int64_t en[kVU];
-    bool ok[kVU];
+  float4 acc = zero4();
+  for (int e = ea; e < eb; e += kTileU) {
+    float4 dv[kTileU], xv[kTileU], tv[kTileU];
+    float av[kTileU], zv[kTileU];
+    int64_t en[kTileU];
+    bool ok[kTileU];
 #pragma unroll
-    for (int u = 0; u < kVU; ++u) {
+    for (int u = 0; u < kTileU; ++u) {
       ok[u] = e + u < eb;
       const int ee = ok[u] ? e + u : e;
-      const bool st = ee < kVCap;
+      const bool st = ee < kTileCap;
       const int col = st ? s_col[ee] : gcol[ee];
       en[u] = st ? s_q[ee] : gq[ee];
-      dv[u] = vbuf4(dd, ok[u] ? (unsigned)col * ldd4 + sub16 : kVOut);
-      xv[u] = vbuf4(xd, ok[u] ? (unsigned)col * ldx4 + (unsigned)HC * 4u + sub16 : kVOut);
+      dv[u] = buf4(dd, ok[u] ? (unsigned)col * ldd4 + sub16 : kOffOut);
+      xv[u] = buf4(xd, ok[u] ? (unsigned)col * ldx4 + (unsigned)HC * 4u + sub16 : kOffOut);
       av[u] = ok[u] ? p.alpha[en[u] * heads + h] : 0.f;
       zv[u] = ok[u] ? p.dscore[en[u] * heads + h] : 0.f;
     }
     gv2_t_load(tv, p.e, p.lde, en, ok, we, ed);
 #pragma unroll
-    for (int u = 0; u < kVU; ++u) {
+    for (int u = 0; u < kTileU; ++u) {
       if (e + u < eb) {
         const float4 s = gv2_s(xl, xv[u], tv[u]);
-        acc = v4add(v4fma(av[u], dv[u], acc), gv2_ds(zv[u], att, s, slope));      // the transposed CSR's order
+        acc = add4(fma4(av[u], dv[u], acc), gv2_ds(zv[u], att, s, slope));      // the transposed CSR's order
       }
     }
   }
@@ -485,28 +432,16 @@ __global__ __launch_bounds__(ROWS * HC / 4) void gatv2_bwd_nodes_kernel(V2NodeAr
 
 bool v2_shape_ok(int64_t n, int32_t heads, int32_t c, int64_t ldx, int32_t edge_dim) {
   if (n < 0 || !(heads == 1 || heads == 2 || heads == 4 || heads == 8) || c < 4 || c > 128) return false;
-  if (edge_dim < 0 || edge_dim > kVEdgeMax) return false;
+  if (edge_dim < 0 || edge_dim > kEdgeMax) return false;
   const int hc = heads * c;
   return (hc == 16 || hc == 32 || hc == 64 || hc == 128) && ldx >= 2 * hc && ldx % 4 == 0 &&
          (uint64_t)n * (uint64_t)ldx * 4u < 0x100000000ull;
 }
-// rows per workgroup of the two backward kernels: 16 at HC = 128, where 32 rows are 1024 threads with 128 registers each and
-// W_e, its gradient and a trip's operands do not fit (they spilled); 512 threads may hold 256
-int v2_bwd_rows(int hc) { return hc == 128 ? 16 : kVRows; }
-bool v2_ld_ok(int64_t ld, int hc) { return ld >= hc && ld % 4 == 0 && ld < (1ll << 30); }
+// (the two backward kernels run conv_tile_rows rows per workgroup: at HC = 128 W_e, its gradient and a trip's operands do not
+// fit beside 32 rows; the forward keeps 32 at every width)
 
 const char* kV2Shapes = "needs heads in {1, 2, 4, 8}, heads * c in {16, 32, 64, 128}, c >= 4, ldx >= 2 * heads * c in multiples of 4 "
                         "floats, n * ldx * 4 < 2^32 and 0 <= edge_dim <= 8";
-
-// the kernels are built for 0, up to 2 and up to 8 edge features: W_e (and its gradient) hold that many float4 per lane, and
-// registers decide how many workgroups a CU keeps in flight
-#define GCNX_V2_DISPATCH_E(ed, HC_, BR_, LAUNCH) \
-  do { if ((ed) == 0) { LAUNCH(HC_, BR_, 0); } else if ((ed) <= 2) { LAUNCH(HC_, BR_, 2); } else { LAUNCH(HC_, BR_, 8); } } while (0)
-#define GCNX_V2_DISPATCH(hc, ed, LAUNCH)                                                        \
-  do {                                                                                          \
-    if ((hc) == 128) GCNX_V2_DISPATCH_E(ed, 128, 16, LAUNCH); else if ((hc) == 64) GCNX_V2_DISPATCH_E(ed, 64, 32, LAUNCH); \
-    else if ((hc) == 32) GCNX_V2_DISPATCH_E(ed, 32, 32, LAUNCH); else GCNX_V2_DISPATCH_E(ed, 16, 32, LAUNCH);             \
-  } while (0)
 
 }  // namespace
 
@@ -518,7 +453,7 @@ int gcnx_gatv2_conv_ok(int64_t n, int32_t heads, int32_t c, int64_t ldx, int32_t
 
 int64_t gcnx_gatv2_bwd_scratch_floats(int64_t n, int32_t heads, int32_t c, int32_t edge_dim) {
   if (n < 0 || heads < 0 || c < 0 || edge_dim < 0) return 0;
-  return (int64_t)gcnx_cdiv(n, v2_bwd_rows(heads * c)) * (1 + edge_dim) * heads * c;
+  return (int64_t)gcnx_cdiv(n, conv_tile_rows(heads * c)) * (1 + edge_dim) * heads * c;
 }
 
 int gcnx_gatv2_aggregate(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, const float* xlr, int64_t ldx, int32_t n,
@@ -532,7 +467,7 @@ int gcnx_gatv2_aggregate(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* co
                      heads, c, (long long)ldx, edge_dim);
   const int hc = heads * c;
   if (!gcnx_aligned16(xlr) || !gcnx_aligned16(w_e) || !gcnx_aligned16(att) || !gcnx_aligned16(bias) || !gcnx_aligned16(out) ||
-      !v2_ld_ok(ldo, hc) || (o_pre && (!gcnx_aligned16(o_pre) || !v2_ld_ok(ldp, hc))))
+      !conv_ld_ok(ldo, hc) || (o_pre && (!gcnx_aligned16(o_pre) || !conv_ld_ok(ldp, hc))))
     return gcnx_fail(ctx, GCNX_ERR_UNSUPPORTED, "gcnx_gatv2_aggregate: xlr, w_e, att, bias, out and o_pre must be 16-byte aligned, with ldo "
                      "and ldp >= heads * c in multiples of 4 floats");
   if (n == 0) return GCNX_OK;
@@ -543,10 +478,10 @@ int gcnx_gatv2_aggregate(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* co
   a.rowptr = rowptr; a.colidx = colidx; a.xlr = xlr; a.ldx = ldx; a.n = n; a.heads = heads; a.lph = c / 4; a.edge_dim = edge_dim;
   a.e = e; a.lde = lde; a.w_e = w_e; a.att = att; a.bias = bias; a.slope = slope; a.out = out; a.ldo = ldo; a.alpha = alpha;
   a.o_pre = o_pre; a.ldp = ldp;
-  const int tiles = gcnx_cdiv(n, kVRows);
-  const size_t dyn = alpha ? (size_t)kVCap * heads * sizeof(float) : 0;
+  const int tiles = gcnx_cdiv(n, kTileRows);
+  const size_t dyn = alpha ? (size_t)kTileCap * heads * sizeof(float) : 0;
 #define GCNX_V2_AGG(HC_, BR_, E_) hipLaunchKernelGGL((gatv2_aggregate_kernel<HC_, E_>), dim3(tiles), dim3(8 * HC_), dyn, ctx->stream, a)
-  GCNX_V2_DISPATCH(hc, edge_dim, GCNX_V2_AGG);
+  GCNX_CONV_DISPATCH(hc, edge_dim, GCNX_V2_AGG);
 #undef GCNX_V2_AGG
   GCNX_LAUNCH_OK(ctx);
   return GCNX_OK;
@@ -564,8 +499,8 @@ int gcnx_gatv2_bwd_edges(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* co
                      heads, c, (long long)ldx, edge_dim);
   const int hc = heads * c;
   if (!gcnx_aligned16(xlr) || !gcnx_aligned16(w_e) || !gcnx_aligned16(att) || !gcnx_aligned16(d_out) || !gcnx_aligned16(o) ||
-      !gcnx_aligned16(dxr) || !gcnx_aligned16(datt) || !gcnx_aligned16(dw_e) || !gcnx_aligned16(scratch) || !v2_ld_ok(ldd, hc) ||
-      !v2_ld_ok(ldo, hc) || !v2_ld_ok(ldg, hc))
+      !gcnx_aligned16(dxr) || !gcnx_aligned16(datt) || !gcnx_aligned16(dw_e) || !gcnx_aligned16(scratch) || !conv_ld_ok(ldd, hc) ||
+      !conv_ld_ok(ldo, hc) || !conv_ld_ok(ldg, hc))
     return gcnx_fail(ctx, GCNX_ERR_UNSUPPORTED, "gcnx_gatv2_bwd_edges: xlr, w_e, att, d_out, o, dxr, datt, dw_e and scratch must be 16-byte "
                      "aligned, with ldd, ldo and ldg >= heads * c in multiples of 4 floats");
   if (n == 0) return GCNX_OK;
@@ -578,9 +513,9 @@ int gcnx_gatv2_bwd_edges(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* co
   a.rowptr = rowptr; a.colidx = colidx; a.xlr = xlr; a.ldx = ldx; a.n = n; a.heads = heads; a.lph = c / 4; a.edge_dim = edge_dim;
   a.e = e; a.lde = lde; a.w_e = w_e; a.att = att; a.slope = slope; a.alpha = alpha; a.d_out = d_out; a.ldd = ldd; a.o = o; a.ldo = ldo;
   a.dscore = dscore; a.dxr = dxr; a.ldg = ldg; a.part = scratch;
-  const int tiles = gcnx_cdiv(n, v2_bwd_rows(hc));
+  const int tiles = gcnx_cdiv(n, conv_tile_rows(hc));
 #define GCNX_V2_BE(HC_, BR_, E_) hipLaunchKernelGGL((gatv2_bwd_edges_kernel<HC_, BR_, E_>), dim3(tiles), dim3(BR_ * HC_ / 4), 0, ctx->stream, a)
-  GCNX_V2_DISPATCH(hc, edge_dim, GCNX_V2_BE);
+  GCNX_CONV_DISPATCH(hc, edge_dim, GCNX_V2_BE);
 #undef GCNX_V2_BE
   GCNX_LAUNCH_OK(ctx);
   const int f = (1 + edge_dim) * hc;
@@ -602,7 +537,7 @@ int gcnx_gatv2_bwd_nodes(gcnx_ctx* ctx, const int32_t* rowptr_t, const int32_t* 
                      heads, c, (long long)ldx, edge_dim);
   const int hc = heads * c;
   if (!gcnx_aligned16(xlr) || !gcnx_aligned16(w_e) || !gcnx_aligned16(att) || !gcnx_aligned16(d_out) || !gcnx_aligned16(dxl) ||
-      !v2_ld_ok(ldd, hc) || !v2_ld_ok(ldg, hc) || !gcnx_fits_buffer(n, ldd, 4))
+      !conv_ld_ok(ldd, hc) || !conv_ld_ok(ldg, hc) || !gcnx_fits_buffer(n, ldd, 4))
     return gcnx_fail(ctx, GCNX_ERR_UNSUPPORTED, "gcnx_gatv2_bwd_nodes: xlr, w_e, att, d_out and dxl must be 16-byte aligned, with ldd and "
                      "ldg >= heads * c in multiples of 4 floats and n * ldd * 4 < 2^32");
   if (n == 0) return GCNX_OK;
@@ -613,9 +548,9 @@ int gcnx_gatv2_bwd_nodes(gcnx_ctx* ctx, const int32_t* rowptr_t, const int32_t* 
   a.rowptr = rowptr_t; a.colidx = colidx_t; a.perm = perm_t; a.xlr = xlr; a.ldx = ldx; a.n = n; a.heads = heads; a.lph = c / 4;
   a.edge_dim = edge_dim; a.e = e; a.lde = lde; a.w_e = w_e; a.att = att; a.slope = slope; a.alpha = alpha; a.dscore = dscore;
   a.d_out = d_out; a.ldd = ldd; a.dxl = dxl; a.ldg = ldg;
-  const int tiles = gcnx_cdiv(n, v2_bwd_rows(hc));
+  const int tiles = gcnx_cdiv(n, conv_tile_rows(hc));
 #define GCNX_V2_BN(HC_, BR_, E_) hipLaunchKernelGGL((gatv2_bwd_nodes_kernel<HC_, BR_, E_>), dim3(tiles), dim3(BR_ * HC_ / 4), 0, ctx->stream, a)
-  GCNX_V2_DISPATCH(hc, edge_dim, GCNX_V2_BN);
+  GCNX_CONV_DISPATCH(hc, edge_dim, GCNX_V2_BN);
 #undef GCNX_V2_BN
   GCNX_LAUNCH_OK(ctx);
   return GCNX_OK;

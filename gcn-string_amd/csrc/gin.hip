@@ -7,8 +7,7 @@
 //
 // composed from existing calls this is a neighbour sum, a scaled add, and two gcnx_gemm, with two [N, F] intermediates written
 // and read back -- at N = 600 ... 20 000 each of them is a launch latency, not a throughput.  Here a workgroup owns 32 rows
-// from the gather to the second bias, like sage_conv_kernel (sage.hip; its device helpers are copied here, not shared: that
-// file's bit-exactness and resource tests are yardsticks and a common header would rebuild it):
+// from the gather to the second bias, like sage_conv_kernel (sage.hip; the device helpers they share: conv_tile.h):
 //     gather the neighbours' rows of x, add (1 + eps) times the row's own -> T tile [32, K0] in LDS
 //     -> MFMA of T with W_a -> bias, ReLU in registers -> U tile [32, k1] in LDS, in the A-operand layout
 //     -> MFMA of U with W_b -> bias -> out
@@ -39,13 +38,10 @@
 //
 // gin_aggregate_kernel is T alone for any width; gin_eps_* is the gradient with respect to eps, sum_i <x_i, dT_i>.
 #include "common.h"
+#include "conv_tile.h"
 
 namespace {
 
-typedef float g32x4v __attribute__((ext_vector_type(4)));
-
-constexpr int kGRows = 32;        // rows per workgroup
-constexpr int kGCap = 1024;       // CSR entries of a tile staged in LDS (the rest is read from global memory)
 constexpr int kGMaxW = 128;       // widest stage
 
 struct GinArgs {
@@ -62,37 +58,28 @@ struct GinArgs {
   float* out; int64_t ldo;
 };
 
-__device__ __forceinline__ float4 gbuf4(__amdgpu_buffer_rsrc_t rs, unsigned off) {
-  const g32x4v r = __builtin_bit_cast(g32x4v, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0));
-  return make_float4(r.x, r.y, r.z, r.w);
-}
-__device__ __forceinline__ float4 g4add(float4 a, float4 h) { return make_float4(a.x + h.x, a.y + h.y, a.z + h.z, a.w + h.w); }
-__device__ __forceinline__ float4 g4fma(float s, float4 h, float4 a) {
-  return make_float4(fmaf(s, h.x, a.x), fmaf(s, h.y, a.y), fmaf(s, h.z, a.z), fmaf(s, h.w, a.w));
-}
-
 template <int K>
 __global__ __launch_bounds__(512) void gin_conv_kernel(GinArgs p) {
   constexpr int LPR = K / 4;                 // lanes per gathered row
   constexpr int GW = 64 / LPR < 4 ? 64 / LPR : 4;   // row groups per wave that hold rows (the lanes behind them idle in the gather)
   constexpr int NG = 8 * GW;                 // row groups per workgroup
-  constexpr int RPG = kGRows / NG;           // rows per group (2 at K = 128)
+  constexpr int RPG = kTileRows / NG;        // rows per group (2 at K = 128)
   constexpr int U = 4;                       // entries per row per trip
   constexpr int SL = 2 * U;                  // slack entries behind the staged ones
   static_assert(K == 16 || K == 32 || K == 64 || K == 128, "gather width");
-  static_assert(NG * RPG == kGRows, "every row of the tile has a lane group");
-  __shared__ __attribute__((aligned(16))) float tile_t[kGRows][K + 4];        // row stride K + 4: see the A-operand read
-  __shared__ __attribute__((aligned(16))) float tile_u[kGRows * (kGMaxW + 4)];   // row stride k1 + 4
-  __shared__ int32_t s_ent[kGCap + SL];      // staged CSR entries: byte offset of the gathered row = column * ldx * 4
-  __shared__ int32_t s_rp[kGRows + 1];
+  static_assert(NG * RPG == kTileRows, "every row of the tile has a lane group");
+  __shared__ __attribute__((aligned(16))) float tile_t[kTileRows][K + 4];        // row stride K + 4: see the A-operand read
+  __shared__ __attribute__((aligned(16))) float tile_u[kTileRows * (kGMaxW + 4)];   // row stride k1 + 4
+  __shared__ int32_t s_ent[kTileCap + SL];   // staged CSR entries: byte offset of the gathered row = column * ldx * 4
+  __shared__ int32_t s_rp[kTileRows + 1];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int ntiles = gridDim.x;
   const int tl = gcnx_xcd_remap(blockIdx.x, ntiles);
-  const int r0 = tl * kGRows, nr = min(p.n - r0, kGRows);
+  const int r0 = tl * kTileRows, nr = min(p.n - r0, kTileRows);
   if (tid <= nr) s_rp[tid] = p.rowptr[r0 + tid];
   const int e0 = p.rowptr[r0], e1 = p.rowptr[r0 + nr];
-  const int staged = min(e1 - e0, kGCap);
+  const int staged = min(e1 - e0, kTileCap);
   const unsigned ld4 = (unsigned)p.ldx * 4u;             // bytes per row of x
   for (int i = tid; i < staged + SL; i += 512) s_ent[i] = i < staged ? (int)((unsigned)p.colidx[e0 + i] * ld4) : 0;
   // ---- the rows' own pieces: in flight from here to the end of the gather -----------------------------------------------
@@ -122,8 +109,8 @@ __global__ __launch_bounds__(512) void gin_conv_kernel(GinArgs p) {
     const bool live = has_rows && r < nr;
     ea[j] = live ? s_rp[r] - e0 : 0;
     eb[j] = live ? s_rp[r + 1] - e0 : 0;
-    ebf[j] = min(eb[j], kGCap);                      // the staged part of the row ...
-    ea[j] = min(ea[j], kGCap);                       // ... (empty if the row starts past it)
+    ebf[j] = min(eb[j], kTileCap);                   // the staged part of the row ...
+    ea[j] = min(ea[j], kTileCap);                    // ... (empty if the row starts past it)
     len = max(len, ebf[j] - ea[j]);
   }
   const unsigned sub16 = (unsigned)sub * 16u;
@@ -137,20 +124,20 @@ __global__ __launch_bounds__(512) void gin_conv_kernel(GinArgs p) {
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int e = eb_ + u;
-        hv[j][u] = gbuf4(xr, e < ebf[j] ? (unsigned)s_ent[e] + sub16 : 0xFFFFFFF0u);
+        hv[j][u] = buf4(xr, e < ebf[j] ? (unsigned)s_ent[e] + sub16 : kOffOut);
       }
     }
     __builtin_amdgcn_sched_barrier(0);                 // all loads of the trip go out before the first is consumed
 #pragma unroll
     for (int j = 0; j < RPG; ++j)
 #pragma unroll
-      for (int u = 0; u < U; ++u) acc[j] = g4add(acc[j], hv[j][u]);
+      for (int u = 0; u < U; ++u) acc[j] = add4(acc[j], hv[j][u]);
   }
-  if (e1 - e0 > kGCap) {       // uniform per workgroup, rare: entries beyond the staged ones, one at a time from global memory
+  if (e1 - e0 > kTileCap) {       // uniform per workgroup, rare: entries beyond the staged ones, one at a time from global memory
 #pragma unroll
     for (int j = 0; j < RPG; ++j)
-      for (int e = max(eb[j] > 0 ? s_rp[gid + j * NG] - e0 : 0, kGCap); e < eb[j]; ++e)   // (ea is clamped: the row's true start)
-        acc[j] = g4add(acc[j], gbuf4(xr, (unsigned)p.colidx[e0 + e] * ld4 + sub16));
+      for (int e = max(eb[j] > 0 ? s_rp[gid + j * NG] - e0 : 0, kTileCap); e < eb[j]; ++e)   // (ea is clamped: the row's true start)
+        acc[j] = add4(acc[j], buf4(xr, (unsigned)p.colidx[e0 + e] * ld4 + sub16));
   }
   // ---- this wave's slice of W_a, in the MFMA B layout; in flight while the tile is written -----------------------------
   const int c16 = lane & 15, kq = lane >> 4;
@@ -169,7 +156,7 @@ __global__ __launch_bounds__(512) void gin_conv_kernel(GinArgs p) {
 #pragma unroll
     for (int j = 0; j < RPG; ++j) {
       const int r = gid + j * NG;
-      const float4 tv = g4fma(scale, own[j], acc[j]);
+      const float4 tv = fma4(scale, own[j], acc[j]);
       if (p.t && r < nr) *reinterpret_cast<float4*>(p.t + (int64_t)(r0 + r) * p.ldt + sub * 4) = tv;
       *reinterpret_cast<float4*>(&tile_t[r][sub * 4]) = tv;          // rows past the end hold zeros
     }
@@ -180,7 +167,7 @@ __global__ __launch_bounds__(512) void gin_conv_kernel(GinArgs p) {
   const int su = p.k1 + 4;                             // row stride of the U tile
   if (on1) {
     const float bcol = p.b_a ? p.b_a[col] : 0.f;
-    g32x4v c0 = {0.f, 0.f, 0.f, 0.f}, c1 = c0;
+    gcnx_f32x4 c0 = {0.f, 0.f, 0.f, 0.f}, c1 = c0;
 #pragma unroll
     for (int kk = 0; kk < K / 4; ++kk) {
       const float a0 = tile_t[c16][4 * kk + kq];
@@ -219,7 +206,7 @@ __global__ __launch_bounds__(512) void gin_conv_kernel(GinArgs p) {
   __syncthreads();
   if (!on2) return;
   const float bcol2 = p.b_b ? p.b_b[col] : 0.f;
-  g32x4v d0 = {0.f, 0.f, 0.f, 0.f}, d1 = d0;
+  gcnx_f32x4 d0 = {0.f, 0.f, 0.f, 0.f}, d1 = d0;
 #pragma unroll
   for (int g = 0; g < kGMaxW / 16; ++g) {
     if (16 * g < p.k1) {
@@ -249,7 +236,7 @@ bool gin_shape_ok(int64_t n, int32_t k0, int32_t k1, int32_t k2, int64_t ldx) {
 }
 
 int launch_gin(gcnx_ctx* ctx, const GinArgs& a, int k0) {
-  const int tiles = gcnx_cdiv(a.n, kGRows);
+  const int tiles = gcnx_cdiv(a.n, kTileRows);
   if (k0 == 128) hipLaunchKernelGGL((gin_conv_kernel<128>), dim3(tiles), dim3(512), 0, ctx->stream, a);
   else if (k0 == 64) hipLaunchKernelGGL((gin_conv_kernel<64>), dim3(tiles), dim3(512), 0, ctx->stream, a);
   else if (k0 == 32) hipLaunchKernelGGL((gin_conv_kernel<32>), dim3(tiles), dim3(512), 0, ctx->stream, a);
@@ -265,8 +252,8 @@ template <> struct GinVec<4> {
   __device__ __forceinline__ void zero() { v = make_float4(0.f, 0.f, 0.f, 0.f); }
   __device__ __forceinline__ void load(const float* p) { v = *reinterpret_cast<const float4*>(p); }
   __device__ __forceinline__ void store(float* p) const { *reinterpret_cast<float4*>(p) = v; }
-  __device__ __forceinline__ void add(const GinVec& o) { v = g4add(v, o.v); }
-  __device__ __forceinline__ void scale_add(float s, const GinVec& o) { v = g4fma(s, o.v, v); }
+  __device__ __forceinline__ void add(const GinVec& o) { v = add4(v, o.v); }
+  __device__ __forceinline__ void scale_add(float s, const GinVec& o) { v = fma4(s, o.v, v); }
 };
 template <> struct GinVec<1> {
   float v;

@@ -12,8 +12,8 @@
 // rounded on its own, no FMA, edge features added in ascending order, then the bias, then x_j; the positive side is m > 0), so
 // they agree on the side of every kink.
 //
-// gine_conv_kernel is gin_conv_kernel's workgroup (gin.hip; its device helpers are copied here, not shared: that file's
-// bit-exactness tests are yardsticks): 512 threads, 32 rows, K0 / 4 lanes per gathered row, the tile's CSR entries staged
+// gine_conv_kernel is gin_conv_kernel's workgroup (gin.hip; the device helpers they share: conv_tile.h): 512 threads, 32 rows,
+// K0 / 4 lanes per gathered row, the tile's CSR entries staged
 // in LDS, four entries per row and trip with every load of a trip issued before the first is consumed, then two chained
 // v_mfma_f32_16x16x4_f32 stages through LDS tiles.  What differs in the gather:
 //   e        an entry's features are read by every lane of its row's group with range-checked scalar-width buffer loads from a
@@ -30,15 +30,11 @@
 // over the forward CSR for dW_e and db_e (per-workgroup parts, then one small launch over them, both in a fixed order);
 // gine_bwd_nodes_kernel the pass over the transposed pattern for dx.
 #include "common.h"
+#include "conv_tile.h"
 
 namespace {
 
-typedef float e32x4v __attribute__((ext_vector_type(4)));
-
-constexpr int kERows = 32;        // rows per workgroup
-constexpr int kECap = 1024;       // CSR entries of a tile staged in LDS (the rest is read from global memory)
 constexpr int kEMaxW = 128;       // widest stage
-constexpr int kEMaxD = 8;         // most edge features
 constexpr int kEdgeRows = 32;     // rows per workgroup of the dW_e / db_e pass
 
 struct GineArgs {
@@ -57,9 +53,6 @@ struct GineArgs {
   float* out; int64_t ldo;
 };
 
-__device__ __forceinline__ e32x4v ebuf4(__amdgpu_buffer_rsrc_t rs, unsigned off) {
-  return __builtin_bit_cast(e32x4v, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0));
-}
 __device__ __forceinline__ float ebuf1(__amdgpu_buffer_rsrc_t rs, unsigned off) {
   return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, off, 0, 0));
 }
@@ -86,23 +79,23 @@ __global__ __launch_bounds__(512) void gine_conv_kernel(GineArgs p) {
   constexpr int LPR = K / 4;                 // lanes per gathered row
   constexpr int GW = 64 / LPR < 4 ? 64 / LPR : 4;   // row groups per wave that hold rows (the lanes behind them idle in the gather)
   constexpr int NG = 8 * GW;                 // row groups per workgroup
-  constexpr int RPG = kERows / NG;           // rows per group (2 at K = 128)
+  constexpr int RPG = kTileRows / NG;        // rows per group (2 at K = 128)
   constexpr int U = 4;                       // entries per row per trip
   constexpr int SL = 2 * U;                  // slack entries behind the staged ones
   static_assert(K == 16 || K == 32 || K == 64 || K == 128, "gather width");
-  static_assert(NG * RPG == kERows, "every row of the tile has a lane group");
-  __shared__ __attribute__((aligned(16))) float tile_t[kERows][K + 4];        // row stride K + 4: see gin.hip, the A-operand read
-  __shared__ __attribute__((aligned(16))) float tile_u[kERows * (kEMaxW + 4)];   // row stride k1 + 4
-  __shared__ int32_t s_ent[kECap + SL];      // staged CSR entries: byte offset of the gathered row = column * ldx * 4
-  __shared__ int32_t s_rp[kERows + 1];
+  static_assert(NG * RPG == kTileRows, "every row of the tile has a lane group");
+  __shared__ __attribute__((aligned(16))) float tile_t[kTileRows][K + 4];        // row stride K + 4: see gin.hip, the A-operand read
+  __shared__ __attribute__((aligned(16))) float tile_u[kTileRows * (kEMaxW + 4)];   // row stride k1 + 4
+  __shared__ int32_t s_ent[kTileCap + SL];   // staged CSR entries: byte offset of the gathered row = column * ldx * 4
+  __shared__ int32_t s_rp[kTileRows + 1];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int ntiles = gridDim.x;
   const int tl = gcnx_xcd_remap(blockIdx.x, ntiles);
-  const int r0 = tl * kERows, nr = min(p.n - r0, kERows);
+  const int r0 = tl * kTileRows, nr = min(p.n - r0, kTileRows);
   if (tid <= nr) s_rp[tid] = p.rowptr[r0 + tid];
   const int e0 = p.rowptr[r0], e1 = p.rowptr[r0 + nr];
-  const int staged = min(e1 - e0, kECap);
+  const int staged = min(e1 - e0, kTileCap);
   const unsigned ld4 = (unsigned)p.ldx * 4u;             // bytes per row of x
   for (int i = tid; i < staged + SL; i += 512) s_ent[i] = i < staged ? (int)((unsigned)p.colidx[e0 + i] * ld4) : 0;
   // ---- the rows' own pieces and the lane's columns of W_e / b_e: in flight from here to the end of the gather ------------
@@ -152,14 +145,14 @@ __global__ __launch_bounds__(512) void gine_conv_kernel(GineArgs p) {
     const bool live = has_rows && r < nr;
     ea[j] = live ? s_rp[r] - e0 : 0;
     eb[j] = live ? s_rp[r + 1] - e0 : 0;
-    ebf[j] = min(eb[j], kECap);                      // the staged part of the row ...
-    ea[j] = min(ea[j], kECap);                       // ... (empty if the row starts past it)
+    ebf[j] = min(eb[j], kTileCap);                   // the staged part of the row ...
+    ea[j] = min(ea[j], kTileCap);                    // ... (empty if the row starts past it)
     len = max(len, ebf[j] - ea[j]);
   }
   const unsigned sub16 = (unsigned)sub * 16u;
   // Branch-free, as in gin.hip: slots past the row's end get out-of-range offsets and fetch nothing.
   for (int tt = 0; __builtin_amdgcn_ballot_w64(tt < len) != 0; tt += U) {
-    e32x4v hv[RPG][U];
+    gcnx_f32x4 hv[RPG][U];
     float ev[RPG][U][DM];
 #pragma unroll
     for (int j = 0; j < RPG; ++j) {
@@ -168,9 +161,9 @@ __global__ __launch_bounds__(512) void gine_conv_kernel(GineArgs p) {
       for (int u = 0; u < U; ++u) {
         const int e = eb_ + u;
         const bool live = e < ebf[j];
-        hv[j][u] = ebuf4(xr, live ? (unsigned)s_ent[e] + sub16 : 0xFFFFFFF0u);
+        hv[j][u] = buf4v(xr, live ? (unsigned)s_ent[e] + sub16 : kOffOut);
 #pragma unroll
-        for (int d = 0; d < DM; ++d) ev[j][u][d] = ebuf1(er, live && d < dn ? (unsigned)e * lde4 + 4u * d : 0xFFFFFFF0u);
+        for (int d = 0; d < DM; ++d) ev[j][u][d] = ebuf1(er, live && d < dn ? (unsigned)e * lde4 + 4u * d : kOffOut);
       }
     }
     __builtin_amdgcn_sched_barrier(0);                 // all loads of the trip go out before the first is consumed
@@ -188,11 +181,11 @@ __global__ __launch_bounds__(512) void gine_conv_kernel(GineArgs p) {
       }
     }
   }
-  if (e1 - e0 > kECap) {       // uniform per workgroup, rare: entries beyond the staged ones, one at a time from global memory
+  if (e1 - e0 > kTileCap) {       // uniform per workgroup, rare: entries beyond the staged ones, one at a time from global memory
 #pragma unroll
     for (int j = 0; j < RPG; ++j)
-      for (int e = max(eb[j] > 0 ? s_rp[gid + j * NG] - e0 : 0, kECap); e < eb[j]; ++e) {   // (ea is clamped: the row's true start)
-        const e32x4v h = ebuf4(xr, (unsigned)p.colidx[e0 + e] * ld4 + sub16);
+      for (int e = max(eb[j] > 0 ? s_rp[gid + j * NG] - e0 : 0, kTileCap); e < eb[j]; ++e) {   // (ea is clamped: the row's true start)
+        const gcnx_f32x4 h = buf4v(xr, (unsigned)p.colidx[e0 + e] * ld4 + sub16);
         float ev1[DM];
 #pragma unroll
         for (int d = 0; d < DM; ++d) ev1[d] = d < dn ? p.e[(int64_t)(e0 + e) * p.lde + d] : 0.f;
@@ -230,7 +223,7 @@ __global__ __launch_bounds__(512) void gine_conv_kernel(GineArgs p) {
   const int su = p.k1 + 4;                             // row stride of the U tile
   if (on1) {
     const float bcol = p.b_a ? p.b_a[col] : 0.f;
-    e32x4v c0 = {0.f, 0.f, 0.f, 0.f}, c1 = c0;
+    gcnx_f32x4 c0 = {0.f, 0.f, 0.f, 0.f}, c1 = c0;
 #pragma unroll
     for (int kk = 0; kk < K / 4; ++kk) {
       const float a0 = tile_t[c16][4 * kk + kq];
@@ -264,7 +257,7 @@ __global__ __launch_bounds__(512) void gine_conv_kernel(GineArgs p) {
   __syncthreads();
   if (!on2) return;
   const float bcol2 = p.b_b ? p.b_b[col] : 0.f;
-  e32x4v d0 = {0.f, 0.f, 0.f, 0.f}, d1 = d0;
+  gcnx_f32x4 d0 = {0.f, 0.f, 0.f, 0.f}, d1 = d0;
 #pragma unroll
   for (int g = 0; g < kEMaxW / 16; ++g) {
     if (16 * g < p.k1) {
@@ -287,7 +280,7 @@ __global__ __launch_bounds__(512) void gine_conv_kernel(GineArgs p) {
 }
 
 bool gine_width_ok(int32_t k) { return k >= 16 && k <= kEMaxW && k % 16 == 0; }
-bool gine_dim_ok(int32_t d) { return d >= 1 && d <= kEMaxD; }
+bool gine_dim_ok(int32_t d) { return d >= 1 && d <= kEdgeMax; }
 
 bool gine_shape_ok(int64_t n, int32_t k0, int32_t k1, int32_t k2, int64_t ldx, int32_t edge_dim) {
   return n >= 0 && n <= 0x7FFFFFFFll && (k0 == 16 || k0 == 32 || k0 == 64 || k0 == 128) && gine_width_ok(k1) && gine_width_ok(k2) &&
@@ -296,7 +289,7 @@ bool gine_shape_ok(int64_t n, int32_t k0, int32_t k1, int32_t k2, int64_t ldx, i
 
 template <int DM>
 int launch_gine(gcnx_ctx* ctx, const GineArgs& a, int k0) {
-  const int tiles = gcnx_cdiv(a.n, kERows);
+  const int tiles = gcnx_cdiv(a.n, kTileRows);
   if (k0 == 128) hipLaunchKernelGGL((gine_conv_kernel<128, DM>), dim3(tiles), dim3(512), 0, ctx->stream, a);
   else if (k0 == 64) hipLaunchKernelGGL((gine_conv_kernel<64, DM>), dim3(tiles), dim3(512), 0, ctx->stream, a);
   else if (k0 == 32) hipLaunchKernelGGL((gine_conv_kernel<32, DM>), dim3(tiles), dim3(512), 0, ctx->stream, a);
@@ -570,10 +563,10 @@ __global__ __launch_bounds__(256) void gine_bwd_nodes_kernel(const int32_t* __re
   do {                                                                                        \
     if (vec) {                                                                                \
       if ((d_n) <= 2) hipLaunchKernelGGL((KERNEL<4, 2>), __VA_ARGS__);                        \
-      else hipLaunchKernelGGL((KERNEL<4, kEMaxD>), __VA_ARGS__);                              \
+      else hipLaunchKernelGGL((KERNEL<4, kEdgeMax>), __VA_ARGS__);                            \
     } else {                                                                                  \
       if ((d_n) <= 2) hipLaunchKernelGGL((KERNEL<1, 2>), __VA_ARGS__);                        \
-      else hipLaunchKernelGGL((KERNEL<1, kEMaxD>), __VA_ARGS__);                              \
+      else hipLaunchKernelGGL((KERNEL<1, kEdgeMax>), __VA_ARGS__);                            \
     }                                                                                         \
   } while (0)
 
@@ -618,7 +611,7 @@ int gcnx_gine_conv(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, 
   a.rowptr = rowptr; a.colidx = colidx; a.x = x; a.ldx = ldx; a.n = n; a.eps = eps; a.e = e; a.lde = lde; a.edge_dim = edge_dim;
   a.w_e = w_e; a.b_e = b_e; a.w_a = w_a; a.b_a = b_a; a.k1 = k1; a.w_b = w_b; a.b_b = b_b; a.k2 = k2;
   a.t = t; a.ldt = ldt; a.u = u; a.ldu = ldu; a.out = out; a.ldo = ldo;
-  return edge_dim <= 2 ? launch_gine<2>(ctx, a, k0) : launch_gine<kEMaxD>(ctx, a, k0);
+  return edge_dim <= 2 ? launch_gine<2>(ctx, a, k0) : launch_gine<kEdgeMax>(ctx, a, k0);
 }
 
 int gcnx_gine_aggregate(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, const float* x, int64_t ldx, const float* eps,

@@ -16,9 +16,9 @@
 // underflows to 0 for a > 88 and g = 1 -- g in [0, 1] and g (1 - g) finite (0 at both ends) for every finite a, no 0 * inf.
 // fp32 throughout, no float atomics, every sum in a fixed order: the same call leaves the same bits.
 //
-// Shape of a workgroup (gatv2.hip's; the device helpers are copied, not shared: that file's, gat.hip's, sage.hip's and
-// fused.hip's bit-exactness tests are yardsticks and a common header would rebuild them): 32 rows, one lane group of H / 4
-// lanes per row with one float4 of the row each -- 8 H threads (H = 128: 16 rows, see rg_rows).  The tile's CSR entries are
+// Shape of a workgroup (gatv2.hip's; the device helpers they share: conv_tile.h): 32 rows, one lane group of H / 4 lanes per
+// row with one float4 of the row each -- 8 H threads (H = 128: 16 rows, see conv_tile_rows: the two blocks of W_e, their
+// gradients and a trip's operands do not fit beside 32 rows).  The tile's CSR entries are
 // staged in LDS (1024 of them; a tile with more reads the rest from global memory).  Q[j] | V[j] are adjacent in P: one
 // entry costs one contiguous 2 H piece of row j, gathered with range-checked buffer loads -- slots past a row's end fetch
 // nothing.  W_ke + W_qe (summed as they are loaded) and W_ve sit in registers: 2 E float4 per lane in the kernel built for
@@ -26,35 +26,11 @@
 #include <cmath>
 
 #include "common.h"
+#include "conv_tile.h"
 
 namespace {
 
-typedef float rgf32x4v __attribute__((ext_vector_type(4)));
-
-constexpr int kRRows = 32;        // rows per workgroup (H = 128: 16)
-constexpr int kRCap = 1024;       // CSR entries of a tile staged in LDS (the rest is read from global memory)
-constexpr int kRU = 4;            // entries per row per trip
-constexpr int kREdgeMax = 8;      // edge features served
-constexpr unsigned kROut = 0xFFFFFFF0u;   // an offset no descriptor holds
-
-__device__ __forceinline__ float4 rbuf4(__amdgpu_buffer_rsrc_t rs, unsigned off) {
-  const rgf32x4v r = __builtin_bit_cast(rgf32x4v, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0));
-  return make_float4(r.x, r.y, r.z, r.w);
-}
-__device__ __forceinline__ float4 r4fma(float v, float4 h, float4 a) {
-  return make_float4(fmaf(v, h.x, a.x), fmaf(v, h.y, a.y), fmaf(v, h.z, a.z), fmaf(v, h.w, a.w));
-}
-__device__ __forceinline__ float4 r4fma4(float4 v, float4 h, float4 a) {
-  return make_float4(fmaf(v.x, h.x, a.x), fmaf(v.y, h.y, a.y), fmaf(v.z, h.z, a.z), fmaf(v.w, h.w, a.w));
-}
-__device__ __forceinline__ float4 r4mul(float4 a, float4 b) { return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w); }
-__device__ __forceinline__ float4 r4add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-__device__ __forceinline__ float4 rld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ float4 rzero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-
-// sigmoid(a) for every finite a: exp(-a) = +inf gives 1 / inf = 0, exp(-a) = 0 gives 1
-__device__ __forceinline__ float rg_sig1(float a) { return __builtin_amdgcn_rcpf(1.0f + __expf(-a)); }
-__device__ __forceinline__ float4 rg_sig(float4 a) { return make_float4(rg_sig1(a.x), rg_sig1(a.y), rg_sig1(a.z), rg_sig1(a.w)); }
+__device__ __forceinline__ float4 rg_sig(float4 a) { return make_float4(sigmoid1(a.x), sigmoid1(a.y), sigmoid1(a.z), sigmoid1(a.w)); }
 // g (1 - g): 0 at g = 0 and at g = 1
 __device__ __forceinline__ float4 rg_dsig(float4 g) {
   return make_float4(g.x * (1.0f - g.x), g.y * (1.0f - g.y), g.z * (1.0f - g.z), g.w * (1.0f - g.w));
@@ -66,23 +42,21 @@ template <int E> struct RGEdgeW { float4 g[E > 0 ? E : 1]; float4 v[E > 0 ? E : 
 template <int E>
 __device__ __forceinline__ RGEdgeW<E> rg_load_we(const float* __restrict__ w_e, int edge_dim, int h, int sub) {
   RGEdgeW<E> r;
-  r.g[0] = rzero4();
-  r.v[0] = rzero4();
+  r.g[0] = zero4();
+  r.v[0] = zero4();
 #pragma unroll
   for (int d = 0; d < E; ++d) {
     const float* row = w_e + (int64_t)d * 3 * h + 4 * sub;
-    r.g[d] = d < edge_dim ? r4add(rld4(row), rld4(row + h)) : rzero4();
-    r.v[d] = d < edge_dim ? rld4(row + 2 * h) : rzero4();
+    r.g[d] = d < edge_dim ? add4(load4(row), load4(row + h)) : zero4();
+    r.v[d] = d < edge_dim ? load4(row + 2 * h) : zero4();
   }
   return r;
 }
-// one entry's edge features (uniform over the lane group)
-template <int E> struct RGEdgeF { float v[E > 0 ? E : 1]; };
 // a += e (W_ke + W_qe), m += e W_ve for the U entries of a trip, d ascending; ok[u] = false: the features read as zeros.
 // Feature d is loaded and used inside the (uniform) test of feature d - 1, so a trip costs edge_dim + 1 branches and every
 // register index is a constant.  The features stay in r for the kernel that needs them again (dw_e).
 template <int Dd, int E, int U>
-__device__ __forceinline__ void rg_edge_from(float4 (&a)[U], float4 (&m)[U], RGEdgeF<E> (&r)[U], const float* __restrict__ e, int64_t lde,
+__device__ __forceinline__ void rg_edge_from(float4 (&a)[U], float4 (&m)[U], EdgeF<E> (&r)[U], const float* __restrict__ e, int64_t lde,
                                              const int64_t (&entry)[U], const bool (&ok)[U], const RGEdgeW<E>& w, int edge_dim) {
   if constexpr (Dd < E) {
     if (Dd < edge_dim) {
@@ -90,15 +64,15 @@ __device__ __forceinline__ void rg_edge_from(float4 (&a)[U], float4 (&m)[U], RGE
       for (int u = 0; u < U; ++u) r[u].v[Dd] = ok[u] ? e[entry[u] * lde + Dd] : 0.f;
 #pragma unroll
       for (int u = 0; u < U; ++u) {
-        a[u] = r4fma(r[u].v[Dd], w.g[Dd], a[u]);
-        m[u] = r4fma(r[u].v[Dd], w.v[Dd], m[u]);
+        a[u] = fma4(r[u].v[Dd], w.g[Dd], a[u]);
+        m[u] = fma4(r[u].v[Dd], w.v[Dd], m[u]);
       }
       rg_edge_from<Dd + 1, E, U>(a, m, r, e, lde, entry, ok, w, edge_dim);
     }
   }
 }
 template <int E, int U>
-__device__ __forceinline__ void rg_edge(float4 (&a)[U], float4 (&m)[U], RGEdgeF<E> (&r)[U], const float* __restrict__ e, int64_t lde,
+__device__ __forceinline__ void rg_edge(float4 (&a)[U], float4 (&m)[U], EdgeF<E> (&r)[U], const float* __restrict__ e, int64_t lde,
                                         const int64_t (&entry)[U], const bool (&ok)[U], const RGEdgeW<E>& w, int edge_dim) {
 #pragma unroll
   for (int u = 0; u < U; ++u)
@@ -108,28 +82,14 @@ __device__ __forceinline__ void rg_edge(float4 (&a)[U], float4 (&m)[U], RGEdgeF<
 }
 // dW_ke + dW_qe's common block += e (x) da, dW_ve += e (x) dm of one entry (nested the same way)
 template <int Dd, int E>
-__device__ __forceinline__ void rg_dwe_from(RGEdgeW<E>& dwe, const RGEdgeF<E>& e, float4 da, float4 dm, int edge_dim) {
+__device__ __forceinline__ void rg_dwe_from(RGEdgeW<E>& dwe, const EdgeF<E>& e, float4 da, float4 dm, int edge_dim) {
   if constexpr (Dd < E) {
     if (Dd < edge_dim) {
-      dwe.g[Dd] = r4fma(e.v[Dd], da, dwe.g[Dd]);
-      dwe.v[Dd] = r4fma(e.v[Dd], dm, dwe.v[Dd]);
+      dwe.g[Dd] = fma4(e.v[Dd], da, dwe.g[Dd]);
+      dwe.v[Dd] = fma4(e.v[Dd], dm, dwe.v[Dd]);
       rg_dwe_from<Dd + 1, E>(dwe, e, da, dm, edge_dim);
     }
   }
-}
-
-// ---- what every tile kernel starts with: its rows, their entry range ----------------------------------------------------
-struct RGTile {
-  int r0, nr, e0, e1;
-};
-__device__ __forceinline__ RGTile rg_tile(const int32_t* __restrict__ rowptr, int32_t n, int32_t* s_rp, int rows) {
-  RGTile t;
-  t.r0 = gcnx_xcd_remap(blockIdx.x, gridDim.x) * rows;
-  t.nr = min(n - t.r0, rows);
-  if ((int)threadIdx.x <= t.nr) s_rp[threadIdx.x] = rowptr[t.r0 + threadIdx.x];
-  t.e0 = rowptr[t.r0];
-  t.e1 = rowptr[t.r0 + t.nr];
-  return t;
 }
 
 struct RGFwdArgs {
@@ -147,11 +107,11 @@ struct RGFwdArgs {
 template <int H, int ROWS, int E>
 __global__ __launch_bounds__(ROWS * H / 4) void resgated_aggregate_kernel(RGFwdArgs p) {
   constexpr int LPR = H / 4, NT = ROWS * LPR;
-  __shared__ int32_t s_col[kRCap];
-  __shared__ int32_t s_rp[kRRows + 1];
+  __shared__ int32_t s_col[kTileCap];
+  __shared__ int32_t s_rp[kTileRows + 1];
   const int tid = threadIdx.x, r = tid / LPR, sub = tid % LPR, ed = p.edge_dim;
-  const RGTile t = rg_tile(p.rowptr, p.n, s_rp, ROWS);
-  const int staged = min(t.e1 - t.e0, kRCap);
+  const ConvTile t = conv_tile(p.rowptr, p.n, s_rp, ROWS);
+  const int staged = min(t.e1 - t.e0, kTileCap);
   for (int i = tid; i < staged; i += NT) s_col[i] = p.colidx[t.e0 + i];
   __syncthreads();
   const bool live = r < t.nr;
@@ -159,37 +119,37 @@ __global__ __launch_bounds__(ROWS * H / 4) void resgated_aggregate_kernel(RGFwdA
   const int64_t row = t.r0 + r;
   const int32_t* __restrict__ gcol = p.colidx + t.e0;
   const RGEdgeW<E> we = rg_load_we<E>(p.w_e, ed, H, sub);
-  const float4 k = live ? rld4(p.p + row * p.ldp + 4 * sub) : rzero4();
+  const float4 k = live ? load4(p.p + row * p.ldp + 4 * sub) : zero4();
   const unsigned ld4 = (unsigned)p.ldp * 4u, qoff = (unsigned)H * 4u + (unsigned)sub * 16u, voff = qoff + (unsigned)H * 4u;
   // the descriptor ends behind the last row's 3 H columns (nothing past them is addressed)
   const __amdgpu_buffer_rsrc_t pd = __builtin_amdgcn_make_buffer_rsrc(
       (void*)p.p, (short)0, (int)((unsigned)(p.n - 1) * ld4 + (unsigned)H * 12u), 0x00020000);
-  float4 acc = rzero4();
-  for (int e = ea; e < eb; e += kRU) {
-    float4 av[kRU], mv[kRU];
-    RGEdgeF<E> ev[kRU];
-    int64_t en[kRU];
-    bool ok[kRU];
+  float4 acc = zero4();
+  for (int e = ea; e < eb; e += kTileU) {
+    float4 av[kTileU], mv[kTileU];
+    EdgeF<E> ev[kTileU];
+    int64_t en[kTileU];
+    bool ok[kTileU];
 #pragma unroll
-    for (int u = 0; u < kRU; ++u) {
+    for (int u = 0; u < kTileU; ++u) {
       ok[u] = e + u < eb;
       const int ee = ok[u] ? e + u : e;
-      const int col = ee < kRCap ? s_col[ee] : gcol[ee];
-      av[u] = rbuf4(pd, ok[u] ? (unsigned)col * ld4 + qoff : kROut);
-      mv[u] = rbuf4(pd, ok[u] ? (unsigned)col * ld4 + voff : kROut);
+      const int col = ee < kTileCap ? s_col[ee] : gcol[ee];
+      av[u] = buf4(pd, ok[u] ? (unsigned)col * ld4 + qoff : kOffOut);
+      mv[u] = buf4(pd, ok[u] ? (unsigned)col * ld4 + voff : kOffOut);
       en[u] = (int64_t)t.e0 + ee;
     }
 #pragma unroll
-    for (int u = 0; u < kRU; ++u) av[u] = r4add(k, av[u]);
+    for (int u = 0; u < kTileU; ++u) av[u] = add4(k, av[u]);
     rg_edge(av, mv, ev, p.e, p.lde, en, ok, we, ed);
 #pragma unroll
-    for (int u = 0; u < kRU; ++u)
-      if (e + u < eb) acc = r4fma4(rg_sig(av[u]), mv[u], acc);     // CSR order
+    for (int u = 0; u < kTileU; ++u)
+      if (e + u < eb) acc = fma44(rg_sig(av[u]), mv[u], acc);     // CSR order
   }
   if (!live) return;
   float4 y = acc;                                        // a row without entries: S + bias
-  if (p.skip) y = r4add(rld4(p.skip + row * p.lds + 4 * sub), y);
-  if (p.bias) y = r4add(y, rld4(p.bias + 4 * sub));
+  if (p.skip) y = add4(load4(p.skip + row * p.lds + 4 * sub), y);
+  if (p.bias) y = add4(y, load4(p.bias + 4 * sub));
   *reinterpret_cast<float4*>(p.out + row * p.ldo + 4 * sub) = y;
 }
 
@@ -209,12 +169,12 @@ struct RGTargetArgs {
 template <int H, int ROWS, int E>
 __global__ __launch_bounds__(ROWS * H / 4) void resgated_bwd_targets_kernel(RGTargetArgs p) {
   constexpr int LPR = H / 4, NT = ROWS * LPR;
-  __shared__ int32_t s_col[kRCap];
-  __shared__ int32_t s_rp[kRRows + 1];
+  __shared__ int32_t s_col[kTileCap];
+  __shared__ int32_t s_rp[kTileRows + 1];
   __shared__ __attribute__((aligned(16))) float4 s_p[ROWS][LPR];
   const int tid = threadIdx.x, r = tid / LPR, sub = tid % LPR, ed = p.edge_dim;
-  const RGTile t = rg_tile(p.rowptr, p.n, s_rp, ROWS);
-  const int staged = min(t.e1 - t.e0, kRCap);
+  const ConvTile t = conv_tile(p.rowptr, p.n, s_rp, ROWS);
+  const int staged = min(t.e1 - t.e0, kTileCap);
   for (int i = tid; i < staged; i += NT) s_col[i] = p.colidx[t.e0 + i];
   __syncthreads();
   const bool live = r < t.nr;
@@ -222,42 +182,42 @@ __global__ __launch_bounds__(ROWS * H / 4) void resgated_bwd_targets_kernel(RGTa
   const int64_t row = t.r0 + r;
   const int32_t* __restrict__ gcol = p.colidx + t.e0;
   const RGEdgeW<E> we = rg_load_we<E>(p.w_e, ed, H, sub);
-  float4 dO = rzero4(), k = dO;
+  float4 dO = zero4(), k = dO;
   if (live) {
-    dO = rld4(p.d_out + row * p.ldd + 4 * sub);
-    k = rld4(p.p + row * p.ldp + 4 * sub);
+    dO = load4(p.d_out + row * p.ldd + 4 * sub);
+    k = load4(p.p + row * p.ldp + 4 * sub);
   }
   const unsigned ld4 = (unsigned)p.ldp * 4u, qoff = (unsigned)H * 4u + (unsigned)sub * 16u, voff = qoff + (unsigned)H * 4u;
   const __amdgpu_buffer_rsrc_t pd = __builtin_amdgcn_make_buffer_rsrc(
       (void*)p.p, (short)0, (int)((unsigned)(p.n - 1) * ld4 + (unsigned)H * 12u), 0x00020000);
-  float4 dk = rzero4();
+  float4 dk = zero4();
   RGEdgeW<E> dwe;
 #pragma unroll
-  for (int d = 0; d < (E > 0 ? E : 1); ++d) dwe.g[d] = dwe.v[d] = rzero4();
-  for (int e = ea; e < eb; e += kRU) {
-    float4 av[kRU], mv[kRU];
-    RGEdgeF<E> ev[kRU];
-    int64_t en[kRU];
-    bool ok[kRU];
+  for (int d = 0; d < (E > 0 ? E : 1); ++d) dwe.g[d] = dwe.v[d] = zero4();
+  for (int e = ea; e < eb; e += kTileU) {
+    float4 av[kTileU], mv[kTileU];
+    EdgeF<E> ev[kTileU];
+    int64_t en[kTileU];
+    bool ok[kTileU];
 #pragma unroll
-    for (int u = 0; u < kRU; ++u) {
+    for (int u = 0; u < kTileU; ++u) {
       ok[u] = e + u < eb;
       const int ee = ok[u] ? e + u : e;
-      const int col = ee < kRCap ? s_col[ee] : gcol[ee];
-      av[u] = rbuf4(pd, ok[u] ? (unsigned)col * ld4 + qoff : kROut);
-      mv[u] = rbuf4(pd, ok[u] ? (unsigned)col * ld4 + voff : kROut);
+      const int col = ee < kTileCap ? s_col[ee] : gcol[ee];
+      av[u] = buf4(pd, ok[u] ? (unsigned)col * ld4 + qoff : kOffOut);
+      mv[u] = buf4(pd, ok[u] ? (unsigned)col * ld4 + voff : kOffOut);
       en[u] = (int64_t)t.e0 + ee;
     }
 #pragma unroll
-    for (int u = 0; u < kRU; ++u) av[u] = r4add(k, av[u]);
+    for (int u = 0; u < kTileU; ++u) av[u] = add4(k, av[u]);
     rg_edge(av, mv, ev, p.e, p.lde, en, ok, we, ed);
 #pragma unroll
-    for (int u = 0; u < kRU; ++u) {
+    for (int u = 0; u < kTileU; ++u) {
       if (e + u < eb) {
         const float4 g = rg_sig(av[u]);
-        const float4 dm = r4mul(dO, g);
-        const float4 da = r4mul(r4mul(dO, mv[u]), rg_dsig(g));
-        dk = r4add(dk, da);                              // CSR order
+        const float4 dm = mul4(dO, g);
+        const float4 da = mul4(mul4(dO, mv[u]), rg_dsig(g));
+        dk = add4(dk, da);                              // CSR order
         rg_dwe_from<0, E>(dwe, ev[u], da, dm, ed);
       }
     }
@@ -276,9 +236,9 @@ __global__ __launch_bounds__(ROWS * H / 4) void resgated_bwd_targets_kernel(RGTa
         s_p[r][sub] = q < E ? dwe.g[d] : dwe.v[d];
         __syncthreads();
         if (tid < LPR) {
-          float4 s = rzero4();
+          float4 s = zero4();
 #pragma unroll 8
-          for (int i = 0; i < ROWS; ++i) s = r4add(s, s_p[i][tid]);
+          for (int i = 0; i < ROWS; ++i) s = add4(s, s_p[i][tid]);
           *reinterpret_cast<float4*>(part + ((q < E ? 0 : ed) + d) * H + 4 * tid) = s;
         }
         __syncthreads();
@@ -320,12 +280,12 @@ struct RGSourceArgs {
 template <int H, int ROWS, int E>
 __global__ __launch_bounds__(ROWS * H / 4) void resgated_bwd_sources_kernel(RGSourceArgs p) {
   constexpr int LPR = H / 4, NT = ROWS * LPR;
-  __shared__ int32_t s_col[kRCap];
-  __shared__ int32_t s_q[kRCap];
-  __shared__ int32_t s_rp[kRRows + 1];
+  __shared__ int32_t s_col[kTileCap];
+  __shared__ int32_t s_q[kTileCap];
+  __shared__ int32_t s_rp[kTileRows + 1];
   const int tid = threadIdx.x, r = tid / LPR, sub = tid % LPR, ed = p.edge_dim;
-  const RGTile t = rg_tile(p.rowptr, p.n, s_rp, ROWS);
-  const int staged = min(t.e1 - t.e0, kRCap);
+  const ConvTile t = conv_tile(p.rowptr, p.n, s_rp, ROWS);
+  const int staged = min(t.e1 - t.e0, kTileCap);
   for (int i = tid; i < staged; i += NT) {
     s_col[i] = p.colidx[t.e0 + i];
     s_q[i] = p.perm[t.e0 + i];
@@ -335,10 +295,10 @@ __global__ __launch_bounds__(ROWS * H / 4) void resgated_bwd_sources_kernel(RGSo
   const int ea = live ? s_rp[r] - t.e0 : 0, eb = live ? s_rp[r + 1] - t.e0 : 0;
   const int64_t row = t.r0 + r;
   const RGEdgeW<E> we = rg_load_we<E>(p.w_e, ed, H, sub);
-  float4 q = rzero4(), v = q;
+  float4 q = zero4(), v = q;
   if (live) {
-    q = rld4(p.p + row * p.ldp + H + 4 * sub);
-    v = rld4(p.p + row * p.ldp + 2 * H + 4 * sub);
+    q = load4(p.p + row * p.ldp + H + 4 * sub);
+    v = load4(p.p + row * p.ldp + 2 * H + 4 * sub);
   }
   const unsigned ldd4 = (unsigned)p.ldd * 4u, ldp4 = (unsigned)p.ldp * 4u, sub16 = (unsigned)sub * 16u;
   const __amdgpu_buffer_rsrc_t dd = __builtin_amdgcn_make_buffer_rsrc(
@@ -348,34 +308,34 @@ __global__ __launch_bounds__(ROWS * H / 4) void resgated_bwd_sources_kernel(RGSo
       (void*)p.p, (short)0, (int)((unsigned)(p.n - 1) * ldp4 + (unsigned)H * 4u), 0x00020000);
   const int32_t* __restrict__ gcol = p.colidx + t.e0;
   const int32_t* __restrict__ gq = p.perm + t.e0;
-  float4 dq = rzero4(), dv = dq;
-  for (int e = ea; e < eb; e += kRU) {
-    float4 dov[kRU], av[kRU], mv[kRU];
-    RGEdgeF<E> ev[kRU];
-    int64_t en[kRU];
-    bool ok[kRU];
+  float4 dq = zero4(), dv = dq;
+  for (int e = ea; e < eb; e += kTileU) {
+    float4 dov[kTileU], av[kTileU], mv[kTileU];
+    EdgeF<E> ev[kTileU];
+    int64_t en[kTileU];
+    bool ok[kTileU];
 #pragma unroll
-    for (int u = 0; u < kRU; ++u) {
+    for (int u = 0; u < kTileU; ++u) {
       ok[u] = e + u < eb;
       const int ee = ok[u] ? e + u : e;
-      const bool st = ee < kRCap;
+      const bool st = ee < kTileCap;
       const int col = st ? s_col[ee] : gcol[ee];
       en[u] = st ? s_q[ee] : gq[ee];
-      dov[u] = rbuf4(dd, ok[u] ? (unsigned)col * ldd4 + sub16 : kROut);
-      av[u] = rbuf4(kd, ok[u] ? (unsigned)col * ldp4 + sub16 : kROut);
+      dov[u] = buf4(dd, ok[u] ? (unsigned)col * ldd4 + sub16 : kOffOut);
+      av[u] = buf4(kd, ok[u] ? (unsigned)col * ldp4 + sub16 : kOffOut);
     }
 #pragma unroll
-    for (int u = 0; u < kRU; ++u) {
-      av[u] = r4add(av[u], q);
+    for (int u = 0; u < kTileU; ++u) {
+      av[u] = add4(av[u], q);
       mv[u] = v;
     }
     rg_edge(av, mv, ev, p.e, p.lde, en, ok, we, ed);
 #pragma unroll
-    for (int u = 0; u < kRU; ++u) {
+    for (int u = 0; u < kTileU; ++u) {
       if (e + u < eb) {
         const float4 g = rg_sig(av[u]);
-        dv = r4fma4(dov[u], g, dv);                      // the transposed CSR's order
-        dq = r4fma4(r4mul(dov[u], mv[u]), rg_dsig(g), dq);
+        dv = fma44(dov[u], g, dv);                      // the transposed CSR's order
+        dq = fma44(mul4(dov[u], mv[u]), rg_dsig(g), dq);
       }
     }
   }
@@ -387,25 +347,11 @@ __global__ __launch_bounds__(ROWS * H / 4) void resgated_bwd_sources_kernel(RGSo
 
 bool rg_shape_ok(int64_t n, int32_t h, int64_t ldp, int32_t edge_dim) {
   if (n < 0 || n > 0x7FFFFFFF || !(h == 16 || h == 32 || h == 64 || h == 128)) return false;
-  if (edge_dim < 0 || edge_dim > kREdgeMax) return false;
+  if (edge_dim < 0 || edge_dim > kEdgeMax) return false;
   return ldp >= 3 * (int64_t)h && ldp % 4 == 0 && (uint64_t)n * (uint64_t)ldp * 4u < 0x100000000ull;
 }
-// rows per workgroup: 16 at H = 128, where 32 rows are 1024 threads with 128 registers each and the two blocks of W_e, their
-// gradients and a trip's operands do not fit; 512 threads may hold 256
-int rg_rows(int h) { return h == 128 ? 16 : kRRows; }
-bool rg_ld_ok(int64_t ld, int w) { return ld >= w && ld % 4 == 0 && ld < (1ll << 30); }
 
 const char* kRGShapes = "needs h in {16, 32, 64, 128}, ldp >= 3 h in multiples of 4 floats, n * ldp * 4 < 2^32 and 0 <= edge_dim <= 8";
-
-// the kernels are built for 0, up to 2 and up to 8 edge features: the blocks of W_e (and their gradients) hold that many
-// float4 per lane, and registers decide how many workgroups a CU keeps in flight
-#define GCNX_RG_DISPATCH_E(ed, H_, R_, LAUNCH) \
-  do { if ((ed) == 0) { LAUNCH(H_, R_, 0); } else if ((ed) <= 2) { LAUNCH(H_, R_, 2); } else { LAUNCH(H_, R_, 8); } } while (0)
-#define GCNX_RG_DISPATCH(h, ed, LAUNCH)                                                        \
-  do {                                                                                         \
-    if ((h) == 128) GCNX_RG_DISPATCH_E(ed, 128, 16, LAUNCH); else if ((h) == 64) GCNX_RG_DISPATCH_E(ed, 64, 32, LAUNCH); \
-    else if ((h) == 32) GCNX_RG_DISPATCH_E(ed, 32, 32, LAUNCH); else GCNX_RG_DISPATCH_E(ed, 16, 32, LAUNCH);             \
-  } while (0)
 
 }  // namespace
 
@@ -417,7 +363,7 @@ int gcnx_resgated_bwd_scratch_floats(int64_t n, int32_t h, int32_t edge_dim, int
   if (!out) return gcnx_fail(nullptr, GCNX_ERR_INVALID, "gcnx_resgated_bwd_scratch_floats: out is NULL");
   if (n < 0 || h <= 0 || edge_dim < 0)
     return gcnx_fail(nullptr, GCNX_ERR_INVALID, "gcnx_resgated_bwd_scratch_floats: needs n >= 0, h > 0 and edge_dim >= 0");
-  *out = (int64_t)gcnx_cdiv(n, rg_rows(h)) * 2 * edge_dim * h;
+  *out = (int64_t)gcnx_cdiv(n, conv_tile_rows(h)) * 2 * edge_dim * h;
   return GCNX_OK;
 }
 
@@ -431,7 +377,7 @@ int gcnx_resgated_aggregate(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t*
     return gcnx_fail(ctx, GCNX_ERR_UNSUPPORTED, "gcnx_resgated_aggregate: %s (got n=%d h=%d ldp=%lld edge_dim=%d)", kRGShapes, n, h,
                      (long long)ldp, edge_dim);
   if (!gcnx_aligned16(p) || !gcnx_aligned16(w_e) || !gcnx_aligned16(skip) || !gcnx_aligned16(bias) || !gcnx_aligned16(out) ||
-      !rg_ld_ok(ldo, h) || (skip && !rg_ld_ok(lds, h)))
+      !conv_ld_ok(ldo, h) || (skip && !conv_ld_ok(lds, h)))
     return gcnx_fail(ctx, GCNX_ERR_UNSUPPORTED, "gcnx_resgated_aggregate: p, w_e, skip, bias and out must be 16-byte aligned, with ldo "
                      "and lds >= h in multiples of 4 floats");
   if (n == 0) return GCNX_OK;
@@ -441,9 +387,9 @@ int gcnx_resgated_aggregate(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t*
   RGFwdArgs a{};
   a.rowptr = rowptr; a.colidx = colidx; a.p = p; a.ldp = ldp; a.n = n; a.edge_dim = edge_dim; a.e = e; a.lde = lde; a.w_e = w_e;
   a.skip = skip; a.lds = lds; a.bias = bias; a.out = out; a.ldo = ldo;
-  const int tiles = gcnx_cdiv(n, rg_rows(h));
+  const int tiles = gcnx_cdiv(n, conv_tile_rows(h));
 #define GCNX_RG_AGG(H_, R_, E_) hipLaunchKernelGGL((resgated_aggregate_kernel<H_, R_, E_>), dim3(tiles), dim3(R_ * H_ / 4), 0, ctx->stream, a)
-  GCNX_RG_DISPATCH(h, edge_dim, GCNX_RG_AGG);
+  GCNX_CONV_DISPATCH(h, edge_dim, GCNX_RG_AGG);
 #undef GCNX_RG_AGG
   GCNX_LAUNCH_OK(ctx);
   return GCNX_OK;
@@ -459,7 +405,7 @@ int gcnx_resgated_bwd_targets(gcnx_ctx* ctx, const int32_t* rowptr, const int32_
     return gcnx_fail(ctx, GCNX_ERR_UNSUPPORTED, "gcnx_resgated_bwd_targets: %s (got n=%d h=%d ldp=%lld edge_dim=%d)", kRGShapes, n, h,
                      (long long)ldp, edge_dim);
   if (!gcnx_aligned16(p) || !gcnx_aligned16(w_e) || !gcnx_aligned16(d_out) || !gcnx_aligned16(dk) || !gcnx_aligned16(ds) ||
-      !gcnx_aligned16(dw_e) || !gcnx_aligned16(scratch) || !rg_ld_ok(ldd, h) || !rg_ld_ok(ldg, h) || (ds && !rg_ld_ok(ldgs, h)))
+      !gcnx_aligned16(dw_e) || !gcnx_aligned16(scratch) || !conv_ld_ok(ldd, h) || !conv_ld_ok(ldg, h) || (ds && !conv_ld_ok(ldgs, h)))
     return gcnx_fail(ctx, GCNX_ERR_UNSUPPORTED, "gcnx_resgated_bwd_targets: p, w_e, d_out, dk, ds, dw_e and scratch must be 16-byte "
                      "aligned, with ldd, ldg and ldgs >= h in multiples of 4 floats");
   if (n == 0) return GCNX_OK;
@@ -471,9 +417,9 @@ int gcnx_resgated_bwd_targets(gcnx_ctx* ctx, const int32_t* rowptr, const int32_
   RGTargetArgs a{};
   a.rowptr = rowptr; a.colidx = colidx; a.p = p; a.ldp = ldp; a.n = n; a.edge_dim = edge_dim; a.e = e; a.lde = lde; a.w_e = w_e;
   a.d_out = d_out; a.ldd = ldd; a.dk = dk; a.ldg = ldg; a.ds = ds; a.ldgs = ldgs; a.part = scratch;
-  const int tiles = gcnx_cdiv(n, rg_rows(h));
+  const int tiles = gcnx_cdiv(n, conv_tile_rows(h));
 #define GCNX_RG_BT(H_, R_, E_) hipLaunchKernelGGL((resgated_bwd_targets_kernel<H_, R_, E_>), dim3(tiles), dim3(R_ * H_ / 4), 0, ctx->stream, a)
-  GCNX_RG_DISPATCH(h, edge_dim, GCNX_RG_BT);
+  GCNX_CONV_DISPATCH(h, edge_dim, GCNX_RG_BT);
 #undef GCNX_RG_BT
   GCNX_LAUNCH_OK(ctx);
   if (edge_dim > 0) {
@@ -493,8 +439,8 @@ int gcnx_resgated_bwd_sources(gcnx_ctx* ctx, const int32_t* rowptr_t, const int3
   if (!rg_shape_ok(n, h, ldp, edge_dim))
     return gcnx_fail(ctx, GCNX_ERR_UNSUPPORTED, "gcnx_resgated_bwd_sources: %s (got n=%d h=%d ldp=%lld edge_dim=%d)", kRGShapes, n, h,
                      (long long)ldp, edge_dim);
-  if (!gcnx_aligned16(p) || !gcnx_aligned16(w_e) || !gcnx_aligned16(d_out) || !gcnx_aligned16(dqv) || !rg_ld_ok(ldd, h) ||
-      !rg_ld_ok(ldg, 2 * h) || !gcnx_fits_buffer(n, ldd, 4))
+  if (!gcnx_aligned16(p) || !gcnx_aligned16(w_e) || !gcnx_aligned16(d_out) || !gcnx_aligned16(dqv) || !conv_ld_ok(ldd, h) ||
+      !conv_ld_ok(ldg, 2 * h) || !gcnx_fits_buffer(n, ldd, 4))
     return gcnx_fail(ctx, GCNX_ERR_UNSUPPORTED, "gcnx_resgated_bwd_sources: p, w_e, d_out and dqv must be 16-byte aligned, with ldd >= h "
                      "and ldg >= 2 h in multiples of 4 floats and n * ldd * 4 < 2^32");
   if (n == 0) return GCNX_OK;
@@ -504,9 +450,9 @@ int gcnx_resgated_bwd_sources(gcnx_ctx* ctx, const int32_t* rowptr_t, const int3
   RGSourceArgs a{};
   a.rowptr = rowptr_t; a.colidx = colidx_t; a.perm = perm_t; a.p = p; a.ldp = ldp; a.n = n; a.edge_dim = edge_dim; a.e = e; a.lde = lde;
   a.w_e = w_e; a.d_out = d_out; a.ldd = ldd; a.dqv = dqv; a.ldg = ldg;
-  const int tiles = gcnx_cdiv(n, rg_rows(h));
+  const int tiles = gcnx_cdiv(n, conv_tile_rows(h));
 #define GCNX_RG_BS(H_, R_, E_) hipLaunchKernelGGL((resgated_bwd_sources_kernel<H_, R_, E_>), dim3(tiles), dim3(R_ * H_ / 4), 0, ctx->stream, a)
-  GCNX_RG_DISPATCH(h, edge_dim, GCNX_RG_BS);
+  GCNX_CONV_DISPATCH(h, edge_dim, GCNX_RG_BS);
 #undef GCNX_RG_BS
   GCNX_LAUNCH_OK(ctx);
   return GCNX_OK;

@@ -5,8 +5,8 @@
 //
 // composed from existing calls this is gcnx_spmm_csr, two gcnx_gemm and a gcnx_add, with three [N, F] intermediates written
 // and read back -- at N = 600 ... 20 000 each of them is a launch latency, not a throughput.  As one product over a doubled
-// K a workgroup owns 32 rows end to end, like gcn_conv_fused_kernel (fused.hip; its device helpers are copied here, not
-// shared: that file's bit-exactness tests are yardsticks and a common header would rebuild it):
+// K a workgroup owns 32 rows end to end, like gcn_conv_fused_kernel (fused.hip, which keeps its own copies of the device helpers:
+// that file is on the benchmark's path; what the conv families share is conv_tile.h):
 //     gather + weight the neighbours' rows of x -> S tile [32, K] in LDS |  the tile's own rows of x -> X tile [32, K] in LDS
 //     -> MFMA of S with W_nb, then of X with W_root into the same accumulators -> bias -> out
 // The backward with respect to x is the same launch on the transposed operator with the weights read as stored:
@@ -28,14 +28,11 @@
 //   epilogue in registers: bias, stores of 4 rows x 64 bytes per instruction; no barrier behind the last MFMA.
 // LDS: two tiles of 32 x (K + 4) floats + 8 KiB of entries -- 41.4 KiB at K = 128, three workgroups per CU.
 #include "common.h"
+#include "conv_tile.h"
 
 namespace {
 
-typedef float s32x4v __attribute__((ext_vector_type(4)));
 typedef float s32x2 __attribute__((ext_vector_type(2)));
-
-constexpr int kSRows = 32;        // rows per workgroup
-constexpr int kSCap = 1024;       // CSR entries of a tile staged in LDS (the rest is read from global memory)
 
 struct SageArgs {
   const int32_t* rowptr; const int32_t* colidx; const float* vals;
@@ -48,10 +45,7 @@ struct SageArgs {
   float* out; int64_t ldo;
 };
 
-__device__ __forceinline__ float4 sbuf4(__amdgpu_buffer_rsrc_t rs, unsigned off) {
-  const s32x4v r = __builtin_bit_cast(s32x4v, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0));
-  return make_float4(r.x, r.y, r.z, r.w);
-}
+// (not conv_tile.h's fma4: two packed fmas)
 __device__ __forceinline__ float4 s4fma(float v, float4 h, float4 a) {
   const s32x2 w = {v, v};
   const s32x2 lo = __builtin_elementwise_fma(w, s32x2{h.x, h.y}, s32x2{a.x, a.y});
@@ -64,25 +58,25 @@ __global__ __launch_bounds__(512, 6) void sage_conv_kernel(SageArgs p) {
   constexpr int LPR = K / 4;                 // lanes per gathered row
   constexpr int GW = 64 / LPR < 4 ? 64 / LPR : 4;   // row groups per wave that hold rows (the lanes behind them idle in the gather)
   constexpr int NG = 8 * GW;                 // row groups per workgroup
-  constexpr int RPG = kSRows / NG;           // rows per group (2 at K = 128)
+  constexpr int RPG = kTileRows / NG;        // rows per group (2 at K = 128)
   constexpr int U = 4;                       // entries per row per trip
   constexpr int SL = 2 * U;                  // slack entries behind the staged ones
-  constexpr int NQ = (kSRows * LPR + 511) / 512;   // 16-byte pieces of the tile's own rows per thread (2 at K = 128)
+  constexpr int NQ = (kTileRows * LPR + 511) / 512;   // 16-byte pieces of the tile's own rows per thread (2 at K = 128)
   static_assert(K == 16 || K == 32 || K == 64 || K == 128, "gather width");
-  static_assert(NG * RPG == kSRows, "every row of the tile has a lane group");
-  __shared__ __attribute__((aligned(16))) float tile_s[kSRows][K + 4];   // row stride K + 4: see the A-operand read
-  __shared__ __attribute__((aligned(16))) float tile_x[kSRows][K + 4];
+  static_assert(NG * RPG == kTileRows, "every row of the tile has a lane group");
+  __shared__ __attribute__((aligned(16))) float tile_s[kTileRows][K + 4];   // row stride K + 4: see the A-operand read
+  __shared__ __attribute__((aligned(16))) float tile_x[kTileRows][K + 4];
   // staged CSR entries: {byte offset of the gathered row = column * ldx * 4, weight}; the slack entries carry weight 0
-  __shared__ __attribute__((aligned(8))) int2 s_ent[kSCap + SL];
-  __shared__ int32_t s_rp[kSRows + 1];
+  __shared__ __attribute__((aligned(8))) int2 s_ent[kTileCap + SL];
+  __shared__ int32_t s_rp[kTileRows + 1];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int ntiles = gridDim.x;
   const int t = gcnx_xcd_remap(blockIdx.x, ntiles);
-  const int r0 = t * kSRows, nr = min(p.n - r0, kSRows);
+  const int r0 = t * kTileRows, nr = min(p.n - r0, kTileRows);
   if (tid <= nr) s_rp[tid] = p.rowptr[r0 + tid];
   const int e0 = p.rowptr[r0], e1 = p.rowptr[r0 + nr];
-  const int staged = min(e1 - e0, kSCap);
+  const int staged = min(e1 - e0, kTileCap);
   const unsigned ld4 = (unsigned)p.ldx * 4u;             // bytes per row of x
   for (int i = tid; i < staged + SL; i += 512) {
     int2 en = make_int2(0, 0);
@@ -118,8 +112,8 @@ __global__ __launch_bounds__(512, 6) void sage_conv_kernel(SageArgs p) {
     const bool live = has_rows && r < nr;
     ea[j] = live ? s_rp[r] - e0 : 0;
     eb[j] = live ? s_rp[r + 1] - e0 : 0;
-    ebf[j] = min(eb[j], kSCap);                      // the staged part of the row ...
-    ea[j] = min(ea[j], kSCap);                       // ... (empty if the row starts past it)
+    ebf[j] = min(eb[j], kTileCap);                   // the staged part of the row ...
+    ea[j] = min(ea[j], kTileCap);                    // ... (empty if the row starts past it)
     len = max(len, ebf[j] - ea[j]);
   }
   const unsigned sub16 = (unsigned)sub * 16u;
@@ -137,7 +131,7 @@ __global__ __launch_bounds__(512, 6) void sage_conv_kernel(SageArgs p) {
         const int e = eb_ + u;
         const int2 en = s_ent[e];
         wv[j][u] = __int_as_float(en.y);
-        hv[j][u] = sbuf4(xr, e < ebf[j] ? (unsigned)en.x + sub16 : 0xFFFFFFF0u);
+        hv[j][u] = buf4(xr, e < ebf[j] ? (unsigned)en.x + sub16 : kOffOut);
       }
     }
     __builtin_amdgcn_sched_barrier(0);                 // all loads of the trip go out before the first is consumed
@@ -146,12 +140,12 @@ __global__ __launch_bounds__(512, 6) void sage_conv_kernel(SageArgs p) {
 #pragma unroll
       for (int u = 0; u < U; ++u) acc[j] = s4fma(wv[j][u], hv[j][u], acc[j]);
   }
-  if (e1 - e0 > kSCap) {       // uniform per workgroup, rare: entries beyond the staged ones, one at a time from global memory
+  if (e1 - e0 > kTileCap) {       // uniform per workgroup, rare: entries beyond the staged ones, one at a time from global memory
 #pragma unroll
     for (int j = 0; j < RPG; ++j)
-      for (int e = max(eb[j] > 0 ? s_rp[gid + j * NG] - e0 : 0, kSCap); e < eb[j]; ++e) {   // (ea is clamped: the row's true start)
+      for (int e = max(eb[j] > 0 ? s_rp[gid + j * NG] - e0 : 0, kTileCap); e < eb[j]; ++e) {   // (ea is clamped: the row's true start)
         const float v = WEIGHTED ? p.vals[e0 + e] : 1.0f;
-        acc[j] = s4fma(v, sbuf4(xr, (unsigned)p.colidx[e0 + e] * ld4 + sub16), acc[j]);
+        acc[j] = s4fma(v, buf4(xr, (unsigned)p.colidx[e0 + e] * ld4 + sub16), acc[j]);
       }
   }
   // ---- this wave's slice of W_nb, in the MFMA B layout; in flight while the tiles are written ------------------------
@@ -177,14 +171,14 @@ __global__ __launch_bounds__(512, 6) void sage_conv_kernel(SageArgs p) {
 #pragma unroll
   for (int q = 0; q < NQ; ++q) {
     const int i = tid + 512 * q, row = i / LPR, c4 = i - row * LPR;
-    if (row < kSRows) *reinterpret_cast<float4*>(&tile_x[row][4 * c4]) = own[q];
+    if (row < kTileRows) *reinterpret_cast<float4*>(&tile_x[row][4 * c4]) = own[q];
   }
   __syncthreads();
   // ---- product and epilogue, in registers: wave w owns output columns [16w, 16w + 16) of all 32 rows ------------------
   // C layout of the 16 x 16 tile: column = lane & 15, rows 4 (lane >> 4) + reg.
   if (!wave_on) return;
   const float bcol = p.bias ? p.bias[col] : 0.f;
-  s32x4v c0 = {0.f, 0.f, 0.f, 0.f}, c1 = c0;
+  gcnx_f32x4 c0 = {0.f, 0.f, 0.f, 0.f}, c1 = c0;
 #pragma unroll
   for (int kk = 0; kk < K / 4; ++kk) {
     const float a0 = tile_s[c16][4 * kk + kq];
@@ -214,7 +208,7 @@ bool sage_shape_ok(int64_t n, int32_t k, int32_t nc, int64_t ldx) {
 }
 
 int launch_sage(gcnx_ctx* ctx, const SageArgs& a, int k) {
-  const int tiles = gcnx_cdiv(a.n, kSRows);
+  const int tiles = gcnx_cdiv(a.n, kTileRows);
 #define GCNX_SAGE_LAUNCH(K_)                                                                                       \
   do {                                                                                                             \
     if (a.vals) hipLaunchKernelGGL((sage_conv_kernel<K_, true>), dim3(tiles), dim3(512), 0, ctx->stream, a);        \

@@ -17,9 +17,9 @@
 // resgated.hip: exp(-a) = +inf gives 0, exp(-a) = 0 gives 1, b (1 - b) is finite for every finite a.
 // fp32 throughout, no float atomics, every sum in a fixed order: the same call leaves the same bits.
 //
-// Shape of a workgroup (gatv2.hip's and resgated.hip's; the device helpers are copied, not shared: those files' bit-exactness
-// tests are yardsticks and a common header would rebuild them): 32 rows, one lane group of HC / 4 lanes per row with one
-// float4 of the row each -- 8 HC threads (HC = 128: 16 rows, see tf_rows).  Head h owns the c / 4 consecutive lanes
+// Shape of a workgroup (gatv2.hip's and resgated.hip's; the device helpers they share: conv_tile.h): 32 rows, one lane group
+// of HC / 4 lanes per row with one float4 of the row each -- 8 HC threads (HC = 128: 16 rows, see conv_tile_rows: W_e with a
+// trip's three float4 per entry does not fit beside 32 rows at E = 8).  Head h owns the c / 4 consecutive lanes
 // [h c / 4, (h + 1) c / 4) of a group, always inside one wave: per-head dots are xor butterflies over those lanes, the beta
 // gate's row dot the same butterfly over the whole group.  The tile's CSR entries are staged in LDS (1024 of them; a tile
 // with more reads the rest from global memory).  K[j] | V[j] are adjacent in P: one entry costs one contiguous 2 HC piece of
@@ -33,44 +33,14 @@
 #include <cmath>
 
 #include "common.h"
+#include "conv_tile.h"
 
 namespace {
 
-typedef float tff32x4v __attribute__((ext_vector_type(4)));
-
-constexpr int kTRows = 32;        // rows per workgroup (HC = 128: 16)
-constexpr int kTCap = 1024;       // CSR entries of a tile staged in LDS (the rest is read from global memory)
-constexpr int kTU = 4;            // entries per row per trip
-constexpr int kTEdgeMax = 8;      // edge features served
-constexpr unsigned kTOut = 0xFFFFFFF0u;   // an offset no descriptor holds
-
-__device__ __forceinline__ float4 tbuf4(__amdgpu_buffer_rsrc_t rs, unsigned off) {
-  const tff32x4v r = __builtin_bit_cast(tff32x4v, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0));
-  return make_float4(r.x, r.y, r.z, r.w);
-}
-__device__ __forceinline__ float4 t4fma(float v, float4 h, float4 a) {
-  return make_float4(fmaf(v, h.x, a.x), fmaf(v, h.y, a.y), fmaf(v, h.z, a.z), fmaf(v, h.w, a.w));
-}
-__device__ __forceinline__ float4 t4scale(float v, float4 a) { return make_float4(v * a.x, v * a.y, v * a.z, v * a.w); }
-__device__ __forceinline__ float4 t4add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-__device__ __forceinline__ float4 t4sub(float4 a, float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
-__device__ __forceinline__ float tdot4(float4 a, float4 b) { return fmaf(a.w, b.w, fmaf(a.z, b.z, fmaf(a.y, b.y, a.x * b.x))); }
-__device__ __forceinline__ float4 tld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ float4 tzero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-// sigmoid(a) for every finite a: exp(-a) = +inf gives 1 / inf = 0, exp(-a) = 0 gives 1
-__device__ __forceinline__ float tf_sig(float a) { return __builtin_amdgcn_rcpf(1.0f + __expf(-a)); }
 // over lph (a power of two <= 32) consecutive lanes: every lane gets the same bits (the partner lane^off comes from a swizzle
 // with a constant mask -- off = 16, 8, 4 -- or a quad permutation -- off = 2, 1).  No branches on lph: a step wider than the
 // group multiplies its partner by 0 (the 0 / 1 factors are formed once per kernel; five tests of lph kept as lane masks
 // through the entry loop cost the scalar registers that spilled).
-template <int OFF>
-__device__ __forceinline__ float tswz_xor(float v) {
-  return __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v), (OFF << 10) | 0x1F));
-}
-template <int CTRL>
-__device__ __forceinline__ float tquad(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
 struct TGroup { float m16, m8, m4, m2, m1; };
 __device__ __forceinline__ TGroup tgroup(int lph) {
   TGroup g;
@@ -79,49 +49,37 @@ __device__ __forceinline__ TGroup tgroup(int lph) {
   return g;
 }
 __device__ __forceinline__ float tgroup_sum(float v, const TGroup& g) {
-  v = fmaf(g.m16, tswz_xor<16>(v), v);
-  v = fmaf(g.m8, tswz_xor<8>(v), v);
-  v = fmaf(g.m4, tswz_xor<4>(v), v);
-  v = fmaf(g.m2, tquad<0x4E>(v), v);                     // lanes [2, 3, 0, 1] of every quad
-  v = fmaf(g.m1, tquad<0xB1>(v), v);                     // lanes [1, 0, 3, 2]
+  v = fmaf(g.m16, swz_xor<16>(v), v);
+  v = fmaf(g.m8, swz_xor<8>(v), v);
+  v = fmaf(g.m4, swz_xor<4>(v), v);
+  v = fmaf(g.m2, quad_perm<0x4E>(v), v);                     // lanes [2, 3, 0, 1] of every quad
+  v = fmaf(g.m1, quad_perm<0xB1>(v), v);                     // lanes [1, 0, 3, 2]
   return v;
 }
 
-// W_e [edge_dim, HC]: this lane's float4 of every row, rows >= edge_dim zero and never used
-template <int E> struct TEdgeW { float4 w[E > 0 ? E : 1]; };
-template <int E>
-__device__ __forceinline__ TEdgeW<E> tf_load_we(const float* __restrict__ w_e, int edge_dim, int hc, int sub) {
-  TEdgeW<E> r;
-  r.w[0] = tzero4();
-#pragma unroll
-  for (int d = 0; d < E; ++d) r.w[d] = d < edge_dim ? tld4(w_e + (int64_t)d * hc + 4 * sub) : tzero4();
-  return r;
-}
-// one entry's edge features (uniform over the lane group)
-template <int E> struct TEdgeF { float v[E > 0 ? E : 1]; };
 // t = e W_e of the U entries of a trip, d ascending.  Feature d is loaded and used inside the (uniform) test of feature
 // d - 1, so a trip costs edge_dim + 1 branches and every register index is a constant.  No mask: the slots past a row's end
 // name the trip's first entry again (a valid address; what they compute is weighted with 0 or never stored).
 // The features stay in r for the kernel that needs them again (dw_e).
 template <int Dd, int E, int U>
-__device__ __forceinline__ void tf_edge_from(float4 (&t)[U], TEdgeF<E> (&r)[U], const float* __restrict__ e, int64_t lde,
-                                             const int64_t (&entry)[U], const TEdgeW<E>& w, int edge_dim) {
+__device__ __forceinline__ void tf_edge_from(float4 (&t)[U], EdgeF<E> (&r)[U], const float* __restrict__ e, int64_t lde,
+                                             const int64_t (&entry)[U], const EdgeW<E>& w, int edge_dim) {
   if constexpr (Dd < E) {
     if (Dd < edge_dim) {
 #pragma unroll
       for (int u = 0; u < U; ++u) r[u].v[Dd] = e[entry[u] * lde + Dd];
 #pragma unroll
-      for (int u = 0; u < U; ++u) t[u] = t4fma(r[u].v[Dd], w.w[Dd], t[u]);
+      for (int u = 0; u < U; ++u) t[u] = fma4(r[u].v[Dd], w.w[Dd], t[u]);
       tf_edge_from<Dd + 1, E, U>(t, r, e, lde, entry, w, edge_dim);
     }
   }
 }
 template <int E, int U>
-__device__ __forceinline__ void tf_edge(float4 (&t)[U], TEdgeF<E> (&r)[U], const float* __restrict__ e, int64_t lde,
-                                        const int64_t (&entry)[U], const TEdgeW<E>& w, int edge_dim) {
+__device__ __forceinline__ void tf_edge(float4 (&t)[U], EdgeF<E> (&r)[U], const float* __restrict__ e, int64_t lde,
+                                        const int64_t (&entry)[U], const EdgeW<E>& w, int edge_dim) {
 #pragma unroll
   for (int u = 0; u < U; ++u) {
-    t[u] = tzero4();
+    t[u] = zero4();
 #pragma unroll
     for (int d = 0; d < (E > 0 ? E : 1); ++d) r[u].v[d] = 0.f;
   }
@@ -130,7 +88,7 @@ __device__ __forceinline__ void tf_edge(float4 (&t)[U], TEdgeF<E> (&r)[U], const
 // A[d] += e[d] dscore, B[d] += e[d] alpha of one entry (nested the same way)
 template <int E> struct TEdgeS { float a[E > 0 ? E : 1]; float b[E > 0 ? E : 1]; };
 template <int Dd, int E>
-__device__ __forceinline__ void tf_ab_from(TEdgeS<E>& s, const TEdgeF<E>& e, float dsc, float al, int edge_dim) {
+__device__ __forceinline__ void tf_ab_from(TEdgeS<E>& s, const EdgeF<E>& e, float dsc, float al, int edge_dim) {
   if constexpr (Dd < E) {
     if (Dd < edge_dim) {
       s.a[Dd] = fmaf(e.v[Dd], dsc, s.a[Dd]);
@@ -138,20 +96,6 @@ __device__ __forceinline__ void tf_ab_from(TEdgeS<E>& s, const TEdgeF<E>& e, flo
       tf_ab_from<Dd + 1, E>(s, e, dsc, al, edge_dim);
     }
   }
-}
-
-// ---- what every tile kernel starts with: its rows, their entry range ----------------------------------------------------
-struct TFTile {
-  int r0, nr, e0, e1;
-};
-__device__ __forceinline__ TFTile tf_tile(const int32_t* __restrict__ rowptr, int32_t n, int32_t* s_rp, int rows) {
-  TFTile t;
-  t.r0 = gcnx_xcd_remap(blockIdx.x, gridDim.x) * rows;
-  t.nr = min(n - t.r0, rows);
-  if ((int)threadIdx.x <= t.nr) s_rp[threadIdx.x] = rowptr[t.r0 + threadIdx.x];
-  t.e0 = rowptr[t.r0];
-  t.e1 = rowptr[t.r0 + t.nr];
-  return t;
 }
 
 struct TFFwdArgs {
@@ -172,13 +116,13 @@ struct TFFwdArgs {
 template <int HC, int ROWS, int E>
 __global__ __launch_bounds__(ROWS * HC / 4) void transformer_aggregate_kernel(TFFwdArgs p) {
   constexpr int LPR = HC / 4, NT = ROWS * LPR;
-  extern __shared__ float s_sc[];                        // with alpha: the staged entries' scores, kTCap * heads floats
-  __shared__ int32_t s_col[kTCap];
-  __shared__ int32_t s_rp[kTRows + 1];
+  extern __shared__ float s_sc[];                        // with alpha: the staged entries' scores, kTileCap * heads floats
+  __shared__ int32_t s_col[kTileCap];
+  __shared__ int32_t s_rp[kTileRows + 1];
   const int tid = threadIdx.x, r = tid / LPR, sub = tid % LPR;
   const int heads = p.heads, lph = p.lph, h = sub / lph, k = sub % lph, ed = p.edge_dim;
-  const TFTile t = tf_tile(p.rowptr, p.n, s_rp, ROWS);
-  const int staged = min(t.e1 - t.e0, kTCap);
+  const ConvTile t = conv_tile(p.rowptr, p.n, s_rp, ROWS);
+  const int staged = min(t.e1 - t.e0, kTileCap);
   for (int i = tid; i < staged; i += NT) s_col[i] = p.colidx[t.e0 + i];
   __syncthreads();
   const bool live = r < t.nr;
@@ -187,52 +131,52 @@ __global__ __launch_bounds__(ROWS * HC / 4) void transformer_aggregate_kernel(TF
   const float scale = p.scale;
   const TGroup gh = tgroup(lph);
   const int32_t* __restrict__ gcol = p.colidx + t.e0;
-  const TEdgeW<E> we = tf_load_we<E>(p.w_e, ed, HC, sub);
-  const float4 q = live ? tld4(p.p + row * p.ldp + 4 * sub) : tzero4();
+  const EdgeW<E> we = load_edge_w<E>(p.w_e, ed, HC, sub);
+  const float4 q = live ? load4(p.p + row * p.ldp + 4 * sub) : zero4();
   const unsigned ld4 = (unsigned)p.ldp * 4u, koff = (unsigned)HC * 4u + (unsigned)sub * 16u, voff = koff + (unsigned)HC * 4u;
   // the descriptor ends behind the last row's 3 HC columns (nothing past them is addressed)
   const __amdgpu_buffer_rsrc_t pd = __builtin_amdgcn_make_buffer_rsrc(
       (void*)p.p, (short)0, (int)((unsigned)(p.n - 1) * ld4 + (unsigned)HC * 12u), 0x00020000);
   float* __restrict__ al = p.alpha ? p.alpha + (int64_t)t.e0 * heads + h : nullptr;
-  float4 acc = tzero4();
+  float4 acc = zero4();
   float m = -INFINITY, l = 0.f;
-  for (int e = ea; e < eb; e += kTU) {                   // (the lanes of a row share ea and eb: they shuffle together)
-    float4 kv[kTU], vv[kTU], tv[kTU];
-    TEdgeF<E> ev[kTU];
-    int64_t en[kTU];
+  for (int e = ea; e < eb; e += kTileU) {                   // (the lanes of a row share ea and eb: they shuffle together)
+    float4 kv[kTileU], vv[kTileU], tv[kTileU];
+    EdgeF<E> ev[kTileU];
+    int64_t en[kTileU];
 #pragma unroll
-    for (int u = 0; u < kTU; ++u) {
+    for (int u = 0; u < kTileU; ++u) {
       const bool ok = e + u < eb;
       const int ee = ok ? e + u : e;
-      const int col = ee < kTCap ? s_col[ee] : gcol[ee];
-      kv[u] = tbuf4(pd, ok ? (unsigned)col * ld4 + koff : kTOut);
-      vv[u] = tbuf4(pd, ok ? (unsigned)col * ld4 + voff : kTOut);
+      const int col = ee < kTileCap ? s_col[ee] : gcol[ee];
+      kv[u] = buf4(pd, ok ? (unsigned)col * ld4 + koff : kOffOut);
+      vv[u] = buf4(pd, ok ? (unsigned)col * ld4 + voff : kOffOut);
       en[u] = (int64_t)t.e0 + ee;
     }
     tf_edge(tv, ev, p.e, p.lde, en, we, ed);
-    float sc[kTU];
+    float sc[kTileU];
     float mt = m;
 #pragma unroll
-    for (int u = 0; u < kTU; ++u) {
-      sc[u] = tgroup_sum(tdot4(q, t4add(kv[u], tv[u])), gh) * scale;
-      vv[u] = t4add(vv[u], tv[u]);
+    for (int u = 0; u < kTileU; ++u) {
+      sc[u] = tgroup_sum(dot4(q, add4(kv[u], tv[u])), gh) * scale;
+      vv[u] = add4(vv[u], tv[u]);
       if (e + u < eb) {
         mt = fmaxf(mt, sc[u]);
         // the raw score, turned into alpha behind the loop: kept in LDS (a store to global memory here would sit in the
         // gathers' queue); an entry beyond the staged ones goes through alpha itself
         if (al && k == 0) {
-          if (e + u < kTCap) s_sc[(e + u) * heads + h] = sc[u];
+          if (e + u < kTileCap) s_sc[(e + u) * heads + h] = sc[u];
           else al[(int64_t)(e + u) * heads] = sc[u];
         }
       }
     }
     const float resc = expf(m - mt);                     // (first trip: exp(-inf) = 0 on acc = 0, l = 0)
-    acc = t4scale(resc, acc);
+    acc = scale4(resc, acc);
     l *= resc;
 #pragma unroll
-    for (int u = 0; u < kTU; ++u) {
+    for (int u = 0; u < kTileU; ++u) {
       const float w = e + u < eb ? expf(sc[u] - mt) : 0.f;
-      acc = t4fma(w, vv[u], acc);                        // CSR order
+      acc = fma4(w, vv[u], acc);                        // CSR order
       l += w;
     }
     m = mt;
@@ -240,24 +184,24 @@ __global__ __launch_bounds__(ROWS * HC / 4) void transformer_aggregate_kernel(TF
   const float inv = eb > ea ? 1.0f / l : 0.f;
   if (p.alpha) {                                         // (uniform)
     __syncthreads();
-    const int ebs = min(eb, kTCap);
+    const int ebs = min(eb, kTileCap);
     for (int e = ea + k; e < ebs; e += lph) al[(int64_t)e * heads] = expf(s_sc[e * heads + h] - m) * inv;     // lane k: entries k, k + lph, ...
     if (k == 0)                                          // rare: this lane's own stores read back
-      for (int e = max(ea, kTCap); e < eb; ++e) al[(int64_t)e * heads] = expf(al[(int64_t)e * heads] - m) * inv;
+      for (int e = max(ea, kTileCap); e < eb; ++e) al[(int64_t)e * heads] = expf(al[(int64_t)e * heads] - m) * inv;
   }
   if (!live) return;
-  const float4 o = t4scale(inv, acc);                    // a row without entries: exact zeros
+  const float4 o = scale4(inv, acc);                    // a row without entries: exact zeros
   if (p.o_pre) *reinterpret_cast<float4*>(p.o_pre + row * p.ldpre + 4 * sub) = o;
   float4 y = o;
   if (p.skip) {
-    const float4 s = tld4(p.skip + row * p.lds + 4 * sub);
+    const float4 s = load4(p.skip + row * p.lds + 4 * sub);
     if (p.w_beta) {
-      const float4 w1 = tld4(p.w_beta + 4 * sub), w2 = tld4(p.w_beta + HC + 4 * sub), w3 = tld4(p.w_beta + 2 * HC + 4 * sub);
-      const float a = tgroup_sum(tdot4(w1, o) + tdot4(w2, s) + tdot4(w3, t4sub(o, s)), tgroup(LPR));      // the whole row
-      const float b = tf_sig(a);
-      y = t4fma(b, s, t4scale(1.0f - b, o));
+      const float4 w1 = load4(p.w_beta + 4 * sub), w2 = load4(p.w_beta + HC + 4 * sub), w3 = load4(p.w_beta + 2 * HC + 4 * sub);
+      const float a = tgroup_sum(dot4(w1, o) + dot4(w2, s) + dot4(w3, sub4(o, s)), tgroup(LPR));      // the whole row
+      const float b = sigmoid1(a);
+      y = fma4(b, s, scale4(1.0f - b, o));
     } else {
-      y = eb > ea ? t4add(o, s) : s;                     // (no entries: S, bit for bit)
+      y = eb > ea ? add4(o, s) : s;                     // (no entries: S, bit for bit)
     }
   }
   *reinterpret_cast<float4*>(p.out + row * p.ldo + 4 * sub) = y;
@@ -283,32 +227,32 @@ __global__ __launch_bounds__(ROWS * HC / 4) void transformer_beta_bwd_kernel(TFB
   const int r0 = blockIdx.x * ROWS;
   const int64_t row = r0 + r;
   const bool live = row < p.n;
-  float4 d = tzero4(), o = d, s = d;
+  float4 d = zero4(), o = d, s = d;
   if (live) {
-    d = tld4(p.d_out + row * p.ldd + 4 * sub);
-    o = tld4(p.o + row * p.ldo + 4 * sub);
-    s = tld4(p.skip + row * p.lds + 4 * sub);
+    d = load4(p.d_out + row * p.ldd + 4 * sub);
+    o = load4(p.o + row * p.ldo + 4 * sub);
+    s = load4(p.skip + row * p.lds + 4 * sub);
   }
-  const float4 w1 = tld4(p.w_beta + 4 * sub), w2 = tld4(p.w_beta + HC + 4 * sub), w3 = tld4(p.w_beta + 2 * HC + 4 * sub);
-  const float4 os = t4sub(o, s);
+  const float4 w1 = load4(p.w_beta + 4 * sub), w2 = load4(p.w_beta + HC + 4 * sub), w3 = load4(p.w_beta + 2 * HC + 4 * sub);
+  const float4 os = sub4(o, s);
   const TGroup gr = tgroup(LPR);
-  const float a = tgroup_sum(tdot4(w1, o) + tdot4(w2, s) + tdot4(w3, os), gr);
-  const float b = tf_sig(a);
-  const float g = -tgroup_sum(tdot4(d, os), gr) * (b * (1.0f - b));       // <d_out, S - O> b (1 - b); a dead row: 0
+  const float a = tgroup_sum(dot4(w1, o) + dot4(w2, s) + dot4(w3, os), gr);
+  const float b = sigmoid1(a);
+  const float g = -tgroup_sum(dot4(d, os), gr) * (b * (1.0f - b));       // <d_out, S - O> b (1 - b); a dead row: 0
   if (live) {
-    *reinterpret_cast<float4*>(p.d_o + row * p.ldgo + 4 * sub) = t4fma(g, t4add(w1, w3), t4scale(1.0f - b, d));
-    *reinterpret_cast<float4*>(p.d_s + row * p.ldgs + 4 * sub) = t4fma(g, t4sub(w2, w3), t4scale(b, d));
+    *reinterpret_cast<float4*>(p.d_o + row * p.ldgo + 4 * sub) = fma4(g, add4(w1, w3), scale4(1.0f - b, d));
+    *reinterpret_cast<float4*>(p.d_s + row * p.ldgs + 4 * sub) = fma4(g, sub4(w2, w3), scale4(b, d));
   }
   // dw1 | dw2 | dw3: this tile's rows, in row order, one block after the other through the same LDS rows
   float* __restrict__ part = p.part + (int64_t)blockIdx.x * 3 * HC;
 #pragma unroll
   for (int q = 0; q < 3; ++q) {
-    s_p[r][sub] = t4scale(g, q == 0 ? o : q == 1 ? s : os);
+    s_p[r][sub] = scale4(g, q == 0 ? o : q == 1 ? s : os);
     __syncthreads();
     if (tid < LPR) {
-      float4 v = tzero4();
+      float4 v = zero4();
 #pragma unroll 8
-      for (int i = 0; i < ROWS; ++i) v = t4add(v, s_p[i][tid]);
+      for (int i = 0; i < ROWS; ++i) v = add4(v, s_p[i][tid]);
       *reinterpret_cast<float4*>(part + q * HC + 4 * tid) = v;
     }
     __syncthreads();
@@ -344,79 +288,79 @@ struct TFTargetArgs {
 template <int HC, int ROWS, int E>
 __global__ __launch_bounds__(ROWS * HC / 4) void transformer_bwd_targets_kernel(TFTargetArgs p) {
   constexpr int LPR = HC / 4, NT = ROWS * LPR;
-  __shared__ int32_t s_col[kTCap];
-  __shared__ int32_t s_rp[kTRows + 1];
+  __shared__ int32_t s_col[kTileCap];
+  __shared__ int32_t s_rp[kTileRows + 1];
   __shared__ __attribute__((aligned(16))) float4 s_p[ROWS][LPR];
   const int tid = threadIdx.x, r = tid / LPR, sub = tid % LPR;
   const int heads = p.heads, lph = p.lph, h = sub / lph, k = sub % lph, ed = p.edge_dim;
-  const TFTile t = tf_tile(p.rowptr, p.n, s_rp, ROWS);
-  const int staged = min(t.e1 - t.e0, kTCap);
+  const ConvTile t = conv_tile(p.rowptr, p.n, s_rp, ROWS);
+  const int staged = min(t.e1 - t.e0, kTileCap);
   for (int i = tid; i < staged; i += NT) s_col[i] = p.colidx[t.e0 + i];
   __syncthreads();
   const bool live = r < t.nr;
   const int ea = live ? s_rp[r] - t.e0 : 0, eb = live ? s_rp[r + 1] - t.e0 : 0;
   const int64_t row = t.r0 + r;
-  const TEdgeW<E> we = tf_load_we<E>(p.w_e, ed, HC, sub);
-  float4 dO = tzero4(), O = dO, q = dO;
+  const EdgeW<E> we = load_edge_w<E>(p.w_e, ed, HC, sub);
+  float4 dO = zero4(), O = dO, q = dO;
   if (live) {
-    dO = tld4(p.d_o + row * p.ldd + 4 * sub);
-    O = tld4(p.o + row * p.ldo + 4 * sub);
-    q = tld4(p.p + row * p.ldp + 4 * sub);
+    dO = load4(p.d_o + row * p.ldd + 4 * sub);
+    O = load4(p.o + row * p.ldo + 4 * sub);
+    q = load4(p.p + row * p.ldp + 4 * sub);
   }
   const TGroup gh = tgroup(lph);
-  const float rr = tgroup_sum(tdot4(dO, O), gh);         // = sum_k alpha_ik dalpha_ik: no second pass over the row
+  const float rr = tgroup_sum(dot4(dO, O), gh);         // = sum_k alpha_ik dalpha_ik: no second pass over the row
   const unsigned ld4 = (unsigned)p.ldp * 4u, koff = (unsigned)HC * 4u + (unsigned)sub * 16u, voff = koff + (unsigned)HC * 4u;
   const __amdgpu_buffer_rsrc_t pd = __builtin_amdgcn_make_buffer_rsrc(
       (void*)p.p, (short)0, (int)((unsigned)(p.n - 1) * ld4 + (unsigned)HC * 12u), 0x00020000);
   const int32_t* __restrict__ gcol = p.colidx + t.e0;
   const float* __restrict__ al = p.alpha + (int64_t)t.e0 * heads + h;
   float* __restrict__ dso = p.dscore + (int64_t)t.e0 * heads + h;
-  float4 dq = tzero4();
+  float4 dq = zero4();
   TEdgeS<E> ab;
 #pragma unroll
   for (int d = 0; d < (E > 0 ? E : 1); ++d) ab.a[d] = ab.b[d] = 0.f;
-  for (int e = ea; e < eb; e += kTU) {
-    float4 kv[kTU], vv[kTU], tv[kTU];
-    TEdgeF<E> ev[kTU];
-    float av[kTU];
-    int64_t en[kTU];
+  for (int e = ea; e < eb; e += kTileU) {
+    float4 kv[kTileU], vv[kTileU], tv[kTileU];
+    EdgeF<E> ev[kTileU];
+    float av[kTileU];
+    int64_t en[kTileU];
 #pragma unroll
-    for (int u = 0; u < kTU; ++u) {
+    for (int u = 0; u < kTileU; ++u) {
       const bool ok = e + u < eb;
       const int ee = ok ? e + u : e;
-      const int col = ee < kTCap ? s_col[ee] : gcol[ee];
-      kv[u] = tbuf4(pd, ok ? (unsigned)col * ld4 + koff : kTOut);
-      vv[u] = tbuf4(pd, ok ? (unsigned)col * ld4 + voff : kTOut);
+      const int col = ee < kTileCap ? s_col[ee] : gcol[ee];
+      kv[u] = buf4(pd, ok ? (unsigned)col * ld4 + koff : kOffOut);
+      vv[u] = buf4(pd, ok ? (unsigned)col * ld4 + voff : kOffOut);
       en[u] = (int64_t)t.e0 + ee;
       av[u] = ok ? al[(int64_t)ee * heads] : 0.f;
     }
     tf_edge(tv, ev, p.e, p.lde, en, we, ed);
 #pragma unroll
-    for (int u = 0; u < kTU; ++u) {
-      const float d = tgroup_sum(tdot4(dO, t4add(vv[u], tv[u])), gh);
+    for (int u = 0; u < kTileU; ++u) {
+      const float d = tgroup_sum(dot4(dO, add4(vv[u], tv[u])), gh);
       const float dsc = av[u] * (d - rr);                // a slot past the row's end: alpha = 0, adds zeros below
       if (e + u < eb && k == 0) dso[(int64_t)(e + u) * heads] = dsc;
-      dq = t4fma(dsc, t4add(kv[u], tv[u]), dq);          // CSR order
+      dq = fma4(dsc, add4(kv[u], tv[u]), dq);          // CSR order
       tf_ab_from<0, E>(ab, ev[u], dsc, av[u], ed);
     }
   }
   if (live) {
-    *reinterpret_cast<float4*>(p.dq + row * p.ldg + 4 * sub) = t4scale(p.scale, dq);
+    *reinterpret_cast<float4*>(p.dq + row * p.ldg + 4 * sub) = scale4(p.scale, dq);
     if (p.ds) *reinterpret_cast<float4*>(p.ds + row * p.ldgs + 4 * sub) = dO;
   }
   // dW_e[d]: s Q[i] A_i[d] + dO[i] B_i[d] of this tile's rows, in row order, one feature after the other through the same LDS rows
   if constexpr (E > 0) {
     float* __restrict__ part = p.part + (int64_t)(t.r0 / ROWS) * ed * HC;
-    const float4 qs = t4scale(p.scale, q);
+    const float4 qs = scale4(p.scale, q);
 #pragma unroll
     for (int d = 0; d < E; ++d) {
       if (d < ed) {                                      // (uniform)
-        s_p[r][sub] = t4fma(ab.a[d], qs, t4scale(ab.b[d], dO));
+        s_p[r][sub] = fma4(ab.a[d], qs, scale4(ab.b[d], dO));
         __syncthreads();
         if (tid < LPR) {
-          float4 s = tzero4();
+          float4 s = zero4();
 #pragma unroll 8
-          for (int i = 0; i < ROWS; ++i) s = t4add(s, s_p[i][tid]);
+          for (int i = 0; i < ROWS; ++i) s = add4(s, s_p[i][tid]);
           *reinterpret_cast<float4*>(part + d * HC + 4 * tid) = s;
         }
         __syncthreads();
@@ -439,13 +383,13 @@ struct TFSourceArgs {
 template <int HC, int ROWS>
 __global__ __launch_bounds__(ROWS * HC / 4) void transformer_bwd_sources_kernel(TFSourceArgs p) {
   constexpr int LPR = HC / 4, NT = ROWS * LPR;
-  __shared__ int32_t s_col[kTCap];
-  __shared__ int32_t s_q[kTCap];
-  __shared__ int32_t s_rp[kTRows + 1];
+  __shared__ int32_t s_col[kTileCap];
+  __shared__ int32_t s_q[kTileCap];
+  __shared__ int32_t s_rp[kTileRows + 1];
   const int tid = threadIdx.x, r = tid / LPR, sub = tid % LPR;
   const int heads = p.heads, h = sub / p.lph;
-  const TFTile t = tf_tile(p.rowptr, p.n, s_rp, ROWS);
-  const int staged = min(t.e1 - t.e0, kTCap);
+  const ConvTile t = conv_tile(p.rowptr, p.n, s_rp, ROWS);
+  const int staged = min(t.e1 - t.e0, kTileCap);
   for (int i = tid; i < staged; i += NT) {
     s_col[i] = p.colidx[t.e0 + i];
     s_q[i] = p.perm[t.e0 + i];
@@ -462,32 +406,32 @@ __global__ __launch_bounds__(ROWS * HC / 4) void transformer_bwd_sources_kernel(
       (void*)p.p, (short)0, (int)((unsigned)(p.n - 1) * ldp4 + (unsigned)HC * 4u), 0x00020000);
   const int32_t* __restrict__ gcol = p.colidx + t.e0;
   const int32_t* __restrict__ gq = p.perm + t.e0;
-  float4 dk = tzero4(), dv = dk;
-  for (int e = ea; e < eb; e += kTU) {
-    float4 dov[kTU], qv[kTU];
-    float av[kTU], zv[kTU];
+  float4 dk = zero4(), dv = dk;
+  for (int e = ea; e < eb; e += kTileU) {
+    float4 dov[kTileU], qv[kTileU];
+    float av[kTileU], zv[kTileU];
 #pragma unroll
-    for (int u = 0; u < kTU; ++u) {
+    for (int u = 0; u < kTileU; ++u) {
       const bool ok = e + u < eb;
       const int ee = ok ? e + u : e;
-      const bool st = ee < kTCap;
+      const bool st = ee < kTileCap;
       const int col = st ? s_col[ee] : gcol[ee];
       const int64_t en = st ? s_q[ee] : gq[ee];
-      dov[u] = tbuf4(dd, ok ? (unsigned)col * ldd4 + sub16 : kTOut);
-      qv[u] = tbuf4(qd, ok ? (unsigned)col * ldp4 + sub16 : kTOut);
+      dov[u] = buf4(dd, ok ? (unsigned)col * ldd4 + sub16 : kOffOut);
+      qv[u] = buf4(qd, ok ? (unsigned)col * ldp4 + sub16 : kOffOut);
       av[u] = ok ? p.alpha[en * heads + h] : 0.f;
       zv[u] = ok ? p.dscore[en * heads + h] : 0.f;
     }
 #pragma unroll
-    for (int u = 0; u < kTU; ++u) {
+    for (int u = 0; u < kTileU; ++u) {
       if (e + u < eb) {
-        dk = t4fma(zv[u], qv[u], dk);                    // the transposed CSR's order
-        dv = t4fma(av[u], dov[u], dv);
+        dk = fma4(zv[u], qv[u], dk);                    // the transposed CSR's order
+        dv = fma4(av[u], dov[u], dv);
       }
     }
   }
   if (live) {
-    *reinterpret_cast<float4*>(p.dkv + row * p.ldg + 4 * sub) = t4scale(p.scale, dk);
+    *reinterpret_cast<float4*>(p.dkv + row * p.ldg + 4 * sub) = scale4(p.scale, dk);
     *reinterpret_cast<float4*>(p.dkv + row * p.ldg + HC + 4 * sub) = dv;
   }
 }
@@ -495,28 +439,16 @@ __global__ __launch_bounds__(ROWS * HC / 4) void transformer_bwd_sources_kernel(
 bool tf_hc_ok(int32_t hc) { return hc == 16 || hc == 32 || hc == 64 || hc == 128; }
 bool tf_shape_ok(int64_t n, int32_t heads, int32_t c, int64_t ldp, int32_t edge_dim) {
   if (n < 0 || n > 0x7FFFFFFF || !(heads == 1 || heads == 2 || heads == 4 || heads == 8) || c < 4 || c > 128) return false;
-  if (edge_dim < 0 || edge_dim > kTEdgeMax) return false;
+  if (edge_dim < 0 || edge_dim > kEdgeMax) return false;
   const int hc = heads * c;
   return tf_hc_ok(hc) && ldp >= 3 * (int64_t)hc && ldp % 4 == 0 && (uint64_t)n * (uint64_t)ldp * 4u < 0x100000000ull;
 }
-// rows per workgroup: 16 at HC = 128, where 32 rows are 1024 threads with 128 registers each and W_e with a trip's three
-// float4 per entry does not fit at E = 8; 512 threads may hold 256
-int tf_rows(int hc) { return hc == 128 ? 16 : kTRows; }
-bool tf_ld_ok(int64_t ld, int w) { return ld >= w && ld % 4 == 0 && ld < (1ll << 30); }
 float tf_scale(int32_t c) { return (float)(1.0 / std::sqrt((double)c)); }
 
 const char* kTFShapes = "needs heads in {1, 2, 4, 8}, heads * c in {16, 32, 64, 128}, c >= 4, ldp >= 3 * heads * c in multiples of 4 "
                         "floats, n * ldp * 4 < 2^32 and 0 <= edge_dim <= 8";
 
-// the gather kernels are built for 0, up to 2 and up to 8 edge features: W_e holds that many float4 per lane, and registers
-// decide how many workgroups a CU keeps in flight
-#define GCNX_TF_DISPATCH_E(ed, HC_, R_, LAUNCH) \
-  do { if ((ed) == 0) { LAUNCH(HC_, R_, 0); } else if ((ed) <= 2) { LAUNCH(HC_, R_, 2); } else { LAUNCH(HC_, R_, 8); } } while (0)
-#define GCNX_TF_DISPATCH(hc, ed, LAUNCH)                                                        \
-  do {                                                                                          \
-    if ((hc) == 128) GCNX_TF_DISPATCH_E(ed, 128, 16, LAUNCH); else if ((hc) == 64) GCNX_TF_DISPATCH_E(ed, 64, 32, LAUNCH); \
-    else if ((hc) == 32) GCNX_TF_DISPATCH_E(ed, 32, 32, LAUNCH); else GCNX_TF_DISPATCH_E(ed, 16, 32, LAUNCH);             \
-  } while (0)
+// the kernels that read no edge features: LAUNCH(width, rows) as GCNX_CONV_DISPATCH picks them
 #define GCNX_TF_DISPATCH_HC(hc, LAUNCH)                                                         \
   do {                                                                                          \
     if ((hc) == 128) { LAUNCH(128, 16); } else if ((hc) == 64) { LAUNCH(64, 32); } else if ((hc) == 32) { LAUNCH(32, 32); } \
@@ -537,7 +469,7 @@ int gcnx_transformer_bwd_scratch_floats(int64_t n, int32_t heads, int32_t c, int
     return gcnx_fail(nullptr, GCNX_ERR_INVALID, "gcnx_transformer_bwd_scratch_floats: needs n >= 0, heads > 0, c > 0 and edge_dim >= 0");
   const int64_t hc = (int64_t)heads * c;
   const int64_t per = edge_dim > (beta ? 3 : 0) ? edge_dim : (beta ? 3 : 0);       // the two calls use it one after the other
-  *out = (int64_t)gcnx_cdiv(n, tf_rows((int)hc)) * per * hc;
+  *out = (int64_t)gcnx_cdiv(n, conv_tile_rows((int)hc)) * per * hc;
   return GCNX_OK;
 }
 
@@ -554,7 +486,7 @@ int gcnx_transformer_aggregate(gcnx_ctx* ctx, const int32_t* rowptr, const int32
                      n, heads, c, (long long)ldp, edge_dim);
   const int hc = heads * c;
   if (!gcnx_aligned16(p) || !gcnx_aligned16(w_e) || !gcnx_aligned16(skip) || !gcnx_aligned16(w_beta) || !gcnx_aligned16(out) ||
-      !gcnx_aligned16(o_pre) || !tf_ld_ok(ldo, hc) || (skip && !tf_ld_ok(lds, hc)) || (o_pre && !tf_ld_ok(ldpre, hc)))
+      !gcnx_aligned16(o_pre) || !conv_ld_ok(ldo, hc) || (skip && !conv_ld_ok(lds, hc)) || (o_pre && !conv_ld_ok(ldpre, hc)))
     return gcnx_fail(ctx, GCNX_ERR_UNSUPPORTED, "gcnx_transformer_aggregate: p, w_e, skip, w_beta, out and o_pre must be 16-byte aligned, "
                      "with ldo, lds and ldpre >= heads * c in multiples of 4 floats");
   if (n == 0) return GCNX_OK;
@@ -566,11 +498,11 @@ int gcnx_transformer_aggregate(gcnx_ctx* ctx, const int32_t* rowptr, const int32
   a.rowptr = rowptr; a.colidx = colidx; a.p = p; a.ldp = ldp; a.n = n; a.heads = heads; a.lph = c / 4; a.edge_dim = edge_dim;
   a.e = e; a.lde = lde; a.w_e = w_e; a.skip = skip; a.lds = lds; a.w_beta = w_beta; a.scale = tf_scale(c); a.out = out; a.ldo = ldo;
   a.alpha = alpha; a.o_pre = o_pre; a.ldpre = ldpre;
-  const int tiles = gcnx_cdiv(n, tf_rows(hc));
-  const size_t dyn = alpha ? (size_t)kTCap * heads * sizeof(float) : 0;
+  const int tiles = gcnx_cdiv(n, conv_tile_rows(hc));
+  const size_t dyn = alpha ? (size_t)kTileCap * heads * sizeof(float) : 0;
 #define GCNX_TF_AGG(HC_, R_, E_) \
   hipLaunchKernelGGL((transformer_aggregate_kernel<HC_, R_, E_>), dim3(tiles), dim3(R_ * HC_ / 4), dyn, ctx->stream, a)
-  GCNX_TF_DISPATCH(hc, edge_dim, GCNX_TF_AGG);
+  GCNX_CONV_DISPATCH(hc, edge_dim, GCNX_TF_AGG);
 #undef GCNX_TF_AGG
   GCNX_LAUNCH_OK(ctx);
   return GCNX_OK;
@@ -585,8 +517,8 @@ int gcnx_transformer_beta_bwd(gcnx_ctx* ctx, const float* d_out, int64_t ldd, co
   if (!tf_hc_ok(hc))
     return gcnx_fail(ctx, GCNX_ERR_UNSUPPORTED, "gcnx_transformer_beta_bwd: needs hc in {16, 32, 64, 128} (got %d)", hc);
   if (!gcnx_aligned16(d_out) || !gcnx_aligned16(o) || !gcnx_aligned16(skip) || !gcnx_aligned16(w_beta) || !gcnx_aligned16(d_o) ||
-      !gcnx_aligned16(d_s) || !gcnx_aligned16(dw_beta) || !gcnx_aligned16(scratch) || !tf_ld_ok(ldd, hc) || !tf_ld_ok(ldo, hc) ||
-      !tf_ld_ok(lds, hc) || !tf_ld_ok(ldgo, hc) || !tf_ld_ok(ldgs, hc))
+      !gcnx_aligned16(d_s) || !gcnx_aligned16(dw_beta) || !gcnx_aligned16(scratch) || !conv_ld_ok(ldd, hc) || !conv_ld_ok(ldo, hc) ||
+      !conv_ld_ok(lds, hc) || !conv_ld_ok(ldgo, hc) || !conv_ld_ok(ldgs, hc))
     return gcnx_fail(ctx, GCNX_ERR_UNSUPPORTED, "gcnx_transformer_beta_bwd: d_out, o, skip, w_beta, d_o, d_s, dw_beta and scratch must be "
                      "16-byte aligned, with ldd, ldo, lds, ldgo and ldgs >= hc in multiples of 4 floats");
   if (n == 0) return GCNX_OK;
@@ -596,7 +528,7 @@ int gcnx_transformer_beta_bwd(gcnx_ctx* ctx, const float* d_out, int64_t ldd, co
   TFBetaArgs a{};
   a.d_out = d_out; a.ldd = ldd; a.o = o; a.ldo = ldo; a.skip = skip; a.lds = lds; a.w_beta = w_beta; a.n = n; a.d_o = d_o; a.ldgo = ldgo;
   a.d_s = d_s; a.ldgs = ldgs; a.part = scratch;
-  const int tiles = gcnx_cdiv(n, tf_rows(hc));
+  const int tiles = gcnx_cdiv(n, conv_tile_rows(hc));
 #define GCNX_TF_BB(HC_, R_) hipLaunchKernelGGL((transformer_beta_bwd_kernel<HC_, R_>), dim3(tiles), dim3(R_ * HC_ / 4), 0, ctx->stream, a)
   GCNX_TF_DISPATCH_HC(hc, GCNX_TF_BB);
 #undef GCNX_TF_BB
@@ -619,8 +551,8 @@ int gcnx_transformer_bwd_targets(gcnx_ctx* ctx, const int32_t* rowptr, const int
                      n, heads, c, (long long)ldp, edge_dim);
   const int hc = heads * c;
   if (!gcnx_aligned16(p) || !gcnx_aligned16(w_e) || !gcnx_aligned16(d_o) || !gcnx_aligned16(o) || !gcnx_aligned16(dq) ||
-      !gcnx_aligned16(ds) || !gcnx_aligned16(dw_e) || !gcnx_aligned16(scratch) || !tf_ld_ok(ldd, hc) || !tf_ld_ok(ldo, hc) ||
-      !tf_ld_ok(ldg, hc) || (ds && !tf_ld_ok(ldgs, hc)))
+      !gcnx_aligned16(ds) || !gcnx_aligned16(dw_e) || !gcnx_aligned16(scratch) || !conv_ld_ok(ldd, hc) || !conv_ld_ok(ldo, hc) ||
+      !conv_ld_ok(ldg, hc) || (ds && !conv_ld_ok(ldgs, hc)))
     return gcnx_fail(ctx, GCNX_ERR_UNSUPPORTED, "gcnx_transformer_bwd_targets: p, w_e, d_o, o, dq, ds, dw_e and scratch must be 16-byte "
                      "aligned, with ldd, ldo, ldg and ldgs >= heads * c in multiples of 4 floats");
   if (n == 0) return GCNX_OK;
@@ -633,10 +565,10 @@ int gcnx_transformer_bwd_targets(gcnx_ctx* ctx, const int32_t* rowptr, const int
   a.rowptr = rowptr; a.colidx = colidx; a.p = p; a.ldp = ldp; a.n = n; a.heads = heads; a.lph = c / 4; a.edge_dim = edge_dim;
   a.e = e; a.lde = lde; a.w_e = w_e; a.alpha = alpha; a.d_o = d_o; a.ldd = ldd; a.o = o; a.ldo = ldo; a.scale = tf_scale(c);
   a.dscore = dscore; a.dq = dq; a.ldg = ldg; a.ds = ds; a.ldgs = ldgs; a.part = scratch;
-  const int tiles = gcnx_cdiv(n, tf_rows(hc));
+  const int tiles = gcnx_cdiv(n, conv_tile_rows(hc));
 #define GCNX_TF_BT(HC_, R_, E_) \
   hipLaunchKernelGGL((transformer_bwd_targets_kernel<HC_, R_, E_>), dim3(tiles), dim3(R_ * HC_ / 4), 0, ctx->stream, a)
-  GCNX_TF_DISPATCH(hc, edge_dim, GCNX_TF_BT);
+  GCNX_CONV_DISPATCH(hc, edge_dim, GCNX_TF_BT);
 #undef GCNX_TF_BT
   GCNX_LAUNCH_OK(ctx);
   if (edge_dim > 0) {
@@ -657,7 +589,7 @@ int gcnx_transformer_bwd_sources(gcnx_ctx* ctx, const int32_t* rowptr_t, const i
     return gcnx_fail(ctx, GCNX_ERR_UNSUPPORTED, "gcnx_transformer_bwd_sources: %s (got n=%d heads=%d c=%d ldp=%lld)", kTFShapes, n, heads,
                      c, (long long)ldp);
   const int hc = heads * c;
-  if (!gcnx_aligned16(p) || !gcnx_aligned16(d_o) || !gcnx_aligned16(dkv) || !tf_ld_ok(ldd, hc) || !tf_ld_ok(ldg, 2 * hc) ||
+  if (!gcnx_aligned16(p) || !gcnx_aligned16(d_o) || !gcnx_aligned16(dkv) || !conv_ld_ok(ldd, hc) || !conv_ld_ok(ldg, 2 * hc) ||
       !gcnx_fits_buffer(n, ldd, 4))
     return gcnx_fail(ctx, GCNX_ERR_UNSUPPORTED, "gcnx_transformer_bwd_sources: p, d_o and dkv must be 16-byte aligned, with ldd >= heads * c "
                      "and ldg >= 2 * heads * c in multiples of 4 floats and n * ldd * 4 < 2^32");
@@ -667,7 +599,7 @@ int gcnx_transformer_bwd_sources(gcnx_ctx* ctx, const int32_t* rowptr_t, const i
   TFSourceArgs a{};
   a.rowptr = rowptr_t; a.colidx = colidx_t; a.perm = perm_t; a.p = p; a.ldp = ldp; a.n = n; a.heads = heads; a.lph = c / 4;
   a.alpha = alpha; a.dscore = dscore; a.d_o = d_o; a.ldd = ldd; a.scale = tf_scale(c); a.dkv = dkv; a.ldg = ldg;
-  const int tiles = gcnx_cdiv(n, tf_rows(hc));
+  const int tiles = gcnx_cdiv(n, conv_tile_rows(hc));
 #define GCNX_TF_BS(HC_, R_) hipLaunchKernelGGL((transformer_bwd_sources_kernel<HC_, R_>), dim3(tiles), dim3(R_ * HC_ / 4), 0, ctx->stream, a)
   GCNX_TF_DISPATCH_HC(hc, GCNX_TF_BS);
 #undef GCNX_TF_BS

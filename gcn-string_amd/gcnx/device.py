@@ -1032,13 +1032,14 @@ def gatv2_bwd_scratch_floats(ctx, n, heads, c, edge_dim=0):
     return int(ctx.lib.gcnx_gatv2_bwd_scratch_floats(int(n), int(heads), int(c), int(edge_dim)))
 
 
-def _gatv2_edge(a, e, w_e, hc):
-    """(e pointer, lde, edge_dim, w_e pointer) of the optional edge operands: e [nnz, D] (any ld), w_e [D, heads * c]."""
+def _edge_operands(a, e, w_e, width):
+    """(e pointer, lde, edge_dim, w_e pointer) of the optional edge operands of GATv2Conv, ResGatedGraphConv and TransformerConv:
+    e [nnz, D] (any ld), w_e [D, width]."""
     if e is None:
         assert w_e is None
         return None, 0, 0, None
     d = e.shape[1]
-    assert e.shape[0] == a.nnz and w_e is not None and w_e.shape == (d, hc) and w_e.contiguous
+    assert e.shape[0] == a.nnz and w_e is not None and w_e.shape == (d, width) and w_e.contiguous
     return _p(e), e.ld, d, _p(w_e)
 
 
@@ -1050,7 +1051,7 @@ def gatv2_aggregate(ctx, a, xlr, att, bias, out, e=None, w_e=None, alpha=None, o
     hc, n = heads * c, xlr.shape[0]
     assert a.n == n and xlr.shape[1] == 2 * hc and out.shape == (n, hc) and att.contiguous and (bias is None or bias.shape == (hc,))
     assert (alpha is None or (alpha.shape == (a.nnz, heads) and alpha.contiguous)) and (o_pre is None or o_pre.shape == (n, hc))
-    ep, lde, d, wp = _gatv2_edge(a, e, w_e, hc)
+    ep, lde, d, wp = _edge_operands(a, e, w_e, hc)
     ctx._ck(ctx.lib.gcnx_gatv2_aggregate(ctx.h, a.rowptr.ptr, a.colidx.ptr, _p(xlr), xlr.ld, n, heads, c, ep, lde, d, wp, _p(att), _p(bias),
                                          float(slope), _p(out), out.ld, _p(alpha), _p(o_pre), o_pre.ld if o_pre is not None else 0))
     return out
@@ -1064,7 +1065,7 @@ def gatv2_bwd_edges(ctx, a, xlr, att, alpha, dout, o, dscore, dxr, datt, scratch
     assert a.n == n and xlr.shape[1] == 2 * hc and dout.shape == o.shape == dxr.shape == (n, hc)
     assert alpha.shape == dscore.shape == (a.nnz, heads) and datt.shape == (heads, c)
     assert att.contiguous and alpha.contiguous and dscore.contiguous and datt.contiguous
-    ep, lde, d, wp = _gatv2_edge(a, e, w_e, hc)
+    ep, lde, d, wp = _edge_operands(a, e, w_e, hc)
     assert (dw_e is None) == (d == 0) and (dw_e is None or (dw_e.shape == (d, hc) and dw_e.contiguous))
     assert scratch.size >= gatv2_bwd_scratch_floats(ctx, n, heads, c, d)
     ctx._ck(ctx.lib.gcnx_gatv2_bwd_edges(ctx.h, a.rowptr.ptr, a.colidx.ptr, _p(xlr), xlr.ld, n, heads, c, ep, lde, d, wp, _p(att),
@@ -1079,7 +1080,7 @@ def gatv2_bwd_nodes(ctx, a, xlr, att, alpha, dscore, dout, dxl, e=None, w_e=None
     hc, n = heads * c, xlr.shape[0]
     assert a.n == n and xlr.shape[1] == 2 * hc and dout.shape == dxl.shape == (n, hc)
     assert alpha.shape == dscore.shape == (a.nnz, heads) and att.contiguous and alpha.contiguous and dscore.contiguous
-    ep, lde, d, wp = _gatv2_edge(a, e, w_e, hc)
+    ep, lde, d, wp = _edge_operands(a, e, w_e, hc)
     rp, ci, pm = a.transpose_perm()
     ctx._ck(ctx.lib.gcnx_gatv2_bwd_nodes(ctx.h, rp.ptr, ci.ptr, pm.ptr, _p(xlr), xlr.ld, n, heads, c, ep, lde, d, wp, _p(att), float(slope),
                                          _p(alpha), _p(dscore), _p(dout), dout.ld, _p(dxl), dxl.ld))
@@ -1098,23 +1099,13 @@ def resgated_bwd_scratch_floats(ctx, n, h, edge_dim=0):
     return int(out.value)
 
 
-def _resgated_edge(a, e, w_e, h):
-    """(e pointer, lde, edge_dim, w_e pointer) of the optional edge operands: e [nnz, D] (any ld), w_e [D, 3 h]."""
-    if e is None:
-        assert w_e is None
-        return None, 0, 0, None
-    d = e.shape[1]
-    assert e.shape[0] == a.nnz and w_e is not None and w_e.shape == (d, 3 * h) and w_e.contiguous
-    return _p(e), e.ld, d, _p(w_e)
-
-
 def resgated_aggregate(ctx, a, p, out, e=None, w_e=None, skip=None, bias=None):
     """out = skip + bias + sum over the stored entries of ``a`` (row = target) of sigmoid(K[i] + Q[j] + e_ij (W_ke + W_qe)) *
     (V[j] + e_ij W_ve) (gcnx_resgated_aggregate).  p = K | Q | V in its first 3 h columns; w_e [D, 3 h] = W_ke | W_qe | W_ve."""
     n, h = out.shape
     assert a.n == n and p.shape[0] == n and p.shape[1] >= 3 * h and (bias is None or bias.shape == (h,))
     assert skip is None or skip.shape == (n, h)
-    ep, lde, d, wp = _resgated_edge(a, e, w_e, h)
+    ep, lde, d, wp = _edge_operands(a, e, w_e, 3 * h)
     ctx._ck(ctx.lib.gcnx_resgated_aggregate(ctx.h, a.rowptr.ptr, a.colidx.ptr, _p(p), p.ld, n, h, ep, lde, d, wp, _p(skip),
                                             skip.ld if skip is not None else 0, _p(bias), _p(out), out.ld))
     return out
@@ -1125,7 +1116,7 @@ def resgated_bwd_targets(ctx, a, p, dout, dk, scratch=None, ds=None, e=None, w_e
     scratch: resgated_bwd_scratch_floats floats (None with no edge features)."""
     n, h = dout.shape
     assert a.n == n and p.shape[0] == n and p.shape[1] >= 3 * h and dk.shape == (n, h) and (ds is None or ds.shape == (n, h))
-    ep, lde, d, wp = _resgated_edge(a, e, w_e, h)
+    ep, lde, d, wp = _edge_operands(a, e, w_e, 3 * h)
     assert (dw_e is None) == (d == 0) and (dw_e is None or (dw_e.shape == (d, 3 * h) and dw_e.contiguous))
     assert d == 0 or scratch.size >= resgated_bwd_scratch_floats(ctx, n, h, d)
     ctx._ck(ctx.lib.gcnx_resgated_bwd_targets(ctx.h, a.rowptr.ptr, a.colidx.ptr, _p(p), p.ld, n, h, ep, lde, d, wp, _p(dout), dout.ld,
@@ -1138,7 +1129,7 @@ def resgated_bwd_sources(ctx, a, p, dout, dqv, e=None, w_e=None):
     gcnx_resgated_bwd_sources)."""
     n, h = dout.shape
     assert a.n == n and p.shape[0] == n and p.shape[1] >= 3 * h and dqv.shape == (n, 2 * h)
-    ep, lde, d, wp = _resgated_edge(a, e, w_e, h)
+    ep, lde, d, wp = _edge_operands(a, e, w_e, 3 * h)
     rp, ci, pm = a.transpose_perm()
     ctx._ck(ctx.lib.gcnx_resgated_bwd_sources(ctx.h, rp.ptr, ci.ptr, pm.ptr, _p(p), p.ld, n, h, ep, lde, d, wp, _p(dout), dout.ld,
                                               _p(dqv), dqv.ld))
@@ -1157,16 +1148,6 @@ def transformer_bwd_scratch_floats(ctx, n, heads, c, edge_dim=0, beta=False):
     return int(out.value)
 
 
-def _transformer_edge(a, e, w_e, hc):
-    """(e pointer, lde, edge_dim, w_e pointer) of the optional edge operands: e [nnz, D] (any ld), w_e [D, heads * c]."""
-    if e is None:
-        assert w_e is None
-        return None, 0, 0, None
-    d = e.shape[1]
-    assert e.shape[0] == a.nnz and w_e is not None and w_e.shape == (d, hc) and w_e.contiguous
-    return _p(e), e.ld, d, _p(w_e)
-
-
 def transformer_aggregate(ctx, a, p, out, heads, e=None, w_e=None, skip=None, w_beta=None, alpha=None, o_pre=None):
     """out = O (+ skip, or the beta-gated mix of skip and O with w_beta [3 heads c]); O = softmax-weighted sum of V[j] + e_ij w_e
     over the stored entries of ``a`` (row = target), the scores <Q[i], K[j] + e_ij w_e> / sqrt(c) per head
@@ -1177,7 +1158,7 @@ def transformer_aggregate(ctx, a, p, out, heads, e=None, w_e=None, skip=None, w_
     assert a.n == n and heads * c == hc and p.shape[0] == n and p.shape[1] >= 3 * hc
     assert (skip is None or skip.shape == (n, hc)) and (w_beta is None or (w_beta.shape == (3 * hc,) and w_beta.contiguous))
     assert (alpha is None or (alpha.shape == (a.nnz, heads) and alpha.contiguous)) and (o_pre is None or o_pre.shape == (n, hc))
-    ep, lde, d, wp = _transformer_edge(a, e, w_e, hc)
+    ep, lde, d, wp = _edge_operands(a, e, w_e, hc)
     ctx._ck(ctx.lib.gcnx_transformer_aggregate(ctx.h, a.rowptr.ptr, a.colidx.ptr, _p(p), p.ld, n, heads, c, ep, lde, d, wp, _p(skip),
                                                skip.ld if skip is not None else 0, _p(w_beta), _p(out), out.ld, _p(alpha), _p(o_pre),
                                                o_pre.ld if o_pre is not None else 0))
@@ -1202,7 +1183,7 @@ def transformer_bwd_targets(ctx, a, p, alpha, d_o, o, dscore, dq, heads, scratch
     c = hc // heads
     assert a.n == n and heads * c == hc and p.shape[0] == n and p.shape[1] >= 3 * hc and o.shape == dq.shape == (n, hc)
     assert (ds is None or ds.shape == (n, hc)) and alpha.shape == dscore.shape == (a.nnz, heads) and alpha.contiguous and dscore.contiguous
-    ep, lde, d, wp = _transformer_edge(a, e, w_e, hc)
+    ep, lde, d, wp = _edge_operands(a, e, w_e, hc)
     assert (dw_e is None) == (d == 0) and (dw_e is None or (dw_e.shape == (d, hc) and dw_e.contiguous))
     assert d == 0 or scratch.size >= transformer_bwd_scratch_floats(ctx, n, heads, c, d)
     ctx._ck(ctx.lib.gcnx_transformer_bwd_targets(ctx.h, a.rowptr.ptr, a.colidx.ptr, _p(p), p.ld, n, heads, c, ep, lde, d, wp, _p(alpha),
