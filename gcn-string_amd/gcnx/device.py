@@ -1679,6 +1679,61 @@ def graph_norm_act_bwd(ctx, seg, dy, z, mean, inv, mean_scale, gamma, beta, dz, 
     return dz
 
 
+def sddmm(ctx, a, l, r, out, scale=None, accumulate=False):
+    """out[e] (+)= scale[e] * <l[row(e)], r[col(e)]> over the stored entries of ``a`` (gcnx_sddmm_csr): with Z = A H the gradient
+    with respect to A's values for l = dZ, r = H.  l, r [n, f] (any leading dimension), scale / out [nnz]."""
+    n, f = l.shape
+    assert a.n == n and r.shape == (n, f) and out.size >= a.nnz and (scale is None or scale.size >= a.nnz)
+    ctx._ck(ctx.lib.gcnx_sddmm_csr(ctx.h, a.rowptr.ptr, a.colidx.ptr, a.n, a.nnz, _p(l), l.ld, _p(r), r.ld, f, _p(scale), _p(out),
+                                   1 if accumulate else 0))
+    return out
+
+
+def mask_scratch_floats(ctx, n=0, f=0, per_row=False):
+    """Floats of scratch for edge_mask_bwd (f = 0) / feat_mask_bwd (gcnx_mask_scratch_floats)."""
+    return int(ctx.lib.gcnx_mask_scratch_floats(int(n), int(f), 1 if per_row else 0))
+
+
+def edge_mask_fwd(ctx, a, logits, vals_out, perm_t=None, vals_t_out=None):
+    """vals_out = a.vals * sigmoid(logits) off the diagonal, a.vals on it; vals_t_out[p] = vals_out[perm_t[p]] (gcnx_edge_mask_fwd)."""
+    assert a.vals is not None and logits.size >= a.nnz and vals_out.size >= a.nnz
+    assert vals_t_out is None or (perm_t is not None and vals_t_out.size >= a.nnz)
+    ctx._ck(ctx.lib.gcnx_edge_mask_fwd(ctx.h, a.rowptr.ptr, a.colidx.ptr, a.n, a.nnz, _p(a.vals), _p(logits),
+                                       perm_t.ptr if perm_t is not None else None, _p(vals_out), _p(vals_t_out)))
+    return vals_out
+
+
+def edge_mask_bwd(ctx, a, logits, dv, dlogits, terms, scratch, c_size=0.0, c_ent=0.0):
+    """dlogits from dv = dLoss/d(masked values) plus the regularisers' gradients, terms[0 .. 1] = sum sigmoid, sum entropy over
+    the off-diagonal entries (gcnx_edge_mask_bwd).  a: the UNMASKED operator."""
+    assert a.vals is not None and min(logits.size, dv.size, dlogits.size) >= a.nnz and terms.size >= 2
+    assert scratch.size >= mask_scratch_floats(ctx)
+    ctx._ck(ctx.lib.gcnx_edge_mask_bwd(ctx.h, a.rowptr.ptr, a.colidx.ptr, a.n, a.nnz, _p(a.vals), _p(logits), _p(dv), float(c_size),
+                                       float(c_ent), _p(dlogits), _p(terms), _p(scratch)))
+    return dlogits
+
+
+def feat_mask_fwd(ctx, x, logits, out):
+    """out = x * sigmoid(logits); logits [1, f] / [f] (one per feature) or [n, f] contiguous (gcnx_feat_mask_fwd)."""
+    n, f = x.shape
+    assert out.shape == (n, f) and logits.contiguous and logits.size in (f, n * f)
+    per_row = logits.size != f                              # (one row: both forms are the same product)
+    ctx._ck(ctx.lib.gcnx_feat_mask_fwd(ctx.h, _p(x), x.ld, _p(logits), 1 if per_row else 0, n, f, _p(out), out.ld))
+    return out
+
+
+def feat_mask_bwd(ctx, dxm, x, logits, dlogits, terms, scratch, c_size=0.0, c_ent=0.0):
+    """dlogits (the shape of logits) from dxm = dLoss/d(x * sigmoid(logits)) plus the regularisers' gradients; terms[0 .. 1] =
+    sum sigmoid, sum entropy over the logits (gcnx_feat_mask_bwd)."""
+    n, f = x.shape
+    assert dxm.shape == (n, f) and logits.contiguous and logits.size in (f, n * f) and dlogits.size == logits.size and terms.size >= 2
+    per_row = logits.size != f
+    assert scratch.size >= mask_scratch_floats(ctx, n, f, per_row)
+    ctx._ck(ctx.lib.gcnx_feat_mask_bwd(ctx.h, _p(dxm), dxm.ld, _p(x), x.ld, _p(logits), 1 if per_row else 0, n, f, float(c_size),
+                                       float(c_ent), _p(dlogits), _p(terms), _p(scratch)))
+    return dlogits
+
+
 def bn_act_pool(ctx, seg, z, mean, inv, gamma, beta, pooled, argmax, act="prelu_shared", alpha=None, mode="max"):
     """pooled[g] = max over graph g's rows of act(BN(z)) and its argmax rows, in one pass (gcnx_bn_act_pool)."""
     n, f = z.shape

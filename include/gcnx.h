@@ -1310,6 +1310,47 @@ GCNX_API int gcnx_graph_norm_act_bwd(gcnx_ctx* ctx, const int32_t* graph_ptr, co
                             float* dz, int64_t lddz, float* dgamma, float* dbeta, float* dmean_scale, float* dalpha,
                             float* scratch);
 
+/* ---- explaining a frozen model: gradients with respect to the operator's values, soft masks (csrc/explain.hip) ----
+ * Sampled dense-dense product on the CSR pattern: out[e] (+)= scale[e] * <L[row(e), :f], R[colidx[e], :f]> for every stored entry
+ * e (row(e): the row whose range of rowptr holds e).  L, R [n, f] with leading dimensions ldl, ldr >= f; scale [nnz] or NULL
+ * (ones); out [nnz], written (accumulate = 0) or added to (1).  With Z = A H this is dLoss/d(value of e) for L = dZ, R = H: the
+ * gradient of learnable edge weights.  f = 16, 32, 64, 128 with 16-byte aligned L and R and leading dimensions in multiples of 4
+ * floats run on the tile kernel; every other width (0 included), alignment and leading dimension on the any-width kernel: no
+ * shape is refused.  Every out[e] has one writer and one order of summation (no atomics): two calls leave the same bits.
+ * n == 0 or nnz == 0: GCNX_OK, nothing launched, nothing read.  GCNX_ERR_INVALID: NULL rowptr / colidx / out, NULL L or R with
+ * f > 0, ldl or ldr < f, out aliasing an operand. */
+GCNX_API int gcnx_sddmm_csr(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, int32_t n, int32_t nnz, const float* l,
+                            int64_t ldl, const float* r, int64_t ldr, int32_t f, const float* scale, float* out, int accumulate);
+/* The masked operator of GNNExplainer: vals_out[e] = a_vals[e] * sigmoid(logits[e]) for an off-diagonal entry, a_vals[e] (bit for
+ * bit; its logit is not read) for a diagonal one, and vals_t_out[p] = vals_out[perm_t[p]] (the values of the transposed pattern,
+ * perm_t from gcnx_csr_transpose_perm; both NULL: not written), in one launch.  sigmoid(a) = 1 / (1 + exp(-a)) for every finite a
+ * (exactly 1 from a = 17 on).  All arrays [nnz]. */
+GCNX_API int gcnx_edge_mask_fwd(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, int32_t n, int32_t nnz, const float* a_vals,
+                                const float* logits, const int32_t* perm_t, float* vals_out, float* vals_t_out);
+/* Floats of `scratch` for gcnx_edge_mask_bwd (f = 0) and gcnx_feat_mask_bwd (n rows of f features, per_row as there). */
+GCNX_API int64_t gcnx_mask_scratch_floats(int64_t n, int32_t f, int per_row);
+/* Its backward with the mask regularisers: with s = sigmoid(logits[e]), ent(p) = -p log(p + 1e-15) - (1 - p) log(1 - p + 1e-15),
+ *     dlogits[e] = (dv[e] a_vals[e] + c_size + c_ent ent'(s)) s (1 - s)    off the diagonal;  0 on it
+ *     terms[0] = sum s, terms[1] = sum ent(s)                              over the off-diagonal entries
+ * dv [nnz]: dLoss/d(vals_out) (two gcnx_sddmm_csr).  c_size, c_ent: the coefficients as they multiply the two sums in the
+ * objective (a mean's 1 / count included).  The sums are folded in a fixed order -- per-workgroup partials in scratch, then one
+ * workgroup -- without atomics.  n == 0 or nnz == 0: terms = 0, 0. */
+GCNX_API int gcnx_edge_mask_bwd(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, int32_t n, int32_t nnz, const float* a_vals,
+                                const float* logits, const float* dv, float c_size, float c_ent, float* dlogits, float* terms,
+                                float* scratch);
+/* The feature mask: out[i, k] = x[i, k] * sigmoid(logits[k]) (per_row = 0: one logit per feature, [f]) or
+ * x[i, k] * sigmoid(logits[i f + k]) (per_row = 1: [n, f] contiguous).  x, out [n, f] with ldx, ldo >= f, any alignment. */
+GCNX_API int gcnx_feat_mask_fwd(gcnx_ctx* ctx, const float* x, int64_t ldx, const float* logits, int per_row, int64_t n, int32_t f,
+                                float* out, int64_t ldo);
+/* Its backward from dxm = dLoss/d(out) [n, f] (ldd): dlogits = (dxm x (per_row = 0: summed over the rows in a fixed order -- parts
+ * of 64 or more rows, each dealt to the row lanes of its column, then over the parts -- in fp64 accumulators with one fp32
+ * rounding per part) + c_size + c_ent ent'(s))
+ * s (1 - s), terms[0 .. 1] = sum s, sum ent(s) over the logits, as gcnx_edge_mask_bwd.  scratch:
+ * gcnx_mask_scratch_floats(n, f, per_row) floats. */
+GCNX_API int gcnx_feat_mask_bwd(gcnx_ctx* ctx, const float* dxm, int64_t ldd, const float* x, int64_t ldx, const float* logits,
+                                int per_row, int64_t n, int32_t f, float c_size, float c_ent, float* dlogits, float* terms,
+                                float* scratch);
+
 /* ---- aggregation with bf16 features ("fp32 and bf16 both reported") ----
  * out[t, :] = bf16(act(sum_e vals[e] * h[colidx[e], :] + bias)): GCNConv.call's / GeneralConv's aggregation (gcn.py:334) on
  * activations stored as bf16 (uint16_t bit patterns), fp32 accumulation, round-to-nearest-even on the way out; bias fp32
