@@ -71,6 +71,17 @@ __device__ __forceinline__ ConvTile conv_tile(const int32_t* __restrict__ rowptr
   return t;
 }
 
+// the row of stored entry e: the last r with rowptr[r] <= e (rows without entries are skipped over) -- for the kernels that
+// run a thread per entry (explain.hip, pdn.hip)
+__device__ __forceinline__ int row_of(const int32_t* __restrict__ rowptr, int n, int e) {
+  int lo = 0, hi = n;                                       // rowptr[lo] <= e < rowptr[hi]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (rowptr[mid] <= e) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
 // W_e [edge_dim, HC]: this lane's float4 of every row, rows >= edge_dim zero and never used
 template <int E> struct EdgeW { float4 w[E > 0 ? E : 1]; };
 template <int E>

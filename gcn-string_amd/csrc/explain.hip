@@ -111,17 +111,7 @@ __global__ __launch_bounds__(256) void sddmm_any_kernel(SddmmArgs p, int g) {
   }
 }
 
-// ---- masks ------------------------------------------------------------------------------------------------------------------
-// the row of stored entry e: the last r with rowptr[r] <= e (rows without entries are skipped over)
-__device__ __forceinline__ int row_of(const int32_t* __restrict__ rowptr, int n, int e) {
-  int lo = 0, hi = n;                                       // rowptr[lo] <= e < rowptr[hi]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (rowptr[mid] <= e) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
+// ---- masks (row_of: conv_tile.h) ----------------------------------------------------------------------------------------------
 // s = sigmoid(a) and q = 1 - s without the cancellation of 1 - s near s = 1: q = exp(-a) s there (exp(-a) <= 1: no overflow)
 struct Sig { float s, q; };
 __device__ __forceinline__ Sig sig2(float a) {

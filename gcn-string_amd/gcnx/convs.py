@@ -1,5 +1,6 @@
 """The launch sequences of the convolutions that a layer (gcnx.layers) and a model (gcnx.models) both run: PNAConv, GATConv,
-GATv2Conv, ResGatedGraphConv, TransformerConv and GINEConv.  This is the one place they are written down.
+GATv2Conv, ResGatedGraphConv, TransformerConv, GINEConv and PDNConv (with the GCNConv sequence it is built on).  This is the one
+place they are written down.
 
 One forward and one backward function per convolution, plain functions over operands: ``ctx``, the pattern, the operands, the
 parameter views, the gradient views, every scratch and output buffer, then the scalars.  The caller owns the storage, the
@@ -180,3 +181,54 @@ def gine_backward(ctx, a, x, e, eps, t, u, dz, w_e, b_e, w_a, w_b, g_eps, g_w_e,
         D.gin_eps_grad(ctx, x, dt, eps_parts, g_eps)                                       # d eps = sum <x, dT>
     if dx is not None:
         D.gine_bwd_nodes(ctx, a, x, eps, e, w_e, b_e, dt, dx)                              # dx (transposed pattern + permutation)
+
+
+# ---- GCNConv (the model's sequence; PDNConv runs it on its own operator) ------------------------------------------------------
+def gcn_forward(ctx, a_hat, x, w, bias, out, h_tmp, s=None):
+    """out = A^ (x W) + bias.  Returns True if it ran as the one-launch (A^ x) W (then ``s``, if given, receives S = A^ x, the
+    operand of dW = S^T dZ, as GCNConv.backward uses it); otherwise gcnx_gemm into h_tmp, then gcnx_spmm_csr."""
+    if a_hat.plan is None and x.contiguous and D.gcn_conv_fused_ok(ctx, x.shape[0], x.shape[1], w.shape[1], x.ld):
+        D.gcn_conv_fwd(ctx, a_hat, x, w, bias, out, act=None, s=s)                         # (A^ x) W + b in one launch
+        return True
+    D.gemm(ctx, x, w, None, h_tmp)
+    D.spmm(ctx, a_hat, h_tmp, bias, out)
+    return False
+
+
+def gcn_backward(ctx, a_t, x, dz, w, g_w, g_bias, t, dx, s=None):
+    """From dz: the bias and weight gradients and, with dx, the gradient of the input.  a_t: the transposed operator.  s: S = A^ x
+    kept by a one-launch forward (with dx only): the association of GCNConv.backward, which leaves dZ W^T in t; otherwise t
+    receives A^T dZ."""
+    D.act_bias_grad(ctx, dz, None, dz, None, db=g_bias)                                    # column sums of dZ
+    if dx is not None and s is not None:
+        D.gemm_dw(ctx, s, dz, g_w)                                                         # dW = S^T dZ
+        D.gemm_dx(ctx, dz, w, t)                                                           # dZ W^T
+        D.spmm(ctx, a_t, t, None, dx)                                                      # dx = A^T (dZ W^T)
+        return
+    D.spmm(ctx, a_t, dz, None, t)                                                          # A^T dZ
+    D.gemm_dw(ctx, x, t, g_w)                                                              # dW = x^T (A^T dZ)
+    if dx is not None:
+        D.gemm_dx(ctx, t, w, dx)                                                           # dx = (A^T dZ) W^T
+
+
+# ---- PDNConv -----------------------------------------------------------------------------------------------------------------
+def pdn_forward(ctx, a, a_v, a_vt, x, e, unit, w_1, b_1, w_2, b_2, w, bias, gate, r, out, h_tmp, s=None):
+    """The layer's operator pair, then GCNConv on it.  a: the pattern with its transposed pattern (DeviceCSR.transpose_perm);
+    a_v / a_vt: CSRs of the pattern / the transposed pattern whose value arrays receive v_e = r_i w_e r_j and v[perm_t]; gate
+    [nnz] and r [n] receive the gates and deg^-1/2 (what the backward reads).  Returns gcn_forward's route flag."""
+    D.pdn_operator(ctx, a, e, w_1, b_1, w_2, b_2, gate, r, a_v.vals, unit=unit, perm_t=a.transpose_perm()[2], vals_t_out=a_vt.vals)
+    return gcn_forward(ctx, a_v, x, w, bias, out, h_tmp, s)
+
+
+def pdn_backward(ctx, a, a_vt, x, e, unit, w_1, b_1, w_2, b_2, gate, r, dz, w, g_w, g_bias, g_w_1, g_b_1, g_w_2, g_b_2, t, tl, gv,
+                 scratch, dx, s=None):
+    """GCNConv's backward on the transposed operator a_vt, then G_e = <(dZ W^T)[i], x[j]> (gcnx_sddmm_csr) and the gate MLP's
+    gradients.  t [n, h] as gcn_backward's; tl [n, f_in]: room for dZ W^T where gcn_backward does not leave it in t; gv [nnz];
+    scratch: pdn_bwd_scratch_floats."""
+    gcn_backward(ctx, a_vt, x, dz, w, g_w, g_bias, t, dx, s)
+    if dx is not None and s is not None:
+        tl = t                                                                             # (the one-launch association left it)
+    else:
+        D.gemm_dx(ctx, dz, w, tl)                                                          # dZ W^T
+    D.sddmm(ctx, a, tl, x, gv)                                                             # G = dLoss/dv on the forward pattern
+    D.pdn_operator_bwd(ctx, a, e, w_1, b_1, w_2, b_2, gate, r, gv, g_w_1, g_b_1, g_w_2, g_b_2, scratch, unit=unit)

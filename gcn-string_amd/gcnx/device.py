@@ -1734,6 +1734,50 @@ def feat_mask_bwd(ctx, dxm, x, logits, dlogits, terms, scratch, c_size=0.0, c_en
     return dlogits
 
 
+def pdn_ok(ctx, edge_dim, edge_hidden):
+    """True if the PDN operator kernels serve this MLP: edge_dim 1 .. 8, edge_hidden 1 .. 64 (gcnx_pdn_ok)."""
+    return bool(ctx.lib.gcnx_pdn_ok(int(edge_dim), int(edge_hidden)))
+
+
+def pdn_bwd_scratch_floats(ctx, n, nnz, edge_dim, edge_hidden):
+    return int(ctx.lib.gcnx_pdn_bwd_scratch_floats(int(n), int(nnz), int(edge_dim), int(edge_hidden)))
+
+
+def _pdn_mlp(e, w1, b1, w2, b2):
+    d, he = w1.shape
+    assert e.shape[1] == d and b1.size == he and w2.size == he and b2.size == 1
+    assert w1.contiguous and b1.contiguous and w2.contiguous
+    return d, he
+
+
+def pdn_operator(ctx, a, e, w1, b1, w2, b2, w_out, r_out, vals_out, unit=None, perm_t=None, vals_t_out=None):
+    """The PDNConv operator on the pattern of ``a``: w_out [nnz] = the gates sigmoid(MLP(e)) (1 where unit), r_out [n] =
+    deg^-1/2 of the weighted degrees, vals_out [nnz] = r_i w_e r_j, vals_t_out[p] = vals_out[perm_t[p]] (gcnx_pdn_operator).
+    e [nnz, d] with any leading dimension; w1 [d, he], b1 [he], w2 [he], b2 [1]; unit: uint8 [nnz] or None."""
+    d, he = _pdn_mlp(e, w1, b1, w2, b2)
+    assert e.shape[0] >= a.nnz and min(w_out.size, vals_out.size) >= a.nnz and r_out.size >= a.n
+    assert (perm_t is None) == (vals_t_out is None) and (vals_t_out is None or vals_t_out.size >= a.nnz)
+    assert unit is None or (unit.dtype == np.uint8 and unit.size >= a.nnz)
+    ctx._ck(ctx.lib.gcnx_pdn_operator(ctx.h, a.rowptr.ptr, a.colidx.ptr, a.n, a.nnz, _p(e), e.ld, d, _p(w1), _p(b1), _p(w2), _p(b2), he,
+                                      unit.ptr if unit is not None else None, perm_t.ptr if perm_t is not None else None, _p(w_out),
+                                      _p(r_out), _p(vals_out), _p(vals_t_out)))
+    return vals_out
+
+
+def pdn_operator_bwd(ctx, a, e, w1, b1, w2, b2, w, r, g, dw1, db1, dw2, db2, scratch, unit=None):
+    """The gradients of the gate MLP from g = dLoss/d(vals_out) [nnz] in forward entry order (gcnx_pdn_operator_bwd); w, r as
+    pdn_operator left them.  ``a`` carries its transposed pattern (DeviceCSR.transpose_perm)."""
+    d, he = _pdn_mlp(e, w1, b1, w2, b2)
+    rp_t, ci_t, pm = a.transpose_perm()
+    assert min(w.size, g.size) >= a.nnz and r.size >= a.n
+    assert dw1.size == d * he and db1.size == he and dw2.size == he and db2.size == 1 and dw1.contiguous
+    assert scratch.size >= pdn_bwd_scratch_floats(ctx, a.n, a.nnz, d, he)
+    assert unit is None or (unit.dtype == np.uint8 and unit.size >= a.nnz)
+    ctx._ck(ctx.lib.gcnx_pdn_operator_bwd(ctx.h, a.rowptr.ptr, a.colidx.ptr, rp_t.ptr, ci_t.ptr, pm.ptr, a.n, a.nnz, _p(e), e.ld, d,
+                                          _p(w1), _p(b1), _p(w2), _p(b2), he, unit.ptr if unit is not None else None, _p(w), _p(r),
+                                          _p(g), _p(dw1), _p(db1), _p(dw2), _p(db2), _p(scratch)))
+
+
 def bn_act_pool(ctx, seg, z, mean, inv, gamma, beta, pooled, argmax, act="prelu_shared", alpha=None, mode="max"):
     """pooled[g] = max over graph g's rows of act(BN(z)) and its argmax rows, in one pass (gcnx_bn_act_pool)."""
     n, f = z.shape

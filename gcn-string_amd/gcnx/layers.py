@@ -468,6 +468,99 @@ class GINEConv(GINConv):
         return dx
 
 
+class PDNConv(Layer):
+    """torch_geometric.nn.PDNConv(in, channels, edge_dim, hidden_channels, add_self_loops=True, normalize=True, bias=True)
+    (Pathfinder Discovery Networks, Rozemberczki et al. 2021): GCNConv on edge weights that a two-layer MLP with a sigmoid
+    learns from the edge features -- the dca / proximity values the reference computes on every contact and bridge and its
+    model drops (gcn_utills.py:319-443; gcn.py:71):
+
+        w_e = sigmoid(mlp.2(relu(mlp.0(e_ij))))     out = D_w^-1/2 A_w D_w^-1/2 (x lin) + bias,   D_w = the row sums of the w_e
+
+    ``PDNConv(channels, edge_dim, hidden_channels, add_self_loops=True, normalize=True, bias=True)``, called as
+    ``layer([x, a, e])`` or ``layer([x, a, e, unit])`` with device operands: e [nnz, edge_dim], row k belonging to stored entry
+    k of ``a``; unit (uint8 [nnz], optional) marks entries whose weight is exactly 1 and not learned.  The pattern is used as
+    stored, values are ignored.  ``a, e, unit = layer.preprocess(a, e)`` is PyG's add_remaining_self_loops(fill_value=1) on a
+    host matrix: missing loops added in sorted position with zero feature rows and their flags (unit None where none was
+    missing); with add_self_loops=False it raises NotImplementedError (pass the matrix as stored), as normalize=False does at
+    construction.  edge_dim 1 .. 8, hidden_channels 1 .. 64.  Parameters under PyG's names: ``bias``, ``lin.weight`` (stored
+    [in, channels]), ``mlp.0.weight`` (stored [edge_dim, hidden]), ``mlp.0.bias``, ``mlp.2.weight`` (stored [hidden, 1]),
+    ``mlp.2.bias``; glorot-uniform weights drawn lin, mlp.0, mlp.2, zero biases.  ``backward(dy, need_dx=True)`` returns dx and
+    leaves every gradient in ``grads``; no gradient flows to e.  ``edge_weights()``: the gates of the last call, a host array.
+
+    Launches (pdn_forward / pdn_backward of gcnx/convs.py, which the model runs too; csrc/pdn.hip): gcnx_pdn_operator, then
+    GCNConv's one launch or gcnx_gemm + gcnx_spmm_csr; backward GCNConv's launches on the transposed operator, gcnx_gemm_dx,
+    gcnx_sddmm_csr, gcnx_pdn_operator_bwd."""
+
+    def __init__(self, channels, edge_dim, hidden_channels, add_self_loops=True, normalize=True, bias=True, **kw):
+        super().__init__(**kw)
+        if not normalize:
+            raise NotImplementedError("PDNConv normalize=False: the kernels build the normalised operator (gcnx_pdn_operator)")
+        if edge_dim is None or not 1 <= int(edge_dim) <= 8:
+            raise NotImplementedError(f"PDNConv edge_dim={edge_dim}: the kernels serve 1 to 8 edge features")
+        if not 1 <= int(hidden_channels) <= 64:
+            raise NotImplementedError(f"PDNConv hidden_channels={hidden_channels}: the kernels serve a gate MLP of 1 to 64 hidden units")
+        self.channels, self.edge_dim, self.hidden_channels = int(channels), int(edge_dim), int(hidden_channels)
+        self.add_self_loops, self.use_bias = bool(add_self_loops), bool(bias)
+
+    def preprocess(self, a, e):
+        """(scipy CSR with unit values, e', unit) of a host adjacency and its per-entry features: the missing loops added."""
+        if not self.add_self_loops:
+            raise NotImplementedError("PDNConv add_self_loops=False has no host transform: pass the adjacency as stored")
+        import scipy.sparse as sp
+        from .models import _with_unit_self_loops
+        t, e, unit = _with_unit_self_loops(a, e, a.shape[0])
+        idx = np.asarray(t.indices, np.int64)
+        return sp.csr_matrix((np.ones(idx.shape[0]), (idx[:, 0], idx[:, 1])), shape=a.shape), e, unit
+
+    def _param_spec(self, in_dim):
+        c, d, he = self.channels, self.edge_dim, self.hidden_channels
+        lin, m0, m2 = glorot_uniform(self._rng, in_dim, c), glorot_uniform(self._rng, d, he), glorot_uniform(self._rng, he, 1)
+        spec = [("bias", (c,), np.zeros(c, np.float32))] if self.use_bias else []
+        return spec + [("lin.weight", (in_dim, c), lin), ("mlp.0.weight", (d, he), m0), ("mlp.0.bias", (he,), np.zeros(he, np.float32)),
+                       ("mlp.2.weight", (he, 1), m2), ("mlp.2.bias", (1,), np.zeros(1, np.float32))]
+
+    def _mlp(self, t):
+        return t["mlp.0.weight"], t["mlp.0.bias"], t["mlp.2.weight"], t["mlp.2.bias"]
+
+    def call(self, inputs, out=None):
+        if len(inputs) not in (3, 4):
+            raise ValueError(f"PDNConv(edge_dim={self.edge_dim}) takes [x, a, e] or [x, a, e, unit]")
+        x, a, e = inputs[:3]
+        unit = inputs[3] if len(inputs) == 4 else None
+        if tuple(e.shape) != (a.nnz, self.edge_dim):
+            raise ValueError(f"PDNConv(edge_dim={self.edge_dim}): e must be [{a.nnz}, {self.edge_dim}] (one row per stored entry), "
+                             f"got {list(e.shape)}")
+        if not self.built:
+            self.build(x.ctx, x.shape[1])
+        ctx, n, c, p, ne = self.ctx, x.shape[0], self.channels, self.params, max(a.nnz, 1)
+        a = a.unweighted()
+        rp_t, ci_t, _ = a.transpose_perm()
+        y = out if out is not None else self._buf("y", (n, c))
+        gate, r, s = self._buf("gate", (ne,)), self._buf("r", (n,)), self._buf("s", (n, x.shape[1]))
+        mk = lambda rp, ci, vals: D.DeviceCSR(ctx, a.n, a.nnz, rp, ci, vals, a.block_ptr, a.n_blocks, False, a.max_block_rows)
+        a_v, a_vt = mk(a.rowptr, a.colidx, self._buf("v", (ne,))), mk(rp_t, ci_t, self._buf("vt", (ne,)))
+        ok = convs.pdn_forward(ctx, a, a_v, a_vt, x, e, unit, *self._mlp(p), p["lin.weight"], p.get("bias"), gate, r, y,
+                               self._buf("h", (n, c)), s=s)
+        self._saved = (x, a, a_vt, e, unit, gate, r, s if ok else None)
+        return y
+
+    def edge_weights(self):
+        """The gates w_e [nnz] of the last call (before normalisation; 1 on unit entries)."""
+        a, gate = self._saved[1], self._saved[5]
+        return gate.numpy()[:a.nnz].copy()
+
+    def backward(self, dy, need_dx=True):
+        x, a, a_vt, e, unit, gate, r, s = self._saved
+        ctx, p, g, (n, f) = self.ctx, self.params, self.grads, x.shape
+        dx = self._buf("dx", x.shape) if need_dx else None
+        scratch = self._buf("scratch", (max(D.pdn_bwd_scratch_floats(ctx, n, a.nnz, self.edge_dim, self.hidden_channels), 4),))
+        db = g["bias"] if self.use_bias else self._buf("db", (self.channels,))
+        convs.pdn_backward(ctx, a, a_vt, x, e, unit, *self._mlp(p), gate, r, dy, p["lin.weight"], g["lin.weight"], db, *self._mlp(g),
+                           self._buf("t", (n, self.channels if s is None or dx is None else f)), self._buf("tl", (n, f)),
+                           self._buf("gv", (max(a.nnz, 1),)), scratch, dx, s)
+        return dx
+
+
 PNA_AGGREGATORS = ("mean", "min", "max", "std")
 PNA_SCALERS = ("identity", "amplification", "attenuation")
 

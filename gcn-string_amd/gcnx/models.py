@@ -63,6 +63,7 @@ class DeviceBatch:
     that does overwrite ``x`` calls ``invalidate()`` afterwards."""
 
     _next_uid = 0
+    unit = None                          # gcnx.PDN: uint8 [nnz] on the device, 1 on the loops it added to a host adjacency (else None)
 
     def __init__(self, ctx, x, a, seg, y=None, e=None, ax=None):
         self.ctx, self.x, self.a, self.seg, self.y, self.e, self.ax = ctx, x, a, seg, y, e, ax
@@ -1403,6 +1404,32 @@ def _with_mean_self_loops(a, e, n):
     return SparseTensor(idx[order], np.ones(order.size), (n, n)), e
 
 
+def _with_unit_self_loops(a, e, n):
+    """PyG's add_remaining_self_loops(fill_value=1) of PDNConv on the batch adjacency (host, COO or scipy; row = target) with
+    edge features e [nnz, S] (one row per stored entry, row-major): every stored entry, a stored loop included, keeps its
+    place among its row's entries and its feature row; a row that stores no loop gets one in sorted position with a zero
+    feature row.  Returns (SparseTensor with unit values, e' in its entry order, unit [nnz'] uint8: 1 on the added loops --
+    the entries whose weight is exactly 1 and not learned -- or None where no loop was missing)."""
+    from .loader import sp_matrix_to_sp_tensor
+    if not isinstance(a, SparseTensor):
+        a = sp_matrix_to_sp_tensor(a)
+    idx = np.asarray(a.indices, np.int64).reshape(-1, 2)
+    e = np.asarray(e)
+    if e.ndim != 2 or e.shape[0] != idx.shape[0]:
+        raise ValueError(f"edge features e have shape {e.shape}: expected one row per stored entry of the adjacency ({idx.shape[0]})")
+    has = np.zeros(n, bool)
+    d = idx[:, 0] == idx[:, 1]
+    has[idx[d, 0]] = True
+    miss = np.nonzero(~has)[0].astype(np.int64)
+    if miss.size == 0:
+        return SparseTensor(idx, np.ones(idx.shape[0]), (n, n)), e.astype(np.float32), None
+    idx = np.concatenate([idx, np.stack([miss, miss], 1)])
+    order = np.lexsort((idx[:, 1], idx[:, 0]))
+    unit = np.concatenate([np.zeros(e.shape[0], np.uint8), np.ones(miss.size, np.uint8)])[order]
+    e = np.concatenate([e.astype(np.float32), np.zeros((miss.size, e.shape[1]), np.float32)])[order]
+    return SparseTensor(idx[order], np.ones(order.size), (n, n)), e, unit
+
+
 def _conv_keys(*names):
     """{k: the names with the convolution's number k appended} -- formatted once per class: the conv hooks run every step."""
     return {k: tuple(f"{name}{k}" for name in names) for k in (1, 2)}
@@ -1751,13 +1778,7 @@ class GCN(_GraphRunner):
     def _conv(self, a_hat, x, w, bias, out, h_tmp, s=None):
         """A^ (x W) + b.  Returns True if it ran as the one-launch (A^ x) W (then ``s`` receives S = A^ x, the operand of
         dW = S^T dZ, as GCNConv.backward uses it)."""
-        ctx = self.ctx
-        if a_hat.plan is None and x.contiguous and D.gcn_conv_fused_ok(ctx, x.shape[0], x.shape[1], w.shape[1], x.ld):
-            D.gcn_conv_fwd(ctx, a_hat, x, w, bias, out, act=None, s=s)     # (A^ x) W + b in one launch
-            return True
-        D.gemm(ctx, x, w, None, h_tmp)
-        D.spmm(ctx, a_hat, h_tmp, bias, out)
-        return False
+        return convs.gcn_forward(self.ctx, a_hat, x, w, bias, out, h_tmp, s)
 
     # the two convolutions of the forward and their backward segments, in terms of the two hooks a subclass with another
     # convolution replaces: conv k reads x and writes bufs["z{k}"]; its backward reads dzk = bufs["dz{k}"] and writes dx if given
@@ -1784,18 +1805,11 @@ class GCN(_GraphRunner):
             bufs["s2_ok"] = ok
 
     def _conv_bwd(self, a_t, x, k, dzk, bufs, dx):
-        ctx, p, g = self.ctx, self.p, self.g
+        p, g = self.p, self.g
         w, b, _ = self._KEYS[k]
-        D.act_bias_grad(ctx, dzk, None, dzk, None, db=g[b])                          # conv_k.bias: column sums of dZ_k
-        if dx is not None and bufs["s2_ok"]:                # forward was (A^ Y1) W2: the association of GCNConv.backward
-            D.gemm_dw(ctx, bufs["s2"], dzk, g["w2"])                                # dW2 = S2^T dZ2
-            D.gemm_dx(ctx, dzk, p["w2"], bufs["t"])                                 # dZ2 W2^T
-            D.spmm(ctx, a_t, bufs["t"], None, dx)                                   # dY1 = A^T (dZ2 W2^T)
-            return
-        D.spmm(ctx, a_t, dzk, None, bufs["t"])                                      # A^T dZ_k
-        D.gemm_dw(ctx, x, bufs["t"], g[w])                                          # dW_k = x^T (A^T dZ_k)
-        if dx is not None:
-            D.gemm_dx(ctx, bufs["t"], p[w], dx)                                     # dY1 = (A^T dZ2) W2^T
+        # conv2 after a one-launch forward (A^ Y1) W2: the association of GCNConv.backward, dW2 = S2^T dZ2
+        s = bufs["s2"] if dx is not None and bufs["s2_ok"] else None
+        convs.gcn_backward(self.ctx, a_t, x, dzk, p[w], g[w], g[b], bufs["t"], dx, s)
 
     def _moments(self, z, mean, inv, bufs, counts):
         """Training-mode BatchNorm statistics over the rows of z; with counts (sync-BN) over every rank's rows: the two moment
@@ -2294,6 +2308,149 @@ class GINE(GIN):
         convs.gine_backward(self.ctx, a, x, bufs["e"], self._eps(k), bufs[t], bufs[u], dz, p[we], p[bl], p[wa], p[wb],
                             g[e] if self.train_eps else None, g[we], g[bl], g[wa], g[ba], g[wb], g[bb], bufs["h1"], bufs[dt],
                             bufs["gine_scratch"], bufs.get("eps_parts"), dx)
+
+
+class PDN(GCN):
+    """``GCN`` whose two GCNConv layers take an ``edge_weight`` learned from the edge features: both convolutions are PyG's
+    PDNConv(in, out, edge_dim=D, hidden_channels=He) (Pathfinder Discovery Networks, Rozemberczki et al. 2021) -- the smallest
+    way to use the dca / proximity values the reference computes on every contact and bridge and its model drops
+    (gcn_utills.py:319-443; gcn.py:71): the convolution stays GCNConv, only its operator is learned,
+
+        w_e = sigmoid(Linear(He, 1)(relu(Linear(D, He)(e_ij))))      A^_v[i, j] = deg_i^-1/2 w_e deg_j^-1/2,  deg_i = sum_row w_e
+
+        PDNConv(F->H)·BN·PReLU -> PDNConv(H->H)·BN·PReLU -> global_max_pool -> Linear(H->H)·BN·PReLU -> Linear(H->1)·BN·PReLU
+
+    ``PDN([ctx,] hidden_channels=64, edge_dim=2, edge_hidden=16, num_classes=1, seed=0)``; edge_dim 1 .. 8 (None raises: the
+    model is nothing without it), edge_hidden 1 .. 64 (what csrc/pdn.hip serves).  The model reads ``batch.e``
+    (``uses_edge_features``): inputs are (x, a, e, i), a DeviceBatch that carries e, or the batches of
+    DeviceDisjointLoader(DeviceDataset(..., edge_features=True)).  Self-loops are PyG's add_remaining_self_loops(fill_value=1):
+    a DeviceCSR / a DeviceBatch is used as stored, a stored loop being an entry like any other that goes through the MLP (the
+    reference's graphs carry every loop); a host adjacency gets the missing loops with weight exactly 1, outside the MLP and
+    without a gradient (_with_unit_self_loops; the flags ride on the batch as ``DeviceBatch.unit``).  Everything behind the
+    convolutions is ``GCN``'s (readout="attention" and norm="graph" included).  One device: ``comm`` is refused.
+
+    Each convolution has its own gate MLP and so its own operator pair (A^_v and, for the backward, a CSR of the transposed
+    pattern with the same values: A^_v is not symmetric even on a symmetric pattern), rebuilt every step.  Hot path per
+    convolution (pdn_forward / pdn_backward of gcnx/convs.py, the one place the sequence is written; gcnx.PDNConv runs the same
+    two functions): gcnx_pdn_operator (csrc/pdn.hip), then GCNConv's launches; backward GCNConv's launches on the transposed
+    operator, gcnx_gemm_dx -> dZ W^T where they did not leave it, gcnx_sddmm_csr -> dLoss/dv, gcnx_pdn_operator_bwd.  No
+    gradient flows to the edge features.
+
+    ``edge_weights(inputs)`` -> (w_1, w_2): the gates of both convolutions before normalisation, host arrays [nnz] in the
+    batch's CSR order (1 on added loops), from a forward in evaluation mode: a trained-in answer to "which contacts matter"
+    (``gcnx.explain.edge_layout`` gives the entries' (source, target) and graphs).
+
+    Weights: per ``conv{1,2}``, PyG's names ``.bias`` [H], ``.lin.weight`` [H, in], ``.mlp.0.weight`` [He, D], ``.mlp.0.bias``
+    [He], ``.mlp.2.weight`` [1, He], ``.mlp.2.bias`` [1] in that order (a module's own parameters before its children's), then
+    ``GCN``'s.  The order follows PyG's source, not a live module: prefer the named dicts.  Initialisation as PyG's
+    reset_parameters: glorot-uniform weights drawn lin, mlp.0, mlp.2 per convolution, zero biases, then the head."""
+
+    OPERATOR, KERNELS = "perm", "PDNConv"
+    MAX_EDGE_HIDDEN = 64
+    _KEYS = _conv_keys("w", "b", "z", "pa", "pb", "pc", "pd", "pw", "pr", "pt")
+    uses_edge_features = True
+    _pending_unit = None
+
+    def _init(self, ctx, hidden_channels=64, edge_dim=2, edge_hidden=16, num_classes=1, seed=0, comm=None):
+        self._one_device(comm)
+        if edge_dim is None:
+            raise NotImplementedError(f"{self._name}: edge_dim=None: the model learns its edge weights from the edge features; "
+                                      "edge_dim must be 1 .. 8")
+        self.edge_dim = self._check_edge_dim(edge_dim)
+        if not 1 <= int(edge_hidden) <= self.MAX_EDGE_HIDDEN:
+            raise NotImplementedError(f"{self._name}: edge_hidden={edge_hidden} must be 1 .. {self.MAX_EDGE_HIDDEN} (what the "
+                                      f"{self.KERNELS} kernels serve)")
+        self.edge_hidden = int(edge_hidden)
+        super()._init(ctx, hidden_channels, num_classes, seed, None)
+        conv = lambda k: (f"w{k}", f"b{k}", f"pa{k}", f"pb{k}", f"pc{k}", f"pd{k}", f"g{k}", f"be{k}", f"a{k}")
+        self.PARAM_ORDER = conv(1) + conv(2) + GCN.PARAM_ORDER[10:]
+        keys = lambda k: ((f"conv{k}.bias", f"b{k}", False), (f"conv{k}.lin.weight", f"w{k}", True),
+                          (f"conv{k}.mlp.0.weight", f"pa{k}", True), (f"conv{k}.mlp.0.bias", f"pb{k}", False),
+                          (f"conv{k}.mlp.2.weight", f"pc{k}", True), (f"conv{k}.mlp.2.bias", f"pd{k}", False))
+        self.TORCH_KEYS = keys(1) + keys(2) + GCN.TORCH_KEYS[4:]
+
+    def _shapes(self, f_in):
+        s = super()._shapes(f_in)
+        d, he = self.edge_dim, self.edge_hidden
+        for k in (1, 2):                        # stored [in, out]: mlp.0.weight [D, He], mlp.2.weight [He, 1]
+            s.update({f"pa{k}": (d, he), f"pb{k}": (he,), f"pc{k}": (he, 1), f"pd{k}": (1,)})
+        return s
+
+    def _initial(self, f_in, shapes, offs):
+        h, d, he, rng = self.hidden, self.edge_dim, self.edge_hidden, self._rng
+        init = {}
+        for k, f in ((1, f_in), (2, h)):        # PyG's reset_parameters per convolution: lin, mlp.0, mlp.2; every bias zero
+            init[f"w{k}"] = glorot_uniform(rng, f, h)
+            init[f"pa{k}"] = glorot_uniform(rng, d, he)
+            init[f"pc{k}"] = glorot_uniform(rng, he, 1)
+        init.update(self._head_initial(shapes))
+        return init
+
+    def _host_inputs(self, inputs):
+        """A host matrix gets the missing loops as unit entries; their flags wait in ``_pending_unit`` for ``_ensure``, which sees
+        the batch built from these inputs next.  A DeviceCSR goes in as stored."""
+        x, a, e, i = inputs
+        self._pending_unit = None
+        if not isinstance(a, D.DeviceCSR):
+            a, e, self._pending_unit = _with_unit_self_loops(a, e, np.asarray(x).shape[0])
+        return (x, a, e, i)
+
+    def _ensure(self, batch, sharded=False):
+        unit, self._pending_unit = self._pending_unit, None
+        if unit is not None and batch.unit is None and unit.size == batch.a.nnz:
+            batch.unit = self.ctx.to_device(unit, np.uint8)
+        bufs = super()._ensure(batch, sharded)
+        self._check_e(batch)
+        nnz = batch.a.nnz
+        if bufs.get("pdn_key") != (batch.n, batch.n_graphs, nnz):          # the entry buffers follow nnz as well as (n, b)
+            v, n, ne = self._views(), batch.n, max(nnz, 1)
+            for k in (1, 2):
+                for name in ("pw", "pv", "pvt"):
+                    bufs[f"{name}{k}"] = v(f"{name}{k}", 1, ne).flat(0, ne)
+                bufs[f"pr{k}"] = v(f"pr{k}", 1, n).flat(0, n)
+            bufs["pt1"], bufs["pt2"] = v("pt1", n, batch.f), v("pt2", n, self.hidden)
+            bufs["pg"] = v("pg", 1, ne).flat(0, ne)
+            ns = max(D.pdn_bwd_scratch_floats(self.ctx, n, nnz, self.edge_dim, self.edge_hidden), 4)
+            bufs["pdn_scratch"] = v("pdn_scratch", 1, ns).flat(0, ns)
+            bufs["pdn_key"], bufs["pdn_ops"] = (batch.n, batch.n_graphs, nnz), None
+        bufs["unit"] = batch.unit
+        return bufs
+
+    def _pair(self, a, bufs, k):
+        """Conv k's operator pair on the pattern ``a``: CSRs of the pattern and of its transposed pattern over the value
+        buffers gcnx_pdn_operator fills every step.  Built once per (batch, buffers); never the symmetric shortcut."""
+        ops = bufs["pdn_ops"]
+        if ops is None or ops[0] is not a:
+            rp_t, ci_t, _ = a.transpose_perm()
+            mk = lambda rp, ci, vals: D.DeviceCSR(self.ctx, a.n, a.nnz, rp, ci, vals, a.block_ptr, a.n_blocks, False, a.max_block_rows)
+            ops = bufs["pdn_ops"] = (a, {j: (mk(a.rowptr, a.colidx, bufs[f"pv{j}"]), mk(rp_t, ci_t, bufs[f"pvt{j}"])) for j in (1, 2)})
+        return ops[1][k]
+
+    def _conv_fwd(self, a, x, k, bufs, keep):
+        p = self.p
+        w, b, z, pa, pb, pc, pd, pw, pr, _ = self._KEYS[k]
+        a_v, a_vt = self._pair(a, bufs, k)
+        ok = convs.pdn_forward(self.ctx, a, a_v, a_vt, x, bufs["e"], bufs["unit"], p[pa], p[pb], p[pc], p[pd], p[w], p[b], bufs[pw],
+                               bufs[pr], bufs[z], bufs["h1"], s=bufs["s2"] if keep and k == 2 else None)
+        if k == 2:
+            bufs["s2_ok"] = ok
+
+    def _conv_bwd(self, a, x, k, dzk, bufs, dx):
+        p, g = self.p, self.g
+        w, b, _, pa, pb, pc, pd, pw, pr, pt = self._KEYS[k]
+        s = bufs["s2"] if dx is not None and bufs["s2_ok"] else None
+        convs.pdn_backward(self.ctx, a, self._pair(a, bufs, k)[1], x, bufs["e"], bufs["unit"], p[pa], p[pb], p[pc], p[pd], bufs[pw],
+                           bufs[pr], dzk, p[w], g[w], g[b], g[pa], g[pb], g[pc], g[pd], bufs["t"], bufs[pt], bufs["pg"],
+                           bufs["pdn_scratch"], dx, s)
+
+    def edge_weights(self, inputs):
+        """(w_1, w_2): the gates of conv1 and conv2 before normalisation, host arrays [nnz] in the batch's CSR order, from a
+        forward in evaluation mode.  An added unit loop reads 1."""
+        batch = self._as_batch(inputs)
+        bufs = self._ensure(batch)
+        self._forward(batch, bufs, "fwd")
+        nnz = batch.a.nnz
+        return bufs["pw1"].numpy()[:nnz].copy(), bufs["pw2"].numpy()[:nnz].copy()
 
 
 class PNA(GCN):

@@ -1351,6 +1351,43 @@ GCNX_API int gcnx_feat_mask_bwd(gcnx_ctx* ctx, const float* dxm, int64_t ldd, co
                                 int per_row, int64_t n, int32_t f, float c_size, float c_ent, float* dlogits, float* terms,
                                 float* scratch);
 
+/* ---- GCNConv on edge weights learned from the edge features: PyG's PDNConv (csrc/pdn.hip) ----
+ * The reference computes dca / proximity values on every contact and bridge and its model drops them (gcn.py:71); here a
+ * two-layer MLP with a sigmoid turns them into the edge weights of GCNConv's operator.  CSR rows are targets; entry e = (i <- j)
+ * has the features x_e = e[e * lde .. + d).  With W1 [d, he] (row-major), b1 [he], w2 [he], b2 [1], all DEVICE pointers:
+ *     z_e = x_e W1 + b1     h_e = relu(z_e)     s_e = <w2, h_e> + b2
+ *     w_e = 1 (exactly; x_e is not read) where unit[e] != 0, else sigmoid(s_e)   (gcnx_edge_mask_fwd's sigmoid: 1 from s = 17 on)
+ *     deg_i = sum of w_e over row i     r_i = deg_i^-1/2, 0 for a row without entries     v_e = r_i w_e r_j
+ * gcn.py:71 -- 1 if d in 1 .. 8 and he in 1 .. 64 (what the two entry points below serve), else 0. */
+GCNX_API int gcnx_pdn_ok(int32_t d, int32_t he);
+/* gcn.py:71 -- writes w_out [nnz], r_out [n], vals_out [nnz] = v and vals_t_out[p] = v[perm_t[p]] (the values on the transposed
+ * pattern, perm_t from gcnx_csr_transpose_perm; evaluated from the same expression: the same bits; both NULL or both given).
+ * unit [nnz] bytes or NULL (no unit entries).  e may have any leading dimension lde >= d and any alignment.  Two launches (a group
+ * of 16 lanes per row: gates and degree; a thread per entry: values), no synchronisation, no atomics: a row's degree is added in one fixed
+ * order (fp64 lane sums, then the lanes), two calls leave the same bits.  Finite inputs give finite outputs (logits of +-40
+ * included).  n == 0 or nnz == 0: GCNX_OK, nothing launched.  GCNX_ERR_INVALID: gcnx_pdn_ok fails, a NULL operand, lde < d. */
+GCNX_API int gcnx_pdn_operator(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, int32_t n, int32_t nnz, const float* e,
+                               int64_t lde, int32_t d, const float* w1, const float* b1, const float* w2, const float* b2, int32_t he,
+                               const uint8_t* unit, const int32_t* perm_t, float* w_out, float* r_out, float* vals_out,
+                               float* vals_t_out);
+/* gcn.py:71 -- floats of `scratch` for gcnx_pdn_operator_bwd: one per entry (rounded up to 4) and at most 256 parts of
+ * d he + 2 he + 1 floats (one part per 64 entries below that).  0 where gcnx_pdn_ok fails.  Answers without a context. */
+GCNX_API int64_t gcnx_pdn_bwd_scratch_floats(int64_t n, int64_t nnz, int32_t d, int32_t he);
+/* gcn.py:71 -- the gradient of the four MLP tensors from g[e] = dLoss/dv_e in forward entry order (gcnx_sddmm_csr), w and r as
+ * gcnx_pdn_operator left them, (rowptr_t, colidx_t, perm_t) the transposed pattern of gcnx_csr_transpose_perm:
+ *     c_e = g_e w_e     q_i = sum_{e in row i} c_e r_col(e) + sum_{p in row i of the transposed pattern} c_{perm_t[p]} r_{colidx_t[p]}
+ *     dw_e = g_e r_i r_j - 1/2 r_i^3 q_i     ds_e = dw_e w_e (1 - w_e), 0 where unit[e]   (1 - w as exp(-s) w for s >= 0)
+ *     dw2 = sum ds_e h_e    db2 = sum ds_e    dz_e = ds_e w2 * [z_e > 0]    dW1 = sum x_e (x) dz_e    db1 = sum dz_e
+ * z_e, h_e and s_e are recomputed from e by the forward's own expression (the same bits: the same side of every ReLU).  dw1
+ * [d, he], db1 [he], dw2 [he], db2 [1] are written, not accumulated.  Three launches: a group of 16 lanes per row (q_i, ds into scratch), at
+ * most 256 workgroups of per-workgroup parts, one workgroup that folds them; fp64 accumulators, a fixed order, no atomics: two
+ * calls leave the same bits.  No gradient flows to e.  n == 0 or nnz == 0: the four gradients are zeroed. */
+GCNX_API int gcnx_pdn_operator_bwd(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, const int32_t* rowptr_t,
+                                   const int32_t* colidx_t, const int32_t* perm_t, int32_t n, int32_t nnz, const float* e, int64_t lde,
+                                   int32_t d, const float* w1, const float* b1, const float* w2, const float* b2, int32_t he,
+                                   const uint8_t* unit, const float* w, const float* r, const float* g, float* dw1, float* db1,
+                                   float* dw2, float* db2, float* scratch);
+
 /* ---- aggregation with bf16 features ("fp32 and bf16 both reported") ----
  * out[t, :] = bf16(act(sum_e vals[e] * h[colidx[e], :] + bias)): GCNConv.call's / GeneralConv's aggregation (gcn.py:334) on
  * activations stored as bf16 (uint16_t bit patterns), fp32 accumulation, round-to-nearest-even on the way out; bias fp32
