@@ -1,5 +1,5 @@
 """The launch sequences of the convolutions that a layer (gcnx.layers) and a model (gcnx.models) both run: PNAConv, GATConv,
-GATv2Conv, ResGatedGraphConv, TransformerConv, GINEConv and PDNConv (with the GCNConv sequence it is built on).  This is the one
+GATv2Conv, ResGatedGraphConv, TransformerConv, GINEConv, PDNConv (with the GCNConv sequence it is built on) and APPNPConv.  This is the one
 place they are written down.
 
 One forward and one backward function per convolution, plain functions over operands: ``ctx``, the pattern, the operands, the
@@ -232,3 +232,22 @@ def pdn_backward(ctx, a, a_vt, x, e, unit, w_1, b_1, w_2, b_2, gate, r, dz, w, g
         D.gemm_dx(ctx, dz, w, tl)                                                          # dZ W^T
     D.sddmm(ctx, a, tl, x, gv)                                                             # G = dLoss/dv on the forward pattern
     D.pdn_operator_bwd(ctx, a, e, w_1, b_1, w_2, b_2, gate, r, gv, g_w_1, g_b_1, g_w_2, g_b_2, scratch, unit=unit)
+
+
+# ---- APPNPConv ---------------------------------------------------------------------------------------------------------------
+def appnp_forward(ctx, a, x, w, bias, h, out, k, alpha, scratch, col_block=0):
+    """h = x W + bias, then out = the k hops z <- (1 - alpha) A z + alpha h from z = h.  scratch: appnp_scratch_floats (read
+    by the streamed route only).  col_block: appnp_propagate's (0: the library's route, -1: streamed)."""
+    D.gemm(ctx, x, w, bias, h)
+    D.appnp_propagate(ctx, a, h, out, k, alpha, scratch=scratch, col_block=col_block)
+
+
+def appnp_backward(ctx, a_t, x, dz, w, g_w, g_bias, dh, k, alpha, scratch, dx, col_block=0):
+    """From dz: dh = P^T dz (the same hops on the transposed operator a_t), the bias gradient (its column sums), dW = x^T dh
+    and, with dx, dx = dh W^T."""
+    D.appnp_propagate(ctx, a_t, dz, dh, k, alpha, scratch=scratch, col_block=col_block)
+    if g_bias is not None:
+        D.act_bias_grad(ctx, dh, None, dh, None, db=g_bias)                                # column sums of dH
+    D.gemm_dw(ctx, x, dh, g_w)                                                             # dW = x^T dH
+    if dx is not None:
+        D.gemm_dx(ctx, dh, w, dx)                                                          # dx = dH W^T

@@ -824,6 +824,31 @@ def sage_conv(ctx, a, x, w_nb, w_root, bias, out, s=None, w_transposed=False):
     return out
 
 
+def appnp_resident_ok(ctx, max_graph_rows, f, ldx=None):
+    """True if the one-launch route of appnp_propagate serves a batch whose tallest graph has this many rows
+    (gcnx_appnp_resident_ok)."""
+    return bool(ctx.lib.gcnx_appnp_resident_ok(int(max_graph_rows), int(f), int(ldx if ldx is not None else f)))
+
+
+def appnp_scratch_floats(ctx, n, f):
+    """Floats of ``scratch`` for the streamed route of appnp_propagate with k >= 2 (gcnx_appnp_scratch_floats)."""
+    return int(ctx.lib.gcnx_appnp_scratch_floats(int(n), int(f)))
+
+
+def appnp_propagate(ctx, a, x, out, k, alpha, scratch=None, col_block=0):
+    """out = z^k, z^0 = x, z^{j+1} = (1 - alpha) A z^j + alpha x (gcnx_appnp_propagate).  The graphs of ``a`` (block_ptr, n_blocks,
+    max_block_rows) let the library keep each graph's rows in LDS across all k hops; without them, or with col_block=-1, k
+    launches alternate between out and scratch (appnp_scratch_floats).  col_block > 0 forces the one-launch route with that
+    many columns per workgroup.  The backward is the same call on ``a.transpose()`` with x = dz."""
+    n, f = x.shape
+    assert a.n == n and out.shape == (n, f) and (scratch is None or scratch.size >= appnp_scratch_floats(ctx, n, f))
+    has_blocks = a.block_ptr is not None and a.n_blocks > 0
+    ctx._ck(ctx.lib.gcnx_appnp_propagate(ctx.h, a.rowptr.ptr, a.colidx.ptr, _p(a.vals), a.block_ptr.ptr if has_blocks else None,
+                                         a.n_blocks if has_blocks else 0, a.max_block_rows if has_blocks else 0, _p(x), x.ld, n, f,
+                                         int(k), float(alpha), int(col_block), _p(out), out.ld, _p(scratch)))
+    return out
+
+
 def gin_conv_ok(ctx, n, k0, k1, k2=0, ldx=None):
     """True if gin_conv serves these shapes (gcnx_gin_conv_ok); k2 = 0: the single-stage form."""
     return bool(ctx.lib.gcnx_gin_conv_ok(int(n), int(k0), int(k1), int(k2), int(ldx if ldx is not None else k0)))

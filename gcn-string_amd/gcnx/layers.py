@@ -271,6 +271,70 @@ class SAGEConv(Layer):
         return dx
 
 
+class APPNPConv(Layer):
+    """spektral.layers.APPNPConv, personalised-PageRank propagation behind a Dense layer (PyG: Linear + APPNP(K, alpha)):
+
+        h = x W + b        z^0 = h        z^{k+1} = (1 - alpha) A^ z^k + alpha h        out = z^propagations
+
+    ``APPNPConv(channels, alpha=0.2, propagations=1, mlp_hidden=None, dropout_rate=0.0, activation=None, use_bias=True)``, called
+    as ``layer([x, a_hat])`` with ``a_hat`` the gcn_filter operator (``APPNPConv.preprocess`` = ``GCNConv.preprocess``, or
+    ``DeviceCSR.gcn_norm``).  The signature follows Spektral's source from memory: Spektral could not be installed to confirm
+    it against a live layer.  ``mlp_hidden`` other than None (hidden Dense layers ahead of the propagation) and
+    ``dropout_rate != 0`` raise NotImplementedError; ``activation`` must be None / "linear".  Parameters ``kernel``
+    [in, channels] (glorot_uniform) and ``bias`` (zeros), Keras' Dense defaults.
+
+    Launches: gcnx_gemm, then gcnx_appnp_propagate (csrc/appnp.hip): one launch that keeps every graph's rows in LDS across all
+    hops where the operator carries its graphs (a disjoint batch), the width is a multiple of 4 and there are enough hops to earn
+    the staging back (3; 2 on graphs of up to 256 rows), otherwise one launch per hop.  Nothing is kept for the backward: it is the same propagation on the transposed operator applied to dy, then the
+    Dense layer's gradients.  ``col_block``: gcnx_appnp_propagate's (0: the library's route, -1: one launch per hop)."""
+
+    def __init__(self, channels, alpha=0.2, propagations=1, mlp_hidden=None, dropout_rate=0.0, activation=None, use_bias=True,
+                 col_block=0, **kw):
+        super().__init__(**kw)
+        if mlp_hidden is not None:
+            raise NotImplementedError(f"APPNPConv mlp_hidden={mlp_hidden!r}: only None (one Dense layer ahead of the propagation)")
+        if float(dropout_rate) != 0.0:
+            raise NotImplementedError(f"APPNPConv dropout_rate={dropout_rate!r}: only 0 (no dropout inside the layer)")
+        if activation not in (None, "linear"):
+            raise NotImplementedError(f"APPNPConv activation {activation!r}: the layer is linear (follow it with BatchNorm1d / PReLU)")
+        if isinstance(propagations, bool) or int(propagations) != propagations or not 0 <= int(propagations) <= 64:
+            raise NotImplementedError(f"APPNPConv propagations={propagations!r} must be an int in 0 .. 64 (what gcnx_appnp_propagate serves)")
+        if not 0.0 <= float(alpha) <= 1.0:
+            raise ValueError(f"APPNPConv alpha={alpha!r} must be in [0, 1]")
+        self.channels, self.alpha, self.propagations = int(channels), float(alpha), int(propagations)
+        self.use_bias, self.activation, self.col_block = bool(use_bias), activation, int(col_block)
+
+    preprocess = staticmethod(GCNConv.preprocess)
+
+    def _param_spec(self, in_dim):
+        spec = [("kernel", (in_dim, self.channels), glorot_uniform(self._rng, in_dim, self.channels))]
+        if self.use_bias:
+            spec.append(("bias", (self.channels,), np.zeros(self.channels, np.float32)))
+        return spec
+
+    def _scratch_buf(self, n):
+        return self._buf("scratch", (max(D.appnp_scratch_floats(self.ctx, n, self.channels), 4),))
+
+    def call(self, inputs, out=None):
+        x, a = inputs
+        if not self.built:
+            self.build(x.ctx, x.shape[1])
+        n, c, p = x.shape[0], self.channels, self.params
+        y = out if out is not None else self._buf("y", (n, c))
+        convs.appnp_forward(self.ctx, a, x, p["kernel"], p.get("bias"), self._buf("h", (n, c)), y, self.propagations, self.alpha,
+                            self._scratch_buf(n), col_block=self.col_block)
+        self._saved = (x, a)
+        return y
+
+    def backward(self, dy, need_dx=True):
+        x, a = self._saved
+        p, g = self.params, self.grads
+        dx = self._buf("dx", x.shape) if need_dx else None
+        convs.appnp_backward(self.ctx, a.transpose(), x, dy, p["kernel"], g["kernel"], g.get("bias"), self._buf("h", dy.shape),
+                             self.propagations, self.alpha, self._scratch_buf(x.shape[0]), dx, col_block=self.col_block)
+        return dx
+
+
 class GINConv(Layer):
     """torch_geometric.nn.GINConv(Sequential(Linear(in, mlp_hidden), ReLU(), Linear(mlp_hidden, channels)), eps, train_eps) --
     spektral.layers.GINConv(channels, mlp_hidden=[mlp_hidden]) is the same layer -- for the slot the reference's author left

@@ -2453,6 +2453,67 @@ class PDN(GCN):
         return bufs["pw1"].numpy()[:nnz].copy(), bufs["pw2"].numpy()[:nnz].copy()
 
 
+class APPNP(GCN):
+    """``GCN`` with each GCNConv replaced by ``Linear`` + PyG's ``APPNP(K, alpha)`` (Gasteiger et al. 2019, "Predict then
+    propagate"; Spektral's APPNPConv), the long-range layer for the slot the reference's author left open
+    (gcn_utills.py:804-806): two one-hop convolutions see a residue's 2-hop neighbourhood, K hops of personalised PageRank
+    reach the inter-chain bridges from most of a chain.
+
+        Linear(F->H)·APPNP(K, alpha)·BN·PReLU -> Linear(H->H)·APPNP(K, alpha)·BN·PReLU -> global_max_pool -> the head of ``GCN``
+
+        APPNP(K, alpha):  z^0 = h      z^{k+1} = (1 - alpha) A^ z^k + alpha h      A^ = GCNConv's operator (gcn_norm, self-loops)
+
+    ``APPNP([ctx,] hidden_channels=64, K=10, alpha=0.1, num_classes=1, seed=0, comm=None, readout=, norm=)``: K an int in
+    0 .. 64 (0: a node MLP), alpha in [0, 1].  The propagation has no parameters and keeps nothing for the backward, which is
+    the same propagation on A^^T.  Everything else is ``GCN``'s: the operator, BN·PReLU, the pool pair, the head,
+    readout="attention", norm="graph", ``fit``, and sync-BN over shards (``comm=``): the propagation never crosses a graph, so
+    a shard's rows are all it needs.
+
+    Hot path per layer (appnp_forward / appnp_backward of gcnx/convs.py; gcnx.APPNPConv runs the same two functions): gcnx_gemm,
+    then gcnx_appnp_propagate (csrc/appnp.hip) -- one launch that keeps each graph's rows in LDS across all K hops, or K launches
+    where the library streams (K below 3 -- below 2 on graphs of up to 256 rows --, hidden_channels not a multiple of 4, a graph too
+    tall for LDS, a batch that does not know its tallest graph); backward gcnx_appnp_propagate on
+    the transposed operator, then the Linear's gradients.  GCNX_APPNP_RESIDENT=0 (read at construction) streams always.
+
+    Weights: torch key names ``lin{1,2}.weight`` ([out, in], as torch; stored [in, out] here), ``lin{1,2}.bias``, then
+    ``GCN``'s.  Initialisation as torch's Linear, U(+-1/sqrt(fan_in)), drawn lin1.weight, lin1.bias, lin2.weight, lin2.bias,
+    then the head.  The key names are this model's own (PyG's APPNP has no parameters; the Linears are named as a module that
+    declares them would): prefer the named dicts."""
+
+    TORCH_KEYS = (("lin1.weight", "w1", True), ("lin1.bias", "b1", False),
+                  ("lin2.weight", "w2", True), ("lin2.bias", "b2", False)) + GCN.TORCH_KEYS[4:]
+    PROBE_KEY = "lin1.weight"
+    OPERATOR, SELF_LOOPS, KERNELS = "gcn", True, "APPNP"
+    MAX_K = 64
+
+    def _init(self, ctx, hidden_channels=64, K=10, alpha=0.1, num_classes=1, seed=0, comm=None):
+        if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or not 0 <= int(K) <= self.MAX_K:
+            raise NotImplementedError(f"{self._name}: K={K!r} must be an int in 0 .. {self.MAX_K} (what the {self.KERNELS} kernels serve)")
+        if not 0.0 <= float(alpha) <= 1.0:
+            raise ValueError(f"{self._name}: alpha={alpha!r} must be in [0, 1]")
+        self.K, self.alpha = int(K), float(alpha)
+        super()._init(ctx, hidden_channels, num_classes, seed, comm)
+        self._col_block = 0 if os.environ.get("GCNX_APPNP_RESIDENT", "1") != "0" else -1    # knob, read once
+
+    def _initial(self, f_in, shapes, offs):
+        h, u = self.hidden, self._uniform
+        return {"w1": u(f_in, f_in, h), "b1": u(f_in, h), "w2": u(h, h, h), "b2": u(h, h), **self._head_initial(shapes)}
+
+    def _conv_fwd(self, a_hat, x, k, bufs, keep):
+        """z_k = P (x W_k + b_k): the Linear into bufs["h1"], then the K hops."""
+        p = self.p
+        w, b, z = self._KEYS[k]
+        convs.appnp_forward(self.ctx, a_hat, x, p[w], p[b], bufs["h1"], bufs[z], self.K, self.alpha, bufs["s2"],
+                            col_block=self._col_block)
+
+    def _conv_bwd(self, a_t, x, k, dzk, bufs, dx):
+        """dZ_k -> dH = P^T dZ_k in bufs["t"], the Linear's gradients and, with dx, dx = dH W^T."""
+        p, g = self.p, self.g
+        w, b, _ = self._KEYS[k]
+        convs.appnp_backward(self.ctx, a_t, x, dzk, p[w], g[w], g[b], bufs["t"], self.K, self.alpha, bufs["s2"], dx,
+                             col_block=self._col_block)
+
+
 class PNA(GCN):
     """``GCN`` with its two GCNConv layers replaced by PyG's PNAConv(aggregators=['mean', 'min', 'max', 'std'],
     scalers=['identity', 'amplification', 'attenuation'], deg, towers=1, pre_layers=1, post_layers=1, divide_input=False),

@@ -1388,6 +1388,41 @@ GCNX_API int gcnx_pdn_operator_bwd(gcnx_ctx* ctx, const int32_t* rowptr, const i
                                    const uint8_t* unit, const float* w, const float* r, const float* g, float* dw1, float* db1,
                                    float* dw2, float* db2, float* scratch);
 
+/* ---- APPNP: K hops of personalised-PageRank propagation (csrc/appnp.hip) ----
+ * Spektral's APPNPConv and PyG's APPNP(K, alpha), the long-range layer for the slot the reference's author left open
+ * (gcn_utills.py:804-806): a Linear (gcnx_gemm) followed by k parameter-free hops on the GCN operator (gcn.py:8's gcn_filter),
+ *     z^0 = x      z^{j+1}[i, :] = (1 - alpha) * sum_{e in row i, CSR order} vals[e] * z^j[colidx[e], :] + alpha * x[i, :]      out = z^k
+ * Per element: one fmaf chain over the row's entries in CSR order from +0, then fmaf(alpha, x, (1 - alpha) * acc) with
+ * 1 - alpha rounded once.  Both routes below and every column block evaluate exactly that, so they leave the same bits.
+ * The backward is the same call: P = M^k + alpha sum_{j<k} M^j with M = (1 - alpha) A, so P^T is the same recursion on A^T:
+ * pass the transposed operator and x = dz, and out receives dLoss/dx.  Nothing is kept for it.
+ *
+ * gcn_utills.py:804-806 -- 1 if the one-launch (resident) route serves a batch whose tallest graph has max_graph_rows rows:
+ * max_graph_rows > 0, f and ldx multiples of 4 with ldx >= f, and two buffers of max_graph_rows x 4 floats plus the graph's
+ * row pointers within 128 KiB of LDS (graphs of up to 3640 rows).  Operands off a 16-byte boundary take the streamed route. */
+GCNX_API int gcnx_appnp_resident_ok(int64_t max_graph_rows, int32_t f, int64_t ldx);
+/* gcn_utills.py:804-806 -- floats of `scratch` for the streamed route with k >= 2: n * f.  Answers without a context. */
+GCNX_API int64_t gcnx_appnp_scratch_floats(int64_t n, int32_t f);
+/* gcn.py:8 -- out [n, f] (ldo) = z^k from x [n, f] (ldx); vals NULL: ones.  graph_ptr [b + 1] (may be NULL) marks the diagonal
+ * blocks of a block-diagonal operator (a disjoint batch), max_graph_rows the rows of its tallest graph (0: unknown).
+ * Resident route (one launch): a workgroup per (graph, block of col_block columns) keeps the graph's slice in LDS across all k
+ * hops, one workgroup barrier per hop; an entry whose column lies outside its graph's rows contributes nothing (no access is
+ * out of range; the result for such input is unspecified); a graph with more than max_graph_rows rows is left untouched
+ * (the rule of gcnx_topk_select).  Streamed route (k launches of a one-hop gather): any n, f, leading dimension and
+ * alignment; it alternates between out and scratch (gcnx_appnp_scratch_floats; may be NULL for k <= 1) so that hop k lands in
+ * out.  col_block 0: the library's choice -- resident where graph_ptr is given, gcnx_appnp_resident_ok holds, x and out are
+ * 16-byte aligned with ldo % 4 == 0 and k >= 3 (k >= 2 where max_graph_rows <= 256: fewer hops do not earn the prologue back),
+ * in the widest block of {f, 64, 32, 16, 8, 4} columns that fits, narrowed while the narrower block's workgroups still fit one
+ * round of the CUs and then while fewer than 16 CSR entries per row can be staged in LDS; otherwise streamed.  col_block > 0: the resident route with that block, GCNX_ERR_UNSUPPORTED with
+ * nothing launched where it is not served (not a multiple of 4, wider than f or 256, too tall for LDS, or any condition above).
+ * col_block -1: streamed.  k == 0 copies x.  n == 0, f == 0 or b == 0 (with graph_ptr): GCNX_OK, nothing launched.
+ * GCNX_ERR_INVALID: k outside 0 .. 64, alpha outside [0, 1], ldx or ldo < f, out overlapping x or scratch (or scratch
+ * overlapping x), the streamed route with k >= 2 and scratch NULL.  No atomics, no read-back: capture-safe, and two calls
+ * leave the same bits. */
+GCNX_API int gcnx_appnp_propagate(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, const float* vals,
+                                  const int32_t* graph_ptr, int32_t b, int32_t max_graph_rows, const float* x, int64_t ldx, int32_t n,
+                                  int32_t f, int32_t k, float alpha, int32_t col_block, float* out, int64_t ldo, float* scratch);
+
 /* ---- aggregation with bf16 features ("fp32 and bf16 both reported") ----
  * out[t, :] = bf16(act(sum_e vals[e] * h[colidx[e], :] + bias)): GCNConv.call's / GeneralConv's aggregation (gcn.py:334) on
  * activations stored as bf16 (uint16_t bit patterns), fp32 accumulation, round-to-nearest-even on the way out; bias fp32
