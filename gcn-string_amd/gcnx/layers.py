@@ -29,6 +29,7 @@ import numpy as np
 from . import convs
 from . import device as D
 from .convs import pna_backward, pna_forward     # (the models and the tests import the two from here)
+from .params import block_views, from_pyg, join_blocks, to_pyg
 
 _FUSED_KNOB = os.environ.get("GCNX_FUSED", "1") != "0"     # tuning knob, read once at import (diagnostics)
 
@@ -42,6 +43,15 @@ class Layer:
     """Keras-like lazy build: parameters are created on the first call, when the input width
     is known.  ``storage`` lets a model place all parameters in one flat buffer."""
 
+    ALIGN = 1           # floats between the starts of two tensors in a caller's store (4: every tensor on a 16-byte boundary)
+    OWN_ALIGN = 1       # the same where the layer allocates its own storage
+    # {attribute: its blocks}: the stacked tensors.  One stored tensor each, kept as ``self.<attribute>`` (its gradient as
+    # ``<attribute>_grad``), allocated where _stored_spec lists its first block and initialised from the blocks' initial values
+    # side by side; ``params`` / ``grads`` hold the named blocks as views.  A block is a name of _stored_spec (skipped where the
+    # spec has none) or an int: that many unnamed zeros.  This table is the only statement of the block order.
+    STACKS = {}
+    LEADING_AXIS = ()   # the names that carry a leading axis of 1 in PyG ([1, heads, channels], [1, 3 heads channels])
+
     def __init__(self, ctx=None, seed=None):
         self.ctx = ctx
         self.built = False
@@ -54,24 +64,95 @@ class Layer:
     def _param_spec(self, in_dim):
         return []
 
+    def _stored_spec(self, in_dim):
+        """_param_spec under the names and in the layouts of ``params`` (a layer whose _param_spec speaks PyG's converts here)."""
+        return self._param_spec(in_dim)
+
+    def _storage(self, in_dim):
+        """(the stored spec, [(attribute or None, [(block name or None, initial value)])] in storage order)."""
+        spec = [(name, np.asarray(init, np.float32).reshape(shape)) for name, shape, init in self._stored_spec(in_dim)]
+        init, stored, seen = dict(spec), [], set()
+        owner = {b: attr for attr, blocks in self.STACKS.items() for b in blocks if b in init}
+        for name, v in spec:
+            attr = owner.get(name)
+            if attr is None:
+                stored.append((None, [(name, v)]))
+            elif attr not in seen:
+                seen.add(attr)
+                stored.append((attr, [(None, np.zeros(b, np.float32)) if isinstance(b, int) else (b, init[b])
+                                      for b in self.STACKS[attr] if isinstance(b, int) or b in init]))
+        return spec, stored
+
     def n_params(self, in_dim):
-        return sum(int(np.prod(s)) for _, s, _ in self._param_spec(in_dim))
+        """Floats of storage in a caller's store."""
+        return sum(-(-sum(v.size for _, v in blocks) // self.ALIGN) * self.ALIGN for _, blocks in self._storage(in_dim)[1])
 
     def build(self, ctx, in_dim, p_store=None, g_store=None, offset=0):
         self.ctx = ctx
-        spec = self._param_spec(in_dim)
-        total = sum(int(np.prod(s)) for _, s, _ in spec)
+        spec, stored = self._storage(in_dim)
+        align = self.ALIGN if p_store is not None else self.OWN_ALIGN
+        pad = lambda n: -(-n // align) * align
         if p_store is None:
-            p_store, g_store, offset = ctx.zeros(max(total, 1)), ctx.zeros(max(total, 1)), 0
-        off = offset
-        for name, shape, init in spec:
-            n = int(np.prod(shape))
-            self.params[name] = p_store.flat(off, n, shape)
-            self.grads[name] = g_store.flat(off, n, shape)
-            self.params[name].copy_from_host(init)
-            off += n
+            total = max(sum(pad(sum(v.size for _, v in blocks)) for _, blocks in stored), 1)
+            p_store, g_store, offset = ctx.zeros(total), ctx.zeros(total), 0
+        off, views = offset, {}
+        for attr in self.STACKS:                            # (a stack none of whose blocks is in the spec stays None)
+            setattr(self, attr, None)
+            setattr(self, attr + "_grad", None)
+        for attr, blocks in stored:
+            init = np.concatenate([v for _, v in blocks], axis=-1)
+            pv, gv = p_store.flat(off, init.size, init.shape), g_store.flat(off, init.size, init.shape)
+            pv.copy_from_host(init)
+            off += pad(init.size)
+            if attr is None:
+                views[blocks[0][0]] = (pv, gv)
+                continue
+            setattr(self, attr, pv)
+            setattr(self, attr + "_grad", gv)
+            widths = [(name, v.shape[-1]) for name, v in blocks]
+            pb, gb = block_views(pv, widths), block_views(gv, widths)
+            views.update({name: (pb[name], gb[name]) for name in pb})
+        for name, _ in spec:                                # ``params`` / ``grads`` list the spec's names in the spec's order
+            self.params[name], self.grads[name] = views[name]
         self.in_dim, self.built = in_dim, True
         return off
+
+    def _load(self, host):
+        """{name in ``params``: array in the stored layout} into the storage; the blocks of a stacked tensor go up as one."""
+        host = dict(host)
+        for attr, blocks in self.STACKS.items():
+            blocks = [b for b in blocks if isinstance(b, int) or b in host]
+            if any(isinstance(b, str) for b in blocks):
+                getattr(self, attr).copy_from_host(join_blocks(host, blocks))
+        for k, v in host.items():
+            self.params[k].copy_from_host(v)
+
+    def _pyg_keys(self, t):
+        """(PyG name, name in t, transposed) of a layer whose names are PyG's: a .weight is [out, in] there, [in, out] here."""
+        return [(k, k, k.endswith(".weight")) for k in t], [k for k in self.LEADING_AXIS if k in t]
+
+    def _pyg(self, t):
+        """{PyG name: array in PyG's layout} of ``params`` or ``grads``."""
+        return to_pyg(t, *self._pyg_keys(t))
+
+    def _edge_inputs(self, inputs, optional=True, refuse_bipartite=False):
+        """(x, a, e) of a call's [x, a] or [x, a, e], checked against the layer's edge_dim: e is [nnz, edge_dim], one row per
+        stored entry of a, and is there exactly when the layer was built with edge_dim.  ``optional=False``: a layer that
+        always reads e.  ``refuse_bipartite``: for PyG's layers that take an (x_source, x_target) pair."""
+        name, d = type(self).__name__, self.edge_dim
+        if len(inputs) not in ((2, 3) if optional else (3,)):
+            raise ValueError(f"{name} takes [x, a] or [x, a, e]" if optional else f"{name}(edge_dim={d}) takes [x, a, e]")
+        x, a = inputs[:2]
+        if refuse_bipartite and isinstance(x, (tuple, list)):
+            raise NotImplementedError(f"{name}: bipartite inputs (x_source, x_target) have no kernel")
+        e = inputs[2] if len(inputs) == 3 else None
+        if e is not None and d is None:
+            raise ValueError(f"{name}: edge features given to a layer built without edge_dim")
+        if e is None and d is not None:
+            raise ValueError(f"{name}(edge_dim={d}) takes [x, a, e]")
+        if e is not None and tuple(e.shape) != (a.nnz, d):
+            raise ValueError(f"{name}(edge_dim={d}): e must be [{a.nnz}, {d}] (one row per stored entry), got {list(e.shape)}")
+        return x, a, e
 
     def _buf(self, key, shape, dtype=np.float32):
         b = self._scratch.get(key)
@@ -84,8 +165,8 @@ class Layer:
         return [self.params[k].numpy() for k in self.params]
 
     def set_weights(self, weights):
-        for k, w in zip(self.params, weights):
-            self.params[k].copy_from_host(w)
+        """Arrays in the order and the stored layouts of ``params``."""
+        self._load(dict(zip(self.params, weights)))
 
     @property
     def trainable_variables(self):
@@ -93,6 +174,12 @@ class Layer:
 
     def __call__(self, inputs, **kw):
         return self.call(inputs, **kw)
+
+
+def _unweighted(a):
+    """The stored pattern of a DeviceCSR, unweighted: no loop added or removed, values ignored (the ``preprocess`` of the layers
+    that use the adjacency exactly as stored)."""
+    return a.unweighted()
 
 
 class GCNConv(Layer):
@@ -369,10 +456,8 @@ class GINConv(Layer):
         self.fused = bool(fused)
         self._eps_dev = None
 
-    @staticmethod
-    def preprocess(a):
-        """The stored pattern of a DeviceCSR, unweighted."""
-        return a.unweighted()
+    OWN_ALIGN = 4                               # own storage: every tensor on a 4-float boundary (gcnx_gin_conv's weights)
+    preprocess = staticmethod(_unweighted)
 
     def _param_spec(self, in_dim):
         c, m = self.channels, self.mlp_hidden
@@ -387,21 +472,7 @@ class GINConv(Layer):
         return spec
 
     def build(self, ctx, in_dim, p_store=None, g_store=None, offset=0):
-        if p_store is not None:
-            off = super().build(ctx, in_dim, p_store, g_store, offset)
-        else:                                   # own storage: every tensor on a 4-float boundary (gcnx_gin_conv's weights)
-            self.ctx = ctx
-            spec = self._param_spec(in_dim)
-            pad = lambda shape: -(-int(np.prod(shape)) // 4) * 4
-            total = sum(pad(s) for _, s, _ in spec)
-            p_store, g_store, off = ctx.zeros(total), ctx.zeros(total), 0
-            for name, shape, init in spec:
-                n = int(np.prod(shape))
-                self.params[name] = p_store.flat(off, n, shape)
-                self.grads[name] = g_store.flat(off, n, shape)
-                self.params[name].copy_from_host(init)
-                off += pad(shape)
-            self.in_dim, self.built = in_dim, True
+        off = super().build(ctx, in_dim, p_store, g_store, offset)
         if not self.train_eps and self.eps != 0.0:
             self._eps_dev = ctx.to_device(np.full(1, self.eps, np.float32))
         return off
@@ -503,12 +574,7 @@ class GINEConv(GINConv):
                 and all(o.ld % 4 == 0 for o in others))
 
     def call(self, inputs, out=None):
-        if len(inputs) != 3:
-            raise ValueError(f"GINEConv(edge_dim={self.edge_dim}) takes [x, a, e]")
-        x, a, e = inputs
-        if tuple(e.shape) != (a.nnz, self.edge_dim):
-            raise ValueError(f"GINEConv(edge_dim={self.edge_dim}): e must be [{a.nnz}, {self.edge_dim}] (one row per stored entry), "
-                             f"got {list(e.shape)}")
+        x, a, e = self._edge_inputs(inputs, optional=False)
         if not self.built:
             self.build(x.ctx, x.shape[1])
         ctx, n, c, m, p = self.ctx, x.shape[0], self.channels, self.mlp_hidden, self.params
@@ -694,10 +760,8 @@ class PNAConv(Layer):
         self.channels, self.use_bias = int(channels), bool(use_bias)
         self.avg_deg_log = pna_delta("PNAConv", deg, avg_deg_log)
 
-    @staticmethod
-    def preprocess(a):
-        """The stored pattern of a DeviceCSR, unweighted."""
-        return a.unweighted()
+    OWN_ALIGN = 4                               # own storage: every tensor on a 4-float boundary (float4 lanes, the dW launches)
+    preprocess = staticmethod(_unweighted)
 
     def _param_spec(self, in_dim):
         f, h = in_dim, self.channels
@@ -708,23 +772,6 @@ class PNAConv(Layer):
             if self.use_bias:
                 spec.append((name + ".bias", (fo,), u(fi, fo)))
         return spec
-
-    def build(self, ctx, in_dim, p_store=None, g_store=None, offset=0):
-        if p_store is not None:
-            return super().build(ctx, in_dim, p_store, g_store, offset)
-        self.ctx = ctx                          # own storage: every tensor on a 4-float boundary (float4 lanes, the dW launches)
-        spec = self._param_spec(in_dim)
-        pad = lambda shape: -(-int(np.prod(shape)) // 4) * 4
-        total = sum(pad(s) for _, s, _ in spec)
-        p_store, g_store, off = ctx.zeros(total), ctx.zeros(total), 0
-        for name, shape, init in spec:
-            n = int(np.prod(shape))
-            self.params[name] = p_store.flat(off, n, shape)
-            self.grads[name] = g_store.flat(off, n, shape)
-            self.params[name].copy_from_host(init)
-            off += pad(shape)
-        self.in_dim, self.built = in_dim, True
-        return off
 
     def call(self, inputs, out=None, training=True):
         x, a = inputs
@@ -786,10 +833,7 @@ class GATConv(Layer):
         self.channels, self.heads, self.negative_slope = int(channels), int(heads), float(negative_slope)
         self.concat, self.use_bias, self.activation = True, bool(use_bias), activation
 
-    @staticmethod
-    def preprocess(a):
-        """The unweighted view of a DeviceCSR: the pattern as stored, no loop added or removed."""
-        return a.unweighted()
+    preprocess = staticmethod(_unweighted)
 
     def _param_spec(self, in_dim):
         h, c = self.heads, self.channels
@@ -801,11 +845,11 @@ class GATConv(Layer):
         spec.append(("lin.weight", (in_dim, h * c), glorot_uniform(self._rng, in_dim, h * c)))
         return spec
 
+    LEADING_AXIS = ("att_src", "att_dst")
+
     def state_dict(self):
         """{PyG name: array in PyG's layout}: att_* [1, heads, channels], lin.weight [heads * channels, in]."""
-        d = {k: v.numpy() for k, v in self.params.items()}
-        d["att_src"], d["att_dst"], d["lin.weight"] = d["att_src"][None], d["att_dst"][None], d["lin.weight"].T.copy()
-        return d
+        return self._pyg(self.params)
 
     def call(self, inputs, out=None):
         if len(inputs) != 2:
@@ -880,10 +924,11 @@ class GATv2Conv(Layer):
         self.concat, self.use_bias, self.activation = True, bool(use_bias), activation
         self.edge_dim = None if edge_dim is None else int(edge_dim)
 
-    @staticmethod
-    def preprocess(a):
-        """The unweighted view of a DeviceCSR: the pattern as stored, no loop added or removed."""
-        return a.unweighted()
+    # Storage order: att, bias, the stacked weight [in, 2 heads channels], the stacked bias, lin_edge.weight -- every tensor on a
+    # 16-byte boundary when ``offset`` is.
+    STACKS = {"lin_weight": ("lin_l.weight", "lin_r.weight"), "lin_bias": ("lin_l.bias", "lin_r.bias")}
+    LEADING_AXIS = ("att",)
+    preprocess = staticmethod(_unweighted)
 
     def _param_spec(self, in_dim):
         """PyG's names in its named_parameters() order, with the stored shapes ([in, heads * channels] weights)."""
@@ -899,69 +944,13 @@ class GATv2Conv(Layer):
             spec.append(("lin_edge.weight", (d, hc), glorot_uniform(rng, d, hc)))
         return spec
 
-    def build(self, ctx, in_dim, p_store=None, g_store=None, offset=0):
-        """Storage order: att, bias, the stacked weight [in, 2 heads channels], the stacked bias, lin_edge.weight -- every
-        tensor on a 16-byte boundary when ``offset`` is."""
-        self.ctx = ctx
-        hc = self.heads * self.channels
-        spec = {name: (shape, init) for name, shape, init in self._param_spec(in_dim)}
-        total = sum(int(np.prod(s)) for s, _ in spec.values())
-        if p_store is None:
-            p_store, g_store, offset = ctx.zeros(total), ctx.zeros(total), 0
-        off = offset
-
-        def take(shape, init):
-            nonlocal off
-            n = int(np.prod(shape))
-            pv, gv = p_store.flat(off, n, shape), g_store.flat(off, n, shape)
-            pv.copy_from_host(init)
-            off += n
-            return pv, gv
-
-        p, g = self.params, self.grads
-        p["att"], g["att"] = take(*spec["att"])
-        if self.use_bias:
-            p["bias"], g["bias"] = take(*spec["bias"])
-        self.lin_weight, self.lin_weight_grad = take((in_dim, 2 * hc), np.concatenate([spec["lin_l.weight"][1], spec["lin_r.weight"][1]], axis=1))
-        self.lin_bias, self.lin_bias_grad = take((2 * hc,), np.concatenate([spec["lin_l.bias"][1], spec["lin_r.bias"][1]]))
-        for t, w, b in ((p, self.lin_weight, self.lin_bias), (g, self.lin_weight_grad, self.lin_bias_grad)):
-            t["lin_l.weight"], t["lin_l.bias"] = w.cols(0, hc), b.flat(0, hc)
-            t["lin_r.weight"], t["lin_r.bias"] = w.cols(hc, 2 * hc), b.flat(hc, hc)
-        if "lin_edge.weight" in spec:
-            p["lin_edge.weight"], g["lin_edge.weight"] = take(*spec["lin_edge.weight"])
-        self.in_dim, self.built = in_dim, True
-        return off
-
-    def set_weights(self, weights):
-        """Arrays in the order and the stored layouts of ``params`` (att [heads, channels], lin_*.weight [in, heads channels])."""
-        w = {k: np.asarray(v, np.float32) for k, v in zip(self.params, weights)}
-        for k in ("att", "bias", "lin_edge.weight"):
-            if k in w:
-                self.params[k].copy_from_host(w[k].reshape(self.params[k].shape))
-        self.lin_weight.copy_from_host(np.concatenate([w["lin_l.weight"], w["lin_r.weight"]], axis=1))
-        self.lin_bias.copy_from_host(np.concatenate([w["lin_l.bias"], w["lin_r.bias"]]))
-
     def state_dict(self):
         """{PyG name: array in PyG's layout}: att [1, heads, channels], lin_l / lin_r / lin_edge .weight [heads * channels, in]."""
-        d = {k: v.numpy() for k, v in self.params.items()}
-        d["att"] = d["att"][None]
-        for k in d:
-            if k.endswith(".weight"):
-                d[k] = d[k].T.copy()
-        return d
+        return self._pyg(self.params)
 
     def call(self, inputs, out=None):
-        if len(inputs) not in (2, 3):
-            raise ValueError("GATv2Conv takes [x, a] or [x, a, e]")
-        x, a = inputs[:2]
-        e = inputs[2] if len(inputs) == 3 else None
+        x, a, e = self._edge_inputs(inputs)
         h, c, d = self.heads, self.channels, self.edge_dim
-        if e is not None and d is None:
-            raise ValueError("GATv2Conv: edge features given to a layer built without edge_dim")
-        if e is None and d is not None:
-            raise ValueError(f"GATv2Conv(edge_dim={d}) takes [x, a, e]")
-        if e is not None and (len(e.shape) != 2 or e.shape != (a.nnz, d)):
-            raise ValueError(f"GATv2Conv(edge_dim={d}): e must be [{a.nnz}, {d}] (one row per stored entry), got {list(e.shape)}")
         if not D.gatv2_conv_ok(x.ctx, x.shape[0], h, c, edge_dim=d or 0):
             raise NotImplementedError(f"GATv2Conv heads={h} channels={c} on {x.shape[0]} rows: the kernels serve heads in {{1, 2, 4, 8}}, "
                                       "heads * channels in {16, 32, 64, 128}, channels >= 4 and rows * heads * channels * 8 < 2^32")
@@ -1031,11 +1020,10 @@ class ResGatedGraphConv(Layer):
             raise NotImplementedError(f"ResGatedGraphConv channels={channels}: the kernels serve 16, 32, 64 and 128 (there is no composed route)")
         self.channels, self.root_weight, self.use_bias, self.activation = int(channels), bool(root_weight), bool(use_bias), activation
         self.edge_dim = None if edge_dim is None else int(edge_dim)
+        # the product's bias: lin_bias and, for the S block, as many zeros behind it (whose gradient is never written)
+        self.STACKS = {"_gemm_bias": ("lin_bias",) + ((self.channels,) if self.root_weight else ())}
 
-    @staticmethod
-    def preprocess(a):
-        """The unweighted view of a DeviceCSR: the pattern as stored, no loop added or removed."""
-        return a.unweighted()
+    preprocess = staticmethod(_unweighted)
 
     def _param_spec(self, in_dim):
         """PyG's names in its named_parameters() order and its layouts ([channels, in + D] weights)."""
@@ -1051,101 +1039,65 @@ class ResGatedGraphConv(Layer):
     def _width(self):
         return (4 if self.root_weight else 3) * self.channels
 
-    def n_params(self, in_dim):
-        """Floats of storage: the named tensors and, with root_weight, the zero bias of the S block (channels floats)."""
-        return super().n_params(in_dim) + (self.channels if self.root_weight else 0)
-
-    def build(self, ctx, in_dim, p_store=None, g_store=None, offset=0):
-        """Storage order: bias, weight [in, 4 channels], lin_bias [3 channels] and the zero bias of the S block behind it (the
-        product's bias is the two together; its gradient is never written), edge_weight -- every tensor on a 16-byte boundary
-        when ``offset`` is."""
-        self.ctx = ctx
-        h, d, w = self.channels, self.edge_dim or 0, self._width()
-        total = self.n_params(in_dim)
-        if p_store is None:
-            p_store, g_store, offset = ctx.zeros(total), ctx.zeros(total), 0
-        off = offset
-
-        def take(name, shape):
-            nonlocal off
-            n = int(np.prod(shape))
-            self.params[name], self.grads[name] = p_store.flat(off, n, shape), g_store.flat(off, n, shape)
-            off += n
-
-        if self.use_bias:
-            take("bias", (h,))
-        take("weight", (in_dim, w))
-        self._gemm_bias = p_store.flat(off, w)
-        take("lin_bias", (3 * h,))
-        off += w - 3 * h
-        if d:
-            take("edge_weight", (d, 3 * h))
-        self.in_dim, self.built = in_dim, True
-        self.load_state_dict({name: init for name, _, init in self._param_spec(in_dim)})
-        return off
-
-    def load_state_dict(self, d):
-        """{PyG name: array in PyG's layout}: the [channels, in + D] tensors are split into their node and edge blocks."""
-        h, ed, f = self.channels, self.edge_dim or 0, self.in_dim
-        names = self._names()
-        missing = [n for n in names if n not in d]
-        if missing:
-            raise KeyError(f"ResGatedGraphConv.load_state_dict: missing {missing}")
-        t = {n: np.asarray(d[n], np.float32) for n in names}
-        for n in self.LINS:
-            if t[n + ".weight"].shape != (h, f + ed) or t[n + ".bias"].shape != (h,):
-                raise ValueError(f"{n}: shapes {t[n + '.weight'].shape}, {t[n + '.bias'].shape} do not fit this layer")
-        blocks = [t[n + ".weight"][:, :f].T for n in self.LINS]
-        if self.root_weight:
-            if t["lin_skip.weight"].shape != (h, f):
-                raise ValueError(f"lin_skip.weight: shape {t['lin_skip.weight'].shape} does not fit this layer")
-            blocks.append(t["lin_skip.weight"].T)
-        self.params["weight"].copy_from_host(np.concatenate(blocks, axis=1))
-        self.params["lin_bias"].copy_from_host(np.concatenate([t[n + ".bias"] for n in self.LINS]))
-        if ed:
-            self.params["edge_weight"].copy_from_host(np.concatenate([t[n + ".weight"][:, f:].T for n in self.LINS], axis=1))
-        if self.use_bias:
-            self.params["bias"].copy_from_host(t["bias"].reshape(h))
-
     def _names(self):
         """PyG's names in _param_spec's order (without drawing the initial values)."""
         return (["bias"] if self.use_bias else []) + [k + t for k in self.LINS for t in (".weight", ".bias")] + \
             (["lin_skip.weight"] if self.root_weight else [])
 
-    def _joined(self, t):
-        h, ed = self.channels, self.edge_dim or 0
-        w, b = t["weight"].numpy(), t["lin_bias"].numpy()
-        we = t["edge_weight"].numpy() if ed else np.zeros((0, 3 * h), np.float32)
-        d = {"bias": t["bias"].numpy()} if self.use_bias else {}
-        for i, n in enumerate(self.LINS):
-            d[n + ".weight"] = np.concatenate([w[:, i * h:(i + 1) * h].T, we[:, i * h:(i + 1) * h].T], axis=1)
-            d[n + ".bias"] = b[i * h:(i + 1) * h].copy()
-        if self.root_weight:
-            d["lin_skip.weight"] = w[:, 3 * h:].T.copy()
-        return d
+    def _blocks(self):
+        """{stored tensor: the names of its column blocks}, PyG's but for the edge blocks ("lin_key.edge": the rows of
+        lin_key.weight that read e).  Storage order: bias, weight [in, 4 channels], lin_bias [3 channels] and the zero bias of the
+        S block behind it (STACKS: the product's bias is the two together; its gradient is never written), edge_weight -- every
+        tensor on a 16-byte boundary when ``offset`` is."""
+        t = {"weight": [k + ".weight" for k in self.LINS] + ["lin_skip.weight"] * self.root_weight, "lin_bias": [k + ".bias" for k in self.LINS]}
+        if self.edge_dim:
+            t["edge_weight"] = [k + ".edge" for k in self.LINS]
+        return t
+
+    def _stored(self, d, in_dim, misfit=None):
+        """{name in ``params``: array} of a {PyG name: array in PyG's layout}: the [channels, in + D] tensors split into their node
+        and edge blocks, the blocks side by side."""
+        h, keys = self.channels, [(n, n, n.endswith(".weight")) for n in self._names()]
+        shapes = {n: (in_dim, h) if tr else (h,) for n, _, tr in keys}
+        edge = {k + ".weight": k + ".edge" for k in self.LINS} if self.edge_dim else None
+        host = from_pyg(d, keys, shapes, "ResGatedGraphConv", edge=edge, edge_dim=self.edge_dim or 0, misfit=misfit)
+        stored = {"bias": host["bias"]} if self.use_bias else {}
+        stored.update({k: join_blocks(host, names) for k, names in self._blocks().items()})
+        return stored
+
+    def _stored_spec(self, in_dim):
+        self._param_spec(in_dim)                # (a seed's values are those of its second draw, as they always were: the first
+        #                                          one used to size the storage)
+        stored = self._stored({name: init for name, _, init in self._param_spec(in_dim)}, in_dim)
+        return [(k, v.shape, v) for k, v in stored.items()]
+
+    def load_state_dict(self, d):
+        """{PyG name: array in PyG's layout}: the [channels, in + D] tensors are split into their node and edge blocks."""
+        def misfit(tk, v, want):
+            n = tk.rsplit(".", 1)[0]
+            if n in self.LINS:
+                return f"{n}: shapes {np.shape(d[n + '.weight'])}, {np.shape(d[n + '.bias'])} do not fit this layer"
+            return f"{tk}: shape {np.shape(d[tk])} does not fit this layer"
+        self._load(self._stored(d, self.in_dim, misfit))
+
+    def _pyg(self, t):
+        h, views = self.channels, {k: t[k] for k in ("bias",) if k in t}
+        for k, names in self._blocks().items():
+            views.update(block_views(t[k], [(n, h) for n in names]))
+        edge = {k + ".weight": k + ".edge" for k in self.LINS} if self.edge_dim else None
+        return to_pyg(views, [(n, n, n.endswith(".weight")) for n in self._names()], edge=edge)
 
     def state_dict(self):
         """{PyG name: array in PyG's layout}: lin_key / lin_query / lin_value .weight [channels, in + D] = [node block ‖ edge block]."""
-        return self._joined(self.params)
+        return self._pyg(self.params)
 
     def gradients(self):
         """The gradients of the last backward under the names and in the layouts of state_dict()."""
-        return self._joined(self.grads)
+        return self._pyg(self.grads)
 
     def call(self, inputs, out=None):
-        if len(inputs) not in (2, 3):
-            raise ValueError("ResGatedGraphConv takes [x, a] or [x, a, e]")
-        x, a = inputs[:2]
-        if isinstance(x, (tuple, list)):
-            raise NotImplementedError("ResGatedGraphConv: bipartite inputs (x_source, x_target) have no kernel")
-        e = inputs[2] if len(inputs) == 3 else None
+        x, a, e = self._edge_inputs(inputs, refuse_bipartite=True)
         h, d = self.channels, self.edge_dim
-        if e is not None and d is None:
-            raise ValueError("ResGatedGraphConv: edge features given to a layer built without edge_dim")
-        if e is None and d is not None:
-            raise ValueError(f"ResGatedGraphConv(edge_dim={d}) takes [x, a, e]")
-        if e is not None and (len(e.shape) != 2 or e.shape != (a.nnz, d)):
-            raise ValueError(f"ResGatedGraphConv(edge_dim={d}): e must be [{a.nnz}, {d}] (one row per stored entry), got {list(e.shape)}")
         w = self._width()
         if not D.resgated_conv_ok(x.ctx, x.shape[0], h, ldp=w, edge_dim=d or 0):
             raise NotImplementedError(f"ResGatedGraphConv channels={h} on {x.shape[0]} rows: the kernels serve channels in "
@@ -1224,10 +1176,11 @@ class TransformerConv(Layer):
         self.concat, self.use_bias, self.activation = True, bool(use_bias), activation
         self.edge_dim = None if edge_dim is None else int(edge_dim)
 
-    @staticmethod
-    def preprocess(a):
-        """The unweighted view of a DeviceCSR: the pattern as stored, no loop added or removed."""
-        return a.unweighted()
+    # Storage order: the stacked weight [in, 4 heads channels], the stacked bias, lin_edge.weight, lin_beta.weight -- every tensor on
+    # a 16-byte boundary when ``offset`` is.
+    STACKS = {"lin_weight": tuple(k + ".weight" for k in BLOCKS), "lin_bias": tuple(k + ".bias" for k in BLOCKS)}
+    LEADING_AXIS = ("lin_beta.weight",)
+    preprocess = staticmethod(_unweighted)
 
     def _blocks(self):
         return self.BLOCKS if self.root_weight else self.BLOCKS[:3]
@@ -1252,82 +1205,19 @@ class TransformerConv(Layer):
     def _width(self):
         return len(self._blocks()) * self.heads * self.channels
 
-    def build(self, ctx, in_dim, p_store=None, g_store=None, offset=0):
-        """Storage order: the stacked weight [in, 4 heads channels], the stacked bias, lin_edge.weight, lin_beta.weight -- every
-        tensor on a 16-byte boundary when ``offset`` is."""
-        self.ctx = ctx
-        hc, w = self.heads * self.channels, self._width()
-        spec = {name: (shape, init) for name, shape, init in self._param_spec(in_dim)}
-        total = sum(int(np.prod(s)) for s, _ in spec.values())
-        if p_store is None:
-            p_store, g_store, offset = ctx.zeros(total), ctx.zeros(total), 0
-        off = offset
-
-        def take(shape, init):
-            nonlocal off
-            n = int(np.prod(shape))
-            pv, gv = p_store.flat(off, n, shape), g_store.flat(off, n, shape)
-            pv.copy_from_host(init)
-            off += n
-            return pv, gv
-
-        blocks = self._blocks()
-        self.lin_weight, self.lin_weight_grad = take((in_dim, w), np.concatenate([spec[k + ".weight"][1] for k in blocks], axis=1))
-        self.lin_bias = self.lin_bias_grad = None
-        if self.use_bias:
-            self.lin_bias, self.lin_bias_grad = take((w,), np.concatenate([spec[k + ".bias"][1] for k in blocks]))
-        views = [{}, {}]
-        for t, wt, b in ((views[0], self.lin_weight, self.lin_bias), (views[1], self.lin_weight_grad, self.lin_bias_grad)):
-            for i, k in enumerate(blocks):
-                t[k + ".weight"] = wt.cols(i * hc, (i + 1) * hc)
-                if b is not None:
-                    t[k + ".bias"] = b.flat(i * hc, hc)
-        for k in ("lin_edge.weight", "lin_beta.weight"):
-            if k in spec:
-                views[0][k], views[1][k] = take(*spec[k])
-        for name in self._names():                                                  # PyG's order
-            self.params[name], self.grads[name] = views[0][name], views[1][name]
-        self.in_dim, self.built = in_dim, True
-        return off
+    def _fit(self, d, keys, leading=()):
+        """from_pyg against the shapes of ``params``, with the layer's words for an array that does not fit."""
+        shapes = {k: v.shape for k, v in self.params.items()}
+        return from_pyg(d, keys, shapes, "TransformerConv", leading,
+                        misfit=lambda tk, v, want: f"{tk}: shape {v.shape} does not fit this layer ({want})")
 
     def set_weights(self, weights):
         """Arrays in the order and the stored layouts of ``params`` (weights [in, heads channels])."""
-        self._load({k: np.asarray(v, np.float32) for k, v in zip(self.params, weights)})
-
-    def _load(self, t):
-        blocks = self._blocks()
-        for k, v in t.items():
-            if v.shape != self.params[k].shape:
-                raise ValueError(f"{k}: shape {v.shape} does not fit this layer ({self.params[k].shape})")
-        self.lin_weight.copy_from_host(np.concatenate([t[k + ".weight"] for k in blocks], axis=1))
-        if self.use_bias:
-            self.lin_bias.copy_from_host(np.concatenate([t[k + ".bias"] for k in blocks]))
-        for k in ("lin_edge.weight", "lin_beta.weight"):
-            if k in self.params:
-                self.params[k].copy_from_host(t[k])
+        self._load(self._fit(dict(zip(self.params, weights)), [(k, k, False) for k in self.params]))
 
     def load_state_dict(self, d):
         """{PyG name: array in PyG's layout ([out, in] weights, lin_beta.weight [1, 3 heads channels])}."""
-        missing = [n for n in self._names() if n not in d]
-        if missing:
-            raise KeyError(f"TransformerConv.load_state_dict: missing {missing}")
-        t = {n: np.asarray(d[n], np.float32) for n in self._names()}
-        for n in t:
-            if n == "lin_beta.weight":
-                t[n] = t[n].reshape(-1)
-            elif n.endswith(".weight"):
-                t[n] = np.ascontiguousarray(t[n].T)
-        self._load(t)
-
-    @staticmethod
-    def _pyg(t):
-        d = {k: v.numpy() for k, v in t.items()}
-        for k in d:
-            if k == "lin_beta.weight":
-                d[k] = d[k][None].copy()
-            elif k.endswith(".weight"):
-                d[k] = d[k].T.copy()
-        return d
+        self._load(self._fit(d, *self._pyg_keys(self.params)))
 
     def state_dict(self):
         """{PyG name: array in PyG's layout}: weights [heads * channels, in], lin_edge.weight [heads * channels, D],
@@ -1339,19 +1229,8 @@ class TransformerConv(Layer):
         return self._pyg(self.grads)
 
     def call(self, inputs, out=None):
-        if len(inputs) not in (2, 3):
-            raise ValueError("TransformerConv takes [x, a] or [x, a, e]")
-        x, a = inputs[:2]
-        if isinstance(x, (tuple, list)):
-            raise NotImplementedError("TransformerConv: bipartite inputs (x_source, x_target) have no kernel")
-        e = inputs[2] if len(inputs) == 3 else None
+        x, a, e = self._edge_inputs(inputs, refuse_bipartite=True)
         h, c, d = self.heads, self.channels, self.edge_dim
-        if e is not None and d is None:
-            raise ValueError("TransformerConv: edge features given to a layer built without edge_dim")
-        if e is None and d is not None:
-            raise ValueError(f"TransformerConv(edge_dim={d}) takes [x, a, e]")
-        if e is not None and (len(e.shape) != 2 or e.shape != (a.nnz, d)):
-            raise ValueError(f"TransformerConv(edge_dim={d}): e must be [{a.nnz}, {d}] (one row per stored entry), got {list(e.shape)}")
         hc, w = h * c, self._width()
         if not D.transformer_conv_ok(x.ctx, x.shape[0], h, c, ldp=w, edge_dim=d or 0):
             raise NotImplementedError(f"TransformerConv heads={h} channels={c} on {x.shape[0]} rows: the kernels serve heads in "
@@ -1938,27 +1817,9 @@ class ECCConv(Layer):
             spec.append(("bias", (fo,), np.zeros(fo, np.float32)))
         return spec
 
-    def build(self, ctx, in_dim, p_store=None, g_store=None, offset=0):
-        """Layer.build with every parameter on a 16-byte boundary (the padding floats have zero gradients, so a single SGD
-        launch over a model's flat buffer leaves them at zero)."""
-        self.ctx = ctx
-        spec = self._param_spec(in_dim)
-        pad = lambda k: -(-int(k) // 4) * 4
-        total = sum(pad(np.prod(s)) for _, s, _ in spec)
-        if p_store is None:
-            p_store, g_store, offset = ctx.zeros(max(total, 1)), ctx.zeros(max(total, 1)), 0
-        off = offset
-        for name, shape, init in spec:
-            k = int(np.prod(shape))
-            self.params[name] = p_store.flat(off, k, shape)
-            self.grads[name] = g_store.flat(off, k, shape)
-            self.params[name].copy_from_host(init)
-            off += pad(k)
-        self.in_dim, self.built = int(in_dim), True
-        return off
-
-    def n_params(self, in_dim):
-        return sum(-(-int(np.prod(s)) // 4) * 4 for _, s, _ in self._param_spec(in_dim))
+    # every parameter on a 16-byte boundary (the padding floats have zero gradients, so a single SGD launch over a model's flat
+    # buffer leaves them at zero)
+    ALIGN = OWN_ALIGN = 4
 
     # ---- weights in the Keras shapes ----------------------------------------------------------------------------------
     def get_weights(self, as_dict=False):

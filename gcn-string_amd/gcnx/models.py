@@ -49,6 +49,7 @@ from . import convs
 from . import device as D
 from .layers import glorot_uniform
 from .loader import SparseTensor
+from .params import block_views, from_pyg, join_blocks, to_pyg
 
 
 class DeviceBatch:
@@ -1489,10 +1490,13 @@ class GCN(_GraphRunner):
                   ("batch_norm_4.weight", "g4", False), ("batch_norm_4.bias", "be4", False))
     PROBE_KEY = "conv1.lin.weight"       # the state_dict tensor whose second dimension is the input width
     EPS = D.TORCH_BN_EPS
-    # ---- what a subclass with another convolution sets (and the hooks _initial, _conv_fwd, _conv_bwd, _stack) -----------------
+    # ---- what a subclass with another convolution sets (and the hooks _initial, _conv_fwd, _conv_bwd) -------------------------
     OPERATOR = "gcn"                     # _op: "gcn" | "mean" | "pattern" | "perm"
     SELF_LOOPS = True                    # a host adjacency gets PyG's add_remaining_self_loops (False: used as stored)
     LEADING_AXIS = ()                    # state_dict keys that carry a leading axis of 1 in PyG ([1, heads, C], [1, 3H])
+    STACKS = {}                          # {key of a stacked tensor: the keys of its column blocks, each ``hidden`` wide, in storage
+    #                                      order}: the only statement of a model's block order (a subclass sets it in _init)
+    EDGE_BLOCKS = {}                     # {state_dict key: the key of its edge block}: ResGated's [node block ‖ edge block] weights
     KERNELS = "GCNConv"                  # the kernel family, as the constructor's messages name it
     HEAD_NOTE = "the one-workgroup head"
     edge_dim = None
@@ -1592,6 +1596,7 @@ class GCN(_GraphRunner):
         # every parameter starts on a 16-byte boundary (the kernels read the weights, biases and attention vectors as float4);
         # the padding floats have zero gradients, so the single update launch over the whole buffer leaves them at zero
         offs = self._alloc_flat([(k, shapes[k]) for k in self.PARAM_ORDER], align=4)
+        self._name_blocks()
         initial = self._initial(f_in, shapes, offs)
         if attention:                       # drawn last: every other tensor keeps the bits its seed gives it
             initial["ar"] = self._uniform(self.hidden, self.hidden)
@@ -1602,8 +1607,7 @@ class GCN(_GraphRunner):
         self.built = True
 
     def _initial(self, f_in, shapes, offs):
-        """{key: initial value}, drawn from self._rng in the model's own fixed order (what ``seed`` means); a subclass also
-        makes its named views of stacked tensors here."""
+        """{key: initial value}, drawn from self._rng in the model's own fixed order (what ``seed`` means)."""
         h, rng = self.hidden, self._rng
         return {"w1": glorot_uniform(rng, f_in, h), "w2": glorot_uniform(rng, h, h), **self._head_initial(shapes)}
 
@@ -1621,10 +1625,14 @@ class GCN(_GraphRunner):
         init.update({k: np.full(1, 0.25) for k in ("a1", "a2", "a3", "a4")})
         return init
 
+    def _name_blocks(self):
+        """The views behind the keys of STACKS' blocks, in ``p`` and ``g`` alike."""
+        for t in (self.p, self.g):
+            for key, names in self.STACKS.items():
+                t.update(block_views(t[key], [(n, self.hidden) for n in names]))
+
     def _named(self, t):
-        d = {tk: (t[k].numpy().T.copy() if tr else t[k].numpy()) for tk, k, tr in self.TORCH_KEYS}
-        d.update({tk: d[tk][None] for tk in self.LEADING_AXIS})
-        return d
+        return to_pyg(t, self.TORCH_KEYS, self.LEADING_AXIS, self.EDGE_BLOCKS)
 
     def state_dict(self):
         """{torch key: array in torch's layout}: conv*.lin.weight [out, in], linear_*.weight [out, in], prelu_*.weight [1]."""
@@ -1638,25 +1646,13 @@ class GCN(_GraphRunner):
         present, weights transposed, the leading axis of LEADING_AXIS keys dropped, every shape that of its view."""
         if not self.built:
             self.build(self._probe_f_in(d))
-        missing = [tk for tk, _, _ in self.TORCH_KEYS if tk not in d]
-        if missing:
-            raise KeyError(f"{self._name}.load_state_dict: missing {missing}")
-        host = {}
-        for tk, k, tr in self.TORCH_KEYS:
-            v = np.asarray(d[tk], np.float32)
-            if tk in self.LEADING_AXIS and v.ndim == len(self.p[k].shape) + 1 and v.shape[0] == 1:
-                v = v[0]
-            v = self._node_block(tk, k, v.T if tr else v, host)
-            if v.shape != self.p[k].shape:
-                raise ValueError(f"{tk}: shape {np.asarray(d[tk]).shape} does not fit this model")
-            host[k] = v
-        return host
-
-    def _node_block(self, tk, k, v, host):
-        return v                          # (ResGated splits the edge block of a [in + D, H] tensor off into ``host``)
+        return from_pyg(d, self.TORCH_KEYS, {k: self.p[k].shape for _, k, _ in self.TORCH_KEYS}, self._name, self.LEADING_AXIS,
+                        self.EDGE_BLOCKS, self.edge_dim or 0)
 
     def _stack(self, host):
-        return host                       # (the models that store stacked tensors concatenate their named blocks)
+        """The named blocks of ``host`` into the stacked tensors of STACKS."""
+        host.update({key: join_blocks(host, names) for key, names in self.STACKS.items()})
+        return host
 
     def load_state_dict(self, d):
         """Inverse of state_dict (a converted torch checkpoint: tensors as NumPy arrays).  Builds the model if needed."""
@@ -2783,6 +2779,8 @@ class GATv2(GCN):
             (((f"conv{k}.lin_edge.weight", f"we{k}", True),) if self.edge_dim else ())
         self.TORCH_KEYS = keys(1) + keys(2) + GCN.TORCH_KEYS[4:]
         self.LEADING_AXIS = ("conv1.att", "conv2.att")                 # [1, heads, C] in PyG, [heads, C] here
+        # PyG's names: the column halves of the stacked weight, the halves of the stacked bias
+        self.STACKS = {"w1": ("wl1", "wr1"), "lb1": ("bl1", "br1"), "w2": ("wl2", "wr2"), "lb2": ("bl2", "br2")}
 
     def _shapes(self, f_in):
         s = super()._shapes(f_in)
@@ -2793,10 +2791,6 @@ class GATv2(GCN):
 
     def _initial(self, f_in, shapes, offs):
         h, heads, d, rng = self.hidden, self.heads, self.edge_dim or 0, self._rng
-        for t in (self.p, self.g):                      # PyG's names: the column halves of the stacked weight, the halves of the bias
-            for k in (1, 2):
-                t[f"wl{k}"], t[f"wr{k}"] = t[f"w{k}"].cols(0, h), t[f"w{k}"].cols(h, 2 * h)
-                t[f"bl{k}"], t[f"br{k}"] = t[f"lb{k}"].flat(0, h), t[f"lb{k}"].flat(h, h)
         alim = np.sqrt(6.0 / (heads + h // heads))
         att = lambda: rng.uniform(-alim, alim, shapes["att1"])
         lin = lambda fi: np.concatenate([glorot_uniform(rng, fi, h), glorot_uniform(rng, fi, h)], axis=1)
@@ -2804,13 +2798,6 @@ class GATv2(GCN):
         if d:
             init.update(we1=glorot_uniform(rng, d, h), we2=glorot_uniform(rng, d, h))
         return init
-
-    def _stack(self, host):
-        """The lin_l / lin_r halves into the stacked tensors."""
-        for k in (1, 2):
-            host[f"w{k}"] = np.concatenate([host.pop(f"wl{k}"), host.pop(f"wr{k}")], axis=1)
-            host[f"lb{k}"] = np.concatenate([host.pop(f"bl{k}"), host.pop(f"br{k}")])
-        return host
 
     def _host_inputs(self, inputs):
         x, a, i = _without_e(inputs)
@@ -2905,6 +2892,13 @@ class ResGated(GCN):
             tuple(t for n, s in self.LINS for t in ((f"conv{k}.{n}.weight", f"w{s}{k}", True), (f"conv{k}.{n}.bias", f"b{s}{k}", False))) + \
             (((f"conv{k}.lin_skip.weight", f"ws{k}", True),) if self.root_weight else ())
         self.TORCH_KEYS = keys(1) + keys(2) + GCN.TORCH_KEYS[4:]
+        self.STACKS, self.EDGE_BLOCKS = {}, {}
+        for k in (1, 2):                                # PyG's names: the column blocks of the stacked tensors
+            self.STACKS[f"w{k}"] = tuple(f"w{s}{k}" for _, s in self.LINS) + ((f"ws{k}",) if self.root_weight else ())
+            self.STACKS[f"lb{k}"] = tuple(f"b{s}{k}" for _, s in self.LINS)
+            if self.edge_dim:
+                self.STACKS[f"we{k}"] = tuple(f"w{s}e{k}" for _, s in self.LINS)
+                self.EDGE_BLOCKS.update({f"conv{k}.{n}.weight": f"w{s}e{k}" for n, s in self.LINS})
 
     def _shapes(self, f_in):
         s = super()._shapes(f_in)
@@ -2918,14 +2912,6 @@ class ResGated(GCN):
         for k in (1, 2):
             assert not self.root_weight or offs[f"lz{k}"] == offs[f"lb{k}"] + 3 * h
             self._gemm_bias[k] = self.flat_p.flat(offs[f"lb{k}"], w)
-        for t in (self.p, self.g):                      # PyG's names: the column blocks of the stacked tensors
-            for k in (1, 2):
-                for i, (_, s) in enumerate(self.LINS):
-                    t[f"w{s}{k}"], t[f"b{s}{k}"] = t[f"w{k}"].cols(i * h, (i + 1) * h), t[f"lb{k}"].flat(i * h, h)
-                    if d:
-                        t[f"w{s}e{k}"] = t[f"we{k}"].cols(i * h, (i + 1) * h)
-                if self.root_weight:
-                    t[f"ws{k}"] = t[f"w{k}"].cols(3 * h, 4 * h)
         init = self._head_initial(shapes)
         for k, f in ((1, f_in), (2, h)):                # torch's Linear on [x ‖ e]: fan_in = in + D for key / query / value
             blocks = [u(f + d, f, 3 * h)] + ([u(f, f, h)] if self.root_weight else [])
@@ -2934,42 +2920,8 @@ class ResGated(GCN):
                 init[f"we{k}"] = u(f + d, d, 3 * h)
         return init
 
-    def _joined(self, d, t):
-        """PyG's [H, in + D] tensors: the edge block of ``t`` (self.p or self.g) joined to the node block the base class returned."""
-        if self.edge_dim:
-            for k in (1, 2):
-                for n, s in self.LINS:
-                    d[f"conv{k}.{n}.weight"] = np.concatenate([d[f"conv{k}.{n}.weight"], t[f"w{s}e{k}"].numpy().T], axis=1)
-        return d
-
-    def state_dict(self):
-        """{PyG key: array in PyG's layout}: conv*.lin_key / lin_query / lin_value .weight [H, in + D] = [node block ‖ edge block]."""
-        return self._joined(super().state_dict(), self.p)
-
-    def gradients(self):
-        return self._joined(super().gradients(), self.g)
-
     def _probe_f_in(self, d):
         return int(np.asarray(d["conv1.lin_key.weight"]).shape[1]) - (self.edge_dim or 0)       # [H, F + D]
-
-    def _node_block(self, tk, k, v, host):
-        """Of a [in + D, H] key / query / value weight: the edge block into ``host`` (wk1 -> wke1), the node block back."""
-        ed = self.edge_dim or 0
-        if ed and tk.startswith("conv") and tk.endswith(".weight") and "lin_skip" not in tk:
-            if v.ndim != 2 or v.shape[0] <= ed:
-                raise ValueError(f"{tk}: shape {v.T.shape} does not fit this model")
-            host[k[:2] + "e" + k[2:]], v = v[-ed:], v[:-ed]
-        return v
-
-    def _stack(self, host):
-        """The node blocks into the stacked weight, the three biases into the stacked bias, the edge blocks into the edge weight."""
-        for k in (1, 2):
-            node = [host.pop(f"w{s}{k}") for _, s in self.LINS] + ([host.pop(f"ws{k}")] if self.root_weight else [])
-            host[f"w{k}"] = np.concatenate(node, axis=1)
-            host[f"lb{k}"] = np.concatenate([host.pop(f"b{s}{k}") for _, s in self.LINS])
-            if self.edge_dim:
-                host[f"we{k}"] = np.concatenate([host.pop(f"w{s}e{k}") for _, s in self.LINS], axis=1)
-        return host
 
     def _ensure(self, batch, sharded=False):
         bufs = super()._ensure(batch, sharded)
@@ -3053,6 +3005,10 @@ class Transformer(GCN):
             (lin(k, "lin_skip", "s") if self.root_weight else ()) + (((f"conv{k}.lin_beta.weight", f"wb{k}", False),) if self.beta else ())
         self.TORCH_KEYS = keys(1) + keys(2) + GCN.TORCH_KEYS[4:]
         self.LEADING_AXIS = ("conv1.lin_beta.weight", "conv2.lin_beta.weight") if self.beta else ()     # [1, 3 H] in PyG, [3 H] here
+        # PyG's names: the column blocks of the stacked weight and bias
+        self.STACKS = {}
+        for k in (1, 2):
+            self.STACKS[f"w{k}"], self.STACKS[f"lb{k}"] = tuple(f"w{s}{k}" for _, s in self.blocks), tuple(f"b{s}{k}" for _, s in self.blocks)
 
     def _shapes(self, f_in):
         s = super()._shapes(f_in)
@@ -3062,10 +3018,6 @@ class Transformer(GCN):
 
     def _initial(self, f_in, shapes, offs):
         h, d, w, u = self.hidden, self.edge_dim or 0, self.width, self._uniform
-        for t in (self.p, self.g):                      # PyG's names: the column blocks of the stacked weight and bias
-            for k in (1, 2):
-                for i, (_, s) in enumerate(self.blocks):
-                    t[f"w{s}{k}"], t[f"b{s}{k}"] = t[f"w{k}"].cols(i * h, (i + 1) * h), t[f"lb{k}"].flat(i * h, h)
         init = self._head_initial(shapes)
         for k, f in ((1, f_in), (2, h)):
             init[f"w{k}"], init[f"lb{k}"] = u(f, f, w), u(f, w)
@@ -3074,13 +3026,6 @@ class Transformer(GCN):
             if self.beta:
                 init[f"wb{k}"] = u(3 * h, 3 * h)
         return init
-
-    def _stack(self, host):
-        """The four Linears' tensors into the stacked ones."""
-        for k in (1, 2):
-            host[f"w{k}"] = np.concatenate([host.pop(f"w{s}{k}") for _, s in self.blocks], axis=1)
-            host[f"lb{k}"] = np.concatenate([host.pop(f"b{s}{k}") for _, s in self.blocks])
-        return host
 
     def _ensure(self, batch, sharded=False):
         bufs = super()._ensure(batch, sharded)

@@ -12,6 +12,7 @@ import appnp_ref as AP
 import attn_pool_ref as AR
 import gcn_bn_ref as R
 import pdn_ref as PR
+from host_fakes import HostContext as _HostContext
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("gcnx_appnp_resident_ok", "gcnx_appnp_scratch_floats", "gcnx_appnp_propagate")
@@ -245,36 +246,6 @@ def test_abi_declares_and_exports_the_appnp_entry_points():
 
 
 # ---- 4. exports, refusals, the state dict ----------------------------------------------------------------------------------------
-class _HostView:
-    def __init__(self, store, off, n, shape):
-        self.store, self.off, self.n, self.shape = store, off, n, tuple(shape)
-
-    def numpy(self):
-        return self.store[self.off:self.off + self.n].reshape(self.shape).copy()
-
-    def copy_from_host(self, host, wait=True):
-        host = np.asarray(host, np.float32)
-        assert host.shape == self.shape, (host.shape, self.shape)
-        self.store[self.off:self.off + self.n] = host.ravel()
-
-
-class _HostBuffer:
-    def __init__(self, n):
-        self.size, self.store, self.views = n, np.zeros(n, np.float32), []
-
-    def flat(self, off, n, shape=None):
-        assert off + n <= self.size
-        self.views.append((off, n, tuple(shape or (n,))))
-        return _HostView(self.store, off, n, shape or (n,))
-
-
-class _HostContext:
-    """Stands in for gcnx.Context in build() / state_dict() / load_state_dict(): host arrays behind zeros(n) and flat()."""
-
-    def zeros(self, n):
-        return _HostBuffer(n)
-
-
 def test_exports_and_constructor_refusals():
     import gcnx
     from gcnx import layers, models

@@ -11,6 +11,7 @@ import pytest
 
 from conftest import ROOT
 import gine_ref as ER
+from host_fakes import HostContext as _HostContext
 from test_sage_host import _graphs
 
 NAMES = ("gcnx_gine_conv_ok", "gcnx_gine_conv", "gcnx_gine_aggregate", "gcnx_gine_bwd_scratch_floats", "gcnx_gine_bwd_edges",
@@ -284,43 +285,6 @@ def test_launch_sequences_of_gine_forward_and_backward(monkeypatch, one_launch, 
 
 
 # ---- 5. the model without a device ---------------------------------------------------------------------------------------
-class _HostView:
-    def __init__(self, store, off, n, shape):
-        self.store, self.off, self.n, self.shape = store, off, n, tuple(shape)
-
-    def numpy(self):
-        return self.store[self.off:self.off + self.n].reshape(self.shape).copy()
-
-    def copy_from_host(self, host, wait=True):
-        host = np.asarray(host, np.float32)
-        assert host.shape == self.shape, (host.shape, self.shape)
-        self.store[self.off:self.off + self.n] = host.ravel()
-
-
-class _HostBuffer:
-    def __init__(self, n):
-        self.size, self.store, self.views = n, np.zeros(n, np.float32), []
-
-    def flat(self, off, n, shape=None):
-        assert off + n <= self.size
-        self.views.append((off, n, tuple(shape or (n,))))
-        return _HostView(self.store, off, n, shape or (n,))
-
-    def numpy(self):
-        return self.store.copy()
-
-
-class _HostContext:
-    """Stands in for gcnx.Context in build() / state_dict() / load_state_dict(): host arrays behind zeros(n) and flat()."""
-
-    def __init__(self):
-        self.buffers = []
-
-    def zeros(self, n):
-        self.buffers.append(_HostBuffer(n))
-        return self.buffers[-1]
-
-
 def test_gine_constructor_refusals():
     from gcnx.models import GINE
     for bad in (None, 0, 9):
