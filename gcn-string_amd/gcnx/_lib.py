@@ -227,6 +227,11 @@ SIGNATURES = {
     "gcnx_appnp_resident_ok": [_i64, _i32, _i64],
     "gcnx_appnp_scratch_floats": [_i64, _i32],
     "gcnx_appnp_propagate": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _i32, _i32, _i32, _f32, _i32, _vp, _i64, _vp],
+    "gcnx_cheb_norm": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp],
+    "gcnx_cheb_resident_ok": [_i64, _i32, _i64],
+    "gcnx_cheb_scratch_floats": [_i64, _i32],
+    "gcnx_cheb_basis": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _i32, _i32, _i32, _f32, _i32, _vp, _i64, _vp],
+    "gcnx_cheb_sum": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _i32, _i32, _i32, _f32, _i32, _vp, _i64, _vp],
     "gcnx_comm_unique_id": [C.c_char_p],
     "gcnx_comm_init_rank": [_vp, C.c_char_p, _int, _int, C.POINTER(_vp)],
     "gcnx_comm_destroy": [_vp],
@@ -237,7 +242,8 @@ _RESTYPE = {"gcnx_last_error": C.c_char_p, "gcnx_dense_bwd_scratch_floats": C.c_
             "gcnx_gcn_conv_bwd_scratch_floats": C.c_int64, "gcnx_gat_bwd_scratch_floats": C.c_int64, "gcnx_gatv2_bwd_scratch_floats": C.c_int64, "gcnx_wimage_elems": C.c_int64, "gcnx_gemm_wimage_parts": C.c_int64,
             "gcnx_attn_pool_scratch_floats": C.c_int64, "gcnx_graph_norm_scratch_floats": C.c_int64,
             "gcnx_gine_bwd_scratch_floats": C.c_int64, "gcnx_mask_scratch_floats": C.c_int64,
-            "gcnx_pdn_bwd_scratch_floats": C.c_int64, "gcnx_appnp_scratch_floats": C.c_int64}
+            "gcnx_pdn_bwd_scratch_floats": C.c_int64, "gcnx_appnp_scratch_floats": C.c_int64,
+            "gcnx_cheb_scratch_floats": C.c_int64}
 
 
 class WimageJob(C.Structure):

@@ -1,6 +1,6 @@
 """The launch sequences of the convolutions that a layer (gcnx.layers) and a model (gcnx.models) both run: PNAConv, GATConv,
-GATv2Conv, ResGatedGraphConv, TransformerConv, GINEConv, PDNConv (with the GCNConv sequence it is built on) and APPNPConv.  This is the one
-place they are written down.
+GATv2Conv, ResGatedGraphConv, TransformerConv, GINEConv, PDNConv (with the GCNConv sequence it is built on), APPNPConv and
+ChebConv.  This is the one place they are written down.
 
 One forward and one backward function per convolution, plain functions over operands: ``ctx``, the pattern, the operands, the
 parameter views, the gradient views, every scratch and output buffer, then the scalars.  The caller owns the storage, the
@@ -251,3 +251,23 @@ def appnp_backward(ctx, a_t, x, dz, w, g_w, g_bias, dh, k, alpha, scratch, dx, c
     D.gemm_dw(ctx, x, dh, g_w)                                                             # dW = x^T dH
     if dx is not None:
         D.gemm_dx(ctx, dh, w, dx)                                                          # dx = dH W^T
+
+
+# ---- ChebConv ----------------------------------------------------------------------------------------------------------------
+def cheb_forward(ctx, a, x, w, bias, h, out, k, lambda_max, scratch, col_block=0):
+    """h = x W, W = [lins.0.weight^T | .. | lins.{k-1}.weight^T] ([in, k c]), then out = sum_j T_j(L^) H_j + bias by Clenshaw
+    summation on a = S (k - 1 gathers).  scratch: cheb_scratch_floats (read by the streamed route only).  col_block:
+    cheb_sum's (0: the library's route, -1: streamed)."""
+    D.gemm(ctx, x, w, None, h)
+    D.cheb_sum(ctx, a, h, bias, out, k, lambda_max, scratch=scratch, col_block=col_block)
+
+
+def cheb_backward(ctx, a_t, x, dz, w, g_w, g_bias, g, k, lambda_max, scratch, dx, col_block=0):
+    """From dz: the bias gradient (its column sums), g [n, k c] = T_j(L^^T) dz in block j (the basis on the transposed operator
+    a_t, k - 1 gathers), dW = x^T g and, with dx, dx = g W^T."""
+    if g_bias is not None:
+        D.act_bias_grad(ctx, dz, None, dz, None, db=g_bias)                                # column sums of dZ
+    D.cheb_basis(ctx, a_t, dz, g, k, lambda_max, scratch=scratch, col_block=col_block)
+    D.gemm_dw(ctx, x, g, g_w)                                                              # dW = x^T G
+    if dx is not None:
+        D.gemm_dx(ctx, g, w, dx)                                                           # dx = G W^T

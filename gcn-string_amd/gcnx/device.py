@@ -377,6 +377,19 @@ class DeviceCSR:
         return DeviceCSR(self.ctx, self.n, self.nnz, self.rowptr, self.colidx, out, self.block_ptr, self.n_blocks,
                          self.symmetric, self.max_block_rows)
 
+    def cheb_norm(self):
+        """ChebConv's operator S (gcnx_cheb_norm): a CSR sharing structure with self, values r_i w_ij r_j off the diagonal and 0
+        on it, r = deg^-1/2 of the column sums without the diagonal (PyG's get_laplacian; L^ = c_s S + c_d I is applied by
+        cheb_basis / cheb_sum).  Built once per operator; its ``transpose()`` is S^T."""
+        if getattr(self, "_cheb", None) is None:
+            out = self.ctx.empty(max(self.nnz, 1), np.float32)
+            t = self.transpose()
+            self.ctx._ck(self.ctx.lib.gcnx_cheb_norm(self.ctx.h, self.rowptr.ptr, self.colidx.ptr, _p(self.vals), t.rowptr.ptr,
+                                                      t.colidx.ptr, _p(t.vals), self.n, out.ptr))
+            self._cheb = DeviceCSR(self.ctx, self.n, self.nnz, self.rowptr, self.colidx, out, self.block_ptr, self.n_blocks,
+                                   self.symmetric, self.max_block_rows)
+        return self._cheb
+
     def transpose(self):
         if self.symmetric:
             return self
@@ -846,6 +859,45 @@ def appnp_propagate(ctx, a, x, out, k, alpha, scratch=None, col_block=0):
     ctx._ck(ctx.lib.gcnx_appnp_propagate(ctx.h, a.rowptr.ptr, a.colidx.ptr, _p(a.vals), a.block_ptr.ptr if has_blocks else None,
                                          a.n_blocks if has_blocks else 0, a.max_block_rows if has_blocks else 0, _p(x), x.ld, n, f,
                                          int(k), float(alpha), int(col_block), _p(out), out.ld, _p(scratch)))
+    return out
+
+
+def cheb_resident_ok(ctx, max_graph_rows, f, ld=None):
+    """True if the one-launch route of cheb_basis / cheb_sum serves a batch whose tallest graph has this many rows
+    (gcnx_cheb_resident_ok); ld: the leading dimension of the call's input."""
+    return bool(ctx.lib.gcnx_cheb_resident_ok(int(max_graph_rows), int(f), int(ld if ld is not None else f)))
+
+
+def cheb_scratch_floats(ctx, n, f):
+    """Floats of ``scratch`` for the streamed route of cheb_sum with k >= 3 (gcnx_cheb_scratch_floats)."""
+    return int(ctx.lib.gcnx_cheb_scratch_floats(int(n), int(f)))
+
+
+def _cheb_graphs(a):
+    has_blocks = a.block_ptr is not None and a.n_blocks > 0
+    return (a.block_ptr.ptr if has_blocks else None, a.n_blocks if has_blocks else 0, a.max_block_rows if has_blocks else 0)
+
+
+def cheb_basis(ctx, a, x, out, k, lambda_max=2.0, scratch=None, col_block=0):
+    """Block j of out [n, k f] = T_j(L^) x, j = 0 .. k-1, on the operator ``a`` = S (DeviceCSR.cheb_norm) (gcnx_cheb_basis): the
+    backward of cheb_sum on ``a.transpose()`` with x = dz.  The graphs of ``a`` let the library keep each graph's rows in LDS
+    across all k - 1 gathers; without them, or with col_block=-1, one launch per gather.  col_block > 0 forces the one-launch
+    route with that many columns per workgroup."""
+    n, f = x.shape
+    assert a.n == n and out.shape == (n, k * f)
+    ctx._ck(ctx.lib.gcnx_cheb_basis(ctx.h, a.rowptr.ptr, a.colidx.ptr, _p(a.vals), *_cheb_graphs(a), _p(x), x.ld, n, f, int(k),
+                                    float(lambda_max), int(col_block), _p(out), out.ld, _p(scratch)))
+    return out
+
+
+def cheb_sum(ctx, a, h, bias, out, k, lambda_max=2.0, scratch=None, col_block=0):
+    """out [n, f] = sum_j T_j(L^) H_j + bias by Clenshaw summation, H_j = block j of h [n, k f] (gcnx_cheb_sum).  scratch
+    (cheb_scratch_floats) is what the streamed route with k >= 3 alternates with out; routes and col_block as cheb_basis."""
+    n, f = out.shape
+    assert a.n == n and h.shape == (n, k * f) and (bias is None or bias.shape == (f,))
+    assert scratch is None or scratch.size >= cheb_scratch_floats(ctx, n, f)
+    ctx._ck(ctx.lib.gcnx_cheb_sum(ctx.h, a.rowptr.ptr, a.colidx.ptr, _p(a.vals), *_cheb_graphs(a), _p(h), h.ld, _p(bias), n, f, int(k),
+                                  float(lambda_max), int(col_block), _p(out), out.ld, _p(scratch)))
     return out
 
 

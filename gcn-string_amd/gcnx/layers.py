@@ -9,6 +9,7 @@ Reference topology: GCNConv -> GCNConv -> global pool -> Linear (gcn_utills.py:8
 names as its next step (gcn_utills.py:804-806); ``GATConv(channels, heads=1)`` is PyG's attention layer for the same slot.
 ``GINConv(channels, mlp_hidden=None, eps=0.0, train_eps=False)`` is PyG's / Spektral's Graph Isomorphism Network layer for it.
 ``GINEConv(channels, edge_dim, mlp_hidden=None, eps=0.0, train_eps=False)`` is PyG's GINEConv: GIN whose neighbour sum reads the edge features (gcn.py:71).
+``ChebConv(channels, K=3, lambda_max=2.0)`` is PyG's Chebyshev spectral convolution: K filter terms, one weight matrix per hop distance.
 ``PNAConv(channels, deg=None, avg_deg_log=None)`` is PyG's PNAConv with the mean / min / max / std aggregators and the three degree scalers.
 ``GATv2Conv(channels, heads=1, edge_dim=None)`` is PyG's GATv2Conv: attention whose scores read the edge features (gcn.py:71).
 ``ResGatedGraphConv(channels, edge_dim=None, root_weight=True)`` is PyG's gated layer: per-channel sigmoid gates that read the edge features.
@@ -419,6 +420,82 @@ class APPNPConv(Layer):
         dx = self._buf("dx", x.shape) if need_dx else None
         convs.appnp_backward(self.ctx, a.transpose(), x, dy, p["kernel"], g["kernel"], g.get("bias"), self._buf("h", dy.shape),
                              self.propagations, self.alpha, self._scratch_buf(x.shape[0]), dx, col_block=self.col_block)
+        return dx
+
+
+class ChebConv(Layer):
+    """torch_geometric.nn.ChebConv(in, channels, K, normalization="sym", lambda_max) (Defferrard et al. 2016), the Chebyshev
+    spectral convolution: the K-hop layer with one weight matrix per hop distance, for the slot the reference's author left open
+    (gcn_utills.py:804-806):
+
+        out = sum_{k < K} T_k(L^) x W_k + b      T_0 = I   T_1 = L^   T_k = 2 L^ T_{k-1} - T_{k-2}      L^ = (2 / lambda_max) L - I
+
+    with L = I - D^-1/2 A D^-1/2 on the adjacency without its loops (PyG's get_laplacian: loops removed, the degree taken on
+    the source index), so L^ = -(2 / lambda_max) S + (2 / lambda_max - 1) I with S = ``ChebConv.preprocess(a)``.  K is PyG's:
+    the NUMBER of terms, 1 .. 16 (spektral.layers.ChebConv(channels, K) counts one less: its K is the highest order).
+    ``lambda_max`` is a number > 0 (default 2.0, which bounds the spectrum of the symmetric normalised Laplacian; nothing is
+    estimated); a value below the operator's largest eigenvalue makes the terms grow with k.
+
+    ``ChebConv(channels, K=3, lambda_max=2.0, use_bias=True, activation=None, col_block=0)``, called as ``layer([x, s])``.
+    Parameters under PyG's names ``lins.{k}.weight`` ([in, channels] here, [channels, in] in PyG; glorot) and ``bias`` (zeros);
+    the weights are the column blocks of one stacked tensor ``weight`` [in, K channels] (gradient ``weight_grad``).
+    ``normalization`` other than "sym", an activation, or K outside 1 .. 16 raise NotImplementedError.
+
+    Launches (cheb_forward / cheb_backward of gcnx/convs.py, which the model runs too; csrc/cheb.hip): gcnx_gemm (H = x W), then
+    gcnx_cheb_sum -- Clenshaw summation, K - 1 gathers in one launch that keeps every graph's rows in LDS where the operator
+    carries its graphs, the width is a multiple of 4 and there are enough gathers to earn the staging back (3; 2 on graphs of up
+    to 256 rows), otherwise one launch per gather.  Nothing is kept for the backward: gcnx_cheb_basis on the transposed operator
+    gives G = [T_k(L^^T) dy], then dW = x^T G (one gcnx_gemm_dw) and dx = G W^T (one gcnx_gemm_dx).  ``col_block``: the kernels'
+    (0: the library's route, -1: one launch per gather)."""
+
+    MAX_K = 16
+
+    def __init__(self, channels, K=3, lambda_max=2.0, use_bias=True, activation=None, col_block=0, normalization="sym", **kw):
+        super().__init__(**kw)
+        if activation not in (None, "linear"):
+            raise NotImplementedError(f"ChebConv activation {activation!r}: the layer is linear (follow it with BatchNorm1d / PReLU)")
+        if normalization != "sym":
+            raise NotImplementedError(f"ChebConv normalization={normalization!r}: only \"sym\"")
+        if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or not 1 <= int(K) <= self.MAX_K:
+            raise NotImplementedError(f"ChebConv K={K!r} must be an int in 1 .. {self.MAX_K} (what the Chebyshev kernels serve)")
+        if not float(lambda_max) > 0.0 or not np.isfinite(float(lambda_max)):
+            raise ValueError(f"ChebConv lambda_max={lambda_max!r} must be a finite number > 0")
+        self.channels, self.K, self.lambda_max = int(channels), int(K), float(lambda_max)
+        self.use_bias, self.activation, self.col_block = bool(use_bias), activation, int(col_block)
+        self.STACKS = {"weight": tuple(f"lins.{k}.weight" for k in range(self.K))}
+
+    @staticmethod
+    def preprocess(a):
+        """The operator S of a DeviceCSR (DeviceCSR.cheb_norm): r_i w_ij r_j off the diagonal, 0 on a stored diagonal entry."""
+        return a.cheb_norm()
+
+    def _param_spec(self, in_dim):
+        c = self.channels
+        spec = [(f"lins.{k}.weight", (in_dim, c), glorot_uniform(self._rng, in_dim, c)) for k in range(self.K)]
+        if self.use_bias:
+            spec.append(("bias", (c,), np.zeros(c, np.float32)))
+        return spec
+
+    def _scratch_buf(self, n):
+        return self._buf("scratch", (max(D.cheb_scratch_floats(self.ctx, n, self.channels), 4),))
+
+    def call(self, inputs, out=None):
+        x, a = inputs
+        if not self.built:
+            self.build(x.ctx, x.shape[1])
+        n, c = x.shape[0], self.channels
+        y = out if out is not None else self._buf("y", (n, c))
+        convs.cheb_forward(self.ctx, a, x, self.weight, self.params.get("bias"), self._buf("h", (n, self.K * c)), y, self.K,
+                           self.lambda_max, self._scratch_buf(n), col_block=self.col_block)
+        self._saved = (x, a)
+        return y
+
+    def backward(self, dy, need_dx=True):
+        x, a = self._saved
+        dx = self._buf("dx", x.shape) if need_dx else None
+        convs.cheb_backward(self.ctx, a.transpose(), x, dy, self.weight, self.weight_grad, self.grads.get("bias"),
+                            self._buf("h", (x.shape[0], self.K * self.channels)), self.K, self.lambda_max,
+                            self._scratch_buf(x.shape[0]), dx, col_block=self.col_block)
         return dx
 
 

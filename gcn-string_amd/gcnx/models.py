@@ -1491,7 +1491,7 @@ class GCN(_GraphRunner):
     PROBE_KEY = "conv1.lin.weight"       # the state_dict tensor whose second dimension is the input width
     EPS = D.TORCH_BN_EPS
     # ---- what a subclass with another convolution sets (and the hooks _initial, _conv_fwd, _conv_bwd) -------------------------
-    OPERATOR = "gcn"                     # _op: "gcn" | "mean" | "pattern" | "perm"
+    OPERATOR = "gcn"                     # _op: "gcn" | "mean" | "cheb" | "pattern" | "perm"
     SELF_LOOPS = True                    # a host adjacency gets PyG's add_remaining_self_loops (False: used as stored)
     LEADING_AXIS = ()                    # state_dict keys that carry a leading axis of 1 in PyG ([1, heads, C], [1, 3H])
     STACKS = {}                          # {key of a stacked tensor: the keys of its column blocks, each ``hidden`` wide, in storage
@@ -1704,7 +1704,8 @@ class GCN(_GraphRunner):
 
     def _op(self, batch):
         """The operator of the batch's unweighted pattern and what the backward walks, built once per batch object.  OPERATOR:
-        "gcn": A^ = D^-1/2 (A + I_missing) D^-1/2 and its transpose; "mean": the row-mean operator and its transpose; "pattern":
+        "gcn": A^ = D^-1/2 (A + I_missing) D^-1/2 and its transpose; "mean": the row-mean operator and its transpose; "cheb":
+        ChebConv's S = D^-1/2 A D^-1/2 without the loops (DeviceCSR.cheb_norm) and its transpose; "pattern":
         the pattern and its transpose; "perm": the pattern twice -- the backward walks its transposed pattern through the entry
         permutation (DeviceCSR.transpose_perm: the one a device loader's batch arrives with, or built here)."""
         if self._op_cache is None or self._op_cache[0] != batch.uid:
@@ -1713,7 +1714,7 @@ class GCN(_GraphRunner):
                 a.transpose_perm()
                 a_t = a
             else:
-                a = a.gcn_norm("pyg") if kind == "gcn" else a.row_mean() if kind == "mean" else a
+                a = a.gcn_norm("pyg") if kind == "gcn" else a.row_mean() if kind == "mean" else a.cheb_norm() if kind == "cheb" else a
                 a_t = a.transpose()
             self._op_cache = (batch.uid, a, a_t)
         return self._op_cache[1], self._op_cache[2]
@@ -2508,6 +2509,83 @@ class APPNP(GCN):
         w, b, _ = self._KEYS[k]
         convs.appnp_backward(self.ctx, a_t, x, dzk, p[w], g[w], g[b], bufs["t"], self.K, self.alpha, bufs["s2"], dx,
                              col_block=self._col_block)
+
+
+class Cheb(GCN):
+    """``GCN`` with each GCNConv replaced by PyG's ``ChebConv(in, hidden, K, normalization="sym", lambda_max)`` (Defferrard et al.
+    2016; Spektral's ChebConv with K one less), the K-hop layer with one weight matrix per hop distance, for the slot the
+    reference's author left open (gcn_utills.py:804-806): with K = 3 .. 5 a residue's filter weighs "itself", "contacts" and
+    "contacts of contacts" separately, and because T_1 = L^ = -S at lambda_max = 2 it can learn differences between a residue and
+    its neighbourhood (a high-pass filter), which GCNConv's low-pass operator cannot.
+
+        ChebConv(F->H, K)·BN·PReLU -> ChebConv(H->H, K)·BN·PReLU -> global_max_pool -> the head of ``GCN``
+
+        ChebConv:  out = sum_{k < K} T_k(L^) x W_k + b     T_0 = I  T_1 = L^  T_k = 2 L^ T_{k-1} - T_{k-2}
+                   L^ = -(2 / lambda_max) S + (2 / lambda_max - 1) I      S = D^-1/2 A D^-1/2 without the loops (get_laplacian)
+
+    ``Cheb([ctx,] hidden_channels=64, K=3, lambda_max=2.0, num_classes=1, seed=0, comm=None, readout=, norm=)``: K the number of
+    terms, an int in 1 .. 16 (1: a node MLP); lambda_max a number > 0 -- nothing is estimated, and a value below the operator's
+    largest eigenvalue makes the terms grow with k.  The adjacency is used as stored, unweighted: a stored loop is ignored, an
+    isolated node gets L^ z = (2 / lambda_max - 1) z.  Everything else is ``GCN``'s: BN·PReLU, the pool pair, the head,
+    readout="attention", norm="graph", ``fit``, and sync-BN over shards (``comm=``): no term crosses a graph.
+
+    Hot path per layer (cheb_forward / cheb_backward of gcnx/convs.py; gcnx.ChebConv runs the same two functions): gcnx_gemm
+    (H = x [W_0 | .. | W_{K-1}]), then gcnx_cheb_sum (csrc/cheb.hip) -- Clenshaw summation, K - 1 gathers in one launch that keeps
+    each graph's rows in LDS, or K - 1 launches where the library streams (fewer than 3 gathers -- 2 on graphs of up to 256 rows
+    --, hidden_channels not a multiple of 4, a graph too tall for LDS, a batch that does not know its tallest graph); backward
+    gcnx_cheb_basis on the transposed operator (G = [T_k(L^^T) dZ], K - 1 gathers), one gcnx_gemm_dw and one gcnx_gemm_dx over
+    the K H wide panel.  Nothing is kept for the backward.  GCNX_CHEB_RESIDENT=0 (read at construction) streams always.
+
+    Weights: PyG's key names ``conv{1,2}.lins.{k}.weight`` ([out, in], as torch; the column blocks of one stacked [in, K out]
+    tensor here), ``conv{1,2}.bias``, then ``GCN``'s.  Initialisation as PyG's: glorot-uniform weights drawn conv1.lins.0 ..
+    conv2.lins.{K-1}, zero biases, then the head.  The order follows PyG's source, not a live module: prefer the named dicts."""
+
+    PROBE_KEY = "conv1.lins.0.weight"
+    OPERATOR, SELF_LOOPS, KERNELS = "cheb", False, "Chebyshev"
+    MAX_K = 16
+
+    def _init(self, ctx, hidden_channels=64, K=3, lambda_max=2.0, num_classes=1, seed=0, comm=None):
+        if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or not 1 <= int(K) <= self.MAX_K:
+            raise NotImplementedError(f"{self._name}: K={K!r} must be an int in 1 .. {self.MAX_K} (what the {self.KERNELS} kernels serve)")
+        if not float(lambda_max) > 0.0 or not np.isfinite(float(lambda_max)):
+            raise ValueError(f"{self._name}: lambda_max={lambda_max!r} must be a finite number > 0")
+        self.K, self.lambda_max = int(K), float(lambda_max)
+        super()._init(ctx, hidden_channels, num_classes, seed, comm)
+        self._col_block = 0 if os.environ.get("GCNX_CHEB_RESIDENT", "1") != "0" else -1     # knob, read once
+        blocks = lambda c: tuple(f"w{c}_{k}" for k in range(self.K))
+        self.STACKS = {"w1": blocks(1), "w2": blocks(2)}        # lins.k.weight^T: the column blocks of the stacked weights
+        keys = lambda c: tuple((f"conv{c}.lins.{k}.weight", f"w{c}_{k}", True) for k in range(self.K)) + ((f"conv{c}.bias", f"b{c}", False),)
+        self.TORCH_KEYS = keys(1) + keys(2) + GCN.TORCH_KEYS[4:]
+
+    def _shapes(self, f_in):
+        s = super()._shapes(f_in)
+        s.update(w1=(f_in, self.K * self.hidden), w2=(self.hidden, self.K * self.hidden))
+        return s
+
+    def _initial(self, f_in, shapes, offs):
+        h, rng = self.hidden, self._rng
+        stack = lambda f: np.concatenate([glorot_uniform(rng, f, h) for _ in range(self.K)], axis=1)
+        return {"w1": stack(f_in), "w2": stack(h), **self._head_initial(shapes)}
+
+    def _ensure(self, batch, sharded=False):
+        bufs = super()._ensure(batch, sharded)
+        if "ch" not in bufs:                # H = x W and G = [T_k(L^^T) dZ]: one [n, K hidden] panel serves both directions
+            bufs["ch"] = self._views()("cheb_panel", batch.n, self.K * self.hidden)
+        return bufs
+
+    def _conv_fwd(self, s_op, x, k, bufs, keep):
+        """z_k = sum_j T_j(L^) (x W_k)_j + b_k: the product into bufs["ch"], then the Clenshaw sum."""
+        p = self.p
+        w, b, z = self._KEYS[k]
+        convs.cheb_forward(self.ctx, s_op, x, p[w], p[b], bufs["ch"], bufs[z], self.K, self.lambda_max, bufs["s2"],
+                           col_block=self._col_block)
+
+    def _conv_bwd(self, s_t, x, k, dzk, bufs, dx):
+        """dZ_k -> the bias gradient, G = [T_j(L^^T) dZ_k] in bufs["ch"], dW = x^T G and, with dx, dx = G W^T."""
+        p, g = self.p, self.g
+        w, b, _ = self._KEYS[k]
+        convs.cheb_backward(self.ctx, s_t, x, dzk, p[w], g[w], g[b], bufs["ch"], self.K, self.lambda_max, bufs["s2"], dx,
+                            col_block=self._col_block)
 
 
 class PNA(GCN):

@@ -1423,6 +1423,64 @@ GCNX_API int gcnx_appnp_propagate(gcnx_ctx* ctx, const int32_t* rowptr, const in
                                   const int32_t* graph_ptr, int32_t b, int32_t max_graph_rows, const float* x, int64_t ldx, int32_t n,
                                   int32_t f, int32_t k, float alpha, int32_t col_block, float* out, int64_t ldo, float* scratch);
 
+/* ---- ChebConv: k Chebyshev filter terms of the scaled Laplacian (csrc/cheb.hip) ----
+ * PyG's ChebConv(in, out, K, normalization="sym", lambda_max) -- Spektral's ChebConv(channels, K) with K one less --, the K-hop
+ * layer with one weight matrix per hop distance for the slot the reference's author left open (gcn_utills.py:804-806).  On the
+ * operator S of gcnx_cheb_norm, with c_s = -2 / lambda_max and c_d = 2 / lambda_max - 1, each rounded once to fp32 on the host:
+ *     L^ z = c_s (S z) + c_d z        T_0 z = z      T_1 z = L^ z      T_j z = 2 L^ T_{j-1} z - T_{j-2} z
+ * Per element and step: acc = +0, acc = fmaf(vals[e], cur[colidx[e]], acc) over the row's entries in CSR order, then
+ * fmaf(a, acc, fmaf(b, cur[i], d)) with
+ *     basis step j = 1 .. k-1:  (a, b) = (c_s, c_d) at j = 1, else (2 c_s, 2 c_d);  cur = T_{j-1} x,  d = -T_{j-2} x [i]  (-0 at j = 1)
+ *     sum step j = k-2 .. 0:    (a, b) = (c_s, c_d) at j = 0, else (2 c_s, 2 c_d);  cur = b_{j+1},  d = H_j[i] - b_{j+2}[i]
+ *                               (b_{k-1} = H_{k-1}, b_k = +0);  step 0 then adds bias[column] (bias NULL: nothing is added)
+ * Both routes below and every column block evaluate exactly that, so they leave the same bits.  The layer is H = x W (one
+ * gcnx_gemm, W = [lins.0.weight^T | .. | lins.{k-1}.weight^T]) and gcnx_cheb_sum; its backward gcnx_cheb_basis on the
+ * transposed operator applied to dZ (G_j = T_j(L^^T) dZ, one panel [n, k f]), then dW = x^T G and dx = G W^T.  Nothing is kept
+ * for it.  A lambda_max below the operator's largest eigenvalue makes the terms grow with j.
+ *
+ * gcn_utills.py:804-806 -- vals_out [nnz] = the values of S on the stored pattern (row = target, column = source; vals NULL: ones):
+ *     S[i, j] = r_i w_ij r_j  for a stored i != j,  exactly +0 for a stored diagonal entry;   r_j = deg_j^-1/2,
+ *     deg_j = sum_{i != j} w_ij over column j,  r_j = 0 where deg_j <= 0        (PyG's get_laplacian: loops removed, the degree
+ * scattered on the source index).  rowptr_t / colidx_t / vals_t: the transposed CSR, which gives the column sums without atomics
+ * (the same three pointers for a symmetric operator; vals_t NULL exactly when vals is).  Degrees are summed in fp64 in CSR
+ * order: two calls leave the same bits.  vals_out may be vals.  Uses the context's workspace (n floats): not capturable.
+ * S^T is the transpose of S's values (gcnx_csr_transpose), not this call on the transposed pattern. */
+GCNX_API int gcnx_cheb_norm(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, const float* vals, const int32_t* rowptr_t,
+                            const int32_t* colidx_t, const float* vals_t, int32_t n, float* vals_out);
+/* gcn_utills.py:804-806 -- 1 if the one-launch (resident) route serves a batch whose tallest graph has max_graph_rows rows:
+ * max_graph_rows > 0, f and ld (the leading dimension of the call's input: x or h) multiples of 4 with ld >= f, and two buffers
+ * of max_graph_rows x 4 floats plus the graph's row pointers within 128 KiB of LDS (graphs of up to 3640 rows).  Operands off a
+ * 16-byte boundary take the streamed route. */
+GCNX_API int gcnx_cheb_resident_ok(int64_t max_graph_rows, int32_t f, int64_t ld);
+/* gcn_utills.py:804-806 -- floats of `scratch` for the streamed route of gcnx_cheb_sum with k >= 3: n * f.  Answers without a
+ * context. */
+GCNX_API int64_t gcnx_cheb_scratch_floats(int64_t n, int32_t f);
+/* gcn_utills.py:804-806 -- gcnx_cheb_basis: block j (columns j f .. (j + 1) f) of out [n, k f] (ldo) = T_j(L^) x for j = 0 .. k-1,
+ * from x [n, f] (ldx).  gcnx_cheb_sum: out [n, f] (ldo) = sum_j T_j(L^) H_j + bias from h [n, k f] (ldh; H_j its block j) by the
+ * Clenshaw steps above; bias [f] may be NULL.  Both run k - 1 gathers; k == 1 runs none (out = x; out = h + bias).
+ * rowptr / colidx / vals (NULL: ones), graph_ptr [b + 1] (may be NULL), b and max_graph_rows (0: unknown) as in
+ * gcnx_appnp_propagate.  Resident route (one launch): a workgroup per (graph, block of col_block columns) keeps two terms of the
+ * graph's slice in LDS across all steps -- the new term overwrites the term two steps back --, one workgroup barrier per step;
+ * an entry whose column lies outside its graph's rows contributes nothing (no access is out of range; the result for such
+ * input is unspecified); a graph with more than max_graph_rows rows is left untouched.  Streamed route (k - 1 launches of a
+ * one-hop gather): any n, f, leading dimension and alignment; gcnx_cheb_basis keeps its terms in the blocks of out and does not
+ * read scratch (may be NULL); gcnx_cheb_sum alternates between out and scratch (gcnx_cheb_scratch_floats; may be NULL for
+ * k <= 2) so that step 0 lands in out.  col_block 0: the library's choice -- resident where graph_ptr is given,
+ * gcnx_cheb_resident_ok holds, input and out are 16-byte aligned with ldo % 4 == 0 and k - 1 >= 3 (k - 1 >= 2 where
+ * max_graph_rows <= 256), in the column block gcnx_appnp_propagate would choose; otherwise streamed.  col_block > 0: the
+ * resident route with that block, GCNX_ERR_UNSUPPORTED with nothing launched where it is not served (not a multiple of 4, wider
+ * than f or 256, too tall for LDS, or any condition above; k == 1 gathers nothing on any route).  col_block -1: streamed.
+ * n == 0, f == 0 or b == 0 (with graph_ptr): GCNX_OK, nothing launched.  GCNX_ERR_INVALID: k outside 1 .. 16, lambda_max not a
+ * finite number > 0, col_block < -1, a leading dimension below its operand's width, out overlapping the input, bias or scratch
+ * (or scratch overlapping the input), the streamed route of gcnx_cheb_sum with k >= 3 and scratch NULL.  No atomics, no
+ * read-back, nothing allocated: capture-safe, and two calls leave the same bits. */
+GCNX_API int gcnx_cheb_basis(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, const float* vals, const int32_t* graph_ptr,
+                             int32_t b, int32_t max_graph_rows, const float* x, int64_t ldx, int32_t n, int32_t f, int32_t k,
+                             float lambda_max, int32_t col_block, float* out, int64_t ldo, float* scratch);
+GCNX_API int gcnx_cheb_sum(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, const float* vals, const int32_t* graph_ptr,
+                           int32_t b, int32_t max_graph_rows, const float* h, int64_t ldh, const float* bias, int32_t n, int32_t f,
+                           int32_t k, float lambda_max, int32_t col_block, float* out, int64_t ldo, float* scratch);
+
 /* ---- aggregation with bf16 features ("fp32 and bf16 both reported") ----
  * out[t, :] = bf16(act(sum_e vals[e] * h[colidx[e], :] + bias)): GCNConv.call's / GeneralConv's aggregation (gcn.py:334) on
  * activations stored as bf16 (uint16_t bit patterns), fp32 accumulation, round-to-nearest-even on the way out; bias fp32
