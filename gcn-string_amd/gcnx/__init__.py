@@ -12,7 +12,7 @@ from .loader import Dataset, DisjointLoader, Graph, ListDataset, NetworkxDataset
 from .train import PiecewiseConstantDecay, auc, binary_acc, fit, roc_curve
 
 __all__ = ["Dataset", "DisjointLoader", "Graph", "ListDataset", "NetworkxDataset", "from_networkx", "entry_edge_features", "format_graph", "SparseTensor", "Context", "default_context", "GCNConv", "GeneralConv",
-           "ECCConv", "SAGEConv", "GINConv", "GINEConv", "PDNConv", "APPNPConv", "ChebConv", "PNAConv", "GATConv", "GATv2Conv", "ResGatedGraphConv", "TransformerConv", "TopKPool", "GlobalSumPool", "GlobalAvgPool", "GlobalMaxPool", "GlobalAttnSumPool", "Dense", "BatchNorm1d", "GraphNorm", "PReLU", "GCN2", "GCN", "SAGE", "GIN", "GINE", "PDN", "APPNP", "Cheb", "PNA", "GAT", "GATv2", "ResGated", "Transformer", "GeneralGNN", "ECCNet", "TopKNet", "DeviceBatch", "Explainer", "Explanation",
+           "ECCConv", "SAGEConv", "GINConv", "GINEConv", "PDNConv", "APPNPConv", "ChebConv", "RGCNConv", "PNAConv", "GATConv", "GATv2Conv", "ResGatedGraphConv", "TransformerConv", "TopKPool", "GlobalSumPool", "GlobalAvgPool", "GlobalMaxPool", "GlobalAttnSumPool", "Dense", "BatchNorm1d", "GraphNorm", "PReLU", "GCN2", "GCN", "SAGE", "GIN", "GINE", "PDN", "APPNP", "Cheb", "RGCN", "PNA", "GAT", "GATv2", "ResGated", "Transformer", "GeneralGNN", "ECCNet", "TopKNet", "DeviceBatch", "Explainer", "Explanation",
            "save_to_npz", "load_weights_npz", "best_epoch", "DeviceDataset", "DeviceDisjointLoader",
            "PiecewiseConstantDecay", "Adam", "SGD", "fit", "roc_curve", "auc", "binary_acc"]
 
@@ -21,13 +21,13 @@ def __getattr__(name):  # device-side names load libgcnx lazily, host-only use n
     if name in ("Context", "default_context", "DeviceArray", "DeviceCSR", "Segments"):
         from . import device
         return getattr(device, name)
-    if name in ("GCNConv", "GeneralConv", "ECCConv", "SAGEConv", "GINConv", "GINEConv", "PDNConv", "APPNPConv", "ChebConv", "PNAConv", "GATConv", "GATv2Conv", "ResGatedGraphConv", "TransformerConv", "TopKPool", "GlobalSumPool", "GlobalAvgPool", "GlobalMaxPool", "GlobalAttnSumPool", "Dense", "BatchNorm1d", "GraphNorm", "PReLU"):
+    if name in ("GCNConv", "GeneralConv", "ECCConv", "SAGEConv", "GINConv", "GINEConv", "PDNConv", "APPNPConv", "ChebConv", "RGCNConv", "PNAConv", "GATConv", "GATv2Conv", "ResGatedGraphConv", "TransformerConv", "TopKPool", "GlobalSumPool", "GlobalAvgPool", "GlobalMaxPool", "GlobalAttnSumPool", "Dense", "BatchNorm1d", "GraphNorm", "PReLU"):
         from . import layers
         return getattr(layers, name)
     if name in ("DeviceDataset", "DeviceDisjointLoader", "collate_on_device"):
         from . import device_loader
         return getattr(device_loader, name)
-    if name in ("GCN2", "GCN", "SAGE", "GIN", "GINE", "PDN", "APPNP", "Cheb", "PNA", "GAT", "GATv2", "ResGated", "Transformer", "GeneralGNN", "ECCNet", "TopKNet", "DeviceBatch", "evaluate"):
+    if name in ("GCN2", "GCN", "SAGE", "GIN", "GINE", "PDN", "APPNP", "Cheb", "RGCN", "PNA", "GAT", "GATv2", "ResGated", "Transformer", "GeneralGNN", "ECCNet", "TopKNet", "DeviceBatch", "evaluate"):
         from . import models
         return getattr(models, name)
     if name in ("Explainer", "Explanation"):

@@ -22,6 +22,8 @@ NORM_SPEKTRAL, NORM_PYG = 0, 1
 RED_SUM, RED_MAX = 0, 1
 CCE_PROBS, CCE_LOGITS = 0, 1
 CSR_SYMMETRIC, CSR_BLOCK_DIAGONAL, CSR_GRAPH_PTR_OK = 1, 2, 4
+RGCN_NONZERO, RGCN_INDEX = 0, 1
+RGCN_RULES = {"nonzero": RGCN_NONZERO, "index": RGCN_INDEX}
 UNIQUE_ID_BYTES = 128
 
 ACTS = {None: ACT_NONE, "linear": ACT_NONE, "none": ACT_NONE, "relu": ACT_RELU, "prelu": ACT_PRELU,
@@ -232,6 +234,10 @@ SIGNATURES = {
     "gcnx_cheb_scratch_floats": [_i64, _i32],
     "gcnx_cheb_basis": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _i32, _i32, _i32, _f32, _i32, _vp, _i64, _vp],
     "gcnx_cheb_sum": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _i32, _i32, _i32, _f32, _i32, _vp, _i64, _vp],
+    "gcnx_rgcn_operator": [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _i32, _i64, _vp, _vp, _vp, _vp],
+    "gcnx_rgcn_conv_ok": [_i64, _i32, _i32, _i32, _i64],
+    "gcnx_rgcn_conv": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _int, _i32, _i32, _int, _vp, _vp, _i64, _vp, _i64],
+    "gcnx_rgcn_aggregate": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _i64],
     "gcnx_comm_unique_id": [C.c_char_p],
     "gcnx_comm_init_rank": [_vp, C.c_char_p, _int, _int, C.POINTER(_vp)],
     "gcnx_comm_destroy": [_vp],

@@ -1,6 +1,6 @@
 """The launch sequences of the convolutions that a layer (gcnx.layers) and a model (gcnx.models) both run: PNAConv, GATConv,
-GATv2Conv, ResGatedGraphConv, TransformerConv, GINEConv, PDNConv (with the GCNConv sequence it is built on), APPNPConv and
-ChebConv.  This is the one place they are written down.
+GATv2Conv, ResGatedGraphConv, TransformerConv, GINEConv, PDNConv (with the GCNConv sequence it is built on), APPNPConv,
+ChebConv and RGCNConv.  This is the one place they are written down.
 
 One forward and one backward function per convolution, plain functions over operands: ``ctx``, the pattern, the operands, the
 parameter views, the gradient views, every scratch and output buffer, then the scalars.  The caller owns the storage, the
@@ -10,8 +10,8 @@ validates.  An optional operand is ``None`` and drops exactly its launch or argu
 stored [in, out].  ``h`` below is the convolution's output width (heads * channels); whether a stacked P = ... | S carries the
 root block S is read off its width (4 h, or 3 h without root_weight).
 
-SAGEConv and GINConv are not here: layer and model choose their one-launch route by different predicates.  GINEConv's two
-routes are here; the caller decides between them (``one_launch``) by its own predicate."""
+SAGEConv and GINConv are not here: layer and model choose their one-launch route by different predicates.  GINEConv's and
+RGCNConv's two routes are here; the caller decides between them (``one_launch``) by its own predicate."""
 from __future__ import annotations
 
 from . import device as D
@@ -271,3 +271,57 @@ def cheb_backward(ctx, a_t, x, dz, w, g_w, g_bias, g, k, lambda_max, scratch, dx
     D.gemm_dw(ctx, x, g, g_w)                                                              # dW = x^T G
     if dx is not None:
         D.gemm_dx(ctx, g, w, dx)                                                           # dx = G W^T
+
+
+# ---- RGCNConv ----------------------------------------------------------------------------------------------------------------
+def _rgcn_blocks(w, r, fi, fo, root_weight):
+    """(W_rel [r fi, fo], W_root [fi, fo] or None): the two parts of the row-stacked weight, as views."""
+    return w.flat(0, r * fi * fo, (r * fi, fo)), w.flat(r * fi * fo, fi * fo, (fi, fo)) if root_weight else None
+
+
+def rgcn_forward(ctx, a, ops, x, w, bias, m, out, h_tmp, r, root_weight, one_launch, keep=True):
+    """out = [A_0 x | .. | A_{r-1} x | x] w + bias.  a: the pattern; ops = (rel, val, rel_t, val_t) of DeviceCSR.rgcn_operator;
+    w: the row-stacked [W_0; ..; W_{r-1}; W_root] (r blocks without root_weight).  one_launch: gcnx_rgcn_conv, which stores the
+    panel M = [A_0 x | .. | A_{r-1} x] into m only with ``keep`` (a backward follows); otherwise the composed route:
+    gcnx_rgcn_aggregate into m, gcnx_gemm over M and, with root_weight, gcnx_gemm over x into h_tmp and gcnx_add."""
+    rel, val = ops[0], ops[1]
+    if one_launch:
+        D.rgcn_conv(ctx, a.rowptr, a.colidx, rel, val, x, w, bias, out, r, root_weight, m=m if keep else None)
+        return
+    fi, fo = x.shape[1], out.shape[1]
+    w_rel, w_root = _rgcn_blocks(w, r, fi, fo, root_weight)
+    D.rgcn_aggregate(ctx, a.rowptr, a.colidx, rel, val, x, m, r)
+    D.gemm(ctx, m, w_rel, bias, out)
+    if root_weight:
+        D.gemm(ctx, x, w_root, None, h_tmp)
+        D.add(ctx, out, h_tmp, out)
+
+
+def rgcn_backward(ctx, a, ops, x, m, dz, w, g_w, g_bias, mt, r, root_weight, one_launch, dx):
+    """From dz: the bias gradient (its column sums), dW_rel = M^T dz and dW_root = x^T dz (one gcnx_gemm_dw2 where the root block
+    starts on a 16-byte boundary) and, with dx, dx = dz W_root^T + sum_q A_q^T (dz W_q^T): gcnx_rgcn_conv on the transposed
+    pattern (a.transpose_perm()) with rel_t / val_t and the weights as stored (one_launch), or gcnx_rgcn_aggregate of dz into mt
+    [n, r fo] and one gcnx_gemm_dx per block."""
+    fi, fo = x.shape[1], dz.shape[1]
+    w_rel, w_root = _rgcn_blocks(w, r, fi, fo, root_weight)
+    g_rel, g_root = _rgcn_blocks(g_w, r, fi, fo, root_weight)
+    if g_bias is not None:
+        D.act_bias_grad(ctx, dz, None, dz, None, db=g_bias)                                # column sums of dZ
+    if root_weight and (r * fi * fo) % 4 == 0:
+        D.gemm_dw2(ctx, m, dz, g_rel, x, dz, g_root)                                       # dW_rel = M^T dZ, dW_root = x^T dZ
+    else:
+        D.gemm_dw(ctx, m, dz, g_rel)
+        if root_weight:
+            D.gemm_dw(ctx, x, dz, g_root)
+    if dx is None:
+        return
+    rp_t, ci_t, _ = a.transpose_perm()
+    rel_t, val_t = ops[2], ops[3]
+    if one_launch:
+        D.rgcn_conv(ctx, rp_t, ci_t, rel_t, val_t, dz, w, None, dx, r, root_weight, w_transposed=True)
+        return
+    D.rgcn_aggregate(ctx, rp_t, ci_t, rel_t, val_t, dz, mt, r)
+    if root_weight:
+        D.gemm_dx(ctx, dz, w_root, dx)                                                     # dZ W_root^T
+    for q in range(r):                                                                     # + (A_q^T dZ) W_q^T
+        D.gemm_dx(ctx, mt.cols(q * fo, (q + 1) * fo), w.flat(q * fi * fo, fi * fo, (fi, fo)), dx, accumulate=root_weight or q > 0)

@@ -390,6 +390,23 @@ class DeviceCSR:
                                    self.symmetric, self.max_block_rows)
         return self._cheb
 
+    def rgcn_operator(self, e, rule="nonzero", num_relations=None):
+        """RGCNConv's per-entry operands (gcnx_rgcn_operator): (rel, val, rel_t, val_t) -- rel [nnz] uint8, the relation of every
+        stored entry read off the edge features e [nnz, edge_dim], val [nnz] = 1 / (entries of the entry's row with its relation),
+        and both in the order of the transposed pattern (``transpose_perm``).  rule "nonzero": the first non-zero column of e,
+        edge_dim where there is none (num_relations = edge_dim + 1); "index": column 0 holds the relation, and a value outside
+        0 .. num_relations - 1 is clamped into that range on the device.  Not cached here: the caller keeps it with the batch."""
+        ctx, ne = self.ctx, max(self.nnz, 1)
+        edge_dim = e.shape[1]
+        r = edge_dim + 1 if num_relations is None and rule == "nonzero" else int(num_relations)
+        assert e.shape[0] >= self.nnz and rule in L.RGCN_RULES
+        _, _, perm = self.transpose_perm()
+        rel, rel_t = ctx.empty(ne, np.uint8), ctx.empty(ne, np.uint8)
+        val, val_t = ctx.empty(ne, np.float32), ctx.empty(ne, np.float32)
+        ctx._ck(ctx.lib.gcnx_rgcn_operator(ctx.h, self.rowptr.ptr, _p(e), e.ld, edge_dim, L.RGCN_RULES[rule], r, perm.ptr, self.n, self.nnz,
+                                           rel.ptr, val.ptr, rel_t.ptr, val_t.ptr))
+        return rel, val, rel_t, val_t
+
     def transpose(self):
         if self.symmetric:
             return self
@@ -899,6 +916,38 @@ def cheb_sum(ctx, a, h, bias, out, k, lambda_max=2.0, scratch=None, col_block=0)
     ctx._ck(ctx.lib.gcnx_cheb_sum(ctx.h, a.rowptr.ptr, a.colidx.ptr, _p(a.vals), *_cheb_graphs(a), _p(h), h.ld, _p(bias), n, f, int(k),
                                   float(lambda_max), int(col_block), _p(out), out.ld, _p(scratch)))
     return out
+
+
+def rgcn_conv_ok(ctx, n, fi, fo, num_relations, ldx=None):
+    """True if rgcn_conv serves these shapes (gcnx_rgcn_conv_ok)."""
+    return bool(ctx.lib.gcnx_rgcn_conv_ok(int(n), int(fi), int(fo), int(num_relations), int(ldx if ldx is not None else fi)))
+
+
+def rgcn_conv(ctx, rowptr, colidx, rel, val, x, w, bias, out, num_relations, root_weight=True, m=None, w_transposed=False):
+    """out = [A_0 x | .. | A_{R-1} x | x] w + bias in one launch (gcnx_rgcn_conv); A_r: the entries of relation ``rel`` == r with
+    their ``val`` (DeviceCSR.rgcn_operator).  w: the row-stacked [W_0; ..; W_{R-1}; W_root] ([(R + 1) fi, fo]; R blocks without
+    root_weight).  m (optional) receives the panel [A_0 x | .. | A_{R-1} x].  w_transposed: every block is [fo, fi] -- the
+    backward form dX = dZ W_root^T + sum_r A_r^T (dZ W_r^T) on the transposed pattern with rel_t / val_t and the layer's
+    weights as stored."""
+    n, fi = x.shape
+    r = int(num_relations)
+    nb = r + (1 if root_weight else 0)
+    fo = out.shape[1]
+    assert w.size == nb * fi * fo and w.contiguous and out.shape == (n, fo) and (bias is None or bias.shape == (fo,))
+    assert m is None or m.shape == (n, r * fi)
+    ctx._ck(ctx.lib.gcnx_rgcn_conv(ctx.h, rowptr.ptr, colidx.ptr, rel.ptr, val.ptr, _p(x), x.ld, n, fi, _p(w), 1 if root_weight else 0,
+                                   fo, r, 1 if w_transposed else 0, _p(bias), _p(m), m.ld if m is not None else 0, _p(out), out.ld))
+    return out
+
+
+def rgcn_aggregate(ctx, rowptr, colidx, rel, val, x, m, num_relations):
+    """m [n, R f] = [A_0 x | .. | A_{R-1} x] for any width, stride and alignment (gcnx_rgcn_aggregate), with the bits of
+    rgcn_conv's panel.  m must not alias x."""
+    n, f = x.shape
+    assert m.shape == (n, int(num_relations) * f)
+    ctx._ck(ctx.lib.gcnx_rgcn_aggregate(ctx.h, rowptr.ptr, colidx.ptr, rel.ptr, val.ptr, _p(x), x.ld, n, f, int(num_relations), _p(m),
+                                        m.ld))
+    return m
 
 
 def gin_conv_ok(ctx, n, k0, k1, k2=0, ldx=None):

@@ -10,6 +10,7 @@ names as its next step (gcn_utills.py:804-806); ``GATConv(channels, heads=1)`` i
 ``GINConv(channels, mlp_hidden=None, eps=0.0, train_eps=False)`` is PyG's / Spektral's Graph Isomorphism Network layer for it.
 ``GINEConv(channels, edge_dim, mlp_hidden=None, eps=0.0, train_eps=False)`` is PyG's GINEConv: GIN whose neighbour sum reads the edge features (gcn.py:71).
 ``ChebConv(channels, K=3, lambda_max=2.0)`` is PyG's Chebyshev spectral convolution: K filter terms, one weight matrix per hop distance.
+``RGCNConv(channels, num_relations=None, relations="nonzero", root_weight=True)`` is PyG's relational convolution (aggr="mean"): one weight matrix per edge type, the type read off the edge features.
 ``PNAConv(channels, deg=None, avg_deg_log=None)`` is PyG's PNAConv with the mean / min / max / std aggregators and the three degree scalers.
 ``GATv2Conv(channels, heads=1, edge_dim=None)`` is PyG's GATv2Conv: attention whose scores read the edge features (gcn.py:71).
 ``ResGatedGraphConv(channels, edge_dim=None, root_weight=True)`` is PyG's gated layer: per-channel sigmoid gates that read the edge features.
@@ -496,6 +497,137 @@ class ChebConv(Layer):
         convs.cheb_backward(self.ctx, a.transpose(), x, dy, self.weight, self.weight_grad, self.grads.get("bias"),
                             self._buf("h", (x.shape[0], self.K * self.channels)), self.K, self.lambda_max,
                             self._scratch_buf(x.shape[0]), dx, col_block=self.col_block)
+        return dx
+
+
+class RGCNConv(Layer):
+    """torch_geometric.nn.RGCNConv(in, channels, num_relations, aggr="mean", root_weight, bias) (Schlichtkrull et al. 2018)
+    without a decomposition: every stored entry has one of R <= 4 relations and every relation its own weight matrix -- the layer
+    that treats the reference's inter-chain DCA bridges differently from its intra-chain contacts (gcn_utills.py:319-443):
+
+        out_i = x_i W_root + b + sum_{r < R} mean_{k in N_r(i)} x_col(k) W_r        N_r(i): the entries of row i with relation r
+
+    ``RGCNConv(channels, num_relations=None, relations="nonzero", root_weight=True, use_bias=True, activation=None)``, called
+    as ``layer([x, a, e])`` with ``a = RGCNConv.preprocess(a)`` (the stored pattern, unweighted: no loop added or removed) and
+    e [nnz, edge_dim], one row per stored entry.  relations="nonzero": an entry's relation is the first non-zero column of its
+    row of e, edge_dim where there is none, so R = edge_dim + 1 (num_relations, if given, must say so); "index": e has one
+    column holding the relation as an integer-valued float, num_relations must be given, and a value outside 0 .. R - 1 is
+    clamped into that range on the device.  Relations and mean weights are built on every call (DeviceCSR.rgcn_operator, two
+    small launches): the layer keeps nothing that could outlive the contents of e (gcnx.RGCN keeps them per batch).  basis / block decomposition, aggr other than "mean" and an activation raise
+    NotImplementedError.
+
+    Parameters under PyG's names: ``weight`` ([R in, channels] here: PyG's [R, in, channels] with the first two axes merged;
+    glorot per relation), ``root`` [in, channels] (glorot) and ``bias`` (zeros).  weight and root are the row blocks of one
+    stored tensor ``stack`` [(R + 1) in, channels] (gradient ``stack_grad``), which the kernel reads as one matrix.
+
+    Launches (rgcn_forward / rgcn_backward of gcnx/convs.py, which the model runs too; csrc/rgcn.hip): gcnx_rgcn_conv where it
+    serves the shapes -- one launch, which keeps the panel M = [mean_0 x | .. | mean_{R-1} x] --, otherwise gcnx_rgcn_aggregate
+    and gcnx_gemm; backward gcnx_gemm_dw2 over M and x, and for dx the same launch on the transposed pattern."""
+
+    ALIGN = OWN_ALIGN = 4
+    MAX_RELATIONS = 4
+
+    def __init__(self, channels, num_relations=None, relations="nonzero", root_weight=True, use_bias=True, activation=None, fused=True,
+                 num_bases=None, num_blocks=None, aggr="mean", **kw):
+        super().__init__(**kw)
+        if activation not in (None, "linear"):
+            raise NotImplementedError(f"RGCNConv activation {activation!r}: the layer is linear (follow it with BatchNorm1d / PReLU)")
+        if num_bases is not None or num_blocks is not None or aggr != "mean":
+            raise NotImplementedError("RGCNConv: basis / block decomposition and aggr other than \"mean\" have no kernel")
+        if relations not in ("nonzero", "index"):
+            raise ValueError(f"RGCNConv relations={relations!r} must be \"nonzero\" or \"index\"")
+        if relations == "index" and num_relations is None:
+            raise ValueError("RGCNConv relations=\"index\" needs num_relations")
+        if num_relations is not None and (isinstance(num_relations, bool) or not isinstance(num_relations, (int, np.integer))
+                                          or not 1 <= int(num_relations) <= self.MAX_RELATIONS):
+            raise NotImplementedError(f"RGCNConv num_relations={num_relations!r} must be an int in 1 .. {self.MAX_RELATIONS}")
+        self.channels, self.R, self.relations = int(channels), None if num_relations is None else int(num_relations), relations
+        self.root_weight, self.use_bias, self.activation, self.fused = bool(root_weight), bool(use_bias), activation, bool(fused)
+
+    @staticmethod
+    def preprocess(a):
+        return _unweighted(a)
+
+    def _param_spec(self, in_dim):
+        r, c = self.R, self.channels
+        spec = [("weight", (r * in_dim, c), np.concatenate([glorot_uniform(self._rng, in_dim, c) for _ in range(r)], axis=0))]
+        if self.root_weight:
+            spec.append(("root", (in_dim, c), glorot_uniform(self._rng, in_dim, c)))
+        if self.use_bias:
+            spec.append(("bias", (c,), np.zeros(c, np.float32)))
+        return spec
+
+    def n_params(self, in_dim):
+        return sum(-(-int(np.prod(s)) // self.ALIGN) * self.ALIGN for s in self._stored_shapes(in_dim))
+
+    def _stored_shapes(self, in_dim):
+        nb = self.R + (1 if self.root_weight else 0)
+        return [(nb * in_dim, self.channels)] + ([(self.channels,)] if self.use_bias else [])
+
+    def build(self, ctx, in_dim, p_store=None, g_store=None, offset=0):
+        """weight and root go into one stored tensor, row blocks of ``stack``; then the bias."""
+        self.ctx = ctx
+        init = {name: np.asarray(v, np.float32).reshape(shape) for name, shape, v in self._param_spec(in_dim)}
+        if p_store is None:
+            p_store, g_store, offset = ctx.zeros(self.n_params(in_dim)), ctx.zeros(self.n_params(in_dim)), 0
+        r, c, off = self.R, self.channels, offset
+        nw = self._stored_shapes(in_dim)[0][0] * c
+        self.stack, self.stack_grad = p_store.flat(off, nw, (nw // c, c)), g_store.flat(off, nw, (nw // c, c))
+        parts = [("weight", 0, r * in_dim)] + ([("root", r * in_dim, in_dim)] if self.root_weight else [])
+        for name, row, rows in parts:
+            self.params[name] = self.stack.flat(row * c, rows * c, (rows, c))
+            self.grads[name] = self.stack_grad.flat(row * c, rows * c, (rows, c))
+        off += -(-nw // self.ALIGN) * self.ALIGN
+        if self.use_bias:
+            self.params["bias"], self.grads["bias"] = p_store.flat(off, c, (c,)), g_store.flat(off, c, (c,))
+            off += -(-c // self.ALIGN) * self.ALIGN
+        for name, v in init.items():
+            self.params[name].copy_from_host(v)
+        self.in_dim, self.built = in_dim, True
+        return off
+
+    def _pyg_keys(self, t):
+        return [(k, k, False) for k in t], []                       # PyG stores weight and root [in, out] too
+
+    def _pyg(self, t):
+        d = super()._pyg(t)
+        d["weight"] = d["weight"].reshape(self.R, -1, self.channels)
+        return d
+
+    def _one_launch(self, x, fo, *others):
+        return (self.fused and D.rgcn_conv_ok(self.ctx, x.shape[0], x.shape[1], fo, self.R, x.ld)
+                and all(v.ptr % 16 == 0 and v.ld % 4 == 0 for v in (x,) + others))
+
+    def call(self, inputs, out=None):
+        if len(inputs) != 3:
+            raise ValueError("RGCNConv takes [x, a, e]")
+        x, a, e = inputs
+        if e is None or len(e.shape) != 2 or e.shape[0] != a.nnz or (self.relations == "index" and e.shape[1] != 1):
+            raise ValueError(f"RGCNConv(relations={self.relations!r}): e must be [{a.nnz}, {'1' if self.relations == 'index' else 'edge_dim'}] "
+                             f"(one row per stored entry), got {None if e is None else list(e.shape)}")
+        if self.R is None:
+            self.R = e.shape[1] + 1
+            if not 1 <= self.R <= self.MAX_RELATIONS:
+                raise NotImplementedError(f"RGCNConv: edge_dim + 1 = {self.R} relations; 1 .. {self.MAX_RELATIONS} are served")
+        if self.relations == "nonzero" and self.R != e.shape[1] + 1:
+            raise ValueError(f"RGCNConv(relations=\"nonzero\"): num_relations={self.R} must be edge_dim + 1 = {e.shape[1] + 1}")
+        if not self.built:
+            self.build(x.ctx, x.shape[1])
+        n, c = x.shape[0], self.channels
+        y = out if out is not None else self._buf("y", (n, c))
+        m = self._buf("m", (n, self.R * x.shape[1]))
+        ops = a.rgcn_operator(e, self.relations, self.R)             # every call: e may have been refilled in place
+        convs.rgcn_forward(self.ctx, a, ops, x, self.stack, self.params.get("bias"), m, y, self._buf("h", (n, c)), self.R,
+                           self.root_weight, self._one_launch(x, c, y, m))
+        self._saved = (x, a, ops, m)
+        return y
+
+    def backward(self, dy, need_dx=True):
+        x, a, ops, m = self._saved
+        dx = self._buf("dx", x.shape) if need_dx else None
+        convs.rgcn_backward(self.ctx, a, ops, x, m, dy, self.stack, self.stack_grad, self.grads.get("bias"),
+                            self._buf("mt", (x.shape[0], self.R * self.channels)), self.R, self.root_weight,
+                            need_dx and self._one_launch(dy, self.in_dim, dx), dx)
         return dx
 
 

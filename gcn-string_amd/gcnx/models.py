@@ -21,6 +21,9 @@ aggregation and a two-layer MLP, one launch per convolution (csrc/gin.hip).
 ``GINE``: ``GIN`` with PyG's GINEConv(edge_dim): every message is relu(x_j + lin(e_ij)), the cheapest way to read the edge
 features (csrc/gine.hip); trains from the same batches as ``ResGated``.
 
+``RGCN``: ``GCN`` with PyG's RGCNConv(num_relations, aggr="mean", root_weight) in the place of both GCNConv layers: the contacts and
+the DCA bridges, which the edge features tell apart, get weights of their own; all relations from one gather (csrc/rgcn.hip).
+
 ``PNA``: ``GCN`` with PyG's PNAConv(mean / min / max / std, identity / amplification / attenuation) in the place of both
 GCNConv layers: four statistics of every neighbourhood from one gather (csrc/pna.hip).
 
@@ -2586,6 +2589,169 @@ class Cheb(GCN):
         w, b, _ = self._KEYS[k]
         convs.cheb_backward(self.ctx, s_t, x, dzk, p[w], g[w], g[b], bufs["ch"], self.K, self.lambda_max, bufs["s2"], dx,
                             col_block=self._col_block)
+
+
+class RGCN(GCN):
+    """``GCN`` with each GCNConv replaced by PyG's ``RGCNConv(in, hidden, num_relations, aggr="mean", root_weight, bias=True)``
+    (Schlichtkrull et al. 2018) without a decomposition: every stored entry has a type, and every type its own weights.  The
+    reference's graphs hold two kinds of edge -- the intra-chain contacts of each protein and the inter-chain DCA bridges that
+    link_graphs adds between them (gcn_utills.py:319) -- and mark them in the edge features: dca is set on the bridges only,
+    proximity on the contacts only (gcn_utills.py:379-443).  Every other model here sums both kinds through one weight matrix
+    or reads the two numbers as continuous features.
+
+        RGCNConv(F->H)·BN·PReLU -> RGCNConv(H->H)·BN·PReLU -> global_max_pool -> the head of ``GCN``
+
+        RGCNConv:  out_i = x_i W_root + b + sum_{r < R} mean_{k in N_r(i)} x_col(k) W_r      N_r(i): row i's entries of relation r
+
+    ``RGCN([ctx,] hidden_channels=64, num_relations=None, relations="nonzero", edge_dim=2, root_weight=True, num_classes=1,
+    seed=0, comm=None, readout=, norm=)``; R = num_relations is 1 .. 4.  The adjacency is used as stored, unweighted: no loop is
+    added or removed, a stored loop is an entry like any other, the mean over no entry is 0.  The relation of an entry is read
+    off ``batch.e`` on the device, once per batch (gcnx_rgcn_operator, kept with the batch's operator):
+
+      relations="nonzero"   the first column d with e[k, d] != 0; edge_dim where there is none; R = edge_dim + 1.  With the
+                            reference's features (dca, proximity): bridges 0, contacts 1, and 2 for an entry that carries
+                            neither (a stored loop, a proximity that processed to exactly 0).
+      relations="index"     e has one column holding the relation as an integer-valued float; num_relations must be given.
+                            Host inputs are checked in NumPy before the upload (ValueError for a value that is not an integer
+                            in 0 .. R - 1); a DeviceBatch is not read back: the kernel clamps a value outside the range into it.
+
+    The model reads ``batch.e`` (``uses_edge_features``): inputs are (x, a, e, i), a DeviceBatch that carries e, or the batches
+    of DeviceDisjointLoader(DeviceDataset(..., edge_features=True)).  Everything behind the convolutions is ``GCN``'s
+    (readout="attention", norm="graph" and ``fit`` included).  One device: ``comm`` is refused.
+
+    Hot path per convolution (rgcn_forward / rgcn_backward of gcnx/convs.py; gcnx.RGCNConv runs the same two functions):
+    gcnx_rgcn_conv, one launch that gathers a row's entries once into R accumulators and multiplies [means | own rows] with the
+    row-stacked weight (csrc/rgcn.hip), keeping the panel M = [mean_0 x | .. | mean_{R-1} x]; backward gcnx_act_bias_grad,
+    gcnx_gemm_dw2 (dW = M^T dZ, dW_root = x^T dZ) and, for conv2, the same launch on the transposed pattern.
+    GCNX_RGCN_FUSED=0 (read at construction), hidden_channels=256 and unaligned widths take the composed route per launch:
+    gcnx_rgcn_aggregate, gcnx_gemm (+ gcnx_gemm, gcnx_add for the root); gcnx_rgcn_aggregate and R + 1 gcnx_gemm_dx backward.
+
+    Weights: PyG's key names and layouts ``conv{1,2}.weight`` [R, in, out], ``conv{1,2}.root`` [in, out] (with root_weight),
+    ``conv{1,2}.bias`` [out], then ``GCN``'s.  Stored as one row-stacked [(R + 1) in, out] tensor per convolution, which the
+    kernel reads and whose gradient the weight-gradient launch writes.  Initialisation as PyG's: glorot-uniform weights, then
+    root, drawn conv1 before conv2, zero biases, then the head.  The order follows PyG's source, not a live module: prefer the
+    named dicts."""
+
+    OPERATOR, SELF_LOOPS, KERNELS = "perm", False, "RGCNConv"
+    MAX_RELATIONS = 4
+    RULES = ("nonzero", "index")
+    uses_edge_features = True
+    _KEYS = _conv_keys("w", "b", "z", "pm")
+    _rel_ops = None
+
+    def _init(self, ctx, hidden_channels=64, num_relations=None, relations="nonzero", edge_dim=2, root_weight=True, num_classes=1,
+              seed=0, comm=None):
+        self._one_device(comm)
+        if relations not in self.RULES:
+            raise ValueError(f"{self._name}: relations={relations!r} must be \"nonzero\" or \"index\"")
+        if relations == "index":
+            if num_relations is None:
+                raise ValueError(f"{self._name}: relations=\"index\" needs num_relations")
+            edge_dim = 1
+        else:
+            edge_dim = self._check_edge_dim(edge_dim)
+            if edge_dim is None:
+                raise ValueError(f"{self._name}: relations=\"nonzero\" reads the relation off the edge features; edge_dim must be 1 .. 3")
+            if num_relations is not None and int(num_relations) != edge_dim + 1:
+                raise ValueError(f"{self._name}: relations=\"nonzero\" has num_relations = edge_dim + 1 = {edge_dim + 1}, got "
+                                 f"num_relations={num_relations}")
+            num_relations = edge_dim + 1
+        if isinstance(num_relations, bool) or not isinstance(num_relations, (int, np.integer)) or \
+                not 1 <= int(num_relations) <= self.MAX_RELATIONS:
+            raise NotImplementedError(f"{self._name}: num_relations={num_relations!r} must be an int in 1 .. {self.MAX_RELATIONS} "
+                                      f"(what the {self.KERNELS} kernels serve)")
+        self.R, self.relations, self.edge_dim, self.root_weight = int(num_relations), relations, int(edge_dim), bool(root_weight)
+        super()._init(ctx, hidden_channels, num_classes, seed, None)
+        self._fused = os.environ.get("GCNX_RGCN_FUSED", "1") != "0"    # knob, read once
+        keys = lambda c: ((f"conv{c}.weight", f"wr{c}", False),) + (((f"conv{c}.root", f"wo{c}", False),) if self.root_weight else ()) + \
+            ((f"conv{c}.bias", f"b{c}", False),)
+        self.TORCH_KEYS = keys(1) + keys(2) + GCN.TORCH_KEYS[4:]
+
+    @property
+    def _nb(self):
+        return self.R + (1 if self.root_weight else 0)
+
+    def _shapes(self, f_in):
+        s = super()._shapes(f_in)
+        s.update(w1=(self._nb * f_in, self.hidden), w2=(self._nb * self.hidden, self.hidden))
+        return s
+
+    def _initial(self, f_in, shapes, offs):
+        h, rng = self.hidden, self._rng
+        stack = lambda f: np.concatenate([glorot_uniform(rng, f, h) for _ in range(self._nb)], axis=0)    # weight[0 .. R-1], root
+        return {"w1": stack(f_in), "w2": stack(h), **self._head_initial(shapes)}
+
+    def _name_blocks(self):
+        """conv{c}.weight and conv{c}.root: the two row blocks of the stacked tensor, in ``p`` and ``g`` alike."""
+        super()._name_blocks()
+        h, r = self.hidden, self.R
+        for t in (self.p, self.g):
+            for c, f in ((1, self.f_in), (2, h)):
+                t[f"wr{c}"] = t[f"w{c}"].flat(0, r * f * h, (r * f, h))
+                if self.root_weight:
+                    t[f"wo{c}"] = t[f"w{c}"].flat(r * f * h, f * h, (f, h))
+
+    def _named(self, t):
+        d = super()._named(t)
+        for c in (1, 2):                        # PyG's [R, in, out]
+            d[f"conv{c}.weight"] = d[f"conv{c}.weight"].reshape(self.R, -1, self.hidden)
+        return d
+
+    def _probe_f_in(self, d):
+        return int(np.asarray(d["conv1.weight"]).shape[-2])
+
+    def _host_state(self, d):
+        if not self.built and "conv1.weight" in d:
+            self.build(self._probe_f_in(d))
+        d = dict(d)
+        for c in (1, 2):                        # PyG's [R, in, out] into the stored [R in, out]
+            w = np.asarray(d.get(f"conv{c}.weight", ()))
+            if w.ndim == 3 and w.shape[0] == self.R:
+                d[f"conv{c}.weight"] = w.reshape(-1, w.shape[2])
+        return super()._host_state(d)
+
+    def _host_inputs(self, inputs):
+        """relations="index": the relation column of a host batch is checked here, before the upload."""
+        if self.relations == "index":
+            e = np.asarray(inputs[2])
+            if e.ndim == 2 and e.shape[1] == 1 and e.size and not (np.all(e == np.floor(e)) and e.min() >= 0 and e.max() <= self.R - 1):
+                raise ValueError(f"{self._name}(relations=\"index\"): e must hold integers in 0 .. {self.R - 1}")
+        return super()._host_inputs(inputs)
+
+    def _op(self, batch):
+        """The pattern with its transposed pattern, and (rel, val, rel_t, val_t) of the batch's edge features: built once per
+        batch object."""
+        fresh = self._op_cache is None or self._op_cache[0] != batch.uid
+        a, a_t = super()._op(batch)
+        if fresh or self._rel_ops is None:
+            self._rel_ops = a.rgcn_operator(batch.e, self.relations, self.R)
+        return a, a_t
+
+    def _ensure(self, batch, sharded=False):
+        bufs = super()._ensure(batch, sharded)
+        self._check_e(batch)
+        if "pm1" not in bufs:               # the panels M of both convolutions, and A^T dZ2's for the composed backward
+            v, n, r = self._views(), batch.n, self.R
+            bufs["pm1"], bufs["pm2"], bufs["pmt"] = v("pm1", n, r * batch.f), v("pm2", n, r * self.hidden), v("pmt", n, r * self.hidden)
+        return bufs
+
+    def _one_launch(self, x, fo, *others):
+        return (self._fused and D.rgcn_conv_ok(self.ctx, x.shape[0], x.shape[1], fo, self.R, x.ld)
+                and all(a.ptr % 16 == 0 and a.ld % 4 == 0 for a in (x,) + others))
+
+    def _conv_fwd(self, a, x, k, bufs, keep):
+        """z_k = [M | x] W_k + b_k, M = [mean_0 x | .. | mean_{R-1} x] kept in bufs["pm{k}"]: one launch, or the composed route."""
+        p = self.p
+        w, b, z, pm = self._KEYS[k]
+        convs.rgcn_forward(self.ctx, a, self._rel_ops, x, p[w], p[b], bufs[pm], bufs[z], bufs["h1"], self.R, self.root_weight,
+                           self._one_launch(x, self.hidden, bufs[z], bufs[pm]), keep)
+
+    def _conv_bwd(self, a, x, k, dzk, bufs, dx):
+        """dZ_k -> conv k's gradients and, with dx, dx = dZ_k W_root^T + sum_r A_r^T (dZ_k W_r^T)."""
+        p, g = self.p, self.g
+        w, b, _, pm = self._KEYS[k]
+        convs.rgcn_backward(self.ctx, a, self._rel_ops, x, bufs[pm], dzk, p[w], g[w], g[b], bufs["pmt"], self.R, self.root_weight,
+                            dx is not None and self._one_launch(dzk, x.shape[1], dx), dx)
 
 
 class PNA(GCN):

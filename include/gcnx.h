@@ -1481,6 +1481,46 @@ GCNX_API int gcnx_cheb_sum(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* 
                            int32_t b, int32_t max_graph_rows, const float* h, int64_t ldh, const float* bias, int32_t n, int32_t f,
                            int32_t k, float lambda_max, int32_t col_block, float* out, int64_t ldo, float* scratch);
 
+/* ---- RGCNConv: typed edges, every relation from one gather (csrc/rgcn.hip) -------------------------------------------------
+ * PyG's RGCNConv(in, out, num_relations, aggr = "mean", root_weight, bias) without a decomposition (Schlichtkrull et al. 2018):
+ *     out_i = x_i W_root + b + sum_{r < R} mean_{k in N_r(i)} x_col(k) W_r      N_r(i): the stored entries of row i of relation r
+ * on the pattern as stored (row = target, column = source): no loop is added or removed, the mean over no entry is 0.  R =
+ * num_relations is 1 .. 4.  In the reference's graphs the relation is in the edge features: gcn_utills.py:379-443 sets dca on the
+ * inter-chain bridges only and proximity on the intra-chain contacts only.
+ *
+ * gcnx_rgcn_operator: rel [nnz] (one byte per stored entry, 0 .. R-1) and val [nnz] = 1 / (entries of the entry's row with the
+ * entry's relation) from the edge features e [nnz, edge_dim] (lde).  rule GCNX_RGCN_NONZERO: the relation is the first column d
+ * with e[k, d] != 0, edge_dim where there is none; num_relations must be edge_dim + 1.  rule GCNX_RGCN_INDEX: column 0 holds the
+ * relation as an integer-valued float; a value outside 0 .. R-1 is clamped into it (a NaN reads 0).  One thread walks a row:
+ * no atomics.  perm_t (gcnx_csr_transpose_perm; may be NULL together with rel_t and val_t): rel_t[p] = rel[perm_t[p]] and
+ * val_t[p] = val[perm_t[p]], the operands of the backward on the transposed pattern (a second launch).  Capture-safe.
+ * GCNX_ERR_INVALID: a rule or num_relations outside its range, edge_dim < 1, lde < edge_dim, the rule NONZERO with
+ * num_relations != edge_dim + 1, perm_t / rel_t / val_t not all given or all NULL. */
+typedef enum { GCNX_RGCN_NONZERO = 0, GCNX_RGCN_INDEX = 1 } gcnx_rgcn_rule;
+GCNX_API int gcnx_rgcn_operator(gcnx_ctx* ctx, const int32_t* rowptr, const float* e, int64_t lde, int32_t edge_dim, int32_t rule,
+                                int32_t num_relations, const int32_t* perm_t, int32_t n, int64_t nnz, uint8_t* rel, float* val,
+                                uint8_t* rel_t, float* val_t);
+/* gcnx_rgcn_conv_ok: 1 if the one launch serves the shapes (fi and fo in {16, 32, 64, 128}, num_relations in 1 .. 4, ldx >= fi,
+ * ldx % 4 == 0, n * ldx * 4 < 2^32); gcnx_rgcn_conv returns GCNX_ERR_UNSUPPORTED otherwise, and for x, w, m or out off a 16-byte
+ * boundary, ldm < num_relations * fi, ldo < fo or either not a multiple of 4.
+ * gcnx_rgcn_conv: out [n, fo] (ldo) = [A_0 x | .. | A_{R-1} x | x] w + bias in one launch; A_r = the entries of relation r with
+ * their val.  w: the row-stacked blocks W_0 .. W_{R-1} and, with root_weight != 0, W_root behind them -- [(R + 1) fi, fo]
+ * contiguous; bias [fo] may be NULL.  m (may be NULL): receives the panel M = [A_0 x | .. | A_{R-1} x], [n, R fi] (ldm), the
+ * operand of the weight gradient dW = M^T dZ.  w_transposed != 0: every block is [fo, fi] -- the backward with respect to x,
+ * dX = dZ W_root^T + sum_r A_r^T (dZ W_r^T), as this call on (rowptr_t, colidx_t, rel_t, val_t) with x = dZ and the layer's
+ * weights as stored.  Every element of M is the chain acc = fma(val_k, x[col(k)], acc) over the row's entries of its relation in
+ * CSR order from +0 (no atomics: the same bits on every call, and the bits of gcnx_rgcn_aggregate); an entry whose column lies
+ * outside [0, n) adds nothing.  The outputs must not alias x or each other (GCNX_ERR_INVALID). */
+GCNX_API int gcnx_rgcn_conv_ok(int64_t n, int32_t fi, int32_t fo, int32_t num_relations, int64_t ldx);
+GCNX_API int gcnx_rgcn_conv(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, const uint8_t* rel, const float* val,
+                            const float* x, int64_t ldx, int32_t n, int32_t fi, const float* w, int root_weight, int32_t fo,
+                            int32_t num_relations, int w_transposed, const float* bias, float* m, int64_t ldm, float* out, int64_t ldo);
+/* The panel alone: m [n, R f] (ldm) = [A_0 x | .. | A_{R-1} x] for any f >= 1, stride and alignment (16-byte loads where f, ldx,
+ * ldm and the pointers allow them), with the chain of gcnx_rgcn_conv.  The composed route of the layer is this, then gcnx_gemm
+ * over M and over x.  GCNX_ERR_INVALID: num_relations outside 1 .. 4, f < 1, ldx < f, ldm < R f, m aliasing x. */
+GCNX_API int gcnx_rgcn_aggregate(gcnx_ctx* ctx, const int32_t* rowptr, const int32_t* colidx, const uint8_t* rel, const float* val,
+                                 const float* x, int64_t ldx, int32_t n, int32_t f, int32_t num_relations, float* m, int64_t ldm);
+
 /* ---- aggregation with bf16 features ("fp32 and bf16 both reported") ----
  * out[t, :] = bf16(act(sum_e vals[e] * h[colidx[e], :] + bias)): GCNConv.call's / GeneralConv's aggregation (gcn.py:334) on
  * activations stored as bf16 (uint16_t bit patterns), fp32 accumulation, round-to-nearest-even on the way out; bias fp32
