@@ -64,6 +64,7 @@ struct gcnx_ctx {
                              // 1.88 x for the row gather + hub segments, and 7-10 % faster since its index loads are few and wide.  GCNX_SPMM_CB=0:
                              // the r3 path; 2: the long rows' items first instead of dealt among the short rows' (no difference measured)
   int knob_dw2_feed = 1;     // GCNX_DW2_FEED=0: the dW1 + dW2 launch walks its interior tiles with gemm_f32_tile's loop (r13) instead of dw_tile_interior
+  int knob_dw2_graph = 1;    // GCNX_DW2_GRAPH=0: gcnx_gemm_dw2_graph_ok answers 0 -- dW2 = S2^T dZ2 on the fp32 MFMA again (gcnx_gemm_dw2; A/B only)
   int knob_pool_split = 0;   // GCNX_POOL_SPLIT=2..16: row slices per graph of the split global pool (0: the library's choice)
   // gcnx_h2d_async: a ring of pinned staging slots (allocated on first use), one event per slot -- a slot is reused only
   // after the copy out of it has completed

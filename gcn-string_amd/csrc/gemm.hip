@@ -28,6 +28,9 @@
 //   gcnx_gemm_dw2         f32, both products split: two dw_job on one plan -> gemm_f32_dw2_kernel / _dw2_head_kernel (head
 //                         leaves inside, else gcnx_head_from_parts first) -> reduce_sgd_kernel | else flush_pending,
 //                         gcnx_head_from_parts, gcnx_gemm_dw twice, gcnx_sgd
+//   gcnx_gemm_dw2_graph   f32 under a SUM / AVG pool with the byte image of [Y2 > 0] (gcnx_gemm_dw2_graph_ok): dw_job (dW1) + the
+//                         C tiles of a slice plan -> gemm_f32_dw2g_kernel (head leaves inside, else gcnx_head_from_parts first) ->
+//                         reduce_sgd_kernel with the scaled set | else GCNX_ERR_UNSUPPORTED, nothing launched
 //   gcnx_dense_bwd, gcnx_dense_bwd_deferred            f32, aligned, fi % 64 == 0: dense_bwd_split -> dX job + dw_job ->
 //                         gemm_f32_duo_kernel, then flush_pending (reduce_duo_kernel) or the record handed to the
 //                         caller | else gcnx_gemm_dx + gcnx_gemm_dw
@@ -608,7 +611,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_wide_kernel(const float* __
 //   [0, n_s)        fold this call's split-K slabs into dW (an interval of the flat gradient buffer) and update it;
 //   [.., + n_pc)    fold a PENDING column-sum reduction (gcnx_dense_bwd_deferred) and update its parameters;
 //   [.., + n_ps)    fold a PENDING split-K reduction and update its parameters;
-//   the rest        p -= lr * g for every parameter outside those three intervals, 256 per workgroup.
+//   [.., + sd.n)    fold the SCALED slabs of the mask-product route (SgdScaled) and update their parameters;
+//   the rest        p -= lr * g for every parameter outside those four intervals, 256 per workgroup.
 // params == NULL: the reductions only (gcnx_gemm_dw2 in a multi-GPU step: the all-reduce comes before the update).
 struct SgdPending {
   const float* cpart; int64_t crows; int32_t cf; int64_t coff;      // partial rows -> grads[coff, coff + cf)
@@ -624,10 +628,78 @@ __device__ __forceinline__ float splitk_sum(const float* __restrict__ part, int6
   return (s[0][el] + s[1][el]) + (s[2][el] + s[3][el]);              // the order of splitk_reduce_kernel
 }
 
+// The scaled fold of the mask-product route (gcnx_gemm_dw2_graph): g[k, j] = sum_s scale[graph(s), j] * slab_s[k, j] over the
+// slices s of the plan, scale[g, j] = dPooled[g, j] (SUM) or dPooled[g, j] * (1.0f / rows of g) (AVG: the product rounded
+// first, the value the backward launch scales its rows by).  Same scheme and order as splitk_group_sum: four groups of
+// consecutive slices, ascending, every load of a chunk -- the slabs through the range-checked descriptor, the scales of
+// the chunk's slices (a slot past the group takes the scale of the group's last slice and a slab value of +0.f) -- issued
+// before the first add; a term is ONE fmaf(scale, slab, acc), no rounded product; then (s0 + s1) + (s2 + s3).
+struct SgdScaled {
+  const float* slabs; int64_t total; int32_t nslices; int64_t off;   // slabs -> grads[off, off + total)
+  const int4* plan; const float* scale; int64_t ldscale; int32_t fo; int avg;
+  int n;                                                             // workgroups
+};
+
+template <int N>
+__device__ __forceinline__ float splitk_chunk_scaled(const float* __restrict__ base, const int4* __restrict__ plan, int cnt,
+                                                     uint32_t slab_bytes, uint32_t lane_bytes, const float* __restrict__ scale,
+                                                     int64_t ldscale, int col, int avg, float acc) {
+  const uint32_t bytes = (uint32_t)(min(cnt, N) - 1) * slab_bytes + min(256u, slab_bytes);
+  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)base, (short)0, (int)bytes, 0x00020000);
+  // the plan is read through the constant address space: wave-uniform entries come back as scalar loads, ahead of the
+  // vector loads, so that a scale load waits for nothing a slab load does not
+  typedef const int __attribute__((address_space(4)))* const_ints;
+  const const_ints cp = (const_ints)plan;
+  float v[N], sc[N], inv[N];
+  int eg[N];
+#pragma unroll
+  for (int u = 0; u < N; ++u) {
+    const int z = 4 * min(u, cnt - 1);
+    eg[u] = cp[z + 2]; inv[u] = __builtin_bit_cast(float, cp[z + 3]);
+  }
+#pragma unroll
+  for (int u = 0; u < N; ++u)
+    v[u] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
+        rs, lane_bytes + (u < cnt ? (uint32_t)u * slab_bytes : 0xFFFFFE00u), 0, 0));
+#pragma unroll
+  for (int u = 0; u < N; ++u) sc[u] = scale[(int64_t)eg[u] * ldscale + col];
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int u = 0; u < N; ++u) sc[u] = avg ? sc[u] * inv[u] : sc[u];
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int u = 0; u < N; ++u) acc = fmaf(sc[u], v[u], acc);
+  return acc;
+}
+
+__device__ __forceinline__ float splitk_sum_scaled(const SgdScaled& sd, int bx, float (*s)[64]) {
+  const int el = threadIdx.x & 63, grp = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t i = (int64_t)bx * 64 + el;
+  float acc = 0.f;
+  if (i < sd.total) {
+    const int per = (sd.nslices + 3) / 4;
+    const int z0 = grp * per, z1 = min(sd.nslices, z0 + per);
+    const int col = (int)(i % sd.fo);
+    const float* base = sd.slabs + (int64_t)z0 * sd.total + (int64_t)bx * 64;
+    if (per <= 16) {
+      if (z0 < z1) acc = splitk_chunk_scaled<16>(base, sd.plan + z0, z1 - z0, (uint32_t)sd.total * 4u, 4u * (uint32_t)el, sd.scale,
+                                                 sd.ldscale, col, sd.avg, acc);
+    } else {
+      for (int z = z0; z < z1; z += 32)
+        acc = splitk_chunk_scaled<32>(base + (int64_t)(z - z0) * sd.total, sd.plan + z, z1 - z, (uint32_t)sd.total * 4u, 4u * (uint32_t)el,
+                                      sd.scale, sd.ldscale, col, sd.avg, acc);
+    }
+  }
+  s[grp][el] = acc;
+  __syncthreads();
+  return (s[0][el] + s[1][el]) + (s[2][el] + s[3][el]);
+}
+
 __global__ __launch_bounds__(256) void reduce_sgd_kernel(const float* __restrict__ part, int64_t slab, int nsplit,
                                                          int64_t total, int n_s, float* __restrict__ params,
                                                          float* __restrict__ grads, int64_t off, int64_t n_params,
-                                                         float lr_arg, SgdPending pd, const float* __restrict__ lr_dev) {
+                                                         float lr_arg, SgdPending pd, const float* __restrict__ lr_dev,
+                                                         SgdScaled sd) {
   const float lr = lr_dev ? *lr_dev : lr_arg;            // (gcnx_set_lr_source)
   __shared__ float4 s4[128][2];
   float (*s)[64] = reinterpret_cast<float(*)[64]>(&s4[0][0]);
@@ -666,11 +738,21 @@ __global__ __launch_bounds__(256) void reduce_sgd_kernel(const float* __restrict
     return;
   }
   bid -= pd.n_ps;
+  if (bid < sd.n) {
+    const int64_t i = (int64_t)bid * 64 + (threadIdx.x & 63);
+    const bool own = (threadIdx.x >> 6) == 0 && i < sd.total;
+    const float p = own && params ? params[sd.off + i] : 0.f;
+    const float g = splitk_sum_scaled(sd, bid, s);
+    if (own) { grads[sd.off + i] = g; if (params) params[sd.off + i] = p - lr * g; }
+    return;
+  }
+  bid -= sd.n;
   const int64_t i = (int64_t)bid * 256 + threadIdx.x;
   if (i >= n_params || !params) return;
   if (i >= off && i < off + total) return;
   if (pd.n_pc && i >= pd.coff && i < pd.coff + pd.cf) return;
   if (pd.n_ps && i >= pd.soff && i < pd.soff + pd.total) return;
+  if (sd.n && i >= sd.off && i < sd.off + sd.total) return;
   params[i] = params[i] - lr * grads[i];
 }
 
@@ -924,6 +1006,157 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(const float* __restrict_
     }
     __builtin_amdgcn_wave_barrier();         // the strip is consumed before the next one overwrites it
   }
+}
+
+// ----------------------------------------------------------------------------------------------
+// dW2 from per-graph mask products (gcnx_gemm_dw2_graph).  With SUM / AVG pooling dZ2[r, j] = mask2[r, j] * dP[g(r), j]
+// (mask2 = [Y2 > 0], the byte image layer 2's forward stores; dP[g] = pool'(dPooled) of r's graph), so
+//   dW2[k, j] = sum_g dP[g, j] * C_g[k, j],   C_g = S2[rows of g, :]^T mask2[rows of g, :].
+// C_g has a 0/1 operand.  An fp32 number is exactly hi + mid + lo, three bf16 numbers (8 + 8 + 8 significand bits, each
+// rounded to nearest even from what the ones before left; the one exclusion: |x| < 2^-110, whose lo can underflow), and a
+// product piece x {0, 1} is exact: three passes of v_mfma_f32_16x16x32_bf16 into one fp32 accumulator -- lo, then mid, then
+// hi, per K step -- form C_g with exact products.  Only the order of the additions differs from the fp32 MFMA, at about a
+// fifth of its matrix-pipe cycles (3 passes of K = 32 for 8 of K = 4).  This is not bf16x3, which drops lo x lo.
+//
+// The rows are cut by a slice plan (gcnx_dw2_slice_plan): {row_begin, row_end, graph, 1 / rows of the graph} per slice, no
+// slice across two graphs.  A C tile is one 64 x 64 output tile of one slice, its slab [fi][fo] at c + slice * fi * fo;
+// reduce_sgd_kernel folds the slabs with dP as a per-column scale (SgdScaled).
+// LDS: one [64 m][32 k] bf16 image per piece of S2 and one [64 n][32 k] image of the mask (1.0 = 0x3F80 / 0), 80-byte row
+// stride as gemm_bf16_kernel (conflict-free ds_read_b128 operand reads): 20 480 B.  Thread t converts column t & 63 of the
+// eight rows 8 (t >> 6) .. + 7 of a K step: eight 4-byte loads of S2 (a wave reads whole 256-byte row segments), eight
+// byte loads of the mask, and one 16-byte LDS store per image (eight consecutive lanes cover the 32 banks once).
+// The loads go through buffer descriptors that end with the slice's last row: a row at or past row_end -- the ragged last
+// K step -- returns zeros from the range check and is NOT read, so no row of another graph enters a product.
+// ----------------------------------------------------------------------------------------------
+struct CJob {
+  const float* s; int64_t lds;            // S2 [n, fi]
+  const uint8_t* m8; int64_t ldm;         // [Y2 > 0] as bytes [n, fo]
+  float* c;                               // [nslices][fi * fo] slabs
+  const int4* plan;                       // [nslices] {row_begin, row_end, graph, bits of 1.0f / graph rows}
+  int32_t fi, fo;
+  int gx, gy;                             // tiles along fo, fi
+};
+constexpr int kCgImage = 64 * HLD;        // bf16 elements of one image
+constexpr int kCgLdsBytes = 4 * kCgImage * 2;
+
+__device__ __forceinline__ void cg_fetch(const __amdgpu_buffer_rsrc_t ra, const __amdgpu_buffer_rsrc_t rb, uint32_t oa, uint32_t ob,
+                                         uint32_t sa, uint32_t sb, float (&va)[8], uint32_t (&vb)[8]) {
+#pragma unroll
+  for (int r = 0; r < 8; ++r) va[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ra, oa + (uint32_t)r * sa, 0, 0));
+#pragma unroll
+  for (int r = 0; r < 8; ++r) vb[r] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rb, ob + (uint32_t)r * sb, 0, 0);
+}
+
+__device__ __forceinline__ void cg_tile(const CJob& j, int bid, __bf16* smem) {
+  __bf16(*As)[64][HLD] = reinterpret_cast<__bf16(*)[64][HLD]>(smem);                 // planes hi, mid, lo
+  __bf16(*Bs)[HLD] = reinterpret_cast<__bf16(*)[HLD]>(smem + 3 * kCgImage);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int bx = bid % j.gx, t = bid / j.gx, by = t % j.gy, sl = t / j.gy;
+  const int4 e = j.plan[sl];
+  const int row0 = __builtin_amdgcn_readfirstlane(e.x), nrows = __builtin_amdgcn_readfirstlane(e.y) - row0;
+  const int m0 = by * 64, n0 = bx * 64;
+  // descriptors: the slice's rows, from its first row's tile columns to the end of its last row's
+  const uint32_t sa = (uint32_t)j.lds * 4u, sb = (uint32_t)j.ldm;
+  const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc((void*)(j.s + (int64_t)row0 * j.lds + m0), (short)0,
+                                                                      (int)((uint32_t)(nrows - 1) * sa + 256u), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc((void*)(j.m8 + (int64_t)row0 * j.ldm + n0), (short)0,
+                                                                      (int)((uint32_t)(nrows - 1) * sb + 64u), 0x00020000);
+  const int kw = wave * 8;                                   // this thread's eight rows of a K step
+  uint32_t oa = (uint32_t)kw * sa + 4u * (uint32_t)lane, ob = (uint32_t)kw * sb + (uint32_t)lane;
+
+  f32x4 acc[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int jj = 0; jj < 2; ++jj) acc[i][jj] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  // One K step of operands in flight: the registers of step t + 1 are requested behind step t's first barrier, under its
+  // MFMAs.  (Two steps ahead -- 32 more registers, the loads of step t + 2 branch-free past the slice -- measured slower:
+  // 19.3 against 18.6 us for the launch at config 2.)
+  float va[8];
+  uint32_t vb[8];
+  cg_fetch(ra, rb, oa, ob, sa, sb, va, vb);
+  const int fr = lane & 15, fq = lane >> 4;
+  for (int k0 = 0; k0 < nrows; k0 += HK) {
+    bf16x8 hi, mid, lo, mk;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+      const float x = va[r];
+      const __bf16 h = (__bf16)x;
+      const float r1 = x - (float)h;
+      const __bf16 m = (__bf16)r1;
+      hi[r] = h; mid[r] = m; lo[r] = (__bf16)(r1 - (float)m);
+      mk[r] = __builtin_bit_cast(__bf16, (unsigned short)(vb[r] ? 0x3F80 : 0));
+    }
+    *reinterpret_cast<bf16x8*>(&As[0][lane][kw]) = hi;
+    *reinterpret_cast<bf16x8*>(&As[1][lane][kw]) = mid;
+    *reinterpret_cast<bf16x8*>(&As[2][lane][kw]) = lo;
+    *reinterpret_cast<bf16x8*>(&Bs[lane][kw]) = mk;
+    __syncthreads();
+    if (k0 + HK < nrows) {
+      oa += HK * sa; ob += HK * sb;
+      cg_fetch(ra, rb, oa, ob, sa, sb, va, vb);
+    }
+    bf16x8 a[3][2], b[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      b[i] = *reinterpret_cast<const bf16x8*>(&Bs[wn * 32 + i * 16 + fr][fq * 8]);
+#pragma unroll
+      for (int p = 0; p < 3; ++p) a[p][i] = *reinterpret_cast<const bf16x8*>(&As[p][wm * 32 + i * 16 + fr][fq * 8]);
+    }
+#pragma unroll
+    for (int p = 2; p >= 0; --p)                             // lo, mid, hi into the one accumulator
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int jj = 0; jj < 2; ++jj) acc[i][jj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[p][i], b[jj], acc[i][jj], 0, 0, 0);
+    __syncthreads();
+  }
+
+  // dw_tile_interior's slab store: each wave passes its 32 x 32 tile through LDS (the images are dead) and writes four store
+  // instructions of eight full 128-byte row segments.  C/D map of a 16 x 16 tile: col = lane & 15, row = 4 (lane >> 4) + reg.
+  float* cz = j.c + (int64_t)sl * j.fi * j.fo;
+  float(*st)[36] = reinterpret_cast<float(*)[36]>(smem) + wave * 32;
+  static_assert(4 * 32 * 36 * 4 <= kCgLdsBytes, "the four waves' staging must fit in the images");
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int jj = 0; jj < 2; ++jj)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) st[i * 16 + fq * 4 + r][jj * 16 + fr] = acc[i][jj][r];
+  __builtin_amdgcn_s_waitcnt(0xc07f);          // lgkmcnt(0): the wave's own LDS writes have landed
+  __builtin_amdgcn_wave_barrier();
+  const int ec = (lane & 7) * 4, er = lane >> 3;
+  const int64_t tr0 = m0 + wm * 32, tc0 = n0 + wn * 32;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int lr = q * 8 + er;
+    *reinterpret_cast<float4*>(cz + (tr0 + lr) * j.fo + tc0 + ec) = *reinterpret_cast<const float4*>(&st[lr][ec]);
+  }
+}
+
+// The dW1 + dW2 launch on the mask-product route: workgroups [0, n_head) the head leaves (HEAD, as gemm_f32_dw2_head_kernel),
+// then the n_a split-K tiles of dW1 = S1^T dZ1 (dw_tile, every bit as before), then the C tiles.
+template <bool HEAD>
+__global__ __launch_bounds__(256) void gemm_f32_dw2g_kernel(GemmJob ja, CJob jc, int n_a, HeadLeaf hl, int n_head, int feed) {
+  constexpr int kFloats = HEAD ? kDw2HeadLds : 2 * 2 * BK * LD;
+  __shared__ __attribute__((aligned(16))) float smem[kFloats];
+  static_assert(kCgLdsBytes <= 2 * 2 * BK * LD * 4, "the C tile's images fit in the fp32 tile images");
+  float (*As)[BK][LD] = reinterpret_cast<float (*)[BK][LD]>(smem);
+  float (*Bs)[BK][LD] = reinterpret_cast<float (*)[BK][LD]>(smem + 2 * BK * LD);
+  int bid = blockIdx.x;                      // uniform per workgroup
+  if (HEAD) {
+    if (bid < n_head) {
+      __builtin_amdgcn_s_setprio(3);
+      gcnx_head::head_body<true, true, 2, 1>(nullptr, hl.ldp, hl.w, hl.bias, hl.y, hl.b, hl.h, hl.c, hl.denom, hl.probs, hl.loss_acc, hl.dw,
+                                          hl.db, hl.dpooled, hl.lddp, hl.slabs, hl.ticket, hl.pp, hl.from_logits, smem, bid, n_head);
+      return;
+    }
+    bid -= n_head;
+  }
+  if (bid < n_a) dw_tile(ja, bid, feed, As, Bs);
+  else cg_tile(jc, bid - n_a, reinterpret_cast<__bf16*>(smem));
 }
 
 
@@ -1597,7 +1830,7 @@ int gcnx_gemm_dw_sgd(gcnx_ctx* ctx, const float* x, int64_t ldx, const float* dh
   const SgdPending pd = sgd_pending(pending, grads);
   const int n_s = gcnx_cdiv(total, 64), n_o = gcnx_cdiv(n_params, 256);
   hipLaunchKernelGGL(reduce_sgd_kernel, dim3(n_s + pd.n_pc + pd.n_ps + n_o), dim3(256), 0, ctx->stream, (const float*)ctx->ws,
-                     total, nsplit, total, n_s, params, grads, (int64_t)(dw - grads), n_params, lr, pd, ctx->lr_dev);
+                     total, nsplit, total, n_s, params, grads, (int64_t)(dw - grads), n_params, lr, pd, ctx->lr_dev, SgdScaled{});
   GCNX_LAUNCH_OK(ctx);
   return GCNX_OK;
 }
@@ -1721,7 +1954,127 @@ int gcnx_gemm_dw2(gcnx_ctx* ctx, const float* xa, int64_t ldxa, const float* dha
   pd.slabs = sb; pd.total = tb; pd.nsplit = nsplit; pd.soff = dwb - base; pd.n_ps = gcnx_cdiv(tb, 64);
   const int n_s = gcnx_cdiv(ta, 64), n_o = params ? gcnx_cdiv(n_params, 256) : 0;
   hipLaunchKernelGGL(reduce_sgd_kernel, dim3(n_s + pd.n_pc + pd.n_ps + n_o), dim3(256), 0, ctx->stream, (const float*)sa,
-                     ta, nsplit, ta, n_s, params, base, (int64_t)(dwa - base), n_params, lr, pd, ctx->lr_dev);
+                     ta, nsplit, ta, n_s, params, base, (int64_t)(dwa - base), n_params, lr, pd, ctx->lr_dev, SgdScaled{});
+  GCNX_LAUNCH_OK(ctx);
+  return GCNX_OK;
+}
+
+// ---- dW2 from per-graph mask products: slice plan, query, entry point ----
+
+// The slices of one batch: every graph of n_g > 0 rows is cut into ceil(n_g / kchunk) parts at multiples of kchunk (a
+// multiple of the K step, 32 rows) counted from the graph's first row, so only a graph's last slice is ragged and no slice
+// spans two graphs.  plan (may be NULL: count only) receives {row_begin, row_end, graph, the bits of 1.0f / (float)rows of the
+// graph -- AVG's factor, the expression the backward launch evaluates} per slice, at most cap of them.  Host code: graph_ptr is the host copy every batch keeps.  Returns the slice count, -1 on bad
+// arguments.
+int gcnx_dw2_slice_plan(const int32_t* graph_ptr, int32_t b, int64_t kchunk, int32_t* plan, int32_t cap) {
+  if (!graph_ptr || b < 0 || kchunk <= 0 || kchunk % BK != 0 || cap < 0) return -1;
+  int64_t cnt = 0;
+  for (int32_t g = 0; g < b; ++g) {
+    const int64_t r0 = graph_ptr[g], r1 = graph_ptr[g + 1];
+    if (r1 < r0) return -1;
+    for (int64_t r = r0; r < r1; r += kchunk, ++cnt)
+      if (plan && cnt < cap) {
+        int32_t* e = plan + 4 * cnt;
+        const float inv = 1.0f / (float)(r1 - r0);
+        e[0] = (int32_t)r; e[1] = (int32_t)std::min(r1, r + kchunk); e[2] = g; e[3] = __builtin_bit_cast(int32_t, inv);
+      }
+    if (cnt > INT32_MAX) return -1;
+  }
+  return (int32_t)cnt;
+}
+
+// The route refuses a plan of more slices than twice the uniform cut's ceil(n / kchunk) -- many tiny graphs: the slabs
+// would outgrow today's -- unless it has at most 64: up to there each of the reduction's four groups still folds its
+// slices in one chunk of loads (splitk_chunk_scaled<16>), which is what a batch of a few small graphs needs.
+int gcnx_dw2_slices_ok(int64_t n, int64_t kchunk, int32_t nslices) {
+  if (n <= 0 || kchunk <= 0 || nslices <= 0) return 0;
+  const int64_t uniform = (n + kchunk - 1) / kchunk;
+  return nslices <= std::max<int64_t>(2 * uniform, 64) ? 1 : 0;
+}
+
+// The rows per slice gcnx_gemm_dw2_graph cuts both products by: gcnx_gemm_dw2's plan for the same shapes.
+int64_t gcnx_gemm_dw2_graph_kchunk(gcnx_ctx* ctx, int64_t n, int32_t fia, int32_t foa, int32_t fib, int32_t fob) {
+  if (!ctx || n <= 0 || fia <= 0 || foa <= 0 || fib <= 0 || fob <= 0) return 0;
+  return splitk_plan_f32(splitk_fill(ctx, dw_tiles(fia, foa) + dw_tiles(fib, fob)), n).kchunk;
+}
+
+int gcnx_gemm_dw2_graph_ok(gcnx_ctx* ctx, int64_t n, int32_t fia, int32_t foa, int32_t fib, int32_t fob, int64_t kchunk,
+                           int32_t nslices, int pool_mode, int prec) {
+  if (!ctx || !ctx->knob_dw2_graph) return 0;
+  if (prec != GCNX_PREC_F32 || (pool_mode != GCNX_POOL_SUM && pool_mode != GCNX_POOL_AVG)) return 0;
+  if (n <= 0 || n > INT32_MAX || fia <= 0 || foa <= 0 || foa % 4 != 0) return 0;
+  if ((fib != 64 && fib != 128) || fob <= 0 || fob % 64 != 0 || (int64_t)fib * fob > kSplitkSlabMax) return 0;
+  if (kchunk <= 0 || kchunk % BK != 0 || kchunk > (1 << 20)) return 0;
+  return gcnx_dw2_slices_ok(n, kchunk, nslices);
+}
+
+int gcnx_gemm_dw2_graph(gcnx_ctx* ctx, const float* xa, int64_t ldxa, const float* dha, int64_t lddha, float* dwa, int32_t fia,
+                        int32_t foa, const float* xb, int64_t ldxb, const uint8_t* mask8, int64_t ldmask8, float* dwb,
+                        int32_t fib, int32_t fob, int64_t n, const int32_t* plan, int32_t nslices, int64_t kchunk,
+                        const float* dpooled, int64_t lddp, int pool_mode, float* params, float* grads, int64_t n_params,
+                        float lr, const gcnx_pending_reduce* pending, const gcnx_head_args* leaf) {
+  GCNX_CHECK_CTX(ctx);
+  // what the route does not serve launches nothing and sets no error: the caller runs gcnx_gemm_dw2
+  if (!gcnx_gemm_dw2_graph_ok(ctx, n, fia, foa, fib, fob, kchunk, nslices, pool_mode, GCNX_PREC_F32)) return GCNX_ERR_UNSUPPORTED;
+  if (pending && !pending->colpart && !pending->slabs) pending = nullptr;
+  if (pending && pending->slabs) return GCNX_ERR_UNSUPPORTED;
+  if (!xa || !dha || !dwa || !xb || !mask8 || !dwb || !plan || !dpooled) return GCNX_ERR_UNSUPPORTED;
+  if (ldxa < fia || lddha < foa || ldxb < fib || ldmask8 < fob || lddp < fob || ldxb >= (1 << 20) || ldmask8 >= (1 << 22)) return GCNX_ERR_UNSUPPORTED;
+  if (!gcnx_aligned16(xb) || ldxb % 4 != 0) return GCNX_ERR_UNSUPPORTED;
+  GCNX_RANGE(ctx, "weight GEMMs (dW1 + mask products of dW2) + head leaves + update");
+  if (leaf) {
+    GCNX_REQUIRE(ctx, leaf->pool_sum && leaf->graph_ptr && leaf->w && leaf->y && leaf->probs && leaf->loss_acc && leaf->dw && leaf->dpooled &&
+                          leaf->pooled && leaf->b > 0 && leaf->h > 0 && leaf->h % 4 == 0 && leaf->c >= 1 && leaf->c <= gcnx_head::kHeadMaxC &&
+                          leaf->denom > 0.f && (leaf->pool_mode == GCNX_POOL_SUM || leaf->pool_mode == GCNX_POOL_AVG) &&
+                          (leaf->cce_mode == GCNX_CCE_PROBS || leaf->cce_mode == GCNX_CCE_LOGITS) && (!leaf->db_relu || leaf->pool_cnt),
+                 "gcnx_gemm_dw2_graph: inconsistent head arguments");
+    GCNX_REQUIRE(ctx, !params || (leaf->dw >= grads && leaf->dw + (int64_t)leaf->h * leaf->c <= grads + n_params),
+                 "gcnx_gemm_dw2_graph: the head's gradients must lie inside the flat gradient buffer");
+  }
+  const int64_t ta = (int64_t)fia * foa, tb = (int64_t)fib * fob;
+  if (params) {
+    GCNX_REQUIRE(ctx, grads != nullptr && n_params >= 0, "gcnx_gemm_dw2_graph: params without grads");
+    GCNX_REQUIRE(ctx, dwa >= grads && dwa + ta <= grads + n_params && dwb >= grads && dwb + tb <= grads + n_params,
+                 "gcnx_gemm_dw2_graph: both gradients must lie inside the flat gradient buffer");
+    if (int rc = pending_colsums_land(ctx, "gcnx_gemm_dw2_graph", pending, grads, n_params)) return rc;
+  }
+  // dW1: gcnx_gemm_dw2's own plan -- the same slices, so the same bits -- but always through slabs: one slab is folded like
+  // many.  (The launch was also measured with dW1 in slices of half the depth, with the C tiles in slices of twice the depth,
+  // and with both: 20.1, 24.4 and 26.4 us against 18.6 for one cut for both products -- LOG.md Round 17.)
+  const GcnxSplit pa = splitk_plan_f32(splitk_fill(ctx, dw_tiles(fia, foa) + dw_tiles(fib, fob)), n);
+  const size_t slab_a = ((size_t)pa.nsplit * ta + 63) & ~(size_t)63;
+  int rc = gcnx_ws_reserve(ctx, (slab_a + (size_t)nslices * tb) * sizeof(float));
+  if (rc) return rc;
+  float* sa = (float*)ctx->ws;
+  float* sb = sa + slab_a;
+  const GemmJob ja = dw_job(xa, ldxa, dha, lddha, sa, fia, foa, n, pa, 1);
+  const CJob jc{xb, ldxb, mask8, ldmask8, sb, reinterpret_cast<const int4*>(plan), fib, fob, fob / 64, fib / 64};
+  const int n_a = ja.gx * ja.gy * ja.gz, n_c = jc.gx * jc.gy * nslices;
+  const bool want_db = leaf && leaf->db_relu;
+  const bool merged = leaf && leaf->c == 2 && gcnx_head::head_lds_floats(leaf->h, leaf->c, want_db) <= (size_t)kDw2HeadLds &&
+                      leaf->b <= gcnx_head::kHeadRows;
+  if (leaf && !merged) { rc = gcnx_head_from_parts(ctx, leaf); if (rc) return rc; }
+  const int feed = ctx->knob_dw2_feed != 0;
+  if (merged) {
+    HeadLeaf hl{leaf->w, leaf->bias, leaf->y, leaf->b, leaf->h, leaf->c, leaf->denom, leaf->probs, leaf->loss_acc, leaf->dw, leaf->db,
+                leaf->dpooled, (int64_t)leaf->h, (int64_t)leaf->h, nullptr, ctx->flag + 3,
+                gcnx_head::PoolParts{leaf->pool_sum, leaf->graph_ptr, leaf->pooled, 1, leaf->pool_mode == GCNX_POOL_AVG ? 1 : 0,
+                                     want_db ? leaf->pool_cnt : nullptr, want_db ? leaf->db_relu : nullptr},
+                leaf->cce_mode == GCNX_CCE_LOGITS ? 1 : 0};
+    hipLaunchKernelGGL(gemm_f32_dw2g_kernel<true>, dim3(1 + n_a + n_c), dim3(256), 0, ctx->stream, ja, jc, n_a, hl, 1, feed);
+  } else {
+    hipLaunchKernelGGL(gemm_f32_dw2g_kernel<false>, dim3(n_a + n_c), dim3(256), 0, ctx->stream, ja, jc, n_a, HeadLeaf{}, 0, feed);
+  }
+  GCNX_LAUNCH_OK(ctx);
+  // the reduction: dW1 is the launch's own set, dW2 the scaled one
+  float* base = params ? grads : std::min(dwa, dwb);
+  if (!params && pending && pending->colpart) base = std::min(base, pending->cout);
+  const SgdPending pd = sgd_pending(pending, base);
+  const SgdScaled sd{sb, tb, nslices, (int64_t)(dwb - base), reinterpret_cast<const int4*>(plan), dpooled, lddp, fob,
+                     pool_mode == GCNX_POOL_AVG ? 1 : 0, gcnx_cdiv(tb, 64)};
+  const int n_s = gcnx_cdiv(ta, 64), n_o = params ? gcnx_cdiv(n_params, 256) : 0;
+  hipLaunchKernelGGL(reduce_sgd_kernel, dim3(n_s + pd.n_pc + pd.n_ps + sd.n + n_o), dim3(256), 0, ctx->stream, (const float*)sa,
+                     ta, pa.nsplit, ta, n_s, params, base, (int64_t)(dwa - base), n_params, lr, pd, ctx->lr_dev, sd);
   GCNX_LAUNCH_OK(ctx);
   return GCNX_OK;
 }

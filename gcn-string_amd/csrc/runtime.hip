@@ -46,7 +46,7 @@ int gcnx_ws_reserve(gcnx_ctx* ctx, size_t bytes) {
 
 extern "C" {
 
-int gcnx_version(void) { return 428; }   // 428: rgcn_operator, rgcn_conv(_ok), rgcn_aggregate; 427: cheb_norm, cheb_resident_ok, cheb_scratch_floats, cheb_basis, cheb_sum; 426: appnp_resident_ok, appnp_scratch_floats, appnp_propagate; 425: pdn_ok, pdn_operator, pdn_bwd_scratch_floats, pdn_operator_bwd; 424: sddmm_csr, edge_mask_fwd, edge_mask_bwd, feat_mask_fwd, feat_mask_bwd, mask_scratch_floats; 423: gine_conv(_ok), gine_aggregate, gine_bwd_scratch_floats, gine_bwd_edges, gine_bwd_nodes; 422: graph_norm_scratch_floats, graph_norm_act, graph_norm_act_bwd; 421: attn_pool_scratch_floats, attn_pool, attn_pool_bwd; 420: transformer_conv_ok, transformer_aggregate, transformer_beta_bwd, transformer_bwd_targets, transformer_bwd_sources, transformer_bwd_scratch_floats; 410: resgated_conv_ok, resgated_aggregate, resgated_bwd_targets, resgated_bwd_sources, resgated_bwd_scratch_floats; 409: pna_aggregate, pna_bwd, pna_bwd_scratch_floats; 408: gin_conv(_ok), gin_aggregate, gin_eps_grad; 407: gatv2_conv_ok, gatv2_aggregate, gatv2_bwd_edges, gatv2_bwd_nodes, gatv2_bwd_scratch_floats; 406: gat_conv_ok, gat_scores, gat_aggregate, gat_bwd_edges, gat_bwd_nodes, gat_bwd_scratch_floats; 405: topk_select(_ok), topk_gather, topk_bwd, csr_induce; 404: sage_conv(_ok); 403: ecc_expand, ecc_bwd, csr_transpose_perm; 402: bn_act_pool_bwd_stats / _apply, bce_head_phase; 401: bn_act_pool(_bwd), bn_prelu_bce_head, GCNX_ACT_PRELU_SHARED; round 3: + plan_bind, wimage *, bf16 storage, stream images, relu_bits_pool, pooled head; 310: dropout, counter_add, add; 311: spmm_csr_minmax(_bwd); 400 (r4): spmm_csr_prod(_bwd)
+int gcnx_version(void) { return 429; }   // 429: dw2_slice_plan, dw2_slices_ok, gemm_dw2_graph_kchunk, gemm_dw2_graph_ok, gemm_dw2_graph; 428: rgcn_operator, rgcn_conv(_ok), rgcn_aggregate; 427: cheb_norm, cheb_resident_ok, cheb_scratch_floats, cheb_basis, cheb_sum; 426: appnp_resident_ok, appnp_scratch_floats, appnp_propagate; 425: pdn_ok, pdn_operator, pdn_bwd_scratch_floats, pdn_operator_bwd; 424: sddmm_csr, edge_mask_fwd, edge_mask_bwd, feat_mask_fwd, feat_mask_bwd, mask_scratch_floats; 423: gine_conv(_ok), gine_aggregate, gine_bwd_scratch_floats, gine_bwd_edges, gine_bwd_nodes; 422: graph_norm_scratch_floats, graph_norm_act, graph_norm_act_bwd; 421: attn_pool_scratch_floats, attn_pool, attn_pool_bwd; 420: transformer_conv_ok, transformer_aggregate, transformer_beta_bwd, transformer_bwd_targets, transformer_bwd_sources, transformer_bwd_scratch_floats; 410: resgated_conv_ok, resgated_aggregate, resgated_bwd_targets, resgated_bwd_sources, resgated_bwd_scratch_floats; 409: pna_aggregate, pna_bwd, pna_bwd_scratch_floats; 408: gin_conv(_ok), gin_aggregate, gin_eps_grad; 407: gatv2_conv_ok, gatv2_aggregate, gatv2_bwd_edges, gatv2_bwd_nodes, gatv2_bwd_scratch_floats; 406: gat_conv_ok, gat_scores, gat_aggregate, gat_bwd_edges, gat_bwd_nodes, gat_bwd_scratch_floats; 405: topk_select(_ok), topk_gather, topk_bwd, csr_induce; 404: sage_conv(_ok); 403: ecc_expand, ecc_bwd, csr_transpose_perm; 402: bn_act_pool_bwd_stats / _apply, bce_head_phase; 401: bn_act_pool(_bwd), bn_prelu_bce_head, GCNX_ACT_PRELU_SHARED; round 3: + plan_bind, wimage *, bf16 storage, stream images, relu_bits_pool, pooled head; 310: dropout, counter_add, add; 311: spmm_csr_minmax(_bwd); 400 (r4): spmm_csr_prod(_bwd)
 
 int gcnx_device_count(int* n) {
   if (!n) return gcnx_fail(nullptr, GCNX_ERR_INVALID, "gcnx_device_count: n is NULL");
@@ -102,6 +102,7 @@ int gcnx_ctx_create(int device, gcnx_ctx** out) {
   if (const char* k = getenv("GCNX_SPMM_BAL")) ctx->knob_spmm_bal = atoi(k);
   if (const char* k = getenv("GCNX_SPMM_CB")) ctx->knob_spmm_cb = atoi(k);
   if (const char* k = getenv("GCNX_DW2_FEED")) ctx->knob_dw2_feed = atoi(k);
+  if (const char* k = getenv("GCNX_DW2_GRAPH")) ctx->knob_dw2_graph = atoi(k);
   if (const char* k = getenv("GCNX_ROCTX")) {
     if (atoi(k)) {                        // tracing aid: named ranges around the kernel classes (rocprofv3 --marker-trace)
       void* lib = dlopen("librocprofiler-sdk-roctx.so", RTLD_NOW | RTLD_GLOBAL);
@@ -173,6 +174,7 @@ int gcnx_set_tuning(gcnx_ctx* ctx, const char* key, int value) {
   else if (k == "spmm_bal") ctx->knob_spmm_bal = value;
   else if (k == "spmm_cb") ctx->knob_spmm_cb = value;
   else if (k == "dw2_feed") ctx->knob_dw2_feed = value;
+  else if (k == "dw2_graph") ctx->knob_dw2_graph = value;
   else return gcnx_fail(ctx, GCNX_ERR_INVALID, "gcnx_set_tuning: unknown key '%s'", key);
   return GCNX_OK;
 }

@@ -1486,6 +1486,56 @@ def gemm_dw2(ctx, xa, dha, dwa, xb, dhb, dwb, prec="f32", params=None, grads=Non
                                   C.byref(pending) if pending is not None else None, C.byref(leaf) if leaf is not None else None))
 
 
+def dw2_slice_plan(graph_ptr_host, kchunk):
+    """The row slices of gemm_dw2_graph for one batch, on the host (gcnx_dw2_slice_plan): int32 [nslices, 4] rows of
+    {row_begin, row_end, graph, float32 bits of 1 / rows of the graph}; no slice spans two graphs, cuts at multiples of kchunk from a graph's start."""
+    gp = np.ascontiguousarray(graph_ptr_host, dtype=np.int32)
+    lib = L.load()
+    cnt = int(lib.gcnx_dw2_slice_plan(gp.ctypes.data, len(gp) - 1, int(kchunk), None, 0))
+    if cnt < 0:
+        raise ValueError("dw2_slice_plan: graph_ptr must be non-decreasing and kchunk a positive multiple of 32")
+    plan = np.zeros((cnt, 4), np.int32)
+    if cnt:
+        assert int(lib.gcnx_dw2_slice_plan(gp.ctypes.data, len(gp) - 1, int(kchunk), plan.ctypes.data, cnt)) == cnt
+    return plan
+
+
+def gemm_dw2_graph_plan(ctx, seg, n, fia, foa, fib, fob, mode="sum", prec="f32"):
+    """(plan on the device, slice count, kchunk) when gemm_dw2_graph serves these shapes for the graphs of ``seg``, else None
+    (gcnx_gemm_dw2_graph_kchunk, gcnx_dw2_slice_plan, gcnx_gemm_dw2_graph_ok).  A constant of the batch: one small upload."""
+    if mode not in ("sum", "avg", "mean") or prec not in L.PRECS:
+        return None
+    kchunk = int(ctx.lib.gcnx_gemm_dw2_graph_kchunk(ctx.h, int(n), fia, foa, fib, fob))
+    if kchunk <= 0:
+        return None
+    plan = dw2_slice_plan(seg.host, kchunk)
+    if not ctx.lib.gcnx_gemm_dw2_graph_ok(ctx.h, int(n), fia, foa, fib, fob, kchunk, len(plan), L.POOLS[mode], L.PRECS[prec]):
+        return None
+    return ctx.to_device(plan, np.int32), len(plan), kchunk
+
+
+def gemm_dw2_graph(ctx, xa, dha, dwa, xb, mask8, dwb, plan, dpooled, mode="sum", params=None, grads=None, lr=0.0, pending=None,
+                   leaf=None):
+    """dwa = xa^T dha as gemm_dw2 computes it, and dwb = xb^T (mask8 * pool'(dpooled)[graph]) from per-graph mask products on
+    the bf16 MFMA (gcnx_gemm_dw2_graph); ``plan`` is gemm_dw2_graph_plan's triple.  False -- nothing launched -- when the
+    library answers GCNX_ERR_UNSUPPORTED."""
+    n, fia = xa.shape
+    foa = dha.shape[1]
+    fib, fob = xb.shape[1], mask8.shape[1]
+    table, nslices, kchunk = plan
+    assert xb.shape[0] == n and dha.shape[0] == n and mask8.shape[0] == n and mask8.dtype == np.uint8
+    assert dwa.shape == (fia, foa) and dwb.shape == (fib, fob) and dpooled.shape[1] == fob
+    rc = ctx.lib.gcnx_gemm_dw2_graph(ctx.h, _p(xa), xa.ld, _p(dha), dha.ld, _p(dwa), fia, foa, _p(xb), xb.ld, mask8.ptr, mask8.ld,
+                                     _p(dwb), fib, fob, n, table.ptr, nslices, kchunk, _p(dpooled), dpooled.ld, L.POOLS[mode],
+                                     _p(params), _p(grads),
+                                     params.size if params is not None else (grads.size if grads is not None else 0), float(lr),
+                                     C.byref(pending) if pending is not None else None, C.byref(leaf) if leaf is not None else None)
+    if rc == L.ERR_UNSUPPORTED:
+        return False
+    ctx._ck(rc)
+    return True
+
+
 def pool_bwd_colsum(ctx, seg, dpooled, y, db, mode="sum"):
     """db = column sums of pool'(dpooled) * [y > 0] without materialising it (gcnx_pool_bwd_colsum)."""
     ctx._ck(ctx.lib.gcnx_pool_bwd_colsum(ctx.h, seg.dev.ptr, seg.n_graphs, _p(dpooled), dpooled.ld, _p(y), y.ld,

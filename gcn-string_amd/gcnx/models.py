@@ -414,6 +414,7 @@ class GCN2(_GraphRunner):
                       "mask8": os.environ.get("GCNX_MASK8", "1") != "0",
                       "ax_reuse": os.environ.get("GCNX_AX_REUSE", "1") != "0"}
         self._s1_uid = None                  # uid of the batch whose S1 = A X bufs["s1"] holds (one-launch route), or None
+        self.dw2_plans_built = 0             # slice plans of gemm_dw2_graph built so far (_dw2_graph_plan): tests read it
         self._rng = np.random.default_rng(seed)
         self.built = False
         self._bufs = None
@@ -465,8 +466,8 @@ class GCN2(_GraphRunner):
             self._bufs["w2t"] = v("w2t", h, h)                  # W2^T, a by-product of layer 2's forward launch
             # [Y2 > 0] as bytes: what the backward launch gathers.  NOTE: a train_step on the head-late route then does not
             # store the fp32 "y2" at all -- the buffer keeps whatever an earlier loss_and_grads / forward call left in it
-            if self._knob["mask8"]:
-                self._bufs["y2m8"] = v("y2m8", n, h, np.uint8)
+            # (GCNX_MASK8=0 only turns that gather back to fp32 rows: the image is still what dW2's mask products read)
+            self._bufs["y2m8"] = v("y2m8", n, h, np.uint8)
             # head inside the backward: the pool's per-tile partial sums / positive counts (layer 2's launch writes them)
             # and the per-graph totals (the backward launch does)
             tr = D.pool_tile_rows(n, b)
@@ -482,7 +483,7 @@ class GCN2(_GraphRunner):
     # ---- the call sequences --------------------------------------------------------------------
     def _forward(self, batch, bufs, with_loss, denom, train=False):
         ctx, p, prec = self.ctx, self.p, self.prec
-        bufs["_mask8"] = None
+        bufs["_mask8"] = bufs["_dw2_mask8"] = None
         if self._fused(batch):
             # small-feature regime: each GCNConv is one launch, evaluated as (A X) W (gcnx_gcn_conv_fwd); A X is kept
             # for the weight gradient when a backward pass follows
@@ -511,9 +512,15 @@ class GCN2(_GraphRunner):
             # keeps it, and so does every route whose pool or head is a launch of its own).
             m8 = bufs["y2m8"] if keep and self._knob["mask8"] else None
             bufs["_mask8"] = m8
+            # The same image is the 0/1 operand of dW2's mask products (gcnx_gemm_dw2_graph), whatever the backward launch
+            # gathers: where that route serves the batch the launch writes it with GCNX_MASK8=0 too (beside the fp32 Y2), so
+            # the knob changes the gather and not one bit of the step.
+            img = m8
+            if keep and self._dw2_graph_plan(batch) is not None:
+                img = bufs["_dw2_mask8"] = bufs["y2m8"]
             D.gcn_conv_fwd(ctx, batch.a, bufs["y1"], p["w2"], p["b2"], None if (m8 is not None and train and late) else bufs["y2"],
                            act="relu", s=bufs["s2"] if keep else None, wt=bufs["w2t"] if keep else None, prec=prec,
-                           pool=(batch.seg, bufs["tp_part"], bufs["tp_cnt"]) if late else None, mask8=m8)
+                           pool=(batch.seg, bufs["tp_part"], bufs["tp_cnt"]) if late else None, mask8=img)
         else:
             bufs["act16"] = False
             if self._s_order() and self._act16_try(batch, with_loss):
@@ -621,9 +628,20 @@ class GCN2(_GraphRunner):
             # pool' + ReLU' + A^T + W2^T + ReLU' in one launch (dZ2 and dZ1 out, db1 partials pending; db2 came out of
             # the head), then both weight gradients -- dW1 = S1^T dZ1, dW2 = S2^T dZ2 -- and the update in the last two
             ha = bufs.get("_head_late")
+            # dZ2 = [Y2 > 0] * pool'(dPooled)[graph] is a 0/1 image scaled per graph and column: dW2 = sum_g dP_g * (S2_g^T mask_g) comes
+            # from the byte image on the bf16 MFMA with exact products (gcnx_gemm_dw2_graph), the backward launch then does not
+            # store dZ2 at all.  Decided BEFORE that launch; what the route does not serve runs the sequence below it.
+            plan = self._dw2_graph_plan(batch) if bufs.get("_dw2_mask8") is not None else None
             pend = D.gcn_conv_bwd_pool(ctx, at, bufs["y2"], batch.seg, None if ha is not None else bufs["dpooled"], p["w2"], bufs["y1"],
-                                       bufs["dz"], bufs["dz2"], db1=g["b1"], mode=self.pool, scratch=self._defer_scratch(batch),
-                                       w2t=bufs["w2t"], prec=prec, head=ha, mask8=bufs.get("_mask8"))
+                                       None if plan is not None else bufs["dz"], bufs["dz2"], db1=g["b1"], mode=self.pool,
+                                       scratch=self._defer_scratch(batch), w2t=bufs["w2t"], prec=prec, head=ha, mask8=bufs.get("_mask8"))
+            if plan is not None:
+                upd = lr is not None
+                if not D.gemm_dw2_graph(ctx, bufs["_s1"], bufs["dz2"], g["w1"], bufs["s2"], bufs["_dw2_mask8"], g["w2"], plan, bufs["dpooled"],
+                                        mode=self.pool, params=self.flat_p if upd else None, grads=self.flat_g.flat(0, self.n_params),
+                                        lr=lr if upd else 0.0, pending=pend, leaf=ha):
+                    raise RuntimeError("gcnx: gcnx_gemm_dw2_graph refused a call gcnx_gemm_dw2_graph_ok had accepted")
+                return upd
             if lr is None:
                 D.gemm_dw2(ctx, bufs["_s1"], bufs["dz2"], g["w1"], bufs["s2"], bufs["dz"], g["w2"], prec="f32",
                            grads=self.flat_g.flat(0, self.n_params), pending=pend, leaf=ha)
@@ -772,6 +790,21 @@ class GCN2(_GraphRunner):
                               and D.gcn_conv_fused_ok(self.ctx, batch.n, self.hidden, self.hidden))
         return route[key]
 
+    def _dw2_graph_plan(self, batch):
+        """The slice plan of gcnx_gemm_dw2_graph for this batch, or None where the route does not serve the step (shapes, too
+        many tiny graphs, the knob dw2_graph).  A constant of the batch, built on the host and uploaded once per
+        batch uid -- before the step's launches, never inside a capture -- and kept WITH the batch (a captured step holds the
+        table's address for as long as the batch lives); DeviceBatch.invalidate() gives the batch a new uid and so a new plan."""
+        if not self._fused(batch):
+            return None
+        route = batch.__dict__.setdefault("_route", {})
+        key = ("dw2_graph", id(self), batch.uid)
+        if key not in route:
+            route[key] = D.gemm_dw2_graph_plan(self.ctx, batch.seg, batch.n, self.f_in, self.hidden, self.hidden, self.hidden,
+                                               mode=self.pool)
+            self.dw2_plans_built += 1
+        return route[key]
+
     def _head_late(self, batch):
         """One-launch layers (see _fused; SUM / AVG pooling), at most 2 classes (the reference's binary labels) and no graph
         without nodes: pool and classifier head are evaluated inside the forward / backward launches (gcnx_gcn_conv_fwd_pool,
@@ -824,6 +857,7 @@ class GCN2(_GraphRunner):
         # (the bucketed form needs the side stream inside the step: with a capturable communicator only when the collective
         # is recorded into the step graph anyway, or the step runs eagerly)
         buckets = multi and self._knob["buckets"] and (fused_comm or not self.use_graph)
+        self._dw2_graph_plan(batch)                             # (an upload the first time a batch is seen: not inside a capture)
 
         def seq():
             self._forward(batch, bufs, "grads", denom, train=_lr is not None)

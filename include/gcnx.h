@@ -795,6 +795,37 @@ GCNX_API int gcnx_gemm_dw2(gcnx_ctx* ctx, const float* xa, int64_t ldxa, const f
                       float* dwb, int32_t fib, int32_t fob, int64_t n, int prec, float* params, float* grads,
                       int64_t n_params, float lr, const gcnx_pending_reduce* pending, const gcnx_head_args* leaf);
 
+/* gcnx_gemm_dw2 for a layer under a SUM / AVG global pool, without dZ2.  There dZ2[r, j] = mask8[r, j] * dP[g(r), j]
+ * (mask8 = [Y2 > 0] as bytes, gcnx_gcn_conv_fwd_mask8; dP[g] = dpooled[g], times 1 / rows of g for AVG), so
+ *   dwb[k, j] = sum_g dP[g, j] * C_g[k, j],   C_g = xb[rows of g, :]^T mask8[rows of g, :].
+ * C_g is formed on the bf16 MFMA from the exact split xb = hi + mid + lo (three bf16 numbers; every product with a 0 / 1
+ * mask entry is exact, fp32 accumulation; entries of xb below 2^-110 in magnitude may lose their lo piece), per row slice
+ * of a plan that never crosses a graph, and the reduction launch folds the slices' slabs with dP as a per-column scale
+ * (one fmaf per slab).  dwa = xa^T dha exactly as gcnx_gemm_dw2 computes it; params / grads / lr / pending / leaf as
+ * there (dpooled may be the array `leaf` writes: it is read by the reduction launch only).
+ *   gcnx_dw2_slice_plan   host code, no device: cuts graph_ptr [b + 1] (host memory) into slices of at most kchunk rows
+ *                         (kchunk a multiple of 32), cuts at multiples of kchunk from each graph's first row; writes
+ *                         {row_begin, row_end, graph, bits of the float 1.0f / rows of the graph} (4 x int32) per slice into plan (cap slices; NULL:
+ *                         count only) and returns the slice count, -1 on bad arguments.  The caller copies the table to
+ *                         the device once per batch.
+ *   gcnx_dw2_slices_ok    1 when nslices <= max(2 * ceil(n / kchunk), 64): many tiny graphs are refused
+ *   gcnx_gemm_dw2_graph_kchunk   the rows per slice gcnx_gemm_dw2 would cut these shapes by
+ *   gcnx_gemm_dw2_graph_ok       1 when gcnx_gemm_dw2_graph serves the call: fp32, SUM / AVG, foa % 4 == 0, fib in {64, 128},
+ *                         fob % 64 == 0, the slice bound, and the tuning knob dw2_graph (GCNX_DW2_GRAPH=0: never)
+ *   gcnx_gemm_dw2_graph   plan: the table on the device (16-byte aligned); mask8 rows ldmask8 bytes apart.  Returns
+ *                         GCNX_ERR_UNSUPPORTED -- nothing launched, gcnx_last_error untouched -- for what _ok refuses,
+ *                         unaligned xb, or a pending split-K record. */
+GCNX_API int gcnx_dw2_slice_plan(const int32_t* graph_ptr, int32_t b, int64_t kchunk, int32_t* plan, int32_t cap);
+GCNX_API int gcnx_dw2_slices_ok(int64_t n, int64_t kchunk, int32_t nslices);
+GCNX_API int64_t gcnx_gemm_dw2_graph_kchunk(gcnx_ctx* ctx, int64_t n, int32_t fia, int32_t foa, int32_t fib, int32_t fob);
+GCNX_API int gcnx_gemm_dw2_graph_ok(gcnx_ctx* ctx, int64_t n, int32_t fia, int32_t foa, int32_t fib, int32_t fob, int64_t kchunk,
+                      int32_t nslices, int pool_mode, int prec);
+GCNX_API int gcnx_gemm_dw2_graph(gcnx_ctx* ctx, const float* xa, int64_t ldxa, const float* dha, int64_t lddha, float* dwa,
+                      int32_t fia, int32_t foa, const float* xb, int64_t ldxb, const uint8_t* mask8, int64_t ldmask8,
+                      float* dwb, int32_t fib, int32_t fob, int64_t n, const int32_t* plan, int32_t nslices, int64_t kchunk,
+                      const float* dpooled, int64_t lddp, int pool_mode, float* params, float* grads, int64_t n_params,
+                      float lr, const gcnx_pending_reduce* pending, const gcnx_head_args* leaf);
+
 /* ---- SAGEConv as one launch, small-feature regime (F <= 128) ---------------------------------------------------
  * The GraphSAGE layer the reference's torch model names as its next step ("consider using class SAGEConv instead",
  * gcn_utills.py:804-806): out = mean_{j in N(i)} x_j W_nb + x_i W_root + b, evaluated as [A x | x] [W_nb ; W_root] so that one
