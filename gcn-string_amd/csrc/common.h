@@ -206,6 +206,9 @@ size_t gcnx_colsum_partials_ws(int64_t rows, int32_t f);
 int gcnx_colsum_partials(gcnx_ctx* ctx, int64_t rows, int32_t f, float* out);
 int gcnx_pool_graph_list(gcnx_ctx* ctx, const int32_t* graph_ptr, const int32_t* glist, int32_t nlist, const float* x, int64_t ldx,
                          int32_t f, int mode, float* pooled, int64_t ldp, float* cnt);
+// reduce.hip: gcnx_segment_pool writing pooled at row stride ldp >= f (gcnx_pool_dense_softmax_cce's separate calls)
+int gcnx_segment_pool_ld(gcnx_ctx* ctx, const int32_t* graph_ptr, const float* x, int64_t ldx, float* pooled, int64_t ldp,
+                         int32_t b, int32_t f, int mode, int32_t* argmax);
 // head.hip: the classifier head from the pool's partial sums as a launch of its own (what gcnx_gemm_dw2 falls back to when
 // the head does not fit inside its launch)
 int gcnx_head_from_parts(gcnx_ctx* ctx, const gcnx_head_args* leaf);

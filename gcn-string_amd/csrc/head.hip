@@ -7,7 +7,7 @@
 // matrices of a few kilobytes ([B,H] x [H,C], B = graphs per batch, C = classes): at BASELINE config 2 each of
 // those launches is pure latency (4-15 us), together a fifth of the training step.
 //
-// One workgroup owns 64 graphs: logits, softmax, loss / accuracy terms, dlogits (gradient of the clipped
+// One workgroup owns 32 graphs (kHeadRows): logits, softmax, loss / accuracy terms, dlogits (gradient of the clipped
 // loss, as gcnx_softmax_cce) and the dPooled rows are row-local.  dW, db and the two loss_acc sums are
 // reductions over graphs: every workgroup writes its partial to a slab of the ctx workspace and the last one
 // to arrive (agent-scope ticket) adds the slabs in workgroup order -- a fixed summation order, so the result
@@ -61,7 +61,11 @@ int gcnx_pooled_dense_softmax_cce(gcnx_ctx* ctx, const int32_t* graph_ptr, int p
     if (rc) return rc;
   }
   int rc = gcnx_dense_softmax_cce(ctx, pooled, ldp, w, bias, y, b, h, c, denom, probs, loss_acc, dw, db, dpooled, lddp, cce_mode);
-  if (rc || !db_relu || b == 0 || h == 0) return rc;
+  if (rc || !db_relu || h == 0) return rc;
+  if (b == 0) {       // an empty shard: zeros, as dw and db above and as gcnx_pool_bwd_colsum
+    GCNX_HIP(ctx, hipMemsetAsync(db_relu, 0, (size_t)h * sizeof(float), ctx->stream));
+    return GCNX_OK;
+  }
   GCNX_REQUIRE(ctx, h % 4 == 0 && gcnx_aligned16(db_relu), "gcnx_pooled_dense_softmax_cce: db_relu needs h %% 4 == 0 and a 16-byte aligned buffer");
   hipLaunchKernelGGL(dp_cnt_kernel, dim3(gcnx_cdiv((int64_t)b * h, 256)), dim3(256), 0, ctx->stream, dpooled, lddp, cnt, graph_ptr, b, h,
                      pool_mode == GCNX_POOL_AVG ? 1 : 0, (float*)ctx->ws);
@@ -107,8 +111,8 @@ int gcnx_pool_dense_softmax_cce(gcnx_ctx* ctx, const int32_t* graph_ptr, const f
     GCNX_LAUNCH_OK(ctx);
     return gcnx_colsum_partials(ctx, b, h, db_relu);
   }
-  if (!fused) {   // MAX pooling, many graphs (no split), operands too large for LDS: the separate calls as they are
-    int rc = gcnx_segment_pool(ctx, graph_ptr, x, ldx, pooled, b, h, pool_mode, argmax);
+  if (!fused) {   // MAX pooling, many graphs (no split), operands too large for LDS: the separate calls, pooled at stride ldp
+    int rc = gcnx_segment_pool_ld(ctx, graph_ptr, x, ldx, pooled, ldp, b, h, pool_mode, argmax);
     if (rc) return rc;
     rc = gcnx_dense_softmax_cce(ctx, pooled, ldp, w, bias, y, b, h, c, denom, probs, loss_acc, dw, db, dpooled, lddp, cce_mode);
     if (rc || !db_relu) return rc;

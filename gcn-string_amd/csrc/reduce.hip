@@ -156,7 +156,7 @@ __global__ __launch_bounds__(16 * RG) void pool_fwd_kernel(const int32_t* __rest
   const int g = glist ? glist[blockIdx.y] : (int)blockIdx.y;
   int lo = gp[g], hi = gp[g + 1];
   const int glo = lo, ghi = hi;
-  const int64_t prow = glist ? ldp : (int64_t)f;
+  const int64_t prow = (glist || ldp > 0) ? ldp : (int64_t)f;       // ldp without a list: gcnx_segment_pool_ld (unsplit launch)
   if (nsplit > 1) {
     const int per = (hi - lo + nsplit - 1) / nsplit;
     lo = min(hi, lo + (int)blockIdx.z * per);
@@ -257,18 +257,18 @@ __global__ __launch_bounds__(16 * RG) void pool_fwd_kernel(const int32_t* __rest
 
 // Second stage of the split pool: pooled[g][c] = sum_z part[z][g][c] (z ascending), / n_g for AVG.
 __global__ __launch_bounds__(256) void pool_combine_kernel(const float* __restrict__ part, const int32_t* __restrict__ gp,
-                                                           float* __restrict__ pooled, int32_t b, int32_t f, int nsplit,
-                                                           int mode) {
+                                                           float* __restrict__ pooled, int64_t ldp, int32_t b, int32_t f,
+                                                           int nsplit, int mode) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (int64_t)b * f) return;
   float acc = 0.f;
   for (int z = 0; z < nsplit; ++z) acc += part[(int64_t)z * b * f + i];
+  const int g = (int)(i / f);
   if (mode == GCNX_POOL_AVG) {
-    const int g = (int)(i / f);
     const int cnt = gp[g + 1] - gp[g];
     if (cnt > 0) acc /= (float)cnt;
   }
-  pooled[i] = acc;
+  pooled[(int64_t)g * ldp + (i - (int64_t)g * f)] = acc;      // the partials are packed (row stride f), pooled has its own
 }
 
 // Pool backward (+ optional fused ReLU mask of the layer that produced the pooled tensor).
@@ -584,13 +584,21 @@ int gcnx_act_bias_grad(gcnx_ctx* ctx, const float* dy, int64_t lddy, const float
 
 int gcnx_segment_pool(gcnx_ctx* ctx, const int32_t* graph_ptr, const float* x, int64_t ldx, float* pooled, int32_t b,
                       int32_t f, int mode, int32_t* argmax) {
+  return gcnx_segment_pool_ld(ctx, graph_ptr, x, ldx, pooled, f, b, f, mode, argmax);
+}
+
+}  // extern "C"
+
+// gcnx_segment_pool with a row stride for pooled (argmax stays packed): the same launches, the same bits.
+int gcnx_segment_pool_ld(gcnx_ctx* ctx, const int32_t* graph_ptr, const float* x, int64_t ldx, float* pooled, int64_t ldp,
+                         int32_t b, int32_t f, int mode, int32_t* argmax) {
   GCNX_CHECK_CTX(ctx);
   GCNX_RANGE(ctx, "global pool");
   GCNX_REQUIRE(ctx, b >= 0 && f >= 0, "gcnx_segment_pool: negative size");
   GCNX_REQUIRE(ctx, mode >= GCNX_POOL_SUM && mode <= GCNX_POOL_MAX, "gcnx_segment_pool: unknown mode %d", mode);
   if (b == 0 || f == 0) return GCNX_OK;
   GCNX_REQUIRE(ctx, graph_ptr && x && pooled, "gcnx_segment_pool: NULL pointer");
-  GCNX_REQUIRE(ctx, ldx >= f, "gcnx_segment_pool: leading dimension too small");
+  GCNX_REQUIRE(ctx, ldx >= f && ldp >= f, "gcnx_segment_pool: leading dimension too small");
   GCNX_REQUIRE(ctx, mode != GCNX_POOL_MAX || argmax, "gcnx_segment_pool: MAX needs an argmax buffer");
   const int vec = gcnx_aligned16(x) && ldx % 4 == 0;
   const int nsplit = gcnx_pool_split(ctx, b, f, mode, 4);
@@ -600,16 +608,18 @@ int gcnx_segment_pool(gcnx_ctx* ctx, const int32_t* graph_ptr, const float* x, i
     rc = gcnx_pool_partials(ctx, graph_ptr, x, ldx, b, f, mode, nsplit, (float*)ctx->ws, nullptr, 0);
     if (rc) return rc;
     hipLaunchKernelGGL(pool_combine_kernel, dim3(gcnx_cdiv((int64_t)b * f, 256)), dim3(256), 0, ctx->stream,
-                       (const float*)ctx->ws, graph_ptr, pooled, b, f, nsplit, mode);
+                       (const float*)ctx->ws, graph_ptr, pooled, ldp, b, f, nsplit, mode);
     GCNX_LAUNCH_OK(ctx);
     return GCNX_OK;
   }
   dim3 grid(gcnx_cdiv(f, 64), b);
   hipLaunchKernelGGL(pool_fwd_kernel<16>, grid, dim3(256), 0, ctx->stream, graph_ptr, x, ldx, pooled, f, mode, argmax, vec, 1,
-                     (float*)nullptr);
+                     (float*)nullptr, (const int32_t*)nullptr, ldp);
   GCNX_LAUNCH_OK(ctx);
   return GCNX_OK;
 }
+
+extern "C" {
 
 int gcnx_segment_pool_bwd(gcnx_ctx* ctx, const int32_t* graph_ptr, const float* dpooled, float* dx, int64_t lddx,
                           int32_t n, int32_t b, int32_t f, int mode, const int32_t* argmax, const float* y,

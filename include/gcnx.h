@@ -331,6 +331,7 @@ GCNX_API int gcnx_dense_softmax_cce(gcnx_ctx* ctx, const float* pooled, int64_t 
  * pair runs as 2 launches instead of 3 (with half as many row slices: the head's workgroup reads them all).
  * Otherwise exactly gcnx_segment_pool + gcnx_dense_softmax_cce.  Results equal those of the two calls up to the
  * fp32 summation order of the pool; deterministic.  argmax: as gcnx_segment_pool (MAX only).
+ * ldp >= h is the row stride of pooled on every route (the separate calls included); columns h .. ldp-1 are not written.
  * db_relu (may be NULL; needs dw and SUM / AVG): float[h] = what gcnx_pool_bwd_colsum(dpooled, y = x) returns, the
  * bias gradient of the layer that produced x through a ReLU (GCNConv, gcn.py:317) -- on the combined path the pool
  * counts the positive entries per (graph, column) in the pass it makes anyway and the head finishes
